@@ -22,10 +22,16 @@ Prints ONE JSON line on rank 0.  `value` counts channel-samples/s (2 per stereo 
 `roofline` prices the dominant kernel (k_seg, mtr_seg.hip: K-weighting as the reference's recurrence with lane = time
 segment + the 4x interpolator on the matrix pipe at f32 grade; the layout every call of this shape takes by default) at
 8 algorithmic bytes per stereo frame (one read of the input) against the 8 TB/s HBM peak, with the
-kernel's duration measured by HIP events on the launching stream inside the timed steps.  `extra.configs` carries every BASELINE config at its stated size, `extra.lv2_run_latency`
-the per-block cost of the LV2 plugins.  `cpu_baseline` times the reference's
-own DSP objects (oracle/_ref, kind "reference") — or the repo's restatement (kind "port") where
-that build is absent — on a bounded sample of the same buffers on the host cores.
+kernel's duration measured by HIP events on the launching stream inside the timed steps.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  What takes runs of its own comes only with --full:
+`cpu_baseline` times the reference's own DSP objects (oracle/_ref, kind "reference") — or the repo's restatement (kind "port") where
+that build is absent — on a bounded sample of the same buffers on the host cores, and, for the headline workload, `extra.configs`
+carries every BASELINE config at its stated size, `extra.lv2_run_latency` the per-block cost of the LV2 plugins.
+
+--dump-outputs DIR writes what a caller of the timed path receives after the last timed step (rank 0's streams and the job's
+reduced histograms / peaks) as DIR/<name>.npy, float32 or float64; per-stream arrays wider than 64 values (histograms) are kept
+for a fixed, seeded sample of streams (`sample_streams.npy`).  The inputs are a seeded synthesis, the same from run to run.
 """
 import argparse
 import json
@@ -222,6 +228,64 @@ def committed_traffic(meters, S, T, layout):
     return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_STREAMS = 512      # streams kept of the per-stream arrays wider than DUMP_WIDE values
+DUMP_WIDE = 64
+
+
+def dump_outputs(out_dir, M, eng, meters, agg_hist=None, agg_max=None):
+    """--dump-outputs: every array the engine hands a caller after the last timed step, as <out_dir>/<name>.npy.  Float arrays
+    keep their width (float32 / float64), integer counts become float64 (exact).  Per-stream arrays of more than DUMP_WIDE values
+    per stream are kept for a fixed sample of streams (seed 0, sorted: sample_streams.npy); the rest for every stream."""
+    import numpy as np
+    S = eng.n_streams
+    arrays = {}
+    if meters & (M.METER_EBU | M.METER_TRUEPEAK | M.METER_TPBALLIST):
+        r = eng.results()
+        if meters & M.METER_EBU:
+            arrays["out9"] = eng.out9()
+            arrays["hist_counts"] = np.array([[x.hist_M_count, x.hist_S_count] for x in r])
+            hm, hs = eng.histograms()
+            arrays["hist_M"], arrays["hist_S"] = hm, hs
+        if meters & M.METER_TRUEPEAK:
+            arrays["truepeak"] = np.array([list(x.truepeak) for x in r], np.float32)
+            arrays["truepeak_call"] = np.array([list(x.truepeak_call) for x in r], np.float32)
+        if meters & M.METER_TPBALLIST:
+            arrays["tpb_level"] = np.array([list(x.tpb_level) for x in r], np.float32)
+            arrays["tpb_peak"] = np.array([list(x.tpb_peak) for x in r], np.float32)
+    if meters & M.METER_SPECTR30:
+        arrays.update(("spectrum_" + k, v) for k, v in eng.spectrum().items())
+    if meters & M.METER_BITSTATS:
+        arrays.update(("bitstats_" + k, v) for k, v in eng.bitstats().items())
+    if meters & M.METER_SIGDIST:
+        arrays.update(("sigdist_" + k, v) for k, v in eng.sigdist().items())
+    if meters & M.METER_DR14:
+        d = eng.dr14()
+        for f, _ in M.engine.Dr14Result._fields_:
+            arrays["dr14_" + f] = np.array([np.array(getattr(x, f), np.float32) for x in d])
+    if meters & M.METER_KMETER:
+        arrays["kmeter_rms"], arrays["kmeter_peak"] = eng.kmeter_read()
+    if agg_hist is not None:
+        arrays["job_hist"] = agg_hist.cpu().numpy().reshape(2, -1)
+        arrays["job_max"] = agg_max.cpu().numpy()
+    pick = np.sort(np.random.default_rng(0).choice(S, size=min(S, DUMP_SAMPLE_STREAMS), replace=False))
+    sampled = False
+    for k, v in list(arrays.items()):
+        v = np.asarray(v)
+        if v.ndim >= 1 and v.shape[0] == S and k not in ("job_hist", "job_max") and v.size // max(S, 1) > DUMP_WIDE:
+            v, sampled = v[pick], True
+        arrays[k] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    if sampled:
+        arrays["sample_streams"] = pick.astype(np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {"dir": out_dir, "arrays": sorted(arrays), "bytes": total}
+
+
 def self_launch(n):
     """`python bench.py --gpus N` with no launcher around it: become `torch.distributed.run --nproc-per-node N bench.py ...`
     (the command the driver itself uses), rendezvous on 127.0.0.1 and a free port.  Rank 0 prints the one JSON line."""
@@ -328,7 +392,13 @@ def main():
     ap.add_argument("--prune", type=int, default=0, help="1 = exact true-peak pruning (identical result, data-dependent speed)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--tail", type=int, default=0, help="0 auto (deferred for batches), 1 serial (everything on the caller's stream), 2 always deferred")
+    ap.add_argument("--full", action="store_true", help="also what the headline does not need: cpu_baseline and, for the headline workload, "
+                                                        "extra (the other layouts, BASELINE configs and meter sets, host path, LV2 latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the engine holds after the last one as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                                 # does not return
@@ -503,6 +573,10 @@ def run(args, rank, local, world):
         rank_devices = [[int(v) for v in r] for r in rows]
     rank_devices = [{"rank": r[0], "hip_device": r[1], "rccl_device": (r[2] if r[2] >= 0 else None)} for r in rank_devices]
     deferred_calls = eng.deferred_calls()
+    if args.dump_outputs and rank == 0:
+        reduced = not mono and bool(meters & (M.METER_EBU | M.METER_TRUEPEAK))    # (what step() all-reduced into agg_*)
+        d = dump_outputs(args.dump_outputs, M, eng, meters, *((agg_hist, agg_max) if reduced else ()))
+        print("bench.py: %d bytes of outputs in %s: %s" % (d["bytes"], d["dir"], " ".join(d["arrays"])), file=sys.stderr)
     if rank == 0:
         frames_job = float(world) * S * T * args.steps
         ms_step = 1e3 * dt / args.steps
@@ -609,10 +683,10 @@ def run(args, rank, local, world):
         out["check"] = {"stream0_integrated_lufs": res.integrated, "stream0_dbtp":
                         float(20 * np.log10(max(res.truepeak[0], res.truepeak[1], 1e-30))),
                         "job_max_truepeak": float(agg_max[:2].max().item())}
-        if world == 1 and not args.no_cpu_baseline and (meters & (M.METER_EBU | M.METER_TRUEPEAK)):
+        if args.full and world == 1 and not args.no_cpu_baseline and (meters & (M.METER_EBU | M.METER_TRUEPEAK)):
             n = min(S, 256)
             out["cpu_baseline"] = cpu_baseline(buf[:n].cpu().numpy(), fs)
-        headline = world == 1 and not args.no_cpu_baseline and not args.no_extra and args.meters == "ebu+tp" and not args.prune \
+        headline = args.full and world == 1 and not args.no_cpu_baseline and not args.no_extra and args.meters == "ebu+tp" and not args.prune \
             and args.layout == 0 and (S, T) == (8192, 480000) and fs == 48000.0
         if headline:
             extra = {}

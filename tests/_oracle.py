@@ -430,3 +430,107 @@ class Reference(_Batch):
 
 def have_reference():
     return os.path.exists(REF_SO)
+
+
+# ---- the reference's answers to the ref tests' own calls, recorded (tests/golden/make_golden_ref_calls.py) ----
+# Where oracle/_ref cannot be built (no reference sources on the machine) the ref tests compare the oracle against these, bit
+# for bit; where it can, every live answer is also held against its recording, so the file cannot drift from the reference.
+REF_CALLS = os.path.join(ROOT, "tests", "golden", "golden_ref_calls_v1.npz")
+REPLAYED = ("kw_coef", "tp_table", "tp_consts", "tp_resampler_state", "band_coef", "vu", "tp_process_seq", "tp_resample",
+            "ebu", "tp", "spectr")
+
+
+def call_key(name, args, kwargs):
+    """A call's identity: the method, its scalar arguments and the sha1 of its array arguments."""
+    import hashlib
+
+    def one(a):
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a)
+            return "%s%s:%s" % (a.dtype.str, a.shape, hashlib.sha1(a.tobytes()).hexdigest()[:16])
+        if isinstance(a, (int, float, np.integer, np.floating)) and not isinstance(a, bool):
+            return repr(float(a))
+        return repr(a)
+    return "|".join([name] + [one(a) for a in args] + ["%s=%s" % (k, one(kwargs[k])) for k in sorted(kwargs)])
+
+
+def _flatten(res):
+    """(kind, {field: array}) of a result: an array, a tuple of numbers or a dict of arrays (None fields left out)."""
+    if isinstance(res, dict):
+        return "dict", {k: np.asarray(v) for k, v in res.items() if v is not None}, sorted(res)
+    if isinstance(res, tuple):
+        return "tuple", {"": np.asarray(res)}, None
+    return "array", {"": np.asarray(res)}, None
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+class RecordedReference:
+    """The reference's answers, replayed: the same methods as Reference (and `run`) for the calls recorded in REF_CALLS."""
+
+    def __init__(self, path=REF_CALLS):
+        import json
+        z = np.load(path)
+        self._z = {k: z[k] for k in z.files}
+        self._index = json.loads(str(self._z.pop("__index__")))
+
+    def replay(self, key):
+        e = self._index.get(key)
+        if e is None:
+            raise KeyError("the reference's answer to %s is not recorded in %s: regenerate it with tests/golden/make_golden_ref_calls.py "
+                           "where the reference sources are" % (key, os.path.relpath(REF_CALLS, ROOT)))
+        arrs = {f: self._z[e["entry"] + "." + f] for f in e["fields"]}
+        if e["kind"] == "dict":
+            return {k: arrs.get(k) for k in e["keys"]}
+        if e["kind"] == "tuple":
+            return tuple(v.item() for v in arrs[""])
+        return arrs[""]
+
+    def run(self, name, fn, *args):
+        return self.replay(call_key(name, args, {}))
+
+    def __getattr__(self, name):
+        if name in REPLAYED:
+            return lambda *args, **kw: self.replay(call_key(name, args, kw))
+        raise AttributeError(name)
+
+
+class CheckedReference:
+    """A live Reference whose every answer is held against its recording (check=True) and/or written into a new one
+    (record=True, save())."""
+
+    def __init__(self, live, check=True, record=False):
+        self.live, self.recorded = live, (RecordedReference() if check else None)
+        self.calls = {} if record else None
+
+    def _answer(self, key, res):
+        if self.recorded is not None:
+            want = self.recorded.replay(key)
+            kind, got, _ = _flatten(res)
+            _, rec, _ = _flatten(want)
+            assert sorted(got) == sorted(rec) and all(_same_bits(got[f], rec[f]) for f in got), \
+                "the reference's answer to %s differs from its recording: regenerate tests/golden/ with make_golden_ref_calls.py" % key
+        if self.calls is not None:
+            self.calls[key] = res
+        return res
+
+    def run(self, name, fn, *args):
+        return self._answer(call_key(name, args, {}), fn(self.live, *args))
+
+    def __getattr__(self, name):
+        if name in REPLAYED:
+            return lambda *args, **kw: self._answer(call_key(name, args, kw), getattr(self.live, name)(*args, **kw))
+        return getattr(self.live, name)
+
+    def save(self, path=REF_CALLS):
+        import json
+        index, arrays = {}, {}
+        for n, (key, res) in enumerate(sorted(self.calls.items())):
+            kind, fields, keys = _flatten(res)
+            index[key] = {"entry": "c%d" % n, "kind": kind, "fields": sorted(fields), "keys": keys}
+            arrays.update(("c%d.%s" % (n, f), v) for f, v in fields.items())
+        np.savez_compressed(path, __index__=np.array(json.dumps(index, sort_keys=True)), **arrays)
+        return len(index)

@@ -1,6 +1,7 @@
 """Pin the CPU restatement (oracle/mtr_oracle.c) bit-for-bit against the reference's own
-objects (oracle/_ref, compiled from /root/reference).  Runs only where that tree exists;
-on the GPU box these are skipped and tests/test_oracle_golden.py carries the pin."""
+objects (oracle/_ref, compiled from the reference's sources where they are present); elsewhere
+against their recorded answers to these very calls (tests/golden/golden_ref_calls_v1.npz).
+tests/test_oracle_golden.py carries the pin on further signals."""
 import numpy as np
 import pytest
 

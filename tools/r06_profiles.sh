@@ -20,7 +20,7 @@ MTR_BENCH_SHARED_GPU=1 MTR_BENCH_TRY_RCCL=1 timeout 600 python bench.py --gpus 2
 MTR_BENCH_SHARED_GPU=1 MTR_BENCH_TRY_RCCL=1 MTR_BENCH_COMM_TIMEOUT_S=6 MTR_BENCH_FAULT=sleep_in_init:1:25 timeout 600 python bench.py --gpus 2 --streams 64 --seconds 3 --steps 2 --warmup 1 --no-extra --no-cpu-baseline > $O/r06_sleeping_rank.json 2> $O/r06_sleeping_rank.err
 # 5. the line (with the traffic figure just taken: bench.py reads profiles/r06_traffic.json)
 cp $O/r06_traffic.json profiles/r06_traffic.json
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/r06_bench_line.json 2> $O/r06_bench.err; cut -c1-300 $O/r06_bench_line.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_line.json 2> $O/r06_bench.err; cut -c1-300 $O/r06_bench_line.json
 find gpurun_out/prof_r06* gpurun_out/trace_r06* -name "*.csv" -size +2M -delete
 python - <<PY
 import json; d = json.load(open("$O/r06_bench_line.json")); r = d["roofline"]
