@@ -86,7 +86,9 @@ typedef struct {
 	                          * Layouts 1, 2 and 5 of earlier versions no longer exist: MTR_ERR_ARG. */
 	uint32_t tune_fir;       /* layout 3 only: 0 = mirror-symmetric form (120 ops / frame), 1 = dense 3 x 48 taps */
 	uint32_t tune_prune;     /* 1 = exact true-peak pruning (branch and bound on L1 * max|x| per tile): identical result,
-	                          * data-dependent speed; off by default so the default timing is the dense one.
+	                          * data-dependent speed; off by default.  (Layout 7's k_seg screens its products with the first one
+	                          * regardless — the same bits, always on: MTR_SEG_SCREEN=0, read by mtr_engine_create, is the test knob
+	                          * that forces its dense form.)
 	                          * 2 (layout 6) = the same, and inside a tile every 256-frame block is screened with the first of
 	                          * the three f16 products and completed only if it can still hold the maximum: also identical.
 	                          * (Pruning is a layout 6 feature: with tune_prune set, layout 7 is not used.) */
@@ -318,8 +320,9 @@ int  mtr_engine_timing_query (mtr_engine* e, float* ms_fused, float* ms_gate, fl
 int  mtr_engine_timing_calls (mtr_engine* e, float* out, uint32_t cap, uint32_t* calls);
 /* With tune_prune: interpolator tile passes considered / skipped since the engine was created. */
 int  mtr_engine_prune_stats (mtr_engine* e, uint64_t* considered, uint64_t* skipped);
-/* With tune_prune = 2 (layout 6): 256-frame channel-blocks screened with the first of the three products / completed
- * with the other two, since the engine was created. */
+/* Products screened with the first of the three f16 products / completed with the other two, since the engine was created:
+ * with tune_prune = 2 (layout 6) 256-frame channel-blocks of k_kwtp16; in layout 7 also k_seg's 16-column chunks (screened
+ * always, unless MTR_SEG_SCREEN=0).  Layout 6 engines without tune_prune = 2 count nothing. */
 int  mtr_engine_refine_stats (mtr_engine* e, uint64_t* screened, uint64_t* completed);
 /* The kernel layout the engine resolved to (tune_layout = 0 picks one from the meters mask): 3, 4, 6 or 7. */
 int  mtr_engine_layout (const mtr_engine* e);

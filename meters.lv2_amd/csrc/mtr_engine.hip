@@ -111,6 +111,7 @@ struct mtr_engine {
 	// moves from the gate into k_history on the caller's stream (tp_call is already being raised by call i + 1).  Results are
 	// bit for bit those of the serial order: same kernels, same inputs, the fragment inserts in fragment order (gates follow
 	// one another on the side stream; ebumeter/ebu_r128_proc.cc:217-244).
+	bool             seg_screen = true;      // k_seg's products screened by the first of the three (mtr_seg.hip: SCREEN); MTR_SEG_SCREEN=0 forces the dense form
 	int              tail_mode = 0;          // 0 auto (a k_seg batch of >= TAIL_AUTO_STREAMS streams and >= TAIL_AUTO_FRAMES stream-frames in an EBU / TRUEPEAK engine), 1 never, 2 always
 	hipStream_t      tail_stream = nullptr;
 	hipEvent_t       ev_fused = nullptr;     // caller's stream -> side: the call's fused kernels are done
@@ -414,6 +415,7 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	}
 	// (test knobs: the whole -m gpu suite and the fuzzers run green with MTR_TAIL_MODE=2 — every call of every test with its tail on the side stream)
 	if (const char* v = getenv ("MTR_TAIL_MODE")) { const int m = atoi (v); if (m >= 0 && m <= 2) e->tail_mode = m; }
+	if (const char* v = getenv ("MTR_SEG_SCREEN")) e->seg_screen = atoi (v) != 0;   // (test knob: 0 = k_seg's dense form, the screened one's bit-for-bit yardstick)
 	if (const char* v = getenv ("MTR_TAIL_DELAY_US")) e->tail_delay_us = (uint32_t) atoi (v);
 	if (const char* v = getenv ("MTR_TAIL_GATE_GRID")) e->tail_gate_grid = (uint32_t) atoi (v);   // (tools/r06_tail_probe.py: the experiment behind the default)
 	e->fragm = (uint32_t) ((int) cfg->sample_rate / 20);     // ebu_r128_proc.cc:170
@@ -989,6 +991,7 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 			sa.n_streams = S; sa.n_segs = sp.n_segs; sa.n_tiles = pl.n_tiles; sa.tile_frames = e->fragm;
 			sa.seg_base = sp.base; sa.seg_rem = sp.rem; sa.n_main = sp.n_main; sa.warm_steps = sp.warm_steps;
 			sa.p0_end = (int64_t) n_frames - 24 - (int64_t) sp.head;
+			sa.screen = e->seg_screen ? 1u : 0u; sa.seg_stats = e->prune_cnt.p + 2;
 			sa.a0 = fa.a0; sa.a1 = fa.a1; sa.a2 = fa.a2; sa.b1 = fa.b1; sa.b2 = fa.b2; sa.c3 = fa.c3; sa.c4 = fa.c4;
 			sa.gain_l = fa.gain_l; sa.gain_r = fa.gain_r;
 			const uint64_t units = (uint64_t) S * sp.n_segs;

@@ -59,7 +59,8 @@ constexpr int COLB  = 128;                   // bytes per column and array: 4 ri
 constexpr int ARRB  = 64 * COLB;             // one array: HL | HR | LL | LR
 constexpr int BLKB  = 16 * COLB;             // 16 columns = one MFMA block
 constexpr int XCHG  = 4 * ARRB;              // exchange area: float [2 ch][4 blocks][4 kg][16 c]
-constexpr int LDS_BYTES = XCHG + 2048;
+constexpr int XEPS  = XCHG + 2048;           // ... and the screen's bounds: float [16 c][4 blocks][2 ch]
+constexpr int LDS_BYTES = XEPS + 512;
 
 typedef unsigned char lds_u8;          // (generic pointers into the dynamic LDS block: the compiler infers the address space)
 
@@ -82,6 +83,23 @@ struct Scale {
 		cap = (uint32_t) (269 - se) << 23;
 	}
 };
+
+// The screen (SCREEN below): a chunk's first product F = sum Ghi Xhi, and the bound on what the other two can add to any of
+// its outputs, |Y - F| <= eps = SCREEN_K_REL * M + SCREEN_K_ABS, in the accumulators' unit (x scale * 2^15).  M = the lane's running
+// maximum of |x| since its segment's first history frame, in the column's current scale: it bounds every sample of the column's
+// 64-sample window.  With h = x * scale, |h| <= M, for every word of the ring (fresh, or rescaled in place by 2^-12 and below):
+//     |Xhi| <= (1 + 2^-11) M + 2^-24,     |Xlo| <= 2^-11 (1 + 2^-11) M + 2^-24 (1 + 2^-12)
+// (round to nearest f16 with its subnormals: half an ulp, relative 2^-11 or absolute 2^-25, per rounding — the split's two and
+// the rescale's one; the lo word is x - Xhi, exact in f32, rounded once by v_fma_mix).  The taps' halves (g * 2^15) have L1
+// norms per row LH = sum |Ghi| <= 84157 and LL = sum |Glo| <= 11.41 (tests/test_seg_screen_bound.py recomputes both from
+// mtr_setup's table), so the exact rest sum Ghi Xlo + Glo Xhi is at most
+//     (LH 2^-11 + LL) (1 + 2^-11) M + (LH + LL) 2^-24 (1 + 2^-12)  =  52.53 M + 0.00503.
+// The four MFMAs that add it round in f32: each by at most 2^-17 (|C| + sum |products|) — 33 additions that truncate, twice
+// over — and |C| + sum |products| <= (LH + LL) ((1 + 2^-11) M + 2^-24) + 52.6 M, so 4 x 2^-17 x 84210 M = 2.57 M more:
+// 55.10 M + 0.0051 in all, rounded up to 56 M + 2^-7 (the 1.6 % also covers the f32 rounding of eps itself).  Products of f16
+// are exact in f32 and no partial sum of them is an f32 subnormal (the smallest is 2^-48), so nothing else rounds.
+constexpr float SCREEN_K_REL = 56.0f;
+constexpr float SCREEN_K_ABS = 0.0078125f;
 
 struct KCoef { v2f a0, a1, a2, b1, b2, c3, c4, eps; };
 struct KState { v2f z1, z2, z3, z4, sj; };
@@ -157,7 +175,13 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 // ALIGNED: the tile (a 50 ms fragment) is a whole number of steps — 48, 96, 192, 32 kHz; otherwise (44.1, 88.2 kHz: 2205, 4410 frames)
 // the step in which a tile ends is followed by a second run of its recurrence, frame by frame from the state the step started with,
 // with the reference's end-of-fragment actions at the exact frame (every other step is the aligned kernel's code).
-template <bool EBU, bool ALIGNED>
+//
+// SCREEN: each chunk runs the first of its three products (Ghi Xhi: MFMAs 0..5) and no more, unless one of its outputs may
+// reach the running peak: a lane whose twelve first-product values all stay eps (above) under the peak of its completed
+// values (pm) cannot raise it, whatever the other two products add.  The check runs in the next chunk; if any lane of the wave
+// fails it (a NaN or Inf fails it), the chunk gets MFMAs 6..17 on the same accumulators — bit for bit the dense values — and
+// its maxima go into pm as in the dense form.  The peak is the dense form's on every input; only the time depends on the data.
+template <bool EBU, bool ALIGNED, bool SCREEN>
 __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 {
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem_[];
@@ -262,6 +286,10 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #pragma unroll
 	for (int b = 0; b < 4; ++b) { pm[b][0][0] = 0.f; pm[b][0][1] = 0.f; pm[b][1][0] = 0.f; pm[b][1][1] = 0.f; }
 
+	float rml = 0.f, rmr = 0.f;                                       // SCREEN: max |x| of the segment so far (history frames included), per channel
+	uint32_t n_scr = 0, n_fin = 0;                                    // ... chunks screened / completed (wave-uniform)
+	bool y1_pend = false;                                             // ... y1 holds the first product of a chunk 7 whose check is still to come
+
 	auto split_store = [&] (const v2f (&x)[R], int slot) __attribute__ ((always_inline)) {
 		const v2f sc = v2f{scl.sc, scr.sc};
 		uint32_t hl[R / 2], hr[R / 2], ll[R / 2], lr[R / 2];
@@ -300,6 +328,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #pragma unroll
 			for (int n = 0; n < R; n += 2) { ml = max3abs (ml, px[k][n].x, px[k][n + 1].x); mr = max3abs (mr, px[k][n].y, px[k][n + 1].y); }
 		scl.set (ml); scr.set (mr);
+		rml = ml; rmr = mr;
 		split_store (px[0], 1); split_store (px[1], 2); split_store (px[2], 3);
 		if (F0 == 0) {
 			// phase 0 of the launch's first outputs is frames -24 .. -1: the history of a launch that starts the call, else the
@@ -382,6 +411,13 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
 		B.l1 = *reinterpret_cast<const uint4*> (l + RA[(U + 2) & 3]);
 	};
+	// SCREEN: the other two products of a chunk whose first one is in y (operands B): MFMAs 6..17 of m16::block's order
+	auto complete = [&] (const m16::BFrag& B, m16::f4 (&y)[3]) __attribute__ ((always_inline)) {
+		m16::block_mfma<6> (A, B, y);  m16::block_mfma<7> (A, B, y);  m16::block_mfma<8> (A, B, y);
+		m16::block_mfma<9> (A, B, y);  m16::block_mfma<10> (A, B, y); m16::block_mfma<11> (A, B, y);
+		m16::block_mfma<12> (A, B, y); m16::block_mfma<13> (A, B, y); m16::block_mfma<14> (A, B, y);
+		m16::block_mfma<15> (A, B, y); m16::block_mfma<16> (A, B, y); m16::block_mfma<17> (A, B, y);
+	};
 	// |max| of the accumulators of (block, channel) bc into pm
 	auto fold = [&] (const m16::f4 (&y)[3], int bc) __attribute__ ((always_inline)) {
 		float ma = pm[bc >> 1][bc & 1][0], mb = pm[bc >> 1][bc & 1][1];
@@ -408,6 +444,12 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	// the products of the call's last step (nothing left to run under them); every chunk folds its predecessor's accumulators
 	// (the first fold is still the step before's)
 	auto products = [&]<int U> () __attribute__ ((always_inline)) {
+		if constexpr (SCREEN) {
+			// (dense: the chunk 7 the last step left for its check is completed here, with the operands it still has in B1)
+			if (y1_pend) { complete (B1, y1); ++n_scr; ++n_fin; }
+			y1_pend = false;
+			n_scr += 8; n_fin += 8;
+		}
 		fetch.template operator()<U> (B0, 0);
 #pragma unroll
 		for (int bc = 0; bc < 8; bc += 2) {
@@ -452,6 +494,10 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		if (__builtin_expect (__ballot (__float_as_uint (ml) >= scl.cap || __float_as_uint (mr) >= scr.cap) != 0, 0)) {
 			// (the last chunk's accumulators of the step before are still waiting for their fold, which chunk 0 does: they
 			// belong to the old scale, so they are folded here, in front of the flush, and cleared)
+			if constexpr (SCREEN) {
+				if (y1_pend) { complete (B1, y1); ++n_scr; ++n_fin; }          // (its operands are still in B1)
+				y1_pend = false;
+			}
 			fold (y1, 7);
 #pragma unroll
 			for (int p = 0; p < 3; ++p) y1[p] = m16::f4{0.f, 0.f, 0.f, 0.f};
@@ -464,6 +510,25 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		lp += (j + 3 < (ALIGNED ? n_steps : n_loads)) ? R / 2 : 0;
 #endif
 		load.template operator()<(U + 3) & 3> ();
+		// SCREEN: eps of the products of step j - 1 for every accumulator lane.  The owner of column 16 b + c (lane 16 b + c)
+		// computes it in the column's current scale; lane (c, kg) needs the four columns c of blocks 0..3: through LDS.
+		float eps[4][2];
+		if constexpr (SCREEN) {
+			rml = fmaxf (rml, ml); rmr = fmaxf (rmr, mr);                // (step j's own samples too: a bound on more is still a bound)
+			if (PROD) {
+				float* const E = reinterpret_cast<float*> (smem_ + XEPS);
+				*reinterpret_cast<float2*> (E + (cc * 4 + kg) * 2) =
+					float2{fmaf (SCREEN_K_REL, rml * scl.sc, SCREEN_K_ABS), fmaf (SCREEN_K_REL, rmr * scr.sc, SCREEN_K_ABS)};
+				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
+				__builtin_amdgcn_wave_barrier ();
+				__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "workgroup");
+				const float4 e0 = *reinterpret_cast<const float4*> (E + cc * 8), e1 = *reinterpret_cast<const float4*> (E + cc * 8 + 4);
+				eps[0][0] = e0.x; eps[0][1] = e0.y; eps[1][0] = e0.z; eps[1][1] = e0.w;
+				eps[2][0] = e1.x; eps[2][1] = e1.y; eps[3][0] = e1.z; eps[3][1] = e1.w;
+				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
+				__builtin_amdgcn_wave_barrier ();
+			}
+		}
 		SPROF_NOW (c1_); SPROF_ADD (0, c1_ - c0_);
 
 		// Eight chunks, one per (block, channel) of the products of step j - 1.  THE SOURCE ORDER IS THE SCHEDULE (this TU
@@ -533,14 +598,72 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #undef MTR_ST
 #undef MTR_M
 		};
-		chunk.template operator()<0> (B0, B1, y0, y1);
+		// The screened chunk: MFMAs 0..5 only, so most of the split, the maxima and the recurrence issue bare (the issue model's
+		// floor: the elimination run without products).  First the check of the previous chunk (its operands are still in Bn: the
+		// fetch of the next chunk's waits for the verdict; its accumulators are ready — a chunk's tail lies behind its last MFMA),
+		// then the fetch, a whole chunk ahead of its use; behind the six MFMAs the scale, the hi words and the lo words' first
+		// halves; then the lo words' second halves, the next step's maxima, six operations of the recurrence and the ring stores
+		// (chunks 6, 7: behind chunk 6's fetch, the last one that reads the slot they overwrite; chunk 7's fetch of the next step
+		// reads them).
+		auto chunk_s = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
+			constexpr int PB = (BC + 7) & 7;
+			const v2f xa = x[2 * BC], xb = x[2 * BC + 1];
+			if (PROD && (BC != 0 || y1_pend)) {
+				float ca = 0.f, cb = 0.f;
+#pragma unroll
+				for (int p = 0; p < 3; ++p) { ca = max3abs (ca, yp[p][0], yp[p][1]); cb = max3abs (cb, yp[p][2], yp[p][3]); }
+				const float pk = fmaxf (pm[PB >> 1][PB & 1][0], pm[PB >> 1][PB & 1][1]);
+				const bool below = fmaxf (ca, cb) + eps[PB >> 1][PB & 1] < pk;       // (false for a NaN anywhere in it)
+				++n_scr;
+				if (__builtin_expect (__ballot (!below) != 0, 0)) {
+					complete (Bn, yp);
+					fold (yp, PB);
+					++n_fin;
+				}
+			}
+			if (PROD && BC < 7) fetch.template operator()<U> (Bn, BC + 1);
+#define MTR_M(I) if (PROD) m16::block_mfma<I> (A, Bc, yc)
+			MTR_M (0);  v2f um = xa * sc2;
+			MTR_M (1);  v2f vm = xb * sc2;
+			MTR_M (2);  hl[BC] = m16::hi_pair (um.x, vm.x);
+			MTR_M (3);  hr[BC] = m16::hi_pair (um.y, vm.y);
+			MTR_M (4);  lo_first (ll[BC], hl[BC], um.x);
+			MTR_M (5);  lo_first (lr[BC], hr[BC], um.y);
+#undef MTR_M
+			// (computed HERE, behind the six MFMAs: otherwise the compiler sinks them towards their uses)
+			asm volatile ("" : "+v"(um), "+v"(vm), "+v"(hl[BC]), "+v"(hr[BC]), "+v"(ll[BC]), "+v"(lr[BC]));
+			lo_second (ll[BC], hl[BC], vm.x);
+			lo_second (lr[BC], hr[BC], vm.y);
+			nl = max3abs (nl, xn[2 * BC].x, xn[2 * BC + 1].x); nr = max3abs (nr, xn[2 * BC].y, xn[2 * BC + 1].y);
+#define MTR_ST(ARR, W_) \
+			if constexpr (BC == 6) *reinterpret_cast<uint4*> (smem + WS[U] + (ARR) * ARRB) = uint4{W_[0], W_[1], W_[2], W_[3]}; \
+			if constexpr (BC == 7) *reinterpret_cast<uint4*> (smem + (WS[U] ^ 16) + (ARR) * ARRB) = uint4{W_[4], W_[5], W_[6], W_[7]}
+			kseq.template operator()<KGAP * BC + 0> ();
+			MTR_ST (0, hl);
+			kseq.template operator()<KGAP * BC + 1> ();
+			MTR_ST (1, hr);
+			kseq.template operator()<KGAP * BC + 2> ();
+			MTR_ST (2, ll);
+			kseq.template operator()<KGAP * BC + 3> ();
+			MTR_ST (3, lr);
+			kseq.template operator()<KGAP * BC + 4> ();
+			if constexpr (BC == 7) fetch.template operator()<(U + 1) & 3> (Bn, 0);      // (Bn of the last chunk = B0 of the next step)
+			kseq.template operator()<KGAP * BC + 5> ();
+#undef MTR_ST
+			if constexpr (BC == 7) if (PROD) y1_pend = true;
+		};
+		auto any_chunk = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
+			if constexpr (SCREEN) chunk_s.template operator()<BC> (Bc, Bn, yc, yp);
+			else chunk.template operator()<BC> (Bc, Bn, yc, yp);
+		};
+		any_chunk.template operator()<0> (B0, B1, y0, y1);
 		SPROF_NOW (c2_); SPROF_ADD (1, c2_ - c1_);
-		chunk.template operator()<1> (B1, B0, y1, y0);
-		chunk.template operator()<2> (B0, B1, y0, y1); chunk.template operator()<3> (B1, B0, y1, y0);
-		chunk.template operator()<4> (B0, B1, y0, y1); chunk.template operator()<5> (B1, B0, y1, y0);
-		chunk.template operator()<6> (B0, B1, y0, y1);
+		any_chunk.template operator()<1> (B1, B0, y1, y0);
+		any_chunk.template operator()<2> (B0, B1, y0, y1); any_chunk.template operator()<3> (B1, B0, y1, y0);
+		any_chunk.template operator()<4> (B0, B1, y0, y1); any_chunk.template operator()<5> (B1, B0, y1, y0);
+		any_chunk.template operator()<6> (B0, B1, y0, y1);
 		SPROF_NOW (c3_); SPROF_ADD (2, c3_ - c2_);
-		chunk.template operator()<7> (B1, B0, y1, y0);
+		any_chunk.template operator()<7> (B1, B0, y1, y0);
 		SPROF_NOW (c4_); SPROF_ADD (3, c4_ - c3_);
 		// the rest of the recurrence's sequence: one packed block
 		if (KW) {
@@ -637,6 +760,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	if (blockIdx.x == gridDim.x / 2 && lane == 0) for (int i = 0; i < 8; ++i) g_seg_prof[i] = sprof_[i];
 #endif
 
+	if (SCREEN && lane == 0 && a.seg_stats) { atomicAdd (&a.seg_stats[0], n_scr); atomicAdd (&a.seg_stats[1], n_fin); }
 	if (live) {
 		atomicMax (&st->tp_call[0], __float_as_uint (fmaxf (pk0.x, pkf.x)));
 		atomicMax (&st->tp_call[1], __float_as_uint (fmaxf (pk0.y, pkf.y)));
@@ -663,9 +787,16 @@ int mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* str
 {
 	hipStream_t st = (hipStream_t) stream;
 	const bool aligned = a.tile_frames % R == 0;
-	if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // (no tiles without Σ y²; the
-	else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // same code but for the launch's last step)
-	else if (aligned) hipLaunchKernelGGL ((k_seg<true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-	else              hipLaunchKernelGGL ((k_seg<true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+	if (a.screen) {
+		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // (no tiles without Σ y²; the
+		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // same code but for the launch's last step)
+		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else              hipLaunchKernelGGL ((k_seg<true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+	} else {
+		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else              hipLaunchKernelGGL ((k_seg<true, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+	}
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }

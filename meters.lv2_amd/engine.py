@@ -487,7 +487,8 @@ class Engine:
         return a.value, b.value
 
     def refine_stats(self):
-        """tune_prune = 2: (channel-blocks screened with the first product, completed with the other two)"""
+        """(products screened with the first f16 product, completed with the other two): k_kwtp16's channel-blocks with
+        tune_prune = 2, k_seg's 16-column chunks (layout 7, unless MTR_SEG_SCREEN=0)"""
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib.mtr_engine_refine_stats(self._h, C.byref(a), C.byref(b)), "refine_stats")
         return a.value, b.value
