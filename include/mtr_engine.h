@@ -63,11 +63,18 @@ typedef struct {
 	uint32_t struct_size;    /* = sizeof(mtr_config) */
 	uint32_t meters;         /* MTR_METER_* mask */
 	uint32_t n_streams;      /* independent streams in the batch (>= 1) */
-	uint32_t n_channels;     /* 2 (interleaved stereo frames) or 1 (mono; SPECTR30 / TPBALLIST only) */
+	uint32_t n_channels;     /* 2 (interleaved stereo frames), 1 (mono: SPECTR30 / TPBALLIST / BITSTATS / SIGDIST / DR14 /
+	                          * KMETER; not EBU / TRUEPEAK: MTR_ERR_UNSUPPORTED) or 3 .. 5 (EBU / TRUEPEAK only: MTR_ERR_UNSUPPORTED
+	                          * with any other meter).  Multichannel loudness (Ebu_r128_proc::init (nchan, fsamp),
+	                          * ebumeter/ebu_r128_proc.h:26, 104): frames interleaved in the BS.1770 order L R C Ls Rs (5.0; a
+	                          * 5.1 programme is passed without its LFE), channel i weighted by _chan_gain = {1, 1, 1, 1.41, 1.41}
+	                          * (ebu_r128_proc.cc:29).  Every 3 .. 5 channel engine runs layout 8 (mtr_kwmc.hip); its true peak
+	                          * is per channel (mtr_engine_truepeak_channels) and truepeak[0] = truepeak[1] = the max over the
+	                          * channels.  0 or more than 5: MTR_ERR_ARG. */
 	float    sample_rate;    /* Hz; reference: instantiate()'s `rate` (src/meters.cc:194) */
 	int32_t  device;         /* HIP device ordinal */
 	uint32_t max_frames;     /* largest n_frames a process call will carry (scratch sizing); 0 = grow on demand */
-	uint32_t tune_run;       /* frames per lane run of the wave-per-segment kernels: 0 = auto, 39 (layouts 3, 4), 19 (layout 4), 38 (layouts 6, 7) */
+	uint32_t tune_run;       /* frames per lane run of the wave-per-segment kernels: 0 = auto, 39 (layouts 3, 4), 19 (layout 4), 38 (layouts 6, 7), 20 (layout 8) */
 	uint32_t tune_segments;  /* time segments per stream per call: 0 = auto (layout 7: also forces the lane = segment kernel
 	                          * onto every call it can serve, however small the batch) */
 	uint32_t tune_layout;    /* 0 = auto,
@@ -83,6 +90,8 @@ typedef struct {
 	                          *     sample rate, stride and position in the stream — the same arithmetic with LANE = TIME
 	                          *     SEGMENT (mtr_seg.hip): whole fragments through that kernel, the rest of a fragment the call
 	                          *     started in and what is left behind the last whole one through layout 6.
+	                          * 8 = k_kwmc (mtr_kwmc.hip), the multichannel kernel: the only layout, and the auto choice, of every
+	                          *     3 .. 5 channel engine; MTR_ERR_ARG on a stereo engine.
 	                          * Layouts 1, 2 and 5 of earlier versions no longer exist: MTR_ERR_ARG. */
 	uint32_t tune_fir;       /* layout 3 only: 0 = mirror-symmetric form (120 ops / frame), 1 = dense 3 x 48 taps */
 	uint32_t tune_prune;     /* 1 = exact true-peak pruning (branch and bound on L1 * max|x| per tile): identical result,
@@ -102,8 +111,9 @@ typedef struct {
 	float   integrated, integ_thr, range_min, range_max, range_thr;
 	int32_t hist_M_count, hist_S_count;
 	float   truepeak[2];       /* max |4x-oversampled sample| since reset, per channel, linear:
-	                            * the max-hold of TruePeakdsp::read() the LV2 glue keeps (src/ebulv2.cc:361-365) */
-	float   truepeak_call[2];  /* the same over the most recent process call only = process_max() + read() */
+	                            * the max-hold of TruePeakdsp::read() the LV2 glue keeps (src/ebulv2.cc:361-365).
+	                            * n_channels 3 .. 5: both slots hold the max over ALL channels (the programme's true peak) */
+	float   truepeak_call[2];  /* the same over the most recent process call only = process_max() + read() (same rule) */
 	float   tpb_level[2];      /* TPBALLIST: TruePeakdsp::read(m, p) after the most recent call: m (src/meters.cc:491-507) */
 	float   tpb_peak[2];       /*            ... and p, the raw true peak of that call */
 } mtr_stream_result;
@@ -131,7 +141,7 @@ int  mtr_engine_spectr_reset_peak (mtr_engine* e);
 /* ---- the hot path --------------------------------------------------------- */
 
 /* Advance every stream by n_frames.  `d_audio` is DEVICE memory, stream s at
- * d_audio + s * stream_stride_frames * n_channels, frames interleaved [L R].
+ * d_audio + s * stream_stride_frames * n_channels, frames interleaved [L R] (n_channels 3 .. 5: [L R C Ls Rs]).
  * Asynchronous on `hip_stream`.
  * replaces, per stream: Ebu_r128_proc::process (ebu_r128_proc.cc:207-248) as called at
  * src/ebulv2.cc:341-342, TruePeakdsp::process_max x2 (:344-347), the per-sample loop of
@@ -182,6 +192,10 @@ int  mtr_engine_deferred_stats (mtr_engine* e, uint64_t* calls);
 
 /* replaces: loudness_M() ... range_thr(), hist_*_count() (ebu_r128_proc.h:81-94), TruePeakdsp::read */
 int  mtr_engine_results (mtr_engine* e, uint32_t first, uint32_t count, mtr_stream_result* out);
+/* Per-channel true peak, any n_channels: hold / last are [count][n_channels] (either may be NULL) — the max-hold since reset and
+ * the most recent call's peak of every channel.  replaces: TruePeakdsp::read () per channel after process_max
+ * (src/ebulv2.cc:344-347, 361-365, one TruePeakdsp per channel).  Needs TRUEPEAK. */
+int  mtr_engine_truepeak_channels (mtr_engine* e, uint32_t first, uint32_t count, float* hold, float* last);
 /* replaces: histogram_M() / histogram_S() (ebu_r128_proc.h:91-92); out arrays are [count][751] */
 int  mtr_engine_histograms (mtr_engine* e, uint32_t first, uint32_t count, int32_t* hist_M, int32_t* hist_S);
 /* Per-fragment mean powers of the most recent call ([count][n_frag], n_frag returned), i.e. the

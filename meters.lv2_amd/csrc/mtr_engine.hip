@@ -86,7 +86,7 @@ struct Plan {
 struct mtr_engine {
 	mtr_config cfg;
 	int      run = 39;            // K: frames per lane run
-	int      layout = 6;          // 3 = exact-f32 VALU interpolator (mtr_fused2.hip), 4 = k_kw, 6 = k_kwtp16 (+ 7: k_seg for the calls it fits)
+	int      layout = 6;          // 3 = exact-f32 VALU interpolator (mtr_fused2.hip), 4 = k_kw, 6 = k_kwtp16 (+ 7: k_seg for the calls it fits), 8 = k_kwmc
 	bool     seg_ok = false;      // layout 7: calls that fit go through k_seg (mtr_seg.hip), the rest through k_kwtp16
 	uint32_t seg_slots = 1024;    // resident k_seg waves: one per SIMD
 	uint64_t seg_calls = 0, seg_frames = 0;
@@ -160,6 +160,12 @@ struct mtr_engine {
 	double                     km_pw1[3];
 	uint32_t                   km_fpp = 0;
 	float                      km_fall = 0.f;
+	// layout 8 (n_channels 1, 3, 4, 5 with EBU / TRUEPEAK, mtr_kwmc.hip): per-channel side buffers; the stream state's kz / tp_* stay unused
+	// by the kernel, its tp_last / tp_hold [0..1] carry the max over the channels (k_history_mc)
+	DevBuf<float>    mc_kz;         // [S][C][4]
+	DevBuf<float>    mc_hist[2];    // [S][47][C] ping-pong with hist_cur
+	DevBuf<uint32_t> mc_tp_call;    // [S][C]
+	DevBuf<float>    mc_tp_last, mc_tp_hold;   // [S][C]
 	DevBuf<float>    fir_g;         // [3][48] taps in device memory
 	DevBuf<uint16_t> m16_a;         // layouts 6, 7: hi / lo A fragments of the f32-grade MFMA interpolator (mtr_mfma16_fir.h)
 	DevBuf<uint32_t> prune_cnt;     // [4] interpolator tile passes considered / skipped, channel-blocks screened / completed
@@ -305,6 +311,15 @@ static int state_init (mtr_engine* e, int what, hipStream_t st)
 	return MTR_OK;
 }
 
+// the per-channel true-peak arrays of layout 8 (TruePeakdsp::reset per channel)
+static int mc_tp_clear (mtr_engine* e, hipStream_t st)
+{
+	HIPCHK (hipMemsetAsync (e->mc_tp_call.p, 0, e->mc_tp_call.n * sizeof (uint32_t), st));
+	HIPCHK (hipMemsetAsync (e->mc_tp_last.p, 0, e->mc_tp_last.n * sizeof (float), st));
+	HIPCHK (hipMemsetAsync (e->mc_tp_hold.p, 0, e->mc_tp_hold.n * sizeof (float), st));
+	return MTR_OK;
+}
+
 extern "C" {
 
 const char* mtr_last_error (void) { return g_err.c_str (); }
@@ -353,6 +368,18 @@ void mtr_hist_loudness (const int32_t* hm, const int32_t* hs, float* integ, floa
 // Which kernels serve a configuration (pure: mtr_engine_create and mtr_plan_query share it).  Returns what is wrong with it, or NULL.
 static const char* resolve_layout (const mtr_config* cfg, int* layout, int* run, bool* seg_ok)
 {
+	const bool fused = cfg->meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK);
+	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_CHANNELS) return "n_channels must be 1 .. 5";
+	if (cfg->n_channels > 2 && fused) {
+		// every EBU / TRUEPEAK engine of 3 .. 5 channels runs k_kwmc (layout 8, mtr_kwmc.hip)
+		if (cfg->tune_layout != 0 && cfg->tune_layout != 8) return "n_channels 3 .. 5: tune_layout must be 0 or 8 (k_kwmc is the only multichannel kernel)";
+		if (cfg->tune_run != 0 && cfg->tune_run != MTR_KWMC_RUN) return "layout 8 runs 20-frame lane runs: tune_run must be 0 or 20";
+		if (cfg->tune_prune != 0) return "layout 8 has no peak pruning: tune_prune must be 0";
+		if (cfg->tune_fir != 0) return "layout 8 has one interpolator form: tune_fir must be 0";
+		*layout = 8; *run = MTR_KWMC_RUN; *seg_ok = false;
+		return nullptr;
+	}
+	if (cfg->tune_layout == 8) return "layout 8 is the multichannel kernel (n_channels 3, 4 or 5 with EBU / TRUEPEAK)";
 	if (cfg->tune_run != 0 && cfg->tune_run != 19 && cfg->tune_run != 38 && cfg->tune_run != 39) return "tune_run must be 0, 19, 38 or 39";
 	if (cfg->tune_layout != 0 && cfg->tune_layout != 3 && cfg->tune_layout != 4 && cfg->tune_layout != 6 && cfg->tune_layout != 7)
 		return "tune_layout must be 0, 3, 4, 6 or 7 (layouts 1, 2 and 5 of earlier versions are gone)";
@@ -377,12 +404,15 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	if (!cfg || !out || cfg->struct_size != sizeof (mtr_config)) return fail (MTR_ERR_ARG, "mtr_engine_create: bad config");
 	*out = nullptr;
 	if (cfg->n_streams == 0 || !(cfg->sample_rate >= 8000.f) || cfg->meters == 0) return fail (MTR_ERR_ARG, "mtr_engine_create: n_streams / sample_rate / meters");
-	if (cfg->n_channels != 1 && cfg->n_channels != 2) return fail (MTR_ERR_ARG, "n_channels must be 1 or 2");
+	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_CHANNELS) return fail (MTR_ERR_ARG, "n_channels must be 1 .. 5");
 	if (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_SPECTR30 | MTR_METER_TPBALLIST | MTR_METER_BITSTATS
 	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER))
 		return fail (MTR_ERR_ARG, "unknown bits in the meters mask");
 	if (cfg->n_channels == 1 && (cfg->meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
-		return fail (MTR_ERR_UNSUPPORTED, "EBU / TRUEPEAK need stereo frames (the reference's EBUr128 plugin is stereo only)");
+		return fail (MTR_ERR_UNSUPPORTED, "EBU / TRUEPEAK take 2 .. 5 channels, not mono");
+	// 3 .. 5 channels: EBU R128 and true peak only (Ebu_r128_proc::init takes up to five, ebumeter/ebu_r128_proc.h:26)
+	if (cfg->n_channels > 2 && (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
+		return fail (MTR_ERR_UNSUPPORTED, "3 .. 5 channels: only EBU and TRUEPEAK meter them");
 	if ((cfg->meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) && cfg->n_channels != 1)
 		return fail (MTR_ERR_UNSUPPORTED, "BITSTATS / SIGDIST take mono streams (the reference's bitmeter / SigDistHist are mono plugins)");
 	{
@@ -429,6 +459,12 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	    || e->fir_hist[0].reserve ((size_t) S * MTR_FIR_HALO * 2) || e->fir_hist[1].reserve ((size_t) S * MTR_FIR_HALO * 2))
 		rc = fail (MTR_ERR_NOMEM, "hipMalloc stream state");
 	if (rc == MTR_OK) rc = upload_consts (e);
+	if (rc == MTR_OK && e->layout == 8) {
+		const size_t C = cfg->n_channels;
+		if (e->mc_kz.reserve ((size_t) S * C * 4) || e->mc_hist[0].reserve ((size_t) S * MTR_FIR_HALO * C) || e->mc_hist[1].reserve ((size_t) S * MTR_FIR_HALO * C)
+		    || e->mc_tp_call.reserve ((size_t) S * C) || e->mc_tp_last.reserve ((size_t) S * C) || e->mc_tp_hold.reserve ((size_t) S * C))
+			rc = fail (MTR_ERR_NOMEM, "hipMalloc multichannel state");
+	}
 	if (rc == MTR_OK) {
 		// max-hold scratch of the multi-workgroup gate: "minus infinity" as a sortable int (mtr_gate.hip)
 		std::vector<int32_t> m ((size_t) S * 2, (int32_t) 0x807fffff);
@@ -482,6 +518,7 @@ void mtr_engine_destroy (mtr_engine* e)
 	if (e->xs_event) (void) hipEventDestroy (e->xs_event);
 	e->bank_coef.release (); e->bank_z.release (); e->bank_val.release (); e->bank_max.release (); e->bank_ac[0].release (); e->bank_ac[1].release ();
 	e->fir_g.release (); e->m16_a.release ();
+	e->mc_kz.release (); e->mc_hist[0].release (); e->mc_hist[1].release (); e->mc_tp_call.release (); e->mc_tp_last.release (); e->mc_tp_hold.release ();
 	e->bim.release (); e->sdh.release (); e->prune_cnt.release ();
 	e->dr_state.release (); e->dr_hist.release (); e->dr_sum.release (); e->dr_peak.release ();
 	e->km_state.release (); e->km_piece.release (); e->km_max.release ();
@@ -499,6 +536,13 @@ int mtr_engine_reset (mtr_engine* e)
 	const size_t hb = (size_t) e->cfg.n_streams * MTR_FIR_HALO * 2 * sizeof (float);
 	HIPCHK (hipMemsetAsync (e->fir_hist[0].p, 0, hb, st));
 	HIPCHK (hipMemsetAsync (e->fir_hist[1].p, 0, hb, st));
+	if (e->layout == 8) {
+		HIPCHK (hipMemsetAsync (e->mc_kz.p, 0, e->mc_kz.n * sizeof (float), st));
+		HIPCHK (hipMemsetAsync (e->mc_hist[0].p, 0, e->mc_hist[0].n * sizeof (float), st));
+		HIPCHK (hipMemsetAsync (e->mc_hist[1].p, 0, e->mc_hist[1].n * sizeof (float), st));
+		const int trc = mc_tp_clear (e, st);
+		if (trc) return trc;
+	}
 	if (e->cfg.meters & MTR_METER_SPECTR30) {
 		HIPCHK (hipMemsetAsync (e->bank_z.p, 0, e->bank_z.n * sizeof (double), st));
 		HIPCHK (hipMemsetAsync (e->bank_val.p, 0, e->bank_val.n * sizeof (float), st));
@@ -668,7 +712,9 @@ int mtr_engine_truepeak_reset (mtr_engine* e)
 	if (!e) return fail (MTR_ERR_ARG, "null engine");
 	e->snap_valid = false;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	return state_init (e, MTR_INIT_TP, e->last_stream);
+	const int rc = state_init (e, MTR_INIT_TP, e->last_stream);
+	if (rc || e->layout != 8) return rc;
+	return mc_tp_clear (e, e->last_stream);
 }
 
 int mtr_engine_spectr_set_speed (mtr_engine* e, float v)
@@ -942,7 +988,7 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 	const bool only_fused = (e->cfg.meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK)) == 0;
 	// (and a batch of thousands of streams: the gate's serial time grows with the streams, what deferring it costs does not — at 1024 streams x 60 s
 	// the serial order is 0.5 % FASTER, at 8192 x 10 s the deferred one by 0.4 - 1.4 % across boxes)
-	const bool defer = (ebu || tp) && (e->tail_mode == 2 || (e->tail_mode == 0 && e->v_cnt == 0 && sp.use && only_fused && S >= TAIL_AUTO_STREAMS
+	const bool defer = (ebu || tp) && e->layout != 8 && (e->tail_mode == 2 || (e->tail_mode == 0 && e->v_cnt == 0 && sp.use && only_fused && S >= TAIL_AUTO_STREAMS
 	                                                          && (uint64_t) S * n_frames >= TAIL_AUTO_FRAMES));
 	if (defer) { const int trc = tail_setup (e); if (trc) return trc; }
 	else if (ebu || tp) { const int jrc = join_tail (e, st); if (jrc) return jrc; }   // a serial gate follows the deferred ones
@@ -1001,6 +1047,21 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 				lrc = mtr_launch_kwtp16 (e->run, ebu, fa, S, st);
 			}
 			e->seg_calls += 1; e->seg_frames += (uint64_t) sp.tiles * e->fragm;
+		} else if (e->layout == 8) {
+			const uint32_t C = e->cfg.n_channels;
+			mtr_kwmc_args ma;
+			ma.audio = d_audio; ma.stride = stride;
+			ma.hist = e->mc_hist[e->hist_cur].p + vo * MTR_FIR_HALO * C;
+			ma.tile_start = fa.tile_start; ma.seg_tile = fa.seg_tile; ma.scan_m = fa.scan_m;
+			ma.kz = e->mc_kz.p + vo * C * 4; ma.tp_call = e->mc_tp_call.p + vo * C;
+			ma.tile_power = fa.tile_power; ma.mfma_a = e->m16_a.p;
+			ma.n_streams = S; ma.n_segs = pl.n_segs; ma.n_tiles = pl.n_tiles; ma.warm_tiles = fa.warm_tiles;
+			ma.n_frames = n_frames;
+			ma.a0 = fa.a0; ma.a1 = fa.a1; ma.a2 = fa.a2; ma.b1 = fa.b1; ma.b2 = fa.b2; ma.c3 = fa.c3; ma.c4 = fa.c4;
+			// _chan_gain, ebu_r128_proc.cc:29 (L R C Ls Rs)
+			const float gains[MTR_MAX_CHANNELS] = { 1.0f, 1.0f, 1.0f, 1.41f, 1.41f };
+			for (int c = 0; c < MTR_MAX_CHANNELS; ++c) ma.gain[c] = gains[c];
+			lrc = mtr_launch_kwmc ((int) C, ebu, tp, ma, S * pl.n_segs, st);
 		} else {
 			lrc = e->layout == 6 ? mtr_launch_kwtp16 (e->run, ebu, fa, S * pl.n_segs, st)
 			    : e->layout == 4 ? mtr_launch_kw (e->run, fa, S * pl.n_segs, st)
@@ -1032,7 +1093,7 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 		ga.tail_tile = ebu ? pl.tail_tile : 0;
 		ga.fragm = (float) e->fragm; ga.integr = e->integr ? 1 : 0;
 		ga.max_scratch = e->gate_max.p + vo * 2;
-		ga.fold_tp = fold_in_history ? 0 : 1;
+		ga.fold_tp = (fold_in_history || e->layout == 8) ? 0 : 1;      // (layout 8: k_history_mc folds the per-channel peaks)
 		ga.polite_grid = defer ? e->tail_gate_grid : 0;
 		if (mtr_launch_gate (ga, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
 		if (tm) { hipEvent_t v = next_event (e, ev0 + 3); if (v) HIPCHK (hipEventRecord (v, gst)); }
@@ -1112,11 +1173,17 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 		// the 47 frames before the next call; after every consumer of the current history
 		// (deferred: the fold of this call's peaks rides here — behind the reduction of the previous call, which reads the holds)
 		if (fold_in_history && e->red_pending) { HIPCHK (hipStreamWaitEvent (st, e->ev_red, 0)); e->red_pending = false; }
-		const int hrc = e->cfg.n_channels == 2
+		const int hrc = e->layout == 8 ? 0 : e->cfg.n_channels == 2
 			? mtr_launch_history (d_audio, stride, n_frames, e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2, e->fir_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * 2, S,
 			                      fold_in_history ? e->state.p + vo : nullptr, st)
 			: mtr_launch_history_mono (d_audio, stride, n_frames, e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2, e->fir_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * 2, S, st);
 		if (hrc) return fail (MTR_ERR_HIP, "k_history launch");
+		if (tp && e->layout == 8) {
+			const uint32_t C = e->cfg.n_channels;
+			if (mtr_launch_history_mc (d_audio, stride, n_frames, C, e->mc_hist[e->hist_cur].p + vo * MTR_FIR_HALO * C, e->mc_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * C, S,
+			                           e->mc_tp_call.p + vo * C, e->mc_tp_last.p + vo * C, e->mc_tp_hold.p + vo * C, e->state.p + vo, st))
+				return fail (MTR_ERR_HIP, "k_history_mc launch");
+		}
 		e->hist_cur ^= 1;
 	}
 	if (tm) {
@@ -1172,7 +1239,7 @@ int mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_fra
 	const uint32_t S = e->cfg.n_streams;
 	// (streams start on 16 bytes in the staging buffers — an even stride of stereo frames, a multiple of four mono ones — so that
 	// every layout can take the call and k_tpb's LDS-DMA its source)
-	const uint64_t dstride = C == 1 ? (n_frames + 3) & ~(uint64_t) 3 : (n_frames + 1) & ~(uint64_t) 1;
+	const uint64_t dstride = C == 2 ? (n_frames + 1) & ~(uint64_t) 1 : (n_frames + 3) & ~(uint64_t) 3;   // (and 1, 3, 4, 5 channels: a multiple of four frames)
 	const size_t row = (size_t) dstride * C;                                  // floats per staged stream
 	uint32_t cs = (uint32_t) std::min<uint64_t> (S, std::max<uint64_t> (1, e->host_chunk_bytes / (row * sizeof (float))));
 	const uint32_t n_chunks = (S + cs - 1) / cs;
@@ -1227,7 +1294,7 @@ int mtr_engine_process_planar_host (mtr_engine* e, const float* const* ch, uint3
 	if (e->cfg.n_streams != 1) return fail (MTR_ERR_ARG, "planar host input is the n_streams == 1 (LV2) path");
 	if (n_frames == 0) return MTR_OK;
 	const uint32_t C = e->cfg.n_channels;
-	if (C == 2 && !ch[1]) return fail (MTR_ERR_ARG, "missing right channel");
+	for (uint32_t c = 1; c < C; ++c) if (!ch[c]) return fail (MTR_ERR_ARG, "mtr_engine_process_planar_host: a channel pointer is NULL");
 	HIPCHK (hipSetDevice (e->cfg.device));
 	hipStream_t st;
 	int rc = host_stream (e, &st);
@@ -1241,7 +1308,8 @@ int mtr_engine_process_planar_host (mtr_engine* e, const float* const* ch, uint3
 	if (e->pin_state.reserve (1) || e->pin_bank.reserve (2 * MTR_NBANDS)) return fail (MTR_ERR_NOMEM, "hipHostMalloc snapshot");
 	float* const il = e->pin_in.p;                 // free: the previous block ended with a wait
 	if (C == 2) for (uint32_t i = 0; i < n_frames; ++i) { il[2 * i] = ch[0][i]; il[2 * i + 1] = ch[1][i]; }
-	else        memcpy (il, ch[0], (size_t) n_frames * sizeof (float));
+	else if (C == 1) memcpy (il, ch[0], (size_t) n_frames * sizeof (float));
+	else for (uint32_t i = 0; i < n_frames; ++i) for (uint32_t c = 0; c < C; ++c) il[(size_t) i * C + c] = ch[c][i];
 	HIPCHK (hipMemcpyAsync (e->stage.p, il, total * sizeof (float), hipMemcpyHostToDevice, st));
 	rc = mtr_engine_process_device (e, e->stage.p, n_frames, n_frames, st);
 	if (rc) return rc;
@@ -1335,6 +1403,33 @@ int mtr_engine_results (mtr_engine* e, uint32_t first, uint32_t count, mtr_strea
 			r.tpb_level[c] = s.tpb_m[c]; r.tpb_peak[c] = s.tpb_p[c];
 		}
 	}
+	return MTR_OK;
+}
+
+// TruePeakdsp::read () per channel (src/ebulv2.cc:361-365 for each of n_channels): what the stereo engine reports in
+// mtr_stream_result.truepeak / truepeak_call, channel by channel
+int mtr_engine_truepeak_channels (mtr_engine* e, uint32_t first, uint32_t count, float* hold, float* last)
+{
+	int rc = check_range (e, first, count);
+	if (rc) return rc;
+	if (!hold && !last) return fail (MTR_ERR_ARG, "mtr_engine_truepeak_channels: null outputs");
+	if (!(e->cfg.meters & MTR_METER_TRUEPEAK)) return fail (MTR_ERR_ARG, "no TRUEPEAK in this engine");
+	if (count == 0) return MTR_OK;
+	const size_t C = e->cfg.n_channels;
+	if (e->layout != 8) {
+		mtr_stream_result* r = new (std::nothrow) mtr_stream_result[count];
+		if (!r) return fail (MTR_ERR_NOMEM, "mtr_engine_truepeak_channels");
+		rc = mtr_engine_results (e, first, count, r);
+		if (rc == MTR_OK)
+			for (uint32_t i = 0; i < count; ++i)
+				for (size_t c = 0; c < C; ++c) { if (hold) hold[i * C + c] = r[i].truepeak[c]; if (last) last[i * C + c] = r[i].truepeak_call[c]; }
+		delete[] r;
+		return rc;
+	}
+	rc = mtr_engine_sync (e);
+	if (rc) return rc;
+	if (hold) HIPCHK (hipMemcpy (hold, e->mc_tp_hold.p + (size_t) first * C, count * C * sizeof (float), hipMemcpyDeviceToHost));
+	if (last) HIPCHK (hipMemcpy (last, e->mc_tp_last.p + (size_t) first * C, count * C * sizeof (float), hipMemcpyDeviceToHost));
 	return MTR_OK;
 }
 
@@ -1708,6 +1803,13 @@ std::vector<StateSection> state_sections (const mtr_engine* e)
 		v.push_back ({ e->dr_hist.p, (size_t) e->cfg.n_channels * MTR_DR_HISTBINS * sizeof (uint32_t) });
 	}
 	if (m & MTR_METER_KMETER) v.push_back ({ e->km_state.p, 2 * sizeof (mtr_kmeter_state) });
+	if (e->layout == 8) {                                      // the per-channel side buffers (stereo blobs are unchanged)
+		const size_t C = e->cfg.n_channels;
+		v.push_back ({ e->mc_kz.p, C * 4 * sizeof (float) });
+		v.push_back ({ e->mc_hist[e->hist_cur].p, (size_t) MTR_FIR_HALO * C * sizeof (float) });
+		v.push_back ({ e->mc_tp_last.p, C * sizeof (float) });
+		v.push_back ({ e->mc_tp_hold.p, C * sizeof (float) });
+	}
 	return v;
 }
 

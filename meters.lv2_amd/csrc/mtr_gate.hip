@@ -541,3 +541,44 @@ int mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint3
 	                    st, hist, n_streams, d_hist, d_max);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- the multichannel engines (layout 8): FIR history and the per-channel true-peak fold ------------------------------
+
+// New 47-frame history = the last 47 frames of (old history ++ this call's audio), C channels (zita-resampler/resampler.cc:229-262);
+// lane i == 0 of a stream also folds the call's peaks (src/ebulv2.cc:361-365, per channel) and reports the programme's true peak,
+// the max over the channels, in the stream state's two slots — what mtr_engine_results, k_aggregate and the reduction read.
+__global__ void k_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in,
+                              float* hist_out, uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= n_streams * MTR_FIR_HALO) return;
+	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
+	const int64_t f = (int64_t) n_frames - MTR_FIR_HALO + i;
+	for (uint32_t c = 0; c < C; ++c)
+		hist_out[((size_t) s * MTR_FIR_HALO + i) * C + c] = (f >= 0) ? audio[((size_t) s * stride + (size_t) f) * C + c]
+		                                                            : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * C + c];
+	if (!tp_call || i != 0) return;
+	float last = 0.f, hold = 0.f;
+	for (uint32_t c = 0; c < C; ++c) {
+		const size_t k = (size_t) s * C + c;
+		const float v = __uint_as_float (tp_call[k]);
+		tp_last[k] = v;
+		if (v > tp_hold[k]) tp_hold[k] = v;
+		tp_call[k] = 0;
+		last = fmaxf (last, v);
+		hold = fmaxf (hold, tp_hold[k]);
+	}
+	mtr_stream_state* const st = state + s;
+	st->tp_last[0] = st->tp_last[1] = last;
+	st->tp_hold[0] = st->tp_hold[1] = hold;
+	st->tp_call[0] = st->tp_call[1] = 0;
+}
+
+int mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
+                           uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state, void* stream)
+{
+	const uint32_t n = n_streams * MTR_FIR_HALO;
+	hipLaunchKernelGGL (k_history_mc, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
+	                    audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}

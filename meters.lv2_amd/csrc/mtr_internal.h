@@ -82,6 +82,26 @@ typedef struct mtr_seg_args {
 	float           gain_l, gain_r;
 } mtr_seg_args;
 
+/* Arguments of the multichannel K-weighting + true-peak kernel (mtr_kwmc.hip, layout 8: n_channels 3, 4 or 5). */
+#define MTR_MAX_CHANNELS 5         /* Ebu_r128_proc::MAXCH, ebumeter/ebu_r128_proc.h:26 */
+#define MTR_KWMC_RUN     20        /* K: frames per lane run (tiles of at most 1280 frames: half a fragment at 48 kHz) */
+typedef struct mtr_kwmc_args {
+	const float*    audio;        /* [S][stride][C] */
+	uint64_t        stride;       /* frames */
+	const float*    hist;         /* [S][47][C]: the 47 frames before frame 0 of this call */
+	const uint32_t* tile_start;   /* the plan, as mtr_fused_args */
+	const uint32_t* seg_tile;
+	const float*    scan_m;       /* [6][16] (A^K)^(2^d), the functionals and M^1 .. M^32 for K = MTR_KWMC_RUN */
+	float*          kz;           /* [S][C][4] K-filter states z1..z4 per channel */
+	uint32_t*       tp_call;      /* [S][C] float bits, atomicMax target; zero between calls */
+	float*          tile_power;   /* [S][n_tiles] sum_c gain_c sum y_c^2 over the tile */
+	const uint16_t* mfma_a;       /* [12][64][8] hi / lo A fragments (mtr_mfma16_fir.h) */
+	uint32_t        n_streams, n_segs, n_tiles, warm_tiles;
+	uint64_t        n_frames;
+	float           a0, a1, a2, b1, b2, c3, c4;
+	float           gain[MTR_MAX_CHANNELS];   /* _chan_gain (ebu_r128_proc.cc:29) */
+} mtr_kwmc_args;
+
 struct mtr_gate_args {
 	mtr_stream_state* state;      /* [S] */
 	int32_t*        hist;         /* [S][2][751] */
@@ -201,6 +221,11 @@ uint32_t mtr_kmeter_pieces (uint64_t n_groups);
 int  mtr_fused2_upload_taps (const float* g144);
 int  mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
                          float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state /* NULL: k_gate folds the peaks */, void* stream);
+int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, uint32_t n_units, void* stream);
+/* [S][47][C] history of the multichannel engines; fold_c != NULL: also TruePeakdsp::read () per channel (tp_call -> tp_last,
+ * tp_hold, all [S][C]) and the max over the channels into the stream state's tp_last[0..1] / tp_hold[0..1] */
+int  mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
+                            uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state, void* stream);
 int  mtr_launch_gate (const mtr_gate_args& a, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);

@@ -113,6 +113,8 @@ def _load():
     L.mtr_engine_process_planar_host.argtypes = [vp, C.POINTER(vp), u32]
     L.mtr_engine_results.argtypes = [vp, u32, u32, C.POINTER(StreamResult)]
     L.mtr_engine_histograms.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "mtr_engine_truepeak_channels"):             # (an addition inside ABI version 2: multichannel engines)
+        L.mtr_engine_truepeak_channels.argtypes = [vp, u32, u32, vp, vp]
     L.mtr_engine_fragment_powers.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32)]
     L.mtr_engine_spectrum.argtypes = [vp, u32, u32, vp, vp, vp, vp]
     L.mtr_engine_aggregate_device.argtypes = [vp, vp, vp, vp]
@@ -299,7 +301,7 @@ class Engine:
                       max_frames=0, tune_run=tune_run, tune_segments=tune_segments,
                       tune_layout=tune_layout, tune_fir=tune_fir, tune_prune=tune_prune)
         self._h = C.c_void_p()
-        self.n_streams, self.meters, self.sample_rate = n_streams, meters, sample_rate
+        self.n_streams, self.meters, self.sample_rate, self.n_channels = n_streams, meters, sample_rate, n_channels
         _check(lib.mtr_engine_create(C.byref(cfg), C.byref(self._h)), "mtr_engine_create")
 
     def close(self):
@@ -340,7 +342,7 @@ class Engine:
         _check(lib.mtr_engine_process_device(self._h, ptr, n_frames, stride or n_frames, stream), "process_device")
 
     def process(self, x):
-        """x: host float32 [S, T, 2] (or [S, T] mono)."""
+        """x: host float32 [S, T, C] (or [S, T] mono), C = n_channels."""
         x = np.ascontiguousarray(x, np.float32)
         assert x.shape[0] == self.n_streams
         _check(lib.mtr_engine_process_host(self._h, x.ctypes.data, x.shape[1], x.shape[1]), "process_host")
@@ -384,6 +386,16 @@ class Engine:
     def truepeak(self, first=0, count=None):
         r = self.results(first, count)
         return np.array([[x.truepeak[0], x.truepeak[1]] for x in r], np.float32)
+
+    def truepeak_channels(self, first=0, count=None):
+        """(hold, last): [count, n_channels] float32 — per channel, the max-hold since reset and the most recent call's peak."""
+        if not hasattr(lib, "mtr_engine_truepeak_channels"):
+            raise EngineError(f"{lib_path} has no mtr_engine_truepeak_channels: rebuild it")
+        count = self.n_streams - first if count is None else count
+        hold = np.zeros((count, self.n_channels), np.float32)
+        last = np.zeros((count, self.n_channels), np.float32)
+        _check(lib.mtr_engine_truepeak_channels(self._h, first, count, hold.ctypes.data, last.ctypes.data), "truepeak_channels")
+        return hold, last
 
     def histograms(self, first=0, count=None):
         count = self.n_streams - first if count is None else count
