@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-/* 2: + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+/* 2 (unchanged by later additions a client looks up by name: mtr_engine_truepeak_channels; mtr_engine_process_device_lengths,
+ *    _process_host_lengths, _stream_frames): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -157,6 +158,27 @@ int  mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_
  * rest not — the streams are no longer in lock step: mtr_engine_reset () before the engine is used again. */
 int  mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames,
                               uint64_t stream_stride_frames);
+/* Per-stream lengths: a batch of tracks that end where their audio ends.
+ * Advance stream s by frames[s] <= n_frames frames of this call (frames: HOST array [n_streams]); frames at or past
+ * frames[s] in the buffer are never metered, whatever they hold.  A stream with frames[s] < n_frames is CLOSED by the
+ * call: its results are those of the reference after exactly its own frames, and no later process call (this entry or
+ * mtr_engine_process_device / _host) changes anything of it until mtr_engine_reset.  frames[s] == n_frames: the stream
+ * stays open, bit for bit as mtr_engine_process_device.  frames[s] == 0 closes a stream without touching it (its
+ * truepeak_call stays that of its previous call).  Closure is not part of the state blob: mtr_engine_reset reopens every
+ * stream, mtr_engine_state_import the streams it imports.
+ * EBU / TRUEPEAK engines only (2 .. 5 channels, every layout): MTR_ERR_UNSUPPORTED with any other meter.
+ * frames == NULL or frames[s] > n_frames: MTR_ERR_ARG before anything is queued, engine unchanged.
+ * Once a stream is closed, every later call on the streams that hold it runs the length-masking kernels (end 0 for the closed ones).
+ * The _host form indexes `frames` by stream as mtr_engine_process_host's chunks do (bit for bit the _device form).
+ * replaces: a host that stops calling run() at a track's end (src/ebulv2.cc:341-347 over the track's frames only). */
+int  mtr_engine_process_device_lengths (mtr_engine* e, const float* d_audio, uint64_t n_frames,
+                                        uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);
+int  mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames,
+                                      uint64_t stream_stride_frames, const uint64_t* frames);
+/* Frames metered per stream since create / reset, and whether it is closed (either pointer may be NULL): [count] each.
+ * (What the process calls queued so far: no synchronisation.  mtr_engine_state_import restarts the count of the streams it writes
+ * at 0: a blob carries no frame count.) */
+int  mtr_engine_stream_frames (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* frames, uint8_t* closed);
 /* Bytes of audio per chunk of mtr_engine_process_host (0 = the default, 256 MiB; at least one stream per chunk). */
 int  mtr_engine_set_host_chunk_bytes (mtr_engine* e, uint64_t bytes);
 /* n_streams == 1, planar host channels — the shape an LV2 run() hands over

@@ -66,6 +66,17 @@ template <typename T> struct PinBuf {
 // STREAM: a call whose (n_frames, fragment phase) differs from the previous one — every call, for 1024-frame blocks at
 // 48 kHz — never overwrites arrays that kernels of an earlier call may still be reading, and never blocks the host.
 constexpr int PLAN_SLOTS = 4;
+
+// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths, or any call once a stream is closed) ride the same way:
+// [ends S | frag_lim S | from_tile S] in the next slot of their own ring, uploaded on the call's stream, busy until the call's last
+// readers (k_history_len on the call's stream, the gate on whichever stream it ran) have passed.
+constexpr int LEN_SLOTS = 4;
+struct LenSlot {
+	DevBuf<uint32_t> dev;
+	PinBuf<uint32_t> pin;
+	hipEvent_t       done[2] = { nullptr, nullptr };
+	bool             pending[2] = { false, false };
+};
 struct PlanSlot {
 	DevBuf<uint32_t> dev;       // [tile_start (n_tiles + 1) | seg_tile (n_segs + 1) | frag_tile (n_frag + 1)]
 	PinBuf<uint32_t> pin;
@@ -74,6 +85,7 @@ struct PlanSlot {
 };
 
 struct Plan {
+	std::vector<uint32_t> frag_end;   // call frame at which fragment f of the call ends (per-stream lengths: fragments that end at or before a stream's end)
 	uint64_t n_frames = 0;
 	uint32_t frcnt_in = 0;      // frames left in the open fragment when the call starts
 	uint32_t frcnt_out = 0;
@@ -173,6 +185,15 @@ struct mtr_engine {
 	float            tpb_w[4];      // w1 w2 w3 g of TruePeakdsp::init
 	Plan             plan;
 	uint32_t         last_n_frag = 0;
+	// Per-stream lengths: frames metered per stream since create / reset, and which streams a call with lengths has closed (a closed
+	// stream is left untouched by every later call until mtr_engine_reset; neither is part of the state blob).  `len_frames` is the
+	// frames [] of the lengths call in progress, indexed by the stream of the view.
+	std::vector<uint64_t> metered;
+	std::vector<uint8_t>  closed;
+	uint32_t         n_closed = 0;
+	const uint64_t*  len_frames = nullptr;
+	LenSlot          len_slot[LEN_SLOTS];
+	int              len_cur = 0;
 
 	// A process call may cover a VIEW of the batch: streams [v_off, v_off + v_cnt) (v_cnt = 0: all of them).  The chunked host
 	// path (mtr_engine_process_host) walks the batch view by view — every per-stream array is indexed from v_off, the host-side
@@ -511,6 +532,7 @@ void mtr_engine_destroy (mtr_engine* e)
 	e->scan_m.release (); e->bin_power.release (); e->tile_power[0].release (); e->tile_power[1].release (); e->frag_power.release ();
 	e->stage.release ();
 	for (PlanSlot& ps : e->plan_slot) { ps.dev.release (); ps.pin.release (); if (ps.done) (void) hipEventDestroy (ps.done); }
+	for (LenSlot& ls : e->len_slot) { ls.dev.release (); ls.pin.release (); for (hipEvent_t v : ls.done) if (v) (void) hipEventDestroy (v); }
 	e->pin_in.release (); e->pin_state.release (); e->pin_bank.release ();
 	if (e->own_stream) (void) hipStreamDestroy (e->own_stream);
 	if (e->copy_stream) (void) hipStreamDestroy (e->copy_stream);
@@ -554,6 +576,9 @@ int mtr_engine_reset (mtr_engine* e)
 	e->frcnt = e->fragm;
 	e->integr = false;
 	e->advanced = false;
+	e->metered.assign (e->cfg.n_streams, 0);                         // (every stream open again)
+	e->closed.assign (e->cfg.n_streams, 0);
+	e->n_closed = 0;
 	e->hist_cur = 0;
 	e->last_n_frag = 0;
 	e->last_deferred = false;
@@ -921,6 +946,8 @@ static int build_plan (mtr_engine* e, uint64_t N, uint32_t head, uint32_t body_t
 	e->head_seg = e->frag_tile + ft.size ();
 	e->tail_seg = e->head_seg + 2;
 
+	pl.frag_end.resize (n_frag);
+	for (uint32_t f = 0; f < n_frag; ++f) pl.frag_end[f] = ts[ft[f + 1]];
 	pl.n_frames = N; pl.frcnt_in = e->frcnt; pl.frcnt_out = left;
 	pl.n_tiles = n_tiles; pl.n_frag = n_frag; pl.n_segs = n_segs; pl.tail_tile = tail; pl.body_tiles = body_tiles; pl.head_tiles = head_tiles;
 	const uint32_t maxlen = til.maxlen;
@@ -983,8 +1010,18 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 	// bound, one wave per SIMD, registers and LDS to spare) the step is 0.04 - 1.4 % shorter than with the gate in front of it; beside k_kw (HBM-bound,
 	// eight waves per CU) it costs 8 % MORE; behind k_bank it would start exactly when the next k_seg does; the chunks of a host
 	// call are link-bound anyway.
+	// Per-stream lengths: a call with them, or any call once a stream of this view is closed (its end is then 0: untouched).  Such a
+	// call launches the LEN instantiations of the kernels; every other call the dense ones, exactly as before.
+	bool ragged = false;
+	if ((ebu || tp) && (e->len_frames || e->n_closed)) {
+		ragged = e->len_frames != nullptr;
+		for (uint32_t i = 0; !ragged && i < S; ++i) ragged = e->closed[vo + i] != 0;
+	}
 	SegPlan sp;
 	if (ebu || tp) { const PlanCtx pctx = plan_ctx (e); sp = seg_plan (&pctx, d_audio, n_frames, stride); }
+	// (k_seg hands the peak of a closing stream's last segments to k_kwtp16, whose tiles hold at most 64 x 38 frames: a whole
+	// fragment up to 48.6 kHz.  Above that a call with lengths takes k_kwtp16 alone.)
+	if (ragged && sp.use && e->fragm > 64u * (uint32_t) e->run) sp.use = false;
 	const bool only_fused = (e->cfg.meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK)) == 0;
 	// (and a batch of thousands of streams: the gate's serial time grows with the streams, what deferring it costs does not — at 1024 streams x 60 s
 	// the serial order is 0.5 % FASTER, at 8192 x 10 s the deferred one by 0.4 - 1.4 % across boxes)
@@ -999,6 +1036,39 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 		int rc = build_plan (e, n_frames, sp.use ? sp.head : 0, sp.use ? sp.tiles : 0, st);
 		if (rc) return rc;
 		const Plan& pl = e->plan;
+		const uint32_t* d_ends = nullptr;
+		const uint32_t* d_lim = nullptr;
+		const uint32_t* d_from = nullptr;
+		bool any_from = false;
+		LenSlot* ls = nullptr;
+		if (ragged) {
+			const int slot = (e->len_cur + 1) % LEN_SLOTS;
+			ls = &e->len_slot[slot];
+			for (int k = 0; k < 2; ++k) if (ls->pending[k]) { HIPCHK (hipEventSynchronize (ls->done[k])); ls->pending[k] = false; }
+			for (int k = 0; k < 2; ++k) if (!ls->done[k]) HIPCHK (hipEventCreateWithFlags (&ls->done[k], hipEventDisableTiming));
+			if (ls->dev.reserve ((size_t) 3 * S) || ls->pin.reserve ((size_t) 3 * S)) return fail (MTR_ERR_NOMEM, "per-stream lengths");
+			uint32_t* const h_end = ls->pin.p;
+			uint32_t* const h_lim = h_end + S;
+			uint32_t* const h_from = h_end + 2 * (size_t) S;
+			for (uint32_t i = 0; i < S; ++i) {
+				const uint64_t f = e->closed[vo + i] ? 0 : e->len_frames ? e->len_frames[i] : n_frames;
+				h_end[i] = (uint32_t) f;
+				// fragments that end at or before the stream's end
+				const uint32_t nf = (uint32_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
+				h_lim[i] = f == 0 ? MTR_GATE_UNTOUCHED : f < n_frames ? (nf | MTR_GATE_CLOSING) : pl.n_frag;
+				h_from[i] = 0xFFFFFFFFu;
+				if (sp.use && f < n_frames) {
+					// k_seg keeps the peak of every segment that reaches past f - 24 to itself; k_kwtp16 covers them from the first one on
+					for (uint32_t q = 0; q < sp.n_segs; ++q) {
+						const uint64_t fq = (uint64_t) q * sp.base + std::min (q, sp.rem), cq = sp.base + (q < sp.rem ? 1u : 0u);
+						if ((fq + cq) * e->fragm + 24 + sp.head > f) { h_from[i] = pl.head_tiles + (uint32_t) fq; any_from = true; break; }
+					}
+				}
+			}
+			HIPCHK (hipMemcpyAsync (ls->dev.p, ls->pin.p, (size_t) 3 * S * sizeof (uint32_t), hipMemcpyHostToDevice, st));
+			e->len_cur = slot;
+			d_ends = ls->dev.p; d_lim = d_ends + S; d_from = d_ends + 2 * (size_t) S;
+		}
 		mtr_fused_args fa;
 		fa.audio = d_audio; fa.stride = stride;
 		fa.hist = e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2;
@@ -1021,6 +1091,7 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 		fa.rotate = e->layout == 3;
 		fa.prune = e->cfg.tune_prune > 2 ? 2 : (int) e->cfg.tune_prune;
 		fa.prune_stats = e->prune_cnt.p;
+		fa.ends = d_ends; fa.from_tile = nullptr;
 		int lrc = 0;
 		if (sp.use) {
 			// the batch path: whole fragments through k_seg; the rest of an open fragment in front of them and what is left of
@@ -1040,8 +1111,15 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 			sa.screen = e->seg_screen ? 1u : 0u; sa.seg_stats = e->prune_cnt.p + 2;
 			sa.a0 = fa.a0; sa.a1 = fa.a1; sa.a2 = fa.a2; sa.b1 = fa.b1; sa.b2 = fa.b2; sa.c3 = fa.c3; sa.c4 = fa.c4;
 			sa.gain_l = fa.gain_l; sa.gain_r = fa.gain_r;
+			sa.ends = d_ends;
 			const uint64_t units = (uint64_t) S * sp.n_segs;
 			if (!lrc) lrc = mtr_launch_seg (ebu, sa, (uint32_t) ((units + 63) / 64), st);
+			if (!lrc && any_from) {
+				// the peaks k_seg left to k_kwtp16: from each closing stream's first such segment to its end (true peak only)
+				fa.seg_tile = e->head_seg + 1; fa.n_segs = 1; fa.from_tile = d_from;
+				lrc = mtr_launch_kwtp16 (e->run, false, fa, S, st);
+				fa.from_tile = nullptr;
+			}
 			if (!lrc && pl.n_tiles > pl.head_tiles + sp.tiles) {
 				fa.seg_tile = e->tail_seg; fa.n_segs = 1;
 				lrc = mtr_launch_kwtp16 (e->run, ebu, fa, S, st);
@@ -1061,7 +1139,7 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 			// _chan_gain, ebu_r128_proc.cc:29 (L R C Ls Rs)
 			const float gains[MTR_MAX_CHANNELS] = { 1.0f, 1.0f, 1.0f, 1.41f, 1.41f };
 			for (int c = 0; c < MTR_MAX_CHANNELS; ++c) ma.gain[c] = gains[c];
-			lrc = mtr_launch_kwmc ((int) C, ebu, tp, ma, S * pl.n_segs, st);
+			lrc = ragged ? mtr_launch_kwmc_len ((int) C, ebu, tp, ma, d_ends, S * pl.n_segs, st) : mtr_launch_kwmc ((int) C, ebu, tp, ma, S * pl.n_segs, st);
 		} else {
 			lrc = e->layout == 6 ? mtr_launch_kwtp16 (e->run, ebu, fa, S * pl.n_segs, st)
 			    : e->layout == 4 ? mtr_launch_kw (e->run, fa, S * pl.n_segs, st)
@@ -1095,7 +1173,8 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 		ga.max_scratch = e->gate_max.p + vo * 2;
 		ga.fold_tp = (fold_in_history || e->layout == 8) ? 0 : 1;      // (layout 8: k_history_mc folds the per-channel peaks)
 		ga.polite_grid = defer ? e->tail_gate_grid : 0;
-		if (mtr_launch_gate (ga, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
+		if (ragged ? mtr_launch_gate_len (ga, d_lim, gst) : mtr_launch_gate (ga, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
+		if (ls) { HIPCHK (hipEventRecord (ls->done[1], gst)); ls->pending[1] = true; }
 		if (tm) { hipEvent_t v = next_event (e, ev0 + 3); if (v) HIPCHK (hipEventRecord (v, gst)); }
 		{
 			PlanSlot& ps = e->plan_slot[e->plan_cur];                 // k_gate is the plan's last reader
@@ -1174,21 +1253,72 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 		// (deferred: the fold of this call's peaks rides here — behind the reduction of the previous call, which reads the holds)
 		if (fold_in_history && e->red_pending) { HIPCHK (hipStreamWaitEvent (st, e->ev_red, 0)); e->red_pending = false; }
 		const int hrc = e->layout == 8 ? 0 : e->cfg.n_channels == 2
-			? mtr_launch_history (d_audio, stride, n_frames, e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2, e->fir_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * 2, S,
-			                      fold_in_history ? e->state.p + vo : nullptr, st)
+			? (ragged ? mtr_launch_history_len (d_audio, stride, n_frames, e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2, e->fir_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * 2, S,
+			                                    fold_in_history ? e->state.p + vo : nullptr, e->len_slot[e->len_cur].dev.p, st)
+			          : mtr_launch_history (d_audio, stride, n_frames, e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2, e->fir_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * 2, S,
+			                                fold_in_history ? e->state.p + vo : nullptr, st))
 			: mtr_launch_history_mono (d_audio, stride, n_frames, e->fir_hist[e->hist_cur].p + vo * MTR_FIR_HALO * 2, e->fir_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * 2, S, st);
 		if (hrc) return fail (MTR_ERR_HIP, "k_history launch");
 		if (tp && e->layout == 8) {
 			const uint32_t C = e->cfg.n_channels;
-			if (mtr_launch_history_mc (d_audio, stride, n_frames, C, e->mc_hist[e->hist_cur].p + vo * MTR_FIR_HALO * C, e->mc_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * C, S,
-			                           e->mc_tp_call.p + vo * C, e->mc_tp_last.p + vo * C, e->mc_tp_hold.p + vo * C, e->state.p + vo, st))
+			if (ragged ? mtr_launch_history_mc_len (d_audio, stride, n_frames, C, e->mc_hist[e->hist_cur].p + vo * MTR_FIR_HALO * C, e->mc_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * C, S,
+			                                        e->mc_tp_call.p + vo * C, e->mc_tp_last.p + vo * C, e->mc_tp_hold.p + vo * C, e->state.p + vo,
+			                                        e->len_slot[e->len_cur].dev.p, st)
+			           : mtr_launch_history_mc (d_audio, stride, n_frames, C, e->mc_hist[e->hist_cur].p + vo * MTR_FIR_HALO * C, e->mc_hist[e->hist_cur ^ 1].p + vo * MTR_FIR_HALO * C, S,
+			                                    e->mc_tp_call.p + vo * C, e->mc_tp_last.p + vo * C, e->mc_tp_hold.p + vo * C, e->state.p + vo, st))
 				return fail (MTR_ERR_HIP, "k_history_mc launch");
 		}
 		e->hist_cur ^= 1;
 	}
+	if (ragged) {                                                    // (the lengths' last reader on this stream: k_history_len, or the fused kernels)
+		LenSlot& ls = e->len_slot[e->len_cur];
+		HIPCHK (hipEventRecord (ls.done[0], st));
+		ls.pending[0] = true;
+	}
+	// frames metered per stream; a stream that ends inside a call with lengths is closed by it
+	for (uint32_t i = 0; i < S; ++i) {
+		const size_t g = vo + i;
+		if (e->closed[g]) continue;
+		const uint64_t f = e->len_frames ? e->len_frames[i] : n_frames;
+		e->metered[g] += f;
+		if (f < n_frames) { e->closed[g] = 1; e->n_closed++; }
+	}
 	if (tm) {
 		hipEvent_t v = next_event (e, ev0 + 5);
 		if (v) { HIPCHK (hipEventRecord (v, st)); e->timed_calls++; }      // (a call without all of its events is not a timed call)
+	}
+	return MTR_OK;
+}
+
+// Per-stream lengths need EBU / TRUEPEAK alone (every layout, 2 .. 5 channels)
+static int lengths_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
+{
+	if ((e->cfg.meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK)) || !(e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
+		return fail (MTR_ERR_UNSUPPORTED, "per-stream lengths: EBU / TRUEPEAK engines only");
+	for (uint32_t i = 0; i < n; ++i)
+		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "per-stream lengths: frames[s] > n_frames");
+	return MTR_OK;
+}
+
+int mtr_engine_process_device_lengths (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
+                                       const uint64_t* frames, void* hip_stream)
+{
+	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_lengths: null argument");
+	const int crc = lengths_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	e->len_frames = frames;
+	const int rc = mtr_engine_process_device (e, d_audio, n_frames, stride, hip_stream);
+	e->len_frames = nullptr;
+	return rc;
+}
+
+int mtr_engine_stream_frames (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* frames, uint8_t* closed)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
+	for (uint32_t i = 0; i < count; ++i) {
+		if (frames) frames[i] = e->metered[first + i];
+		if (closed) closed[i] = e->closed[first + i];
 	}
 	return MTR_OK;
 }
@@ -1229,9 +1359,8 @@ int mtr_engine_set_host_chunk_bytes (mtr_engine* e, uint64_t bytes)
 // chunk k + 1 crosses the host link on a copy stream while the kernels of chunk k run on the engine's own; two device
 // buffers of one chunk each instead of a copy of the whole batch.  End to end the call runs at the link's rate
 // (bench.py: extra.end_to_end_host).
-int mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride)
+static int process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
-	if (!e || !h_audio) return fail (MTR_ERR_ARG, "mtr_engine_process_host: null argument");
 	if (n_frames == 0) return MTR_OK;
 	if (stride < n_frames) return fail (MTR_ERR_ARG, "stream_stride_frames < n_frames");
 	HIPCHK (hipSetDevice (e->cfg.device));
@@ -1270,7 +1399,9 @@ int mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_fra
 		                           n_frames * C * sizeof (float), cnt, hipMemcpyHostToDevice, e->copy_stream));
 		HOSTCHK (hipEventRecord (e->ev_copied[b], e->copy_stream));
 		HOSTCHK (hipStreamWaitEvent (st, e->ev_copied[b], 0));
+		e->len_frames = frames ? frames + off : nullptr;              // (the lengths of the chunk's streams: indexed from its first)
 		rc = process_view (e, dst, n_frames, dstride, st, off, cnt, k + 1 == n_chunks);
+		e->len_frames = nullptr;
 		if (rc) goto done;
 		HOSTCHK (hipEventRecord (e->ev_computed[b], st));
 	}
@@ -1284,6 +1415,20 @@ done:
 		if (hs != hipSuccess) return fail (MTR_ERR_HIP, "hipStreamSynchronize (copy stream)", hs);
 	}
 	return MTR_OK;
+}
+
+int mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride)
+{
+	if (!e || !h_audio) return fail (MTR_ERR_ARG, "mtr_engine_process_host: null argument");
+	return process_host (e, h_audio, n_frames, stride, nullptr);
+}
+
+int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_lengths: null argument");
+	const int crc = lengths_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_host (e, h_audio, n_frames, stride, frames);
 }
 
 // One LV2 block: interleave into page-locked memory, one H2D copy, the kernels, one D2H copy of the stream's state
@@ -1900,6 +2045,10 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	for (const StateSection& s : state_sections (e)) {
 		if (h.count) HIPCHK (hipMemcpy (const_cast<unsigned char*> (static_cast<const unsigned char*> (s.base)) + (size_t) first * s.elem, i, (size_t) h.count * s.elem, hipMemcpyHostToDevice));
 		i += (size_t) h.count * s.elem;
+	}
+	for (uint32_t k = 0; k < h.count; ++k) {                     // (an imported stream is open — closure is not part of the blob — and
+		if (e->closed[first + k]) { e->closed[first + k] = 0; e->n_closed--; }   // its count starts again: the blob does not carry one)
+		e->metered[first + k] = 0;
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->frcnt = h.frcnt; e->integr = h.integr != 0; e->omega = h.omega; e->dr_scnt = h.dr_scnt;

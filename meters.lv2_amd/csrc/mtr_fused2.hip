@@ -188,7 +188,12 @@ __device__ __forceinline__ void fir_sym (const v2f* xs, int nvalid, float& pk_l,
 	}
 }
 
-template <int K, int R, bool EBU, bool TP, bool SYM, bool ROT>
+// LEN: the call carries per-stream lengths (a.ends, mtr_engine_process_*_lengths).  Frames at or past stream s's end E are staged as
+// +0.0f (the tile that holds E takes the plain staging path, which issues no load for them), only outputs m < E count towards the peak
+// (the masked epilogue), a segment that starts at or past E does nothing — its whole workgroup leaves before the first barrier — and
+// the tiles behind E run on zeros (the role loops keep their common trip count).  The dense instantiation (LEN false) is the kernel's
+// code as it always was.
+template <int K, int R, bool EBU, bool TP, bool SYM, bool ROT, bool LEN>
 __global__ __launch_bounds__ (TP ? 256 : 64) void k_fused2 (const mtr_fused_args a)
 {
 	static_assert (K == 3 * R && (K & 1) == 1, "three FIR waves x R outputs per lane run; odd lane stride");
@@ -216,6 +221,10 @@ __global__ __launch_bounds__ (TP ? 256 : 64) void k_fused2 (const mtr_fused_args
 	const int nwarm = (EBU && q > 0) ? (int) a.warm_tiles : 0;
 	const int ntile = (int) (jt1 - jt0);
 	constexpr int LT = 64 * K;
+	// the stream's end in this call (N_END: an expression, so that the dense instantiation reads a.n_frames where it always did)
+	const int64_t n_end_ = LEN ? min ((int64_t) a.ends[s], (int64_t) a.n_frames) : 0;
+#define N_END (LEN ? n_end_ : (int64_t) a.n_frames)
+	if (LEN && seg_start >= N_END) return;                         // (workgroup-uniform: every wave leaves)
 
 	// tile jj -> (first frame, length); warm-up tiles are full tiles before the segment
 	auto tile_of = [&] (int jj, int64_t& t0, int& len) {
@@ -231,7 +240,7 @@ __global__ __launch_bounds__ (TP ? 256 : 64) void k_fused2 (const mtr_fused_args
 		// 16-byte pairs need an even first frame; the one tile that ends on an odd final frame of the
 		// call cannot fetch that frame as half of a pair without reading past the stream: plain path.
 		const bool tail_odd = (t0 + len + R >= (int64_t) a.n_frames) && (a.n_frames & 1);
-		if (t0 >= 48 && src_even && ((t0 & 1) == 0) && !tail_odd) {
+		if (t0 >= 48 && src_even && ((t0 & 1) == 0) && !tail_odd && !(LEN && t0 - 48 + nslot > N_END)) {
 			// LDS-DMA, 16 bytes (two frames) per lane per instruction, 1 KiB per wave-instruction.
 			// Source addresses past the end of the call are clamped (those slots are never consumed).
 			const int64_t fmax = (int64_t) a.n_frames - 2;
@@ -246,7 +255,7 @@ __global__ __launch_bounds__ (TP ? 256 : 64) void k_fused2 (const mtr_fused_args
 			for (int i = lane; i < nslot; i += 64) {
 				const int64_t f = t0 - 48 + i;
 				v2f v = 0;
-				if (f >= 0) v = src[f < (int64_t) a.n_frames ? f : (int64_t) a.n_frames - 1];
+				if (f >= 0) { if (!LEN || f < N_END) v = src[f < (int64_t) a.n_frames ? f : (int64_t) a.n_frames - 1]; }
 				else if (f >= -MTR_FIR_HALO) v = hist[MTR_FIR_HALO + f];
 				buf[i] = v;
 			}
@@ -330,10 +339,12 @@ __global__ __launch_bounds__ (TP ? 256 : 64) void k_fused2 (const mtr_fused_args
 	auto fir_tile = [&] (const v2f* cur, int jj, int w, float& pk_l, float& pk_r) {
 		const int m0 = lane * K + R * w;
 		const int len = (int) (a.tile_start[jt0 + jj + 1] - a.tile_start[jt0 + jj]);
-		const int rlw = min (max (len - m0, 0), R);        // valid outputs of this lane's register tile
+		// (LEN: the tile's outputs in front of the stream's end; a tile it cuts takes the masked epilogue)
+		const int plen_ = LEN ? (int) min ((int64_t) len, max (N_END - (int64_t) a.tile_start[jt0 + jj], (int64_t) 0)) : 0;
+		const int rlw = min (max ((LEN ? plen_ : len) - m0, 0), R);        // valid outputs of this lane's register tile
 		if (rlw <= 0) return;
 		if (SYM) {
-			if (a.tile_start[jt0 + jj + 1] == (uint32_t) a.n_frames) {
+			if (a.tile_start[jt0 + jj + 1] == (uint32_t) a.n_frames || (LEN && plen_ < len)) {
 				// last tile of the call: frames past its end do not exist yet
 				fir_sym<7, true> (cur + m0, min (rlw, 7), pk_l, pk_r);
 				if (rlw > 7) fir_sym<6, true> (cur + m0 + 7, rlw - 7, pk_l, pk_r);
@@ -485,25 +496,32 @@ __global__ __launch_bounds__ (TP ? 256 : 64) void k_fused2 (const mtr_fused_args
 			atomicMax (&st->tp_call[1], __float_as_uint (pk_r));
 		}
 	}
+#undef N_END
 }
 
-template <int K, int R, bool SYM, bool ROT>
-static int launch2 (bool ebu, bool tp, const mtr_fused_args& a, uint32_t n_units, hipStream_t st)
+template <int K, int R, bool SYM, bool ROT, bool LEN>
+static int launch2_len (bool ebu, bool tp, const mtr_fused_args& a, uint32_t n_units, hipStream_t st)
 {
 	const size_t lds = (size_t) 2 * a.buf_slots * sizeof (v2f);
 	const dim3 grid (n_units);
 	static bool raised = false;
 	if (!raised) {
 		const int mx = 160 * 1024;
-		(void) hipFuncSetAttribute ((const void*) k_fused2<K, R, true, true, SYM, ROT>,  hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-		(void) hipFuncSetAttribute ((const void*) k_fused2<K, R, true, false, SYM, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-		(void) hipFuncSetAttribute ((const void*) k_fused2<K, R, false, true, SYM, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+		(void) hipFuncSetAttribute ((const void*) k_fused2<K, R, true, true, SYM, ROT, LEN>,  hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+		(void) hipFuncSetAttribute ((const void*) k_fused2<K, R, true, false, SYM, ROT, LEN>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+		(void) hipFuncSetAttribute ((const void*) k_fused2<K, R, false, true, SYM, ROT, LEN>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
 		raised = true;
 	}
-	if (ebu && tp)  hipLaunchKernelGGL ((k_fused2<K, R, true, true, SYM, ROT>),  grid, dim3 (256), lds, st, a);
-	else if (ebu)   hipLaunchKernelGGL ((k_fused2<K, R, true, false, SYM, ROT>), grid, dim3 (64),  lds, st, a);
-	else            hipLaunchKernelGGL ((k_fused2<K, R, false, true, SYM, ROT>), grid, dim3 (256), lds, st, a);
+	if (ebu && tp)  hipLaunchKernelGGL ((k_fused2<K, R, true, true, SYM, ROT, LEN>),  grid, dim3 (256), lds, st, a);
+	else if (ebu)   hipLaunchKernelGGL ((k_fused2<K, R, true, false, SYM, ROT, LEN>), grid, dim3 (64),  lds, st, a);
+	else            hipLaunchKernelGGL ((k_fused2<K, R, false, true, SYM, ROT, LEN>), grid, dim3 (256), lds, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+template <int K, int R, bool SYM, bool ROT>
+static int launch2 (bool ebu, bool tp, const mtr_fused_args& a, uint32_t n_units, hipStream_t st)
+{
+	return a.ends ? launch2_len<K, R, SYM, ROT, true> (ebu, tp, a, n_units, st) : launch2_len<K, R, SYM, ROT, false> (ebu, tp, a, n_units, st);
 }
 
 int mtr_launch_fused2 (int run, bool ebu, bool tp, const mtr_fused_args& a, uint32_t n_units, void* stream)

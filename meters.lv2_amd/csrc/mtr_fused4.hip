@@ -62,7 +62,13 @@ __device__ __forceinline__ void pow2_scale (uint32_t e_, float& scale, float& un
 	unscale = __uint_as_float ((uint32_t) (239 - se) << 23);      // 2^-(se - 127) * 2^-15
 }
 
-template <int K, bool EBU>
+// LEN: the call carries per-stream lengths (a.ends, mtr_engine_process_*_lengths).  Stream s ends at frame E = ends [s] of this call:
+// frames at or past E are read as +0.0f before they reach the scale, the K-filter or the interpolator's window (a NaN there would
+// turn in-range columns into NaN through the zero taps of the block-Toeplitz product), only the columns t < E count towards the
+// peak (phase 0 of the last 24 frames included: never, as p0 of a call's end), a segment that starts at or past E does nothing,
+// and a.from_tile (if set) moves the segment's first tile to from_tile [s].  Tile powers past E are computed from zeros and feed
+// fragments the gate never inserts for the stream.  The dense instantiation (LEN false) is the kernel's code as it always was.
+template <int K, bool EBU, bool LEN>
 __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 {
 	static_assert ((K & 1) == 0, "even runs: sample pairs never straddle two lanes");
@@ -86,12 +92,18 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 	asm volatile ("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(b1), "+v"(b2), "+v"(c3), "+v"(c4));
 	const v2f eps2 = v2f{1e-15f, 1e-15f};
 
-	const uint32_t jt0 = a.seg_tile[q], jt1 = a.seg_tile[q + 1];
+	const uint32_t jt0 = (LEN && a.from_tile) ? max (a.seg_tile[q], a.from_tile[s]) : a.seg_tile[q], jt1 = a.seg_tile[q + 1];
+	// the stream's end in this call.  (N_END and PLEN below are expressions, not variables: the dense instantiation then reads
+	// a.n_frames and len where it always did, and compiles to the code it always was — an alias alone moves its registers.)
+	const int64_t n_end_ = LEN ? min ((int64_t) a.ends[s], (int64_t) a.n_frames) : 0;
+#define N_END (LEN ? n_end_ : (int64_t) a.n_frames)
+	if (LEN && jt0 >= jt1) return;
 	const int64_t seg_start = a.tile_start[jt0];
+	if (LEN && seg_start >= N_END) return;                             // (wholly past the stream's end: no loads, no products, no writes)
 	const int nwarm = (q > 0) ? (int) a.warm_tiles : 0;
 	const int ntile = (int) (jt1 - jt0);
 	constexpr int LT = 64 * K;
-	const int64_t id_end = (int64_t) a.n_frames - 24;                  // phase 0 of this call ends with frame n_frames - 25
+	const int64_t id_end = N_END - 24;                                 // phase 0 of this call ends with frame n_frames - 25
 
 	auto tile_of = [&] (int jj, int64_t& t0, int& len) {
 		if (jj < 0) { t0 = seg_start + (int64_t) jj * LT; len = LT; }
@@ -106,7 +118,7 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 	// tile are masked and no valid output's window reaches them; scale: lanes past the tile are left out).
 	const v2f* const hst = reinterpret_cast<const v2f*> (a.hist) + (size_t) s * MTR_FIR_HALO;
 	auto frame_at = [&] (int64_t f) -> v2f {                             // call-relative frame, history in front of frame 0
-		if (f >= 0) return src[f];
+		if (f >= 0) return (!LEN || f < N_END) ? src[f] : v2f{0.f, 0.f};
 		if (f >= -MTR_FIR_HALO && q == 0) return hst[f + MTR_FIR_HALO];
 		return v2f{0.f, 0.f};
 	};
@@ -114,13 +126,13 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 		int64_t t0; int len;
 		tile_of (jj, t0, len);
 		const int64_t base = t0 + (int64_t) K * lane;
-		if (src_even && !(t0 & 1) && t0 + (int64_t) LT <= (int64_t) a.n_frames) {
+		if (src_even && !(t0 & 1) && t0 + (int64_t) LT <= N_END) {
 			const float4* const p4 = reinterpret_cast<const float4*> (src + base);
 #pragma unroll
 			for (int i = 0; i < K / 2; ++i) { const float4 v = p4[i]; xn[2 * i] = v2f{v.x, v.y}; xn[2 * i + 1] = v2f{v.z, v.w}; }
 		} else {
 #pragma unroll
-			for (int n = 0; n < K; ++n) xn[n] = base + n < (int64_t) a.n_frames ? src[base + n] : v2f{0.f, 0.f};
+			for (int n = 0; n < K; ++n) xn[n] = base + n < N_END ? src[base + n] : v2f{0.f, 0.f};
 		}
 		g0 = v2f{0.f, 0.f}; g1 = v2f{0.f, 0.f};
 		if (lane < HALO / 2) { g0 = frame_at (t0 - HALO + 2 * lane); g1 = frame_at (t0 - HALO + 2 * lane + 1); }
@@ -155,6 +167,7 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 	for (int jj = -nwarm; jj < ntile; ++jj) {
 		int64_t t0; int len;
 		tile_of (jj, t0, len);
+		if (LEN && t0 >= N_END) break;                                 // (the stream has ended: nothing of it is left in this segment)
 
 		PROF_NOW (c0_);
 		asm volatile ("s_waitcnt vmcnt(0)" ::: "memory");      // this tile has landed in the run registers
@@ -195,7 +208,7 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 				// positions 24..47 <-> frames t0 - 24 .. t0 - 1; position p counts while frame t0 + p - 48 < n_frames - 24 (t0 = 0
 				// unless this launch finishes a call behind the lane = segment kernel: a tail shorter than 24 frames leaves
 				// the last frames in front of it to the next call, as k_seg's p0_end does — ADVICE r3)
-				const int64_t plim = (int64_t) a.n_frames + 24 - t0;
+				const int64_t plim = N_END + 24 - t0;
 				if (2 * lane < plim)     { il = fmaxf (il, fabsf (ph0.x)); ir = fmaxf (ir, fabsf (ph0.y)); }
 				if (2 * lane + 1 < plim) { il = fmaxf (il, fabsf (ph1.x)); ir = fmaxf (ir, fabsf (ph1.y)); }
 			}
@@ -206,7 +219,10 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 		// Exact peak pruning (a.prune): |y| <= L1 * max |x| over the window, 2.5684 = the largest L1 norm of the taps;
 		// a channel whose bound cannot beat its peak so far needs no products (the result is unchanged bit for bit).
 		// Only this option needs the maxima and the peaks so far wave-wide, per tile.
-		bool need_l = jj >= 0, need_r = jj >= 0;
+		// LEN: the tile's columns in front of the stream's end (all of them on an open stream); none: no products
+		const int plen_ = LEN ? (int) min ((int64_t) len, max (n_end_ - t0, (int64_t) 0)) : 0;
+#define PLEN (LEN ? plen_ : len)
+		bool need_l = jj >= 0 && (!LEN || plen_ > 0), need_r = jj >= 0 && (!LEN || plen_ > 0);
 		float tml = 0.f, tmr = 0.f, run_l = 0.f, run_r = 0.f;
 		if (a.prune && jj >= 0) {
 			tml = mtrw::max63 (fmaxf (inside ? ml : 0.f, hl)); tmr = mtrw::max63 (fmaxf (inside ? mr : 0.f, hr));
@@ -299,7 +315,7 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 			__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
 			asm volatile ("s_waitcnt lgkmcnt(0)" ::: "memory");            // the words of every lane are in LDS
 			float pl = 0.f, pr = 0.f;
-			const int nfull = len >> 8;                                      // blocks whose 256 outputs all belong to the tile
+			const int nfull = PLEN >> 8;                                      // blocks whose 256 outputs all belong to the tile
 			const int fo = 2 * col8 + kg4;                                   // + r: output frame of register r inside its block
 			m16::BFrag bl, br;
 			m16::f4 yl[3], yr[3];
@@ -315,10 +331,10 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 				const float k15 = (float) (1 << MTR_M16_TAP_SHIFT);
 				const float thr_l = run_l * sc_l * k15 - (2.5684f * 1.05f / 1024.f) * k15 * (tml * sc_l);
 				const float thr_r = run_r * sc_r * k15 - (2.5684f * 1.05f / 1024.f) * k15 * (tmr * sc_r);
-				const int nb = (len + 255) >> 8;
+				const int nb = (PLEN + 255) >> 8;
 				for (int b = 0; b < nb; ++b) {
 					const int w = min (128 * b + col8, 8 * CMAX) + kg4;
-					const int lim = len - 256 * b - fo;                          // registers r < lim are outputs of this tile
+					const int lim = PLEN - 256 * b - fo;                          // registers r < lim are outputs of this tile
 					bl.h0 = *reinterpret_cast<const uint4*> (HL + w); bl.h1 = *reinterpret_cast<const uint4*> (HL + w + 16);
 					br.h0 = *reinterpret_cast<const uint4*> (HR + w); br.h1 = *reinterpret_cast<const uint4*> (HR + w + 16);
 					m16::block_first (A, bl.h0, bl.h1, yl);
@@ -378,7 +394,7 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 			}
 #pragma unroll
 			for (int p = 0; p < 3; ++p) { pr = max3abs (pr, yr[p][0], yr[p][1]); pr = max3abs (pr, yr[p][2], yr[p][3]); }
-			if ((len & 255) && (len & 255) <= 128) {
+			if ((PLEN & 255) && (PLEN & 255) <= 128) {
 				// the tile's last block holds at most eight columns per channel (48 kHz: 2400 = 9 x 256 + 96): both channels
 				// share ONE block — columns 0..7 read the left arrays, columns 8..15 the right ones, at the same positions
 				const bool rside = (lane & 8) != 0;
@@ -386,7 +402,7 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 				const int wm = min (128 * nfull + cc8, 8 * CMAX) + kg4;
 				m16::fetch_b (br, rside ? HR : HL, rside ? LR : LL, wm);
 				m16::block (A, br, yr);
-				const int lim = len - 256 * nfull - (2 * cc8 + kg4);         // registers r < lim are outputs of this tile
+				const int lim = PLEN - 256 * nfull - (2 * cc8 + kg4);         // registers r < lim are outputs of this tile
 				float pm = 0.f;
 #pragma unroll
 				for (int p = 0; p < 3; ++p)
@@ -394,13 +410,13 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 					for (int r = 0; r < 4; ++r) pm = fmaxf (pm, r < lim ? fabsf (yr[p][r]) : 0.f);
 				pl = fmaxf (pl, rside ? 0.f : pm);
 				pr = fmaxf (pr, rside ? pm : 0.f);
-			} else if (len & 255) {
+			} else if (PLEN & 255) {
 				// the tile's last block: frames past its end belong to the next tile (or do not exist yet)
 				m16::fetch_b (br, HR, LR, wlast);
 				m16::block (A, bl, yl);
 				m16::block (A, br, yr);
-				const int lim = len - 256 * nfull - fo;                      // registers r < lim are outputs of this tile
-				if ((len & 3) == 0) {
+				const int lim = PLEN - 256 * nfull - fo;                      // registers r < lim are outputs of this tile
+				if ((PLEN & 3) == 0) {
 					// a lane's four registers are all in or all out: one branch on the lane mask, no per-register tests
 					if (lim > 0) {
 #pragma unroll
@@ -443,6 +459,8 @@ __global__ __launch_bounds__ (64, 2) void k_kwtp16 (const mtr_fused_args a)
 		atomicAdd (&a.prune_stats[2], n_blk);
 		atomicAdd (&a.prune_stats[3], n_fin);
 	}
+#undef PLEN
+#undef N_END
 	pk_l = mtrw::max63 (pk_l);
 	pk_r = mtrw::max63 (pk_r);
 	if (lane == 0) {
@@ -455,8 +473,11 @@ template <int K>
 int launch_kwtp16 (bool ebu, const mtr_fused_args& a, uint32_t n_units, hipStream_t st)
 {
 	const size_t lds = ((size_t) 4 * ((HALO + 64 * K) / 2) * sizeof (uint32_t) + 15) & ~(size_t) 15;
-	if (ebu) hipLaunchKernelGGL ((k_kwtp16<K, true>), dim3 (n_units), dim3 (64), lds, st, a);
-	else     hipLaunchKernelGGL ((k_kwtp16<K, false>), dim3 (n_units), dim3 (64), lds, st, a);
+	if (a.ends) {
+		if (ebu) hipLaunchKernelGGL ((k_kwtp16<K, true, true>), dim3 (n_units), dim3 (64), lds, st, a);
+		else     hipLaunchKernelGGL ((k_kwtp16<K, false, true>), dim3 (n_units), dim3 (64), lds, st, a);
+	} else if (ebu) hipLaunchKernelGGL ((k_kwtp16<K, true, false>), dim3 (n_units), dim3 (64), lds, st, a);
+	else            hipLaunchKernelGGL ((k_kwtp16<K, false, false>), dim3 (n_units), dim3 (64), lds, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -484,6 +505,32 @@ __global__ void k_history (const float* audio, uint64_t stride, uint64_t n_frame
 	v2f* hout = reinterpret_cast<v2f*> (hist_out) + (size_t) s * MTR_FIR_HALO;
 	hout[i] = (f >= 0) ? src[f] : hin[MTR_FIR_HALO + f];
 	if (fold_state && i == 0) mtr_fold_truepeak (fold_state + s);
+}
+
+// The same for a call with per-stream lengths: a stream the call does not touch (ends [s] == 0) keeps its history bit for bit
+// (the buffers ping-pong) and is not folded.  A stream that closes keeps whatever follows its end: nothing reads it again.
+__global__ void k_history_len (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
+                               float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= n_streams * MTR_FIR_HALO) return;
+	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
+	const bool touched = ends[s] != 0;
+	const int64_t f = touched ? (int64_t) n_frames - MTR_FIR_HALO + i : (int64_t) i - MTR_FIR_HALO;
+	const v2f* src = reinterpret_cast<const v2f*> (audio) + (size_t) s * stride;
+	const v2f* hin = reinterpret_cast<const v2f*> (hist_in) + (size_t) s * MTR_FIR_HALO;
+	v2f* hout = reinterpret_cast<v2f*> (hist_out) + (size_t) s * MTR_FIR_HALO;
+	hout[i] = (f >= 0) ? src[f] : hin[MTR_FIR_HALO + f];
+	if (fold_state && touched && i == 0) mtr_fold_truepeak (fold_state + s);
+}
+
+int mtr_launch_history_len (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
+                            uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream)
+{
+	const uint32_t n = n_streams * MTR_FIR_HALO;
+	hipLaunchKernelGGL (k_history_len, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
+	                    audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state, ends);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 int mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,

@@ -19,9 +19,19 @@
 //     occupied bins in the reference's order so that the float accumulation of integrate() is the reference's.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mtr_internal.h"
 
 #define CHUNK 256
+
+// the kernel arguments of a gate kernel: the dense instantiation's are the struct it always took
+template <bool LEN> using gate_args_t = std::conditional_t<LEN, mtr_gate_len_args, mtr_gate_args>;
+template <bool LEN> __device__ __forceinline__ uint32_t gate_lim (const gate_args_t<LEN>& a, uint32_t s)
+{
+	if constexpr (LEN) return a.frag_lim[s];
+	else return 0u;
+}
 
 __device__ __forceinline__ float log10f_cr (float x) { return (float) log10 ((double) x); }
 __device__ __forceinline__ float divf_cr (float a, float b) { return (float) ((double) a / (double) b); }
@@ -135,7 +145,12 @@ __device__ __forceinline__ void hist_add (int32_t* h, int32_t* count, int32_t* e
 	atomicAdd (count, 1);
 }
 
-__global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
+// LEN (per-stream lengths, a.frag_lim): stream s inserts only the first frag_lim [s] fragments of the call — those that end at or
+// before its end — f_calc and the values a getter sees follow from that count; a stream the call closes does not carry its open
+// fragment, and an untouched one (MTR_GATE_UNTOUCHED) is left as it is, fold included.  The dense instantiation is the kernel as
+// it always was.
+template <bool LEN>
+__global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[64 + CHUNK];          // chronological fragment powers: 64 history + chunk
@@ -147,6 +162,15 @@ __global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
 	// (a workgroup walks streams blockIdx.x, blockIdx.x + gridDim.x, ...: one each when the grid is the batch — the serial
 	// order — sixteen each in the deferred tail's 512-workgroup launch, see mtr_launch_gate)
 	for (uint32_t s = blockIdx.x; s < a.n_streams; s += gridDim.x) {
+	uint32_t n_frag_s = 0;
+	bool carry = true;
+	if constexpr (LEN) {
+		const uint32_t lim = a.frag_lim[s];
+		if (lim == MTR_GATE_UNTOUCHED) continue;                    // (workgroup-uniform)
+		n_frag_s = min (a.n_frag, lim & ~MTR_GATE_CLOSING);
+		carry = !(lim & MTR_GATE_CLOSING);
+	}
+#define NFRAG (LEN ? n_frag_s : a.n_frag)      /* (the dense instantiation reads a.n_frag where it always did) */
 	mtr_stream_state* const st = a.state + s;
 	const float* const tp = a.tile_power + (size_t) s * a.n_tiles;
 	int32_t* const ghist = a.hist + (size_t) s * 2 * MTR_HIST_LEN;
@@ -164,14 +188,14 @@ __global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
 	// Index (within this call) of the last fragment at which _div2 wraps: calc_* run there.
 	// _div2 after fragment f (0-based) is (div2_0 + f + 1) mod 10.
 	int f_calc = -1;
-	if (a.integr && a.n_frag > 0) {
-		const int r = (div2_0 + (int) a.n_frag) % 10;      // value after the last fragment
-		const int f = (int) a.n_frag - 1 - r;
+	if (a.integr && NFRAG > 0) {
+		const int r = (div2_0 + (int) NFRAG) % 10;      // value after the last fragment
+		const int f = (int) NFRAG - 1 - r;
 		if (f >= 0) f_calc = f;
 	}
 
-	for (uint32_t base = 0; base < a.n_frag; base += CHUNK) {
-		const int nf = min ((int) (a.n_frag - base), CHUNK);
+	for (uint32_t base = 0; base < NFRAG; base += CHUNK) {
+		const int nf = min ((int) (NFRAG - base), CHUNK);
 		// fragment mean powers of this chunk
 		if (tid < nf) {
 			const uint32_t f = base + tid;
@@ -213,7 +237,7 @@ __global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
 		if (tid < nf) {                              // max-hold is order-free: per-lane, folded once at the end
 			max_M = lm > max_M ? lm : max_M;
 			max_S = ls > max_S ? ls : max_S;
-			if (f_abs == (int) a.n_frag - 1) { sh_red[0][0] = lm; sh_red[1][0] = ls; }   // the values a getter sees
+			if (f_abs == (int) NFRAG - 1) { sh_red[0][0] = lm; sh_red[1][0] = ls; }   // the values a getter sees
 		}
 		__syncthreads ();
 		// slide the power window: keep the newest 64 as history for the next chunk
@@ -225,7 +249,7 @@ __global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
 	}
 
 	// fold the per-lane maxima
-	if (a.n_frag > 0) { last_M = sh_red[0][0]; last_S = sh_red[1][0]; }
+	if (NFRAG > 0) { last_M = sh_red[0][0]; last_S = sh_red[1][0]; }
 	__syncthreads ();
 	sh_red[0][tid] = max_M; sh_red[1][tid] = max_S;
 	__syncthreads ();
@@ -239,13 +263,13 @@ __global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
 	max_M = sh_red[0][0]; max_S = sh_red[1][0];
 	// tiles of the still-open fragment: partial power carried to the next call
 	if (tid == 0) {
-		float acc = (a.n_frag == 0) ? frpwr0 : 1e-30f;
+		float acc = (NFRAG == 0) ? frpwr0 : 1e-30f;
 		for (uint32_t j = a.tail_tile; j < a.n_tiles; ++j) acc += tp[j];
-		st->frpwr = acc;
+		if (!LEN || carry) st->frpwr = acc;
 		st->loud_M = last_M; st->loud_S = last_S;
 		st->max_M = max_M;   st->max_S = max_S;
-		st->div1 = a.integr ? (div1_0 + (int) a.n_frag) % 2 : div1_0;
-		st->div2 = a.integr ? (div2_0 + (int) a.n_frag) % 10 : div2_0;
+		st->div1 = a.integr ? (div1_0 + (int) NFRAG) % 2 : div1_0;
+		st->div2 = a.integr ? (div2_0 + (int) NFRAG) % 10 : div2_0;
 		st->cnt_M = sh_cnt[0]; st->cnt_S = sh_cnt[1]; st->err_M = sh_cnt[2]; st->err_S = sh_cnt[3];
 		// true-peak hold (a deferred gate runs beside the next call's fused kernel, which is already raising tp_call:
 		// then k_history has folded it on the caller's stream — mtr_fold_truepeak, mtr_internal.h)
@@ -253,6 +277,7 @@ __global__ __launch_bounds__ (256) void k_gate (const mtr_gate_args a)
 	}
 	for (int i = tid; i < 64; i += 256) st->ring[i] = pw[i];
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) ghist[i] = (&sh_hist[0][0])[i];
+#undef NFRAG
 	}
 }
 
@@ -282,15 +307,16 @@ __device__ __forceinline__ float frag_power_of (const mtr_gate_args& a, const mt
 	return divf_cr (acc, a.fragm);
 }
 
-__device__ __forceinline__ int gate_f_calc (const mtr_gate_args& a, int div2_0)
+__device__ __forceinline__ int gate_f_calc (const mtr_gate_args& a, int div2_0, uint32_t n_frag)
 {
-	if (!a.integr || a.n_frag == 0) return -1;
-	const int r = (div2_0 + (int) a.n_frag) % 10;          // _div2 after the last fragment
-	const int f = (int) a.n_frag - 1 - r;
+	if (!a.integr || n_frag == 0) return -1;
+	const int r = (div2_0 + (int) n_frag) % 10;            // _div2 after the last fragment
+	const int f = (int) n_frag - 1 - r;
 	return f >= 0 ? f : -1;
 }
 
-__global__ __launch_bounds__ (256) void k_gate_frag (const mtr_gate_args a)
+template <bool LEN>
+__global__ __launch_bounds__ (256) void k_gate_frag (const gate_args_t<LEN> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[64 + GATE_FPB];
@@ -298,13 +324,16 @@ __global__ __launch_bounds__ (256) void k_gate_frag (const mtr_gate_args a)
 	__shared__ int32_t sh_cnt[4];
 	const uint32_t s = blockIdx.y;
 	const int tid = threadIdx.x;
+	const uint32_t lim = gate_lim<LEN> (a, s);
+	if (LEN && lim == MTR_GATE_UNTOUCHED) return;
+	const uint32_t n_frag = LEN ? min (a.n_frag, lim & ~MTR_GATE_CLOSING) : a.n_frag;
 	const int f0 = (int) blockIdx.x * GATE_FPB;
-	const int nf = min ((int) a.n_frag - f0, GATE_FPB);
+	const int nf = min ((int) n_frag - f0, GATE_FPB);
 	if (nf <= 0) return;
 	mtr_stream_state* const st = a.state + s;
 	const float* const tp = a.tile_power + (size_t) s * a.n_tiles;
 	const int div1_0 = st->div1, div2_0 = st->div2;
-	const int f_calc = gate_f_calc (a, div2_0);
+	const int f_calc = gate_f_calc (a, div2_0, n_frag);
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) (&sh_hist[0][0])[i] = 0;
 	if (tid < 4) sh_cnt[tid] = 0;
 	for (int i = tid; i < 64 + nf; i += 256) {
@@ -349,7 +378,8 @@ __global__ __launch_bounds__ (256) void k_gate_frag (const mtr_gate_args a)
 	}
 }
 
-__global__ __launch_bounds__ (256) void k_gate_final (const mtr_gate_args a)
+template <bool LEN>
+__global__ __launch_bounds__ (256) void k_gate_final (const gate_args_t<LEN> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[192];                 // powers of fragments n_frag - 192 .. n_frag - 1, chronological
@@ -357,12 +387,16 @@ __global__ __launch_bounds__ (256) void k_gate_final (const mtr_gate_args a)
 	__shared__ int32_t sh_cnt[4];
 	const uint32_t s = blockIdx.x;
 	const int tid = threadIdx.x;
+	const uint32_t lim = gate_lim<LEN> (a, s);
+	if (LEN && lim == MTR_GATE_UNTOUCHED) return;
+	const uint32_t n_frag = LEN ? min (a.n_frag, lim & ~MTR_GATE_CLOSING) : a.n_frag;
+	const bool carry = !LEN || !(lim & MTR_GATE_CLOSING);
 	mtr_stream_state* const st = a.state + s;
 	const float* const tp = a.tile_power + (size_t) s * a.n_tiles;
 	int32_t* const ghist = a.hist + (size_t) s * 2 * MTR_HIST_LEN;
-	const int n = (int) a.n_frag;
+	const int n = (int) n_frag;
 	const int div1_0 = st->div1, div2_0 = st->div2;
-	const int f_calc = gate_f_calc (a, div2_0);
+	const int f_calc = gate_f_calc (a, div2_0, n_frag);
 	if (tid < 192) pw[tid] = frag_power_of (a, st, tp, n - 192 + tid);
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) (&sh_hist[0][0])[i] = ghist[i];
 	if (tid < 4) sh_cnt[tid] = (tid == 0) ? st->cnt_M : (tid == 1) ? st->cnt_S : (tid == 2) ? st->err_M : st->err_S;
@@ -397,7 +431,7 @@ __global__ __launch_bounds__ (256) void k_gate_final (const mtr_gate_args a)
 		a.max_scratch[2 * s + 1] = sortable (-INFINITY);
 		float acc = (n == 0) ? st->frpwr : 1e-30f;
 		for (uint32_t j = a.tail_tile; j < a.n_tiles; ++j) acc += tp[j];
-		st->frpwr = acc;
+		if (carry) st->frpwr = acc;
 		st->loud_M = last_M; st->loud_S = last_S;
 		st->max_M = max_M;   st->max_S = max_S;
 		st->div1 = a.integr ? (div1_0 + n) % 2 : div1_0;
@@ -426,13 +460,14 @@ int mtr_launch_delay (uint32_t us, void* stream)
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-int mtr_launch_gate (const mtr_gate_args& a, void* stream)
+template <bool LEN>
+static int launch_gate (const gate_args_t<LEN>& a, void* stream)
 {
 	// many fragments per call and few streams: spread a stream over several workgroups
 	if (a.n_frag >= 4 * GATE_FPB && a.max_scratch) {
 		const uint32_t nb = (a.n_frag + GATE_FPB - 1) / GATE_FPB;
-		hipLaunchKernelGGL (k_gate_frag, dim3 (nb, a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
-		hipLaunchKernelGGL (k_gate_final, dim3 (a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
+		hipLaunchKernelGGL (k_gate_frag<LEN>, dim3 (nb, a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
+		hipLaunchKernelGGL (k_gate_final<LEN>, dim3 (a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
 		return hipGetLastError () == hipSuccess ? 0 : -1;
 	}
 	// A deferred gate (a.polite_grid) runs beside the next call's fused kernel, whose one-wave workgroups own a SIMD each for
@@ -440,8 +475,18 @@ int mtr_launch_gate (const mtr_gate_args& a, void* stream)
 	// those (344 VGPRs of 512, 35 KB of 160), so the gate is launched as that many workgroups, each walking its share of the
 	// streams, and cannot stand in the way of k_seg's placement whenever the two are dispatched together.
 	const uint32_t grid = a.polite_grid ? (a.n_streams < a.polite_grid ? a.n_streams : a.polite_grid) : a.n_streams;
-	hipLaunchKernelGGL (k_gate, dim3 (grid), dim3 (256), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL (k_gate<LEN>, dim3 (grid), dim3 (256), 0, (hipStream_t) stream, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+int mtr_launch_gate (const mtr_gate_args& a, void* stream) { return launch_gate<false> (a, stream); }
+
+int mtr_launch_gate_len (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream)
+{
+	mtr_gate_len_args la;
+	static_cast<mtr_gate_args&> (la) = a;
+	la.frag_lim = frag_lim;
+	return launch_gate<true> (la, stream);
 }
 
 // ---- state initialisation --------------------------------------------------------------------
@@ -572,6 +617,47 @@ __global__ void k_history_mc (const float* audio, uint64_t stride, uint64_t n_fr
 	st->tp_last[0] = st->tp_last[1] = last;
 	st->tp_hold[0] = st->tp_hold[1] = hold;
 	st->tp_call[0] = st->tp_call[1] = 0;
+}
+
+// The same for a call with per-stream lengths: a stream the call does not touch (ends [s] == 0) keeps its history bit for bit (the
+// buffers ping-pong) and its peaks are not folded.  A stream that closes keeps whatever follows its end: nothing reads it again.
+__global__ void k_history_mc_len (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in,
+                                  float* hist_out, uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                                  const uint32_t* ends)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= n_streams * MTR_FIR_HALO) return;
+	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
+	const bool touched = ends[s] != 0;
+	const int64_t f = touched ? (int64_t) n_frames - MTR_FIR_HALO + i : (int64_t) i - MTR_FIR_HALO;
+	for (uint32_t c = 0; c < C; ++c)
+		hist_out[((size_t) s * MTR_FIR_HALO + i) * C + c] = (f >= 0) ? audio[((size_t) s * stride + (size_t) f) * C + c]
+		                                                            : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * C + c];
+	if (!tp_call || !touched || i != 0) return;
+	float last = 0.f, hold = 0.f;
+	for (uint32_t c = 0; c < C; ++c) {
+		const size_t k = (size_t) s * C + c;
+		const float v = __uint_as_float (tp_call[k]);
+		tp_last[k] = v;
+		if (v > tp_hold[k]) tp_hold[k] = v;
+		tp_call[k] = 0;
+		last = fmaxf (last, v);
+		hold = fmaxf (hold, tp_hold[k]);
+	}
+	mtr_stream_state* const st = state + s;
+	st->tp_last[0] = st->tp_last[1] = last;
+	st->tp_hold[0] = st->tp_hold[1] = hold;
+	st->tp_call[0] = st->tp_call[1] = 0;
+}
+
+int mtr_launch_history_mc_len (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
+                               uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                               const uint32_t* ends, void* stream)
+{
+	const uint32_t n = n_streams * MTR_FIR_HALO;
+	hipLaunchKernelGGL (k_history_mc_len, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
+	                    audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state, ends);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 int mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,

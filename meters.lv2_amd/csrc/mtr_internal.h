@@ -55,6 +55,11 @@ struct mtr_fused_args {
 	const uint16_t* mfma_a;       /* layout 6: [12][64][8] hi / lo A fragments of the matrix-pipe interpolator (mtr_mfma16_fir.h) */
 	float           a0, a1, a2, b1, b2, c3, c4;
 	float           gain_l, gain_r;
+	/* per-stream lengths (mtr_engine_process_*_lengths; NULL on every other call, which then launches the dense instantiations):
+	 * ends [S] = frames of stream s in this call (<= n_frames; 0: the stream is not touched), from_tile [S] = first tile of the
+	 * launch's one segment that stream s covers (0xFFFFFFFF: none; NULL: every tile) — k_seg's peak hand-over, mtr_seg.hip */
+	const uint32_t* ends;
+	const uint32_t* from_tile;
 };
 
 /* Arguments of the lane = time segment kernel (mtr_seg.hip, layout 7).  The launch covers the whole fragments of a call,
@@ -80,6 +85,7 @@ typedef struct mtr_seg_args {
 	uint32_t*       seg_stats;    /* screen: [2] chunks screened / completed (device counters), may be NULL */
 	float           a0, a1, a2, b1, b2, c3, c4;
 	float           gain_l, gain_r;
+	const uint32_t* ends;         /* per-stream lengths, CALL-relative (head included), or NULL: see mtr_fused_args and mtr_seg.hip */
 } mtr_seg_args;
 
 /* Arguments of the multichannel K-weighting + true-peak kernel (mtr_kwmc.hip, layout 8: n_channels 3, 4 or 5). */
@@ -101,6 +107,12 @@ typedef struct mtr_kwmc_args {
 	float           a0, a1, a2, b1, b2, c3, c4;
 	float           gain[MTR_MAX_CHANNELS];   /* _chan_gain (ebu_r128_proc.cc:29) */
 } mtr_kwmc_args;
+#ifdef __cplusplus
+/* ... of a call with per-stream lengths (a struct of its own, as mtr_gate_len_args): ends [S] = frames of stream s in this call */
+struct mtr_kwmc_len_args : mtr_kwmc_args {
+	const uint32_t* ends;
+};
+#endif
 
 struct mtr_gate_args {
 	mtr_stream_state* state;      /* [S] */
@@ -117,6 +129,16 @@ struct mtr_gate_args {
 	uint32_t        polite_grid;  /* 0: one workgroup per stream; else at most this many workgroups, each walking several streams (deferred gate) */
 	int32_t         fold_tp;      /* 1: fold tp_call into tp_last / tp_hold here (the serial order); 0: k_history has done it (deferred gate) */
 };
+/* ... of a call with per-stream lengths (a struct of its own: the dense gate's kernel arguments stay as they were):
+ * frag_lim [S] = fragments of this call that stream s inserts (<= n_frag), | MTR_GATE_CLOSING if the call closes it (its open
+ * fragment is not carried); MTR_GATE_UNTOUCHED: the workgroup leaves the stream as it is, fold included */
+#ifdef __cplusplus
+struct mtr_gate_len_args : mtr_gate_args {
+	const uint32_t* frag_lim;
+};
+#endif
+#define MTR_GATE_CLOSING   0x80000000u
+#define MTR_GATE_UNTOUCHED 0xFFFFFFFFu
 
 struct mtr_bank_args {
 	const float*    audio;
@@ -221,12 +243,21 @@ uint32_t mtr_kmeter_pieces (uint64_t n_groups);
 int  mtr_fused2_upload_taps (const float* g144);
 int  mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
                          float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state /* NULL: k_gate folds the peaks */, void* stream);
+/* ... of a call with per-stream lengths: a stream with ends [s] == 0 keeps its history and is not folded */
+int  mtr_launch_history_len (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
+                             uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream);
 int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, uint32_t n_units, void* stream);
+int  mtr_launch_kwmc_len (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
+/* ... of a call with per-stream lengths: a stream with ends [s] == 0 keeps its history and is not folded */
+int  mtr_launch_history_mc_len (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
+                                uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                                const uint32_t* ends, void* stream);
 /* [S][47][C] history of the multichannel engines; fold_c != NULL: also TruePeakdsp::read () per channel (tp_call -> tp_last,
  * tp_hold, all [S][C]) and the max over the channels into the stream state's tp_last[0..1] / tp_hold[0..1] */
 int  mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
                             uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state, void* stream);
 int  mtr_launch_gate (const mtr_gate_args& a, void* stream);
+int  mtr_launch_gate_len (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
 int  mtr_launch_bank (const mtr_bank_args& a, void* stream);

@@ -30,7 +30,7 @@ namespace {
 
 __device__ __forceinline__ v2f scrub (v2f v) { return v2f{isfinite (v.x) ? v.x : 0.f, isfinite (v.y) ? v.y : 0.f}; }
 
-template <int K>
+template <int K, bool LEN>
 __global__ __launch_bounds__ (64) void k_kw (const mtr_fused_args a)
 {
 	static_assert ((K & 1) == 1, "odd lane stride: conflict-free 64-bit LDS reads");
@@ -41,6 +41,11 @@ __global__ __launch_bounds__ (64) void k_kw (const mtr_fused_args a)
 	const uint32_t unit = blockIdx.x;
 	const uint32_t s = unit / a.n_segs;
 	const uint32_t q = unit - s * a.n_segs;
+	// LEN (per-stream lengths): a stream the call does not touch (ends [s] == 0) keeps its K-filter state.  Nothing else is masked:
+	// the recurrence and the scan only carry state forward in time, so the tile powers in front of a stream's end are the ones a
+	// call of exactly its frames gives, and those behind it (whatever the buffer holds there) feed only fragments that the gate
+	// never inserts for the stream (frag_lim, mtr_gate.hip).
+	if (LEN && a.ends[s] == 0) return;
 	const v2f* const src = reinterpret_cast<const v2f*> (a.audio) + (size_t) s * a.stride;
 	mtr_stream_state* const st = a.state + s;
 	const bool src_even = ((((size_t) s * a.stride) & 1) == 0) && ((reinterpret_cast<size_t> (a.audio) & 15) == 0);
@@ -168,7 +173,8 @@ template <int K>
 int launch_kw (const mtr_fused_args& a, uint32_t n_units, hipStream_t st)
 {
 	const size_t lds = (size_t) a.buf_slots * sizeof (v2f);
-	hipLaunchKernelGGL ((k_kw<K>), dim3 (n_units), dim3 (64), lds, st, a);
+	if (a.ends) hipLaunchKernelGGL ((k_kw<K, true>), dim3 (n_units), dim3 (64), lds, st, a);
+	else        hipLaunchKernelGGL ((k_kw<K, false>), dim3 (n_units), dim3 (64), lds, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

@@ -23,6 +23,8 @@
 
 #include <utility>
 
+#include <type_traits>
+
 #include "mtr_internal.h"
 #include "mtr_mfma16_fir.h"
 #include "mtr_wave.h"
@@ -48,8 +50,20 @@ __device__ __forceinline__ void pow2_scale (uint32_t e_, float& scale, float& un
 	unscale = __uint_as_float ((uint32_t) (239 - se) << 23);
 }
 
-template <int C, bool EBU, bool TP>
-__global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
+// LEN: the call carries per-stream lengths (mtr_kwmc_len_args, mtr_engine_process_*_lengths).  Frames at or past stream s's end E are
+// read as +0.0f, per channel, before they reach the scale, the K-filter or the interpolator's window (no load is issued for them);
+// only columns t < E count towards a channel's peak (phase 0 of the last 24 frames never does, as at a call's end); a segment starts
+// and stops at E, and one that starts at or past it does nothing.  Tile powers behind E feed fragments the gate never inserts for the
+// stream.  The dense instantiation (LEN false) takes the struct it always took and is the kernel's code as it always was.
+template <bool LEN> using kwmc_args_t = std::conditional_t<LEN, mtr_kwmc_len_args, mtr_kwmc_args>;
+template <bool LEN> __device__ __forceinline__ int64_t kwmc_end (const kwmc_args_t<LEN>& a, uint32_t s)
+{
+	if constexpr (LEN) return min ((int64_t) a.ends[s], (int64_t) a.n_frames);
+	else return 0;
+}
+
+template <int C, bool EBU, bool TP, bool LEN>
+__global__ __launch_bounds__ (64) void k_kwmc (const kwmc_args_t<LEN> a)
 {
 	static_assert (C >= 1 && C <= MTR_MAX_CHANNELS, "1 .. 5 channels (an odd count pads its last pair with a silent channel)");
 	static_assert ((K * C) % 4 == 0, "a lane's run is whole 16-byte words");
@@ -67,7 +81,11 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 	const int64_t seg_start = a.tile_start[jt0];
 	const int nwarm = (EBU && q > 0) ? (int) a.warm_tiles : 0;
 	const int ntile = (int) (jt1 - jt0);
-	const int64_t id_end = (int64_t) a.n_frames - 24;                 // phase 0 of this call ends with frame n_frames - 25
+	// the stream's end in this call (N_END: an expression, so that the dense instantiation reads a.n_frames where it always did)
+	const int64_t n_end_ = kwmc_end<LEN> (a, s);
+#define N_END (LEN ? n_end_ : (int64_t) a.n_frames)
+	if (LEN && seg_start >= N_END) return;                             // (wholly past the stream's end: no loads, no products, no writes)
+	const int64_t id_end = N_END - 24;                                 // phase 0 of this call ends with frame n_frames - 25
 
 	auto tile_of = [&] (int jj, int64_t& t0, int& len) {
 		if (jj < 0) { t0 = seg_start + (int64_t) jj * LT; len = LT; }
@@ -97,6 +115,7 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 	for (int jj = -nwarm; jj < ntile; ++jj) {
 		int64_t t0; int len;
 		tile_of (jj, t0, len);
+		if (LEN && t0 >= N_END) break;                                 // (the stream has ended: nothing of it is left in this segment)
 		const int64_t f0 = t0 + (int64_t) K * lane;                   // this lane's first frame
 		const int rl = min (max (len - K * lane, 0), K);              // frames of the run inside the tile
 
@@ -104,7 +123,7 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 		float xr[K * C];
 		{
 			const float* const p = src + f0 * C;
-			if (((reinterpret_cast<uintptr_t> (p) & 15) == 0) && f0 + K <= (int64_t) a.n_frames) {
+			if (((reinterpret_cast<uintptr_t> (p) & 15) == 0) && f0 + K <= N_END) {
 #pragma unroll
 				for (int i = 0; i < K * C / 4; ++i) {
 					const float4 v = reinterpret_cast<const float4*> (p)[i];
@@ -112,7 +131,7 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 				}
 			} else {
 #pragma unroll
-				for (int i = 0; i < K * C; ++i) xr[i] = f0 + i / C < (int64_t) a.n_frames ? p[i] : 0.f;
+				for (int i = 0; i < K * C; ++i) xr[i] = f0 + i / C < N_END ? p[i] : 0.f;
 			}
 #pragma unroll
 			for (int i = 0; i < K * C; ++i) if (i / C >= rl) xr[i] = 0.f;   // the next tile's frames (or none)
@@ -181,7 +200,10 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 			m16::AFrag A;
 			A.load (a.mfma_a, lane);
 			const int wrun = HALO / 2 + (K / 2) * lane;                  // first word of this lane's run
-			const int nb = (len + 255) >> 8;
+			// (LEN: the tile's columns in front of the stream's end)
+			const int plen_ = LEN ? (int) min ((int64_t) len, N_END - t0) : 0;
+#define PLEN (LEN ? plen_ : len)
+			const int nb = (PLEN + 255) >> 8;
 #pragma unroll
 			for (int c = 0; c < C; ++c) {
 				// the halo: positions 2 i, 2 i + 1 <-> frames t0 - 48 + 2 i (+ 1), lanes i < 24; history in front of the call
@@ -189,7 +211,7 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 				if (lane < HALO / 2) {
 					const int64_t f = t0 - HALO + 2 * lane;
 					auto at = [&] (int64_t ff) -> float {
-						if (ff >= 0) return src[ff * C + c];
+						if (ff >= 0) return (!LEN || ff < N_END) ? src[ff * C + c] : 0.f;
 						if (ff >= -MTR_FIR_HALO && q == 0) return a.hist[((size_t) s * MTR_FIR_HALO + (size_t) (ff + MTR_FIR_HALO)) * C + c];
 						return 0.f;
 					};
@@ -208,7 +230,7 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 						for (int n = 0; n < K; ++n) if (n < lim) i0 = fmaxf (i0, fabsf (xr[n * C + c]));
 					}
 					if (q == 0 && jj == 0 && lane >= HALO / 4 && lane < HALO / 2) {
-						const int64_t plim = (int64_t) a.n_frames + 24 - t0;
+						const int64_t plim = N_END + 24 - t0;
 						if (2 * lane < plim)     i0 = fmaxf (i0, fabsf (g0));
 						if (2 * lane + 1 < plim) i0 = fmaxf (i0, fabsf (g1));
 					}
@@ -239,7 +261,7 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 					m16::fetch_b (B, H, L, w);
 					m16::f4 y[3];
 					m16::block (A, B, y);
-					const int lim = len - 256 * b - fo;                  // registers r < lim are outputs of this tile
+					const int lim = PLEN - 256 * b - fo;                 // registers r < lim are outputs of this tile
 #pragma unroll
 					for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -247,8 +269,10 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 				}
 				pk[c] = fmaxf (pk[c], pc * un);                          // back to the samples' own scale (exact)
 			}
+#undef PLEN
 		}
 	}
+#undef N_END
 	if (EBU && q == a.n_segs - 1 && lane == 0) {
 #pragma unroll
 		for (int p = 0; p < NP; ++p) {
@@ -266,25 +290,38 @@ __global__ __launch_bounds__ (64) void k_kwmc (const mtr_kwmc_args a)
 	}
 }
 
-template <int C>
-int launch_c (bool ebu, bool tp, const mtr_kwmc_args& a, uint32_t n_units, hipStream_t st)
+template <int C, bool LEN>
+int launch_c (bool ebu, bool tp, const kwmc_args_t<LEN>& a, uint32_t n_units, hipStream_t st)
 {
-	if (ebu && tp)  hipLaunchKernelGGL ((k_kwmc<C, true, true>), dim3 (n_units), dim3 (64), 0, st, a);
-	else if (ebu)   hipLaunchKernelGGL ((k_kwmc<C, true, false>), dim3 (n_units), dim3 (64), 0, st, a);
-	else if (tp)    hipLaunchKernelGGL ((k_kwmc<C, false, true>), dim3 (n_units), dim3 (64), 0, st, a);
+	if (ebu && tp)  hipLaunchKernelGGL ((k_kwmc<C, true, true, LEN>), dim3 (n_units), dim3 (64), 0, st, a);
+	else if (ebu)   hipLaunchKernelGGL ((k_kwmc<C, true, false, LEN>), dim3 (n_units), dim3 (64), 0, st, a);
+	else if (tp)    hipLaunchKernelGGL ((k_kwmc<C, false, true, LEN>), dim3 (n_units), dim3 (64), 0, st, a);
 	else return -2;
 	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+template <bool LEN>
+int launch_any (int C, bool ebu, bool tp, const kwmc_args_t<LEN>& a, uint32_t n_units, hipStream_t st)
+{
+	switch (C) {
+	case 3: return launch_c<3, LEN> (ebu, tp, a, n_units, st);
+	case 4: return launch_c<4, LEN> (ebu, tp, a, n_units, st);
+	case 5: return launch_c<5, LEN> (ebu, tp, a, n_units, st);
+	default: return -2;
+	}
 }
 
 }  // namespace
 
 int mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, uint32_t n_units, void* stream)
 {
-	const hipStream_t st = (hipStream_t) stream;
-	switch (C) {
-	case 3: return launch_c<3> (ebu, tp, a, n_units, st);
-	case 4: return launch_c<4> (ebu, tp, a, n_units, st);
-	case 5: return launch_c<5> (ebu, tp, a, n_units, st);
-	default: return -2;
-	}
+	return launch_any<false> (C, ebu, tp, a, n_units, (hipStream_t) stream);
+}
+
+int mtr_launch_kwmc_len (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream)
+{
+	mtr_kwmc_len_args la;
+	static_cast<mtr_kwmc_args&> (la) = a;
+	la.ends = ends;
+	return launch_any<true> (C, ebu, tp, la, n_units, (hipStream_t) stream);
 }

@@ -181,7 +181,14 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 // values (pm) cannot raise it, whatever the other two products add.  The check runs in the next chunk; if any lane of the wave
 // fails it (a NaN or Inf fails it), the chunk gets MFMAs 6..17 on the same accumulators — bit for bit the dense values — and
 // its maxima go into pm as in the dense form.  The peak is the dense form's on every input; only the time depends on the data.
-template <bool EBU, bool ALIGNED, bool SCREEN>
+//
+// LEN: the call carries per-stream lengths (a.ends, call-relative: mtr_engine_process_*_lengths).  Every frame at or past a stream's
+// end E is read as +0.0f — the global loads behind it are not issued — so the scale, the ring and the recurrence never see what the
+// buffer holds there.  The peak of a lane counts only where all of its columns and phase-0 frames lie in front of E - 24: a segment
+// that reaches further on a stream the call closes (E < n_frames) keeps its peak to itself, and the engine hands exactly those
+// segments' peaks to k_kwtp16_len (a.from_tile: from the first such segment's first tile, masked at E).  A stream the call does not
+// touch (E == 0) keeps its K-filter state.  The dense instantiation (LEN false) is the kernel's code as it always was.
+template <bool EBU, bool ALIGNED, bool SCREEN, bool LEN>
 __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 {
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem_[];
@@ -211,6 +218,10 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	const bool cut = last_rows < R;
 	const bool lastq = !ALIGNED && q == a.n_segs - 1;
 	const int n_loads = n_steps - (cut ? 1 : 0);                      // steps the stream pointers walk
+	// LEN: the stream's end relative to `src`; does this lane's peak count (see above)?
+	const int64_t e_src = LEN ? (int64_t) a.ends[s] - (int64_t) a.head : 0;
+	const bool closing = LEN && e_src < a.p0_end + 24;
+	const bool peak_ok = !closing || (int64_t) (fq + cq) * a.tile_frames + 24 <= e_src;
 
 	KCoef kc;
 	kc.a0 = a.a0; kc.a1 = a.a1; kc.a2 = a.a2; kc.b1 = a.b1; kc.b2 = a.b2; kc.c3 = a.c3; kc.c4 = a.c4; kc.eps = 1e-15f;
@@ -227,11 +238,33 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	typedef f4v_ float4_a8 __attribute__ ((aligned (8)));              // (a segment may start on any frame: 8-byte alignment is all there is)
 	const float4_a8* lp = reinterpret_cast<const float4_a8*> (src + F0 - (warm ? (int64_t) a.warm_steps * R : 0));
 	v2f xq[4][R];
+	const float4_a8* const lp_base = reinterpret_cast<const float4_a8*> (src);
 	auto load = [&]<int B> () __attribute__ ((always_inline)) {
+		if constexpr (LEN) {
+			// frames of this line in front of the stream's end: all of them but in the one line that holds the end
+			const int64_t left = e_src - 2 * (int64_t) (lp - lp_base);
+			if (__builtin_expect (left >= R, 1)) {
+#pragma unroll
+				for (int i = 0; i < R / 2; ++i) {
+					const f4v_ v = lp[i];
+					xq[B][2 * i] = v2f{v.x, v.y}; xq[B][2 * i + 1] = v2f{v.z, v.w};
+				}
+			} else {
+				const int nl = (int) max (left, (int64_t) 0);
+#pragma unroll
+				for (int i = 0; i < R / 2; ++i) {
+					f4v_ v = f4v_{0.f, 0.f, 0.f, 0.f};
+					if (2 * i < nl) v = lp[i];
+					if (2 * i + 1 >= nl) { v.z = 0.f; v.w = 0.f; }
+					xq[B][2 * i] = v2f{v.x, v.y}; xq[B][2 * i + 1] = v2f{v.z, v.w};
+				}
+			}
+		} else {
 #pragma unroll
 		for (int i = 0; i < R / 2; ++i) {
 			const f4v_ v = lp[i];        // (plain loads: the eight 16-byte reads of a lane's line merge in the L1 — as nt loads they go to the L2 one by one: 17.4 ms)
 			xq[B][2 * i] = v2f{v.x, v.y}; xq[B][2 * i + 1] = v2f{v.z, v.w};
+		}
 		}
 	};
 	load.template operator()<0> (); lp += R / 2;
@@ -320,7 +353,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			for (int n = 0; n < R; ++n) {
 				const int64_t f = F0 - 48 + R * k + n;
 				const int64_t fc = f + (int64_t) a.head;                     // the call's own frame; in front of it: the history
-				px[k][n] = fc >= 0 ? src[f] : (fc >= -MTR_FIR_HALO ? hst[fc + MTR_FIR_HALO] : v2f{0.f, 0.f});
+				px[k][n] = fc >= 0 ? ((!LEN || f < e_src) ? src[f] : v2f{0.f, 0.f}) : (fc >= -MTR_FIR_HALO ? hst[fc + MTR_FIR_HALO] : v2f{0.f, 0.f});
 			}
 		float ml = 0.f, mr = 0.f;
 #pragma unroll
@@ -517,7 +550,9 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			rml = fmaxf (rml, ml); rmr = fmaxf (rmr, mr);                // (step j's own samples too: a bound on more is still a bound)
 			if (PROD) {
 				float* const E = reinterpret_cast<float*> (smem_ + XEPS);
-				*reinterpret_cast<float2*> (E + (cc * 4 + kg) * 2) =
+				// (LEN: a column whose peak does not count passes the screen whatever its values — eps = -inf — so that the zeros
+				// behind a stream's end, which never pass it, do not complete every chunk of their waves)
+				*reinterpret_cast<float2*> (E + (cc * 4 + kg) * 2) = (LEN && !peak_ok) ? float2{-INFINITY, -INFINITY} :
 					float2{fmaf (SCREEN_K_REL, rml * scl.sc, SCREEN_K_ABS), fmaf (SCREEN_K_REL, rmr * scr.sc, SCREEN_K_ABS)};
 				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
 				__builtin_amdgcn_wave_barrier ();
@@ -718,7 +753,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #pragma unroll
 		for (int n = 0; n < R; ++n) t[n] = f[min (n, rows - 1)];
 #pragma unroll
-		for (int n = 0; n < R; ++n) xq[U][n] = n < rows ? t[n] : v2f{0.f, 0.f};
+		for (int n = 0; n < R; ++n) xq[U][n] = (n < rows && (!LEN || F0 + (int64_t) (n_steps - 1) * R + n < e_src)) ? t[n] : v2f{0.f, 0.f};
 		maxabs.template operator()<U> ();                             // (the maxima computed a step early saw a stale line)
 	};
 	auto do_step = [&]<int U, bool PROD> () __attribute__ ((always_inline)) {
@@ -762,9 +797,11 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 
 	if (SCREEN && lane == 0 && a.seg_stats) { atomicAdd (&a.seg_stats[0], n_scr); atomicAdd (&a.seg_stats[1], n_fin); }
 	if (live) {
-		atomicMax (&st->tp_call[0], __float_as_uint (fmaxf (pk0.x, pkf.x)));
-		atomicMax (&st->tp_call[1], __float_as_uint (fmaxf (pk0.y, pkf.y)));
-		if (EBU && q == a.n_segs - 1) {
+		if (peak_ok) {
+			atomicMax (&st->tp_call[0], __float_as_uint (fmaxf (pk0.x, pkf.x)));
+			atomicMax (&st->tp_call[1], __float_as_uint (fmaxf (pk0.y, pkf.y)));
+		}
+		if (EBU && q == a.n_segs - 1 && (!LEN || a.ends[s] != 0)) {
 			const KState& kf = ALIGNED ? ks : kfin;                       // (unaligned: the state at the lane's last tile end)
 			st->kz[0] = kf.z1.x; st->kz[1] = kf.z1.y; st->kz[2] = kf.z2.x; st->kz[3] = kf.z2.y;
 			st->kz[4] = kf.z3.x; st->kz[5] = kf.z3.y; st->kz[6] = kf.z4.x; st->kz[7] = kf.z4.y;
@@ -787,16 +824,28 @@ int mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* str
 {
 	hipStream_t st = (hipStream_t) stream;
 	const bool aligned = a.tile_frames % R == 0;
-	if (a.screen) {
-		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // (no tiles without Σ y²; the
-		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // same code but for the launch's last step)
-		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else              hipLaunchKernelGGL ((k_seg<true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+	if (a.ends) {
+		if (a.screen) {
+			if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+			else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+			else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+			else              hipLaunchKernelGGL ((k_seg<true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		} else {
+			if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+			else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+			else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+			else              hipLaunchKernelGGL ((k_seg<true, false, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		}
+	} else if (a.screen) {
+		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // (no tiles without Σ y²; the
+		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // same code but for the launch's last step)
+		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else              hipLaunchKernelGGL ((k_seg<true, false, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
 	} else {
-		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else              hipLaunchKernelGGL ((k_seg<true, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else              hipLaunchKernelGGL ((k_seg<true, false, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
 	}
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }

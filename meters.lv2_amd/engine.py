@@ -109,6 +109,10 @@ def _load():
     L.mtr_engine_spectr_set_speed.argtypes = [vp, f32]
     L.mtr_engine_process_device.argtypes = [vp, vp, u64, u64, vp]
     L.mtr_engine_process_host.argtypes = [vp, vp, u64, u64]
+    if hasattr(L, "mtr_engine_stream_frames"):                 # (an addition inside ABI version 2: per-stream lengths)
+        L.mtr_engine_process_device_lengths.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_lengths.argtypes = [vp, vp, u64, u64, vp]
+        L.mtr_engine_stream_frames.argtypes = [vp, u32, u32, vp, vp]
     L.mtr_engine_set_host_chunk_bytes.argtypes = [vp, u64]
     L.mtr_engine_process_planar_host.argtypes = [vp, C.POINTER(vp), u32]
     L.mtr_engine_results.argtypes = [vp, u32, u32, C.POINTER(StreamResult)]
@@ -346,6 +350,39 @@ class Engine:
         x = np.ascontiguousarray(x, np.float32)
         assert x.shape[0] == self.n_streams
         _check(lib.mtr_engine_process_host(self._h, x.ctypes.data, x.shape[1], x.shape[1]), "process_host")
+
+    def _lengths(self, frames, n_frames):
+        if not hasattr(lib, "mtr_engine_stream_frames"):
+            raise EngineError(f"{lib_path} has no per-stream lengths: rebuild it")
+        f = np.ascontiguousarray(frames, np.uint64)
+        if f.shape != (self.n_streams,):
+            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
+        return f
+
+    def process_device_lengths(self, ptr, n_frames, frames, stride=None, stream=0):
+        """Advance stream s by frames[s] <= n_frames frames of the device buffer at `ptr`; a stream with frames[s] < n_frames
+        is closed by the call (its results are final until reset()), frames[s] == n_frames leaves it open."""
+        f = self._lengths(frames, n_frames)
+        _check(lib.mtr_engine_process_device_lengths(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
+               "process_device_lengths")
+
+    def process_lengths(self, x, frames):
+        """process() with per-stream lengths: x host float32 [S, T, C], frames [S] <= T."""
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.shape[0] == self.n_streams
+        f = self._lengths(frames, x.shape[1])
+        _check(lib.mtr_engine_process_host_lengths(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
+               "process_host_lengths")
+
+    def stream_frames(self, first=0, count=None):
+        """(frames, closed): [count] uint64 frames metered per stream since create / reset, [count] bool closed."""
+        if not hasattr(lib, "mtr_engine_stream_frames"):
+            raise EngineError(f"{lib_path} has no per-stream lengths: rebuild it")
+        count = self.n_streams - first if count is None else count
+        frames = np.zeros(count, np.uint64)
+        closed = np.zeros(count, np.uint8)
+        _check(lib.mtr_engine_stream_frames(self._h, first, count, frames.ctypes.data, closed.ctypes.data), "stream_frames")
+        return frames, closed.astype(bool)
 
     def set_host_chunk_bytes(self, n):
         """Bytes of audio per chunk of process() (host memory crosses the link chunk by chunk under the kernels)."""
