@@ -60,7 +60,8 @@ constexpr int ARRB  = 64 * COLB;             // one array: HL | HR | LL | LR
 constexpr int BLKB  = 16 * COLB;             // 16 columns = one MFMA block
 constexpr int XCHG  = 4 * ARRB;              // exchange area: float [2 ch][4 blocks][4 kg][16 c]
 constexpr int XEPS  = XCHG + 2048;           // ... and the screen's bounds: float [16 c][4 blocks][2 ch]
-constexpr int LDS_BYTES = XEPS + 512;
+constexpr int XREF  = XEPS + 512;            // ... and its stream references, the same layout
+constexpr int LDS_BYTES = XREF + 512;
 
 typedef unsigned char lds_u8;          // (generic pointers into the dynamic LDS block: the compiler infers the address space)
 
@@ -100,6 +101,29 @@ struct Scale {
 // are exact in f32 and no partial sum of them is an f32 subnormal (the smallest is 2^-48), so nothing else rounds.
 constexpr float SCREEN_K_REL = 56.0f;
 constexpr float SCREEN_K_ABS = 0.0078125f;
+
+// The screen's stream reference.  k_seg's result is the maximum per (stream, channel) of what its lanes count (tp_call, at the
+// end): a chunk none of whose outputs can exceed a value already counted for the same (stream, channel) cannot change it, even
+// where it would set a record of its own accumulator lane.  So the vote takes, besides the lane's own pm, R = the largest value
+// the lanes of the column's stream in this wave have counted so far: each owner lane offers max (pk0, pkf) where its peak counts
+// (live and peak_ok; otherwise +0, which every peak already bounds), the lanes of an aligned 16-lane row take the maximum of the
+// offers of their own stream (four DPP steps, each taken only from a partner of the same stream: a subset of the stream's lanes,
+// which is all a bound needs — streams that straddle rows or waves need nothing across them), every fourth step (a stale R is
+// still counted), and the owner converts it into the column's unit each step, R * scale * 2^15, through LDS next to eps.  Then
+//     fl (F + eps) < max (pm, R')   =>   |Y| <= F + eps < R' (or pm)   =>   the dense peak is the same bits.
+//   * R holds only values of this launch that its final atomicMax counts for that (stream, channel) (pk0 and pkf only grow), never
+//     a hold or a previous call's peak, and no !peak_ok lane (LEN: those segments go to k_kwtp16_len) feeds it.
+//   * NaN: pk0 and pkf never hold one (fmaxf drops it, conservatively), and the vote's fmaxf would drop a NaN R too; a NaN in F
+//     still fails the vote.  The offers are non-negative floats, so their maximum is the unsigned one of their bit patterns.
+//   * An Inf sample: R becomes Inf (where its phase 0 counts), every finite chunk passes and Inf ones fail; the result is Inf
+//     either way.
+//   * R' overflows to +Inf where R * scale * 2^15 >= 2^128: a finite fl (F + eps) <= FLT_MAX lies below the true R', so a pass is
+//     still exact.  R' rounds only where it is subnormal, and then it cannot decide a vote: fl (F + eps) >= eps >= 2^-7.  A normal
+//     R' is exact (a power of two times a float).
+//   * The scale: R' is written in the step that checks the chunks, after its rescale — in the scale of every chunk checked there
+//     (a chunk 7 still pending at a rescale is completed in front of it, as for eps).
+// A wave in the bench's shape (8 segments per stream) holds 8 streams; their quiet segments stop completing against their own
+// small records.  tests/test_gpu_seg_stream_reference.py holds the screened form to the dense one bit for bit.
 
 struct KCoef { v2f a0, a1, a2, b1, b2, c3, c4, eps; };
 struct KState { v2f z1, z2, z3, z4, sj; };
@@ -178,9 +202,12 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 //
 // SCREEN: each chunk runs the first of its three products (Ghi Xhi: MFMAs 0..5) and no more, unless one of its outputs may
 // reach the running peak: a lane whose twelve first-product values all stay eps (above) under the peak of its completed
-// values (pm) cannot raise it, whatever the other two products add.  The check runs in the next chunk; if any lane of the wave
-// fails it (a NaN or Inf fails it), the chunk gets MFMAs 6..17 on the same accumulators — bit for bit the dense values — and
-// its maxima go into pm as in the dense form.  The peak is the dense form's on every input; only the time depends on the data.
+// values (pm) or under its stream's reference (what the launch has already counted for the stream: above) cannot raise the
+// result, whatever the other two products add.  The check runs in the next chunk; if any lane of the wave fails it (a NaN or
+// Inf fails it), the chunk reads its lo operands and gets MFMAs 6..17 on the same accumulators — bit for bit the dense values —
+// and its maxima go into pm as in the dense form.  The peak is the dense form's on every input; only the time depends on the data.
+// Chunks 6 and 7 read their lo operands with their hi ones: the ring stores of chunks 6 and 7 overwrite slot U, the oldest
+// quarter of their windows, before their checks (chunk 6's in chunk 7, chunk 7's in the next step's chunk 0).
 //
 // LEN: the call carries per-stream lengths (a.ends, call-relative: mtr_engine_process_*_lengths).  Every frame at or past a stream's
 // end E is read as +0.0f — the global loads behind it are not issued — so the scale, the ring and the recurrence never see what the
@@ -322,6 +349,21 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	float rml = 0.f, rmr = 0.f;                                       // SCREEN: max |x| of the segment so far (history frames included), per channel
 	uint32_t n_scr = 0, n_fin = 0;                                    // ... chunks screened / completed (wave-uniform)
 	bool y1_pend = false;                                             // ... y1 holds the first product of a chunk 7 whose check is still to come
+	uint32_t refl = 0, refr = 0;                                      // ... the stream's reference (float bits, unscaled), per channel
+	// ... the lanes it is taken from: the partners of the four DPP steps that meter the same stream, and whether this lane's peak counts
+	const bool ref_own = live && peak_ok;
+	const bool ref_q1 = SCREEN && (uint32_t) __builtin_amdgcn_mov_dpp ((int) s, 0xB1, 0xF, 0xF, false) == s;   // quad_perm [1,0,3,2]
+	const bool ref_q2 = SCREEN && (uint32_t) __builtin_amdgcn_mov_dpp ((int) s, 0x4E, 0xF, 0xF, false) == s;   // quad_perm [2,3,0,1]
+	const bool ref_hm = SCREEN && (uint32_t) __builtin_amdgcn_mov_dpp ((int) s, 0x141, 0xF, 0xF, false) == s;  // row_half_mirror
+	const bool ref_rm = SCREEN && (uint32_t) __builtin_amdgcn_mov_dpp ((int) s, 0x140, 0xF, 0xF, false) == s;  // row_mirror
+	auto ref_row = [&] (uint32_t v) __attribute__ ((always_inline)) {
+		uint32_t t;
+		t = max (v, (uint32_t) __builtin_amdgcn_update_dpp (0, (int) v, 0xB1, 0xF, 0xF, true));  v = ref_q1 ? t : v;
+		t = max (v, (uint32_t) __builtin_amdgcn_update_dpp (0, (int) v, 0x4E, 0xF, 0xF, true));  v = ref_q2 ? t : v;
+		t = max (v, (uint32_t) __builtin_amdgcn_update_dpp (0, (int) v, 0x141, 0xF, 0xF, true)); v = ref_hm ? t : v;
+		t = max (v, (uint32_t) __builtin_amdgcn_update_dpp (0, (int) v, 0x140, 0xF, 0xF, true)); v = ref_rm ? t : v;
+		return v;
+	};
 
 	auto split_store = [&] (const v2f (&x)[R], int slot) __attribute__ ((always_inline)) {
 		const v2f sc = v2f{scl.sc, scr.sc};
@@ -444,6 +486,17 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
 		B.l1 = *reinterpret_cast<const uint4*> (l + RA[(U + 2) & 3]);
 	};
+	// SCREEN: the same operands in two parts — the hi words for MFMAs 0..5, the lo words only for a chunk that completes
+	auto fetch_hi = [&]<int U> (m16::BFrag& B, int bc) __attribute__ ((always_inline)) {
+		const lds_u8* const h = smem + (bc & 1) * ARRB + (bc >> 1) * BLKB;
+		B.h0 = *reinterpret_cast<const uint4*> (h + RA[U]);
+		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
+	};
+	auto fetch_lo = [&]<int U> (m16::BFrag& B, int bc) __attribute__ ((always_inline)) {
+		const lds_u8* const l = smem + (2 + (bc & 1)) * ARRB + (bc >> 1) * BLKB;
+		B.l0 = *reinterpret_cast<const uint4*> (l + RA[U]);
+		B.l1 = *reinterpret_cast<const uint4*> (l + RA[(U + 2) & 3]);
+	};
 	// SCREEN: the other two products of a chunk whose first one is in y (operands B): MFMAs 6..17 of m16::block's order
 	auto complete = [&] (const m16::BFrag& B, m16::f4 (&y)[3]) __attribute__ ((always_inline)) {
 		m16::block_mfma<6> (A, B, y);  m16::block_mfma<7> (A, B, y);  m16::block_mfma<8> (A, B, y);
@@ -535,7 +588,8 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #pragma unroll
 			for (int p = 0; p < 3; ++p) y1[p] = m16::f4{0.f, 0.f, 0.f, 0.f};
 			rescale (ml, mr);
-			if (PROD) fetch.template operator()<U> (B0, 0);               // (fetched before the ring was rescaled: again)
+			if constexpr (SCREEN) { if (PROD) fetch_hi.template operator()<U> (B0, 0); }
+			else if (PROD) fetch.template operator()<U> (B0, 0);          // (fetched before the ring was rescaled: again)
 		}
 
 		// the stream, three steps ahead (the pointer stops with the segment: the last loads re-read its last line)
@@ -545,21 +599,31 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		load.template operator()<(U + 3) & 3> ();
 		// SCREEN: eps of the products of step j - 1 for every accumulator lane.  The owner of column 16 b + c (lane 16 b + c)
 		// computes it in the column's current scale; lane (c, kg) needs the four columns c of blocks 0..3: through LDS.
-		float eps[4][2];
+		float eps[4][2], ref[4][2];
 		if constexpr (SCREEN) {
 			rml = fmaxf (rml, ml); rmr = fmaxf (rmr, mr);                // (step j's own samples too: a bound on more is still a bound)
+			if constexpr (U == 0) {                                       // the stream reference, every fourth step
+				refl = ref_row (ref_own ? max (__float_as_uint (pk0.x), __float_as_uint (pkf.x)) : 0u);
+				refr = ref_row (ref_own ? max (__float_as_uint (pk0.y), __float_as_uint (pkf.y)) : 0u);
+			}
 			if (PROD) {
 				float* const E = reinterpret_cast<float*> (smem_ + XEPS);
 				// (LEN: a column whose peak does not count passes the screen whatever its values — eps = -inf — so that the zeros
 				// behind a stream's end, which never pass it, do not complete every chunk of their waves)
 				*reinterpret_cast<float2*> (E + (cc * 4 + kg) * 2) = (LEN && !peak_ok) ? float2{-INFINITY, -INFINITY} :
 					float2{fmaf (SCREEN_K_REL, rml * scl.sc, SCREEN_K_ABS), fmaf (SCREEN_K_REL, rmr * scr.sc, SCREEN_K_ABS)};
+				float* const Q = reinterpret_cast<float*> (smem_ + XREF);
+				*reinterpret_cast<float2*> (Q + (cc * 4 + kg) * 2) =
+					float2{__uint_as_float (refl) * (scl.sc * 32768.f), __uint_as_float (refr) * (scr.sc * 32768.f)};
 				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
 				__builtin_amdgcn_wave_barrier ();
 				__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "workgroup");
 				const float4 e0 = *reinterpret_cast<const float4*> (E + cc * 8), e1 = *reinterpret_cast<const float4*> (E + cc * 8 + 4);
 				eps[0][0] = e0.x; eps[0][1] = e0.y; eps[1][0] = e0.z; eps[1][1] = e0.w;
 				eps[2][0] = e1.x; eps[2][1] = e1.y; eps[3][0] = e1.z; eps[3][1] = e1.w;
+				const float4 r0 = *reinterpret_cast<const float4*> (Q + cc * 8), r1 = *reinterpret_cast<const float4*> (Q + cc * 8 + 4);
+				ref[0][0] = r0.x; ref[0][1] = r0.y; ref[1][0] = r0.z; ref[1][1] = r0.w;
+				ref[2][0] = r1.x; ref[2][1] = r1.y; ref[3][0] = r1.z; ref[3][1] = r1.w;
 				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
 				__builtin_amdgcn_wave_barrier ();
 			}
@@ -647,16 +711,18 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 				float ca = 0.f, cb = 0.f;
 #pragma unroll
 				for (int p = 0; p < 3; ++p) { ca = max3abs (ca, yp[p][0], yp[p][1]); cb = max3abs (cb, yp[p][2], yp[p][3]); }
-				const float pk = fmaxf (pm[PB >> 1][PB & 1][0], pm[PB >> 1][PB & 1][1]);
+				const float pk = fmaxf (fmaxf (pm[PB >> 1][PB & 1][0], pm[PB >> 1][PB & 1][1]), ref[PB >> 1][PB & 1]);
 				const bool below = fmaxf (ca, cb) + eps[PB >> 1][PB & 1] < pk;       // (false for a NaN anywhere in it)
 				++n_scr;
 				if (__builtin_expect (__ballot (!below) != 0, 0)) {
+					if constexpr (PB < 6) fetch_lo.template operator()<U> (Bn, PB);   // (the ring still holds them: its stores come in chunks 6, 7)
 					complete (Bn, yp);
 					fold (yp, PB);
 					++n_fin;
 				}
 			}
-			if (PROD && BC < 7) fetch.template operator()<U> (Bn, BC + 1);
+			if constexpr (BC + 1 >= 6) { if (PROD && BC < 7) fetch.template operator()<U> (Bn, BC + 1); }
+			else if (PROD) fetch_hi.template operator()<U> (Bn, BC + 1);
 #define MTR_M(I) if (PROD) m16::block_mfma<I> (A, Bc, yc)
 			MTR_M (0);  v2f um = xa * sc2;
 			MTR_M (1);  v2f vm = xb * sc2;
@@ -682,7 +748,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			kseq.template operator()<KGAP * BC + 3> ();
 			MTR_ST (3, lr);
 			kseq.template operator()<KGAP * BC + 4> ();
-			if constexpr (BC == 7) fetch.template operator()<(U + 1) & 3> (Bn, 0);      // (Bn of the last chunk = B0 of the next step)
+			if constexpr (BC == 7) fetch_hi.template operator()<(U + 1) & 3> (Bn, 0);   // (Bn of the last chunk = B0 of the next step)
 			kseq.template operator()<KGAP * BC + 5> ();
 #undef MTR_ST
 			if constexpr (BC == 7) if (PROD) y1_pend = true;
