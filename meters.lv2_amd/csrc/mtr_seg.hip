@@ -120,8 +120,8 @@ constexpr float SCREEN_K_ABS = 0.0078125f;
 //   * R' overflows to +Inf where R * scale * 2^15 >= 2^128: a finite fl (F + eps) <= FLT_MAX lies below the true R', so a pass is
 //     still exact.  R' rounds only where it is subnormal, and then it cannot decide a vote: fl (F + eps) >= eps >= 2^-7.  A normal
 //     R' is exact (a power of two times a float).
-//   * The scale: R' is written in the step that checks the chunks, after its rescale — in the scale of every chunk checked there
-//     (a chunk 7 still pending at a rescale is completed in front of it, as for eps).
+//   * The scale: R' is written in the step that runs and checks the chunks, after its rescale — in the scale of every chunk checked
+//     there (a step votes on all eight of its chunks and completes the failing ones itself: none is pending at the next rescale).
 // A wave in the bench's shape (8 segments per stream) holds 8 streams; their quiet segments stop completing against their own
 // small records.  tests/test_gpu_seg_stream_reference.py holds the screened form to the dense one bit for bit.
 
@@ -203,11 +203,14 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 // SCREEN: each chunk runs the first of its three products (Ghi Xhi: MFMAs 0..5) and no more, unless one of its outputs may
 // reach the running peak: a lane whose twelve first-product values all stay eps (above) under the peak of its completed
 // values (pm) or under its stream's reference (what the launch has already counted for the stream: above) cannot raise the
-// result, whatever the other two products add.  The check runs in the next chunk; if any lane of the wave fails it (a NaN or
-// Inf fails it), the chunk reads its lo operands and gets MFMAs 6..17 on the same accumulators — bit for bit the dense values —
-// and its maxima go into pm as in the dense form.  The peak is the dense form's on every input; only the time depends on the data.
-// Chunks 6 and 7 read their lo operands with their hi ones: the ring stores of chunks 6 and 7 overwrite slot U, the oldest
-// quarter of their windows, before their checks (chunk 6's in chunk 7, chunk 7's in the next step's chunk 0).
+// result, whatever the other two products add.  A step issues its eight chunks' first products back to back; each chunk's vote
+// runs behind the next chunk's MFMAs (chunk 7's behind its own tail), on complete accumulators, and leaves a lane mask, and the
+// step branches once, on the OR of the eight.  Every chunk one lane of which failed (a NaN or Inf fails) then runs MFMAs 0..17
+// from zero on all four of its operands, read again from the ring — m16::block's order, so bit for bit the dense values — and
+// its maxima go into pm as in the dense form.  The step's ring stores (slot U: the oldest quarter of every window of its
+// products) come only behind that, so all of a step's windows are intact when a chunk completes, and no step leaves a chunk
+// pending: a rescale at the next step's head finds nothing to complete.  A vote reads pm and the bounds of its own step, which
+// only its own chunk's completion can change.  The peak is the dense form's on every input; only the time depends on the data.
 //
 // LEN: the call carries per-stream lengths (a.ends, call-relative: mtr_engine_process_*_lengths).  Every frame at or past a stream's
 // end E is read as +0.0f — the global loads behind it are not issued — so the scale, the ring and the recurrence never see what the
@@ -348,7 +351,6 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 
 	float rml = 0.f, rmr = 0.f;                                       // SCREEN: max |x| of the segment so far (history frames included), per channel
 	uint32_t n_scr = 0, n_fin = 0;                                    // ... chunks screened / completed (wave-uniform)
-	bool y1_pend = false;                                             // ... y1 holds the first product of a chunk 7 whose check is still to come
 	uint32_t refl = 0, refr = 0;                                      // ... the stream's reference (float bits, unscaled), per channel
 	// ... the lanes it is taken from: the partners of the four DPP steps that meter the same stream, and whether this lane's peak counts
 	const bool ref_own = live && peak_ok;
@@ -486,23 +488,11 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
 		B.l1 = *reinterpret_cast<const uint4*> (l + RA[(U + 2) & 3]);
 	};
-	// SCREEN: the same operands in two parts — the hi words for MFMAs 0..5, the lo words only for a chunk that completes
+	// SCREEN: the hi words alone, for MFMAs 0..5 (a chunk that completes reads all four again: fetch)
 	auto fetch_hi = [&]<int U> (m16::BFrag& B, int bc) __attribute__ ((always_inline)) {
 		const lds_u8* const h = smem + (bc & 1) * ARRB + (bc >> 1) * BLKB;
 		B.h0 = *reinterpret_cast<const uint4*> (h + RA[U]);
 		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
-	};
-	auto fetch_lo = [&]<int U> (m16::BFrag& B, int bc) __attribute__ ((always_inline)) {
-		const lds_u8* const l = smem + (2 + (bc & 1)) * ARRB + (bc >> 1) * BLKB;
-		B.l0 = *reinterpret_cast<const uint4*> (l + RA[U]);
-		B.l1 = *reinterpret_cast<const uint4*> (l + RA[(U + 2) & 3]);
-	};
-	// SCREEN: the other two products of a chunk whose first one is in y (operands B): MFMAs 6..17 of m16::block's order
-	auto complete = [&] (const m16::BFrag& B, m16::f4 (&y)[3]) __attribute__ ((always_inline)) {
-		m16::block_mfma<6> (A, B, y);  m16::block_mfma<7> (A, B, y);  m16::block_mfma<8> (A, B, y);
-		m16::block_mfma<9> (A, B, y);  m16::block_mfma<10> (A, B, y); m16::block_mfma<11> (A, B, y);
-		m16::block_mfma<12> (A, B, y); m16::block_mfma<13> (A, B, y); m16::block_mfma<14> (A, B, y);
-		m16::block_mfma<15> (A, B, y); m16::block_mfma<16> (A, B, y); m16::block_mfma<17> (A, B, y);
 	};
 	// |max| of the accumulators of (block, channel) bc into pm
 	auto fold = [&] (const m16::f4 (&y)[3], int bc) __attribute__ ((always_inline)) {
@@ -530,18 +520,13 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	// the products of the call's last step (nothing left to run under them); every chunk folds its predecessor's accumulators
 	// (the first fold is still the step before's)
 	auto products = [&]<int U> () __attribute__ ((always_inline)) {
-		if constexpr (SCREEN) {
-			// (dense: the chunk 7 the last step left for its check is completed here, with the operands it still has in B1)
-			if (y1_pend) { complete (B1, y1); ++n_scr; ++n_fin; }
-			y1_pend = false;
-			n_scr += 8; n_fin += 8;
-		}
+		if constexpr (SCREEN) { n_scr += 8; n_fin += 8; }                // (dense; the step before left nothing pending)
 		fetch.template operator()<U> (B0, 0);
 #pragma unroll
 		for (int bc = 0; bc < 8; bc += 2) {
 			fetch.template operator()<U> (B1, bc + 1);
 			m16::block (A, B0, y0);
-			if (bc == 0) fold (y1, 7); else fold_last (y1, bc - 1);
+			if (bc == 0) { if constexpr (!SCREEN) fold (y1, 7); } else fold_last (y1, bc - 1);
 			if (bc + 2 < 8) fetch.template operator()<U> (B0, bc + 2);
 			m16::block (A, B1, y1);
 			fold_last (y0, bc);
@@ -578,15 +563,14 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			for (int n = 0; n < R; ++n) if (n < lim) pk0 = v2f{fmaxf (pk0.x, fabsf (x[n].x)), fmaxf (pk0.y, fabsf (x[n].y))};
 		}
 		if (__builtin_expect (__ballot (__float_as_uint (ml) >= scl.cap || __float_as_uint (mr) >= scr.cap) != 0, 0)) {
-			// (the last chunk's accumulators of the step before are still waiting for their fold, which chunk 0 does: they
-			// belong to the old scale, so they are folded here, in front of the flush, and cleared)
-			if constexpr (SCREEN) {
-				if (y1_pend) { complete (B1, y1); ++n_scr; ++n_fin; }          // (its operands are still in B1)
-				y1_pend = false;
-			}
-			fold (y1, 7);
+			// (dense: the last chunk's accumulators of the step before are still waiting for their fold, which chunk 0 does: they
+			// belong to the old scale, so they are folded here, in front of the flush, and cleared.  SCREEN: the step before has
+			// voted on all of its chunks and completed the failing ones — nothing is pending)
+			if constexpr (!SCREEN) {
+				fold (y1, 7);
 #pragma unroll
-			for (int p = 0; p < 3; ++p) y1[p] = m16::f4{0.f, 0.f, 0.f, 0.f};
+				for (int p = 0; p < 3; ++p) y1[p] = m16::f4{0.f, 0.f, 0.f, 0.f};
+			}
 			rescale (ml, mr);
 			if constexpr (SCREEN) { if (PROD) fetch_hi.template operator()<U> (B0, 0); }
 			else if (PROD) fetch.template operator()<U> (B0, 0);          // (fetched before the ring was rescaled: again)
@@ -653,7 +637,17 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		auto kseq = [&]<int I> () __attribute__ ((always_inline)) {
 			if constexpr (KW && I < KOPS) kopx<kseq_tab.op[I]> (kc, ks, kw, x, kseq_tab.frame[I]);
 		};
-		auto chunk = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
+		// SCREEN: the vote on chunk K's first product y — the lanes that may reach the running peak, as a wave-uniform mask
+		uint64_t msk[8];
+		auto vote = [&]<int K> (const m16::f4 (&y)[3]) __attribute__ ((always_inline)) {
+			float ca = 0.f, cb = 0.f;
+#pragma unroll
+			for (int p = 0; p < 3; ++p) { ca = max3abs (ca, y[p][0], y[p][1]); cb = max3abs (cb, y[p][2], y[p][3]); }
+			const float pk = fmaxf (fmaxf (pm[K >> 1][K & 1][0], pm[K >> 1][K & 1][1]), ref[K >> 1][K & 1]);
+			const bool below = fmaxf (ca, cb) + eps[K >> 1][K & 1] < pk;           // (false for a NaN anywhere in it)
+			msk[K] = __ballot (!below);
+		};
+		auto chunk =[&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
 			constexpr int PB = (BC + 7) & 7;
 			const v2f xa = x[2 * BC], xb = x[2 * BC + 1];
 			if (PROD && BC < 7) fetch.template operator()<U> (Bn, BC + 1);
@@ -698,31 +692,15 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #undef MTR_M
 		};
 		// The screened chunk: MFMAs 0..5 only, so most of the split, the maxima and the recurrence issue bare (the issue model's
-		// floor: the elimination run without products).  First the check of the previous chunk (its operands are still in Bn: the
-		// fetch of the next chunk's waits for the verdict; its accumulators are ready — a chunk's tail lies behind its last MFMA),
-		// then the fetch, a whole chunk ahead of its use; behind the six MFMAs the scale, the hi words and the lo words' first
-		// halves; then the lo words' second halves, the next step's maxima, six operations of the recurrence and the ring stores
-		// (chunks 6, 7: behind chunk 6's fetch, the last one that reads the slot they overwrite; chunk 7's fetch of the next step
-		// reads them).
+		// floor: the elimination run without products).  No verdict stands between two chunks' products: the next chunk's hi
+		// operands are fetched first, whatever the vote, a whole chunk ahead of their use; behind the six MFMAs the scale, the hi
+		// words and the lo words' first halves; then the lo words' second halves, the next step's maxima, the vote of the PREVIOUS
+		// chunk (its accumulators are complete: this chunk's six MFMAs ran behind them) and six operations of the recurrence.  The
+		// vote leaves its failing lanes as a mask; chunk 7 votes on itself behind its own tail, and the step branches once (the
+		// SCREEN block behind chunk 7, below).
 		auto chunk_s = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
-			constexpr int PB = (BC + 7) & 7;
 			const v2f xa = x[2 * BC], xb = x[2 * BC + 1];
-			if (PROD && (BC != 0 || y1_pend)) {
-				float ca = 0.f, cb = 0.f;
-#pragma unroll
-				for (int p = 0; p < 3; ++p) { ca = max3abs (ca, yp[p][0], yp[p][1]); cb = max3abs (cb, yp[p][2], yp[p][3]); }
-				const float pk = fmaxf (fmaxf (pm[PB >> 1][PB & 1][0], pm[PB >> 1][PB & 1][1]), ref[PB >> 1][PB & 1]);
-				const bool below = fmaxf (ca, cb) + eps[PB >> 1][PB & 1] < pk;       // (false for a NaN anywhere in it)
-				++n_scr;
-				if (__builtin_expect (__ballot (!below) != 0, 0)) {
-					if constexpr (PB < 6) fetch_lo.template operator()<U> (Bn, PB);   // (the ring still holds them: its stores come in chunks 6, 7)
-					complete (Bn, yp);
-					fold (yp, PB);
-					++n_fin;
-				}
-			}
-			if constexpr (BC + 1 >= 6) { if (PROD && BC < 7) fetch.template operator()<U> (Bn, BC + 1); }
-			else if (PROD) fetch_hi.template operator()<U> (Bn, BC + 1);
+			if (PROD && BC < 7) fetch_hi.template operator()<U> (Bn, BC + 1);
 #define MTR_M(I) if (PROD) m16::block_mfma<I> (A, Bc, yc)
 			MTR_M (0);  v2f um = xa * sc2;
 			MTR_M (1);  v2f vm = xb * sc2;
@@ -736,22 +714,14 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			lo_second (ll[BC], hl[BC], vm.x);
 			lo_second (lr[BC], hr[BC], vm.y);
 			nl = max3abs (nl, xn[2 * BC].x, xn[2 * BC + 1].x); nr = max3abs (nr, xn[2 * BC].y, xn[2 * BC + 1].y);
-#define MTR_ST(ARR, W_) \
-			if constexpr (BC == 6) *reinterpret_cast<uint4*> (smem + WS[U] + (ARR) * ARRB) = uint4{W_[0], W_[1], W_[2], W_[3]}; \
-			if constexpr (BC == 7) *reinterpret_cast<uint4*> (smem + (WS[U] ^ 16) + (ARR) * ARRB) = uint4{W_[4], W_[5], W_[6], W_[7]}
+			if constexpr (BC > 0) if (PROD) vote.template operator()<BC - 1> (yp);
 			kseq.template operator()<KGAP * BC + 0> ();
-			MTR_ST (0, hl);
 			kseq.template operator()<KGAP * BC + 1> ();
-			MTR_ST (1, hr);
 			kseq.template operator()<KGAP * BC + 2> ();
-			MTR_ST (2, ll);
 			kseq.template operator()<KGAP * BC + 3> ();
-			MTR_ST (3, lr);
 			kseq.template operator()<KGAP * BC + 4> ();
-			if constexpr (BC == 7) fetch_hi.template operator()<(U + 1) & 3> (Bn, 0);   // (Bn of the last chunk = B0 of the next step)
 			kseq.template operator()<KGAP * BC + 5> ();
-#undef MTR_ST
-			if constexpr (BC == 7) if (PROD) y1_pend = true;
+			if constexpr (BC == 7) if (PROD) vote.template operator()<7> (yc);
 		};
 		auto any_chunk = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
 			if constexpr (SCREEN) chunk_s.template operator()<BC> (Bc, Bn, yc, yp);
@@ -766,7 +736,35 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		SPROF_NOW (c3_); SPROF_ADD (2, c3_ - c2_);
 		any_chunk.template operator()<7> (B1, B0, y1, y0);
 		SPROF_NOW (c4_); SPROF_ADD (3, c4_ - c3_);
-		// the rest of the recurrence's sequence: one packed block
+		if constexpr (SCREEN) {
+			// One branch per step: the chunks some lane of which failed its vote run their three products from zero (m16::block:
+			// MFMAs 0..17 in the dense order, so the dense values bit for bit) on operands read again from the ring — its slot U,
+			// the oldest quarter of every window of this step's products, is overwritten only below — and fold into pm as there.
+			if (PROD) {
+				n_scr += 8;
+				if (__builtin_expect ((msk[0] | msk[1] | msk[2] | msk[3] | msk[4] | msk[5] | msk[6] | msk[7]) != 0, 0)) {
+					[&]<int... Ks> (std::integer_sequence<int, Ks...>) __attribute__ ((always_inline)) {
+						([&] () __attribute__ ((always_inline)) {
+							if (msk[Ks] != 0) { fetch.template operator()<U> (B1, Ks); m16::block (A, B1, y0); fold (y0, Ks); ++n_fin; }
+						} (), ...);
+					} (std::make_integer_sequence<int, 8>{});
+				}
+			}
+			// the step's ring stores (slot U), then the next step's first operands, which read them (Bn of chunk 7 = B0 of the next step)
+			lds_u8* const w0 = smem + WS[U];
+			lds_u8* const w1 = smem + (WS[U] ^ 16);
+			*reinterpret_cast<uint4*> (w0)            = uint4{hl[0], hl[1], hl[2], hl[3]};
+			*reinterpret_cast<uint4*> (w1)            = uint4{hl[4], hl[5], hl[6], hl[7]};
+			*reinterpret_cast<uint4*> (w0 + ARRB)     = uint4{hr[0], hr[1], hr[2], hr[3]};
+			*reinterpret_cast<uint4*> (w1 + ARRB)     = uint4{hr[4], hr[5], hr[6], hr[7]};
+			*reinterpret_cast<uint4*> (w0 + 2 * ARRB) = uint4{ll[0], ll[1], ll[2], ll[3]};
+			*reinterpret_cast<uint4*> (w1 + 2 * ARRB) = uint4{ll[4], ll[5], ll[6], ll[7]};
+			*reinterpret_cast<uint4*> (w0 + 3 * ARRB) = uint4{lr[0], lr[1], lr[2], lr[3]};
+			*reinterpret_cast<uint4*> (w1 + 3 * ARRB) = uint4{lr[4], lr[5], lr[6], lr[7]};
+			fetch_hi.template operator()<(U + 1) & 3> (B0, 0);
+		}
+		SPROF_NOW (c5_); SPROF_ADD (4, c5_ - c4_);
+		// the rest of the recurrence's sequence: one packed block (SCREEN: the ring stores and the fetch above drain under it)
 		if (KW) {
 			[&]<int... Is> (std::integer_sequence<int, Is...>) __attribute__ ((always_inline)) {
 				(kseq.template operator()<8 * KGAP + Is> (), ...);
@@ -782,7 +780,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			ks.z1 = scrub (ks.z1); ks.z2 = scrub (ks.z2); ks.z3 = scrub (ks.z3); ks.z4 = scrub (ks.z4);   // ebu_r128_proc.cc:331-334
 			tile_left = spt; ++tile;
 		}
-		SPROF_NOW (c5_); SPROF_ADD (4, c5_ - c4_); SPROF_ADD (5, c5_ - c0_); SPROF_ADD (6, 1);
+		SPROF_NOW (c6_); SPROF_ADD (5, c6_ - c5_); SPROF_ADD (6, c6_ - c0_); SPROF_ADD (7, 1);
 	};
 
 	// An unaligned tile ends inside a step (the same step and frame for all lanes: every lane starts on a tile boundary).  That

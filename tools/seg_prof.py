@@ -21,9 +21,10 @@ with M.Engine(S, fs, meters, tune_layout=7) as e:
     torch.cuda.synchronize()
     out = (C.c_ulonglong * 8)()
     E.lib.mtr_debug_seg_prof(out)
-    n = max(out[6], 1)
-    names = ["step head: phase 0, scale check, operand fetch 0, 8 loads issued", "chunk 0 (waits for the stream)", "chunks 1-6",
-             "chunk 7 (+ ring stores, next operand fetch)", "the recurrence's packed block (EBU), tile bookkeeping", "whole step"]
+    n = max(out[7], 1)
+    names = ["step head: phase 0, scale check, screen bounds, 8 loads issued", "chunk 0 (waits for the stream)", "chunks 1-6",
+             "chunk 7 (+ its own vote)", "the step's branch, completions, ring stores, next operand fetch (SCREEN)",
+             "the recurrence's packed block (EBU), tile bookkeeping", "whole step"]
     print(what, fs, "steps", n, "seg_stats", e.seg_stats())
     for i, nm in enumerate(names):
         print("  %-70s %9.1f cycles / step" % (nm, out[i] / n))
