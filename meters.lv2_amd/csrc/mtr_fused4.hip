@@ -524,21 +524,14 @@ __global__ void k_history_len (const float* audio, uint64_t stride, uint64_t n_f
 	if (fold_state && touched && i == 0) mtr_fold_truepeak (fold_state + s);
 }
 
-int mtr_launch_history_len (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
-                            uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream)
+int mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
+                        uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream)
 {
-	const uint32_t n = n_streams * MTR_FIR_HALO;
-	hipLaunchKernelGGL (k_history_len, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
-	                    audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state, ends);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-int mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                        float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state, void* stream)
-{
-	const uint32_t n = n_streams * MTR_FIR_HALO;
-	hipLaunchKernelGGL (k_history, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
-	                    audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state);
+	const dim3 grid ((n_streams * MTR_FIR_HALO + 255) / 256);
+	if (ends) hipLaunchKernelGGL (k_history_len, grid, dim3 (256), 0, (hipStream_t) stream,
+	                              audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state, ends);
+	else      hipLaunchKernelGGL (k_history, grid, dim3 (256), 0, (hipStream_t) stream,
+	                              audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

@@ -479,10 +479,9 @@ static int launch_gate (const gate_args_t<LEN>& a, void* stream)
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-int mtr_launch_gate (const mtr_gate_args& a, void* stream) { return launch_gate<false> (a, stream); }
-
-int mtr_launch_gate_len (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream)
+int mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream)
 {
+	if (!frag_lim) return launch_gate<false> (a, stream);
 	mtr_gate_len_args la;
 	static_cast<mtr_gate_args&> (la) = a;
 	la.frag_lim = frag_lim;
@@ -650,21 +649,14 @@ __global__ void k_history_mc_len (const float* audio, uint64_t stride, uint64_t 
 	st->tp_call[0] = st->tp_call[1] = 0;
 }
 
-int mtr_launch_history_mc_len (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
-                               uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                               const uint32_t* ends, void* stream)
-{
-	const uint32_t n = n_streams * MTR_FIR_HALO;
-	hipLaunchKernelGGL (k_history_mc_len, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
-	                    audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state, ends);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
 int mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
-                           uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state, void* stream)
+                           uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                           const uint32_t* ends, void* stream)
 {
-	const uint32_t n = n_streams * MTR_FIR_HALO;
-	hipLaunchKernelGGL (k_history_mc, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
-	                    audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state);
+	const dim3 grid ((n_streams * MTR_FIR_HALO + 255) / 256);
+	if (ends) hipLaunchKernelGGL (k_history_mc_len, grid, dim3 (256), 0, (hipStream_t) stream,
+	                              audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state, ends);
+	else      hipLaunchKernelGGL (k_history_mc, grid, dim3 (256), 0, (hipStream_t) stream,
+	                              audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }

@@ -241,23 +241,17 @@ int  mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream);
 void mtr_kmeter_powers (float omega, double* pw1 /* [3] */);
 uint32_t mtr_kmeter_pieces (uint64_t n_groups);
 int  mtr_fused2_upload_taps (const float* g144);
-int  mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                         float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state /* NULL: k_gate folds the peaks */, void* stream);
-/* ... of a call with per-stream lengths: a stream with ends [s] == 0 keeps its history and is not folded */
-int  mtr_launch_history_len (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
-                             uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream);
-int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, uint32_t n_units, void* stream);
-int  mtr_launch_kwmc_len (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
-/* ... of a call with per-stream lengths: a stream with ends [s] == 0 keeps its history and is not folded */
-int  mtr_launch_history_mc_len (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
-                                uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                                const uint32_t* ends, void* stream);
-/* [S][47][C] history of the multichannel engines; fold_c != NULL: also TruePeakdsp::read () per channel (tp_call -> tp_last,
+/* A trailing `ends` / `frag_lim` (per stream, device memory) selects the instantiation of a call with per-stream lengths; NULL the
+ * dense one.  With lengths a stream with ends [s] == 0 keeps its history and is not folded. */
+int  mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
+                         uint32_t n_streams, mtr_stream_state* fold_state /* NULL: k_gate folds the peaks */, const uint32_t* ends, void* stream);
+int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
+/* [S][47][C] history of the multichannel engines; tp_call != NULL: also TruePeakdsp::read () per channel (tp_call -> tp_last,
  * tp_hold, all [S][C]) and the max over the channels into the stream state's tp_last[0..1] / tp_hold[0..1] */
 int  mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
-                            uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state, void* stream);
-int  mtr_launch_gate (const mtr_gate_args& a, void* stream);
-int  mtr_launch_gate_len (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream);
+                            uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                            const uint32_t* ends, void* stream);
+int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
 int  mtr_launch_bank (const mtr_bank_args& a, void* stream);

@@ -313,13 +313,9 @@ int launch_any (int C, bool ebu, bool tp, const kwmc_args_t<LEN>& a, uint32_t n_
 
 }  // namespace
 
-int mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, uint32_t n_units, void* stream)
+int mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream)
 {
-	return launch_any<false> (C, ebu, tp, a, n_units, (hipStream_t) stream);
-}
-
-int mtr_launch_kwmc_len (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream)
-{
+	if (!ends) return launch_any<false> (C, ebu, tp, a, n_units, (hipStream_t) stream);
 	mtr_kwmc_len_args la;
 	static_cast<mtr_kwmc_args&> (la) = a;
 	la.ends = ends;

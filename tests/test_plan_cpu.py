@@ -1,5 +1,5 @@
 """How the engine tiles and routes a call — the host logic behind mtr_engine_process_* (seg_plan / plan_tiling in
-csrc/mtr_engine.hip), through mtr_plan_query: pure arithmetic, runs without a GPU.
+csrc/mtr_plan.cpp), through mtr_plan_query: pure arithmetic, runs without a GPU.
 
 The reference has no counterpart (it walks its samples one by one, ebumeter/ebu_r128_proc.cc:217-244); what is held here
 is the contract the kernels rely on: tiles cover the call exactly, the lane = time segment kernel only ever gets whole
