@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 /* 2 (unchanged by later additions a client looks up by name: mtr_engine_truepeak_channels; mtr_engine_process_device_lengths,
- *    _process_host_lengths, _stream_frames): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _process_host_lengths, _stream_frames; mtr_engine_process_host_pcm, _process_device_pcm, _pcm_stats, mtr_pcm_sample_bytes,
+ *    mtr_pcm_decode_host): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -188,6 +189,45 @@ int  mtr_engine_process_planar_host (mtr_engine* e, const float* const* channels
  * a full reset — staging buffers, the engine's stream and the kernels' code objects then exist, and the first run() of the
  * host's audio thread costs what every later one does (tests/test_lv2_latency.py) instead of several milliseconds. */
 int  mtr_engine_prepare_host (mtr_engine* e, uint32_t max_block_frames);
+
+/* ---- integer PCM in (decoded on the GPU) ---------------------------------------- */
+
+/* A library or a broadcast day is 16- or 24-bit integer PCM, not float: these entry points take the integers as they are, so
+ * that host-resident audio crosses the host link at 2 (S16) or 3 (S24) bytes per sample instead of 4, and no CPU pass widens it.
+ * Samples of a stream are interleaved by channel exactly as the float entry points expect, any n_channels of the engine.
+ * The conversion is exact integer-to-float: S16 and S24 are exact in f32; S32 is the int-to-float conversion with round to
+ * nearest even, then an exact scale (INT32_MAX -> 1.0f, INT32_MIN -> -1.0f).  Every result is bit for bit that of the float
+ * entry point on mtr_pcm_decode_host () of the same integers.  No reference counterpart (LV2 and JACK hand it floats). */
+#define MTR_PCM_S16  1   /* int16_t, little endian                      x * 2^-15 */
+#define MTR_PCM_S24  2   /* 3 bytes per sample, packed, little endian,
+                            two's complement                            x * 2^-23 */
+#define MTR_PCM_S32  3   /* int32_t, little endian          (float) x * 2^-31     */
+/* Host PCM: mtr_engine_process_host with one more step per chunk of streams — chunk k + 1's INTEGER rows cross the link on the
+ * copy stream, k_pcm (mtr_pcm.hip) turns chunk k into floats on the engine's stream, the meters run on that float chunk, laid
+ * out exactly as mtr_engine_process_host stages it (mtr_engine_set_host_chunk_bytes counts DECODED float bytes here, so the
+ * chunks are those of the float path).  stream s at h_pcm + s * stream_stride_frames * n_channels * sample bytes.
+ * frames == NULL: every stream advances by n_frames (as mtr_engine_process_host); else per-stream lengths with every rule of
+ * mtr_engine_process_host_lengths.  Returns when the caller's memory has been read.  Unknown format, NULL engine or buffer,
+ * stream_stride_frames < n_frames: MTR_ERR_ARG before anything is queued, engine unchanged; n_frames == 0: MTR_OK, nothing done. */
+int  mtr_engine_process_host_pcm (mtr_engine* e, const void* h_pcm, int format, uint64_t n_frames,
+                                  uint64_t stream_stride_frames, const uint64_t* frames);
+/* The same for integer samples already in DEVICE memory: the same chunks without the copy, decoded straight from the caller's
+ * rows (any stride; S16 rows on any even byte, S24 rows on any byte, S32 rows on 4 bytes — rows that start on 16 bytes take the
+ * kernel's 16-byte path).  Asynchronous on `hip_stream` like mtr_engine_process_device.  It costs one extra pass over the batch
+ * on top of the meters (read the sample's 2 .. 4 bytes, write 4): a caller whose floats already exist passes them instead.
+ * The floats live in the engine's two staging buffers of mtr_engine_set_host_chunk_bytes each, and the meters' kernels are planned
+ * for the whole batch: with chunks of few streams they leave the chip idle (the host form hides that under the link) — a caller with
+ * HBM to spare sets the chunk to the decoded batch (n_streams * n_frames * n_channels * 4 bytes). */
+int  mtr_engine_process_device_pcm (mtr_engine* e, const void* d_pcm, int format, uint64_t n_frames,
+                                    uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);
+/* 2, 3, 4; 0 for an unknown format */
+size_t mtr_pcm_sample_bytes (int format);
+/* The conversion on the host, plain C: n_samples from src (any alignment) to dst.  The definition k_pcm is held against. */
+int  mtr_pcm_decode_host (int format, const void* src, size_t n_samples, float* dst);
+/* PCM chunks decoded and bytes of PCM taken since the engine was created; decode_ms = sum of the decode kernels' times while
+ * mtr_engine_timing_enable is on (else 0; synchronises).  With timing on the decode kernel also lies inside its chunk's
+ * first-to-last event span (the fourth value per call of mtr_engine_timing_calls).  Any pointer may be NULL. */
+int  mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, float* decode_ms);
 
 /* Wait for everything queued by process calls (on the caller's stream and on the engine's side stream, below). */
 int  mtr_engine_sync (mtr_engine* e);

@@ -211,14 +211,22 @@ struct mtr_engine {
 	// the chunked host path (mtr_engine_process_host)
 	size_t           host_chunk_bytes = (size_t) 256 << 20;
 	Stream           copy_stream;
-	Event            ev_copied[2], ev_computed[2];
+	Event            ev_copied[2], ev_computed[2];   // per staging buffer: the chunk has landed / its landing buffer has been read
+	// integer PCM in (mtr_engine_process_*_pcm): the host form's integer rows land in two raw buffers of one chunk each, k_pcm
+	// (mtr_pcm.hip) decodes a chunk from there — or from the caller's device rows — into `stage`
+	DevBuf<uint8_t>  pcm_raw;
+	uint64_t         pcm_chunks = 0, pcm_bytes = 0;
+	std::vector<Event> pcm_ev;      // while timing is on: pairs around the decode kernels not yet summed into pcm_ms
+	uint32_t         pcm_timed = 0;
+	float            pcm_ms = 0.f;
 
 	bool timing = false;
-	std::vector<Event> ev;          // groups of EV_PER_CALL: start, fused end, gate begin, gate end (those two on the stream the gate ran on), rest begin, end
+	std::vector<Event> ev;          // groups of EV_PER_CALL: start, fused end, gate begin, gate end (those two on the stream the gate ran on), rest begin, end; a PCM chunk's start in front of its decode
+	std::vector<uint8_t> ev_decode; // per timed call: it began with a decode (its whole span starts at the group's last event, not at the first)
 	uint32_t timed_calls = 0;
 };
 
-constexpr int EV_PER_CALL = 6;
+constexpr int EV_PER_CALL = 7;
 constexpr uint32_t TAIL_AUTO_STREAMS = 4096;       // ... and streams per call
 constexpr uint64_t TAIL_AUTO_FRAMES = 1ull << 24;   // stream-frames per call (134 MB of stereo f32: ~40 us of the fused kernel) from which the tail is deferred
 
@@ -784,15 +792,16 @@ static int build_plan (mtr_engine* e, uint64_t N, uint32_t head, uint32_t body_t
 	return MTR_OK;
 }
 
-static hipEvent_t next_event (mtr_engine* e, size_t idx)
+static hipEvent_t next_event (std::vector<Event>& ev, size_t idx)
 {
-	while (e->ev.size () <= idx) {
+	while (ev.size () <= idx) {
 		Event v;
 		if (v.ensure (hipEventDefault) != hipSuccess) return nullptr;
-		e->ev.push_back (std::move (v));
+		ev.push_back (std::move (v));
 	}
-	return e->ev[idx].v;
+	return ev[idx].v;
 }
+static hipEvent_t next_event (mtr_engine* e, size_t idx) { return next_event (e->ev, idx); }
 
 // ---- one process call -------------------------------------------------------------------------------------------------------
 
@@ -806,6 +815,12 @@ struct Call {
 	const uint64_t* frames;       // per-stream lengths, indexed from the view's first stream, or nullptr
 	bool            chunk;        // a chunk of a host call (mtr_engine_process_host walks the batch view by view), not a batch of its own
 	bool            commit;       // the lock-step cursors move with this call: the last view of a host call, every other call
+	// integer PCM: the call first decodes the view's rows from `pcm` (device memory, row pitch in bytes) into `audio` — a staging buffer
+	// of the engine's — with k_pcm, and records `pcm_read` (if any) behind that: the integer rows have been read
+	const void*     pcm = nullptr;
+	uint64_t        pcm_pitch = 0;
+	int             pcm_format = 0;
+	hipEvent_t      pcm_read = nullptr;
 };
 
 // Where a call goes (pure apart from reading the engine)
@@ -881,8 +896,27 @@ struct CallRun {
 	int mark (int idx, hipStream_t s) const
 	{
 		if (!tm) return MTR_OK;
-		const hipEvent_t v = next_event (e, ev0 + idx);
+		const hipEvent_t v = next_event (e, ev0 + EV_PER_CALL - 1) ? e->ev[ev0 + idx].v : nullptr;   // (the whole group exists or none of it is used)
 		if (v) HIPCHK (hipEventRecord (v, s));
+		return MTR_OK;
+	}
+
+	// A PCM chunk's first step: its integer rows to floats, where the meters will read them
+	int decode ()
+	{
+		const uint64_t n = c.n_frames * e->cfg.n_channels;
+		hipEvent_t t0 = nullptr, t1 = nullptr;
+		if (e->timing && e->pcm_timed < 4096) {
+			t0 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2);
+			t1 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2 + 1);
+		}
+		if (t0 && t1) HIPCHK (hipEventRecord (t0, c.st));
+		if (mtr_launch_pcm (c.pcm_format, c.pcm, c.pcm_pitch, const_cast<float*> (c.audio), c.stride * e->cfg.n_channels, c.cnt, n, c.st))
+			return fail (MTR_ERR_HIP, "k_pcm launch");
+		if (t0 && t1) { HIPCHK (hipEventRecord (t1, c.st)); e->pcm_timed++; }
+		if (c.pcm_read) HIPCHK (hipEventRecord (c.pcm_read, c.st));
+		e->pcm_chunks++;
+		e->pcm_bytes += (uint64_t) c.cnt * n * mtr_setup_pcm_sample_bytes (c.pcm_format);
 		return MTR_OK;
 	}
 
@@ -1185,7 +1219,12 @@ struct CallRun {
 		if ((rc = enter_stream (e, c.st))) return rc;
 		const bool fused = ebu || tp;
 		const uint32_t meters = e->cfg.meters;
+		if (c.pcm && ((rc = mark (6, c.st)) || (rc = decode ()))) return rc;
 		if ((rc = mark (0, c.st))) return rc;
+		if (tm) {
+			if (e->ev_decode.size () <= e->timed_calls) e->ev_decode.resize ((size_t) e->timed_calls + 1);
+			e->ev_decode[e->timed_calls] = c.pcm != nullptr;
+		}
 
 		r = route ();
 		if (r.defer) rc = tail_setup (e);
@@ -1286,18 +1325,34 @@ int mtr_engine_set_host_chunk_bytes (mtr_engine* e, uint64_t bytes)
 	return MTR_OK;
 }
 
-// Host memory in, CHUNKED by streams (results are per stream: chunking is exact, and the routing of a call — which kernel,
+// Where a chunked call takes its samples from: host or device memory, f32 or integer PCM (format MTR_PCM_*, 0 = f32)
+struct Source {
+	const void* p;
+	int         format;
+	bool        host;
+	void*       hip_stream;   // device source: the caller's stream (a host source runs on the engine's own)
+};
+
+// Memory in, CHUNKED by streams (results are per stream: chunking is exact, and the routing of a call — which kernel,
 // how many time segments — is decided for the whole batch, so every stream sees the arithmetic it would see resident):
 // chunk k + 1 crosses the host link on a copy stream while the kernels of chunk k run on the engine's own; two device
 // buffers of one chunk each instead of a copy of the whole batch.  End to end the call runs at the link's rate
 // (bench.py: extra.end_to_end_host).
-static int process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+// Integer PCM is the same loop with one more step: the chunk's INTEGER rows cross the link into one of two raw buffers (rows on 16
+// bytes), and the chunk's call decodes them into the float buffer first (CallRun::decode) — the float chunk is laid out exactly as the
+// float path stages it (same dstride, same chunks: host_chunk_bytes counts decoded bytes), so the meters see the very same call.  The
+// raw buffer is free again once the decode has read it, the float buffer once the meters have: stream order, both on the engine's stream.
+// PCM in device memory: the same chunks without the copy, decoded straight from the caller's rows on the caller's stream.
+static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
 	if (n_frames == 0) return MTR_OK;
 	if (stride < n_frames) return fail (MTR_ERR_ARG, "stream_stride_frames < n_frames");
+	int rc = check_limits (e, n_frames);
+	if (rc) return rc;
 	HIPCHK (hipSetDevice (e->cfg.device));
 	const size_t C = e->cfg.n_channels;
 	const uint32_t S = e->cfg.n_streams;
+	const size_t sb = src.format ? mtr_setup_pcm_sample_bytes (src.format) : sizeof (float);   // bytes per sample at the source
 	// (streams start on 16 bytes in the staging buffers — an even stride of stereo frames, a multiple of four mono ones — so that
 	// every layout can take the call and k_tpb's LDS-DMA its source)
 	const uint64_t dstride = C == 2 ? (n_frames + 1) & ~(uint64_t) 1 : (n_frames + 3) & ~(uint64_t) 3;   // (and 1, 3, 4, 5 channels: a multiple of four frames)
@@ -1306,17 +1361,27 @@ static int process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames,
 	const uint32_t n_chunks = (S + cs - 1) / cs;
 	cs = (S + n_chunks - 1) / n_chunks;                                         // even chunks
 	const size_t buf_floats = ((size_t) cs * row + 63) & ~(size_t) 63;         // the second buffer starts on 256 bytes
-	HIPCHK (e->own_stream.ensure ());
-	const hipStream_t st = e->own_stream.v;
-	int rc = MTR_OK;
-	HIPCHK (e->copy_stream.ensure ());
-	for (int b = 0; b < 2; ++b) {
-		HIPCHK (e->ev_copied[b].ensure ());
-		HIPCHK (e->ev_computed[b].ensure ());
+	const size_t raw_pitch = (n_frames * C * sb + 15) & ~(size_t) 15;          // PCM from the host: bytes per landed row ...
+	const size_t raw_bytes = ((size_t) cs * raw_pitch + 255) & ~(size_t) 255;  // ... and per raw buffer
+	const bool landing = src.host && src.format;
+	hipStream_t st = (hipStream_t) src.hip_stream;
+	if (src.host) {
+		HIPCHK (e->own_stream.ensure ());
+		st = e->own_stream.v;
+		HIPCHK (e->copy_stream.ensure ());
+		for (int b = 0; b < 2; ++b) {
+			HIPCHK (e->ev_copied[b].ensure ());
+			HIPCHK (e->ev_computed[b].ensure ());
+		}
+		// the staging buffers may still be read by the previous call (on whatever stream that ran)
+		HIPCHK (hipStreamSynchronize (e->last_stream));
+	} else if (e->stage.n < buf_floats * (n_chunks > 1 ? 2 : 1)) {
+		// (a device source never waits for the previous call — the chunk's call orders its stream behind it before the decode writes the
+		// staging buffer — unless that buffer has to grow)
+		if ((rc = sync_all (e))) return rc;
 	}
-	// the staging buffers may still be read by the previous call (on whatever stream that ran)
-	HIPCHK (hipStreamSynchronize (e->last_stream));
 	if (e->stage.reserve (buf_floats * (n_chunks > 1 ? 2 : 1))) return fail (MTR_ERR_NOMEM, "hipMalloc staging buffers");
+	if (landing && e->pcm_raw.reserve (raw_bytes * (n_chunks > 1 ? 2 : 1))) return fail (MTR_ERR_NOMEM, "hipMalloc PCM buffers");
 	// (every exit behind the first copy goes through ONE place that waits for the copy stream: the source is pageable caller
 	// memory and the copies are truly asynchronous — the caller may free or reuse it as soon as we return, error or not)
 	hipError_t he = hipSuccess;
@@ -1326,26 +1391,45 @@ static int process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames,
 		const uint32_t cnt = std::min (cs, S - off);
 		const int b = (int) (k & 1);
 		float* const dst = e->stage.p + (size_t) b * buf_floats;
-		if (k >= 2) HOSTCHK (hipStreamWaitEvent (e->copy_stream.v, e->ev_computed[b].v, 0));   // the kernels of chunk k - 2 have read this buffer
-		HOSTCHK (hipMemcpy2DAsync (dst, row * sizeof (float), h_audio + (size_t) off * stride * C, stride * C * sizeof (float),
-		                           n_frames * C * sizeof (float), cnt, hipMemcpyHostToDevice, e->copy_stream.v));
-		HOSTCHK (hipEventRecord (e->ev_copied[b].v, e->copy_stream.v));
-		HOSTCHK (hipStreamWaitEvent (st, e->ev_copied[b].v, 0));
 		// (the lengths of the chunk's streams are indexed from its first; the cursors move with the last chunk)
-		rc = process_call (e, { dst, n_frames, dstride, st, off, cnt, frames ? frames + off : nullptr, true, k + 1 == n_chunks });
+		Call c { dst, n_frames, dstride, st, off, cnt, frames ? frames + off : nullptr, true, k + 1 == n_chunks };
+		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * stride * C * sb;
+		size_t pitch = stride * C * sb;
+		if (src.host) {
+			void* const land = landing ? (void*) (e->pcm_raw.p + (size_t) b * raw_bytes) : (void*) dst;
+			const size_t land_pitch = landing ? raw_pitch : row * sizeof (float);
+			if (k >= 2) HOSTCHK (hipStreamWaitEvent (e->copy_stream.v, e->ev_computed[b].v, 0));   // the kernels of chunk k - 2 have read this buffer
+			HOSTCHK (hipMemcpy2DAsync (land, land_pitch, from, pitch, n_frames * C * sb, cnt, hipMemcpyHostToDevice, e->copy_stream.v));
+			HOSTCHK (hipEventRecord (e->ev_copied[b].v, e->copy_stream.v));
+			HOSTCHK (hipStreamWaitEvent (st, e->ev_copied[b].v, 0));
+			from = (const uint8_t*) land;
+			pitch = land_pitch;
+		}
+		if (src.format) {
+			c.pcm = from;
+			c.pcm_pitch = pitch;
+			c.pcm_format = src.format;
+			if (landing) c.pcm_read = e->ev_computed[b].v;
+		}
+		rc = process_call (e, c);
 		if (rc) goto done;
-		HOSTCHK (hipEventRecord (e->ev_computed[b].v, st));
+		if (src.host && !landing) HOSTCHK (hipEventRecord (e->ev_computed[b].v, st));
 	}
 #undef HOSTCHK
 done:
-	{
+	if (src.host) {
 		// wait for the copies (not for the kernels)
 		const hipError_t hs = hipStreamSynchronize (e->copy_stream.v);
 		if (what) return fail (MTR_ERR_HIP, what, he);
 		if (rc) return rc;
 		if (hs != hipSuccess) return fail (MTR_ERR_HIP, "hipStreamSynchronize (copy stream)", hs);
 	}
-	return MTR_OK;
+	return rc;
+}
+
+static int process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
 }
 
 int mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride)
@@ -1360,6 +1444,56 @@ int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64
 	const int crc = lengths_check (e, n_frames, frames, e->cfg.n_streams);
 	if (crc) return crc;
 	return process_host (e, h_audio, n_frames, stride, frames);
+}
+
+// Integer PCM: what every PCM entry point checks before anything is queued
+static int pcm_check (mtr_engine* e, const void* pcm, int format, uint64_t n_frames, const uint64_t* frames, const char* who)
+{
+	if (!e || !pcm) return fail (MTR_ERR_ARG, who);
+	if (!mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown PCM format (MTR_PCM_S16, _S24, _S32)");
+	return frames ? lengths_check (e, n_frames, frames, e->cfg.n_streams) : MTR_OK;
+}
+
+int mtr_engine_process_host_pcm (mtr_engine* e, const void* h_pcm, int format, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	const int crc = pcm_check (e, h_pcm, format, n_frames, frames, "mtr_engine_process_host_pcm: null argument");
+	if (crc) return crc;
+	return process_chunked (e, { h_pcm, format, true, nullptr }, n_frames, stride, frames);
+}
+
+int mtr_engine_process_device_pcm (mtr_engine* e, const void* d_pcm, int format, uint64_t n_frames, uint64_t stride,
+                                   const uint64_t* frames, void* hip_stream)
+{
+	const int crc = pcm_check (e, d_pcm, format, n_frames, frames, "mtr_engine_process_device_pcm: null argument");
+	if (crc) return crc;
+	return process_chunked (e, { d_pcm, format, false, hip_stream }, n_frames, stride, frames);
+}
+
+size_t mtr_pcm_sample_bytes (int format) { return mtr_setup_pcm_sample_bytes (format); }
+
+int mtr_pcm_decode_host (int format, const void* src, size_t n_samples, float* dst)
+{
+	if (!mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown PCM format (MTR_PCM_S16, _S24, _S32)");
+	if (n_samples && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_pcm_decode_host: null argument");
+	return mtr_setup_pcm_decode (format, src, n_samples, dst) ? fail (MTR_ERR_ARG, "mtr_pcm_decode_host") : MTR_OK;
+}
+
+int mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, float* decode_ms)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if (e->pcm_timed) {
+		const int rc = mtr_engine_sync (e);
+		if (rc) return rc;
+		for (uint32_t i = 0; i < e->pcm_timed && (size_t) 2 * i + 1 < e->pcm_ev.size (); ++i) {
+			float ms;
+			if (hipEventElapsedTime (&ms, e->pcm_ev[2 * i].v, e->pcm_ev[2 * i + 1].v) == hipSuccess) e->pcm_ms += ms;
+		}
+		e->pcm_timed = 0;
+	}
+	if (chunks) *chunks = e->pcm_chunks;
+	if (bytes) *bytes = e->pcm_bytes;
+	if (decode_ms) *decode_ms = e->pcm_ms;
+	return MTR_OK;
 }
 
 // One LV2 block: interleave into page-locked memory, one H2D copy, the kernels, one D2H copy of the stream's state
@@ -1844,7 +1978,8 @@ int mtr_engine_timing_calls (mtr_engine* e, float* out, uint32_t cap, uint32_t* 
 		const Event* const v = &e->ev[(size_t) i * EV_PER_CALL];
 		for (int k = 0; k < 3; ++k)
 			if (hipEventElapsedTime (&o[k], v[2 * k].v, v[2 * k + 1].v) != hipSuccess) o[k] = 0.f;
-		if (hipEventElapsedTime (&o[3], v[0].v, v[5].v) != hipSuccess) o[3] = 0.f;     // (on the caller's stream: a deferred gate is not in it)
+		const int first = i < e->ev_decode.size () && e->ev_decode[i] ? 6 : 0;        // (a PCM chunk's span holds its decode)
+		if (hipEventElapsedTime (&o[3], v[first].v, v[5].v) != hipSuccess) o[3] = 0.f;     // (on the caller's stream: a deferred gate is not in it)
 	}
 	return MTR_OK;
 }

@@ -227,6 +227,8 @@ void mtr_setup_bin_power (float* out100);
 void mtr_setup_kweight_matrix (const float* k7, double* A16, double* B4);
 void mtr_setup_hist_loudness (const int32_t* hist_M, const int32_t* hist_S, float* integ, float* integ_thr,
                               float* rmin, float* rmax, float* rthr);
+size_t mtr_setup_pcm_sample_bytes (int format);
+int  mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst);   /* -1: unknown format */
 #ifdef __cplusplus
 }
 
@@ -263,6 +265,8 @@ int  mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_frames,
 int  mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
                               float* hist_out, uint32_t n_streams, void* stream);
 int  mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint32_t n_streams, int32_t* d_hist, float* d_max, void* stream);
+/* rows of packed integer PCM (format MTR_PCM_*, n_samples per row, pitch in bytes) to rows of f32 (pitch in floats): mtr_pcm.hip */
+int  mtr_launch_pcm (int format, const void* src, uint64_t src_pitch, float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_samples, void* stream);
 int  mtr_launch_synth (float* d_audio, uint32_t n_streams, uint64_t n_frames, uint64_t stride,
                        uint32_t seed, float fs, int kind, void* stream);
 #endif

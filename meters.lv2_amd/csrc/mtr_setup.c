@@ -214,3 +214,43 @@ void mtr_setup_hist_loudness (const int32_t* hm, const int32_t* hs, float* integ
 		*rmax = (hi - 699) / 10.0f;
 	}
 }
+
+/* Integer PCM to float, the contract of include/mtr_engine.h (MTR_PCM_*): little-endian samples read byte-wise through
+ * memcpy (any alignment), S16 / S24 exact, S32 the int-to-float conversion (round to nearest even) and an exact scale.
+ * What k_pcm (mtr_pcm.hip) is held against. */
+size_t mtr_setup_pcm_sample_bytes (int format)
+{
+	return format == MTR_PCM_S16 ? 2 : format == MTR_PCM_S24 ? 3 : format == MTR_PCM_S32 ? 4 : 0;
+}
+
+int mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst)
+{
+	const unsigned char* p = (const unsigned char*) src;
+	switch (format) {
+	case MTR_PCM_S16:
+		for (size_t i = 0; i < n; ++i) {
+			unsigned char b[2];
+			memcpy (b, p + 2 * i, 2);
+			const int32_t v = (int32_t) (((uint32_t) b[0] << 16) | ((uint32_t) b[1] << 24));   /* the sample in the top 16 bits */
+			dst[i] = (float) v * 0x1p-31f;
+		}
+		return 0;
+	case MTR_PCM_S24:
+		for (size_t i = 0; i < n; ++i) {
+			unsigned char b[3];
+			memcpy (b, p + 3 * i, 3);
+			const int32_t v = (int32_t) (((uint32_t) b[0] << 8) | ((uint32_t) b[1] << 16) | ((uint32_t) b[2] << 24));   /* ... the top 24 */
+			dst[i] = (float) v * 0x1p-31f;
+		}
+		return 0;
+	case MTR_PCM_S32:
+		for (size_t i = 0; i < n; ++i) {
+			unsigned char b[4];
+			memcpy (b, p + 4 * i, 4);
+			const int32_t v = (int32_t) ((uint32_t) b[0] | ((uint32_t) b[1] << 8) | ((uint32_t) b[2] << 16) | ((uint32_t) b[3] << 24));
+			dst[i] = (float) v * 0x1p-31f;
+		}
+		return 0;
+	}
+	return -1;
+}

@@ -15,6 +15,7 @@ METER_EBU, METER_TRUEPEAK, METER_SPECTR30, METER_TPBALLIST = 0x01, 0x02, 0x04, 0
 METER_BITSTATS, METER_SIGDIST, METER_DR14, METER_KMETER = 0x10, 0x20, 0x40, 0x80
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
+PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3        # MTR_PCM_*: little-endian int16 / packed 3-byte / int32 samples
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MTR_LIB: an alternative build of the same library (instrumented kernels, tools/f4_prof.py); never a different backend
@@ -113,6 +114,13 @@ def _load():
         L.mtr_engine_process_device_lengths.argtypes = [vp, vp, u64, u64, vp, vp]
         L.mtr_engine_process_host_lengths.argtypes = [vp, vp, u64, u64, vp]
         L.mtr_engine_stream_frames.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "mtr_engine_pcm_stats"):                     # (an addition inside ABI version 2: integer PCM in)
+        L.mtr_engine_process_host_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp]
+        L.mtr_engine_process_device_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp, vp]
+        L.mtr_engine_pcm_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(f32)]
+        L.mtr_pcm_sample_bytes.argtypes = [C.c_int]
+        L.mtr_pcm_sample_bytes.restype = C.c_size_t
+        L.mtr_pcm_decode_host.argtypes = [C.c_int, vp, C.c_size_t, vp]
     L.mtr_engine_set_host_chunk_bytes.argtypes = [vp, u64]
     L.mtr_engine_process_planar_host.argtypes = [vp, C.POINTER(vp), u32]
     L.mtr_engine_results.argtypes = [vp, u32, u32, C.POINTER(StreamResult)]
@@ -224,6 +232,40 @@ def plan_query(n_streams, n_frames, sample_rate=48000.0, meters=METER_EBU | METE
     info = PlanInfo()
     _check(lib.mtr_plan_query(C.byref(cfg), frames_left_in_fragment, n_frames, n_slots, C.byref(info)), "mtr_plan_query")
     return info.as_dict()
+
+
+def _need_pcm():
+    if not hasattr(lib, "mtr_engine_pcm_stats"):
+        raise EngineError(f"{lib_path} has no integer PCM entry points: rebuild it")
+
+
+def _pcm_format(x, format):
+    """The MTR_PCM_* format of an array of integer samples: inferred from int16 / int32, PCM_S24 must be named (packed uint8)."""
+    want = {np.dtype(np.int16): PCM_S16, np.dtype(np.int32): PCM_S32, np.dtype(np.uint8): PCM_S24}.get(x.dtype)
+    if want is None:
+        raise ValueError(f"integer PCM is int16 (PCM_S16), int32 (PCM_S32) or packed uint8 (PCM_S24), not {x.dtype}")
+    if format is None and want == PCM_S24:
+        raise ValueError("uint8 bytes: name the format (format=PCM_S24)")
+    if format is not None and format != want:
+        raise ValueError(f"format {format} does not go with dtype {x.dtype}")
+    return want
+
+
+def pcm_decode(format, array):
+    """mtr_pcm_decode_host: the integer samples of `array` (int16 for PCM_S16, int32 for PCM_S32, packed little-endian uint8 bytes
+    for PCM_S24) as float32 — the same shape, PCM_S24 a third of the last axis.  The definition the GPU decode is held against."""
+    _need_pcm()
+    x = np.ascontiguousarray(array)
+    _pcm_format(x, format)
+    if format == PCM_S24:
+        if x.ndim == 0 or x.shape[-1] % 3:
+            raise ValueError(f"PCM_S24: the last axis holds 3 bytes per sample, not {x.shape}")
+        shape = x.shape[:-1] + (x.shape[-1] // 3,)
+    else:
+        shape = x.shape
+    out = np.empty(shape, np.float32)
+    _check(lib.mtr_pcm_decode_host(format, x.ctypes.data, out.size, out.ctypes.data), "mtr_pcm_decode_host")
+    return out
 
 
 def synth_fill_device(ptr, n_streams, n_frames, stride, seed, fs=48000.0, kind=1, stream=0):
@@ -373,6 +415,39 @@ class Engine:
         f = self._lengths(frames, x.shape[1])
         _check(lib.mtr_engine_process_host_lengths(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
                "process_host_lengths")
+
+    def process_pcm(self, x, format=None, frames=None):
+        """process() for host integer PCM, decoded on the GPU: x int16 or int32 [S, T, C] (or [S, T] mono; the format is inferred),
+        or packed 24-bit samples as uint8 [S, T * C * 3] with format=PCM_S24.  frames: per-stream lengths as process_lengths()."""
+        _need_pcm()
+        x = np.ascontiguousarray(x)
+        fmt = _pcm_format(x, format)
+        C_ = self.n_channels
+        if fmt == PCM_S24:
+            if x.ndim != 2 or x.shape[0] != self.n_streams or x.shape[1] % (3 * C_):
+                raise ValueError(f"PCM_S24: uint8 [{self.n_streams}, T * {C_} * 3], not {x.shape}")
+            n = x.shape[1] // (3 * C_)
+        else:
+            if x.shape[:1] != (self.n_streams,) or not (x.shape[2:] == (C_,) and x.ndim == 3 or (C_ == 1 and x.ndim == 2)):
+                raise ValueError(f"integer PCM: [{self.n_streams}, T, {C_}]" + (" or [S, T]" if C_ == 1 else "") + f", not {x.shape}")
+            n = x.shape[1]
+        f = None if frames is None else self._lengths(frames, n)
+        _check(lib.mtr_engine_process_host_pcm(self._h, x.ctypes.data, fmt, n, n, None if f is None else f.ctypes.data), "process_host_pcm")
+
+    def process_device_pcm(self, ptr, format, n_frames, stride=None, frames=None, stream=0):
+        """process_device() for integer PCM in device memory at `ptr` (stream s at ptr + s * stride * n_channels * sample bytes): one
+        decode pass on top of the meters.  frames: per-stream lengths as process_device_lengths()."""
+        _need_pcm()
+        f = None if frames is None else self._lengths(frames, n_frames)
+        _check(lib.mtr_engine_process_device_pcm(self._h, ptr, int(format), n_frames, stride or n_frames,
+                                                 None if f is None else f.ctypes.data, stream), "process_device_pcm")
+
+    def pcm_stats(self):
+        """(PCM chunks decoded, bytes of PCM taken, ms of the decode kernels while timing was on) since the engine was created."""
+        _need_pcm()
+        a, b, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib.mtr_engine_pcm_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)), "pcm_stats")
+        return a.value, b.value, ms.value
 
     def stream_frames(self, first=0, count=None):
         """(frames, closed): [count] uint64 frames metered per stream since create / reset, [count] bool closed."""
