@@ -27,7 +27,7 @@ extern "C" {
 
 /* 2 (unchanged by later additions a client looks up by name: mtr_engine_truepeak_channels; mtr_engine_process_device_lengths,
  *    _process_host_lengths, _stream_frames; mtr_engine_process_host_pcm, _process_device_pcm, _pcm_stats, mtr_pcm_sample_bytes,
- *    mtr_pcm_decode_host): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -69,7 +69,7 @@ typedef struct {
 	                          * KMETER; not EBU / TRUEPEAK: MTR_ERR_UNSUPPORTED) or 3 .. 5 (EBU / TRUEPEAK only: MTR_ERR_UNSUPPORTED
 	                          * with any other meter).  Multichannel loudness (Ebu_r128_proc::init (nchan, fsamp),
 	                          * ebumeter/ebu_r128_proc.h:26, 104): frames interleaved in the BS.1770 order L R C Ls Rs (5.0; a
-	                          * 5.1 programme is passed without its LFE), channel i weighted by _chan_gain = {1, 1, 1, 1.41, 1.41}
+	                          * 5.1 programme: mtr_engine_set_frame_layout), channel i weighted by _chan_gain = {1, 1, 1, 1.41, 1.41}
 	                          * (ebu_r128_proc.cc:29).  Every 3 .. 5 channel engine runs layout 8 (mtr_kwmc.hip); its true peak
 	                          * is per channel (mtr_engine_truepeak_channels) and truepeak[0] = truepeak[1] = the max over the
 	                          * channels.  0 or more than 5: MTR_ERR_ARG. */
@@ -228,6 +228,35 @@ int  mtr_pcm_decode_host (int format, const void* src, size_t n_samples, float* 
  * mtr_engine_timing_enable is on (else 0; synchronises).  With timing on the decode kernel also lies inside its chunk's
  * first-to-last event span (the fourth value per call of mtr_engine_timing_calls).  Any pointer may be NULL. */
 int  mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, float* decode_ms);
+
+/* ---- frame layouts: meter selected channels of wider frames (5.1 files, multi-programme frames, mono files) ---------------- */
+
+#define MTR_MAX_FRAME_CHANNELS 8
+/* The buffers of every later process call (device, host, lengths, PCM) hold frames of `frame_channels` interleaved samples;
+ * engine channel c is source channel map[c] (map: n_channels entries, each < frame_channels; the same source channel may be named
+ * more than once; frame_channels may be smaller than n_channels).  stream_stride_frames keeps counting frames: stream s starts at
+ * base + s * stride * frame_channels * sample bytes.  Channels the map does not name are never metered, whatever they hold.
+ * frame_channels == 0 (map ignored): back to the default — frames of n_channels, in order.  It describes buffers, not streams:
+ * callable between any two process calls, not part of the state blob, kept across mtr_engine_reset.
+ * frame_channels > MTR_MAX_FRAME_CHANNELS, map == NULL, an entry >= frame_channels: MTR_ERR_ARG, layout unchanged.
+ * mtr_engine_process_planar_host / _prepare_host take planar channels and are not affected.
+ * A 5.1 file (WAVE order L R C LFE Ls Rs) on a 5-channel engine: frame_channels 6, map {0, 1, 2, 4, 5}; the stereo mix in channels
+ * 6 and 7 of an 8-channel frame on a stereo engine: 8, {6, 7}; a mono file on a stereo engine (the reference's mono loudness is the
+ * stereo loudness of L = R): 1, {0, 0}.  A call with a non-default layout runs k_pick (mtr_pick.hip) in front of the meters: the
+ * wide rows (for host memory: as they crossed the link) are decoded and picked into the float chunk the default layout would have
+ * staged — for device memory in chunks of mtr_engine_set_host_chunk_bytes, as mtr_engine_process_device_pcm (set it to the picked
+ * batch where HBM allows) —, so every result is bit for bit that of the default layout on mtr_pick_decode_host () of the same buffer.
+ * One layout is not staged: 6, {0, 1, 2, 4, 5} on a 5-channel engine through mtr_engine_process_device / _device_lengths, whose
+ * kernel reads the 5.1 frames itself (mtr_kwmc.hip: k_kwmc51; the same bits, no extra pass over the batch).  The explicit
+ * identity (frame_channels == n_channels, map 0 .. n_channels - 1) is the default and takes the default's paths. */
+int  mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const uint8_t* map);
+int  mtr_engine_frame_layout (const mtr_engine* e, uint32_t* frame_channels, uint8_t* map /* [n_channels], may be NULL */);
+/* The definition the kernels are held against, plain C on the host (format 0 = f32, else MTR_PCM_*): dst [n_frames][n_channels].
+ * f32 samples are copied as bit patterns, integers convert exactly as mtr_pcm_decode_host does. */
+int  mtr_pick_decode_host (int format, const void* src, size_t n_frames, uint32_t frame_channels,
+                           const uint8_t* map, uint32_t n_channels, float* dst);
+/* chunks that went through the pick kernel / process calls whose kernel read the wide frames itself, since create */
+int  mtr_engine_layout_stats (mtr_engine* e, uint64_t* staged_chunks, uint64_t* direct_calls);
 
 /* Wait for everything queued by process calls (on the caller's stream and on the engine's side stream, below). */
 int  mtr_engine_sync (mtr_engine* e);

@@ -219,6 +219,14 @@ struct mtr_engine {
 	std::vector<Event> pcm_ev;      // while timing is on: pairs around the decode kernels not yet summed into pcm_ms
 	uint32_t         pcm_timed = 0;
 	float            pcm_ms = 0.f;
+	// frame layout (mtr_engine_set_frame_layout): the buffers of a process call hold frames of frame_channels samples, engine channel c
+	// is source channel frame_map[c]; 0 = the default.  `picks`: the layout is not the identity, every chunk goes through k_pick
+	// (mtr_pick.hip) — from the raw landing buffers (host memory) or the caller's rows (device memory) into `stage`
+	uint32_t         frame_channels = 0;
+	uint8_t          frame_map[MTR_MAX_CHANNELS] = { 0, 1, 2, 3, 4 };
+	bool             picks = false;
+	bool             wave51 = false;      // ... and it is 6, {0, 1, 2, 4, 5} on a 5-channel engine: device f32 calls go to k_kwmc51 instead
+	uint64_t         lay_staged = 0, lay_direct = 0;
 
 	bool timing = false;
 	std::vector<Event> ev;          // groups of EV_PER_CALL: start, fused end, gate begin, gate end (those two on the stream the gate ran on), rest begin, end; a PCM chunk's start in front of its decode
@@ -821,6 +829,10 @@ struct Call {
 	uint64_t        pcm_pitch = 0;
 	int             pcm_format = 0;
 	hipEvent_t      pcm_read = nullptr;
+	// frame layout: the rows at `pcm` (format 0: f32) hold frames of pick_fc samples, k_pick decodes and picks them (0: k_pcm on frames of C)
+	uint32_t        pick_fc = 0;
+	// ... or `audio` itself holds WAVE 5.1 frames, [cnt][stride][6], which the 5-channel kernels read themselves (k_kwmc51, k_history_mc51)
+	bool            wave51 = false;
 };
 
 // Where a call goes (pure apart from reading the engine)
@@ -906,17 +918,30 @@ struct CallRun {
 	{
 		const uint64_t n = c.n_frames * e->cfg.n_channels;
 		hipEvent_t t0 = nullptr, t1 = nullptr;
+		if (c.pick_fc && !c.pcm_format) {                          // wide f32 frames: picked, nothing of it counts as PCM
+			if (mtr_launch_pick (0, c.pcm, c.pcm_pitch, c.pick_fc, e->frame_map, e->cfg.n_channels, const_cast<float*> (c.audio),
+			                     c.stride * e->cfg.n_channels, c.cnt, c.n_frames, c.st))
+				return fail (MTR_ERR_HIP, "k_pick launch");
+			if (c.pcm_read) HIPCHK (hipEventRecord (c.pcm_read, c.st));
+			e->lay_staged++;
+			return MTR_OK;
+		}
 		if (e->timing && e->pcm_timed < 4096) {
 			t0 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2);
 			t1 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2 + 1);
 		}
 		if (t0 && t1) HIPCHK (hipEventRecord (t0, c.st));
-		if (mtr_launch_pcm (c.pcm_format, c.pcm, c.pcm_pitch, const_cast<float*> (c.audio), c.stride * e->cfg.n_channels, c.cnt, n, c.st))
+		if (c.pick_fc) {
+			if (mtr_launch_pick (c.pcm_format, c.pcm, c.pcm_pitch, c.pick_fc, e->frame_map, e->cfg.n_channels, const_cast<float*> (c.audio),
+			                     c.stride * e->cfg.n_channels, c.cnt, c.n_frames, c.st))
+				return fail (MTR_ERR_HIP, "k_pick launch");
+			e->lay_staged++;
+		} else if (mtr_launch_pcm (c.pcm_format, c.pcm, c.pcm_pitch, const_cast<float*> (c.audio), c.stride * e->cfg.n_channels, c.cnt, n, c.st))
 			return fail (MTR_ERR_HIP, "k_pcm launch");
 		if (t0 && t1) { HIPCHK (hipEventRecord (t1, c.st)); e->pcm_timed++; }
 		if (c.pcm_read) HIPCHK (hipEventRecord (c.pcm_read, c.st));
 		e->pcm_chunks++;
-		e->pcm_bytes += (uint64_t) c.cnt * n * mtr_setup_pcm_sample_bytes (c.pcm_format);
+		e->pcm_bytes += (uint64_t) c.cnt * c.n_frames * (c.pick_fc ? c.pick_fc : e->cfg.n_channels) * mtr_setup_pcm_sample_bytes (c.pcm_format);
 		return MTR_OK;
 	}
 
@@ -1028,6 +1053,7 @@ struct CallRun {
 		ma.n_streams = c.cnt; ma.n_segs = pl.n_segs; ma.n_tiles = pl.n_tiles; ma.warm_tiles = warm_tiles;
 		ma.n_frames = c.n_frames;
 		set_kweight (e, ma);
+		if (c.wave51) return mtr_launch_kwmc51 (ebu, tp, ma, d_ends, c.cnt * pl.n_segs, c.st);
 		return mtr_launch_kwmc ((int) C, ebu, tp, ma, d_ends, c.cnt * pl.n_segs, c.st);
 	}
 
@@ -1201,7 +1227,9 @@ struct CallRun {
 			if (hrc) return fail (MTR_ERR_HIP, "k_history launch");
 		} else if (tp) {
 			const size_t vc = (size_t) c.off * C;
-			if (mtr_launch_history_mc (c.audio, c.stride, c.n_frames, C, mc_hist (0), mc_hist (1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc, e->mc_tp_hold.p + vc,
+			if (c.wave51 ? mtr_launch_history_mc51 (c.audio, c.stride, c.n_frames, mc_hist (0), mc_hist (1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc,
+			                                        e->mc_tp_hold.p + vc, state, d_ends, c.st)
+			             : mtr_launch_history_mc (c.audio, c.stride, c.n_frames, C, mc_hist (0), mc_hist (1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc, e->mc_tp_hold.p + vc,
 			                           state, d_ends, c.st))
 				return fail (MTR_ERR_HIP, "k_history_mc launch");
 		}
@@ -1271,12 +1299,25 @@ struct CallRun {
 
 static int process_call (mtr_engine* e, const Call& c) { return CallRun { e, c }.run (); }
 
+struct Source;
+static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames, uint64_t stride, const uint64_t* frames);
+static int process_device_picked (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream);
+
 static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
+	// A frame layout.  WAVE 5.1 on a 5-channel engine: k_kwmc51 and k_history_mc51 read the 6-channel frames where they lie (a pick pass
+	// in front of an HBM-bound kernel would read 6/5 and write 5/5 of the batch on top).  Every other map: the wide rows are picked chunk
+	// by chunk into the staging buffers, as device PCM is decoded.
+	const bool direct = e->picks && e->wave51;
+	if (e->picks && !direct) return process_device_picked (e, d_audio, n_frames, stride, frames, hip_stream);
 	if (n_frames == 0) return MTR_OK;
 	if (stride < n_frames) return fail (MTR_ERR_ARG, "stream_stride_frames < n_frames");
 	HIPCHK (hipSetDevice (e->cfg.device));
-	return process_call (e, { d_audio, n_frames, stride, (hipStream_t) hip_stream, 0, e->cfg.n_streams, frames, false, true });
+	Call c { d_audio, n_frames, stride, (hipStream_t) hip_stream, 0, e->cfg.n_streams, frames, false, true };
+	c.wave51 = direct;
+	const int rc = process_call (e, c);
+	if (!rc && direct) e->lay_direct++;
+	return rc;
 }
 
 extern "C" {
@@ -1361,9 +1402,12 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 	const uint32_t n_chunks = (S + cs - 1) / cs;
 	cs = (S + n_chunks - 1) / n_chunks;                                         // even chunks
 	const size_t buf_floats = ((size_t) cs * row + 63) & ~(size_t) 63;         // the second buffer starts on 256 bytes
-	const size_t raw_pitch = (n_frames * C * sb + 15) & ~(size_t) 15;          // PCM from the host: bytes per landed row ...
+	// frame layout: the source rows hold frames of FC samples (the default: C), picked by the chunk's first step as PCM is decoded by it
+	const bool pick = e->picks;
+	const size_t FC = pick ? e->frame_channels : C;
+	const size_t raw_pitch = (n_frames * FC * sb + 15) & ~(size_t) 15;         // PCM / wide frames from the host: bytes per landed row ...
 	const size_t raw_bytes = ((size_t) cs * raw_pitch + 255) & ~(size_t) 255;  // ... and per raw buffer
-	const bool landing = src.host && src.format;
+	const bool landing = src.host && (src.format || pick);
 	hipStream_t st = (hipStream_t) src.hip_stream;
 	if (src.host) {
 		HIPCHK (e->own_stream.ensure ());
@@ -1393,22 +1437,23 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 		float* const dst = e->stage.p + (size_t) b * buf_floats;
 		// (the lengths of the chunk's streams are indexed from its first; the cursors move with the last chunk)
 		Call c { dst, n_frames, dstride, st, off, cnt, frames ? frames + off : nullptr, true, k + 1 == n_chunks };
-		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * stride * C * sb;
-		size_t pitch = stride * C * sb;
+		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * stride * FC * sb;
+		size_t pitch = stride * FC * sb;
 		if (src.host) {
 			void* const land = landing ? (void*) (e->pcm_raw.p + (size_t) b * raw_bytes) : (void*) dst;
 			const size_t land_pitch = landing ? raw_pitch : row * sizeof (float);
 			if (k >= 2) HOSTCHK (hipStreamWaitEvent (e->copy_stream.v, e->ev_computed[b].v, 0));   // the kernels of chunk k - 2 have read this buffer
-			HOSTCHK (hipMemcpy2DAsync (land, land_pitch, from, pitch, n_frames * C * sb, cnt, hipMemcpyHostToDevice, e->copy_stream.v));
+			HOSTCHK (hipMemcpy2DAsync (land, land_pitch, from, pitch, n_frames * FC * sb, cnt, hipMemcpyHostToDevice, e->copy_stream.v));
 			HOSTCHK (hipEventRecord (e->ev_copied[b].v, e->copy_stream.v));
 			HOSTCHK (hipStreamWaitEvent (st, e->ev_copied[b].v, 0));
 			from = (const uint8_t*) land;
 			pitch = land_pitch;
 		}
-		if (src.format) {
+		if (src.format || pick) {
 			c.pcm = from;
 			c.pcm_pitch = pitch;
 			c.pcm_format = src.format;
+			c.pick_fc = pick ? (uint32_t) FC : 0;
 			if (landing) c.pcm_read = e->ev_computed[b].v;
 		}
 		rc = process_call (e, c);
@@ -1426,6 +1471,15 @@ done:
 	}
 	return rc;
 }
+
+}   // extern "C"
+
+static int process_device_picked (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
+{
+	return process_chunked (e, { d_audio, 0, false, hip_stream }, n_frames, stride, frames);
+}
+
+extern "C" {
 
 static int process_host (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
@@ -1493,6 +1547,56 @@ int mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, floa
 	if (chunks) *chunks = e->pcm_chunks;
 	if (bytes) *bytes = e->pcm_bytes;
 	if (decode_ms) *decode_ms = e->pcm_ms;
+	return MTR_OK;
+}
+
+int mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const uint8_t* map)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	const uint32_t C = e->cfg.n_channels;
+	if (frame_channels == 0) {
+		e->frame_channels = 0;
+		for (uint32_t c = 0; c < MTR_MAX_CHANNELS; ++c) e->frame_map[c] = (uint8_t) c;
+		e->picks = e->wave51 = false;
+		return MTR_OK;
+	}
+	if (frame_channels > MTR_MAX_FRAME_CHANNELS) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: frame_channels > MTR_MAX_FRAME_CHANNELS");
+	if (!map) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: null map");
+	bool identity = frame_channels == C;
+	for (uint32_t c = 0; c < C; ++c) {
+		if (map[c] >= frame_channels) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: a map entry >= frame_channels");
+		identity = identity && map[c] == c;
+	}
+	e->frame_channels = frame_channels;
+	for (uint32_t c = 0; c < C; ++c) e->frame_map[c] = map[c];
+	e->picks = !identity;                                          // (the explicit identity is the default and takes its paths)
+	e->wave51 = e->layout == 8 && C == 5 && frame_channels == 6 && map[0] == 0 && map[1] == 1 && map[2] == 2 && map[3] == 4 && map[4] == 5;
+	return MTR_OK;
+}
+
+int mtr_engine_frame_layout (const mtr_engine* e, uint32_t* frame_channels, uint8_t* map)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if (frame_channels) *frame_channels = e->frame_channels ? e->frame_channels : e->cfg.n_channels;
+	if (map) for (uint32_t c = 0; c < e->cfg.n_channels; ++c) map[c] = e->frame_map[c];
+	return MTR_OK;
+}
+
+int mtr_pick_decode_host (int format, const void* src, size_t n_frames, uint32_t frame_channels, const uint8_t* map, uint32_t n_channels, float* dst)
+{
+	if (format && !mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown format (0 = f32, MTR_PCM_S16, _S24, _S32)");
+	if (!map || !frame_channels || frame_channels > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_CHANNELS)
+		return fail (MTR_ERR_ARG, "mtr_pick_decode_host: map / frame_channels / n_channels");
+	if (n_frames && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_pick_decode_host: null argument");
+	return mtr_setup_pick_decode (format, src, n_frames, frame_channels, map, n_channels, dst)
+	       ? fail (MTR_ERR_ARG, "mtr_pick_decode_host: a map entry >= frame_channels") : MTR_OK;
+}
+
+int mtr_engine_layout_stats (mtr_engine* e, uint64_t* staged_chunks, uint64_t* direct_calls)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if (staged_chunks) *staged_chunks = e->lay_staged;
+	if (direct_calls) *direct_calls = e->lay_direct;
 	return MTR_OK;
 }
 

@@ -649,6 +649,48 @@ __global__ void k_history_mc_len (const float* audio, uint64_t stride, uint64_t 
 	st->tp_call[0] = st->tp_call[1] = 0;
 }
 
+// The same two for five channels read from WAVE 5.1 frames (audio [S][stride][6]: L R C LFE Ls Rs, the call k_kwmc51 served): the
+// history itself stays [S][47][5].  ends == NULL: the dense call.
+__global__ void k_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
+                                float* hist_out, uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                                const uint32_t* ends)
+{
+	constexpr uint32_t C = 5, FC = 6;
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= n_streams * MTR_FIR_HALO) return;
+	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
+	const bool touched = !ends || ends[s] != 0;
+	const int64_t f = touched ? (int64_t) n_frames - MTR_FIR_HALO + i : (int64_t) i - MTR_FIR_HALO;
+	for (uint32_t c = 0; c < C; ++c)
+		hist_out[((size_t) s * MTR_FIR_HALO + i) * C + c] = (f >= 0) ? audio[((size_t) s * stride + (size_t) f) * FC + (c < 3 ? c : c + 1)]
+		                                                            : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * C + c];
+	if (!tp_call || !touched || i != 0) return;
+	float last = 0.f, hold = 0.f;
+	for (uint32_t c = 0; c < C; ++c) {
+		const size_t k = (size_t) s * C + c;
+		const float v = __uint_as_float (tp_call[k]);
+		tp_last[k] = v;
+		if (v > tp_hold[k]) tp_hold[k] = v;
+		tp_call[k] = 0;
+		last = fmaxf (last, v);
+		hold = fmaxf (hold, tp_hold[k]);
+	}
+	mtr_stream_state* const st = state + s;
+	st->tp_last[0] = st->tp_last[1] = last;
+	st->tp_hold[0] = st->tp_hold[1] = hold;
+	st->tp_call[0] = st->tp_call[1] = 0;
+}
+
+int mtr_launch_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
+                             uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                             const uint32_t* ends, void* stream)
+{
+	const dim3 grid ((n_streams * MTR_FIR_HALO + 255) / 256);
+	hipLaunchKernelGGL (k_history_mc51, grid, dim3 (256), 0, (hipStream_t) stream,
+	                    audio, stride, n_frames, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state, ends);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
 int mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
                            uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
                            const uint32_t* ends, void* stream)

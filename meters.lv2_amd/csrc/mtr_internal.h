@@ -229,6 +229,8 @@ void mtr_setup_hist_loudness (const int32_t* hist_M, const int32_t* hist_S, floa
                               float* rmin, float* rmax, float* rthr);
 size_t mtr_setup_pcm_sample_bytes (int format);
 int  mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst);   /* -1: unknown format */
+/* frames of fc samples (format 0 = f32, else MTR_PCM_*) to frames of C floats, channel c = source channel map[c]; -1: bad argument */
+int  mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_t fc, const uint8_t* map, uint32_t C, float* dst);
 #ifdef __cplusplus
 }
 
@@ -253,6 +255,12 @@ int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const ui
 int  mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
                             uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
                             const uint32_t* ends, void* stream);
+/* ... and the two for a 5-channel engine whose call's buffer holds WAVE 5.1 frames (a.audio / audio: [S][stride][6], L R C LFE Ls Rs;
+ * mtr_engine_set_frame_layout with 6, {0, 1, 2, 4, 5} on device f32): the kernels read the wide frames themselves */
+int  mtr_launch_kwmc51 (bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
+int  mtr_launch_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
+                              uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
+                              const uint32_t* ends, void* stream);
 int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
@@ -267,6 +275,10 @@ int  mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_fr
 int  mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint32_t n_streams, int32_t* d_hist, float* d_max, void* stream);
 /* rows of packed integer PCM (format MTR_PCM_*, n_samples per row, pitch in bytes) to rows of f32 (pitch in floats): mtr_pcm.hip */
 int  mtr_launch_pcm (int format, const void* src, uint64_t src_pitch, float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_samples, void* stream);
+/* rows of n_frames wide frames (frame_channels samples: format 0 = f32, else MTR_PCM_*; pitch in bytes) to rows of n_frames x n_channels
+ * f32 (pitch in floats), channel c = source channel map[c]: mtr_pick.hip */
+int  mtr_launch_pick (int format, const void* src, uint64_t src_pitch, uint32_t frame_channels, const uint8_t* map, uint32_t n_channels,
+                      float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_frames, void* stream);
 int  mtr_launch_synth (float* d_audio, uint32_t n_streams, uint64_t n_frames, uint64_t stride,
                        uint32_t seed, float fs, int kind, void* stream);
 #endif

@@ -254,3 +254,20 @@ int mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst)
 	}
 	return -1;
 }
+
+/* Frames of fc samples to frames of C floats, channel c = source channel map[c] (mtr_engine_set_frame_layout): f32 samples move as
+ * bit patterns (memcpy: a NaN keeps its payload), integers convert as above.  What k_pick (mtr_pick.hip) is held against. */
+int mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_t fc, const uint8_t* map, uint32_t C, float* dst)
+{
+	const size_t sb = format ? mtr_setup_pcm_sample_bytes (format) : sizeof (float);
+	if (!sb || !map || !fc || !C) return -1;
+	for (uint32_t c = 0; c < C; ++c) if (map[c] >= fc) return -1;
+	const unsigned char* p = (const unsigned char*) src;
+	for (size_t i = 0; i < n_frames; ++i)
+		for (uint32_t c = 0; c < C; ++c) {
+			const unsigned char* s = p + (i * fc + map[c]) * sb;
+			if (format) mtr_setup_pcm_decode (format, s, 1, dst + i * C + c);
+			else memcpy (dst + i * C + c, s, sizeof (float));
+		}
+	return 0;
+}

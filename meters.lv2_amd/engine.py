@@ -121,6 +121,11 @@ def _load():
         L.mtr_pcm_sample_bytes.argtypes = [C.c_int]
         L.mtr_pcm_sample_bytes.restype = C.c_size_t
         L.mtr_pcm_decode_host.argtypes = [C.c_int, vp, C.c_size_t, vp]
+    if hasattr(L, "mtr_engine_set_frame_layout"):              # (an addition inside ABI version 2: frame layouts)
+        L.mtr_engine_set_frame_layout.argtypes = [vp, u32, vp]
+        L.mtr_engine_frame_layout.argtypes = [vp, C.POINTER(u32), vp]
+        L.mtr_engine_layout_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.mtr_pick_decode_host.argtypes = [C.c_int, vp, C.c_size_t, u32, vp, u32, vp]
     L.mtr_engine_set_host_chunk_bytes.argtypes = [vp, u64]
     L.mtr_engine_process_planar_host.argtypes = [vp, C.POINTER(vp), u32]
     L.mtr_engine_results.argtypes = [vp, u32, u32, C.POINTER(StreamResult)]
@@ -268,6 +273,40 @@ def pcm_decode(format, array):
     return out
 
 
+def _need_frames():
+    if not hasattr(lib, "mtr_engine_set_frame_layout"):
+        raise EngineError(f"{lib_path} has no frame layouts: rebuild it")
+
+
+def pick_decode(format, array, map, n_channels=None):
+    """mtr_pick_decode_host: frames of frame_channels samples to frames of n_channels (= len(map)) float32, channel c = source
+    channel map[c].  The last axis of `array` is one frame: float32 [..., frame_channels] for format 0, int16 / int32
+    [..., frame_channels] for PCM_S16 / PCM_S32, packed uint8 [..., frame_channels * 3] for PCM_S24.  Returns [..., n_channels].
+    The definition the GPU pick is held against."""
+    _need_frames()
+    m = np.ascontiguousarray(map, np.uint8)
+    n_channels = m.size if n_channels is None else n_channels
+    if m.ndim != 1 or m.size != n_channels:
+        raise ValueError(f"map: {n_channels} entries, not {m.shape}")
+    x = np.ascontiguousarray(array)
+    if format == 0:
+        if x.dtype != np.float32:
+            raise ValueError(f"format 0 takes float32, not {x.dtype}")
+        fc = x.shape[-1]
+    else:
+        _pcm_format(x, format)
+        if format == PCM_S24:
+            if x.shape[-1] % 3:
+                raise ValueError(f"PCM_S24: the last axis holds frame_channels * 3 bytes, not {x.shape}")
+            fc = x.shape[-1] // 3
+        else:
+            fc = x.shape[-1]
+    out = np.empty(x.shape[:-1] + (n_channels,), np.float32)
+    n_frames = out.size // n_channels
+    _check(lib.mtr_pick_decode_host(int(format), x.ctypes.data, n_frames, fc, m.ctypes.data, n_channels, out.ctypes.data), "mtr_pick_decode_host")
+    return out
+
+
 def synth_fill_device(ptr, n_streams, n_frames, stride, seed, fs=48000.0, kind=1, stream=0):
     _check(lib.mtr_synth_fill_device(ptr, n_streams, n_frames, stride, seed, fs, kind, stream),
            "mtr_synth_fill_device")
@@ -387,10 +426,18 @@ class Engine:
     def process_device(self, ptr, n_frames, stride=None, stream=0):
         _check(lib.mtr_engine_process_device(self._h, ptr, n_frames, stride or n_frames, stream), "process_device")
 
-    def process(self, x):
-        """x: host float32 [S, T, C] (or [S, T] mono), C = n_channels."""
+    def _frames_f32(self, x):
+        """x as contiguous float32 [S, T, W] (or [S, T] where W == 1), W = the frame width the process calls take: n_channels, or
+        frame_channels once a layout is set — a narrower array would be read past its end, a wider one mis-metered"""
         x = np.ascontiguousarray(x, np.float32)
-        assert x.shape[0] == self.n_streams
+        W = self._width()
+        if x.shape[:1] != (self.n_streams,) or not (x.ndim == 3 and x.shape[2] == W or (W == 1 and x.ndim == 2)):
+            raise ValueError(f"float32 [{self.n_streams}, T, {W}]" + (" or [S, T]" if W == 1 else "") + f", not {x.shape}")
+        return x
+
+    def process(self, x):
+        """x: host float32 [S, T, W] (or [S, T] where W == 1), W = n_channels, or frame_channels once set_frame_layout() set one."""
+        x = self._frames_f32(x)
         _check(lib.mtr_engine_process_host(self._h, x.ctypes.data, x.shape[1], x.shape[1]), "process_host")
 
     def _lengths(self, frames, n_frames):
@@ -409,9 +456,8 @@ class Engine:
                "process_device_lengths")
 
     def process_lengths(self, x, frames):
-        """process() with per-stream lengths: x host float32 [S, T, C], frames [S] <= T."""
-        x = np.ascontiguousarray(x, np.float32)
-        assert x.shape[0] == self.n_streams
+        """process() with per-stream lengths: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        x = self._frames_f32(x)
         f = self._lengths(frames, x.shape[1])
         _check(lib.mtr_engine_process_host_lengths(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
                "process_host_lengths")
@@ -422,7 +468,7 @@ class Engine:
         _need_pcm()
         x = np.ascontiguousarray(x)
         fmt = _pcm_format(x, format)
-        C_ = self.n_channels
+        C_ = self._width()                                       # (frames of frame_channels samples once a layout is set)
         if fmt == PCM_S24:
             if x.ndim != 2 or x.shape[0] != self.n_streams or x.shape[1] % (3 * C_):
                 raise ValueError(f"PCM_S24: uint8 [{self.n_streams}, T * {C_} * 3], not {x.shape}")
@@ -448,6 +494,34 @@ class Engine:
         a, b, ms = C.c_uint64(), C.c_uint64(), C.c_float()
         _check(lib.mtr_engine_pcm_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)), "pcm_stats")
         return a.value, b.value, ms.value
+
+    def set_frame_layout(self, frame_channels, map=None):
+        """The buffers of every later process call hold frames of `frame_channels` samples, engine channel c = source channel map[c]
+        (mtr_engine_set_frame_layout); frame_channels 0: back to frames of n_channels.  process / process_lengths / process_pcm then take
+        [S, T, frame_channels] arrays (PCM_S24: uint8 [S, T * frame_channels * 3])."""
+        _need_frames()
+        m = None if map is None else np.ascontiguousarray(map, np.uint8)
+        if m is not None and m.shape != (self.n_channels,):
+            raise ValueError(f"map: one source channel per engine channel, shape ({self.n_channels},), not {m.shape}")
+        _check(lib.mtr_engine_set_frame_layout(self._h, int(frame_channels), None if m is None else m.ctypes.data), "set_frame_layout")
+
+    def frame_layout(self):
+        """(frame_channels, map) as mtr_engine_frame_layout reads them back: map a tuple of n_channels source channels."""
+        _need_frames()
+        fc, m = C.c_uint32(), np.zeros(self.n_channels, np.uint8)
+        _check(lib.mtr_engine_frame_layout(self._h, C.byref(fc), m.ctypes.data), "frame_layout")
+        return fc.value, tuple(int(v) for v in m)
+
+    def layout_stats(self):
+        """(chunks that went through the pick kernel, process calls whose kernel read the wide frames itself) since create"""
+        _need_frames()
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib.mtr_engine_layout_stats(self._h, C.byref(a), C.byref(b)), "layout_stats")
+        return a.value, b.value
+
+    def _width(self):
+        """samples per frame of the buffers a process call takes"""
+        return self.frame_layout()[0] if hasattr(lib, "mtr_engine_set_frame_layout") else self.n_channels
 
     def stream_frames(self, first=0, count=None):
         """(frames, closed): [count] uint64 frames metered per stream since create / reset, [count] bool closed."""
