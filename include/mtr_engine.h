@@ -27,7 +27,8 @@ extern "C" {
 
 /* 2 (unchanged by later additions a client looks up by name: mtr_engine_truepeak_channels; mtr_engine_process_device_lengths,
  *    _process_host_lengths, _stream_frames; mtr_engine_process_host_pcm, _process_device_pcm, _pcm_stats, mtr_pcm_sample_bytes,
- *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host; MTR_METER_STCORR, mtr_stcorr_coef,
+ *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -52,6 +53,7 @@ extern "C" {
 #define MTR_METER_SIGDIST    0x20u  /* signal distribution histogram                (src/sigdistlv2.c:303-318) */
 #define MTR_METER_DR14       0x40u  /* DR-14 dynamic range (dr_operation_mode)      (src/dr14.c:283-352, 394-412) */
 #define MTR_METER_KMETER     0x80u  /* Kmeterdsp: RMS + peak with hold / fall-back  (jmeters/kmeterdsp.cc:56-140) */
+#define MTR_METER_STCORR     0x200u /* Stcorrdsp: stereo phase correlation          (jmeters/stcorrdsp.cc:47-93); 0x100 is no meter */
 
 #define MTR_HIST_LEN   751          /* src/uris.h:45  HIST_LEN */
 #define MTR_NBANDS     30           /* src/spectrumlv2.c:33  FILTER_COUNT */
@@ -66,7 +68,7 @@ typedef struct {
 	uint32_t meters;         /* MTR_METER_* mask */
 	uint32_t n_streams;      /* independent streams in the batch (>= 1) */
 	uint32_t n_channels;     /* 2 (interleaved stereo frames), 1 (mono: SPECTR30 / TPBALLIST / BITSTATS / SIGDIST / DR14 /
-	                          * KMETER; not EBU / TRUEPEAK: MTR_ERR_UNSUPPORTED) or 3 .. 5 (EBU / TRUEPEAK only: MTR_ERR_UNSUPPORTED
+	                          * KMETER; not EBU / TRUEPEAK / STCORR: MTR_ERR_UNSUPPORTED) or 3 .. 5 (EBU / TRUEPEAK only: MTR_ERR_UNSUPPORTED
 	                          * with any other meter).  Multichannel loudness (Ebu_r128_proc::init (nchan, fsamp),
 	                          * ebumeter/ebu_r128_proc.h:26, 104): frames interleaved in the BS.1770 order L R C Ls Rs (5.0; a
 	                          * 5.1 programme: mtr_engine_set_frame_layout), channel i weighted by _chan_gain = {1, 1, 1, 1.41, 1.41}
@@ -333,6 +335,9 @@ int  mtr_engine_dr14_reset (mtr_engine* e);
 int  mtr_engine_kmeter_read (mtr_engine* e, uint32_t first, uint32_t count, float* rms, float* peak);
 /* replaces: Kmeterdsp::reset (:142-146) */
 int  mtr_engine_kmeter_reset (mtr_engine* e);
+
+/* Stcorrdsp for a batch (MTR_METER_STCORR): mtr_stcorr_coef and mtr_engine_stcorr_set_period / _read / _series / _reset */
+#include "mtr_stcorr.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

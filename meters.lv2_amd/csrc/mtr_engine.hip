@@ -113,6 +113,8 @@ struct Cursors {
 	uint64_t dr_scnt = 0;         // samples in the open DR-14 window
 	uint32_t km_fpp = 0;          // Kmeterdsp's frames per period and the fall-back factor that goes with it
 	float    km_fall = 0.f;
+	uint64_t sc_fill = 0;         // STCORR: frames in the open period of the reading series ...
+	uint64_t sc_points = 0;       // ... and periods completed since reset
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 };
 
@@ -187,6 +189,12 @@ struct mtr_engine {
 	DevBuf<double>             km_piece;
 	DevBuf<float>              km_max;
 	double                     km_pw1[3];
+	DevBuf<mtr_stcorr_state>   sc_state;      // [S]
+	DevBuf<double>             sc_piece;      // [S][pieces][MTR_STCORR_PIECE]
+	DevBuf<float>              sc_series;     // [S][sc_cap]
+	uint32_t                   sc_period = 0, sc_cap = 0;   // frames per process () of the series (0: the call), points per stream it holds
+	float                      sc_w[2];       // w1, w2 of Stcorrdsp::init
+	uint32_t                   sc_warm = 0, sc_chunk = 0;   // mtr_stcorr_geometry
 	// layout 8 (n_channels 1, 3, 4, 5 with EBU / TRUEPEAK, mtr_kwmc.hip): per-channel side buffers; the stream state's kz / tp_* stay unused
 	// by the kernel, its tp_last / tp_hold [0..1] carry the max over the channels (k_history_mc)
 	DevBuf<float>    mc_kz;         // [S][C][4]
@@ -419,10 +427,12 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	if (cfg->n_streams == 0 || !(cfg->sample_rate >= 8000.f) || cfg->meters == 0) return fail (MTR_ERR_ARG, "mtr_engine_create: n_streams / sample_rate / meters");
 	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_CHANNELS) return fail (MTR_ERR_ARG, "n_channels must be 1 .. 5");
 	if (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_SPECTR30 | MTR_METER_TPBALLIST | MTR_METER_BITSTATS
-	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER))
+	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_STCORR))
 		return fail (MTR_ERR_ARG, "unknown bits in the meters mask");
 	if (cfg->n_channels == 1 && (cfg->meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
 		return fail (MTR_ERR_UNSUPPORTED, "EBU / TRUEPEAK take 2 .. 5 channels, not mono");
+	if (cfg->n_channels == 1 && (cfg->meters & MTR_METER_STCORR))
+		return fail (MTR_ERR_UNSUPPORTED, "STCORR is the correlation of a stereo pair: n_channels 2");
 	// 3 .. 5 channels: EBU R128 and true peak only (Ebu_r128_proc::init takes up to five, ebumeter/ebu_r128_proc.h:26)
 	if (cfg->n_channels > 2 && (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
 		return fail (MTR_ERR_UNSUPPORTED, "3 .. 5 channels: only EBU and TRUEPEAK meter them");
@@ -465,6 +475,8 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	e->pos.frcnt = e->fragm;
 	mtr_setup_kweight (cfg->sample_rate, e->kw);
 	e->omega = 1.0f - expf (-2.0 * M_PI * 1.0 / (double) cfg->sample_rate);   // spectrumlv2.c:98
+	mtr_setup_stcorr (cfg->sample_rate, e->sc_w);
+	mtr_stcorr_geometry (e->sc_w[0], &e->sc_warm, &e->sc_chunk);
 
 	const uint32_t S = cfg->n_streams;
 	int rc = MTR_OK;
@@ -554,7 +566,81 @@ int mtr_engine_reset (mtr_engine* e)
 	e->last_deferred = false;
 	if (e->cfg.meters & MTR_METER_DR14) { const int drc = mtr_engine_dr14_reset (e); if (drc) return drc; }
 	if (e->cfg.meters & MTR_METER_KMETER) { const int krc = mtr_engine_kmeter_reset (e); if (krc) return krc; e->pos.km_fpp = 0; e->pos.km_fall = 0.f; }
+	if (e->cfg.meters & MTR_METER_STCORR) { const int src = mtr_engine_stcorr_reset (e); if (src) return src; }
 	if (e->cfg.meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) return mtr_engine_intstat_reset (e);
+	return MTR_OK;
+}
+
+int mtr_stcorr_coef (float sample_rate, float* out2)
+{
+	if (!out2 || !(sample_rate >= 1.f)) return fail (MTR_ERR_ARG, "mtr_stcorr_coef");
+	mtr_setup_stcorr (sample_rate, out2);
+	return MTR_OK;
+}
+
+static int no_stcorr (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_STCORR); }
+
+int mtr_engine_stcorr_reset (mtr_engine* e)
+{
+	if (no_stcorr (e)) return fail (MTR_ERR_ARG, "no STCORR in this engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t S = e->cfg.n_streams;
+	if (e->sc_state.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR state");
+	std::vector<mtr_stcorr_state> h (S);
+	memset (h.data (), 0, S * sizeof (mtr_stcorr_state));          // stcorrdsp.cc:33-36
+	for (auto& v : h) v.period = e->sc_period;
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemcpy (e->sc_state.p, h.data (), S * sizeof (mtr_stcorr_state), hipMemcpyHostToDevice));
+	e->pos.sc_fill = 0;
+	e->pos.sc_points = 0;
+	return MTR_OK;
+}
+
+int mtr_engine_stcorr_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
+{
+	if (no_stcorr (e)) return fail (MTR_ERR_ARG, "no STCORR in this engine");
+	if (period_frames && (period_frames < (uint32_t) e->cfg.sample_rate / 20 || period_frames >= 0x7fffffffu))
+		return fail (MTR_ERR_ARG, "mtr_engine_stcorr_set_period: a period is 0 or at least (uint32_t) sample_rate / 20 frames");
+	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_stcorr_set_period: only on an engine that has processed nothing since create / reset");
+	HIPCHK (hipSetDevice (e->cfg.device));
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	const size_t n = (size_t) e->cfg.n_streams * capacity_points;
+	if (n && e->sc_series.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR series");
+	if (n) HIPCHK (hipMemset (e->sc_series.p, 0, n * sizeof (float)));
+	e->sc_period = period_frames;
+	e->sc_cap = capacity_points;
+	return mtr_engine_stcorr_reset (e);
+}
+
+int mtr_engine_stcorr_read (mtr_engine* e, uint32_t first, uint32_t count, float* corr, float* state5)
+{
+	if (no_stcorr (e) || !corr) return fail (MTR_ERR_ARG, "no STCORR in this engine");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
+	HIPCHK (hipSetDevice (e->cfg.device));
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	std::vector<mtr_stcorr_state> h (count);
+	if (count) HIPCHK (hipMemcpy (h.data (), e->sc_state.p + first, count * sizeof (mtr_stcorr_state), hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < count; ++i) {
+		corr[i] = h[i].corr;
+		if (state5) memcpy (state5 + (size_t) i * 5, h[i].z, sizeof (h[i].z));
+	}
+	return MTR_OK;
+}
+
+int mtr_engine_stcorr_series (mtr_engine* e, uint32_t first, uint32_t count, float* out, uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	if (no_stcorr (e)) return fail (MTR_ERR_ARG, "no STCORR in this engine");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
+	const uint64_t n = e->pos.sc_points, kept = std::min<uint64_t> (n, e->sc_cap);
+	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
+	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
+	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	if (!out || !count || !take) return MTR_OK;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemcpy2D (out, (size_t) capacity * sizeof (float), e->sc_series.p + (size_t) first * e->sc_cap, (size_t) e->sc_cap * sizeof (float),
+	                     take * sizeof (float), count, hipMemcpyDeviceToHost));
 	return MTR_OK;
 }
 
@@ -858,6 +944,8 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 		return fail (MTR_ERR_ARG, "BITSTATS / SIGDIST: n_frames per call must be < 2^31 - 1");
 	if ((e->cfg.meters & MTR_METER_KMETER) && n_frames >= 0x7fffffffull)
 		return fail (MTR_ERR_ARG, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)");
+	if ((e->cfg.meters & MTR_METER_STCORR) && n_frames >= 0x7fffffffull)
+		return fail (MTR_ERR_ARG, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)");
 	if ((e->cfg.meters & MTR_METER_TPBALLIST) && n_frames >= 0x7ffff000ull)
 		return fail (MTR_ERR_ARG, "TPBALLIST: n_frames per call must be < 2^31 - 4096");
 	if ((e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)) && n_frames >= 0xFFFFFFFFull)
@@ -1203,6 +1291,28 @@ struct CallRun {
 		return MTR_OK;
 	}
 
+	// The periods of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+	int stcorr ()
+	{
+		const size_t vo = c.off;
+		const uint64_t P = e->sc_period;
+		mtr_stcorr_args sa;
+		sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
+		sa.period = P; sa.e0 = P ? P - e->pos.sc_fill : c.n_frames;
+		sa.n_streams = c.cnt; sa.chunk = e->sc_chunk; sa.warm = e->sc_warm;
+		sa.n_pieces = mtr_stcorr_pieces (c.n_frames, sa.e0, P, sa.chunk);
+		sa.w1 = e->sc_w[0]; sa.w2 = e->sc_w[1];
+		sa.capacity = e->sc_cap; sa.point0 = e->pos.sc_points;
+		if (e->sc_piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_STCORR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR pieces");
+		sa.state = e->sc_state.p + vo; sa.piece = e->sc_piece.p + vo * sa.n_pieces * MTR_STCORR_PIECE;
+		sa.series = e->sc_cap ? e->sc_series.p + vo * e->sc_cap : nullptr;
+		if (mtr_launch_stcorr (sa, c.st)) return fail (MTR_ERR_HIP, "k_stcorr launch");
+		const uint64_t tot = e->pos.sc_fill + c.n_frames;
+		nx.sc_fill = P ? tot % P : 0;
+		nx.sc_points = e->pos.sc_points + (P ? tot / P : 0);
+		return MTR_OK;
+	}
+
 	int tpb () const
 	{
 		mtr_tpb_args ta;
@@ -1274,6 +1384,7 @@ struct CallRun {
 		if ((meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) && (rc = intstat ())) return rc;
 		if ((meters & MTR_METER_DR14) && (rc = dr14 ())) return rc;
 		if ((meters & MTR_METER_KMETER) && (rc = kmeter ())) return rc;
+		if ((meters & MTR_METER_STCORR) && (rc = stcorr ())) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, or the fused kernels)
@@ -1899,6 +2010,9 @@ std::vector<StateSection> state_sections (const mtr_engine* e)
 		v.push_back ({ e->mc_tp_last.p, C * sizeof (float) });
 		v.push_back ({ e->mc_tp_hold.p, C * sizeof (float) });
 	}
+	// (the LAST section, and only of an engine with the bit: every other blob is byte for byte what it was.  The header has no room
+	// for the period and the frames into the open one: they travel in every stream's mtr_stcorr_state, written by the export)
+	if (m & MTR_METER_STCORR) v.push_back ({ e->sc_state.p, sizeof (mtr_stcorr_state) });
 	return v;
 }
 
@@ -1949,6 +2063,14 @@ int mtr_engine_state_export (mtr_engine* e, uint32_t first, uint32_t count, void
 		if (count) HIPCHK (hipMemcpy (o, static_cast<const unsigned char*> (s.base) + (size_t) first * s.elem, (size_t) count * s.elem, hipMemcpyDeviceToHost));
 		o += (size_t) count * s.elem;
 	}
+	if (e->cfg.meters & MTR_METER_STCORR)
+		for (uint32_t k = 0; k < count; ++k) {                   // the host's cursors, not whatever the device copy holds
+			mtr_stcorr_state v;
+			unsigned char* const at = o - (size_t) (count - k) * sizeof (v);
+			memcpy (&v, at, sizeof (v));
+			v.period = e->sc_period; v.fill = (uint32_t) e->pos.sc_fill;
+			memcpy (at, &v, sizeof (v));
+		}
 	h.payload_fnv = fnv1a64 (o0, (size_t) (o - o0));
 	memcpy (blob, &h, sizeof (h));
 	return MTR_OK;
@@ -1980,6 +2102,19 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	// speed included, whatever integr_start / spectr_set_speed said before: they are part of where the streams stand — any other
 	// must stand at the same ones
 	const bool fresh = !e->advanced;
+	uint32_t sc_period = e->sc_period, sc_fill = (uint32_t) e->pos.sc_fill;
+	if ((e->cfg.meters & MTR_METER_STCORR) && h.count) {
+		const unsigned char* const sec = i0 + (size_t) h.count * (h.per_stream_bytes - sizeof (mtr_stcorr_state));
+		for (uint32_t k = 0; k < h.count; ++k) {
+			mtr_stcorr_state v;
+			memcpy (&v, sec + (size_t) k * sizeof (v), sizeof (v));
+			if (k == 0) { sc_period = v.period; sc_fill = v.fill; }
+			if (v.period != sc_period || v.fill != sc_fill || (sc_period ? sc_fill >= sc_period || sc_period < (uint32_t) e->cfg.sample_rate / 20 : sc_fill != 0))
+				return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (period of the STCORR series)");
+		}
+		if (!fresh && (sc_period != e->sc_period || sc_fill != e->pos.sc_fill))
+			return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period of the STCORR series)");
+	}
 	if (!fresh && (e->pos.frcnt != h.frcnt || e->integr != (h.integr != 0) || e->omega != h.omega || e->pos.dr_scnt != h.dr_scnt))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (fragment phase, integration, bank speed or DR-14 window)");
 	rc = mtr_engine_sync (e);
@@ -1996,6 +2131,7 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->omega = h.omega; e->pos.dr_scnt = h.dr_scnt;
+		e->sc_period = sc_period; e->pos.sc_fill = sc_fill;
 		e->plan.valid = false;
 		e->advanced = true;
 	}

@@ -205,6 +205,33 @@ typedef struct mtr_kmeter_args {
 	float*          piece_max;    /* [S][n_pieces][2] */
 } mtr_kmeter_args;
 
+/* Stcorrdsp per-stream state (jmeters/stcorrdsp.h: _zl _zr _zlr _zll _zrr), the last reading, and — for the state blob, whose header has
+ * no room for them — the engine's period and the frames into the open period (the host's copies rule; export writes them in) */
+typedef struct mtr_stcorr_state {
+	float    z[5];                /* zl zr zlr zll zrr */
+	float    corr;                /* Stcorrdsp::read () at the end of the most recent process (): the call (period 0) or the last completed period */
+	uint32_t period, fill;
+} mtr_stcorr_state;
+
+#define MTR_STCORR_PIECE 9         /* doubles per (stream, piece): the sums of zlr zll zrr carried to the piece's end, zl and zr there; of a piece
+                                    * that starts where a period ended inside the call also sum c rho zl, sum c rho zr (rho = (1 - w1)^(frames
+                                    * since the period end): what the sums owe to the start state) and the zl, zr it started from */
+typedef struct mtr_stcorr_args {
+	const float*    audio;        /* [S][stride][2] */
+	uint64_t        stride, n_frames;
+	uint64_t        period;       /* frames per process () of the reading series; 0: the call is one process () */
+	uint64_t        e0;           /* call frame at which the period open on entry ends (period 0: n_frames) */
+	uint32_t        n_streams, n_pieces;
+	uint32_t        chunk;        /* a period is cut into pieces of at most this many frames */
+	uint32_t        warm;         /* frames in front of a piece over which its first-stage state is rebuilt */
+	float           w1, w2;
+	uint32_t        capacity;     /* points per stream the series holds */
+	uint64_t        point0;       /* periods completed before this call: the series index of the first one that ends in it */
+	mtr_stcorr_state* state;      /* [S] */
+	double*         piece;        /* [S][n_pieces][MTR_STCORR_PIECE] */
+	float*          series;       /* [S][capacity], NULL if capacity == 0 */
+} mtr_stcorr_args;
+
 typedef struct mtr_tpb_args mtr_tpb_args;
 struct mtr_tpb_args {
 	const float*    audio;        /* [S][stride][C] */
@@ -231,6 +258,7 @@ size_t mtr_setup_pcm_sample_bytes (int format);
 int  mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst);   /* -1: unknown format */
 /* frames of fc samples (format 0 = f32, else MTR_PCM_*) to frames of C floats, channel c = source channel map[c]; -1: bad argument */
 int  mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_t fc, const uint8_t* map, uint32_t C, float* dst);
+void mtr_setup_stcorr (float fsamp, float* out2);   /* w1, w2 of Stcorrdsp::init ((int) fsamp, 2e3f, 0.3f) */
 #ifdef __cplusplus
 }
 
@@ -244,6 +272,10 @@ int  mtr_launch_dr14 (const mtr_dr14_args& a, void* stream);
 int  mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream);
 void mtr_kmeter_powers (float omega, double* pw1 /* [3] */);
 uint32_t mtr_kmeter_pieces (uint64_t n_groups);
+/* mtr_stcorr.hip: the warm-up and the piece size that go with w1; the pieces of a call (its periods, each cut at `chunk`); the launch */
+void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk);
+uint32_t mtr_stcorr_pieces (uint64_t n_frames, uint64_t e0, uint64_t period, uint32_t chunk);
+int  mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream);
 int  mtr_fused2_upload_taps (const float* g144);
 /* A trailing `ends` / `frag_lim` (per stream, device memory) selects the instantiation of a call with per-stream lengths; NULL the
  * dense one.  With lengths a stream with ends [s] == 0 keeps its history and is not folded. */

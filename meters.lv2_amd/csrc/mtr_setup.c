@@ -271,3 +271,12 @@ int mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_
 		}
 	return 0;
 }
+
+/* Stcorrdsp::init ((int) fsamp, 2e3f, 0.3f) as the plugins call it (jmeters/stcorrdsp.cc:85-93; src/meters.cc:202-207) */
+void mtr_setup_stcorr (float fsamp, float* out2)
+{
+	const int fs = (int) fsamp;
+	const float flp = 2e3f, tcf = 0.3f;
+	out2[0] = 6.28f * flp / fs;
+	out2[1] = 1 / (tcf * fs);
+}

@@ -1,0 +1,359 @@
+// mtr_stcorr.hip — Stcorrdsp (the COR plugin's, the goniometer's and the surround plugins' stereo phase correlation) for a
+// batch (gfx950).
+//
+// Replaces Stcorrdsp::process (jmeters/stcorrdsp.cc:47-76): per frame
+//     zl += w1 (l - zl) + 1e-20f, zr alike;  zlr += w2 (zl zr - zlr), zll and zrr alike;
+// at the END of a process () each of the five states that is not finite becomes 0 and zlr, zll, zrr get + 1e-10f; read ()
+// (:79-82) is zlr / sqrt (zll zrr + 1e-10f).  One process () is the engine call, or — with a period P, for the reading
+// series — every block of exactly P frames, wherever the calls cut the audio.
+//
+// The second stage is linear in the products p = zl zr, zl^2, zr^2:
+//     z_end = q^N z_0 + w2 sum_n q^(N - 1 - n) p [n],  q = 1 - w2,
+// so a call is cut into PIECES that never span a period boundary (and are at most `chunk` frames, so that one long period
+// still fills the chip); one workgroup reduces one (stream, piece) to the three sums carried to the piece's end, and one
+// thread per stream walks the pieces in order — z = q^len z + sum — and does the flush, the + 1e-10f, the reading and the
+// series append at every period end.  Plain and deterministic: no atomics.
+//
+// The products are not pointwise in the input: zl is a one-pole over the samples.  A workgroup takes its piece tile by tile
+// (4096 frames, staged in LDS by coalesced 16-byte loads); lane t walks the 16 contiguous frames t of the tile twice: once
+// from zero for its run's end value, then — after a (decay, value) prefix scan across the wave (DPP) and the four waves
+// (LDS) gave it the state its run starts from — again for the products.  The tiles are aligned to the piece's END, so the
+// first tile starts in front of the piece: over those frames (at least `warm`: |1 - w1|^warm < 2^-48) the first-stage state
+// is rebuilt from the audio, and they weigh nothing.  In front of frame 0 of the call there is no audio: there the input
+// is zero and the carried zl, zr enter at "frame -1", exactly.  Everything is summed in double: the result is the recurrence
+// in exact arithmetic on the f32 samples and coefficients, rounded to f32 where the reference holds an f32 between two
+// process () calls (tests/test_gpu_stcorr.py holds it to the reference's own distance from exact arithmetic).
+//
+// Not finite: a NaN or Inf sample sticks in its channel's zl until the end of the process (), where the reference sets it to
+// 0.  Here a piece's sums are then not finite, the walk keeps them so to the period's end, and the channel's zl is 0 from
+// there on, as the reference's.  The piece that FOLLOWS a period end inside the call cannot know that when it runs: it starts
+// from the state rebuilt over the frames in front of it (samples and a carried state that are not finite taken as 0: such a one
+// means the period before is flushed) and reports, beside its sums, what they owe to that start state — with rho = (1 - w1)^(frames
+// since the period end), zl [n] = zl0 [n] + rho s, so the sums are quadratic in s with the coefficients sum c rho zl, sum c rho zr
+// and sum c rho^2 — and the walk, which knows whether the period before was flushed, moves the sums to the start state 0.
+// (A finite sample so large that the reference's f32 zll overflows inside a process () — |x| beyond 1e19 — flushes that period
+// there; here the double sum may decay back into f32's range before the period ends and a finite reading comes out.)
+#include <hip/hip_runtime.h>
+
+#include "mtr_internal.h"
+
+namespace {
+
+constexpr int NT = 256;                  // threads per workgroup
+constexpr int K = 16;                    // frames per lane run
+constexpr int TILE = NT * K;             // frames per tile
+constexpr int SLOT = K + 1;              // LDS frames per run: lane stride 34 dwords, ds_read_b64 without bank conflicts
+constexpr int MAX_TILES = 8;             // tiles per piece (chunk + warm)
+constexpr int NPAIR = TILE / 2 + 1;      // 16-byte pairs that cover a tile starting on either parity
+
+struct Piece {
+	int64_t b0, b1;                      // frames [b0, b1) of the call
+	bool    after_period;                // starts where a period ended inside this call
+	bool    closes;                      // ends a process (): a period, or (period 0) the call
+};
+
+__host__ __device__ inline uint64_t div_up (uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+
+// piece i of a call: the open period's rest [0, e0), then whole periods, then what the call leaves open — each cut at `chunk`
+__device__ inline Piece piece_of (const mtr_stcorr_args& a, uint32_t i)
+{
+	const uint64_t N = a.n_frames, first = a.e0 < N ? a.e0 : N;
+	const uint32_t c0 = (uint32_t) div_up (first, a.chunk);
+	uint64_t s0, s1;
+	uint32_t k;
+	if (i < c0) { s0 = 0; s1 = a.e0; k = i; }
+	else {
+		const uint32_t cp = (uint32_t) div_up (a.period, a.chunk);
+		s0 = a.e0 + (uint64_t) ((i - c0) / cp) * a.period; s1 = s0 + a.period; k = (i - c0) % cp;
+	}
+	const uint64_t e = s1 < N ? s1 : N;
+	Piece p;
+	p.b0 = (int64_t) (s0 + (uint64_t) k * a.chunk);
+	p.b1 = (int64_t) (p.b0 + a.chunk < e ? p.b0 + a.chunk : e);
+	p.after_period = k == 0 && s0 > 0;
+	p.closes = (uint64_t) p.b1 == e && s1 <= N;
+	return p;
+}
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dppd (double v)
+{
+	// (lanes without a source — out of row, masked row — read 0)
+	const int lo = __builtin_amdgcn_update_dpp (0, __double2loint (v), CTRL, ROW_MASK, 0xF, true);
+	const int hi = __builtin_amdgcn_update_dpp (0, __double2hiint (v), CTRL, ROW_MASK, 0xF, true);
+	return __hiloint2double (hi, lo);
+}
+
+// x^n, n >= 0 small (x may be negative: 1 - w1 = -0.57 at 8 kHz)
+__host__ __device__ inline double ipow (double x, uint64_t n)
+{
+	double y = 1.0;
+	for (; n; n >>= 1, x *= x) if (n & 1) y *= x;
+	return y;
+}
+
+// the constant decays of the wave scan: d = r^K per lane
+struct ScanPow {
+	double d1, d2, d4, d8;               // wave-uniform
+	double dp, dq;                       // d^((lane & 15) + 1), d^(lane - 31) (lanes 32 .. 63)
+};
+
+// in-place inclusive scan over the wave: v_l <- sum_{j <= l} d^(l - j) v_j (the pattern of mtrw::scan, one-pole)
+__device__ __forceinline__ double scan (double v, const ScanPow& s)
+{
+	v = fma (s.d1, dppd<0x111, 0xF> (v), v);
+	v = fma (s.d2, dppd<0x112, 0xF> (v), v);
+	v = fma (s.d4, dppd<0x114, 0xF> (v), v);
+	v = fma (s.d8, dppd<0x118, 0xF> (v), v);
+	v = fma (s.dp, dppd<0x142, 0xA> (v), v);     // rows 1, 3 <- the complete scan of lane 15 / 47's row
+	v = fma (s.dq, dppd<0x143, 0xC> (v), v);     // rows 2, 3 <- the complete scan at lane 31
+	return v;
+}
+
+// frame f of a stream, 0 outside [lo, hi)
+__device__ __forceinline__ float2 frame_at (const float* src, int64_t f, int64_t lo, int64_t hi, bool al8)
+{
+	if (f < lo || f >= hi) return float2{0.f, 0.f};
+	if (al8) return *reinterpret_cast<const float2*> (src + 2 * f);
+	return float2{src[2 * f], src[2 * f + 1]};
+}
+
+__global__ __launch_bounds__ (NT) void k_stcorr_pieces (const mtr_stcorr_args a)
+{
+	const uint32_t s = blockIdx.y;
+	const Piece pc = piece_of (a, blockIdx.x);
+	const float* const src = a.audio + (size_t) s * a.stride * 2;
+	const int64_t b0 = pc.b0, b1 = pc.b1;
+	const int64_t warm = b0 == 0 ? 1 : (int64_t) a.warm;          // (the call's first piece: only the slot of frame -1)
+	const int nt = (int) ((b1 - b0 + warm + TILE - 1) / TILE);      // <= MAX_TILES: chunk + warm = MAX_TILES * TILE
+	const int64_t lo = b0 - warm > 0 ? b0 - warm : 0;              // the first frame that is read
+	const int64_t T0 = b1 - (int64_t) nt * TILE;                    // < b0
+	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	// 16-byte loads: pairs of frames from an even frame of the BUFFER
+	const bool al8 = (reinterpret_cast<size_t> (a.audio) & 7) == 0;
+	const int64_t base = (int64_t) ((size_t) s * a.stride + (reinterpret_cast<size_t> (a.audio) >> 3));
+
+	const double w1 = (double) a.w1, r = 1.0 - w1, q1 = 1.0 - (double) a.w2, bias = (double) 1e-20f;
+	double zc[2] = { (double) a.state[s].z[0], (double) a.state[s].z[1] };         // the carried zl, zr: "frame -1"
+	if (pc.after_period) {                                         // (not finite: the period before is flushed, its zl with it)
+		if (!isfinite (zc[0])) zc[0] = 0.0;
+		if (!isfinite (zc[1])) zc[1] = 0.0;
+	}
+	ScanPow sp;
+	const double r2 = r * r, r4 = r2 * r2, r8 = r4 * r4;
+	sp.d1 = r8 * r8; sp.d2 = sp.d1 * sp.d1; sp.d4 = sp.d2 * sp.d2; sp.d8 = sp.d4 * sp.d4;   // (K = 16: d > 0 also where r < 0)
+	sp.dp = ipow (sp.d1, (lane & 15) + 1);
+	sp.dq = lane >= 32 ? ipow (sp.d1, lane - 31) : 0.0;
+	const double dl = ipow (sp.d1, lane);                          // from the wave's first frame to this lane's run
+	const double d64 = sp.d8 * sp.d8 * sp.d8 * sp.d8 * sp.d8 * sp.d8 * sp.d8 * sp.d8;   // ... and over a whole wave
+	// weight of a run's sums at the piece's end: w2 q^(frames behind the run); from tile to tile it grows by q^-TILE
+	double W = (double) a.w2 * pow (q1, (double) ((int64_t) nt * TILE - (int64_t) K * (tid + 1)));
+	const double g = pow (q1, (double) -TILE);
+
+	__shared__ float2 lds[NT * SLOT];
+	__shared__ double sh_tot[NT / 64][2];
+	__shared__ double sh_red[NT / 64][5];
+	double zt[2] = { 0.0, 0.0 };                                   // zl, zr in front of the tile (the first one starts from nothing)
+	double tot[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };                   // lr ll rr, and (after a period end) sum c rho zl, sum c rho zr
+	double* const out = a.piece + ((size_t) s * a.n_pieces + blockIdx.x) * MTR_STCORR_PIECE;
+
+	float4 pre[(NPAIR + NT - 1) / NT];
+	auto fetch = [&] (int64_t T) {
+		const int64_t P0 = T - ((base + T) & 1);
+#pragma unroll
+		for (int j = 0; j < (NPAIR + NT - 1) / NT; ++j) {
+			const int i = tid + j * NT;
+			const int64_t f = P0 + 2 * (int64_t) i;
+			float4 v = float4{0.f, 0.f, 0.f, 0.f};
+			if (i < NPAIR) {
+				if (al8 && f >= lo && f + 1 < b1) v = *reinterpret_cast<const float4*> (src + 2 * f);
+				else {
+					const float2 x = frame_at (src, f, lo, b1, al8), y = frame_at (src, f + 1, lo, b1, al8);
+					v = float4{x.x, x.y, y.x, y.y};
+				}
+			}
+			pre[j] = v;
+		}
+	};
+	auto stash = [&] (int64_t T) {
+		const int64_t P0 = T - ((base + T) & 1);
+#pragma unroll
+		for (int j = 0; j < (NPAIR + NT - 1) / NT; ++j) {
+			const int i = tid + j * NT;
+			const int o = (int) (P0 - T) + 2 * i;                  // tile index of the pair's first frame: -1 .. TILE
+			if (i < NPAIR) {
+				if (o >= 0 && o < TILE) lds[(o >> 4) * SLOT + (o & 15)] = float2{pre[j].x, pre[j].y};
+				if (o + 1 < TILE) lds[((o + 1) >> 4) * SLOT + ((o + 1) & 15)] = float2{pre[j].z, pre[j].w};
+			}
+		}
+	};
+
+	fetch (T0);
+	for (int t = 0; t < nt; ++t) {
+		const int64_t T = T0 + (int64_t) t * TILE;
+		stash (T);
+		__syncthreads ();
+		if (t + 1 < nt) fetch (T + TILE);                          // (in flight under this tile's arithmetic)
+		const bool head = T < b0;                                  // frames in front of the piece: they rebuild zl, zr and weigh nothing
+		const int64_t f0 = T + (int64_t) K * tid;
+		// ---- pass 1: the inputs of the one-pole, and the run's end value from zero ----
+		double ul[K], ur[K];
+		double vl = 0.0, vr = 0.0;
+#pragma unroll
+		for (int k = 0; k < K; ++k) {
+			float2 x = lds[tid * SLOT + k];
+			if (!head) {
+				ul[k] = fma (w1, (double) x.x, bias); ur[k] = fma (w1, (double) x.y, bias);
+			} else {
+				const int64_t f = f0 + k;
+				if (pc.after_period && f < b0) {                   // (see the head of the file)
+					if (!isfinite (x.x)) x.x = 0.f;
+					if (!isfinite (x.y)) x.y = 0.f;
+				}
+				ul[k] = f >= 0 ? fma (w1, (double) x.x, bias) : f == -1 ? zc[0] : 0.0;
+				ur[k] = f >= 0 ? fma (w1, (double) x.y, bias) : f == -1 ? zc[1] : 0.0;
+			}
+			vl = fma (r, vl, ul[k]); vr = fma (r, vr, ur[k]);
+		}
+		// ---- the state each run starts from: scan across the wave, then across the waves ----
+		vl = scan (vl, sp); vr = scan (vr, sp);
+		if (lane == 63) { sh_tot[wid][0] = vl; sh_tot[wid][1] = vr; }
+		__syncthreads ();                                          // (and every lane has read its run: the next stash may overwrite the tile)
+		double cin[2] = { 0.0, 0.0 };
+#pragma unroll
+		for (int w = 0; w < NT / 64; ++w) {
+			if (w == wid) { cin[0] = zt[0]; cin[1] = zt[1]; }
+			zt[0] = fma (d64, zt[0], sh_tot[w][0]); zt[1] = fma (d64, zt[1], sh_tot[w][1]);
+		}
+		double zl = fma (dl, cin[0], dppd<0x138, 0xF> (vl));       // (wave_shr:1: the scan of the lane to the left, lane 0 reads 0)
+		double zr = fma (dl, cin[1], dppd<0x138, 0xF> (vr));
+		// ---- pass 2: the products, carried to the run's end ----
+		// (behind a period end, while rho is above the sums' resolution: also what the sums owe to the state the piece started from)
+		const bool owes = pc.after_period && T < b0 + warm;            // uniform
+		double alr = 0.0, all = 0.0, arr = 0.0, abl = 0.0, abr = 0.0;
+		double rho = owes && f0 > b0 ? ipow (r, (uint64_t) (f0 - b0)) : 1.0;
+#pragma unroll
+		for (int k = 0; k < K; ++k) {
+			zl = fma (r, zl, ul[k]); zr = fma (r, zr, ur[k]);
+			double plr = zl * zr, pll = zl * zl, prr = zr * zr;
+			if (head && f0 + k < b0) { plr = 0.0; pll = 0.0; prr = 0.0; }
+			alr = fma (alr, q1, plr); all = fma (all, q1, pll); arr = fma (arr, q1, prr);
+			if (owes) {
+				const int64_t f = f0 + k;
+				if (f == b0 - 1) { out[7] = zl; out[8] = zr; }         // the start state itself (one lane of the workgroup)
+				const bool in = f >= b0;
+				if (in) rho *= r;
+				abl = fma (abl, q1, in ? rho * zl : 0.0); abr = fma (abr, q1, in ? rho * zr : 0.0);
+			}
+		}
+		tot[0] = fma (W, alr, tot[0]); tot[1] = fma (W, all, tot[1]); tot[2] = fma (W, arr, tot[2]);
+		if (owes) { tot[3] = fma (W, abl, tot[3]); tot[4] = fma (W, abr, tot[4]); }
+		W *= g;
+	}
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+		for (int j = 0; j < 5; ++j) tot[j] += __shfl_xor (tot[j], d, 64);
+	if (lane == 0) for (int j = 0; j < 5; ++j) sh_red[wid][j] = tot[j];
+	__syncthreads ();
+	if (tid == 0) {
+		for (int j = 0; j < 5; ++j) {
+			double e = 0.0;
+			for (int w = 0; w < NT / 64; ++w) e += sh_red[w][j];
+			out[j < 3 ? j : j + 2] = e;
+		}
+		out[3] = zt[0]; out[4] = zt[1];
+	}
+}
+
+// one thread per stream: the pieces in order, and stcorrdsp.cc:65-75 + read () at every end of a process ()
+__global__ void k_stcorr_final (const mtr_stcorr_args a)
+{
+	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= a.n_streams) return;
+	mtr_stcorr_state* const st = a.state + s;
+	const double q1 = 1.0 - (double) a.w2;
+	double z[3] = { (double) st->z[2], (double) st->z[3], (double) st->z[4] };
+	float zl = st->z[0], zr = st->z[1], corr = st->corr;
+	uint64_t point = a.point0;
+	int64_t len_of = -1;
+	double qp = 1.0;
+	bool flushed[2] = { false, false };
+	for (uint32_t i = 0; i < a.n_pieces; ++i) {
+		const Piece pc = piece_of (a, i);
+		const int64_t len = pc.b1 - pc.b0;
+		if (len != len_of) { qp = pow (q1, (double) len); len_of = len; }
+		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_STCORR_PIECE;
+		double sum[3] = { pv[0], pv[1], pv[2] }, el = pv[3], er = pv[4];
+		if (pc.after_period && (flushed[0] || flushed[1])) {
+			// the period before left zl (zr) = 0 where the piece started from pv[7] (pv[8]): with rho = r^(frames since), zl' = zl + rho dl
+			const double dl = flushed[0] ? -pv[7] : 0.0, dr = flushed[1] ? -pv[8] : 0.0;
+			const double r = 1.0 - (double) a.w1, r2 = r * r;
+			double cq = 0.0, rr = 1.0;                                 // sum c rho^2 = w2 sum_m q^(len - m) r^(2m), m = 1 .. len
+			for (int64_t m = 1; m <= len && rr > 1e-300; ++m) { rr *= r2; cq += ipow (q1, (uint64_t) (len - m)) * rr; }
+			cq *= (double) a.w2;
+			sum[0] += dr * pv[5] + dl * pv[6] + dl * dr * cq;
+			sum[1] += 2.0 * dl * pv[5] + dl * dl * cq;
+			sum[2] += 2.0 * dr * pv[6] + dr * dr * cq;
+			const double re = ipow (r, (uint64_t) len);
+			el += re * dl; er += re * dr;
+		}
+		if (pc.after_period) flushed[0] = flushed[1] = false;
+		for (int j = 0; j < 3; ++j) z[j] = fma (qp, z[j], sum[j]);
+		const bool last = i + 1 == a.n_pieces;
+		if (last) { zl = (float) el; zr = (float) er; }
+		if (!pc.closes) continue;
+		float f[3] = { (float) z[0], (float) z[1], (float) z[2] };
+		flushed[0] = !isfinite (f[1]); flushed[1] = !isfinite (f[2]);  // this period leaves zl (zr) = 0 to the next
+		// (the channel's first stage: not finite anywhere in the process () means not finite at its end, stcorrdsp.cc:65-66)
+		if (last && (!isfinite (zl) || !isfinite (f[1]))) zl = 0.f;
+		if (last && (!isfinite (zr) || !isfinite (f[2]))) zr = 0.f;
+		for (int j = 0; j < 3; ++j) {
+			if (!isfinite (f[j])) f[j] = 0.f;                      // :67-69
+			f[j] = __fadd_rn (f[j], 1e-10f);                       // :73-75
+			z[j] = (double) f[j];
+		}
+		corr = f[0] / sqrtf (__fadd_rn (__fmul_rn (f[1], f[2]), 1e-10f));   // :81
+		if (a.period) {
+			if (point < a.capacity) a.series[(size_t) s * a.capacity + point] = corr;
+			++point;
+		}
+	}
+	st->z[0] = zl; st->z[1] = zr;
+	for (int j = 0; j < 3; ++j) st->z[2 + j] = (float) z[j];
+	st->corr = corr;
+}
+
+}  // namespace
+
+void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk)
+{
+	// |1 - w1|^J < 2^-48: what the rebuilt state lacks is below the resolution of the double sums, not only of an f32.
+	// (|1 - w1| < 1 from 8 kHz up — w1 = 1.57 there; a rate so high that J would take half the tiles gets half the tiles.)
+	const double ar = fabs (1.0 - (double) w1);
+	double J = ar > 0.0 && ar < 1.0 ? ceil (-48.0 * log (2.0) / log (ar)) : 1.0;
+	const double most = (double) (MAX_TILES / 2 * TILE);
+	if (!(J >= 1.0)) J = 1.0;
+	if (J > most) J = most;
+	*warm = ((uint32_t) J + K) / K * K;                            // (+ the slot of frame -1)
+	*chunk = MAX_TILES * TILE - *warm;
+}
+
+uint32_t mtr_stcorr_pieces (uint64_t n_frames, uint64_t e0, uint64_t period, uint32_t chunk)
+{
+	const uint64_t first = e0 < n_frames ? e0 : n_frames;
+	uint64_t n = div_up (first, chunk);
+	if (period && n_frames > e0) {
+		const uint64_t rest = n_frames - e0;
+		n += rest / period * div_up (period, chunk) + div_up (rest % period, chunk);
+	}
+	return (uint32_t) n;
+}
+
+int mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream)
+{
+	hipStream_t st = (hipStream_t) stream;
+	hipLaunchKernelGGL (k_stcorr_pieces, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+	hipLaunchKernelGGL (k_stcorr_final, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}

@@ -13,6 +13,7 @@ import numpy as np
 
 METER_EBU, METER_TRUEPEAK, METER_SPECTR30, METER_TPBALLIST = 0x01, 0x02, 0x04, 0x08
 METER_BITSTATS, METER_SIGDIST, METER_DR14, METER_KMETER = 0x10, 0x20, 0x40, 0x80
+METER_STCORR = 0x200                       # (0x100 is no meter)
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
 PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3        # MTR_PCM_*: little-endian int16 / packed 3-byte / int32 samples
@@ -142,6 +143,12 @@ def _load():
     L.mtr_engine_dr14_reset.argtypes = [vp]
     L.mtr_engine_kmeter_read.argtypes = [vp, u32, u32, vp, vp]
     L.mtr_engine_kmeter_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_stcorr_read"):                   # (an addition inside ABI version 2: stereo phase correlation)
+        L.mtr_stcorr_coef.argtypes = [f32, vp]
+        L.mtr_engine_stcorr_set_period.argtypes = [vp, u32, u32]
+        L.mtr_engine_stcorr_read.argtypes = [vp, u32, u32, vp, vp]
+        L.mtr_engine_stcorr_series.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_stcorr_reset.argtypes = [vp]
     L.mtr_engine_prune_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_refine_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_layout.argtypes = [vp]
@@ -217,6 +224,13 @@ def band_coef(rate, band):
     out = np.zeros(36, np.float64)
     _check(lib.mtr_band_coef(float(rate), band, out.ctypes.data), "mtr_band_coef")
     return out.reshape(6, 6)
+
+
+def stcorr_coef(fs):
+    """(w1, w2) of Stcorrdsp::init ((int) fs, 2e3f, 0.3f) as float32."""
+    out = np.zeros(2, np.float32)
+    _check(lib.mtr_stcorr_coef(fs, out.ctypes.data), "mtr_stcorr_coef")
+    return out
 
 
 def hist_loudness(hist_M, hist_S):
@@ -629,6 +643,32 @@ class Engine:
 
     def kmeter_reset(self):
         _check(lib.mtr_engine_kmeter_reset(self._h), "kmeter_reset")
+
+    def stcorr_set_period(self, period_frames, capacity_points=0):
+        """0: every call is one Stcorrdsp::process (); P > 0: blocks of exactly P frames wherever the calls cut the audio, read () after
+        each appended to a series of `capacity_points` per stream.  Only before the first process call since create / reset."""
+        _check(lib.mtr_engine_stcorr_set_period(self._h, int(period_frames), int(capacity_points)), "stcorr_set_period")
+
+    def stcorr_read(self, first=0, count=None):
+        """(corr [count], state5 [count, 5] = zl zr zlr zll zrr): Stcorrdsp::read () after the most recent call / completed period."""
+        count = self.n_streams - first if count is None else count
+        corr = np.zeros(count, np.float32)
+        st = np.zeros((count, 5), np.float32)
+        _check(lib.mtr_engine_stcorr_read(self._h, first, count, corr.ctypes.data, st.ctypes.data), "stcorr_read")
+        return corr, st
+
+    def stcorr_series(self, first=0, count=None):
+        """(points [count, kept], n_points, dropped): the readings after every completed period since reset that the series holds."""
+        count = self.n_streams - first if count is None else count
+        n, d = C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_stcorr_series(self._h, first, count, None, 0, C.byref(n), C.byref(d)), "stcorr_series")
+        kept = n.value - d.value
+        out = np.zeros((count, max(kept, 1)), np.float32)
+        _check(lib.mtr_engine_stcorr_series(self._h, first, count, out.ctypes.data, out.shape[1], C.byref(n), C.byref(d)), "stcorr_series")
+        return out[:, :kept], n.value, d.value
+
+    def stcorr_reset(self):
+        _check(lib.mtr_engine_stcorr_reset(self._h), "stcorr_reset")
 
     def dr14_reset(self):
         _check(lib.mtr_engine_dr14_reset(self._h), "dr14_reset")
