@@ -16,7 +16,24 @@
 // the loop — the kernel runs at that instruction floor (profiles/).
 #include <hip/hip_runtime.h>
 
-#include "mtr_internal.h"
+#include <cmath>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+
+struct mtr_bank_args {
+	const float*    audio;
+	uint64_t        stride;
+	uint64_t        n_frames;
+	const double*   coef;         /* [30][6][5]: b0 b1 b2 a1 a2 per section */
+	double*         z;            /* [S][30][12] section states */
+	float*          val;          /* [S][30] */
+	float*          mx;           /* [S][30] */
+	const int32_t*  ac_in;        /* [S] dither toggle parity at the start of the call (shared by the 30 bands of a stream) */
+	int32_t*        ac_out;       /* [S] ... and after it: ANOTHER buffer (a workgroup that starts late must still read the old one) */
+	uint32_t        n_streams, n_channels;
+	float           omega;
+};
 
 #define BANK_ROWS  4      /* streams a wave of 64 lanes can touch: ceil (63 / 30) + 1 */
 #define BANK_CHUNK 128    /* frames staged per stream per iteration: two per lane */
@@ -162,7 +179,7 @@ __global__ __launch_bounds__ (64) void k_bank (const mtr_bank_args a)
 	}
 }
 
-int mtr_launch_bank (const mtr_bank_args& a, void* stream)
+static int mtr_launch_bank (const mtr_bank_args& a, void* stream)
 {
 	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
 	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
@@ -238,3 +255,117 @@ int mtr_launch_synth (float* d_audio, uint32_t n_streams, uint64_t n_frames, uin
 	                    d_audio, n_streams, n_frames, stride, seed, fs, kind);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- SPECTR30 in the engine: set-up, reset, the call's step, the blob's sections, the getters ----------------------------------------
+
+int bank_create (mtr_engine* e)
+{
+	const mtr_config* const cfg = &e->cfg;
+	e->bank.omega = 1.0f - expf (-2.0 * M_PI * 1.0 / (double) cfg->sample_rate);   // spectrumlv2.c:98
+	if (!(cfg->meters & MTR_METER_SPECTR30)) return MTR_OK;
+	const uint32_t S = cfg->n_streams;
+	std::vector<double> c (MTR_NBANDS * 6 * 5);
+	for (uint32_t b = 0; b < MTR_NBANDS; ++b) {
+		double w[36];
+		mtr_setup_band ((double) cfg->sample_rate, b, w);
+		for (int i = 0; i < 6; ++i) {
+			double* o = &c[(b * 6 + i) * 5];
+			o[0] = w[i * 6 + 3]; o[1] = w[i * 6 + 4]; o[2] = w[i * 6 + 5];   // b0 b1 b2
+			o[3] = w[i * 6 + 1]; o[4] = w[i * 6 + 2];                         // a1 a2
+		}
+	}
+	if (e->bank.coef.reserve (c.size ()) || e->bank.z.reserve ((size_t) S * MTR_NBANDS * 12)
+	    || e->bank.val.reserve ((size_t) S * MTR_NBANDS) || e->bank.max.reserve ((size_t) S * MTR_NBANDS)
+	    || e->bank.ac[0].reserve (S) || e->bank.ac[1].reserve (S))
+		return fail (MTR_ERR_NOMEM, "hipMalloc bank state");
+	if (hipMemcpy (e->bank.coef.p, c.data (), c.size () * sizeof (double), hipMemcpyHostToDevice) != hipSuccess)
+		return fail (MTR_ERR_HIP, "hipMemcpy bank_coef");
+	return MTR_OK;
+}
+
+int bank_reset (mtr_engine* e, hipStream_t st)
+{
+	HIPCHK (hipMemsetAsync (e->bank.z.p, 0, e->bank.z.n * sizeof (double), st));
+	HIPCHK (hipMemsetAsync (e->bank.val.p, 0, e->bank.val.n * sizeof (float), st));
+	HIPCHK (hipMemsetAsync (e->bank.max.p, 0, e->bank.max.n * sizeof (float), st));
+	HIPCHK (hipMemsetAsync (e->bank.ac[0].p, 0, e->bank.ac[0].n * sizeof (int32_t), st));
+	HIPCHK (hipMemsetAsync (e->bank.ac[1].p, 0, e->bank.ac[1].n * sizeof (int32_t), st));
+	e->pos.bank_ac_cur = 0;
+	return MTR_OK;
+}
+
+int bank_step (mtr_engine* e, const Call& c, Cursors& nx)
+{
+	const size_t vo = c.off;
+	mtr_bank_args ba;
+	ba.audio = c.audio; ba.stride = c.stride; ba.n_frames = c.n_frames;
+	ba.coef = e->bank.coef.p; ba.z = e->bank.z.p + vo * MTR_NBANDS * 12; ba.val = e->bank.val.p + vo * MTR_NBANDS; ba.mx = e->bank.max.p + vo * MTR_NBANDS;
+	ba.ac_in = e->bank.ac[e->pos.bank_ac_cur].p + vo; ba.ac_out = e->bank.ac[e->pos.bank_ac_cur ^ 1].p + vo;
+	ba.n_streams = c.cnt; ba.n_channels = e->cfg.n_channels; ba.omega = e->bank.omega;
+	if (mtr_launch_bank (ba, c.st)) return fail (MTR_ERR_HIP, "k_bank launch");
+	nx.bank_ac_cur = e->pos.bank_ac_cur ^ 1;
+	return MTR_OK;
+}
+
+void bank_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	v.push_back ({ e->bank.z.p, (size_t) MTR_NBANDS * 12 * sizeof (double) });
+	v.push_back ({ e->bank.val.p, (size_t) MTR_NBANDS * sizeof (float) });
+	v.push_back ({ e->bank.max.p, (size_t) MTR_NBANDS * sizeof (float) });
+	v.push_back ({ e->bank.ac[e->pos.bank_ac_cur].p, sizeof (int32_t) });
+}
+
+extern "C" {
+
+int mtr_engine_spectr_set_speed (mtr_engine* e, float v)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if (v < 0.01) v = 0.01;                                    // spectrumlv2.c:172-175
+	if (v > 15.0) v = 15.0;
+	e->bank.omega = 1.0f - expf (-2.0 * M_PI * v / (double) e->cfg.sample_rate);
+	return MTR_OK;
+}
+
+int mtr_engine_spectr_reset_peak (mtr_engine* e)
+{
+	if (!e || !(e->cfg.meters & MTR_METER_SPECTR30)) return fail (MTR_ERR_ARG, "no SPECTR30 in this engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	HIPCHK (hipMemsetAsync (e->bank.max.p, 0, e->bank.max.n * sizeof (float), e->last_stream));
+	e->queued = true;
+	return MTR_OK;
+}
+
+int mtr_engine_spectrum (mtr_engine* e, uint32_t first, uint32_t count, float* val, float* mx, float* val_db, float* max_db)
+{
+	int rc = check_range (e, first, count);
+	if (rc) return rc;
+	if (!(e->cfg.meters & MTR_METER_SPECTR30)) return fail (MTR_ERR_ARG, "no SPECTR30 in this engine");
+	if (count == 0) return MTR_OK;
+	const size_t n = (size_t) count * MTR_NBANDS;
+	std::vector<float> hv;
+	const float* v = nullptr; const float* m = nullptr;
+	if (e->snap_valid && e->cfg.n_streams == 1) {
+		v = e->pin_bank.p; m = e->pin_bank.p + MTR_NBANDS;            // came back with the block's own wait: no heap, no copy
+	} else {
+		rc = mtr_engine_sync (e);
+		if (rc) return rc;
+		hv.resize (2 * n);
+		HIPCHK (hipMemcpy (hv.data (), e->bank.val.p + (size_t) first * MTR_NBANDS, n * 4, hipMemcpyDeviceToHost));
+		HIPCHK (hipMemcpy (hv.data () + n, e->bank.max.p + (size_t) first * MTR_NBANDS, n * 4, hipMemcpyDeviceToHost));
+		v = hv.data (); m = hv.data () + n;
+	}
+	for (size_t i = 0; i < n; ++i) {
+		// spectrumlv2.c:240-247.  The stored val carries the +1e-20f of :237; above the -100 dB floor
+		// (val > 5e-11) that addition does not change the float, so the port value is unaffected.
+		const float vs = sqrtf (2. * v[i]);
+		const float ms = sqrtf (2. * m[i]);
+		if (val) val[i] = v[i];
+		if (mx) mx[i] = m[i];
+		if (val_db) val_db[i] = vs > .00001f ? 20.0 * log10f (vs) : -100.0;
+		if (max_db) max_db[i] = ms > .00001f ? 20.0 * log10f (ms) : -100.0;
+	}
+	return MTR_OK;
+}
+
+} // extern "C"

@@ -14,7 +14,29 @@
 // 0.01 dB bin, which moves the score by at most that — tests/test_gpu_dr14.py states +-0.02 dB.
 #include <hip/hip_runtime.h>
 
-#include "mtr_internal.h"
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+
+/* DR-14 per-stream state (src/dr14.c LV2dr14: rms_sum, peak_cur, peak_hist, m_rms, m_peak, num_fragments) */
+typedef struct mtr_dr14_state {
+	float    rms_sum[2], peak_cur[2], peak_hist[2][2], m_rms[2], m_peak[2];
+	uint32_t num_fragments;
+} mtr_dr14_state;
+
+typedef struct mtr_dr14_args {
+	const float*    audio;        /* [S][stride][C] */
+	uint64_t        stride, n_frames;
+	uint64_t        window;       /* n_sample_cnt + 1 samples close a window (dr14.c:404) */
+	uint64_t        e0;           /* call frame at which the window open on entry closes */
+	uint32_t        n_streams, n_channels, n_pieces, n_windows;
+	mtr_dr14_state* state;        /* [S] */
+	uint32_t*       hist;         /* [S][C][8000] */
+	double*         piece_sum;    /* [S][n_pieces][2] */
+	float*          piece_peak;   /* [S][n_pieces][2] */
+} mtr_dr14_args;
 
 namespace {
 
@@ -164,7 +186,7 @@ __global__ __launch_bounds__ (64) void k_dr14_windows (const mtr_dr14_args a)
 
 }  // namespace
 
-int mtr_launch_dr14 (const mtr_dr14_args& a, void* stream)
+static int mtr_launch_dr14 (const mtr_dr14_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
 	if (a.n_channels == 2) {
@@ -176,3 +198,83 @@ int mtr_launch_dr14 (const mtr_dr14_args& a, void* stream)
 	}
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- DR14 in the engine: the call's step, the blob's sections, reset, the results ------------------------------------------------------
+
+int dr14_step (mtr_engine* e, const Call& c, Cursors& nx)
+{
+	const size_t vo = c.off;
+	mtr_dr14_args da;
+	da.audio = c.audio; da.stride = c.stride; da.n_frames = c.n_frames;
+	da.window = (uint64_t) rintf (e->cfg.sample_rate * 3.0f) + 1;       // dr14.c:155, :404
+	da.e0 = da.window - e->pos.dr_scnt;
+	const uint64_t tot = e->pos.dr_scnt + c.n_frames;
+	da.n_windows = (uint32_t) (tot / da.window);
+	da.n_pieces = da.n_windows + (tot % da.window ? 1 : 0);
+	da.n_streams = c.cnt; da.n_channels = e->cfg.n_channels;
+	if (e->dr.sum.reserve ((size_t) e->cfg.n_streams * da.n_pieces * 2) || e->dr.peak.reserve ((size_t) e->cfg.n_streams * da.n_pieces * 2))
+		return fail (MTR_ERR_NOMEM, "hipMalloc DR14 pieces");
+	da.state = e->dr.state.p + vo; da.hist = e->dr.hist.p + vo * e->cfg.n_channels * MTR_DR_HISTBINS;
+	da.piece_sum = e->dr.sum.p + vo * da.n_pieces * 2; da.piece_peak = e->dr.peak.p + vo * da.n_pieces * 2;
+	if (mtr_launch_dr14 (da, c.st)) return fail (MTR_ERR_HIP, "k_dr14 launch");
+	nx.dr_scnt = tot % da.window;
+	return MTR_OK;
+}
+
+void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	v.push_back ({ e->dr.state.p, sizeof (mtr_dr14_state) });
+	v.push_back ({ e->dr.hist.p, (size_t) e->cfg.n_channels * MTR_DR_HISTBINS * sizeof (uint32_t) });
+}
+
+extern "C" {
+
+int mtr_engine_dr14_reset (mtr_engine* e)
+{
+	if (!e || !(e->cfg.meters & MTR_METER_DR14)) return fail (MTR_ERR_ARG, "no DR14 in this engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t S = e->cfg.n_streams;
+	if (e->dr.state.reserve (S) || e->dr.hist.reserve ((size_t) S * e->cfg.n_channels * MTR_DR_HISTBINS))
+		return fail (MTR_ERR_NOMEM, "hipMalloc DR14 state");
+	std::vector<mtr_dr14_state> h (S);
+	memset (h.data (), 0, S * sizeof (mtr_dr14_state));
+	for (auto& v : h) for (int c = 0; c < 2; ++c) { v.m_rms[c] = -81.f; v.m_peak[c] = -81.f; }   // dr14.c:247-248
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemcpy (e->dr.state.p, h.data (), S * sizeof (mtr_dr14_state), hipMemcpyHostToDevice));
+	HIPCHK (hipMemset (e->dr.hist.p, 0, (size_t) S * e->cfg.n_channels * MTR_DR_HISTBINS * sizeof (uint32_t)));
+	e->pos.dr_scnt = 0;
+	return MTR_OK;
+}
+
+int mtr_engine_dr14_results (mtr_engine* e, uint32_t first, uint32_t count, mtr_dr14_result* out)
+{
+	int rc = meter_range (e, e && out && (e->cfg.meters & MTR_METER_DR14), "no DR14 in this engine", first, count);
+	if (rc || (rc = wait_stream (e))) return rc;
+	std::vector<mtr_dr14_state> h (count);
+	HIPCHK (hipMemcpy (h.data (), e->dr.state.p + first, count * sizeof (mtr_dr14_state), hipMemcpyDeviceToHost));
+	const int C = (int) e->cfg.n_channels;
+	for (uint32_t i = 0; i < count; ++i) {
+		mtr_dr14_result& r = out[i];
+		memset (&r, 0, sizeof (r));
+		float total = 0.f;
+		int valid = 0;
+		for (int c = 0; c < C; ++c) {                          // dr14.c:430-441
+			const float rdb = h[i].m_rms[c], pdb = h[i].m_peak[c];
+			const float dr = (0.f < pdb ? 0.f : pdb) - rdb;
+			const bool ok = rdb > -80.f && pdb > -80.f;
+			if (ok) { total += dr; ++valid; }
+			const float cl = 20.f < dr ? 20.f : dr;
+			r.dr[c] = ok ? (1.f > cl ? 1.f : cl) : 21.f;
+			r.m_rms[c] = rdb; r.m_peak[c] = pdb;
+		}
+		if (C > 1) {                                           // :443-450
+			if (valid > 0) { const float m = total / (float) valid; const float cl = 20.f < m ? 20.f : m; r.dr_total = 1.f > cl ? 1.f : cl; }
+			else r.dr_total = 21.f;
+		}
+		r.block_count = 3.0f * (float) h[i].num_fragments;
+	}
+	return MTR_OK;
+}
+
+} // extern "C"

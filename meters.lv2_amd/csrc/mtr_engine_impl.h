@@ -1,0 +1,314 @@
+// mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
+// EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip).  Not installed; needs the HIP
+// runtime header, so the planner (mtr_plan.cpp) never sees it.
+#ifndef MTR_ENGINE_IMPL_H
+#define MTR_ENGINE_IMPL_H
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "mtr_internal.h"
+#include "mtr_host.h"
+
+#pragma GCC visibility push(hidden)   // (cross-TU helpers, not ABI)
+
+// Everything the engine allocates is owned by a member that frees it: mtr_engine_destroy selects the device, waits for it and
+// deletes the engine.  None of the owners can be copied.
+// PINNED: page-locked host memory (staging of the n_streams = 1 host path, plan uploads, result snapshots)
+// (T may be incomplete where the engine is only passed around: sizeof (T) is needed by reserve alone)
+template <typename T, bool PINNED> struct Buf {
+	T*     p = nullptr;
+	size_t n = 0;
+	Buf () = default;
+	Buf (const Buf&) = delete;
+	Buf& operator= (const Buf&) = delete;
+	~Buf () { drop (); }
+	void drop () { if (p) (void) (PINNED ? hipHostFree (p) : hipFree (p)); p = nullptr; n = 0; }
+	int reserve (size_t want) {
+		if (want <= n) return 0;
+		drop ();
+		if ((PINNED ? hipHostMalloc ((void**) &p, want * sizeof (T), hipHostMallocDefault) : hipMalloc ((void**) &p, want * sizeof (T))) != hipSuccess) return -1;
+		n = want;
+		return 0;
+	}
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinBuf = Buf<T, true>;
+
+// An event that is created where it is first needed (ensure), so that a path that never needs it — an LV2 run () — never pays for it
+struct Event {
+	hipEvent_t v = nullptr;
+	Event () = default;
+	Event (Event&& o) noexcept : v (o.v) { o.v = nullptr; }
+	~Event () { if (v) (void) hipEventDestroy (v); }
+	hipError_t ensure (unsigned flags = hipEventDisableTiming) { return v ? hipSuccess : hipEventCreateWithFlags (&v, flags); }
+};
+
+// ... and a stream of the engine's own, likewise
+struct Stream {
+	hipStream_t v = nullptr;
+	Stream () = default;
+	Stream (const Stream&) = delete;
+	Stream& operator= (const Stream&) = delete;
+	~Stream () { if (v) (void) hipStreamDestroy (v); }
+	hipError_t ensure () { return v ? hipSuccess : hipStreamCreateWithFlags (&v, hipStreamNonBlocking); }
+};
+
+// The tiling plan of a call lives in one of PLAN_SLOTS device buffers, uploaded from page-locked memory ON THE CALL'S
+// STREAM: a call whose (n_frames, fragment phase) differs from the previous one — every call, for 1024-frame blocks at
+// 48 kHz — never overwrites arrays that kernels of an earlier call may still be reading, and never blocks the host.
+constexpr int PLAN_SLOTS = 4;
+
+// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths, or any call once a stream is closed) ride the same way:
+// [ends S | frag_lim S | from_tile S] in the next slot of their own ring, uploaded on the call's stream, busy until the call's last
+// readers (k_history_len on the call's stream, the gate on whichever stream it ran) have passed.
+constexpr int LEN_SLOTS = 4;
+struct LenSlot {
+	DevBuf<uint32_t> dev;
+	PinBuf<uint32_t> pin;
+	Event            done[2];
+	bool             pending[2] = { false, false };
+};
+struct PlanSlot {
+	DevBuf<uint32_t> dev;       // [tile_start (n_tiles + 1) | seg_tile (n_segs + 1) | frag_tile (n_frag + 1)]
+	PinBuf<uint32_t> pin;
+	Event            done;             // recorded behind the last kernel that reads `dev`
+	bool             pending = false;
+};
+
+struct Plan {
+	std::vector<uint32_t> frag_end;   // call frame at which fragment f of the call ends (per-stream lengths: fragments that end at or before a stream's end)
+	uint64_t n_frames = 0;
+	uint32_t frcnt_in = 0;      // frames left in the open fragment when the call starts
+	uint32_t frcnt_out = 0;
+	uint32_t n_tiles = 0, n_frag = 0, n_segs = 0, tail_tile = 0, buf_slots = 0, kw_slots = 0;
+	uint32_t body_tiles = 0;    // whole-fragment tiles (the lane = segment kernel's part of the call), 0 = none
+	uint32_t head_tiles = 0;    // ... and the tiles in front of them (the rest of a fragment the call started in)
+	bool     valid = false;
+};
+
+// The lock-step cursors: where the streams of the engine stand between two process calls.  A call reads them, computes their
+// successors as it goes and stores them in ONE place, behind its last launch (CallRun::run) — a chunk of a host call that is
+// not the last stores nothing, nor does a call that fails.  A cursor added here needs no other book-keeping.
+struct Cursors {
+	uint32_t frcnt = 0;           // frames remaining in the open fragment
+	int      hist_cur = 0;        // which of fir_hist [2] / mc_hist [2] holds the 47 frames before the next call
+	int      bank_ac_cur = 0;     // ... and which of bank.ac [2] the dither parity
+	uint64_t dr_scnt = 0;         // samples in the open DR-14 window
+	uint32_t km_fpp = 0;          // Kmeterdsp's frames per period and the fall-back factor that goes with it
+	float    km_fall = 0.f;
+	uint64_t sc_fill = 0;         // STCORR: frames in the open period of the reading series ...
+	uint64_t sc_points = 0;       // ... and periods completed since reset
+	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
+};
+
+// per-stream state of the side meters: defined where their kernels are
+struct mtr_sigdist_state;
+struct mtr_dr14_state;
+struct mtr_kmeter_state;
+struct mtr_stcorr_state;
+
+// The engine: core, tail, plan rings, host path, then one member per side meter
+struct mtr_engine {
+	mtr_config cfg;
+	int      run = 39;            // K: frames per lane run
+	int      layout = 6;          // 3 = exact-f32 VALU interpolator (mtr_fused2.hip), 4 = k_kw, 6 = k_kwtp16 (+ 7: k_seg for the calls it fits), 8 = k_kwmc
+	bool     seg_ok = false;      // layout 7: calls that fit go through k_seg (mtr_seg.hip), the rest through k_kwtp16
+	uint32_t seg_slots = 1024;    // resident k_seg waves: one per SIMD
+	uint32_t fragm = 0;           // frames per 50 ms fragment
+	Cursors  pos;
+	bool     integr = false;
+	bool     advanced = false;    // a process call has run since create / reset: `pos` is no longer a fresh engine's
+	float    kw[7];
+	hipStream_t last_stream = nullptr;
+	bool             queued = false;         // something has been launched on last_stream
+	Event            xs_event;               // orders a new stream behind the previous one
+
+	DevBuf<mtr_stream_state> state;
+	DevBuf<int32_t>  hist;
+	DevBuf<int32_t>  gate_max;      // [S][2] max-hold scratch of the multi-workgroup gate path
+	DevBuf<float>    fir_hist[2];   // ping-pong 47-frame history (pos.hist_cur)
+	DevBuf<float>    scan_m, bin_power, tile_power[2], frag_power, stage;
+	// layout 8 (n_channels 1, 3, 4, 5 with EBU / TRUEPEAK, mtr_kwmc.hip): per-channel side buffers; the stream state's kz / tp_* stay unused
+	// by the kernel, its tp_last / tp_hold [0..1] carry the max over the channels (k_history_mc)
+	DevBuf<float>    mc_kz;         // [S][C][4]
+	DevBuf<float>    mc_hist[2];    // [S][47][C] ping-pong with hist_cur
+	DevBuf<uint32_t> mc_tp_call;    // [S][C]
+	DevBuf<float>    mc_tp_last, mc_tp_hold;   // [S][C]
+	DevBuf<float>    fir_g;         // [3][48] taps in device memory
+	DevBuf<uint16_t> m16_a;         // layouts 6, 7: hi / lo A fragments of the f32-grade MFMA interpolator (mtr_mfma16_fir.h)
+	DevBuf<uint32_t> prune_cnt;     // [4] interpolator tile passes considered / skipped, channel-blocks screened / completed
+	uint64_t         prune_tot[4] = { 0, 0, 0, 0 };
+	float            tpb_w[4];      // w1 w2 w3 g of TruePeakdsp::init
+	bool             seg_screen = true;      // k_seg's products screened by the first of the three (mtr_seg.hip: SCREEN); MTR_SEG_SCREEN=0 forces the dense form
+	uint32_t         last_n_frag = 0;
+	// Per-stream lengths: frames metered per stream since create / reset, and which streams a call with lengths has closed (a closed
+	// stream is left untouched by every later call until mtr_engine_reset; neither is part of the state blob).
+	std::vector<uint64_t> metered;
+	std::vector<uint8_t>  closed;
+	uint32_t         n_closed = 0;
+
+	// The call's tail — k_gate, then the job's reduction (k_aggregate + the RCCL all-reduce) — DEFERRED to an engine-owned side
+	// stream: the fused kernel of call i + 1 needs only what the fused kernel and k_history of call i wrote (K-filter state, FIR
+	// history), never the gate's bookkeeping, so the tail of call i runs beside it instead of in front of it.  tile_power is
+	// double-buffered (the gate of call i reads one while the fused kernel of call i + 1 fills the other); the true-peak fold
+	// moves from the gate into k_history on the caller's stream (tp_call is already being raised by call i + 1).  Results are
+	// bit for bit those of the serial order: same kernels, same inputs, the fragment inserts in fragment order (gates follow
+	// one another on the side stream; ebumeter/ebu_r128_proc.cc:217-244).
+	int              tail_mode = 0;          // 0 auto (a k_seg batch of >= TAIL_AUTO_STREAMS streams and >= TAIL_AUTO_FRAMES stream-frames in an EBU / TRUEPEAK engine), 1 never, 2 always
+	Stream           tail_stream;
+	Event            ev_fused;               // caller's stream -> side: the call's fused kernels are done
+	Event            ev_gate[2];             // side -> caller's: the gate that read tile_power[b] is done
+	bool             gate_pending[2] = { false, false };
+	Event            ev_red;                 // side -> caller's: the reduction that read the peak holds is done (the next fold waits for it)
+	bool             red_pending = false;
+	Event            ev_main;                // caller's -> side: everything the reduction reads from the caller's stream (the fold) is done
+	Event            ev_join;
+	bool             tail_pending = false;   // the side stream holds work nobody has waited for yet
+	bool             last_deferred = false;  // the most recent process call deferred its tail: mtr_engine_reduce follows it there
+	int              tp_cur = 0;             // tile_power buffer of the most recent call
+	uint64_t         deferred_calls = 0;
+	uint32_t         tail_gate_grid = 512;   // workgroups of a deferred gate: two per CU (set from the device's CU count)
+	uint32_t         tail_delay_us = 100;    // see CallRun::gate: the deferred gate must not be dispatched together with the next fused kernel
+
+	// the plan and lengths rings
+	PlanSlot         plan_slot[PLAN_SLOTS];
+	int              plan_cur = 0;
+	const uint32_t*  tile_start = nullptr;   // into plan_slot[plan_cur].dev
+	const uint32_t*  seg_tile = nullptr;
+	const uint32_t*  frag_tile = nullptr;
+	const uint32_t*  head_seg = nullptr;     // {0, first tile of the k_seg body}: the one segment of the k_kwtp16 launch in front of it (if any)
+	const uint32_t*  tail_seg = nullptr;     // {first tile behind the k_seg body, n_tiles}: the one segment of the k_kwtp16 launch that finishes such a call
+	Plan             plan;
+	LenSlot          len_slot[LEN_SLOTS];
+	int              len_cur = 0;
+
+	// n_streams = 1 host path (the shape of an LV2 run ()): own stream, page-locked staging, and ONE synchronisation per
+	// block — the state (and the bank's levels) come back with the same wait and serve the result getters
+	Stream           own_stream;
+	PinBuf<float>    pin_in;
+	PinBuf<mtr_stream_state> pin_state;
+	PinBuf<float>    pin_bank;               // [2][30] val, max
+	bool             snap_valid = false;
+	// the chunked host path (mtr_engine_process_host)
+	size_t           host_chunk_bytes = (size_t) 256 << 20;
+	Stream           copy_stream;
+	Event            ev_copied[2], ev_computed[2];   // per staging buffer: the chunk has landed / its landing buffer has been read
+	// integer PCM in (mtr_engine_process_*_pcm): the host form's integer rows land in two raw buffers of one chunk each, k_pcm
+	// (mtr_pcm.hip) decodes a chunk from there — or from the caller's device rows — into `stage`
+	DevBuf<uint8_t>  pcm_raw;
+	uint64_t         pcm_chunks = 0, pcm_bytes = 0;
+	std::vector<Event> pcm_ev;      // while timing is on: pairs around the decode kernels not yet summed into pcm_ms
+	uint32_t         pcm_timed = 0;
+	float            pcm_ms = 0.f;
+	// frame layout (mtr_engine_set_frame_layout): the buffers of a process call hold frames of frame_channels samples, engine channel c
+	// is source channel frame_map[c]; 0 = the default.  `picks`: the layout is not the identity, every chunk goes through k_pick
+	// (mtr_pick.hip) — from the raw landing buffers (host memory) or the caller's rows (device memory) into `stage`
+	uint32_t         frame_channels = 0;
+	uint8_t          frame_map[MTR_MAX_CHANNELS] = { 0, 1, 2, 3, 4 };
+	bool             picks = false;
+	bool             wave51 = false;      // ... and it is 6, {0, 1, 2, 4, 5} on a 5-channel engine: device f32 calls go to k_kwmc51 instead
+	uint64_t         lay_staged = 0, lay_direct = 0;
+
+	bool timing = false;
+	std::vector<Event> ev;          // groups of EV_PER_CALL: start, fused end, gate begin, gate end (those two on the stream the gate ran on), rest begin, end; a PCM chunk's start in front of its decode
+	std::vector<uint8_t> ev_decode; // per timed call: it began with a decode (its whole span starts at the group's last event, not at the first)
+	uint32_t timed_calls = 0;
+
+	// the side meters, each with its host code next to its kernels
+	struct Bank {                               // SPECTR30 (mtr_bank.hip)
+		DevBuf<double>   coef, z;
+		DevBuf<float>    val, max;
+		DevBuf<int32_t>  ac[2];                 // ping-pong (pos.bank_ac_cur): k_bank reads one, writes the other
+		float            omega = 0.f;
+	} bank;
+	struct IntStat {                            // BITSTATS, SIGDIST (mtr_intstat.hip)
+		DevBuf<mtr_bitstats_state> bim;
+		DevBuf<mtr_sigdist_state>  sdh;
+	} is;
+	struct Dr14 {                               // DR14 (mtr_dr14.hip)
+		DevBuf<mtr_dr14_state>     state;
+		DevBuf<uint32_t>           hist;        // [S][C][8000]
+		DevBuf<double>             sum;         // [S][pieces][2]
+		DevBuf<float>              peak;
+	} dr;
+	struct Kmeter {                             // KMETER (mtr_kmeter.hip)
+		DevBuf<mtr_kmeter_state>   state;       // [S][2]
+		DevBuf<double>             piece;
+		DevBuf<float>              max;
+		double                     pw1[3];
+	} km;
+	struct Stcorr {                             // STCORR (mtr_stcorr.hip)
+		DevBuf<mtr_stcorr_state>   state;       // [S]
+		DevBuf<double>             piece;       // [S][pieces][MTR_STCORR_PIECE]
+		DevBuf<float>              series;      // [S][cap]
+		uint32_t                   period = 0, cap = 0;   // frames per process () of the series (0: the call), points per stream it holds
+		float                      w[2];        // w1, w2 of Stcorrdsp::init
+		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
+	} sc;
+};
+
+constexpr int EV_PER_CALL = 7;
+
+// What a process call is told.  Every entry point (device memory, with or without lengths; each chunk of the host path; an LV2
+// block) builds one and hands it to process_call: nothing about a call is parked in the engine between the two.
+struct Call {
+	const float*    audio;        // device memory, [cnt][stride][C]
+	uint64_t        n_frames, stride;
+	hipStream_t     st;
+	uint32_t        off, cnt;     // the VIEW of the batch the call covers: streams [off, off + cnt); every per-stream array is indexed from off
+	const uint64_t* frames;       // per-stream lengths, indexed from the view's first stream, or nullptr
+	bool            chunk;        // a chunk of a host call (mtr_engine_process_host walks the batch view by view), not a batch of its own
+	bool            commit;       // the lock-step cursors move with this call: the last view of a host call, every other call
+	// integer PCM: the call first decodes the view's rows from `pcm` (device memory, row pitch in bytes) into `audio` — a staging buffer
+	// of the engine's — with k_pcm, and records `pcm_read` (if any) behind that: the integer rows have been read
+	const void*     pcm = nullptr;
+	uint64_t        pcm_pitch = 0;
+	int             pcm_format = 0;
+	hipEvent_t      pcm_read = nullptr;
+	// frame layout: the rows at `pcm` (format 0: f32) hold frames of pick_fc samples, k_pick decodes and picks them (0: k_pcm on frames of C)
+	uint32_t        pick_fc = 0;
+	// ... or `audio` itself holds WAVE 5.1 frames, [cnt][stride][6], which the 5-channel kernels read themselves (k_kwmc51, k_history_mc51)
+	bool            wave51 = false;
+};
+
+struct StateSection { const void* base; size_t elem; };   // a per-stream array of the state blob: `elem` bytes per stream
+
+// ---- mtr_engine.hip -------------------------------------------------------------------------------------------------------------
+// `st` waits for everything the side stream holds (a serial gate, a reset, the caller's own aggregate behind deferred gates)
+int join_tail (mtr_engine* e, hipStream_t st);
+// the host waits for the caller's stream and the side stream
+int sync_all (mtr_engine* e);
+// "null engine" / "stream range out of bounds"
+int check_range (mtr_engine* e, uint32_t first, uint32_t count);
+// what a side meter's getter begins with: the meter is in the engine (`none` if not) and the streams are ("stream range") ...
+int meter_range (const mtr_engine* e, bool has, const char* none, uint32_t first, uint32_t count);
+// ... then the engine's device selected and its stream waited for
+int wait_stream (mtr_engine* e);
+
+// ---- a side meter's hooks: create-time set-up (where it has one), its step of a call, its sections of the state blob --------------
+// A step queues the meter's kernels for the view of call `c` and moves the meter's cursors in `nx` (CallRun::run stores them).
+int  bank_create (mtr_engine* e);
+int  bank_reset (mtr_engine* e, hipStream_t st);
+int  bank_step (mtr_engine* e, const Call& c, Cursors& nx);
+void bank_sections (const mtr_engine* e, std::vector<StateSection>& v);
+int  intstat_step (mtr_engine* e, const Call& c, Cursors& nx);
+void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v);
+int  dr14_step (mtr_engine* e, const Call& c, Cursors& nx);
+void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v);
+int  kmeter_step (mtr_engine* e, const Call& c, Cursors& nx);
+void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v);
+void stcorr_create (mtr_engine* e);
+int  stcorr_step (mtr_engine* e, const Call& c, Cursors& nx);
+void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v);
+// STCORR's section of a blob carries the period and the frames into the open one in every stream's entry (the header has no room for
+// them).  Export writes the host's copies into the `count` entries at `sec`; import checks the entries (MTR_ERR_STATE with the text set if
+// they are corrupt or — `fresh` false — not where the engine stands) and returns the two.
+void stcorr_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
+int  stcorr_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* period, uint32_t* fill);
+
+#pragma GCC visibility pop
+
+#endif

@@ -1,5 +1,6 @@
-// mtr_host.h — what the host-side TUs of libmtr_engine.so share (mtr_engine.hip, mtr_plan.cpp, mtr_comm.hip): the error path and
-// the planner's interface.  No HIP header here: the planner is built without one.
+// mtr_host.h — what ALL the host-side TUs of libmtr_engine.so share, the planner (mtr_plan.cpp) and the communicator (mtr_comm.hip)
+// included: the error path, the planner's interface, the communicator's.  No HIP header here: the planner is built without one.  What
+// needs one — the engine itself, a call — is in mtr_engine_impl.h.
 #ifndef MTR_HOST_H
 #define MTR_HOST_H
 

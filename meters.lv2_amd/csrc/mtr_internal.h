@@ -1,4 +1,6 @@
-/* mtr_internal.h — shared between the engine host code and the HIP kernel TUs. Not installed. */
+/* mtr_internal.h — what more than one TU of libmtr_engine.so needs of the kernels: the arguments and launchers of the fused path (the host side
+ * is mtr_call.hip), the stream state, the set-up math.  A side meter's arguments, state and launcher are in the meter's own file, next to
+ * its kernels and its host code.  Not installed. */
 #ifndef MTR_INTERNAL_H
 #define MTR_INTERNAL_H
 
@@ -18,7 +20,6 @@
 typedef struct mtr_stream_state mtr_stream_state;
 typedef struct mtr_fused_args mtr_fused_args;
 typedef struct mtr_gate_args mtr_gate_args;
-typedef struct mtr_bank_args mtr_bank_args;
 
 /* Per-stream persistent state (device). */
 struct mtr_stream_state {
@@ -140,97 +141,12 @@ struct mtr_gate_len_args : mtr_gate_args {
 #define MTR_GATE_CLOSING   0x80000000u
 #define MTR_GATE_UNTOUCHED 0xFFFFFFFFu
 
-struct mtr_bank_args {
-	const float*    audio;
-	uint64_t        stride;
-	uint64_t        n_frames;
-	const double*   coef;         /* [30][6][5]: b0 b1 b2 a1 a2 per section */
-	double*         z;            /* [S][30][12] section states */
-	float*          val;          /* [S][30] */
-	float*          mx;           /* [S][30] */
-	const int32_t*  ac_in;        /* [S] dither toggle parity at the start of the call (shared by the 30 bands of a stream) */
-	int32_t*        ac_out;       /* [S] ... and after it: ANOTHER buffer (a workgroup that starts late must still read the old one) */
-	uint32_t        n_streams, n_channels;
-	float           omega;
-};
-
-/* per-stream state of the integer paths */
+/* per-stream state of BITSTATS: shared by mtr_bitstats.hip (the kernel) and mtr_intstat.hip (the meter's host side) */
 typedef struct mtr_bitstats_state {
 	int32_t hist[MTR_BIM_LAST];      /* src/uris.h:53-60 layout */
 	int32_t n_zero, n_pos, n_nan, n_inf, n_den;
 	float   vmin, vmax;              /* bim_min (init +inf), bim_max (init 0) */
 } mtr_bitstats_state;
-
-typedef struct mtr_sigdist_state {
-	int32_t  bins[MTR_DIST_BIN];
-	int32_t  peak_cnt, peak_bin;
-	double   avg, var_m, var_s;      /* hist_avgS (sum), hist_tmpS (mean), hist_varS (M2) */
-	int64_t  count, n_binned;
-	unsigned long long last[MTR_DIST_BIN];   /* 1-based index of the last sample per bin (peak tie-break) */
-} mtr_sigdist_state;
-
-/* DR-14 per-stream state (src/dr14.c LV2dr14: rms_sum, peak_cur, peak_hist, m_rms, m_peak, num_fragments) */
-typedef struct mtr_dr14_state {
-	float    rms_sum[2], peak_cur[2], peak_hist[2][2], m_rms[2], m_peak[2];
-	uint32_t num_fragments;
-} mtr_dr14_state;
-
-typedef struct mtr_dr14_args {
-	const float*    audio;        /* [S][stride][C] */
-	uint64_t        stride, n_frames;
-	uint64_t        window;       /* n_sample_cnt + 1 samples close a window (dr14.c:404) */
-	uint64_t        e0;           /* call frame at which the window open on entry closes */
-	uint32_t        n_streams, n_channels, n_pieces, n_windows;
-	mtr_dr14_state* state;        /* [S] */
-	uint32_t*       hist;         /* [S][C][8000] */
-	double*         piece_sum;    /* [S][n_pieces][2] */
-	float*          piece_peak;   /* [S][n_pieces][2] */
-} mtr_dr14_args;
-
-/* Kmeterdsp per (stream, channel) state (jmeters/kmeterdsp.h) */
-typedef struct mtr_kmeter_state {
-	float    z1, z2, rms, peak;
-	int32_t  cnt, flag;
-} mtr_kmeter_state;
-
-typedef struct mtr_kmeter_args {
-	const float*    audio;        /* [S][stride][C] */
-	uint64_t        stride, n_groups;   /* n_frames / 4 (kmeterdsp.cc:71) */
-	uint32_t        n_streams, n_channels, n_pieces, fpp;
-	int32_t         hold;
-	float           omega, fall;
-	double          pw1[3];       /* A = [[a, 0], [c, b]] per group of four samples */
-	mtr_kmeter_state* state;      /* [S][2] */
-	double*         piece_state;  /* [S][n_pieces][4]: each chunk's weighted sums (z1, z2 per channel), already carried to the call's end */
-	float*          piece_max;    /* [S][n_pieces][2] */
-} mtr_kmeter_args;
-
-/* Stcorrdsp per-stream state (jmeters/stcorrdsp.h: _zl _zr _zlr _zll _zrr), the last reading, and — for the state blob, whose header has
- * no room for them — the engine's period and the frames into the open period (the host's copies rule; export writes them in) */
-typedef struct mtr_stcorr_state {
-	float    z[5];                /* zl zr zlr zll zrr */
-	float    corr;                /* Stcorrdsp::read () at the end of the most recent process (): the call (period 0) or the last completed period */
-	uint32_t period, fill;
-} mtr_stcorr_state;
-
-#define MTR_STCORR_PIECE 9         /* doubles per (stream, piece): the sums of zlr zll zrr carried to the piece's end, zl and zr there; of a piece
-                                    * that starts where a period ended inside the call also sum c rho zl, sum c rho zr (rho = (1 - w1)^(frames
-                                    * since the period end): what the sums owe to the start state) and the zl, zr it started from */
-typedef struct mtr_stcorr_args {
-	const float*    audio;        /* [S][stride][2] */
-	uint64_t        stride, n_frames;
-	uint64_t        period;       /* frames per process () of the reading series; 0: the call is one process () */
-	uint64_t        e0;           /* call frame at which the period open on entry ends (period 0: n_frames) */
-	uint32_t        n_streams, n_pieces;
-	uint32_t        chunk;        /* a period is cut into pieces of at most this many frames */
-	uint32_t        warm;         /* frames in front of a piece over which its first-stage state is rebuilt */
-	float           w1, w2;
-	uint32_t        capacity;     /* points per stream the series holds */
-	uint64_t        point0;       /* periods completed before this call: the series index of the first one that ends in it */
-	mtr_stcorr_state* state;      /* [S] */
-	double*         piece;        /* [S][n_pieces][MTR_STCORR_PIECE] */
-	float*          series;       /* [S][capacity], NULL if capacity == 0 */
-} mtr_stcorr_args;
 
 typedef struct mtr_tpb_args mtr_tpb_args;
 struct mtr_tpb_args {
@@ -268,14 +184,6 @@ int  mtr_launch_kw (int run, const mtr_fused_args& a, uint32_t n_units, void* st
 int  mtr_launch_kwtp16 (int run, bool ebu, const mtr_fused_args& a, uint32_t n_units, void* stream);
 int  mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* stream);
 size_t mtr_seg_lds_bytes (void);
-int  mtr_launch_dr14 (const mtr_dr14_args& a, void* stream);
-int  mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream);
-void mtr_kmeter_powers (float omega, double* pw1 /* [3] */);
-uint32_t mtr_kmeter_pieces (uint64_t n_groups);
-/* mtr_stcorr.hip: the warm-up and the piece size that go with w1; the pieces of a call (its periods, each cut at `chunk`); the launch */
-void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk);
-uint32_t mtr_stcorr_pieces (uint64_t n_frames, uint64_t e0, uint64_t period, uint32_t chunk);
-int  mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream);
 int  mtr_fused2_upload_taps (const float* g144);
 /* A trailing `ends` / `frag_lim` (per stream, device memory) selects the instantiation of a call with per-stream lengths; NULL the
  * dense one.  With lengths a stream with ends [s] == 0 keeps its history and is not folded. */
@@ -296,12 +204,9 @@ int  mtr_launch_history_mc51 (const float* audio, uint64_t stride, uint64_t n_fr
 int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
-int  mtr_launch_bank (const mtr_bank_args& a, void* stream);
 int  mtr_launch_tpb (const mtr_tpb_args& a, void* stream);
 int  mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
                           uint32_t n_streams, void* stream);
-int  mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_frames, mtr_sigdist_state* out,
-                         uint32_t n_streams, void* stream);
 int  mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
                               float* hist_out, uint32_t n_streams, void* stream);
 int  mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint32_t n_streams, int32_t* d_hist, float* d_max, void* stream);

@@ -24,7 +24,20 @@
 // (tests/test_gpu_intstat.py checks both, var_m / var_s against the oracle at 1e-12 relative).
 #include <hip/hip_runtime.h>
 
-#include "mtr_internal.h"
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+
+/* per-stream state of SIGDIST (BITSTATS: mtr_bitstats_state, mtr_internal.h) */
+typedef struct mtr_sigdist_state {
+	int32_t  bins[MTR_DIST_BIN];
+	int32_t  peak_cnt, peak_bin;
+	double   avg, var_m, var_s;      /* hist_avgS (sum), hist_tmpS (mean), hist_varS (M2) */
+	int64_t  count, n_binned;
+	unsigned long long last[MTR_DIST_BIN];   /* 1-based index of the last sample per bin (peak tie-break) */
+} mtr_sigdist_state;
 
 
 __global__ __launch_bounds__ (256) void k_sigdist (const float* audio, uint64_t stride, uint64_t n_frames,
@@ -146,9 +159,92 @@ __global__ __launch_bounds__ (256) void k_sigdist (const float* audio, uint64_t 
 	}
 }
 
-int mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_frames, mtr_sigdist_state* out,
+static int mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_frames, mtr_sigdist_state* out,
                         uint32_t n_streams, void* stream)
 {
 	hipLaunchKernelGGL (k_sigdist, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- BITSTATS and SIGDIST in the engine (they share their reset and their step): the call's step, the blob's sections, reset, the getters
+
+// (the integer tables are int32, as the reference's, which stops counting at 2^31 - 1 samples; the kernels index
+// a call's samples with 32 bits: checked on entry)
+int intstat_step (mtr_engine* e, const Call& c, Cursors&)
+{
+	if (e->cfg.meters & MTR_METER_BITSTATS)
+		if (mtr_launch_bitstats (c.audio, c.stride, c.n_frames, e->is.bim.p + c.off, c.cnt, c.st)) return fail (MTR_ERR_HIP, "k_bitstats launch");
+	if (e->cfg.meters & MTR_METER_SIGDIST)
+		if (mtr_launch_sigdist (c.audio, c.stride, c.n_frames, e->is.sdh.p + c.off, c.cnt, c.st)) return fail (MTR_ERR_HIP, "k_sigdist launch");
+	return MTR_OK;
+}
+
+void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	const uint32_t m = e->cfg.meters;
+	if (m & MTR_METER_BITSTATS) v.push_back ({ e->is.bim.p, sizeof (mtr_bitstats_state) });
+	if (m & MTR_METER_SIGDIST) v.push_back ({ e->is.sdh.p, sizeof (mtr_sigdist_state) });
+}
+
+extern "C" {
+
+int mtr_engine_intstat_reset (mtr_engine* e)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t S = e->cfg.n_streams;
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	if (e->cfg.meters & MTR_METER_BITSTATS) {
+		std::vector<mtr_bitstats_state> h (S);
+		memset (h.data (), 0, S * sizeof (mtr_bitstats_state));
+		for (auto& b : h) { b.vmin = INFINITY; b.vmax = 0; }          // bim_clear, src/bitmeter.c:47-55
+		if (e->is.bim.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc bitstats state");
+		HIPCHK (hipMemcpy (e->is.bim.p, h.data (), S * sizeof (mtr_bitstats_state), hipMemcpyHostToDevice));
+	}
+	if (e->cfg.meters & MTR_METER_SIGDIST) {
+		if (e->is.sdh.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc sigdist state");
+		std::vector<mtr_sigdist_state> h (S);
+		memset (h.data (), 0, S * sizeof (mtr_sigdist_state));
+		for (auto& d : h) d.peak_bin = -1;                            // sdh_reset, src/sigdistlv2.c:54: no peak yet
+		HIPCHK (hipMemcpy (e->is.sdh.p, h.data (), S * sizeof (mtr_sigdist_state), hipMemcpyHostToDevice));
+	}
+	return MTR_OK;
+}
+
+int mtr_engine_bitstats (mtr_engine* e, uint32_t first, uint32_t count, int32_t* hist, int32_t* counters, float* minmax)
+{
+	if (!e || !(e->cfg.meters & MTR_METER_BITSTATS)) return fail (MTR_ERR_ARG, "no BITSTATS in this engine");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range out of bounds");
+	if (count == 0) return MTR_OK;
+	int rc = mtr_engine_sync (e);
+	if (rc) return rc;
+	std::vector<mtr_bitstats_state> h (count);
+	HIPCHK (hipMemcpy (h.data (), e->is.bim.p + first, count * sizeof (mtr_bitstats_state), hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < count; ++i) {
+		if (hist) memcpy (hist + (size_t) i * MTR_BIM_LAST, h[i].hist, sizeof (h[i].hist));
+		if (counters) { int32_t* c = counters + (size_t) i * 5; c[0] = h[i].n_zero; c[1] = h[i].n_pos; c[2] = h[i].n_nan; c[3] = h[i].n_inf; c[4] = h[i].n_den; }
+		if (minmax) { minmax[2 * i] = h[i].vmin; minmax[2 * i + 1] = h[i].vmax; }
+	}
+	return MTR_OK;
+}
+
+int mtr_engine_sigdist (mtr_engine* e, uint32_t first, uint32_t count, int32_t* bins, int32_t* peak, double* moments, int64_t* n)
+{
+	if (!e || !(e->cfg.meters & MTR_METER_SIGDIST)) return fail (MTR_ERR_ARG, "no SIGDIST in this engine");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range out of bounds");
+	if (count == 0) return MTR_OK;
+	int rc = mtr_engine_sync (e);
+	if (rc) return rc;
+	std::vector<mtr_sigdist_state> h (count);
+	HIPCHK (hipMemcpy (h.data (), e->is.sdh.p + first, count * sizeof (mtr_sigdist_state), hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < count; ++i) {
+		if (bins) memcpy (bins + (size_t) i * MTR_DIST_BIN, h[i].bins, sizeof (h[i].bins));
+		if (peak) { peak[2 * i] = h[i].peak_cnt; peak[2 * i + 1] = h[i].peak_bin; }
+		if (moments) { moments[3 * i] = h[i].avg; moments[3 * i + 1] = h[i].var_m; moments[3 * i + 2] = h[i].var_s; }
+		if (n) n[i] = h[i].count;
+	}
+	return MTR_OK;
+}
+
+} // extern "C"

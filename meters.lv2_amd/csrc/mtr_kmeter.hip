@@ -20,7 +20,30 @@
 // relative against the restatement.
 #include <hip/hip_runtime.h>
 
-#include "mtr_internal.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+
+/* Kmeterdsp per (stream, channel) state (jmeters/kmeterdsp.h) */
+typedef struct mtr_kmeter_state {
+	float    z1, z2, rms, peak;
+	int32_t  cnt, flag;
+} mtr_kmeter_state;
+
+typedef struct mtr_kmeter_args {
+	const float*    audio;        /* [S][stride][C] */
+	uint64_t        stride, n_groups;   /* n_frames / 4 (kmeterdsp.cc:71) */
+	uint32_t        n_streams, n_channels, n_pieces, fpp;
+	int32_t         hold;
+	float           omega, fall;
+	double          pw1[3];       /* A = [[a, 0], [c, b]] per group of four samples */
+	mtr_kmeter_state* state;      /* [S][2] */
+	double*         piece_state;  /* [S][n_pieces][4]: each chunk's weighted sums (z1, z2 per channel), already carried to the call's end */
+	float*          piece_max;    /* [S][n_pieces][2] */
+} mtr_kmeter_args;
 
 namespace {
 
@@ -141,16 +164,16 @@ __global__ void k_kmeter_final (const mtr_kmeter_args a)
 
 }  // namespace
 
-void mtr_kmeter_powers (float omega, double* pw1 /* [3] */)
+static void mtr_kmeter_powers (float omega, double* pw1 /* [3] */)
 {
 	const double w = (double) omega;
 	const double a1 = pow (1.0 - w, 4.0), b1 = 1.0 - 4.0 * w, c1 = 4.0 * w * a1;
 	pw1[0] = a1; pw1[1] = c1; pw1[2] = b1;
 }
 
-uint32_t mtr_kmeter_pieces (uint64_t n_groups) { return (uint32_t) ((n_groups + CH - 1) / CH); }
+static uint32_t mtr_kmeter_pieces (uint64_t n_groups) { return (uint32_t) ((n_groups + CH - 1) / CH); }
 
-int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
+static int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
 	if (a.n_pieces) {
@@ -161,3 +184,61 @@ int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
 	hipLaunchKernelGGL (k_kmeter_final, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- KMETER in the engine: the call's step, the blob's section, reset, the reading ------------------------------------------------------
+
+int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx)
+{
+	const size_t vo = c.off;
+	mtr_kmeter_args ka;
+	ka.audio = c.audio; ka.stride = c.stride; ka.n_groups = c.n_frames / 4;
+	ka.n_streams = c.cnt; ka.n_channels = e->cfg.n_channels;
+	ka.n_pieces = mtr_kmeter_pieces (ka.n_groups);
+	if (nx.km_fpp != (uint32_t) c.n_frames) {                          // kmeterdsp.cc:60-65
+		nx.km_fall = powf (10.0f, -0.05f * 15.0f * ((float) c.n_frames / e->cfg.sample_rate));
+		nx.km_fpp = (uint32_t) c.n_frames;
+	}
+	ka.fpp = nx.km_fpp; ka.fall = nx.km_fall;
+	ka.hold = (int32_t) (0.5f * e->cfg.sample_rate + 0.5f);             // :51
+	ka.omega = 9.72f / e->cfg.sample_rate;
+	memcpy (ka.pw1, e->km.pw1, sizeof (ka.pw1));
+	ka.state = e->km.state.p + vo * 2;
+	if (e->km.piece.reserve ((size_t) e->cfg.n_streams * std::max<uint32_t> (ka.n_pieces, 1) * 4) || e->km.max.reserve ((size_t) e->cfg.n_streams * std::max<uint32_t> (ka.n_pieces, 1) * 2))
+		return fail (MTR_ERR_NOMEM, "hipMalloc KMETER pieces");
+	ka.piece_state = e->km.piece.p + vo * ka.n_pieces * 4; ka.piece_max = e->km.max.p + vo * ka.n_pieces * 2;
+	if (mtr_launch_kmeter (ka, c.st)) return fail (MTR_ERR_HIP, "k_kmeter launch");
+	return MTR_OK;
+}
+
+void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	v.push_back ({ e->km.state.p, 2 * sizeof (mtr_kmeter_state) });
+}
+
+extern "C" {
+
+int mtr_engine_kmeter_reset (mtr_engine* e)
+{
+	if (!e || !(e->cfg.meters & MTR_METER_KMETER)) return fail (MTR_ERR_ARG, "no KMETER in this engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const size_t n = (size_t) e->cfg.n_streams * 2;
+	if (e->km.state.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc KMETER state");
+	mtr_kmeter_powers (9.72f / e->cfg.sample_rate, e->km.pw1);           // kmeterdsp.cc:52
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemset (e->km.state.p, 0, n * sizeof (mtr_kmeter_state)));   // :142-146
+	return MTR_OK;
+}
+
+int mtr_engine_kmeter_read (mtr_engine* e, uint32_t first, uint32_t count, float* rms, float* peak)
+{
+	int rc = meter_range (e, e && rms && peak && (e->cfg.meters & MTR_METER_KMETER), "no KMETER in this engine", first, count);
+	if (rc || (rc = wait_stream (e))) return rc;
+	std::vector<mtr_kmeter_state> h ((size_t) count * 2);
+	HIPCHK (hipMemcpy (h.data (), e->km.state.p + (size_t) first * 2, h.size () * sizeof (mtr_kmeter_state), hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < h.size (); ++i) { rms[i] = h[i].rms; peak[i] = h[i].peak; h[i].flag = 1; }
+	HIPCHK (hipMemcpy (e->km.state.p + (size_t) first * 2, h.data (), h.size () * sizeof (mtr_kmeter_state), hipMemcpyHostToDevice));
+	return MTR_OK;
+}
+
+} // extern "C"

@@ -35,7 +35,39 @@
 // there; here the double sum may decay back into f32's range before the period ends and a finite reading comes out.)
 #include <hip/hip_runtime.h>
 
-#include "mtr_internal.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+
+/* Stcorrdsp per-stream state (jmeters/stcorrdsp.h: _zl _zr _zlr _zll _zrr), the last reading, and — for the state blob, whose header has
+ * no room for them — the engine's period and the frames into the open period (the host's copies rule; export writes them in) */
+typedef struct mtr_stcorr_state {
+	float    z[5];                /* zl zr zlr zll zrr */
+	float    corr;                /* Stcorrdsp::read () at the end of the most recent process (): the call (period 0) or the last completed period */
+	uint32_t period, fill;
+} mtr_stcorr_state;
+
+#define MTR_STCORR_PIECE 9         /* doubles per (stream, piece): the sums of zlr zll zrr carried to the piece's end, zl and zr there; of a piece
+                                    * that starts where a period ended inside the call also sum c rho zl, sum c rho zr (rho = (1 - w1)^(frames
+                                    * since the period end): what the sums owe to the start state) and the zl, zr it started from */
+typedef struct mtr_stcorr_args {
+	const float*    audio;        /* [S][stride][2] */
+	uint64_t        stride, n_frames;
+	uint64_t        period;       /* frames per process () of the reading series; 0: the call is one process () */
+	uint64_t        e0;           /* call frame at which the period open on entry ends (period 0: n_frames) */
+	uint32_t        n_streams, n_pieces;
+	uint32_t        chunk;        /* a period is cut into pieces of at most this many frames */
+	uint32_t        warm;         /* frames in front of a piece over which its first-stage state is rebuilt */
+	float           w1, w2;
+	uint32_t        capacity;     /* points per stream the series holds */
+	uint64_t        point0;       /* periods completed before this call: the series index of the first one that ends in it */
+	mtr_stcorr_state* state;      /* [S] */
+	double*         piece;        /* [S][n_pieces][MTR_STCORR_PIECE] */
+	float*          series;       /* [S][capacity], NULL if capacity == 0 */
+} mtr_stcorr_args;
 
 namespace {
 
@@ -326,7 +358,7 @@ __global__ void k_stcorr_final (const mtr_stcorr_args a)
 
 }  // namespace
 
-void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk)
+static void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk)
 {
 	// |1 - w1|^J < 2^-48: what the rebuilt state lacks is below the resolution of the double sums, not only of an f32.
 	// (|1 - w1| < 1 from 8 kHz up — w1 = 1.57 there; a rate so high that J would take half the tiles gets half the tiles.)
@@ -339,7 +371,7 @@ void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk)
 	*chunk = MAX_TILES * TILE - *warm;
 }
 
-uint32_t mtr_stcorr_pieces (uint64_t n_frames, uint64_t e0, uint64_t period, uint32_t chunk)
+static uint32_t mtr_stcorr_pieces (uint64_t n_frames, uint64_t e0, uint64_t period, uint32_t chunk)
 {
 	const uint64_t first = e0 < n_frames ? e0 : n_frames;
 	uint64_t n = div_up (first, chunk);
@@ -350,10 +382,145 @@ uint32_t mtr_stcorr_pieces (uint64_t n_frames, uint64_t e0, uint64_t period, uin
 	return (uint32_t) n;
 }
 
-int mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream)
+static int mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
 	hipLaunchKernelGGL (k_stcorr_pieces, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
 	hipLaunchKernelGGL (k_stcorr_final, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- STCORR in the engine: set-up, the call's step, the blob's section and the cursors in it, the C entry points -----------------------
+
+void stcorr_create (mtr_engine* e)
+{
+	mtr_setup_stcorr (e->cfg.sample_rate, e->sc.w);
+	mtr_stcorr_geometry (e->sc.w[0], &e->sc.warm, &e->sc.chunk);
+}
+
+// The periods of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+int stcorr_step (mtr_engine* e, const Call& c, Cursors& nx)
+{
+	const size_t vo = c.off;
+	const uint64_t P = e->sc.period;
+	mtr_stcorr_args sa;
+	sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
+	sa.period = P; sa.e0 = P ? P - e->pos.sc_fill : c.n_frames;
+	sa.n_streams = c.cnt; sa.chunk = e->sc.chunk; sa.warm = e->sc.warm;
+	sa.n_pieces = mtr_stcorr_pieces (c.n_frames, sa.e0, P, sa.chunk);
+	sa.w1 = e->sc.w[0]; sa.w2 = e->sc.w[1];
+	sa.capacity = e->sc.cap; sa.point0 = e->pos.sc_points;
+	if (e->sc.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_STCORR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR pieces");
+	sa.state = e->sc.state.p + vo; sa.piece = e->sc.piece.p + vo * sa.n_pieces * MTR_STCORR_PIECE;
+	sa.series = e->sc.cap ? e->sc.series.p + vo * e->sc.cap : nullptr;
+	if (mtr_launch_stcorr (sa, c.st)) return fail (MTR_ERR_HIP, "k_stcorr launch");
+	const uint64_t tot = e->pos.sc_fill + c.n_frames;
+	nx.sc_fill = P ? tot % P : 0;
+	nx.sc_points = e->pos.sc_points + (P ? tot / P : 0);
+	return MTR_OK;
+}
+
+void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	v.push_back ({ e->sc.state.p, sizeof (mtr_stcorr_state) });
+}
+
+void stcorr_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
+{
+	for (uint32_t k = 0; k < count; ++k) {
+		mtr_stcorr_state v;
+		unsigned char* const at = sec + (size_t) k * sizeof (v);
+		memcpy (&v, at, sizeof (v));
+		v.period = e->sc.period; v.fill = (uint32_t) e->pos.sc_fill;
+		memcpy (at, &v, sizeof (v));
+	}
+}
+
+int stcorr_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* period, uint32_t* fill)
+{
+	uint32_t sc_period = 0, sc_fill = 0;
+	for (uint32_t k = 0; k < count; ++k) {
+		mtr_stcorr_state v;
+		memcpy (&v, sec + (size_t) k * sizeof (v), sizeof (v));
+		if (k == 0) { sc_period = v.period; sc_fill = v.fill; }
+		if (v.period != sc_period || v.fill != sc_fill || (sc_period ? sc_fill >= sc_period || sc_period < (uint32_t) e->cfg.sample_rate / 20 : sc_fill != 0))
+			return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (period of the STCORR series)");
+	}
+	if (!fresh && (sc_period != e->sc.period || sc_fill != e->pos.sc_fill))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period of the STCORR series)");
+	*period = sc_period; *fill = sc_fill;
+	return MTR_OK;
+}
+
+extern "C" {
+
+int mtr_stcorr_coef (float sample_rate, float* out2)
+{
+	if (!out2 || !(sample_rate >= 1.f)) return fail (MTR_ERR_ARG, "mtr_stcorr_coef");
+	mtr_setup_stcorr (sample_rate, out2);
+	return MTR_OK;
+}
+
+static int no_stcorr (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_STCORR); }
+
+int mtr_engine_stcorr_reset (mtr_engine* e)
+{
+	if (no_stcorr (e)) return fail (MTR_ERR_ARG, "no STCORR in this engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t S = e->cfg.n_streams;
+	if (e->sc.state.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR state");
+	std::vector<mtr_stcorr_state> h (S);
+	memset (h.data (), 0, S * sizeof (mtr_stcorr_state));          // stcorrdsp.cc:33-36
+	for (auto& v : h) v.period = e->sc.period;
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemcpy (e->sc.state.p, h.data (), S * sizeof (mtr_stcorr_state), hipMemcpyHostToDevice));
+	e->pos.sc_fill = 0;
+	e->pos.sc_points = 0;
+	return MTR_OK;
+}
+
+int mtr_engine_stcorr_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
+{
+	if (no_stcorr (e)) return fail (MTR_ERR_ARG, "no STCORR in this engine");
+	if (period_frames && (period_frames < (uint32_t) e->cfg.sample_rate / 20 || period_frames >= 0x7fffffffu))
+		return fail (MTR_ERR_ARG, "mtr_engine_stcorr_set_period: a period is 0 or at least (uint32_t) sample_rate / 20 frames");
+	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_stcorr_set_period: only on an engine that has processed nothing since create / reset");
+	{ const int rc = wait_stream (e); if (rc) return rc; }
+	const size_t n = (size_t) e->cfg.n_streams * capacity_points;
+	if (n && e->sc.series.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR series");
+	if (n) HIPCHK (hipMemset (e->sc.series.p, 0, n * sizeof (float)));
+	e->sc.period = period_frames;
+	e->sc.cap = capacity_points;
+	return mtr_engine_stcorr_reset (e);
+}
+
+int mtr_engine_stcorr_read (mtr_engine* e, uint32_t first, uint32_t count, float* corr, float* state5)
+{
+	int rc = meter_range (e, !no_stcorr (e) && corr, "no STCORR in this engine", first, count);
+	if (rc || (rc = wait_stream (e))) return rc;
+	std::vector<mtr_stcorr_state> h (count);
+	if (count) HIPCHK (hipMemcpy (h.data (), e->sc.state.p + first, count * sizeof (mtr_stcorr_state), hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < count; ++i) {
+		corr[i] = h[i].corr;
+		if (state5) memcpy (state5 + (size_t) i * 5, h[i].z, sizeof (h[i].z));
+	}
+	return MTR_OK;
+}
+
+int mtr_engine_stcorr_series (mtr_engine* e, uint32_t first, uint32_t count, float* out, uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_stcorr (e), "no STCORR in this engine", first, count);
+	if (rc) return rc;
+	const uint64_t n = e->pos.sc_points, kept = std::min<uint64_t> (n, e->sc.cap);
+	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
+	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
+	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	if (!out || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	HIPCHK (hipMemcpy2D (out, (size_t) capacity * sizeof (float), e->sc.series.p + (size_t) first * e->sc.cap, (size_t) e->sc.cap * sizeof (float),
+	                     take * sizeof (float), count, hipMemcpyDeviceToHost));
+	return MTR_OK;
+}
+
+} // extern "C"
