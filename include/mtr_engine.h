@@ -28,7 +28,8 @@ extern "C" {
 /* 2 (unchanged by later additions a client looks up by name: mtr_engine_truepeak_channels; mtr_engine_process_device_lengths,
  *    _process_host_lengths, _stream_frames; mtr_engine_process_host_pcm, _process_device_pcm, _pcm_stats, mtr_pcm_sample_bytes,
  *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host; MTR_METER_STCORR, mtr_stcorr_coef,
- *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset; mtr_engine_loudlog_set_period, _loudlog_period,
+ *    _loudlog_series, _loudlog_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -338,6 +339,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 
 /* Stcorrdsp for a batch (MTR_METER_STCORR): mtr_stcorr_coef and mtr_engine_stcorr_set_period / _read / _series / _reset */
 #include "mtr_stcorr.h"
+
+/* The loudness log of an MTR_METER_EBU engine — momentary / short-term loudness over time, a (M, S) point per period of P fragments
+ * and stream: mtr_engine_loudlog_set_period / _period / _series / _reset */
+#include "mtr_loudlog.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

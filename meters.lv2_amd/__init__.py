@@ -10,5 +10,5 @@ from .engine import (  # noqa: F401
     Engine, EngineError, StreamResult, lib, lib_path, Comm, comm_unique_id,
     METER_EBU, METER_TRUEPEAK, METER_SPECTR30, METER_TPBALLIST, METER_BITSTATS, METER_SIGDIST, METER_DR14, METER_KMETER, METER_STCORR,
     fir_table, kweight_coef, band_coef, hist_loudness, stcorr_coef, synth_fill_device, exported_symbols, plan_query,
-    PCM_S16, PCM_S24, PCM_S32, pcm_decode, pick_decode,
+    PCM_S16, PCM_S24, PCM_S32, pcm_decode, pick_decode, LOUDLOG_SAMPLE, LOUDLOG_MAX,
 )

@@ -381,7 +381,10 @@ struct CallRun {
 		ga.max_scratch = e->gate_max.p + (size_t) c.off * 2;
 		ga.fold_tp = (fold_in_history || e->layout == 8) ? 0 : 1;   // (layout 8: k_history_mc folds the per-channel peaks)
 		ga.polite_grid = r.defer ? e->tail_gate_grid : 0;
-		if (mtr_launch_gate (ga, d_lim, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
+		// (the loudness log: where the streams stand in it is an argument, computed here — the gate may run a call late)
+		mtr_loudlog_args la;
+		const bool log = ebu && loudlog_args (e, e->pos, c.off, &la);
+		if (mtr_launch_gate (ga, d_lim, log ? &la : nullptr, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
 		if (ls) { HIPCHK (hipEventRecord (ls->done[1].v, gst)); ls->pending[1] = true; }
 		{ const int rc = mark (3, gst); if (rc) return rc; }
 		{
@@ -392,6 +395,7 @@ struct CallRun {
 		if (r.defer) { HIPCHK (hipEventRecord (e->ev_gate[tb].v, gst)); e->gate_pending[tb] = true; }
 		e->last_n_frag = ga.n_frag;
 		nx.frcnt = pl.frcnt_out;
+		if (log) nx.ll_frags = e->pos.ll_frags + ga.n_frag;
 		return MTR_OK;
 	}
 
@@ -478,11 +482,17 @@ struct CallRun {
 			if (v) { HIPCHK (hipEventRecord (v, c.st)); e->timed_calls++; }   // (a call without all of its events is not a timed call)
 		}
 		// everything is queued.  Frames metered per stream; a stream that ends inside a call with lengths is closed by it
+		const bool log = ebu && e->ll.period;
 		for (uint32_t i = 0; i < c.cnt; ++i) {
 			const size_t g = (size_t) c.off + i;
 			if (e->closed[g]) continue;
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
+			if (log) {
+				// periods the stream completed: those that end within the fragments it ended (as upload_lengths counts them)
+				const uint64_t nf = f == c.n_frames ? pl.n_frag : (uint64_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
+				e->ll.points[g] += (e->pos.ll_frags % e->ll.period + nf) / e->ll.period;
+			}
 			if (f < c.n_frames) { e->closed[g] = 1; e->n_closed++; }
 		}
 		if (c.commit) e->pos = nx;

@@ -335,6 +335,7 @@ int mtr_engine_reset (mtr_engine* e)
 	if (e->cfg.meters & MTR_METER_DR14) { const int drc = mtr_engine_dr14_reset (e); if (drc) return drc; }
 	if (e->cfg.meters & MTR_METER_KMETER) { const int krc = mtr_engine_kmeter_reset (e); if (krc) return krc; e->pos.km_fpp = 0; e->pos.km_fall = 0.f; }
 	if (e->cfg.meters & MTR_METER_STCORR) { const int src = mtr_engine_stcorr_reset (e); if (src) return src; }
+	if (e->ll.period) { const int lrc = loudlog_reset (e, st); if (lrc) return lrc; }
 	if (e->cfg.meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) return mtr_engine_intstat_reset (e);
 	return MTR_OK;
 }

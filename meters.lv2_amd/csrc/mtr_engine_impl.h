@@ -1,6 +1,7 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
 // EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
-// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip).  Not installed; needs the HIP
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip), and mtr_loudlog.hip (the host
+// side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
 #ifndef MTR_ENGINE_IMPL_H
 #define MTR_ENGINE_IMPL_H
@@ -102,6 +103,7 @@ struct Cursors {
 	uint64_t sc_fill = 0;         // STCORR: frames in the open period of the reading series ...
 	uint64_t sc_points = 0;       // ... and periods completed since reset
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
+	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 };
 
 // per-stream state of the side meters: defined where their kernels are
@@ -248,6 +250,14 @@ struct mtr_engine {
 		float                      w[2];        // w1, w2 of Stcorrdsp::init
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
 	} sc;
+	struct LoudLog {                            // the loudness log of an EBU engine (mtr_loudlog.hip; the gate appends: mtr_gate.hip)
+		DevBuf<float>              M, S;        // [S][cap]
+		DevBuf<float>              run;         // [S][2] MAX: maxima of the period open between two calls
+		DevBuf<int32_t>            run_new;     // [S][2] ... scratch of the multi-workgroup gate, sortable ints
+		uint32_t                   period = 0, cap = 0;   // fragments per point (0: off), points per stream the series holds
+		int                        mode = 0;
+		std::vector<uint64_t>      points;      // [S] periods each stream has completed (streams end at their own lengths)
+	} ll;
 };
 
 constexpr int EV_PER_CALL = 7;
@@ -306,6 +316,10 @@ void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v);
 // STCORR's section of a blob carries the period and the frames into the open one in every stream's entry (the header has no room for
 // them).  Export writes the host's copies into the `count` entries at `sec`; import checks the entries (MTR_ERR_STATE with the text set if
 // they are corrupt or — `fresh` false — not where the engine stands) and returns the two.
+// the loudness log: what the gate of a call that starts at cursors `pos` appends to, for the view [off, off + cnt) (false: the log is off);
+// its part of mtr_engine_reset
+bool loudlog_args (const mtr_engine* e, const Cursors& pos, uint32_t off, mtr_loudlog_args* out);
+int  loudlog_reset (mtr_engine* e, hipStream_t st);
 void stcorr_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
 int  stcorr_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* period, uint32_t* fill);
 

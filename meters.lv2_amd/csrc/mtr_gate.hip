@@ -25,9 +25,12 @@
 
 #define CHUNK 256
 
-// the kernel arguments of a gate kernel: the dense instantiation's are the struct it always took
-template <bool LEN> using gate_args_t = std::conditional_t<LEN, mtr_gate_len_args, mtr_gate_args>;
-template <bool LEN> __device__ __forceinline__ uint32_t gate_lim (const gate_args_t<LEN>& a, uint32_t s)
+// the kernel arguments of a gate kernel: the dense instantiation's are the struct it always took; LOG (the loudness log is on,
+// mtr_loudlog.hip) puts the log's arguments behind them — without it an instantiation is the kernel it was before there was a log
+template <bool LEN> using gate_base_t = std::conditional_t<LEN, mtr_gate_len_args, mtr_gate_args>;
+template <bool LEN> struct gate_log_args : gate_base_t<LEN> { mtr_loudlog_args log; };
+template <bool LEN, bool LOG = false> using gate_args_t = std::conditional_t<LOG, gate_log_args<LEN>, gate_base_t<LEN>>;
+template <bool LEN> __device__ __forceinline__ uint32_t gate_lim (const gate_base_t<LEN>& a, uint32_t s)
 {
 	if constexpr (LEN) return a.frag_lim[s];
 	else return 0u;
@@ -149,14 +152,23 @@ __device__ __forceinline__ void hist_add (int32_t* h, int32_t* count, int32_t* e
 // before its end — f_calc and the values a getter sees follow from that count; a stream the call closes does not carry its open
 // fragment, and an untouched one (MTR_GATE_UNTOUCHED) is left as it is, fold included.  The dense instantiation is the kernel as
 // it always was.
-template <bool LEN>
-__global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN> a)
+//
+// LOG (the loudness log): the lane that holds the last fragment of a period appends the period's point — its own (lm, ls)
+// (MTR_LOUDLOG_SAMPLE) or the maxima over the period's fragments (MTR_LOUDLOG_MAX): those of this chunk from LDS, those before it —
+// earlier chunks, earlier calls — from the running maxima the workgroup carries from chunk to chunk and the stream from call to call.
+template <bool LEN, bool LOG>
+__global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN, LOG> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[64 + CHUNK];          // chronological fragment powers: 64 history + chunk
 	__shared__ int32_t sh_hist[2][MTR_HIST_LEN];
 	__shared__ float   sh_red[2][256];
 	__shared__ int32_t sh_cnt[4];               // cnt_M cnt_S err_M err_S
+	float* ll = nullptr;                        // LOG, MAX: [2][CHUNK] lm / ls of the chunk, then the two running maxima
+	if constexpr (LOG) {
+		__shared__ float sh_ll[2 * CHUNK + 2];
+		ll = sh_ll;
+	}
 
 	const int tid = threadIdx.x;
 	// (a workgroup walks streams blockIdx.x, blockIdx.x + gridDim.x, ...: one each when the grid is the batch — the serial
@@ -183,6 +195,8 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN> a)
 	const float frpwr0 = st->frpwr;
 	float max_M = st->max_M, max_S = st->max_S;
 	float last_M = st->loud_M, last_S = st->loud_S;
+	float run_M = -INFINITY, run_S = -INFINITY;    // LOG, MAX: maxima of the open period in front of the chunk (workgroup-uniform)
+	if constexpr (LOG) if (a.log.mode == MTR_LOUDLOG_MAX) { run_M = a.log.run[2 * s]; run_S = a.log.run[2 * s + 1]; }
 	__syncthreads ();
 
 	// Index (within this call) of the last fragment at which _div2 wraps: calc_* run there.
@@ -213,6 +227,33 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN> a)
 			ls = addfrags (&pw[64 + tid], 60);
 			if (!isfinite (lm) || lm < -200.f) lm = -200.0f;
 			if (!isfinite (ls) || ls < -200.f) ls = -200.0f;
+		}
+		if constexpr (LOG) {
+			const mtr_loudlog_args& g = a.log;
+			float* const Mrow = g.M + (size_t) s * g.cap + g.point0;
+			float* const Srow = g.S + (size_t) s * g.cap + g.point0;
+			const uint32_t q = g.phase + base + (uint32_t) tid + 1;     // fragments of the log up to and including this lane's, from the start of the period open when the call began
+			const bool ends = tid < nf && q % g.period == 0;
+			if (g.mode == MTR_LOUDLOG_SAMPLE) {
+				if (ends && q / g.period - 1 < g.room) { Mrow[q / g.period - 1] = lm; Srow[q / g.period - 1] = ls; }
+			} else {
+				ll[tid] = lm; ll[CHUNK + tid] = ls;
+				__syncthreads ();
+				if (ends || tid == nf - 1) {
+					const uint32_t in_period = ends ? g.period : q % g.period;      // fragments of this lane's period up to and including its own
+					const int here = (int) min (in_period, (uint32_t) tid + 1);      // ... of which in this chunk
+					float m = -INFINITY, v = -INFINITY;
+					for (int i = 0; i < here; ++i) {
+						m = ll[tid - i] > m ? ll[tid - i] : m;
+						v = ll[CHUNK + tid - i] > v ? ll[CHUNK + tid - i] : v;
+					}
+					if (in_period > (uint32_t) tid + 1) { m = run_M > m ? run_M : m; v = run_S > v ? run_S : v; }   // it began in front of the chunk
+					if (ends && q / g.period - 1 < g.room) { Mrow[q / g.period - 1] = m; Srow[q / g.period - 1] = v; }
+					if (tid == nf - 1) { ll[2 * CHUNK] = ends ? -INFINITY : m; ll[2 * CHUNK + 1] = ends ? -INFINITY : v; }
+				}
+				__syncthreads ();
+				run_M = ll[2 * CHUNK]; run_S = ll[2 * CHUNK + 1];
+			}
 		}
 		// histogram inserts up to and including f_calc go in now, the rest after calc_*
 		const int f_abs = (int) base + tid;
@@ -274,6 +315,7 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN> a)
 		// true-peak hold (a deferred gate runs beside the next call's fused kernel, which is already raising tp_call:
 		// then k_history has folded it on the caller's stream — mtr_fold_truepeak, mtr_internal.h)
 		if (a.fold_tp) mtr_fold_truepeak (st);
+		if constexpr (LOG) if (a.log.mode == MTR_LOUDLOG_MAX) { a.log.run[2 * s] = run_M; a.log.run[2 * s + 1] = run_S; }
 	}
 	for (int i = tid; i < 64; i += 256) st->ring[i] = pw[i];
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) ghist[i] = (&sh_hist[0][0])[i];
@@ -315,13 +357,23 @@ __device__ __forceinline__ int gate_f_calc (const mtr_gate_args& a, int div2_0, 
 	return f >= 0 ? f : -1;
 }
 
-template <bool LEN>
-__global__ __launch_bounds__ (256) void k_gate_frag (const gate_args_t<LEN> a)
+// LOG, MTR_LOUDLOG_MAX: a period that lies inside one block and inside this call is stored by the lane of its last fragment, as in
+// k_gate.  Every other period — it straddles blocks, or it was open when the call began — gets each block's part with atomicMax on
+// sortable ints: into its slot of the series (cleared to -inf and written by no other call) if it ends in this call, else into
+// run_new; k_gate_final turns those slots into floats, folds the maxima carried in and carries the open period out.  Which slots those
+// are follows from the call's geometry alone, and a maximum does not depend on which workgroup came first.
+template <bool LEN, bool LOG>
+__global__ __launch_bounds__ (256) void k_gate_frag (const gate_args_t<LEN, LOG> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[64 + GATE_FPB];
 	__shared__ int32_t sh_hist[2][MTR_HIST_LEN];
 	__shared__ int32_t sh_cnt[4];
+	float* ll = nullptr;                        // LOG, MAX: [2][GATE_FPB] lm / ls of the block
+	if constexpr (LOG) {
+		__shared__ float sh_ll[2 * GATE_FPB];
+		ll = sh_ll;
+	}
 	const uint32_t s = blockIdx.y;
 	const int tid = threadIdx.x;
 	const uint32_t lim = gate_lim<LEN> (a, s);
@@ -351,6 +403,16 @@ __global__ __launch_bounds__ (256) void k_gate_frag (const gate_args_t<LEN> a)
 		if (!isfinite (ls) || ls < -200.f) ls = -200.0f;
 		mxM = lm > mxM ? lm : mxM;
 		mxS = ls > mxS ? ls : mxS;
+		if constexpr (LOG) {
+			const mtr_loudlog_args& g = a.log;
+			if (g.mode == MTR_LOUDLOG_SAMPLE) {
+				const uint32_t q = g.phase + (uint32_t) f + 1;
+				if (q % g.period == 0 && q / g.period - 1 < g.room) {
+					g.M[(size_t) s * g.cap + g.point0 + (q / g.period - 1)] = lm;
+					g.S[(size_t) s * g.cap + g.point0 + (q / g.period - 1)] = ls;
+				}
+			} else { ll[i] = lm; ll[GATE_FPB + i] = ls; }
+		}
 		if (a.integr && f <= f_calc) {
 			if ((div1_0 + f + 1) % 2 == 0)  hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
 			if ((div2_0 + f + 1) % 10 == 0) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
@@ -365,6 +427,39 @@ __global__ __launch_bounds__ (256) void k_gate_frag (const gate_args_t<LEN> a)
 		atomicMax (&a.max_scratch[2 * s + 1], sortable (mxS));
 	}
 	__syncthreads ();
+	if constexpr (LOG) if (a.log.mode == MTR_LOUDLOG_MAX) {
+		const mtr_loudlog_args& g = a.log;
+		float* const Mrow = g.M + (size_t) s * g.cap + g.point0;
+		float* const Srow = g.S + (size_t) s * g.cap + g.point0;
+		for (int i = tid; i < nf; i += 256) {
+			const uint32_t fc = (uint32_t) (f0 + i) + 1;                     // fragments of the call up to and including this one
+			const uint32_t q = g.phase + fc;
+			const bool ends = q % g.period == 0;
+			if (!ends && i != nf - 1) continue;
+			const uint32_t in_period = ends ? g.period : q % g.period;
+			const int here = (int) min (in_period, (uint32_t) i + 1);        // fragments of the period in this block
+			float m = -INFINITY, v = -INFINITY;
+			for (int k = 0; k < here; ++k) {
+				m = ll[i - k] > m ? ll[i - k] : m;
+				v = ll[GATE_FPB + i - k] > v ? ll[GATE_FPB + i - k] : v;
+			}
+			if (ends && in_period <= (uint32_t) i + 1) {                     // the whole period, in this block and this call
+				if (q / g.period - 1 < g.room) { Mrow[q / g.period - 1] = m; Srow[q / g.period - 1] = v; }
+				continue;
+			}
+			// a part of it: the period ends with fragment fc + (period - in_period) of the call, if the stream has that many
+			const uint32_t j = (q + (g.period - in_period)) / g.period - 1;
+			if (fc + (g.period - in_period) <= n_frag) {
+				if (j < g.room) {
+					atomicMax (reinterpret_cast<int32_t*> (Mrow + j), sortable (m));
+					atomicMax (reinterpret_cast<int32_t*> (Srow + j), sortable (v));
+				}
+			} else {
+				atomicMax (&g.run_new[2 * s], sortable (m));
+				atomicMax (&g.run_new[2 * s + 1], sortable (v));
+			}
+		}
+	}
 	int32_t* const ghist = a.hist + (size_t) s * 2 * MTR_HIST_LEN;
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) {
 		const int32_t c = (&sh_hist[0][0])[i];
@@ -378,8 +473,8 @@ __global__ __launch_bounds__ (256) void k_gate_frag (const gate_args_t<LEN> a)
 	}
 }
 
-template <bool LEN>
-__global__ __launch_bounds__ (256) void k_gate_final (const gate_args_t<LEN> a)
+template <bool LEN, bool LOG>
+__global__ __launch_bounds__ (256) void k_gate_final (const gate_args_t<LEN, LOG> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[192];                 // powers of fragments n_frag - 192 .. n_frag - 1, chronological
@@ -439,6 +534,37 @@ __global__ __launch_bounds__ (256) void k_gate_final (const gate_args_t<LEN> a)
 		st->cnt_M = sh_cnt[0]; st->cnt_S = sh_cnt[1]; st->err_M = sh_cnt[2]; st->err_S = sh_cnt[3];
 		if (a.fold_tp) mtr_fold_truepeak (st);
 	}
+	if constexpr (LOG) if (tid == 64 && n > 0 && a.log.mode == MTR_LOUDLOG_MAX) {
+		// the slots k_gate_frag filled with atomicMax (see there) become floats; the period open when the call began takes the
+		// maxima carried in, the one it leaves open carries its own out
+		const mtr_loudlog_args& g = a.log;
+		float* const Mrow = g.M + (size_t) s * g.cap + g.point0;
+		float* const Srow = g.S + (size_t) s * g.cap + g.point0;
+		const float in_M = g.run[2 * s], in_S = g.run[2 * s + 1];
+		const uint32_t done = (g.phase + n_frag) / g.period;             // periods the stream completes in this call
+		uint32_t last_j = 0xFFFFFFFFu;
+		if (g.phase > 0 && done > 0) {
+			if (g.room > 0) {
+				const float m = unsortable (__float_as_int (Mrow[0])), v = unsortable (__float_as_int (Srow[0]));
+				Mrow[0] = in_M > m ? in_M : m; Srow[0] = in_S > v ? in_S : v;
+			}
+			last_j = 0;
+		}
+		for (uint32_t fb = GATE_FPB; fb < n_frag; fb += GATE_FPB) {
+			const uint32_t q = g.phase + fb;                             // fragments of the log in front of the block boundary
+			if (q % g.period == 0) continue;                             // a period ends there: none straddles it
+			const uint32_t j = q / g.period;
+			if (j >= done) break;                                        // the period the call leaves open
+			if (j == last_j) continue;                                   // (one period over several boundaries)
+			last_j = j;
+			if (j < g.room) { Mrow[j] = unsortable (__float_as_int (Mrow[j])); Srow[j] = unsortable (__float_as_int (Srow[j])); }
+		}
+		const float out_M = unsortable (g.run_new[2 * s]), out_S = unsortable (g.run_new[2 * s + 1]);
+		g.run[2 * s]     = done ? out_M : (in_M > out_M ? in_M : out_M);
+		g.run[2 * s + 1] = done ? out_S : (in_S > out_S ? in_S : out_S);
+		g.run_new[2 * s] = sortable (-INFINITY);
+		g.run_new[2 * s + 1] = sortable (-INFINITY);
+	}
 	__syncthreads ();
 	// only the bins the late inserts touched differ from the global histogram: write all back
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) ghist[i] = (&sh_hist[0][0])[i];
@@ -460,14 +586,18 @@ int mtr_launch_delay (uint32_t us, void* stream)
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-template <bool LEN>
-static int launch_gate (const gate_args_t<LEN>& a, void* stream)
+template <bool LEN, bool LOG>
+static int launch_gate (const mtr_gate_args& ga, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream)
 {
+	gate_args_t<LEN, LOG> a;
+	static_cast<mtr_gate_args&> (a) = ga;
+	if constexpr (LEN) a.frag_lim = frag_lim;
+	if constexpr (LOG) a.log = *log;
 	// many fragments per call and few streams: spread a stream over several workgroups
 	if (a.n_frag >= 4 * GATE_FPB && a.max_scratch) {
 		const uint32_t nb = (a.n_frag + GATE_FPB - 1) / GATE_FPB;
-		hipLaunchKernelGGL (k_gate_frag<LEN>, dim3 (nb, a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
-		hipLaunchKernelGGL (k_gate_final<LEN>, dim3 (a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
+		hipLaunchKernelGGL ((k_gate_frag<LEN, LOG>), dim3 (nb, a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
+		hipLaunchKernelGGL ((k_gate_final<LEN, LOG>), dim3 (a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
 		return hipGetLastError () == hipSuccess ? 0 : -1;
 	}
 	// A deferred gate (a.polite_grid) runs beside the next call's fused kernel, whose one-wave workgroups own a SIMD each for
@@ -475,17 +605,14 @@ static int launch_gate (const gate_args_t<LEN>& a, void* stream)
 	// those (344 VGPRs of 512, 35 KB of 160), so the gate is launched as that many workgroups, each walking its share of the
 	// streams, and cannot stand in the way of k_seg's placement whenever the two are dispatched together.
 	const uint32_t grid = a.polite_grid ? (a.n_streams < a.polite_grid ? a.n_streams : a.polite_grid) : a.n_streams;
-	hipLaunchKernelGGL (k_gate<LEN>, dim3 (grid), dim3 (256), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL ((k_gate<LEN, LOG>), dim3 (grid), dim3 (256), 0, (hipStream_t) stream, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-int mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream)
+int mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream)
 {
-	if (!frag_lim) return launch_gate<false> (a, stream);
-	mtr_gate_len_args la;
-	static_cast<mtr_gate_args&> (la) = a;
-	la.frag_lim = frag_lim;
-	return launch_gate<true> (la, stream);
+	if (log) return frag_lim ? launch_gate<true, true> (a, frag_lim, log, stream) : launch_gate<false, true> (a, nullptr, log, stream);
+	return frag_lim ? launch_gate<true, false> (a, frag_lim, nullptr, stream) : launch_gate<false, false> (a, nullptr, nullptr, stream);
 }
 
 // ---- state initialisation --------------------------------------------------------------------

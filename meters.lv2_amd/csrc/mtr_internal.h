@@ -141,6 +141,22 @@ struct mtr_gate_len_args : mtr_gate_args {
 #define MTR_GATE_CLOSING   0x80000000u
 #define MTR_GATE_UNTOUCHED 0xFFFFFFFFu
 
+/* The loudness log (mtr_engine_loudlog_set_period; host side: mtr_loudlog.hip) as a gate sees it — a struct of its own again, behind the
+ * gate's arguments in the LOG instantiations only.  Where the streams of the call stand is computed by the host at queue time (a
+ * deferred gate runs beside the next call): fragment f of the call is fragment phase + f of the period that was open when the call
+ * began, point j = (phase + f + 1) / period - 1 of the call is completed by the fragment with (phase + f + 1) % period == 0 and lands
+ * in row [s][point0 + j] if j < room. */
+typedef struct mtr_loudlog_args {
+	float*          M;            /* [S][cap] series of the view's streams */
+	float*          S;
+	float*          run;          /* [S][2] MTR_LOUDLOG_MAX: max M / S of the period open between two calls (-inf: no fragment yet) */
+	int32_t*        run_new;      /* [S][2] ... and, as sortable ints, of the period the multi-workgroup path leaves open (-inf between calls) */
+	uint32_t        period, phase;
+	uint32_t        cap, point0, room;   /* row pitch; points every open stream completed before the call (clamped to cap); cap - point0 */
+	int32_t         mode;         /* MTR_LOUDLOG_SAMPLE / _MAX */
+} mtr_loudlog_args;
+#define MTR_LOUDLOG_EMPTY 0x807fffff   /* -inf as a sortable int (mtr_gate.hip): what the series and run_new are cleared to */
+
 /* per-stream state of BITSTATS: shared by mtr_bitstats.hip (the kernel) and mtr_intstat.hip (the meter's host side) */
 typedef struct mtr_bitstats_state {
 	int32_t hist[MTR_BIM_LAST];      /* src/uris.h:53-60 layout */
@@ -201,7 +217,8 @@ int  mtr_launch_kwmc51 (bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_
 int  mtr_launch_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
                               uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
                               const uint32_t* ends, void* stream);
-int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, void* stream);
+/* log != NULL: the instantiations that append the call's points to the loudness log; NULL: the kernels as they are without it */
+int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
 int  mtr_launch_tpb (const mtr_tpb_args& a, void* stream);

@@ -17,6 +17,7 @@ METER_STCORR = 0x200                       # (0x100 is no meter)
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
 PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3        # MTR_PCM_*: little-endian int16 / packed 3-byte / int32 samples
+LOUDLOG_SAMPLE, LOUDLOG_MAX = 0, 1         # MTR_LOUDLOG_*: a point is the period's last (M, S) / the maxima over the period
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MTR_LIB: an alternative build of the same library (instrumented kernels, tools/f4_prof.py); never a different backend
@@ -149,6 +150,11 @@ def _load():
         L.mtr_engine_stcorr_read.argtypes = [vp, u32, u32, vp, vp]
         L.mtr_engine_stcorr_series.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_stcorr_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
+        L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
+        L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
+        L.mtr_engine_loudlog_series.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp]
+        L.mtr_engine_loudlog_reset.argtypes = [vp]
     L.mtr_engine_prune_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_refine_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_layout.argtypes = [vp]
@@ -669,6 +675,39 @@ class Engine:
 
     def stcorr_reset(self):
         _check(lib.mtr_engine_stcorr_reset(self._h), "stcorr_reset")
+
+    def _need_loudlog(self):
+        if not hasattr(lib, "mtr_engine_loudlog_series"):
+            raise EngineError(f"{lib_path} has no loudness log: rebuild it")
+
+    def loudlog_set_period(self, period_fragments, capacity_points, mode=LOUDLOG_SAMPLE):
+        """The loudness log of an EBU engine: a (M, S) point per stream every `period_fragments` 50 ms fragments, wherever the calls cut
+        the audio, `capacity_points` of them kept per stream; 0 turns it off.  Only before the first process call since create / reset."""
+        self._need_loudlog()
+        _check(lib.mtr_engine_loudlog_set_period(self._h, int(period_fragments), int(capacity_points), int(mode)), "loudlog_set_period")
+
+    def loudlog_period(self):
+        """(period_fragments, capacity_points, mode) as set; period 0: the log is off."""
+        self._need_loudlog()
+        p, c, m = C.c_uint32(), C.c_uint32(), C.c_int()
+        _check(lib.mtr_engine_loudlog_period(self._h, C.byref(p), C.byref(c), C.byref(m)), "loudlog_period")
+        return p.value, c.value, m.value
+
+    def loudlog_series(self, first=0, count=None):
+        """(M [count, cap] float32, S, n_points [count] uint32, dropped): the points each stream holds, rows filled with NaN past the
+        stream's own min(n_points, cap)."""
+        self._need_loudlog()
+        count = self.n_streams - first if count is None else count
+        cap = self.loudlog_period()[1]
+        M = np.full((count, cap), np.nan, np.float32)
+        S = np.full((count, cap), np.nan, np.float32)
+        n, d = np.zeros(count, np.uint32), np.zeros(count, np.uint32)
+        _check(lib.mtr_engine_loudlog_series(self._h, first, count, M.ctypes.data, S.ctypes.data, cap, n.ctypes.data, d.ctypes.data), "loudlog_series")
+        return M, S, n, d
+
+    def loudlog_reset(self):
+        self._need_loudlog()
+        _check(lib.mtr_engine_loudlog_reset(self._h), "loudlog_reset")
 
     def dr14_reset(self):
         _check(lib.mtr_engine_dr14_reset(self._h), "dr14_reset")
