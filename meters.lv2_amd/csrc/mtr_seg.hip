@@ -43,7 +43,7 @@
 
 // -DMTR_SEG_PROF: shader cycles per part of a step, summed over one wave's main loop (tools/seg_prof.py)
 #ifdef MTR_SEG_PROF
-__device__ unsigned long long g_seg_prof[8];
+__device__ unsigned long long g_seg_prof[10];
 #define SPROF_NOW(v) unsigned long long v; asm volatile ("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
 #define SPROF_ADD(i, d) sprof_[i] += (d)
 #else
@@ -549,7 +549,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	// one step: the scalar / packed work of step j on buffer U (ring slot U), and — PROD — the products of step j - 1,
 	// interleaved by hand (the source order is the schedule: see the chunks below)
 #ifdef MTR_SEG_PROF
-	unsigned long long sprof_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	unsigned long long sprof_[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 #endif
 	// KW: the recurrence rides in this step's schedule (EBU; not in the step of an unaligned tile's end)
 	auto step = [&]<int U, bool PROD, bool KW> () __attribute__ ((always_inline)) {
@@ -581,8 +581,16 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		lp += (j + 3 < (ALIGNED ? n_steps : n_loads)) ? R / 2 : 0;
 #endif
 		load.template operator()<(U + 3) & 3> ();
+		SPROF_NOW (h1_); SPROF_ADD (8, h1_ - c0_);
 		// SCREEN: eps of the products of step j - 1 for every accumulator lane.  The owner of column 16 b + c (lane 16 b + c)
 		// computes it in the column's current scale; lane (c, kg) needs the four columns c of blocks 0..3: through LDS.
+		// The exchange relies on the hardware's DS ordering within a wave, not on the language's memory model: a wave's DS
+		// instructions execute in issue order, and the block is this one wave, so the reads see the writes in front of them and
+		// the next step's writes come behind these reads — as the ring stores and the operand fetch behind them have always
+		// relied on.  All the compiler is told is not to move or forward across the two points (a fence there drained the LDS
+		// queue twice a step, lgkmcnt (0), with no other wave to run under it); the bounds are first read by chunk 0's vote,
+		// behind chunk 1's MFMAs.  flush_pm and rescale keep their fences: they run once per rescale and once at the end of a
+		// launch, their values are consumed at once, so a drain there costs nothing that could be hidden.
 		float eps[4][2], ref[4][2];
 		if constexpr (SCREEN) {
 			rml = fmaxf (rml, ml); rmr = fmaxf (rmr, mr);                // (step j's own samples too: a bound on more is still a bound)
@@ -599,17 +607,16 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 				float* const Q = reinterpret_cast<float*> (smem_ + XREF);
 				*reinterpret_cast<float2*> (Q + (cc * 4 + kg) * 2) =
 					float2{__uint_as_float (refl) * (scl.sc * 32768.f), __uint_as_float (refr) * (scr.sc * 32768.f)};
-				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
-				__builtin_amdgcn_wave_barrier ();
-				__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "workgroup");
+				asm volatile ("" ::: "memory");
 				const float4 e0 = *reinterpret_cast<const float4*> (E + cc * 8), e1 = *reinterpret_cast<const float4*> (E + cc * 8 + 4);
 				eps[0][0] = e0.x; eps[0][1] = e0.y; eps[1][0] = e0.z; eps[1][1] = e0.w;
 				eps[2][0] = e1.x; eps[2][1] = e1.y; eps[3][0] = e1.z; eps[3][1] = e1.w;
 				const float4 r0 = *reinterpret_cast<const float4*> (Q + cc * 8), r1 = *reinterpret_cast<const float4*> (Q + cc * 8 + 4);
 				ref[0][0] = r0.x; ref[0][1] = r0.y; ref[1][0] = r0.z; ref[1][1] = r0.w;
 				ref[2][0] = r1.x; ref[2][1] = r1.y; ref[3][0] = r1.z; ref[3][1] = r1.w;
-				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
-				__builtin_amdgcn_wave_barrier ();
+				SPROF_NOW (h2_);
+				asm volatile ("" ::: "memory");
+				SPROF_NOW (h3_); SPROF_ADD (9, h3_ - h2_);
 			}
 		}
 		SPROF_NOW (c1_); SPROF_ADD (0, c1_ - c0_);
@@ -856,7 +863,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	}
 	flush_pm ();
 #ifdef MTR_SEG_PROF
-	if (blockIdx.x == gridDim.x / 2 && lane == 0) for (int i = 0; i < 8; ++i) g_seg_prof[i] = sprof_[i];
+	if (blockIdx.x == gridDim.x / 2 && lane == 0) for (int i = 0; i < 10; ++i) g_seg_prof[i] = sprof_[i];
 #endif
 
 	if (SCREEN && lane == 0 && a.seg_stats) { atomicAdd (&a.seg_stats[0], n_scr); atomicAdd (&a.seg_stats[1], n_fin); }
@@ -880,7 +887,7 @@ size_t mtr_seg_lds_bytes (void) { return LDS_BYTES; }
 #ifdef MTR_SEG_PROF
 extern "C" int mtr_debug_seg_prof (unsigned long long* out)
 {
-	return hipMemcpyFromSymbol (out, HIP_SYMBOL (g_seg_prof), 8 * sizeof (unsigned long long)) == hipSuccess ? 0 : -1;
+	return hipMemcpyFromSymbol (out, HIP_SYMBOL (g_seg_prof), 10 * sizeof (unsigned long long)) == hipSuccess ? 0 : -1;
 }
 #endif
 
