@@ -48,7 +48,8 @@ extern "C" {
 /* ---- meters (bit mask) --------------------------------------------------- */
 #define MTR_METER_EBU        0x01u  /* Ebu_r128_proc: K-weighting + gated loudness  (ebumeter/ebu_r128_proc.cc) */
 #define MTR_METER_TRUEPEAK   0x02u  /* TruePeakdsp::process_max: 4x true peak       (jmeters/truepeakdsp.cc:101-124) */
-#define MTR_METER_SPECTR30   0x04u  /* 30-band 1/3-octave bank                      (src/spectr.c, src/spectrumlv2.c) */
+#define MTR_METER_SPECTR30   0x04u  /* 30-band 1/3-octave bank                      (src/spectr.c, src/spectrumlv2.c); below 35 650 Hz
+                                    * the top bands do not exist and are silent: see mtr_band_coef */
 #define MTR_METER_TPBALLIST  0x08u  /* TruePeakdsp::process: PPM-style ballistics   (jmeters/truepeakdsp.cc:41-99) */
 #define MTR_METER_BITSTATS   0x10u  /* float_stats                                   (src/bitmeter.c:63-105) */
 #define MTR_METER_SIGDIST    0x20u  /* signal distribution histogram                (src/sigdistlv2.c:303-318) */
@@ -139,7 +140,10 @@ int  mtr_engine_integr_pause (mtr_engine* e);
 int  mtr_engine_integr_reset (mtr_engine* e);
 /* replaces: TruePeakdsp::reset on every stream (src/meters.cc:451-456) */
 int  mtr_engine_truepeak_reset (mtr_engine* e);
-/* replaces: the speed-port handler (src/spectrumlv2.c:170-177) and the peak-hold reset (:191-205) */
+/* replaces: the speed-port handler (src/spectrumlv2.c:170-177) and the peak-hold reset (:191-205).  The speed (clamped to
+ * [0.01, 15], 1 after create) is a CONTROL, not state: mtr_engine_reset zeroes the bank's filter states, levels, peak holds and
+ * dither parity and leaves the speed as it was set.  (It travels in the state blob all the same: mtr_engine_state_export.)  The
+ * plugin's rule that a speed change also resets the peak hold is the plugin's (lv2_plugin.c); set_speed alone moves no level. */
 int  mtr_engine_spectr_set_speed (mtr_engine* e, float v);
 int  mtr_engine_spectr_reset_peak (mtr_engine* e);
 
@@ -468,7 +472,16 @@ int  mtr_plan_query (const mtr_config* cfg, uint32_t frames_left_in_fragment, ui
 int  mtr_kweight_coef (float sample_rate, float* out7);
 /* the 120-float polyphase table (Resampler_table ctor, fr = 1, hl = 24, np = 4) */
 int  mtr_fir_table (float* out120);
-/* 36 doubles [section][a0 a1 a2 b0 b1 b2] of band `band` at `rate` (bandpass_setup, src/spectr.c:89-206) */
+/* 36 doubles [section][a0 a1 a2 b0 b1 b2] of band `band` at `rate` (bandpass_setup, src/spectr.c:89-206).
+ * A band whose lower edge f_m - bw / 2 = 0.88422 f_m lies at or above rate / 2 does not exist at that rate: the reference stops
+ * there (assert (wu > wl), spectr.c:134; without the assert it computes NaN or finite garbage coefficients and shows levels the
+ * signal does not have).  Here such a band is SILENT: section 0's numerator is 0 and no section has poles (a1 = a2 = 0) — these
+ * are the coefficients returned, with MTR_OK — so on any input, NaN / Inf included, mtr_engine_spectrum gives val_db = max_db =
+ * -100.0 exactly and finite val / max that hold nothing but the epilogue's 1e-20 per call, as for silence (each call adds it,
+ * the level's own decay takes it away: < 1e-18 up to a hundred calls, always far below the -100 dB floor of 5e-11), and on finite input nothing non-finite is
+ * ever in flight, in its states or in a state blob.  The first rate at which all 30 bands exist is 35 650 Hz (band
+ * 29: 0.88422 x 20 158.7 Hz x 2); at 32 kHz band 29 is silent, at 22.05 kHz 27 - 29, at 16 kHz 26 - 29, at 11.025 kHz 24 - 29, at
+ * 8 kHz 23 - 29. */
 int  mtr_band_coef (double rate, uint32_t band, double* out36);
 
 /* Fill device memory with the repo's seeded synthetic programme signal:

@@ -104,12 +104,23 @@ void mtr_setup_band (double rate, uint32_t band, double* out)
 	if (hi > M_PI - 1e-9) hi = M_PI - 1e-9;
 	if (lo < 1e-9) lo = 1e-9;
 	hi *= .5; lo *= .5;
+	double (*W)[6] = (double (*)[6]) out;
+
+	/* A band whose lower edge lies at or above Nyquist does not exist at this rate: the reference stops here (assert (wu > wl),
+	 * spectr.c:134); computing on gives NaN or finite garbage coefficients, a band that reports a level nothing in the signal
+	 * has.  Such a band is silent: section 0's gain is 0 and no section has poles, so its levels stay what silence gives. */
+	if (!(hi > lo)) {
+		for (int i = 0; i < order; ++i) {
+			W[i][0] = 1.; W[i][1] = 0.; W[i][2] = 0.;
+			W[i][3] = i ? 1. : 0.; W[i][4] = i ? ((i & 1) ? -2. : 2.) : 0.; W[i][5] = i ? 1. : 0.;
+		}
+		return;
+	}
 
 	const double ca  = cos (hi + lo) / cos (hi - lo);
 	const double cb  = 1. / tan (hi - lo);
 	const double w0  = 2. * atan (sqrt (tan (hi) * tan (lo)));
 	const double ca2 = ca * ca, cb2 = cb * cb, ab2 = 2. * ca * cb;
-	double (*W)[6] = (double (*)[6]) out;
 
 	for (int i = 0; i < order / 2; ++i) {
 		const double th = M_PI_2 + (2 * i + 1) * M_PI / (2. * (double) order);

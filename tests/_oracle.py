@@ -116,6 +116,54 @@ class MoBand(C.Structure):
     _fields_ = [("f", MoBiquad * 6), ("stages", C.c_uint32), ("ac", C.c_int)]
 
 
+class MoSpectr(C.Structure):
+    """mo_spectr of oracle/mtr_oracle.h: one spectr30 plugin instance (src/spectrumlv2.c:46-66)."""
+    _fields_ = [("nchannels", C.c_uint32), ("rate", C.c_double), ("omega", C.c_float),
+                ("val_f", C.c_float * NBANDS), ("max_f", C.c_float * NBANDS), ("flt", MoBand * NBANDS),
+                ("spec_db", C.c_float * NBANDS), ("max_db", C.c_float * NBANDS)]
+
+
+class SpectrStream:
+    """One spectr30 instance fed call by call, with its two controls: run() is one spectrum_run, so one engine process call (the
+    epilogue's scrub and its + 1e-20f happen once per run)."""
+
+    def __init__(self, lib, fs, nchannels=2):
+        self.lib, self.s, self.nchannels = lib, MoSpectr(), nchannels
+        lib.mo_spectr_init.argtypes = [C.POINTER(MoSpectr), C.c_uint32, C.c_double]
+        lib.mo_spectr_set_speed.argtypes = [C.POINTER(MoSpectr), C.c_float]
+        lib.mo_spectr_run.argtypes = [C.POINTER(MoSpectr), _f32p, _f32p, C.c_uint32]
+        lib.mo_spectr_reset_peak.argtypes = [C.POINTER(MoSpectr)]
+        for f in ("mo_spectr_init", "mo_spectr_set_speed", "mo_spectr_run", "mo_spectr_reset_peak"):
+            getattr(lib, f).restype = None
+        lib.mo_spectr_init(C.byref(self.s), nchannels, float(fs))
+
+    @property
+    def omega(self):
+        return np.float32(self.s.omega)
+
+    def set_speed(self, v):
+        self.lib.mo_spectr_set_speed(C.byref(self.s), v)
+
+    def reset_peak(self):
+        self.lib.mo_spectr_reset_peak(C.byref(self.s))
+
+    def read(self):
+        """dict(val, max, val_db, max_db) as the last run() (or a reset_peak() after it) left them.  The dB ports are run()'s."""
+        s = self.s
+        return dict(val=np.array(s.val_f[:], np.float32), max=np.array(s.max_f[:], np.float32),
+                    val_db=np.array(s.spec_db[:], np.float32), max_db=np.array(s.max_db[:], np.float32))
+
+    def run(self, x):
+        """x: float32 [n, 2] (stereo) or [n] (mono; a stereo instance takes it as L = R).  -> read() after the call."""
+        x = np.asarray(x, np.float32)
+        if x.ndim == 2 and self.nchannels == 1:
+            raise ValueError("a mono instance takes [n]")
+        left = np.ascontiguousarray(x[:, 0] if x.ndim == 2 else x)
+        right = np.ascontiguousarray(x[:, 1]) if x.ndim == 2 else left
+        self.lib.mo_spectr_run(C.byref(self.s), left, right, left.size)
+        return self.read()
+
+
 class MoBitstats(C.Structure):
     _fields_ = [("hist", C.c_int32 * BIM_LAST), ("n_zero", C.c_int32), ("n_pos", C.c_int32),
                 ("n_nan", C.c_int32), ("n_inf", C.c_int32), ("n_den", C.c_int32),
@@ -206,6 +254,9 @@ class Oracle(_Batch):
 
     def tp_stream(self, fs=48000.0):
         return TpStream(self.lib, fs)
+
+    def spectr_stream(self, fs=48000.0, nchannels=2):
+        return SpectrStream(self.lib, fs, nchannels)
 
     def __init__(self):
         lib = C.CDLL(build_oracle())

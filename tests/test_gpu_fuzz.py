@@ -124,6 +124,9 @@ def test_fuzzed_filter_bank(M, oracle, seed):  # noqa: F811
         assert np.allclose(r["val"][s], o["val"], rtol=1e-4, atol=1e-30), (seed, s, fs, mono, calls)
         live = o["val_db"] > -90
         assert np.allclose(r["val_db"][s][live], o["val_db"][live], atol=1e-3), (seed, s)
+        assert np.allclose(r["max"][s], o["max"], rtol=1e-4, atol=1e-30), (seed, s, fs, mono, calls)
+        live = o["max_db"] > -90
+        assert np.allclose(r["max_db"][s][live], o["max_db"][live], atol=1e-3), (seed, s)
 
 
 @pytest.mark.parametrize("seed", range(12))

@@ -292,16 +292,20 @@ def test_filter_bank_batch_and_rates(M, oracle):
         with M.Engine(S, fs, M.METER_SPECTR30) as e:
             e.process(x)
             r = e.spectrum()
-        for s in (0, 7, 18):
+        for s in range(S):
             o = oracle.spectr(x[s], fs, T)
             assert np.allclose(r["val"][s], o["val"], rtol=1e-4), (fs, s)
             assert np.allclose(r["val_db"][s], o["val_db"], atol=1e-3)
+            assert np.allclose(r["max"][s], o["max"], rtol=1e-4), (fs, s)
+            assert np.allclose(r["max_db"][s], o["max_db"], atol=1e-3)
     # mono variant (spectr30mono): input is the single channel itself
     with M.Engine(2, 48000.0, M.METER_SPECTR30, n_channels=1) as e:
         e.process(np.ascontiguousarray(x[:2, :, 0]))
         r = e.spectrum()
     stereo_same = np.repeat(x[0, :, :1], 2, axis=1)
-    assert np.allclose(r["val"][0], oracle.spectr(stereo_same, 48000.0, T)["val"], rtol=1e-4)
+    o = oracle.spectr(stereo_same, 48000.0, T)
+    assert np.allclose(r["val"][0], o["val"], rtol=1e-4)
+    assert np.allclose(r["max"][0], o["max"], rtol=1e-4) and np.allclose(r["max_db"][0], o["max_db"], atol=1e-3)
 
 
 def test_all_meters_together(M, oracle):

@@ -185,6 +185,51 @@ def test_spectr30_stereo(host, oracle):
     inst.cleanup()
 
 
+@pytest.mark.gpu
+def test_spectr30_speed_change_and_peak_reset(host, oracle):
+    """A change of the speed port resets the peak hold (src/spectrumlv2.c:170-205: it clears the reset latch): that run's peak
+    ports carry the <= -500 markers, and from then on levels and peaks are those of an instance given set_speed + reset_peak at
+    that block; a reset through the reset port likewise.  Behind each reset the block's one-wait path must hand back the hold as
+    it is after the memset, not a snapshot from before it."""
+    nblk, at_speed, at_reset = 20, 8, 14
+    x = sig.lcg_noise(nblk * 1024, 4711, 0.5)
+    inst = Instance(host, "spectr30stereo")
+    assert inst.ok()
+    spec = [_f() for _ in range(30)]
+    mx = [_f() for _ in range(30)]
+    spd, rst, amp, st = _f(1.0), _f(-4.0), _f(0.0), _f(0.0)
+    for i in range(30):
+        inst.connect(i, spec[i]); inst.connect(30 + i, mx[i])
+    for port, arr in ((60, spd), (61, rst), (62, amp), (63, st)):
+        inst.connect(port, arr)
+    h, unreset = oracle.spectr_stream(48000.0), oracle.spectr_stream(48000.0)
+    seen = 0
+    for b in range(nblk):
+        if b == at_speed:
+            spd[0] = 15.0
+            h.set_speed(15.0); h.reset_peak()
+            unreset.set_speed(15.0)
+        if b == at_reset:
+            rst[0] = 1.0
+            h.reset_peak()
+        bl, br = x[b * 1024:(b + 1) * 1024, 0].copy(), x[b * 1024:(b + 1) * 1024, 1].copy()
+        for port, arr in ((64, bl), (65, bl), (66, br), (67, br)):
+            inst.connect(port, arr)
+        inst.run(1024)
+        want, other = h.run(x[b * 1024:(b + 1) * 1024]), unreset.run(x[b * 1024:(b + 1) * 1024])
+        got = np.array([s[0] for s in spec]), np.array([m[0] for m in mx])
+        live = want["val_db"] > -90
+        assert live.sum() >= (30 if b >= 4 else 20) and np.allclose(got[0][live], want["val_db"][live], atol=1e-3), b
+        if b in (at_speed, at_reset):
+            assert (got[1] <= -500).all(), b
+        else:
+            live = want["max_db"] > -90
+            assert np.allclose(got[1][live], want["max_db"][live], atol=1e-3), (b, got[1], want["max_db"])
+            seen += int((np.abs(want["max_db"] - other["max_db"]) > 0.01).sum())
+    assert seen >= 30                                           # (an instance whose hold was never reset reads otherwise: the comparison saw the resets)
+    inst.cleanup()
+
+
 # The EBUr128 plugin has its own file: tests/test_lv2_ebur128.py (the whole UI protocol, message by message).
 
 
