@@ -29,7 +29,8 @@ extern "C" {
  *    _process_host_lengths, _stream_frames; mtr_engine_process_host_pcm, _process_device_pcm, _pcm_stats, mtr_pcm_sample_bytes,
  *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host; MTR_METER_STCORR, mtr_stcorr_coef,
  *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset; mtr_engine_loudlog_set_period, _loudlog_period,
- *    _loudlog_series, _loudlog_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _loudlog_series, _loudlog_reset; MTR_METER_NEEDLE, mtr_needle_coef, mtr_engine_needle_configure, _needle_set_gain, _needle_read,
+ *    _needle_series, _needle_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -56,6 +57,8 @@ extern "C" {
 #define MTR_METER_DR14       0x40u  /* DR-14 dynamic range (dr_operation_mode)      (src/dr14.c:283-352, 394-412) */
 #define MTR_METER_KMETER     0x80u  /* Kmeterdsp: RMS + peak with hold / fall-back  (jmeters/kmeterdsp.cc:56-140) */
 #define MTR_METER_STCORR     0x200u /* Stcorrdsp: stereo phase correlation          (jmeters/stcorrdsp.cc:47-93); 0x100 is no meter */
+#define MTR_METER_NEEDLE     0x800u /* Vumeterdsp / Iec1ppmdsp / Iec2ppmdsp / Msppmdsp (jmeters/), see mtr_needle.h; 0x400 is no meter
+                                    * either (tests/test_stcorr_cpu.py holds both refused) */
 
 #define MTR_HIST_LEN   751          /* src/uris.h:45  HIST_LEN */
 #define MTR_NBANDS     30           /* src/spectrumlv2.c:33  FILTER_COUNT */
@@ -70,7 +73,7 @@ typedef struct {
 	uint32_t meters;         /* MTR_METER_* mask */
 	uint32_t n_streams;      /* independent streams in the batch (>= 1) */
 	uint32_t n_channels;     /* 2 (interleaved stereo frames), 1 (mono: SPECTR30 / TPBALLIST / BITSTATS / SIGDIST / DR14 /
-	                          * KMETER; not EBU / TRUEPEAK / STCORR: MTR_ERR_UNSUPPORTED) or 3 .. 5 (EBU / TRUEPEAK only: MTR_ERR_UNSUPPORTED
+	                          * KMETER / NEEDLE; not EBU / TRUEPEAK / STCORR: MTR_ERR_UNSUPPORTED) or 3 .. 5 (EBU / TRUEPEAK only: MTR_ERR_UNSUPPORTED
 	                          * with any other meter).  Multichannel loudness (Ebu_r128_proc::init (nchan, fsamp),
 	                          * ebumeter/ebu_r128_proc.h:26, 104): frames interleaved in the BS.1770 order L R C Ls Rs (5.0; a
 	                          * 5.1 programme: mtr_engine_set_frame_layout), channel i weighted by _chan_gain = {1, 1, 1, 1.41, 1.41}
@@ -347,6 +350,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The loudness log of an MTR_METER_EBU engine — momentary / short-term loudness over time, a (M, S) point per period of P fragments
  * and stream: mtr_engine_loudlog_set_period / _period / _series / _reset */
 #include "mtr_loudlog.h"
+
+/* The needle meters for a batch (MTR_METER_NEEDLE) — VU, IEC I / II PPM and M/S PPM, with a reading series: mtr_needle_coef and
+ * mtr_engine_needle_configure / _set_gain / _read / _series / _reset */
+#include "mtr_needle.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

@@ -114,6 +114,7 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 		{ MTR_METER_BITSTATS | MTR_METER_SIGDIST, 0x7fffffffull, "BITSTATS / SIGDIST: n_frames per call must be < 2^31 - 1" },
 		{ MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
+		{ MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_TPBALLIST, 0x7ffff000ull, "TPBALLIST: n_frames per call must be < 2^31 - 4096" },
 		{ MTR_METER_EBU | MTR_METER_TRUEPEAK, 0xFFFFFFFFull, "n_frames per call must be < 2^32 - 1" },
 	};
@@ -471,6 +472,7 @@ struct CallRun {
 		if ((meters & MTR_METER_DR14) && (rc = dr14_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_KMETER) && (rc = kmeter_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_STCORR) && (rc = stcorr_step (e, c, nx))) return rc;
+		if ((meters & MTR_METER_NEEDLE) && (rc = needle_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, or the fused kernels)

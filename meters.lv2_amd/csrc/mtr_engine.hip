@@ -221,7 +221,7 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	if (cfg->n_streams == 0 || !(cfg->sample_rate >= 8000.f) || cfg->meters == 0) return fail (MTR_ERR_ARG, "mtr_engine_create: n_streams / sample_rate / meters");
 	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_CHANNELS) return fail (MTR_ERR_ARG, "n_channels must be 1 .. 5");
 	if (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_SPECTR30 | MTR_METER_TPBALLIST | MTR_METER_BITSTATS
-	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_STCORR))
+	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_STCORR | MTR_METER_NEEDLE))
 		return fail (MTR_ERR_ARG, "unknown bits in the meters mask");
 	if (cfg->n_channels == 1 && (cfg->meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
 		return fail (MTR_ERR_UNSUPPORTED, "EBU / TRUEPEAK take 2 .. 5 channels, not mono");
@@ -289,6 +289,7 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 		else if (hipMemcpy (e->gate_max.p, m.data (), m.size () * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail (MTR_ERR_HIP, "hipMemcpy gate scratch");
 	}
 	if (rc == MTR_OK) rc = bank_create (e);
+	if (rc == MTR_OK && (cfg->meters & MTR_METER_NEEDLE)) rc = needle_create (e);
 	if (rc != MTR_OK) { mtr_engine_destroy (e); return rc; }
 	rc = mtr_engine_reset (e);
 	if (rc != MTR_OK) { mtr_engine_destroy (e); return rc; }     // never an error code together with a live handle
@@ -335,6 +336,7 @@ int mtr_engine_reset (mtr_engine* e)
 	if (e->cfg.meters & MTR_METER_DR14) { const int drc = mtr_engine_dr14_reset (e); if (drc) return drc; }
 	if (e->cfg.meters & MTR_METER_KMETER) { const int krc = mtr_engine_kmeter_reset (e); if (krc) return krc; e->pos.km_fpp = 0; e->pos.km_fall = 0.f; }
 	if (e->cfg.meters & MTR_METER_STCORR) { const int src = mtr_engine_stcorr_reset (e); if (src) return src; }
+	if (e->cfg.meters & MTR_METER_NEEDLE) { const int nrc = mtr_engine_needle_reset (e); if (nrc) return nrc; }
 	if (e->ll.period) { const int lrc = loudlog_reset (e, st); if (lrc) return lrc; }
 	if (e->cfg.meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) return mtr_engine_intstat_reset (e);
 	return MTR_OK;

@@ -1,6 +1,6 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
 // EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
-// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip), and mtr_loudlog.hip (the host
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip), and mtr_loudlog.hip (the host
 // side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
 #ifndef MTR_ENGINE_IMPL_H
@@ -102,6 +102,8 @@ struct Cursors {
 	float    km_fall = 0.f;
 	uint64_t sc_fill = 0;         // STCORR: frames in the open period of the reading series ...
 	uint64_t sc_points = 0;       // ... and periods completed since reset
+	uint32_t nd_fill = 0;         // NEEDLE: frames in the open period of the reading series ...
+	uint64_t nd_points = 0;       // ... and periods completed since reset (what the series does not hold of them is dropped)
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 };
@@ -111,6 +113,7 @@ struct mtr_sigdist_state;
 struct mtr_dr14_state;
 struct mtr_kmeter_state;
 struct mtr_stcorr_state;
+struct mtr_needle_hdr;
 
 // The engine: core, tail, plan rings, host path, then one member per side meter
 struct mtr_engine {
@@ -250,6 +253,14 @@ struct mtr_engine {
 		float                      w[2];        // w1, w2 of Stcorrdsp::init
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
 	} sc;
+	struct Needle {                             // NEEDLE (mtr_needle.hip)
+		DevBuf<unsigned char>      state;       // [S] of { mtr_needle_hdr, mtr_needle_state [kinds][C] }
+		DevBuf<float>              series;      // [kinds][S][cap][C]
+		uint32_t                   kinds = 0, period = 0, cap = 0;   // MTR_NEEDLE_* selected, frames per process () of the series (0: the call), points per stream and kind
+		uint32_t                   kind[4] = { 0, 0, 0, 0 };         // the selected kinds in the order of their bits ...
+		float                      w[4][4];     // ... and their w1 w2 w3 g
+		float                      db[2], mv[2];   // Msppmdsp's gains, M and S: a control (it survives a reset)
+	} nd;
 	struct LoudLog {                            // the loudness log of an EBU engine (mtr_loudlog.hip; the gate appends: mtr_gate.hip)
 		DevBuf<float>              M, S;        // [S][cap]
 		DevBuf<float>              run;         // [S][2] MAX: maxima of the period open between two calls
@@ -313,6 +324,9 @@ void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v);
 void stcorr_create (mtr_engine* e);
 int  stcorr_step (mtr_engine* e, const Call& c, Cursors& nx);
 void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v);
+int  needle_create (mtr_engine* e);
+int  needle_step (mtr_engine* e, const Call& c, Cursors& nx);
+void needle_sections (const mtr_engine* e, std::vector<StateSection>& v);
 // STCORR's section of a blob carries the period and the frames into the open one in every stream's entry (the header has no room for
 // them).  Export writes the host's copies into the `count` entries at `sec`; import checks the entries (MTR_ERR_STATE with the text set if
 // they are corrupt or — `fresh` false — not where the engine stands) and returns the two.
@@ -322,6 +336,12 @@ bool loudlog_args (const mtr_engine* e, const Cursors& pos, uint32_t off, mtr_lo
 int  loudlog_reset (mtr_engine* e, hipStream_t st);
 void stcorr_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
 int  stcorr_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* period, uint32_t* fill);
+// NEEDLE's section likewise: kinds, period, the frames into the open period and the two gains in front of every stream's detectors.  A blob
+// whose kinds or period are not the engine's is refused (MTR_ERR_STATE); a fresh engine takes the rest (needle_take_cursors)
+void needle_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
+int  needle_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, mtr_needle_hdr* out);
+void needle_take_cursors (mtr_engine* e, const mtr_needle_hdr* h);
+size_t needle_hdr_bytes (void);
 
 #pragma GCC visibility pop
 

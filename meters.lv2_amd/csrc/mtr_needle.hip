@@ -1,0 +1,603 @@
+// mtr_needle.hip — the needle meters (Vumeterdsp, Iec1ppmdsp, Iec2ppmdsp, Msppmdsp: the VU, DIN / Nordic, BBC / EBU and BBC M6 plugins'
+// detectors) for a batch, with a reading series (gfx950).
+//
+// Replaces Iec1ppmdsp::process = Iec2ppmdsp::process (jmeters/iec1ppmdsp.cc:47-80, iec2ppmdsp.cc:47-80), Msppmdsp::processM / processS
+// (msppmdsp.cc:50-114) and Vumeterdsp::process (vumeterdsp.cc:45-73), and their read ().  Per group of four frames a PPM does
+//     z1 *= w3, z2 *= w3;  four times: t = |x| (M/S: mv |l +- r|), if (t > z1) z1 += w1 (t - z1), if (t > z2) z2 += w2 (t - z2);
+//     t = z1 + z2, if (t > m) m = t
+// between a clamp of z1, z2 to [0, 20] at the start of a process () and a + 1e-10f at its end; the VU
+//     t2 = z2 / 2;  four times: t1 = |x| - t2, z1 += w (t1 - z1);  z2 += 4 w (z1 - z2), if (z2 > m) m = z2
+// between a clamp to [-20, 20] and, at the end, the flush of a z that is not finite (to 0, with m = INFINITY), z2 + 1e-10f otherwise.
+// The n mod 4 trailing frames of a process () are dropped.  One process () is the engine call, or — with a period P, for the reading
+// series — every block of exactly P frames, wherever the calls cut the audio; read () = g m follows each such block.
+//
+// The attack is not linear (it is a max of two affine maps, as k_tpb's), so there is no weighted-sum form: a chain per
+// (stream, channel, filter), serial in time, parallel over the streams only.  Being a plain serial chain it does the reference's own f32
+// operations in the reference's own order — this file is compiled without FMA contraction and without fast-math, f32 subnormals are kept
+// — and the readings and states are bit for bit the reference's (tests/test_gpu_needle.py).  The comparisons are written as there: a NaN
+// sample loses every one of them and is ignored, an Inf sticks until the end of the process () and is clamped at the start of the next.
+//
+// Lane map.  A workgroup takes 32 / C streams (16 stereo, 32 mono) and has four waves, one per selected kind — a wave without a kind
+// only helps to stage — so code and constants are wave-uniform and the audio is read from HBM ONCE however many kinds run.  A PPM wave's lane is (stream, channel, filter): the two
+// attack filters of a detector sit in neighbouring lanes and z1 + z2 is formed across the pair (DPP) once per group — half the chain
+// of a lane that runs both.  The VU's two stages are coupled: lane = (stream, channel), half the wave.  The streams advance in lock
+// step, so where a group or a period stands is the same in every lane: all of the control flow is scalar.
+//
+// Staging.  The waves of a workgroup stage chunks of 256 frames per stream through two LDS buffers by 16-byte loads from addresses
+// that are multiples of 16 — whatever the row's own alignment: each row is fetched from the aligned quad in front of the chunk, so an odd
+// stride or an odd base only shifts where the quads land; the chunks at a call's ends, whose quads could reach outside the call's
+// frames, are fetched dword by dword — with the next chunk in flight in registers under the chain.  A row is padded by one frame: the
+// chain lanes read the same frame of 16 (32) different rows, 2 (1) banks apart.  State lives in registers across the call; a period's
+// end inside a chunk is handled in the chain: the end-of-block constants, the point, m = 0, the P mod 4 frames skipped, the clamp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+
+/* a detector: per (stream, selected kind, channel).  z1 z2 m are where the chain stands — inside a period the locals of the open
+ * process () — s1 s2 what the most recent completed process () stored, `last` the reading of the last completed period */
+typedef struct mtr_needle_state {
+	float    z1, z2, m, last, s1, s2;
+	uint32_t res;                 /* _res: read () has taken the maximum, the next process () starts a new one (period 0) */
+	uint32_t pad;
+} mtr_needle_state;
+
+/* in front of a stream's detectors: what the state blob needs of the engine (the host's copies rule; export writes them in) */
+typedef struct mtr_needle_hdr {
+	uint32_t kinds, period, fill, pad;
+	float    db[2], mv[2];
+} mtr_needle_hdr;
+
+typedef struct mtr_needle_args {
+	const float*    audio;        /* [S][stride][C] */
+	uint64_t        stride, n_frames;
+	uint32_t        n_streams, n_kinds;
+	uint32_t        kind[4];      /* the kind of wave i */
+	float           w[4][4];      /* ... and its w1 w2 w3 g (VU: w, 4 w, 0, g) */
+	float           mv[2];        /* Msppmdsp's gains: M, S */
+	uint32_t        period;       /* frames per process (): P, or the call's n_frames */
+	uint32_t        fill;         /* frames into the open period on entry */
+	uint32_t        series;       /* P > 0: read () after every period, appended to the series */
+	uint32_t        capacity;
+	uint64_t        point0;       /* periods completed before this call */
+	unsigned char*  state;        /* [S] of { mtr_needle_hdr, mtr_needle_state [n_kinds][C] } */
+	uint32_t        state_pitch;
+	float*          points;       /* [n_kinds][..][capacity][C], from the view's first stream */
+	uint64_t        kind_pitch;   /* floats from kind to kind */
+} mtr_needle_args;
+
+namespace {
+
+constexpr int CH = 256;                  // frames per staged chunk
+constexpr int NW = 4;                    // waves per workgroup: one per selected kind runs a chain, all of them stage
+
+template <int C> struct Geo {
+	static constexpr int NS = 32 / C;            // streams per workgroup
+	static constexpr int ROW = CH * C;           // dwords of a row's chunk
+	static constexpr int PITCH = ROW + C;        // ... padded by one frame
+	static constexpr int NQ = ROW / 4 + 1;       // aligned quads that cover a chunk starting at any of the four alignments
+	static constexpr int ITEMS = NS * NQ;
+};
+
+__device__ __forceinline__ float pair_other (float v)
+{
+	return __int_as_float (__builtin_amdgcn_update_dpp (0, __float_as_int (v), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+}
+
+// Iec1ppmdsp / Iec2ppmdsp / Msppmdsp: lane = (row, filter)
+template <int C, bool MS> struct Ppm {
+	float z, m, s, last, w, w3, g, mv;
+	uint32_t res, sgn;
+	int   base;                                  // the lane's dword in a staged frame 0
+	bool  series;
+
+	using Raw = std::conditional_t<MS, float2, float>;
+	struct Quad { Raw r[4]; };
+
+	__device__ __forceinline__ Raw raw (const float* buf, int k) const
+	{
+		if constexpr (MS) return *reinterpret_cast<const float2*> (buf + base + 2 * k);
+		else return buf[base + k * C];
+	}
+	__device__ __forceinline__ Quad load (const float* buf, int k) const { return Quad{{ raw (buf, k), raw (buf, k + 1), raw (buf, k + 2), raw (buf, k + 3) }}; }
+	__device__ __forceinline__ float val (Raw x) const
+	{
+		if constexpr (MS) return mv * fabsf (x.x + __uint_as_float (__float_as_uint (x.y) ^ sgn));         // l + r, l - r
+		else return fabsf (x);
+	}
+	__device__ __forceinline__ void start ()
+	{
+		z = z > 20 ? 20 : (z < 0 ? 0 : z);
+		m = series || res ? 0 : m;
+		res = 0;
+	}
+	template <bool FIRST, bool LAST> __device__ __forceinline__ void one (Raw x)
+	{
+		const float t = val (x);
+		if (FIRST) z *= w3;
+		if (t > z) z += w * (t - z);
+		if (LAST) {
+			const float u = z + pair_other (z);
+			if (u > m) m = u;
+		}
+	}
+	__device__ __forceinline__ void step (const float* buf, int k, int q)
+	{
+		if (q == 0) one<true, false> (raw (buf, k));
+		else if (q == 3) one<false, true> (raw (buf, k));
+		else one<false, false> (raw (buf, k));
+	}
+	__device__ __forceinline__ void group (const Quad& x)
+	{
+		one<true, false> (x.r[0]); one<false, false> (x.r[1]); one<false, false> (x.r[2]); one<false, true> (x.r[3]);
+	}
+	__device__ __forceinline__ float end ()
+	{
+		z = z + 1e-10f;
+		s = z;
+		if (series) last = g * m;
+		return last;
+	}
+};
+
+// Vumeterdsp: lane = row
+template <int C> struct Vu {
+	float z1, z2, t2, m, s1, s2, last, w, w4, g;
+	uint32_t res;
+	int   base;
+	bool  series;
+
+	__device__ __forceinline__ void start ()
+	{
+		z1 = z1 > 20 ? 20 : (z1 < -20 ? -20 : z1);
+		z2 = z2 > 20 ? 20 : (z2 < -20 ? -20 : z2);
+		m = series || res ? 0 : m;
+		res = 0;
+	}
+	struct Quad { float r[4]; };
+	__device__ __forceinline__ float raw (const float* buf, int k) const { return buf[base + k * C]; }
+	__device__ __forceinline__ Quad load (const float* buf, int k) const { return Quad{{ raw (buf, k), raw (buf, k + 1), raw (buf, k + 2), raw (buf, k + 3) }}; }
+	template <bool FIRST, bool LAST> __device__ __forceinline__ void one (float x)
+	{
+		if (FIRST) t2 = z2 / 2;
+		const float t1 = fabsf (x) - t2;
+		z1 += w * (t1 - z1);
+		if (LAST) {
+			z2 += w4 * (z1 - z2);
+			if (z2 > m) m = z2;
+		}
+	}
+	__device__ __forceinline__ void step (const float* buf, int k, int q)
+	{
+		if (q == 0) one<true, false> (raw (buf, k));
+		else if (q == 3) one<false, true> (raw (buf, k));
+		else one<false, false> (raw (buf, k));
+	}
+	__device__ __forceinline__ void group (const Quad& x)
+	{
+		one<true, false> (x.r[0]); one<false, false> (x.r[1]); one<false, false> (x.r[2]); one<false, true> (x.r[3]);
+	}
+	__device__ __forceinline__ float end ()
+	{
+		if (!isfinite (z1)) { z1 = 0; m = INFINITY; }
+		if (!isfinite (z2)) { z2 = 0; m = INFINITY; } else z2 = z2 + 1e-10f;
+		s1 = z1; s2 = z2;
+		if (series) last = g * m;
+		return last;
+	}
+};
+
+// where the lock-step streams stand in the period, and what happens at its ends: scalar
+struct Walk {
+	uint32_t j, P, P4;                           // frames into the period, its length, the frames of it that are kept
+	uint64_t point;
+};
+
+// the `nf` staged frames of a chunk through a chain; `put (reading, point)` stores a point of the series
+template <class Chain, class Put>
+__device__ __forceinline__ void walk (Chain& c, Walk& w, const float* buf, int nf, Put put)
+{
+	int k = 0;
+	while (k < nf) {
+		if (w.j == 0) c.start ();
+		if (w.j < w.P4) {
+			int run = (int) min ((uint32_t) (nf - k), w.P4 - w.j);
+			int q = (int) (w.j & 3);
+			w.j += (uint32_t) run;
+			for (; run > 0 && q; --run, ++k, q = (q + 1) & 3) c.step (buf, k, q);
+			for (; run >= 16; run -= 16, k += 16) {  // four groups: their LDS reads issued together, one exposed wait per 16 frames
+				const typename Chain::Quad x0 = c.load (buf, k), x1 = c.load (buf, k + 4), x2 = c.load (buf, k + 8), x3 = c.load (buf, k + 12);
+				c.group (x0); c.group (x1); c.group (x2); c.group (x3);
+			}
+			for (; run >= 4; run -= 4, k += 4) c.group (c.load (buf, k));
+			for (; run > 0; --run, ++k, ++q) c.step (buf, k, q);
+		} else {                                 // the P mod 4 frames at the period's end: dropped
+			const uint32_t skip = min ((uint32_t) (nf - k), w.P - w.j);
+			k += (int) skip; w.j += skip;
+		}
+		if (w.j == w.P) {
+			const float r = c.end ();
+			if (c.series) put (r, w.point);
+			++w.point;
+			w.j = 0;
+		}
+	}
+}
+
+template <int C>
+__global__ __launch_bounds__ (64 * NW) void k_needle (const mtr_needle_args a)
+{
+	using G = Geo<C>;
+	constexpr int NT = 64 * NW, PER = (G::ITEMS + NT - 1) / NT;
+	__shared__ float lds[2][G::NS * G::PITCH];
+
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int wid = __builtin_amdgcn_readfirstlane (tid >> 6);
+	const uint32_t s0 = blockIdx.x * G::NS;
+	const int64_t rowlen = (int64_t) a.n_frames * C;                  // dwords of a row that belong to the call
+	const bool al4 = (reinterpret_cast<size_t> (a.audio) & 3) == 0;
+	const uint64_t abase = reinterpret_cast<size_t> (a.audio) >> 2;
+
+	// ---- staging: item i = (row, aligned quad) ----
+	float4 pre[PER];
+	auto place = [&] (int i, int64_t T, int& r, int64_t& d) __attribute__ ((always_inline)) -> bool {
+		r = i / G::NQ;
+		const int q = i - r * G::NQ;
+		const uint32_t s = s0 + (uint32_t) r;
+		if (i >= G::ITEMS || s >= a.n_streams) return false;
+		const uint64_t row = (uint64_t) s * a.stride * C;
+		const int al = (int) ((abase + row + (uint64_t) T * C) & 3);   // dwords from the aligned quad to the chunk's first
+		d = T * C - al + 4 * q;                                        // the quad's first dword in the row
+		return true;
+	};
+	// (a chunk whose quads all lie inside the call's frames, whatever the rows' alignment — every chunk but a call's first and its
+	// last two at most, the same for all lanes — is fetched by 16-byte loads alone: a load that shares its registers with the careful
+	// path's would be waited for where it is issued)
+	auto fetch = [&] (int64_t T) __attribute__ ((always_inline)) {
+		if (al4 && T > 0 && (T + CH) * C + 3 < rowlen) {
+#pragma unroll
+			for (int j = 0; j < PER; ++j) {
+				int r; int64_t d;
+				float4 v = float4{0.f, 0.f, 0.f, 0.f};
+				if (place (tid + j * NT, T, r, d)) v = *reinterpret_cast<const float4*> (a.audio + (uint64_t) (s0 + (uint32_t) r) * a.stride * C + d);
+				pre[j] = v;
+			}
+		} else {
+#pragma unroll
+			for (int j = 0; j < PER; ++j) {
+				int r; int64_t d;
+				float4 v = float4{0.f, 0.f, 0.f, 0.f};
+				if (place (tid + j * NT, T, r, d)) {
+					const float* const p = a.audio + (uint64_t) (s0 + (uint32_t) r) * a.stride * C;
+					if (d >= 0 && d < rowlen) v.x = p[d];
+					if (d + 1 >= 0 && d + 1 < rowlen) v.y = p[d + 1];
+					if (d + 2 >= 0 && d + 2 < rowlen) v.z = p[d + 2];
+					if (d + 3 >= 0 && d + 3 < rowlen) v.w = p[d + 3];
+				}
+				pre[j] = v;
+			}
+		}
+	};
+	auto stash = [&] (int b, int64_t T) __attribute__ ((always_inline)) {
+#pragma unroll
+		for (int j = 0; j < PER; ++j) {
+			int r; int64_t d;
+			if (place (tid + j * NT, T, r, d)) {
+				const int o = (int) (d - T * C);                           // -3 .. ROW
+				float* const dst = &lds[b][r * G::PITCH];
+				if (o >= 0 && o + 3 < G::ROW) { dst[o] = pre[j].x; dst[o + 1] = pre[j].y; dst[o + 2] = pre[j].z; dst[o + 3] = pre[j].w; }
+				else {
+					if (o >= 0 && o < G::ROW) dst[o] = pre[j].x;
+					if (o + 1 >= 0 && o + 1 < G::ROW) dst[o + 1] = pre[j].y;
+					if (o + 2 >= 0 && o + 2 < G::ROW) dst[o + 2] = pre[j].z;
+					if (o + 3 >= 0 && o + 3 < G::ROW) dst[o + 3] = pre[j].w;
+				}
+			}
+		}
+	};
+
+	// ---- the chains ----
+	const uint32_t kind = a.kind[wid < (int) a.n_kinds ? wid : 0];
+	const bool vu = kind == MTR_NEEDLE_VU;
+	const int row = vu ? (lane & 31) : (lane >> 1);
+	const int filt = lane & 1;
+	const int sl = row / C, ch = row % C;
+	const uint32_t s = s0 + (uint32_t) sl;
+	const bool live = s < a.n_streams;
+	const bool writer = live && (vu ? lane < 32 : true);
+	const int64_t N = (int64_t) a.n_frames;
+	const int64_t nchunks = (N + CH - 1) / CH;
+	if (wid >= (int) a.n_kinds) {                                      // no chain of its own: this wave only helps to stage
+		fetch (0);
+		for (int64_t c = 0; c < nchunks; ++c) {
+			stash ((int) (c & 1), c * CH);
+			__syncthreads ();
+			if (c + 1 < nchunks) fetch ((c + 1) * CH);
+		}
+		return;
+	}
+	mtr_needle_state* const st = reinterpret_cast<mtr_needle_state*> (a.state + (size_t) (live ? s : 0) * a.state_pitch + sizeof (mtr_needle_hdr)) + wid * C + ch;
+	float* const pts = a.points ? a.points + (size_t) wid * a.kind_pitch + (size_t) s * a.capacity * C + ch : nullptr;
+	const float w1 = a.w[wid][0], w2 = a.w[wid][1], w3 = a.w[wid][2], g = a.w[wid][3];
+	const uint32_t cap = a.capacity;
+	// the carried state, here before the first chunk is asked for: nothing in the loop below waits for it behind a chunk's loads
+	mtr_needle_state v0 = *st;
+	asm volatile ("" : "+v" (v0.z1), "+v" (v0.z2), "+v" (v0.m), "+v" (v0.last), "+v" (v0.s1), "+v" (v0.s2), "+v" (v0.res));
+
+	// One loop per kind: the waves of a workgroup meet at its barrier from different places (the three chains, the helpers), once per chunk each.  Chunk c + 1 is on its
+	// way into registers while chunk c goes through the chain; it is stored behind the barrier that says chunk c - 1's readers are done.
+	auto run = [&] (auto& chain, auto put) __attribute__ ((always_inline)) {
+		Walk wk;
+		wk.j = a.fill; wk.P = a.period; wk.P4 = a.period & ~3u; wk.point = a.point0;
+		fetch (0);
+		for (int64_t c = 0; c < nchunks; ++c) {
+			stash ((int) (c & 1), c * CH);
+			__syncthreads ();
+			if (c + 1 < nchunks) fetch ((c + 1) * CH);
+			walk (chain, wk, lds[c & 1], (int) min ((int64_t) CH, N - c * CH), put);
+		}
+	};
+	if (vu) {
+		Vu<C> p;
+		p.z1 = v0.z1; p.z2 = v0.z2; p.m = v0.m; p.s1 = v0.s1; p.s2 = v0.s2; p.last = v0.last; p.res = v0.res;
+		p.t2 = p.z2 / 2;
+		p.w = w1; p.w4 = w2; p.g = g; p.base = sl * G::PITCH + ch; p.series = a.series != 0;
+		run (p, [&] (float r, uint64_t point) { if (writer && point < cap) pts[point * C] = r; });
+		if (writer) { st->z1 = p.z1; st->z2 = p.z2; st->m = p.m; st->s1 = p.s1; st->s2 = p.s2; st->last = p.last; st->res = p.res; }
+		return;
+	}
+	auto ppm = [&] (auto& p) __attribute__ ((always_inline)) {
+		p.z = filt ? v0.z2 : v0.z1; p.m = v0.m; p.s = filt ? v0.s2 : v0.s1; p.last = v0.last; p.res = v0.res;
+		p.w = filt ? w2 : w1; p.w3 = w3; p.g = g; p.mv = a.mv[ch]; p.sgn = ch ? 0x80000000u : 0u; p.series = a.series != 0;
+		run (p, [&] (float r, uint64_t point) { if (writer && !filt && point < cap) pts[point * C] = r; });
+		if (!writer) return;
+		if (filt) { st->z2 = p.z; st->s2 = p.s; }
+		else { st->z1 = p.z; st->s1 = p.s; st->m = p.m; st->last = p.last; st->res = p.res; }
+	};
+	if (C == 2 && kind == MTR_NEEDLE_MS) {
+		Ppm<C, true> p;
+		p.base = sl * G::PITCH;
+		ppm (p);
+	} else {
+		Ppm<C, false> p;
+		p.base = sl * G::PITCH + ch;
+		ppm (p);
+	}
+}
+
+int kind_index (uint32_t kinds, uint32_t kind)
+{
+	if (!kind || (kind & (kind - 1)) || !(kinds & kind)) return -1;
+	return __builtin_popcount (kinds & (kind - 1));
+}
+
+}  // namespace
+
+template <int C> static void launch_c (const mtr_needle_args& a, hipStream_t st)
+{
+	hipLaunchKernelGGL ((k_needle<C>), dim3 ((a.n_streams + Geo<C>::NS - 1) / Geo<C>::NS), dim3 (64 * NW), 0, st, a);
+}
+
+static int mtr_launch_needle (const mtr_needle_args& a, uint32_t n_channels, void* stream)
+{
+	if (n_channels == 2) launch_c<2> (a, (hipStream_t) stream);
+	else launch_c<1> (a, (hipStream_t) stream);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// ---- NEEDLE in the engine: set-up, the call's step, the blob's section and the cursors in it, the C entry points ------------------------
+
+static uint32_t needle_count (const mtr_engine* e) { return (uint32_t) __builtin_popcount (e->nd.kinds); }
+static size_t needle_pitch (const mtr_engine* e)
+{
+	return sizeof (mtr_needle_hdr) + (size_t) needle_count (e) * e->cfg.n_channels * sizeof (mtr_needle_state);
+}
+
+// the coefficients of the selected kinds, in the order of their bits: the order of the waves, the states and the series
+static void needle_coefs (mtr_engine* e)
+{
+	uint32_t i = 0;
+	for (uint32_t k = 1; k <= MTR_NEEDLE_MS; k <<= 1)
+		if (e->nd.kinds & k) { e->nd.kind[i] = k; mtr_setup_needle (k, e->cfg.sample_rate, e->nd.w[i]); ++i; }
+}
+
+int needle_create (mtr_engine* e)
+{
+	e->nd.kinds = MTR_NEEDLE_IEC2;
+	e->nd.period = 0; e->nd.cap = 0;
+	e->nd.db[0] = e->nd.db[1] = 0.f; e->nd.mv[0] = e->nd.mv[1] = 1.0f;   // msppmdsp.cc:34-43 ...
+	needle_coefs (e);
+	int rc = mtr_engine_needle_set_gain (e, 0, -6.f);                     // ... and src/meters.cc:211-212
+	if (rc == MTR_OK) rc = mtr_engine_needle_set_gain (e, 1, -6.f);
+	return rc;
+}
+
+int needle_step (mtr_engine* e, const Call& c, Cursors& nx)
+{
+	const uint32_t P = e->nd.period, C = e->cfg.n_channels;
+	mtr_needle_args a;
+	memset (&a, 0, sizeof (a));
+	a.audio = c.audio; a.stride = c.stride; a.n_frames = c.n_frames;
+	a.n_streams = c.cnt; a.n_kinds = needle_count (e);
+	memcpy (a.kind, e->nd.kind, sizeof (a.kind));
+	memcpy (a.w, e->nd.w, sizeof (a.w));
+	a.mv[0] = e->nd.mv[0]; a.mv[1] = e->nd.mv[1];
+	a.period = P ? P : (uint32_t) c.n_frames; a.fill = P ? e->pos.nd_fill : 0; a.series = P != 0;
+	a.capacity = e->nd.cap; a.point0 = e->pos.nd_points;
+	a.state_pitch = (uint32_t) needle_pitch (e);
+	a.state = e->nd.state.p + (size_t) c.off * a.state_pitch;
+	a.kind_pitch = (uint64_t) e->cfg.n_streams * e->nd.cap * C;
+	a.points = P && e->nd.cap ? e->nd.series.p + (size_t) c.off * e->nd.cap * C : nullptr;
+	if (!a.points) a.capacity = 0;
+	if (mtr_launch_needle (a, C, c.st)) return fail (MTR_ERR_HIP, "k_needle launch");
+	const uint64_t tot = (uint64_t) e->pos.nd_fill + c.n_frames;
+	nx.nd_fill = P ? (uint32_t) (tot % P) : 0;
+	nx.nd_points = e->pos.nd_points + (P ? tot / P : 0);
+	return MTR_OK;
+}
+
+void needle_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	v.push_back ({ e->nd.state.p, needle_pitch (e) });
+}
+
+void needle_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
+{
+	const size_t pitch = needle_pitch (e);
+	for (uint32_t k = 0; k < count; ++k) {
+		mtr_needle_hdr h;
+		memset (&h, 0, sizeof (h));
+		h.kinds = e->nd.kinds; h.period = e->nd.period; h.fill = e->pos.nd_fill;
+		memcpy (h.db, e->nd.db, sizeof (h.db)); memcpy (h.mv, e->nd.mv, sizeof (h.mv));
+		memcpy (sec + (size_t) k * pitch, &h, sizeof (h));
+	}
+}
+
+int needle_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, mtr_needle_hdr* out)
+{
+	const size_t pitch = needle_pitch (e);
+	mtr_needle_hdr h0;
+	memset (&h0, 0, sizeof (h0));
+	for (uint32_t k = 0; k < count; ++k) {
+		mtr_needle_hdr h;
+		memcpy (&h, sec + (size_t) k * pitch, sizeof (h));
+		if (k == 0) h0 = h;
+		if (memcmp (&h, &h0, sizeof (h)) || (h.period ? h.fill >= h.period || h.period < 16 : h.fill != 0) || !h.kinds || (h.kinds & ~15u)
+		    || !(h.mv[0] >= 0.f) || !(h.mv[1] >= 0.f))
+			return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (cursors of the needle meters)");
+	}
+	if (h0.kinds != e->nd.kinds || h0.period != e->nd.period)
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the blob's needle meters are configured otherwise (kinds or period)");
+	if (!fresh && (h0.fill != e->pos.nd_fill || memcmp (h0.db, e->nd.db, sizeof (h0.db)) || memcmp (h0.mv, e->nd.mv, sizeof (h0.mv))))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period or gains of the needle meters)");
+	*out = h0;
+	return MTR_OK;
+}
+
+void needle_take_cursors (mtr_engine* e, const mtr_needle_hdr* h)
+{
+	e->pos.nd_fill = h->fill;
+	memcpy (e->nd.db, h->db, sizeof (h->db)); memcpy (e->nd.mv, h->mv, sizeof (h->mv));
+}
+
+size_t needle_hdr_bytes (void) { return sizeof (mtr_needle_hdr); }
+
+extern "C" {
+
+int mtr_needle_coef (uint32_t kind, float sample_rate, float* out4)
+{
+	if (!out4 || !(sample_rate >= 1.f)) return fail (MTR_ERR_ARG, "mtr_needle_coef");
+	if (mtr_setup_needle (kind, sample_rate, out4)) return fail (MTR_ERR_ARG, "mtr_needle_coef: kind is one of MTR_NEEDLE_VU / _IEC1 / _IEC2 / _MS");
+	return MTR_OK;
+}
+
+static int no_needle (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_NEEDLE); }
+
+int mtr_engine_needle_reset (mtr_engine* e)
+{
+	if (no_needle (e)) return fail (MTR_ERR_ARG, "no NEEDLE in this engine");
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t S = e->cfg.n_streams, per = needle_count (e) * e->cfg.n_channels;
+	const size_t pitch = needle_pitch (e);
+	if (e->nd.state.reserve ((size_t) S * pitch)) return fail (MTR_ERR_NOMEM, "hipMalloc NEEDLE state");
+	std::vector<unsigned char> h ((size_t) S * pitch, 0);             // the constructors: z1 = z2 = m = 0, _res = true
+	for (uint32_t s = 0; s < S; ++s)
+		for (uint32_t i = 0; i < per; ++i) {
+			mtr_needle_state v;
+			memset (&v, 0, sizeof (v));
+			v.res = 1;
+			memcpy (h.data () + (size_t) s * pitch + sizeof (mtr_needle_hdr) + (size_t) i * sizeof (v), &v, sizeof (v));
+		}
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemcpy (e->nd.state.p, h.data (), h.size (), hipMemcpyHostToDevice));
+	e->pos.nd_fill = 0;
+	e->pos.nd_points = 0;
+	return MTR_OK;
+}
+
+int mtr_engine_needle_configure (mtr_engine* e, uint32_t kinds, uint32_t period_frames, uint32_t capacity_points)
+{
+	if (no_needle (e)) return fail (MTR_ERR_ARG, "no NEEDLE in this engine");
+	if (!kinds || (kinds & ~(uint32_t) (MTR_NEEDLE_VU | MTR_NEEDLE_IEC1 | MTR_NEEDLE_IEC2 | MTR_NEEDLE_MS)))
+		return fail (MTR_ERR_ARG, "mtr_engine_needle_configure: kinds is a non-empty subset of MTR_NEEDLE_VU | _IEC1 | _IEC2 | _MS");
+	if ((kinds & MTR_NEEDLE_MS) && e->cfg.n_channels != 2)
+		return fail (MTR_ERR_UNSUPPORTED, "MTR_NEEDLE_MS meters the sum and the difference of a stereo pair: n_channels 2");
+	if (period_frames && (period_frames < 16 || period_frames >= 0x7fffffffu))
+		return fail (MTR_ERR_ARG, "mtr_engine_needle_configure: a period is 0 or at least 16 frames");
+	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_needle_configure: only on an engine that has processed nothing since create / reset");
+	{ const int rc = wait_stream (e); if (rc) return rc; }
+	const size_t n = period_frames ? (size_t) __builtin_popcount (kinds) * e->cfg.n_streams * capacity_points * e->cfg.n_channels : 0;
+	if (n && e->nd.series.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc NEEDLE series");
+	if (n) HIPCHK (hipMemset (e->nd.series.p, 0, n * sizeof (float)));
+	e->nd.kinds = kinds;
+	e->nd.period = period_frames;
+	e->nd.cap = period_frames ? capacity_points : 0;
+	needle_coefs (e);
+	return mtr_engine_needle_reset (e);
+}
+
+int mtr_engine_needle_set_gain (mtr_engine* e, int side, float db)
+{
+	if (no_needle (e)) return fail (MTR_ERR_ARG, "no NEEDLE in this engine");
+	if (side < 0 || side > 1 || !std::isfinite (db)) return fail (MTR_ERR_ARG, "mtr_engine_needle_set_gain: side 0 (M) or 1 (S), a finite gain");
+	if (e->nd.db[side] == db) return MTR_OK;                          // msppmdsp.cc:143-145
+	e->nd.db[side] = db;
+	e->nd.mv[side] = mtr_setup_needle_gain (db);
+	return MTR_OK;
+}
+
+int mtr_engine_needle_read (mtr_engine* e, uint32_t kind, uint32_t first, uint32_t count, float* level, float* state)
+{
+	int rc = meter_range (e, !no_needle (e) && level, "no NEEDLE in this engine", first, count);
+	if (rc) return rc;
+	const int ki = kind_index (e->nd.kinds, kind);
+	if (ki < 0) return fail (MTR_ERR_ARG, "mtr_engine_needle_read: kind is one of the engine's selected kinds");
+	if ((rc = wait_stream (e))) return rc;
+	const uint32_t C = e->cfg.n_channels;
+	const size_t pitch = needle_pitch (e);
+	std::vector<unsigned char> h ((size_t) count * pitch);
+	if (count) HIPCHK (hipMemcpy (h.data (), e->nd.state.p + (size_t) first * pitch, h.size (), hipMemcpyDeviceToHost));
+	const float g = e->nd.w[ki][3];
+	for (uint32_t i = 0; i < count; ++i)
+		for (uint32_t c = 0; c < C; ++c) {
+			unsigned char* const at = h.data () + (size_t) i * pitch + sizeof (mtr_needle_hdr) + ((size_t) ki * C + c) * sizeof (mtr_needle_state);
+			mtr_needle_state v;
+			memcpy (&v, at, sizeof (v));
+			if (e->nd.period) level[(size_t) i * C + c] = v.last;
+			else {
+				level[(size_t) i * C + c] = g * v.m;                      // read (): _res = true; return _g * _m
+				v.res = 1;
+				memcpy (at, &v, sizeof (v));
+			}
+			if (state) { state[((size_t) i * C + c) * 2] = v.s1; state[((size_t) i * C + c) * 2 + 1] = v.s2; }
+		}
+	if (count && !e->nd.period) HIPCHK (hipMemcpy (e->nd.state.p + (size_t) first * pitch, h.data (), h.size (), hipMemcpyHostToDevice));
+	return MTR_OK;
+}
+
+int mtr_engine_needle_series (mtr_engine* e, uint32_t kind, uint32_t first, uint32_t count, float* out, uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_needle (e), "no NEEDLE in this engine", first, count);
+	if (rc) return rc;
+	const int ki = kind_index (e->nd.kinds, kind);
+	if (ki < 0) return fail (MTR_ERR_ARG, "mtr_engine_needle_series: kind is one of the engine's selected kinds");
+	const uint64_t n = e->pos.nd_points, kept = std::min<uint64_t> (n, e->nd.cap);
+	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
+	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
+	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	if (!out || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	const size_t C = e->cfg.n_channels;
+	const float* const src = e->nd.series.p + ((size_t) ki * e->cfg.n_streams + first) * e->nd.cap * C;
+	HIPCHK (hipMemcpy2D (out, (size_t) capacity * C * sizeof (float), src, (size_t) e->nd.cap * C * sizeof (float),
+	                     take * C * sizeof (float), count, hipMemcpyDeviceToHost));
+	return MTR_OK;
+}
+
+} // extern "C"

@@ -291,3 +291,30 @@ void mtr_setup_stcorr (float fsamp, float* out2)
 	out2[0] = 6.28f * flp / fs;
 	out2[1] = 1 / (tcf * fs);
 }
+
+/* w1 w2 w3 g of Iec1ppmdsp::init (kind 2, iec1ppmdsp.cc:89-95) / Iec2ppmdsp::init = Msppmdsp::init (kinds 4, 8; iec2ppmdsp.cc:89-95,
+ * msppmdsp.cc:131-137); Vumeterdsp::init (kind 1, vumeterdsp.cc:82-86) as w, 4 w, 0, g.  -1: not one of the four kinds */
+int mtr_setup_needle (uint32_t kind, float fsamp, float* out4)
+{
+	switch (kind) {
+	case 1u: {
+		const float w = 11.1f / fsamp;
+		out4[0] = w; out4[1] = 4 * w; out4[2] = 0.f; out4[3] = 1.5f * 1.571f;
+		return 0;
+	}
+	case 2u:
+		out4[0] = 450.0f / fsamp; out4[1] = 1300.0f / fsamp; out4[2] = 1.0f - 5.4f / fsamp; out4[3] = 0.5108f;
+		return 0;
+	case 4u:
+	case 8u:
+		out4[0] = 200.0f / fsamp; out4[1] = 860.0f / fsamp; out4[2] = 1.0f - 4.0f / fsamp; out4[3] = 0.5141f;
+		return 0;
+	}
+	return -1;
+}
+
+/* Msppmdsp::set_gain's mv (msppmdsp.cc:140-148) */
+float mtr_setup_needle_gain (float db)
+{
+	return powf (10, .05 * db);
+}

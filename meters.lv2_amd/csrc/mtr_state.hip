@@ -55,7 +55,24 @@ std::vector<StateSection> state_sections (const mtr_engine* e)
 	// (the LAST section, and only of an engine with the bit: every other blob is byte for byte what it was.  The header has no room
 	// for the period and the frames into the open one: they travel in every stream's entry, stcorr_export_cursors / _import_cursors)
 	if (m & MTR_METER_STCORR) stcorr_sections (e, v);
+	// (behind it, likewise: kinds, period, cursor and gains in every stream's entry, needle_export_cursors / _import_cursors)
+	if (m & MTR_METER_NEEDLE) needle_sections (e, v);
 	return v;
+}
+
+// where the entries of section `idx` start in the payload of a blob of `count` streams
+size_t section_offset (const std::vector<StateSection>& secs, size_t idx, uint32_t count)
+{
+	size_t o = 0;
+	for (size_t i = 0; i < idx; ++i) o += (size_t) count * secs[i].elem;
+	return o;
+}
+
+// STCORR's and NEEDLE's sections are the last ones, in this order
+size_t needle_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - 1; }
+size_t stcorr_section (const mtr_engine* e, const std::vector<StateSection>& secs)
+{
+	return secs.size () - 1 - ((e->cfg.meters & MTR_METER_NEEDLE) ? 1 : 0);
 }
 
 size_t state_per_stream (const mtr_engine* e)
@@ -106,7 +123,9 @@ int mtr_engine_state_export (mtr_engine* e, uint32_t first, uint32_t count, void
 		if (count) HIPCHK (hipMemcpy (o, static_cast<const unsigned char*> (s.base) + (size_t) first * s.elem, (size_t) count * s.elem, hipMemcpyDeviceToHost));
 		o += (size_t) count * s.elem;
 	}
-	if (e->cfg.meters & MTR_METER_STCORR) stcorr_export_cursors (e, o - (size_t) count * secs.back ().elem, count);   // the host's cursors, not whatever the device copy holds
+	// the host's cursors, not whatever the device copy holds
+	if (e->cfg.meters & MTR_METER_STCORR) stcorr_export_cursors (e, o0 + section_offset (secs, stcorr_section (e, secs), count), count);
+	if (e->cfg.meters & MTR_METER_NEEDLE) needle_export_cursors (e, o0 + section_offset (secs, needle_section (e, secs), count), count);
 	h.payload_fnv = fnv1a64 (o0, (size_t) (o - o0));
 	memcpy (blob, &h, sizeof (h));
 	return MTR_OK;
@@ -141,7 +160,13 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	const std::vector<StateSection> secs = state_sections (e);
 	uint32_t sc_period = e->sc.period, sc_fill = (uint32_t) e->pos.sc_fill;
 	if ((e->cfg.meters & MTR_METER_STCORR) && h.count) {
-		rc = stcorr_import_cursors (e, i0 + (size_t) h.count * (h.per_stream_bytes - secs.back ().elem), h.count, fresh, &sc_period, &sc_fill);
+		rc = stcorr_import_cursors (e, i0 + section_offset (secs, stcorr_section (e, secs), h.count), h.count, fresh, &sc_period, &sc_fill);
+		if (rc) return rc;
+	}
+	std::vector<unsigned char> nd_hdr (needle_hdr_bytes ());
+	const bool nd_take = (e->cfg.meters & MTR_METER_NEEDLE) && h.count;
+	if (nd_take) {
+		rc = needle_import_cursors (e, i0 + section_offset (secs, needle_section (e, secs), h.count), h.count, fresh, reinterpret_cast<mtr_needle_hdr*> (nd_hdr.data ()));
 		if (rc) return rc;
 	}
 	if (!fresh && (e->pos.frcnt != h.frcnt || e->integr != (h.integr != 0) || e->bank.omega != h.omega || e->pos.dr_scnt != h.dr_scnt))
@@ -161,6 +186,7 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;
 		e->sc.period = sc_period; e->pos.sc_fill = sc_fill;
+		if (nd_take) needle_take_cursors (e, reinterpret_cast<const mtr_needle_hdr*> (nd_hdr.data ()));
 		e->plan.valid = false;
 		e->advanced = true;
 	}

@@ -14,6 +14,8 @@ import numpy as np
 METER_EBU, METER_TRUEPEAK, METER_SPECTR30, METER_TPBALLIST = 0x01, 0x02, 0x04, 0x08
 METER_BITSTATS, METER_SIGDIST, METER_DR14, METER_KMETER = 0x10, 0x20, 0x40, 0x80
 METER_STCORR = 0x200                       # (0x100 is no meter)
+METER_NEEDLE = 0x800                       # VU, IEC I / II PPM, M/S PPM: include/mtr_needle.h (0x400 is no meter either)
+NEEDLE_VU, NEEDLE_IEC1, NEEDLE_IEC2, NEEDLE_MS = 1, 2, 4, 8
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
 PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3        # MTR_PCM_*: little-endian int16 / packed 3-byte / int32 samples
@@ -150,6 +152,13 @@ def _load():
         L.mtr_engine_stcorr_read.argtypes = [vp, u32, u32, vp, vp]
         L.mtr_engine_stcorr_series.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_stcorr_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_needle_read"):                   # (an addition inside ABI version 2: the needle meters)
+        L.mtr_needle_coef.argtypes = [u32, f32, vp]
+        L.mtr_engine_needle_configure.argtypes = [vp, u32, u32, u32]
+        L.mtr_engine_needle_set_gain.argtypes = [vp, C.c_int, f32]
+        L.mtr_engine_needle_read.argtypes = [vp, u32, u32, u32, vp, vp]
+        L.mtr_engine_needle_series.argtypes = [vp, u32, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_needle_reset.argtypes = [vp]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -207,9 +216,10 @@ def _check(rc, what):
         raise err
 
 
-def exported_symbols():
-    """Every function include/mtr_engine.h declares, parsed from the header itself."""
-    hdr = os.path.join(os.path.dirname(_HERE), "include", "mtr_engine.h")
+def exported_symbols(header="mtr_engine.h"):
+    """Every function include/mtr_engine.h — or one of the headers it includes, e.g. "mtr_needle.h" — declares itself, parsed from the
+    header."""
+    hdr = os.path.join(os.path.dirname(_HERE), "include", header)
     txt = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
     return sorted(set(re.findall(r"\b(mtr_[a-z0-9_]+)\s*\(", txt)))
 
@@ -236,6 +246,13 @@ def stcorr_coef(fs):
     """(w1, w2) of Stcorrdsp::init ((int) fs, 2e3f, 0.3f) as float32."""
     out = np.zeros(2, np.float32)
     _check(lib.mtr_stcorr_coef(fs, out.ctypes.data), "mtr_stcorr_coef")
+    return out
+
+
+def needle_coef(kind, fs):
+    """(w1, w2, w3, g) of the needle meter `kind` (one NEEDLE_* bit) as float32; NEEDLE_VU: (w, 4 w, 0, g)."""
+    out = np.zeros(4, np.float32)
+    _check(lib.mtr_needle_coef(int(kind), fs, out.ctypes.data), "mtr_needle_coef")
     return out
 
 
@@ -675,6 +692,38 @@ class Engine:
 
     def stcorr_reset(self):
         _check(lib.mtr_engine_stcorr_reset(self._h), "stcorr_reset")
+
+    def needle_configure(self, kinds, period_frames=0, capacity_points=0):
+        """kinds: NEEDLE_* bits.  period 0: every call is one process () per (stream, channel, kind); P >= 16: blocks of exactly P frames
+        wherever the calls cut the audio, read () after each appended to a series of `capacity_points` per stream and kind.  Only
+        before the first process call since create / reset."""
+        _check(lib.mtr_engine_needle_configure(self._h, int(kinds), int(period_frames), int(capacity_points)), "needle_configure")
+
+    def needle_set_gain(self, side, db):
+        """Msppmdsp::set_gain of the M (side 0) or S (side 1) detectors; applies from the next process call."""
+        _check(lib.mtr_engine_needle_set_gain(self._h, int(side), float(db)), "needle_set_gain")
+
+    def needle_read(self, kind, first=0, count=None):
+        """(level [count, C], state [count, C, 2] = z1 z2 as stored): read () now (period 0; arms a new maximum) or of the last
+        completed period."""
+        count = self.n_streams - first if count is None else count
+        level = np.zeros((count, self.n_channels), np.float32)
+        st = np.zeros((count, self.n_channels, 2), np.float32)
+        _check(lib.mtr_engine_needle_read(self._h, int(kind), first, count, level.ctypes.data, st.ctypes.data), "needle_read")
+        return level, st
+
+    def needle_series(self, kind, first=0, count=None):
+        """(points [count, kept, C], n_points, dropped): the readings of `kind` after every completed period since reset that the series holds."""
+        count = self.n_streams - first if count is None else count
+        n, d = C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_needle_series(self._h, int(kind), first, count, None, 0, C.byref(n), C.byref(d)), "needle_series")
+        kept = n.value - d.value
+        out = np.zeros((count, max(kept, 1), self.n_channels), np.float32)
+        _check(lib.mtr_engine_needle_series(self._h, int(kind), first, count, out.ctypes.data, out.shape[1], C.byref(n), C.byref(d)), "needle_series")
+        return out[:, :kept], n.value, d.value
+
+    def needle_reset(self):
+        _check(lib.mtr_engine_needle_reset(self._h), "needle_reset")
 
     def _need_loudlog(self):
         if not hasattr(lib, "mtr_engine_loudlog_series"):
