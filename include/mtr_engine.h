@@ -59,6 +59,8 @@ extern "C" {
 #define MTR_METER_STCORR     0x200u /* Stcorrdsp: stereo phase correlation          (jmeters/stcorrdsp.cc:47-93); 0x100 is no meter */
 #define MTR_METER_NEEDLE     0x800u /* Vumeterdsp / Iec1ppmdsp / Iec2ppmdsp / Msppmdsp (jmeters/), see mtr_needle.h; 0x400 is no meter
                                     * either (tests/test_stcorr_cpu.py holds both refused) */
+#define MTR_METER_SURROUND   0x2000u /* sur_run: C x Kmeterdsp + up to four Stcorrdsp on selectable pairs, 3 .. 8 channels (src/surmeter.c:115-147),
+                                    * see mtr_surround.h; 0x1000 is no meter, like 0x100 and 0x400 (tests/test_needle_cpu.py holds it refused) */
 
 #define MTR_HIST_LEN   751          /* src/uris.h:45  HIST_LEN */
 #define MTR_NBANDS     30           /* src/spectrumlv2.c:33  FILTER_COUNT */
@@ -354,6 +356,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The needle meters for a batch (MTR_METER_NEEDLE) — VU, IEC I / II PPM and M/S PPM, with a reading series: mtr_needle_coef and
  * mtr_engine_needle_configure / _set_gain / _read / _series / _reset */
 #include "mtr_needle.h"
+
+/* The surround meter for a batch (MTR_METER_SURROUND) — 3 .. 8 K-meters and up to four pair correlations from one read of the frames,
+ * with a reading series: mtr_engine_surround_set_pairs / _pairs / _set_period / _read / _pair_states / _series / _reset */
+#include "mtr_surround.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

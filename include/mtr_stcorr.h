@@ -12,7 +12,8 @@ extern "C" {
 #endif
 
 /* Stcorrdsp for a batch (MTR_METER_STCORR; stereo engines only — a pair of a wider frame: mtr_engine_set_frame_layout, e.g. 6, {4, 5}
- * for Ls / Rs of a 5.1 file, the surround plugins' selectable pairs, src/surmeter.c).  Combines with every other stereo meter; not with
+ * for Ls / Rs of a 5.1 file; all four selectable pairs of the surround plugins, src/surmeter.c, with their K-meters from one read of
+ * the wide frames: MTR_METER_SURROUND, mtr_surround.h).  Combines with every other stereo meter; not with
  * the per-stream-lengths entry points.  n_frames per call < 2^31 - 1.
  * w1, w2 of Stcorrdsp::init ((int) sample_rate, 2e3f, 0.3f) (stcorrdsp.cc:85-93; src/meters.cc:202-207) */
 int  mtr_stcorr_coef (float sample_rate, float* out2);

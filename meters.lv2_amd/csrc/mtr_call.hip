@@ -115,6 +115,7 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 		{ MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
+		{ MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_TPBALLIST, 0x7ffff000ull, "TPBALLIST: n_frames per call must be < 2^31 - 4096" },
 		{ MTR_METER_EBU | MTR_METER_TRUEPEAK, 0xFFFFFFFFull, "n_frames per call must be < 2^32 - 1" },
 	};
@@ -473,6 +474,7 @@ struct CallRun {
 		if ((meters & MTR_METER_KMETER) && (rc = kmeter_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_STCORR) && (rc = stcorr_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_NEEDLE) && (rc = needle_step (e, c, nx))) return rc;
+		if ((meters & MTR_METER_SURROUND) && (rc = surround_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, or the fused kernels)
@@ -615,7 +617,8 @@ static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frame
 	// A frame layout.  WAVE 5.1 on a 5-channel engine: k_kwmc51 and k_history_mc51 read the 6-channel frames where they lie (a pick pass
 	// in front of an HBM-bound kernel would read 6/5 and write 5/5 of the batch on top).  Every other map: the wide rows are picked chunk
 	// by chunk into the staging buffers, as device PCM is decoded.
-	const bool direct = e->picks && e->wave51;
+	// (not beside the surround meter, whose kernel takes frames of the engine's five channels: that engine stages the call like any other map)
+	const bool direct = e->picks && e->wave51 && !(e->cfg.meters & MTR_METER_SURROUND);
 	if (e->picks && !direct) return process_chunked (e, { d_audio, 0, false, hip_stream }, n_frames, stride, frames);
 	if (n_frames == 0) return MTR_OK;
 	if (stride < n_frames) return fail (MTR_ERR_ARG, "stream_stride_frames < n_frames");
@@ -743,7 +746,7 @@ int mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const u
 	const uint32_t C = e->cfg.n_channels;
 	if (frame_channels == 0) {
 		e->frame_channels = 0;
-		for (uint32_t c = 0; c < MTR_MAX_CHANNELS; ++c) e->frame_map[c] = (uint8_t) c;
+		for (uint32_t c = 0; c < MTR_MAX_ENGINE_CHANNELS; ++c) e->frame_map[c] = (uint8_t) c;
 		e->picks = e->wave51 = false;
 		return MTR_OK;
 	}
@@ -772,7 +775,7 @@ int mtr_engine_frame_layout (const mtr_engine* e, uint32_t* frame_channels, uint
 int mtr_pick_decode_host (int format, const void* src, size_t n_frames, uint32_t frame_channels, const uint8_t* map, uint32_t n_channels, float* dst)
 {
 	if (format && !mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown format (0 = f32, MTR_PCM_S16, _S24, _S32)");
-	if (!map || !frame_channels || frame_channels > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_CHANNELS)
+	if (!map || !frame_channels || frame_channels > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_ENGINE_CHANNELS)
 		return fail (MTR_ERR_ARG, "mtr_pick_decode_host: map / frame_channels / n_channels");
 	if (n_frames && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_pick_decode_host: null argument");
 	return mtr_setup_pick_decode (format, src, n_frames, frame_channels, map, n_channels, dst)
@@ -832,7 +835,8 @@ int mtr_engine_prepare_host (mtr_engine* e, uint32_t max_block_frames)
 	// one silent block of the largest size: page-locked staging, device buffers, the engine's stream and every kernel's
 	// code object exist afterwards (a first launch loads the module: milliseconds); then back to the state of a new engine
 	std::vector<float> zeros (max_block_frames, 0.f);
-	const float* ch[2] = { zeros.data (), zeros.data () };
+	const float* ch[MTR_MAX_ENGINE_CHANNELS];
+	for (const float*& p : ch) p = zeros.data ();
 	int rc = mtr_engine_process_planar_host (e, ch, max_block_frames);
 	if (rc) return rc;
 	return mtr_engine_reset (e);

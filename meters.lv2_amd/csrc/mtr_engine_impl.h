@@ -1,6 +1,6 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
 // EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
-// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip), and mtr_loudlog.hip (the host
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip), and mtr_loudlog.hip (the host
 // side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
 #ifndef MTR_ENGINE_IMPL_H
@@ -104,6 +104,10 @@ struct Cursors {
 	uint64_t sc_points = 0;       // ... and periods completed since reset
 	uint32_t nd_fill = 0;         // NEEDLE: frames in the open period of the reading series ...
 	uint64_t nd_points = 0;       // ... and periods completed since reset (what the series does not hold of them is dropped)
+	uint64_t su_fill = 0;         // SURROUND: frames in the open block of the reading series ...
+	uint64_t su_points = 0;       // ... blocks completed since reset ...
+	uint32_t su_fpp = 0;          // ... and its Kmeterdsps' frames per period with the fall-back factor that goes with it
+	float    su_fall = 0.f;
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 };
@@ -114,6 +118,7 @@ struct mtr_dr14_state;
 struct mtr_kmeter_state;
 struct mtr_stcorr_state;
 struct mtr_needle_hdr;
+struct mtr_sur_state;
 
 // The engine: core, tail, plan rings, host path, then one member per side meter
 struct mtr_engine {
@@ -212,7 +217,7 @@ struct mtr_engine {
 	// is source channel frame_map[c]; 0 = the default.  `picks`: the layout is not the identity, every chunk goes through k_pick
 	// (mtr_pick.hip) — from the raw landing buffers (host memory) or the caller's rows (device memory) into `stage`
 	uint32_t         frame_channels = 0;
-	uint8_t          frame_map[MTR_MAX_CHANNELS] = { 0, 1, 2, 3, 4 };
+	uint8_t          frame_map[MTR_MAX_ENGINE_CHANNELS] = { 0, 1, 2, 3, 4, 5, 6, 7 };
 	bool             picks = false;
 	bool             wave51 = false;      // ... and it is 6, {0, 1, 2, 4, 5} on a 5-channel engine: device f32 calls go to k_kwmc51 instead
 	uint64_t         lay_staged = 0, lay_direct = 0;
@@ -261,6 +266,17 @@ struct mtr_engine {
 		float                      w[4][4];     // ... and their w1 w2 w3 g
 		float                      db[2], mv[2];   // Msppmdsp's gains, M and S: a control (it survives a reset)
 	} nd;
+	struct Surround {                           // SURROUND (mtr_surround.hip)
+		DevBuf<mtr_sur_state>      state;       // [S]
+		DevBuf<double>             piece;       // [S][pieces][MTR_SUR_PIECE]
+		DevBuf<float>              s_level, s_peak, s_corr;   // [S][cap][C], [S][cap][C], [S][cap][4]
+		uint32_t                   period = 0, cap = 0;   // frames per sur_run of the series (0: the call), points per stream it holds
+		uint8_t                    pa[4] = { 0, 0, 0, 0 }, pb[4] = { 0, 0, 0, 0 };   // the pairs' channels: a control (it survives a reset)
+		float                      w[2];        // w1, w2 of Stcorrdsp::init
+		double                     pw[3];       // Kmeterdsp's A per group of four frames
+		double                     k[18];       // mtr_sur_consts: the pieces kernel's constants
+		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
+	} su;
 	struct LoudLog {                            // the loudness log of an EBU engine (mtr_loudlog.hip; the gate appends: mtr_gate.hip)
 		DevBuf<float>              M, S;        // [S][cap]
 		DevBuf<float>              run;         // [S][2] MAX: maxima of the period open between two calls
@@ -327,6 +343,9 @@ void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v);
 int  needle_create (mtr_engine* e);
 int  needle_step (mtr_engine* e, const Call& c, Cursors& nx);
 void needle_sections (const mtr_engine* e, std::vector<StateSection>& v);
+void surround_create (mtr_engine* e);
+int  surround_step (mtr_engine* e, const Call& c, Cursors& nx);
+void surround_sections (const mtr_engine* e, std::vector<StateSection>& v);
 // STCORR's section of a blob carries the period and the frames into the open one in every stream's entry (the header has no room for
 // them).  Export writes the host's copies into the `count` entries at `sec`; import checks the entries (MTR_ERR_STATE with the text set if
 // they are corrupt or — `fresh` false — not where the engine stands) and returns the two.
@@ -342,6 +361,13 @@ void needle_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t co
 int  needle_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, mtr_needle_hdr* out);
 void needle_take_cursors (mtr_engine* e, const mtr_needle_hdr* h);
 size_t needle_hdr_bytes (void);
+// SURROUND's section likewise: period, the frames into the open block, _fpp / _fall and the pairs in front of every stream's entry.  A
+// fresh engine takes them (surround_take_cursors, from the surround_hdr_bytes () that _import_cursors wrote to `out`); any other must
+// stand at the same period, fill and pairs
+void surround_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
+int  surround_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, unsigned char* out);
+void surround_take_cursors (mtr_engine* e, const unsigned char* hdr);
+size_t surround_hdr_bytes (void);
 
 #pragma GCC visibility pop
 

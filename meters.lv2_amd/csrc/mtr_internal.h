@@ -90,7 +90,8 @@ typedef struct mtr_seg_args {
 } mtr_seg_args;
 
 /* Arguments of the multichannel K-weighting + true-peak kernel (mtr_kwmc.hip, layout 8: n_channels 3, 4 or 5). */
-#define MTR_MAX_CHANNELS 5         /* Ebu_r128_proc::MAXCH, ebumeter/ebu_r128_proc.h:26 */
+#define MTR_MAX_CHANNELS 5         /* Ebu_r128_proc::MAXCH, ebumeter/ebu_r128_proc.h:26: what the K-weighting kernels take */
+#define MTR_MAX_ENGINE_CHANNELS 8  /* ... and an engine (6 .. 8: MTR_METER_SURROUND alone), k_pick and the frame map: the surround8 plugin's, = MTR_MAX_FRAME_CHANNELS */
 #define MTR_KWMC_RUN     20        /* K: frames per lane run (tiles of at most 1280 frames: half a fragment at 48 kHz) */
 typedef struct mtr_kwmc_args {
 	const float*    audio;        /* [S][stride][C] */

@@ -10,7 +10,7 @@
 //        pieces; the bytes behind the row's last whole 16 (fewer than 16, last tile of the row only) one by one;
 //     2. lane t takes output PIECES t, t + 256, ...: four consecutive floats of the destination row.  Float o of the tile is channel
 //        c = o mod C of frame o / C (C is a template parameter: a multiply and a shift), its sample lies at (frame * fc + map[c]) in
-//        LDS — the map is five 4-bit fields of one SGPR, picked with a shift, so no register array is indexed by a run-time value —
+//        LDS — the map is up to eight 4-bit fields of one SGPR, picked with a shift, so no register array is indexed by a run-time value —
 //        and is decoded exactly as k_pcm does (the sample in the top bits of an int32, one conversion, one exact scale; f32 samples
 //        move as bit patterns); one 16-byte store per piece; the floats behind the row's last whole piece one by one.
 //   any other row (the device entry points on a caller's rows: f32 on any 4 bytes, S16 on any even byte, S24 on any byte): every
@@ -115,6 +115,9 @@ int launch_fmt (uint32_t C, dim3 g, hipStream_t st, const uint8_t* s, uint64_t s
 	case 3: hipLaunchKernelGGL ((k_pick<FMT, 3>), g, b, 0, st, s, sp, d, dp, n_rows, n_frames, fc, map, tf, tiles); break;
 	case 4: hipLaunchKernelGGL ((k_pick<FMT, 4>), g, b, 0, st, s, sp, d, dp, n_rows, n_frames, fc, map, tf, tiles); break;
 	case 5: hipLaunchKernelGGL ((k_pick<FMT, 5>), g, b, 0, st, s, sp, d, dp, n_rows, n_frames, fc, map, tf, tiles); break;
+	case 6: hipLaunchKernelGGL ((k_pick<FMT, 6>), g, b, 0, st, s, sp, d, dp, n_rows, n_frames, fc, map, tf, tiles); break;
+	case 7: hipLaunchKernelGGL ((k_pick<FMT, 7>), g, b, 0, st, s, sp, d, dp, n_rows, n_frames, fc, map, tf, tiles); break;
+	case 8: hipLaunchKernelGGL ((k_pick<FMT, 8>), g, b, 0, st, s, sp, d, dp, n_rows, n_frames, fc, map, tf, tiles); break;
 	default: return -1;
 	}
 	return hipGetLastError () == hipSuccess ? 0 : -1;
@@ -126,7 +129,7 @@ int mtr_launch_pick (int format, const void* src, uint64_t src_pitch, uint32_t f
                      float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_frames, void* stream)
 {
 	if (!n_rows || !n_frames) return 0;
-	if (!frame_channels || frame_channels > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_CHANNELS) return -1;
+	if (!frame_channels || frame_channels > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_ENGINE_CHANNELS) return -1;
 	const size_t sb = format ? mtr_setup_pcm_sample_bytes (format) : sizeof (float);
 	if (!sb) return -1;
 	uint32_t mbits = 0;

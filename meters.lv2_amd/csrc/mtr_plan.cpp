@@ -12,7 +12,8 @@
 const char* resolve_layout (const mtr_config* cfg, int* layout, int* run, bool* seg_ok)
 {
 	const bool fused = cfg->meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK);
-	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_CHANNELS) return "n_channels must be 1 .. 5";
+	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_ENGINE_CHANNELS || (cfg->n_channels > MTR_MAX_CHANNELS && cfg->meters != MTR_METER_SURROUND))
+		return "n_channels must be 1 .. 5 (6 .. 8: MTR_METER_SURROUND alone)";
 	if (cfg->n_channels > 2 && fused) {
 		// every EBU / TRUEPEAK engine of 3 .. 5 channels runs k_kwmc (layout 8, mtr_kwmc.hip)
 		if (cfg->tune_layout != 0 && cfg->tune_layout != 8) return "n_channels 3 .. 5: tune_layout must be 0 or 8 (k_kwmc is the only multichannel kernel)";

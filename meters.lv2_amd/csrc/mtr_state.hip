@@ -57,6 +57,9 @@ std::vector<StateSection> state_sections (const mtr_engine* e)
 	if (m & MTR_METER_STCORR) stcorr_sections (e, v);
 	// (behind it, likewise: kinds, period, cursor and gains in every stream's entry, needle_export_cursors / _import_cursors)
 	if (m & MTR_METER_NEEDLE) needle_sections (e, v);
+	// (and the surround meter's — never beside those two, which meter one or two channels: period, cursor, _fpp and pairs in every stream's
+	// entry, surround_export_cursors / _import_cursors)
+	if (m & MTR_METER_SURROUND) surround_sections (e, v);
 	return v;
 }
 
@@ -68,7 +71,8 @@ size_t section_offset (const std::vector<StateSection>& secs, size_t idx, uint32
 	return o;
 }
 
-// STCORR's and NEEDLE's sections are the last ones, in this order
+// STCORR's and NEEDLE's sections are the last ones, in this order; SURROUND's (3 .. 8 channels: never in their engine) is the last one
+size_t surround_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - 1; }
 size_t needle_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - 1; }
 size_t stcorr_section (const mtr_engine* e, const std::vector<StateSection>& secs)
 {
@@ -126,6 +130,7 @@ int mtr_engine_state_export (mtr_engine* e, uint32_t first, uint32_t count, void
 	// the host's cursors, not whatever the device copy holds
 	if (e->cfg.meters & MTR_METER_STCORR) stcorr_export_cursors (e, o0 + section_offset (secs, stcorr_section (e, secs), count), count);
 	if (e->cfg.meters & MTR_METER_NEEDLE) needle_export_cursors (e, o0 + section_offset (secs, needle_section (e, secs), count), count);
+	if (e->cfg.meters & MTR_METER_SURROUND) surround_export_cursors (e, o0 + section_offset (secs, surround_section (e, secs), count), count);
 	h.payload_fnv = fnv1a64 (o0, (size_t) (o - o0));
 	memcpy (blob, &h, sizeof (h));
 	return MTR_OK;
@@ -169,6 +174,12 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		rc = needle_import_cursors (e, i0 + section_offset (secs, needle_section (e, secs), h.count), h.count, fresh, reinterpret_cast<mtr_needle_hdr*> (nd_hdr.data ()));
 		if (rc) return rc;
 	}
+	std::vector<unsigned char> su_hdr (surround_hdr_bytes ());
+	const bool su_take = (e->cfg.meters & MTR_METER_SURROUND) && h.count;
+	if (su_take) {
+		rc = surround_import_cursors (e, i0 + section_offset (secs, surround_section (e, secs), h.count), h.count, fresh, su_hdr.data ());
+		if (rc) return rc;
+	}
 	if (!fresh && (e->pos.frcnt != h.frcnt || e->integr != (h.integr != 0) || e->bank.omega != h.omega || e->pos.dr_scnt != h.dr_scnt))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (fragment phase, integration, bank speed or DR-14 window)");
 	rc = mtr_engine_sync (e);
@@ -187,6 +198,7 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;
 		e->sc.period = sc_period; e->pos.sc_fill = sc_fill;
 		if (nd_take) needle_take_cursors (e, reinterpret_cast<const mtr_needle_hdr*> (nd_hdr.data ()));
+		if (su_take) surround_take_cursors (e, su_hdr.data ());
 		e->plan.valid = false;
 		e->advanced = true;
 	}

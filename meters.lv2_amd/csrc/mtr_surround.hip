@@ -1,0 +1,755 @@
+// mtr_surround.hip — sur_run (src/surmeter.c:115-147: the surround3 .. surround8 plugins) for a batch (gfx950): per stream of C = 3 .. 8
+// channels C x Kmeterdsp::process + read (m, p) (jmeters/kmeterdsp.cc:56-153) and n_pairs = C > 3 ? 4 : 3 x Stcorrdsp::process + read ()
+// (jmeters/stcorrdsp.cc:47-93) on the channel pairs (a [p], b [p]) — from ONE read of the frames.
+//
+// One sur_run is the engine call, or — with a period P, for the reading series — every block of exactly P frames, wherever the calls
+// cut the audio.  A call is cut into PIECES exactly as mtr_stcorr.hip cuts it (mtr_stcorr_scan.h: never across a block boundary, at
+// most `chunk` frames — a multiple of four, so that a block's pieces start on Kmeterdsp's groups of four); one workgroup reduces one
+// (stream, piece), one thread per (stream, channel) and one per (stream, pair) walk the pieces in order and do everything that happens
+// at a block's end.  No atomics; the same bits on every run.
+//
+// A workgroup takes its piece tile by tile (1792 frames = 256 lanes x 7; the tiles are aligned to the piece's END, the first one starts
+// `warm` frames or more in front of it).  The tile's frames — C x 1792 contiguous floats of the stream's row — are loaded ONCE with
+// 16-byte loads on 16-byte addresses of the buffer (the floats in front of the first / behind the last whole quad that lies inside the
+// stream's frames [lo, b1) one by one: an odd C leaves a row only 4-byte aligned, and nothing outside [lo, b1) is ever read) and stored
+// channel-planar in LDS: [C][1792] floats, 57 344 bytes at C = 8.  Everything else reads LDS: lane t owns frames 7 t .. 7 t + 6 of the
+// tile (stride 7 dwords: no bank conflicts).
+//
+//  * K-meters.  Kmeterdsp's end state is linear in the squares s = x^2 (mtr_kmeter.hip): z1 is a one-pole per frame (decay r = 1 - w),
+//    z2 takes 4 w (z1 - z2) at the end of every group of four.  A frame at offset j of its block (group j / 4, slot j mod 4) gives
+//    w r^(E - 1 - j) s to z1 at the piece's end E and w r^(ge - 1 - j) (c_k + 4 w b^k) s to z2 there — ge its group's end, k the group ends
+//    behind it inside the piece, A^k = [[a^k, 0], [c_k, b^k]] as in mtr_kmeter.hip.  Frames at j >= L - L mod 4 (L = P, or the call's
+//    length) weigh nothing and do not enter the maximum (kmeterdsp.cc:71), nor do the warm-up frames in front of the piece.  A lane
+//    takes the three powers of its first frame in the first tile from exp () of logarithms the host computed, steps them through its
+//    seven frames and from tile to tile by constants (no pow () in the loop); the sums are double.  The walk
+//    carries (z1, z2) from piece to piece in closed form — also through a call that ends inside a group — and rounds to f32 where the
+//    reference ends a process ().  A square that is not finite makes the block's z1 NaN in the reference (Inf - Inf at the next frame)
+//    unless it is the block's very last frame: the kernel adds a NaN for it, so the sums become what the reference's would be.
+//  * Correlations.  Per pair exactly k_stcorr_pieces' two passes (the head of mtr_stcorr.hip explains them: the carried zl / zr at
+//    "frame -1", the first stage rebuilt over `warm` frames, what the sums "owe" behind a period end that flushed), on 7-frame runs;
+//    the four pairs walk the staged tile one after the other, and the second pass computes its inputs from the staged samples again
+//    instead of holding them: with the constants every lane would compute alike passed from the host (scalar registers), every pair's
+//    carried first-stage state in LDS and the rare "owes" sums reduced where they arise, the kernel holds 223 .. 248 VGPRs, no
+//    scratch, and two workgroups fit a CU.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mtr_engine_impl.h"
+#include "mtr_stcorr_scan.h"
+
+#define MTR_SUR_MAXCH 8
+#define MTR_SUR_PAIRS 4
+
+/* per (stream, channel): Kmeterdsp (jmeters/kmeterdsp.h).  z1, z2 are doubles: inside a block that a call cut they are the exact
+ * continuation; at a block's end they hold the f32 the reference stores */
+typedef struct mtr_sur_chan {
+	double   z1, z2;
+	float    level, peak;         /* read (m, p): P = 0 _rms (max-held until read) and _peak; P > 0 those after the last completed block */
+	float    tmax;                /* max x^2 of the open block so far */
+	int32_t  cnt, flag;
+	uint32_t pad_;
+} mtr_sur_chan;
+
+/* per (stream, pair): Stcorrdsp (jmeters/stcorrdsp.h) and its last reading */
+typedef struct mtr_sur_pair {
+	float    z[5];                /* zl zr zlr zll zrr */
+	float    corr;
+} mtr_sur_pair;
+
+/* per stream; in front, for the state blob (whose header has no room for them): the engine's period, the frames into the open block,
+ * Kmeterdsp's _fpp / _fall and the pairs — the host's copies rule, export writes them in */
+typedef struct mtr_sur_state {
+	uint32_t     period, fill;
+	uint32_t     fpp;
+	float        fall;
+	uint8_t      pa[MTR_SUR_PAIRS], pb[MTR_SUR_PAIRS];
+	mtr_sur_chan ch[MTR_SUR_MAXCH];
+	mtr_sur_pair pr[MTR_SUR_PAIRS];
+} mtr_sur_state;
+
+#define MTR_SUR_PIECE_PAIR 9       /* doubles per (stream, piece, pair): as MTR_STCORR_PIECE */
+#define MTR_SUR_PIECE (MTR_SUR_PAIRS * MTR_SUR_PIECE_PAIR + 3 * MTR_SUR_MAXCH)   /* ... and per channel: what the piece's frames give to z1 and z2 at its end, max x^2 */
+
+/* the constants of k_sur_pieces, computed once on the host in double (kr = 1 - omega, ka = kr^4, kb = 1 - 4 omega; r = 1 - w1, q = 1 - w2) */
+typedef struct mtr_sur_consts {
+	double lkr, lkb, lq;          /* log kr, log kb, log q */
+	double kri, kai, kbi, kr3;    /* 1 / kr, 1 / ka, 1 / kb, kr^3 */
+	double ca, cb;                /* omega c / (ka - kb), omega (4 omega - c / (ka - kb)): the z2 weight of a frame is kr^(..) (ca ka^k + cb kb^k) */
+	double st1, sta, stb, sq;     /* kr^-TILE, ka^-(TILE / 4), kb^-(TILE / 4), q^-TILE: from tile to tile */
+	double d1, d2, d4, d8, d64;   /* r^K to the powers of the wave scan */
+} mtr_sur_consts;
+
+typedef struct mtr_sur_args {
+	const float*    audio;        /* [S][stride][C] */
+	uint64_t        stride, n_frames;
+	uint64_t        period;       /* frames per sur_run of the reading series; 0: the call is one */
+	uint64_t        e0;           /* call frame at which the block open on entry ends (period 0: n_frames) */
+	uint64_t        block;        /* L: frames per block (the period, or the call's length) */
+	uint32_t        n_streams, n_channels, n_pairs, n_pieces;
+	uint32_t        chunk, warm;
+	float           w1, w2;       /* Stcorrdsp::init */
+	float           omega, fall;  /* Kmeterdsp: 9.72f / fs, the fall-back factor of fpp */
+	uint32_t        fpp;
+	int32_t         hold;
+	double          pw[3];        /* A = [[a, 0], [c, b]] per group of four frames (mtr_kmeter.hip) */
+	mtr_sur_consts  k;            /* what every lane would compute alike: in scalar registers */
+	uint8_t         pa[MTR_SUR_PAIRS], pb[MTR_SUR_PAIRS];
+	uint32_t        capacity;     /* points per stream the series hold */
+	uint64_t        point0;       /* blocks completed before this call */
+	mtr_sur_state*  state;        /* [S] */
+	double*         piece;        /* [S][n_pieces][MTR_SUR_PIECE] */
+	float*          s_level;      /* [S][capacity][C], NULL if capacity == 0 */
+	float*          s_peak;       /* [S][capacity][C] */
+	float*          s_corr;       /* [S][capacity][4] */
+} mtr_sur_args;
+
+namespace {
+
+using namespace mtr_sc;
+
+constexpr int NT = 256;                  // threads per workgroup
+constexpr int K = 7;                     // frames per lane run: an odd dword stride in LDS
+constexpr int TILE = NT * K;             // frames per tile: 1792
+constexpr int MAX_TILES = 8;             // tiles per piece (chunk + warm)
+
+// the call frame at which the block of piece `pc` starts (negative: it started in an earlier call)
+__device__ __forceinline__ int64_t block_start (const mtr_sur_args& a, const Piece& pc)
+{
+	if ((uint64_t) pc.b0 < a.e0) return (int64_t) a.e0 - (int64_t) a.block;
+	return (int64_t) (a.e0 + ((uint64_t) pc.b0 - a.e0) / a.period * a.period);
+}
+
+template <int C>
+__global__ __launch_bounds__ (NT, 2) void k_sur_pieces (const mtr_sur_args a)
+{
+	const uint32_t s = blockIdx.y;
+	const Piece pc = piece_of (a, blockIdx.x);
+	const float* const src = a.audio + (size_t) s * a.stride * C;
+	const int64_t b0 = pc.b0, b1 = pc.b1;
+	const int64_t warm = b0 == 0 ? 1 : (int64_t) a.warm;          // (the call's first piece: only the slot of frame -1)
+	const int nt = (int) ((b1 - b0 + warm + TILE - 1) / TILE);      // <= MAX_TILES: chunk + warm <= MAX_TILES * TILE
+	const int64_t lo = b0 - warm > 0 ? b0 - warm : 0;              // the first frame that is read
+	const int64_t T0 = b1 - (int64_t) nt * TILE;                    // < b0
+	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+
+	__shared__ float lds[C * TILE];
+	__shared__ double sh_tot[NT / 64][2];
+	__shared__ double sh_red[NT / 64][5];
+	__shared__ double sh_zt[MTR_SUR_PAIRS][2];                     // zl, zr of every pair in front of the tile (the first one starts from nothing)
+	__shared__ double sh_owe[NT / 64][MTR_SUR_PAIRS][2];           // per wave: sum c rho zl, sum c rho zr of a piece behind a period end
+	if (tid < 2 * MTR_SUR_PAIRS) sh_zt[tid >> 1][tid & 1] = 0.0;
+	if (tid < 2 * MTR_SUR_PAIRS * (NT / 64)) (&sh_owe[0][0][0])[tid] = 0.0;
+	double* const out = a.piece + ((size_t) s * a.n_pieces + blockIdx.x) * MTR_SUR_PIECE;
+
+	// ---- the K-meters' geometry: block offsets ----
+	const int64_t blk0 = block_start (a, pc);
+	const int64_t Lg = (int64_t) (a.block & ~(uint64_t) 3);        // frames of a block the K-meters take
+	// block offset at which the piece's z1 stands: its end, but never inside the block's dropped trailing frames — a call may end there
+	// (P mod 4 != 0), and Kmeterdsp never runs z1 over them
+	const int64_t E1 = b1 - blk0 < Lg ? b1 - blk0 : Lg;
+	const int64_t pe = E1 & ~(int64_t) 3;                           // ... and its last group end
+	// the powers of the lane's first frame in the first tile — its distance to the piece's end E1 for z1, inside its group and in group
+	// ends behind it for z2 — from exp (); from tile to tile (1792 frames = 448 groups) they move by constants
+	const int64_t jt0 = T0 + (int64_t) K * tid - blk0;
+	const int64_t gt0 = (jt0 | 3) + 1;                             // its group's end
+	int32_t kt = (int32_t) ((pe - gt0) >> 2);                      // group ends behind that one inside the piece; < 0: none
+	double pt1 = (double) a.omega * exp ((double) (E1 - 1 - jt0) * a.k.lkr);
+	double pta = a.k.ca * exp ((double) (4 * kt) * a.k.lkr), ptb = a.k.cb * exp ((double) kt * a.k.lkb);
+	const double pg0 = ipow (1.0 - (double) a.omega, (uint64_t) (gt0 - 1 - jt0));
+	double e1[C], e2[C];
+	float tm[C];
+#pragma unroll
+	for (int c = 0; c < C; ++c) { e1[c] = 0.0; e2[c] = 0.0; tm[c] = 0.f; }
+
+	// ---- the correlations' constants (mtr_stcorr.hip) ----
+	const double w1 = (double) a.w1, r = 1.0 - w1, q1 = 1.0 - (double) a.w2, bias = (double) 1e-20f;
+	ScanPow sp;
+	sp.d1 = a.k.d1; sp.d2 = a.k.d2; sp.d4 = a.k.d4; sp.d8 = a.k.d8;
+	sp.dp = ipow (sp.d1, (lane & 15) + 1);
+	sp.dq = lane >= 32 ? ipow (sp.d1, lane - 31) : 0.0;
+	const double dl = ipow (sp.d1, lane);                          // from the wave's first frame to this lane's run
+	const double d64 = a.k.d64;                                    // ... and over a whole wave
+	// weight of a run's sums at the piece's end: w2 q^(frames behind the run); from tile to tile it grows by q^-TILE
+	double W = (double) a.w2 * exp ((double) ((int64_t) nt * TILE - (int64_t) K * (tid + 1)) * a.k.lq);
+	double tot[MTR_SUR_PAIRS][3];                                  // lr ll rr
+#pragma unroll
+	for (int p = 0; p < MTR_SUR_PAIRS; ++p) tot[p][0] = tot[p][1] = tot[p][2] = 0.0;
+
+	// 16-byte loads on 16-byte addresses: quads of floats from a float of the BUFFER whose index is a multiple of four
+	const int64_t base = (int64_t) ((reinterpret_cast<size_t> (src) >> 2) & 3);
+	const int64_t glo = lo * C, ghi = b1 * C;                      // the floats of the stream's row that may be read
+
+	for (int t = 0; t < nt; ++t) {
+		const int64_t T = T0 + (int64_t) t * TILE;
+		// ---- stage the tile: floats [T C, (T + TILE) C) of the row, channel-planar ----
+		{
+			const int64_t gt = T * C;
+			const int64_t gq0 = gt - ((base + gt) & 3);
+#pragma unroll 2
+			for (int i = tid; i < TILE * C / 4 + 1; i += NT) {
+				const int64_t gq = gq0 + 4 * (int64_t) i;
+				float v[4] = { 0.f, 0.f, 0.f, 0.f };
+				if (gq >= glo && gq + 3 < ghi) {
+					const float4 q = *reinterpret_cast<const float4*> (src + gq);
+					v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+				} else {
+#pragma unroll
+					for (int e = 0; e < 4; ++e) if (gq + e >= glo && gq + e < ghi) v[e] = src[gq + e];
+				}
+#pragma unroll
+				for (int e = 0; e < 4; ++e) {
+					const int64_t li = gq + e - gt;
+					if (li >= 0 && li < (int64_t) TILE * C) {
+						const uint32_t u = (uint32_t) li, fr = u / C, ch = u - fr * C;
+						lds[ch * TILE + fr] = v[e];
+					}
+				}
+			}
+		}
+		__syncthreads ();
+		const bool head = T < b0;                                  // frames in front of the piece: they rebuild zl, zr and weigh nothing
+		const int64_t f0 = T + (int64_t) K * tid;
+
+		// ---- the K-meters: the lane's seven frames of every channel ----
+		if (f0 + K > b0) {                                         // (frames of the piece end at the tile's end)
+			// the lane's powers stepped frame by frame, every channel's square in turn
+			const int64_t j0 = f0 - blk0;
+			int32_t kk = kt;
+			double p1 = pt1, pa = pta, pb = ptb, pg = pg0;           // omega kr^(E1 - 1 - j), ca ka^k, cb kb^k, kr^(ge - 1 - j)
+#pragma unroll
+			for (int k = 0; k < K; ++k) {
+				const int64_t jk = j0 + k;
+				if (f0 + k >= b0 && jk < Lg) {                     // (jk < E1 with it: E1 = min (Lg, b1 - blk0))
+					const double wz1 = p1, wz2 = kk >= 0 ? pg * (pa + pb) : 0.0;
+#pragma unroll
+					for (int c = 0; c < C; ++c) {
+						const float x = lds[c * TILE + tid * K + k];
+						float sq = x * x;
+						tm[c] = tm[c] < sq ? sq : tm[c];               // kmeterdsp.cc:84: if (t < s) t = s (a NaN never enters)
+						if (!isfinite (sq) && !(jk == Lg - 1 && sq == INFINITY)) sq = NAN;   // (see the head of the file)
+						e1[c] = fma (wz1, (double) sq, e1[c]);
+						e2[c] = fma (wz2, (double) sq, e2[c]);
+					}
+				}
+				p1 *= a.k.kri;
+				if (((jk + 1) & 3) == 0) { kk -= 1; pa *= a.k.kai; pb *= a.k.kbi; pg = a.k.kr3; }
+				else pg *= a.k.kri;
+			}
+		}
+		pt1 *= a.k.st1; pta *= a.k.sta; ptb *= a.k.stb; kt -= TILE / 4;
+
+		// ---- the correlations: the pairs one after the other over the staged tile ----
+#pragma unroll
+		for (int p = 0; p < MTR_SUR_PAIRS; ++p) {
+			if (p >= (int) a.n_pairs) break;
+			const float* const la = lds + (uint32_t) a.pa[p] * TILE + tid * K;
+			const float* const lb = lds + (uint32_t) a.pb[p] * TILE + tid * K;
+			double zc[2] = { 0.0, 0.0 };                           // the carried zl, zr: "frame -1" (in the call's first tile alone)
+			if (T < 0) { zc[0] = (double) a.state[s].pr[p].z[0]; zc[1] = (double) a.state[s].pr[p].z[1]; }
+			if (pc.after_period) {                                 // (not finite: the period before is flushed, its zl with it)
+				if (!isfinite (zc[0])) zc[0] = 0.0;
+				if (!isfinite (zc[1])) zc[1] = 0.0;
+			}
+			double* const po = out + p * MTR_SUR_PIECE_PAIR;
+			// the inputs of the one-pole (both passes compute them from the staged samples: fourteen doubles less to hold)
+			auto input = [&] (int k, double& ul, double& ur) {
+				float xa = la[k], xb = lb[k];
+				if (!head) {
+					ul = fma (w1, (double) xa, bias); ur = fma (w1, (double) xb, bias);
+				} else {
+					const int64_t f = f0 + k;
+					if (pc.after_period && f < b0) {
+						if (!isfinite (xa)) xa = 0.f;
+						if (!isfinite (xb)) xb = 0.f;
+					}
+					ul = f >= 0 ? fma (w1, (double) xa, bias) : f == -1 ? zc[0] : 0.0;
+					ur = f >= 0 ? fma (w1, (double) xb, bias) : f == -1 ? zc[1] : 0.0;
+				}
+			};
+			// pass 1: the run's end value from zero
+			double vl = 0.0, vr = 0.0;
+#pragma unroll
+			for (int k = 0; k < K; ++k) {
+				double ul, ur;
+				input (k, ul, ur);
+				vl = fma (r, vl, ul); vr = fma (r, vr, ur);
+			}
+			// the state each run starts from: scan across the wave, then across the waves
+			vl = scan (vl, sp); vr = scan (vr, sp);
+			__syncthreads ();                                      // (the pair before has read sh_tot)
+			if (lane == 63) { sh_tot[wid][0] = vl; sh_tot[wid][1] = vr; }
+			__syncthreads ();
+			double cin[2] = { 0.0, 0.0 }, zt[2] = { sh_zt[p][0], sh_zt[p][1] };
+#pragma unroll
+			for (int w = 0; w < NT / 64; ++w) {
+				if (w == wid) { cin[0] = zt[0]; cin[1] = zt[1]; }
+				zt[0] = fma (d64, zt[0], sh_tot[w][0]); zt[1] = fma (d64, zt[1], sh_tot[w][1]);
+			}
+			__syncthreads ();                                      // (every lane has read the state in front of this tile)
+			if (tid == 0) { sh_zt[p][0] = zt[0]; sh_zt[p][1] = zt[1]; }
+			double zl = fma (dl, cin[0], dppd<0x138, 0xF> (vl));   // (wave_shr:1: the scan of the lane to the left, lane 0 reads 0)
+			double zr = fma (dl, cin[1], dppd<0x138, 0xF> (vr));
+			// pass 2: the products, carried to the run's end
+			const bool owes = pc.after_period && T < b0 + warm;    // uniform
+			double alr = 0.0, all = 0.0, arr = 0.0, abl = 0.0, abr = 0.0;
+			double rho = owes && f0 > b0 ? ipow (r, (uint64_t) (f0 - b0)) : 1.0;
+#pragma unroll
+			for (int k = 0; k < K; ++k) {
+				double ul, ur;
+				input (k, ul, ur);
+				zl = fma (r, zl, ul); zr = fma (r, zr, ur);
+				double plr = zl * zr, pll = zl * zl, prr = zr * zr;
+				if (head && f0 + k < b0) { plr = 0.0; pll = 0.0; prr = 0.0; }
+				alr = fma (alr, q1, plr); all = fma (all, q1, pll); arr = fma (arr, q1, prr);
+				if (owes) {
+					const int64_t f = f0 + k;
+					if (f == b0 - 1) { po[7] = zl; po[8] = zr; }   // the start state itself (one lane of the workgroup)
+					const bool in = f >= b0;
+					if (in) rho *= r;
+					abl = fma (abl, q1, in ? rho * zl : 0.0); abr = fma (abr, q1, in ? rho * zr : 0.0);
+				}
+			}
+			tot[p][0] = fma (W, alr, tot[p][0]); tot[p][1] = fma (W, all, tot[p][1]); tot[p][2] = fma (W, arr, tot[p][2]);
+			if (owes) {                                            // (the first tiles of such a piece alone: summed over the wave at once)
+				abl *= W; abr *= W;
+#pragma unroll
+				for (int d = 32; d >= 1; d >>= 1) { abl += __shfl_xor (abl, d, 64); abr += __shfl_xor (abr, d, 64); }
+				if (lane == 0) { sh_owe[wid][p][0] += abl; sh_owe[wid][p][1] += abr; }
+			}
+		}
+		W *= a.k.sq;
+		__syncthreads ();                                          // (every lane has read its runs: the next tile may overwrite them)
+	}
+
+	// ---- the workgroup's sums: the pairs, then the channels ----
+#pragma unroll
+	for (int p = 0; p < MTR_SUR_PAIRS; ++p) {
+		if (p >= (int) a.n_pairs) break;
+#pragma unroll
+		for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+			for (int j = 0; j < 3; ++j) tot[p][j] += __shfl_xor (tot[p][j], d, 64);
+		__syncthreads ();
+		if (lane == 0) { for (int j = 0; j < 3; ++j) sh_red[wid][j] = tot[p][j]; sh_red[wid][3] = sh_owe[wid][p][0]; sh_red[wid][4] = sh_owe[wid][p][1]; }
+		__syncthreads ();
+		if (tid == 0) {
+			double* const po = out + p * MTR_SUR_PIECE_PAIR;
+			for (int j = 0; j < 5; ++j) {
+				double e = 0.0;
+				for (int w = 0; w < NT / 64; ++w) e += sh_red[w][j];
+				po[j < 3 ? j : j + 2] = e;
+			}
+			po[3] = sh_zt[p][0]; po[4] = sh_zt[p][1];
+		}
+	}
+#pragma unroll
+	for (int c = 0; c < C; ++c) {
+#pragma unroll
+		for (int d = 32; d >= 1; d >>= 1) {
+			e1[c] += __shfl_xor (e1[c], d, 64); e2[c] += __shfl_xor (e2[c], d, 64);
+			tm[c] = fmaxf (tm[c], __shfl_xor (tm[c], d, 64));
+		}
+		__syncthreads ();
+		if (lane == 0) { sh_red[wid][0] = e1[c]; sh_red[wid][1] = e2[c]; sh_red[wid][2] = (double) tm[c]; }
+		__syncthreads ();
+		if (tid == 0) {
+			double x1 = 0.0, x2 = 0.0, xm = 0.0;
+			for (int w = 0; w < NT / 64; ++w) { x1 += sh_red[w][0]; x2 += sh_red[w][1]; xm = fmax (xm, sh_red[w][2]); }
+			double* const co = out + MTR_SUR_PAIRS * MTR_SUR_PIECE_PAIR + 3 * c;
+			co[0] = x1; co[1] = x2; co[2] = xm;
+		}
+	}
+}
+
+// one thread per (stream, channel): the pieces in order, and kmeterdsp.cc:74-75, 101-138 + read (m, p) at every end of a block
+__device__ void final_channel (const mtr_sur_args& a, uint32_t s, uint32_t c)
+{
+#pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
+	mtr_sur_chan* const st = &a.state[s].ch[c];
+	const double kw = (double) a.omega, kr = 1.0 - kw, ka = a.pw[0], kb = a.pw[2];
+	const int64_t Lg = (int64_t) (a.block & ~(uint64_t) 3);
+	double z1 = st->z1, z2 = st->z2;
+	float level = st->level, peak = st->peak, tmax = st->tmax;
+	int32_t cnt = st->cnt, flag = st->flag;
+	uint64_t point = a.point0;
+	for (uint32_t i = 0; i < a.n_pieces; ++i) {
+		const Piece pc = piece_of (a, i);
+		const int64_t blk0 = block_start (a, pc);
+		const int64_t p0 = pc.b0 - blk0, E1 = pc.b1 - blk0 < Lg ? pc.b1 - blk0 : Lg;   // (as the pieces kernel's: z1 stops at Lg)
+		if (p0 == 0) {                                             // :74-75 (a NaN state falls through, as there; it is an f32 here)
+			z1 = z1 > 50 ? 50 : (z1 < 0 ? 0 : z1);
+			z2 = z2 > 50 ? 50 : (z2 < 0 ? 0 : z2);
+			tmax = 0.f;
+		}
+		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_SUR_PIECE + MTR_SUR_PAIRS * MTR_SUR_PIECE_PAIR + 3 * c;
+		if (E1 > p0) {
+			const int64_t m = (E1 >> 2) - (p0 >> 2);               // group ends in (p0, E1]
+			if (m > 0) {
+				const double am = pow (ka, (double) m), bm = pow (kb, (double) m);
+				z2 = bm * z2 + 4.0 * kw * ipow (kr, (uint64_t) (4 - (p0 & 3))) * ((am - bm) / (ka - kb)) * z1 + pv[1];
+			}
+			z1 = pow (kr, (double) (E1 - p0)) * z1 + pv[0];
+		}
+		const float pm = (float) pv[2];
+		tmax = tmax < pm ? pm : tmax;
+		if (!pc.closes) continue;
+		float f1 = (float) z1, f2 = (float) z2, t = tmax;
+		if (isnan (f1)) f1 = 0;                                    // :101-103
+		if (isnan (f2)) f2 = 0;
+		if (!isfinite (t)) t = 0;
+		z1 = (double) (f1 + 1e-20f);                      // :106-107
+		z2 = (double) (f2 + 1e-20f);
+		const float rms = sqrtf (2.0f * f2);
+		t = sqrtf (t);
+		if (a.period || flag) { level = rms; flag = 0; }           // :112-121 (a host that reads after every block always finds the flag set)
+		else if (rms > level) level = rms;
+		if (t >= peak) { peak = t; cnt = a.hold; }                 // :124-139
+		else if (cnt > 0) cnt -= (int32_t) a.fpp;
+		else { peak *= a.fall; peak += 1e-10f; }
+		if (a.period) {
+			if (point < a.capacity) {
+				const size_t o = ((size_t) s * a.capacity + point) * a.n_channels + c;
+				a.s_level[o] = level; a.s_peak[o] = peak;
+			}
+			++point;
+		}
+	}
+	st->z1 = z1; st->z2 = z2; st->level = level; st->peak = peak; st->tmax = tmax; st->cnt = cnt; st->flag = flag;
+}
+
+// one thread per (stream, pair): k_stcorr_final
+__device__ void final_pair (const mtr_sur_args& a, uint32_t s, uint32_t p)
+{
+#pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
+	mtr_sur_pair* const st = &a.state[s].pr[p];
+	const double q1 = 1.0 - (double) a.w2;
+	double z[3] = { (double) st->z[2], (double) st->z[3], (double) st->z[4] };
+	float zl = st->z[0], zr = st->z[1], corr = st->corr;
+	uint64_t point = a.point0;
+	int64_t len_of = -1;
+	double qp = 1.0;
+	bool flushed[2] = { false, false };
+	for (uint32_t i = 0; i < a.n_pieces; ++i) {
+		const Piece pc = piece_of (a, i);
+		const int64_t len = pc.b1 - pc.b0;
+		if (len != len_of) { qp = pow (q1, (double) len); len_of = len; }
+		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_SUR_PIECE + p * MTR_SUR_PIECE_PAIR;
+		double sum[3] = { pv[0], pv[1], pv[2] }, el = pv[3], er = pv[4];
+		if (pc.after_period && (flushed[0] || flushed[1])) {
+			// the period before left zl (zr) = 0 where the piece started from pv[7] (pv[8]): with rho = r^(frames since), zl' = zl + rho dl
+			const double dl = flushed[0] ? -pv[7] : 0.0, dr = flushed[1] ? -pv[8] : 0.0;
+			const double r = 1.0 - (double) a.w1, r2 = r * r;
+			double cq = 0.0, rr = 1.0;                             // sum c rho^2 = w2 sum_m q^(len - m) r^(2m), m = 1 .. len
+			for (int64_t m = 1; m <= len && rr > 1e-300; ++m) { rr *= r2; cq += ipow (q1, (uint64_t) (len - m)) * rr; }
+			cq *= (double) a.w2;
+			sum[0] += dr * pv[5] + dl * pv[6] + dl * dr * cq;
+			sum[1] += 2.0 * dl * pv[5] + dl * dl * cq;
+			sum[2] += 2.0 * dr * pv[6] + dr * dr * cq;
+			const double re = ipow (r, (uint64_t) len);
+			el += re * dl; er += re * dr;
+		}
+		if (pc.after_period) flushed[0] = flushed[1] = false;
+		for (int j = 0; j < 3; ++j) z[j] = fma (qp, z[j], sum[j]);
+		const bool last = i + 1 == a.n_pieces;
+		if (last) { zl = (float) el; zr = (float) er; }
+		if (!pc.closes) continue;
+		float f[3] = { (float) z[0], (float) z[1], (float) z[2] };
+		flushed[0] = !isfinite (f[1]); flushed[1] = !isfinite (f[2]);  // this period leaves zl (zr) = 0 to the next
+		if (last && (!isfinite (zl) || !isfinite (f[1]))) zl = 0.f;    // stcorrdsp.cc:65-66
+		if (last && (!isfinite (zr) || !isfinite (f[2]))) zr = 0.f;
+		for (int j = 0; j < 3; ++j) {
+			if (!isfinite (f[j])) f[j] = 0.f;                      // :67-69
+			f[j] = f[j] + 1e-10f;                       // :73-75
+			z[j] = (double) f[j];
+		}
+		corr = f[0] / sqrtf (f[1] * f[2] + 1e-10f);   // :81
+		if (a.period) {
+			if (point < a.capacity) a.s_corr[((size_t) s * a.capacity + point) * MTR_SUR_PAIRS + p] = corr;
+			++point;
+		}
+	}
+	st->z[0] = zl; st->z[1] = zr;
+	for (int j = 0; j < 3; ++j) st->z[2 + j] = (float) z[j];
+	st->corr = corr;
+}
+
+__global__ void k_sur_final (const mtr_sur_args a)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, per = a.n_channels + a.n_pairs;
+	if (i >= a.n_streams * per) return;
+	const uint32_t s = i / per, u = i % per;
+	if (u < a.n_channels) final_channel (a, s, u);
+	else final_pair (a, s, u - a.n_channels);
+}
+
+}  // namespace
+
+static void mtr_sur_geometry (float w1, uint32_t* warm, uint32_t* chunk)
+{
+	// |1 - w1|^J < 2^-48, as mtr_stcorr_geometry; the chunk a multiple of four frames (Kmeterdsp's groups)
+	const double ar = fabs (1.0 - (double) w1);
+	double J = ar > 0.0 && ar < 1.0 ? ceil (-48.0 * log (2.0) / log (ar)) : 1.0;
+	const double most = (double) (MAX_TILES / 2 * TILE);
+	if (!(J >= 1.0)) J = 1.0;
+	if (J > most) J = most;
+	*warm = ((uint32_t) J + K) / K * K;                            // (+ the slot of frame -1)
+	*chunk = (MAX_TILES * TILE - *warm) & ~3u;
+}
+
+static int mtr_launch_sur (const mtr_sur_args& a, void* stream)
+{
+	hipStream_t st = (hipStream_t) stream;
+	const dim3 g (a.n_pieces, a.n_streams), b (NT);
+	switch (a.n_channels) {
+	case 3: hipLaunchKernelGGL (k_sur_pieces<3>, g, b, 0, st, a); break;
+	case 4: hipLaunchKernelGGL (k_sur_pieces<4>, g, b, 0, st, a); break;
+	case 5: hipLaunchKernelGGL (k_sur_pieces<5>, g, b, 0, st, a); break;
+	case 6: hipLaunchKernelGGL (k_sur_pieces<6>, g, b, 0, st, a); break;
+	case 7: hipLaunchKernelGGL (k_sur_pieces<7>, g, b, 0, st, a); break;
+	case 8: hipLaunchKernelGGL (k_sur_pieces<8>, g, b, 0, st, a); break;
+	default: return -1;
+	}
+	const uint32_t n = a.n_streams * (a.n_channels + a.n_pairs);
+	hipLaunchKernelGGL (k_sur_final, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// ---- SURROUND in the engine: set-up, the call's step, the blob's section and the cursors in it, the C entry points --------------------
+
+static uint32_t sur_pairs (const mtr_engine* e) { return e->cfg.n_channels > 3 ? 4u : 3u; }
+
+void surround_create (mtr_engine* e)
+{
+	const uint32_t C = e->cfg.n_channels;
+	mtr_setup_stcorr (e->cfg.sample_rate, e->su.w);
+	mtr_sur_geometry (e->su.w[0], &e->su.warm, &e->su.chunk);
+	const double w = (double) (9.72f / e->cfg.sample_rate);        // kmeterdsp.cc:53; A as mtr_kmeter.hip
+	const double a1 = pow (1.0 - w, 4.0);
+	e->su.pw[0] = a1; e->su.pw[1] = 4.0 * w * a1; e->su.pw[2] = 1.0 - 4.0 * w;
+	{
+		static_assert (sizeof (mtr_sur_consts) == sizeof (e->su.k), "mtr_sur_consts");
+		mtr_sur_consts k;
+		const double kr = 1.0 - w, ka = a1, kb = e->su.pw[2], cab = e->su.pw[1] / (ka - kb);
+		const double r = 1.0 - (double) e->su.w[0], q = 1.0 - (double) e->su.w[1];
+		k.lkr = log (kr); k.lkb = log (kb); k.lq = log (q);
+		k.kri = 1.0 / kr; k.kai = 1.0 / ka; k.kbi = 1.0 / kb; k.kr3 = kr * kr * kr;
+		k.ca = w * cab; k.cb = w * (4.0 * w - cab);
+		k.st1 = pow (kr, (double) -TILE); k.sta = pow (ka, (double) (-TILE / 4)); k.stb = pow (kb, (double) (-TILE / 4)); k.sq = pow (q, (double) -TILE);
+		k.d1 = ipow (r, K); k.d2 = k.d1 * k.d1; k.d4 = k.d2 * k.d2; k.d8 = k.d4 * k.d4; k.d64 = ipow (k.d8, 8);
+		memcpy (e->su.k, &k, sizeof (k));
+	}
+	for (uint32_t p = 0; p < MTR_SUR_PAIRS; ++p) {                 // the surround8 port defaults (lv2ttl/surmeter.h), clamped
+		e->su.pa[p] = (uint8_t) std::min (2 * p, C - 1); e->su.pb[p] = (uint8_t) std::min (2 * p + 1, C - 1);
+	}
+}
+
+// The blocks of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+int surround_step (mtr_engine* e, const Call& c, Cursors& nx)
+{
+	const size_t vo = c.off;
+	const uint64_t P = e->su.period;
+	mtr_sur_args sa;
+	memset (&sa, 0, sizeof (sa));
+	sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
+	sa.period = P; sa.e0 = P ? P - e->pos.su_fill : c.n_frames;
+	sa.block = P ? P : c.n_frames;
+	sa.n_streams = c.cnt; sa.n_channels = e->cfg.n_channels; sa.n_pairs = sur_pairs (e);
+	sa.chunk = e->su.chunk; sa.warm = e->su.warm;
+	sa.n_pieces = mtr_sc::n_pieces (c.n_frames, sa.e0, P, sa.chunk);
+	sa.w1 = e->su.w[0]; sa.w2 = e->su.w[1];
+	const uint32_t fpp = P ? (uint32_t) P : (uint32_t) c.n_frames;
+	if (nx.su_fpp != fpp) {                                        // kmeterdsp.cc:65-70
+		nx.su_fall = powf (10.0f, -0.05f * 15.0f * ((float) fpp / e->cfg.sample_rate));
+		nx.su_fpp = fpp;
+	}
+	sa.fpp = nx.su_fpp; sa.fall = nx.su_fall;
+	sa.hold = (int32_t) (0.5f * e->cfg.sample_rate + 0.5f);        // :52
+	sa.omega = 9.72f / e->cfg.sample_rate;
+	memcpy (sa.pw, e->su.pw, sizeof (sa.pw));
+	memcpy (&sa.k, e->su.k, sizeof (sa.k));
+	memcpy (sa.pa, e->su.pa, sizeof (sa.pa)); memcpy (sa.pb, e->su.pb, sizeof (sa.pb));
+	sa.capacity = e->su.cap; sa.point0 = e->pos.su_points;
+	if (e->su.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_SUR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND pieces");
+	sa.state = e->su.state.p + vo; sa.piece = e->su.piece.p + vo * sa.n_pieces * MTR_SUR_PIECE;
+	if (e->su.cap) {
+		sa.s_level = e->su.s_level.p + vo * e->su.cap * sa.n_channels;
+		sa.s_peak = e->su.s_peak.p + vo * e->su.cap * sa.n_channels;
+		sa.s_corr = e->su.s_corr.p + vo * e->su.cap * MTR_SUR_PAIRS;
+	}
+	if (mtr_launch_sur (sa, c.st)) return fail (MTR_ERR_HIP, "k_sur launch");
+	const uint64_t tot = e->pos.su_fill + c.n_frames;
+	nx.su_fill = P ? tot % P : 0;
+	nx.su_points = e->pos.su_points + (P ? tot / P : 0);
+	return MTR_OK;
+}
+
+void surround_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	v.push_back ({ e->su.state.p, sizeof (mtr_sur_state) });
+}
+
+void surround_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
+{
+	for (uint32_t k = 0; k < count; ++k) {
+		unsigned char* const at = sec + (size_t) k * sizeof (mtr_sur_state);
+		mtr_sur_state h;
+		memcpy (&h, at, offsetof (mtr_sur_state, ch));
+		h.period = e->su.period; h.fill = (uint32_t) e->pos.su_fill; h.fpp = e->pos.su_fpp; h.fall = e->pos.su_fall;
+		memcpy (h.pa, e->su.pa, sizeof (h.pa)); memcpy (h.pb, e->su.pb, sizeof (h.pb));
+		memcpy (at, &h, offsetof (mtr_sur_state, ch));
+	}
+}
+
+// checks the entries (MTR_ERR_STATE if they are corrupt or — `fresh` false — not where the engine stands); a fresh engine takes them
+int surround_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, unsigned char* out)
+{
+	const size_t hb = offsetof (mtr_sur_state, ch);
+	const uint32_t C = e->cfg.n_channels;
+	mtr_sur_state h0;
+	memset (&h0, 0, sizeof (h0));
+	for (uint32_t k = 0; k < count; ++k) {
+		mtr_sur_state h;
+		memcpy (&h, sec + (size_t) k * sizeof (mtr_sur_state), hb);
+		if (k == 0) memcpy (&h0, &h, hb);
+		bool ok = memcmp (&h, &h0, hb) == 0 && (h.period ? h.fill < h.period && h.period >= (uint32_t) e->cfg.sample_rate / 20 && h.period < 0x7fffffffu : h.fill == 0);
+		for (int p = 0; p < MTR_SUR_PAIRS; ++p) ok = ok && h.pa[p] < C && h.pb[p] < C;
+		if (!ok) return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (period or pairs of the SURROUND meter)");
+	}
+	if (!fresh && (h0.period != e->su.period || h0.fill != e->pos.su_fill || memcmp (h0.pa, e->su.pa, sizeof (h0.pa)) || memcmp (h0.pb, e->su.pb, sizeof (h0.pb))))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period or pairs of the SURROUND meter)");
+	memcpy (out, &h0, hb);
+	return MTR_OK;
+}
+
+size_t surround_hdr_bytes (void) { return offsetof (mtr_sur_state, ch); }
+
+void surround_take_cursors (mtr_engine* e, const unsigned char* hdr)
+{
+	mtr_sur_state h;
+	memcpy (&h, hdr, offsetof (mtr_sur_state, ch));
+	e->su.period = h.period; e->pos.su_fill = h.fill; e->pos.su_fpp = h.fpp; e->pos.su_fall = h.fall;
+	memcpy (e->su.pa, h.pa, sizeof (h.pa)); memcpy (e->su.pb, h.pb, sizeof (h.pb));
+}
+
+extern "C" {
+
+static int no_sur (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_SURROUND); }
+static const char* const NO_SUR = "no SURROUND in this engine";
+
+int mtr_engine_surround_reset (mtr_engine* e)
+{
+	if (no_sur (e)) return fail (MTR_ERR_ARG, NO_SUR);
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t S = e->cfg.n_streams;
+	if (e->su.state.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND state");
+	HIPCHK (hipStreamSynchronize (e->last_stream));
+	HIPCHK (hipMemset (e->su.state.p, 0, S * sizeof (mtr_sur_state)));   // kmeterdsp.cc:33-40, stcorrdsp.cc:33-36
+	e->pos.su_fill = 0;
+	e->pos.su_points = 0;
+	e->pos.su_fpp = 0;
+	e->pos.su_fall = 0.f;
+	return MTR_OK;
+}
+
+int mtr_engine_surround_set_pairs (mtr_engine* e, const uint8_t* a4, const uint8_t* b4)
+{
+	if (no_sur (e) || !a4 || !b4) return fail (MTR_ERR_ARG, e && (e->cfg.meters & MTR_METER_SURROUND) ? "mtr_engine_surround_set_pairs: null argument" : NO_SUR);
+	if (e->su.period && e->pos.su_fill) return fail (MTR_ERR_STATE, "mtr_engine_surround_set_pairs: a block of the reading series is open");
+	const uint8_t top = (uint8_t) (e->cfg.n_channels - 1);
+	for (int p = 0; p < MTR_SUR_PAIRS; ++p) {                      // surmeter.c:124-125
+		e->su.pa[p] = std::min (a4[p], top); e->su.pb[p] = std::min (b4[p], top);
+	}
+	return MTR_OK;
+}
+
+int mtr_engine_surround_pairs (const mtr_engine* e, uint8_t* a4, uint8_t* b4)
+{
+	if (no_sur (e)) return fail (MTR_ERR_ARG, NO_SUR);
+	if (a4) memcpy (a4, e->su.pa, MTR_SUR_PAIRS);
+	if (b4) memcpy (b4, e->su.pb, MTR_SUR_PAIRS);
+	return MTR_OK;
+}
+
+int mtr_engine_surround_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
+{
+	if (no_sur (e)) return fail (MTR_ERR_ARG, NO_SUR);
+	if (period_frames && (period_frames < (uint32_t) e->cfg.sample_rate / 20 || period_frames >= 0x7fffffffu))
+		return fail (MTR_ERR_ARG, "mtr_engine_surround_set_period: a period is 0 or at least (uint32_t) sample_rate / 20 frames");
+	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_surround_set_period: only on an engine that has processed nothing since create / reset");
+	{ const int rc = wait_stream (e); if (rc) return rc; }
+	const size_t n = (size_t) e->cfg.n_streams * capacity_points, C = e->cfg.n_channels;
+	if (n && (e->su.s_level.reserve (n * C) || e->su.s_peak.reserve (n * C) || e->su.s_corr.reserve (n * MTR_SUR_PAIRS))) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND series");
+	if (n) {
+		HIPCHK (hipMemset (e->su.s_level.p, 0, n * C * sizeof (float)));
+		HIPCHK (hipMemset (e->su.s_peak.p, 0, n * C * sizeof (float)));
+		HIPCHK (hipMemset (e->su.s_corr.p, 0, n * MTR_SUR_PAIRS * sizeof (float)));
+	}
+	e->su.period = period_frames;
+	e->su.cap = capacity_points;
+	return mtr_engine_surround_reset (e);
+}
+
+static int sur_states (mtr_engine* e, uint32_t first, uint32_t count, std::vector<mtr_sur_state>& h)
+{
+	int rc = meter_range (e, !no_sur (e), NO_SUR, first, count);
+	if (rc || (rc = wait_stream (e))) return rc;
+	h.resize (count);
+	if (count) HIPCHK (hipMemcpy (h.data (), e->su.state.p + first, count * sizeof (mtr_sur_state), hipMemcpyDeviceToHost));
+	return MTR_OK;
+}
+
+int mtr_engine_surround_read (mtr_engine* e, uint32_t first, uint32_t count, float* level, float* peak, float* corr)
+{
+	std::vector<mtr_sur_state> h;
+	const int rc = sur_states (e, first, count, h);
+	if (rc) return rc;
+	const uint32_t C = e->cfg.n_channels;
+	for (uint32_t i = 0; i < count; ++i) {
+		for (uint32_t c = 0; c < C; ++c) {
+			if (level) level[(size_t) i * C + c] = h[i].ch[c].level;
+			if (peak) peak[(size_t) i * C + c] = h[i].ch[c].peak;
+			h[i].ch[c].flag = 1;
+		}
+		if (corr) for (int p = 0; p < MTR_SUR_PAIRS; ++p) corr[(size_t) i * MTR_SUR_PAIRS + p] = h[i].pr[p].corr;
+	}
+	// (P = 0: Kmeterdsp::read arms the next process () to restart the rms maximum, kmeterdsp.cc:154)
+	if (!e->su.period && count) HIPCHK (hipMemcpy (e->su.state.p + first, h.data (), count * sizeof (mtr_sur_state), hipMemcpyHostToDevice));
+	return MTR_OK;
+}
+
+int mtr_engine_surround_pair_states (mtr_engine* e, uint32_t first, uint32_t count, float* state5)
+{
+	if (!state5) return fail (MTR_ERR_ARG, "mtr_engine_surround_pair_states: null argument");
+	std::vector<mtr_sur_state> h;
+	const int rc = sur_states (e, first, count, h);
+	if (rc) return rc;
+	for (uint32_t i = 0; i < count; ++i)
+		for (int p = 0; p < MTR_SUR_PAIRS; ++p) memcpy (state5 + ((size_t) i * MTR_SUR_PAIRS + p) * 5, h[i].pr[p].z, sizeof (h[i].pr[p].z));
+	return MTR_OK;
+}
+
+int mtr_engine_surround_series (mtr_engine* e, uint32_t first, uint32_t count, float* level, float* peak, float* corr,
+                                uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_sur (e), NO_SUR, first, count);
+	if (rc) return rc;
+	const uint64_t n = e->pos.su_points, kept = std::min<uint64_t> (n, e->su.cap);
+	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
+	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
+	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	if ((!level && !peak && !corr) || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	const size_t C = e->cfg.n_channels;
+	const struct { float* out; const float* src; size_t w; } row[3] = { { level, e->su.s_level.p, C }, { peak, e->su.s_peak.p, C }, { corr, e->su.s_corr.p, MTR_SUR_PAIRS } };
+	for (const auto& q : row)
+		if (q.out) HIPCHK (hipMemcpy2D (q.out, (size_t) capacity * q.w * sizeof (float), q.src + (size_t) first * e->su.cap * q.w, (size_t) e->su.cap * q.w * sizeof (float),
+		                                take * q.w * sizeof (float), count, hipMemcpyDeviceToHost));
+	return MTR_OK;
+}
+
+} // extern "C"

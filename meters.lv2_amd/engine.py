@@ -15,6 +15,7 @@ METER_EBU, METER_TRUEPEAK, METER_SPECTR30, METER_TPBALLIST = 0x01, 0x02, 0x04, 0
 METER_BITSTATS, METER_SIGDIST, METER_DR14, METER_KMETER = 0x10, 0x20, 0x40, 0x80
 METER_STCORR = 0x200                       # (0x100 is no meter)
 METER_NEEDLE = 0x800                       # VU, IEC I / II PPM, M/S PPM: include/mtr_needle.h (0x400 is no meter either)
+METER_SURROUND = 0x2000                    # sur_run: C K-meters + four pair correlations, 3 .. 8 channels: include/mtr_surround.h (0x1000 is no meter)
 NEEDLE_VU, NEEDLE_IEC1, NEEDLE_IEC2, NEEDLE_MS = 1, 2, 4, 8
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
@@ -159,6 +160,14 @@ def _load():
         L.mtr_engine_needle_read.argtypes = [vp, u32, u32, u32, vp, vp]
         L.mtr_engine_needle_series.argtypes = [vp, u32, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_needle_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_surround_read"):                 # (an addition inside ABI version 2: the surround meter)
+        L.mtr_engine_surround_set_pairs.argtypes = [vp, vp, vp]
+        L.mtr_engine_surround_pairs.argtypes = [vp, vp, vp]
+        L.mtr_engine_surround_set_period.argtypes = [vp, u32, u32]
+        L.mtr_engine_surround_read.argtypes = [vp, u32, u32, vp, vp, vp]
+        L.mtr_engine_surround_pair_states.argtypes = [vp, u32, u32, vp]
+        L.mtr_engine_surround_series.argtypes = [vp, u32, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_surround_reset.argtypes = [vp]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -724,6 +733,60 @@ class Engine:
 
     def needle_reset(self):
         _check(lib.mtr_engine_needle_reset(self._h), "needle_reset")
+
+    def surround_set_pairs(self, a, b):
+        """The four correlation pairs' channels (the plugin's cor?A / cor?B ports): entries >= n_channels are clamped; from the next
+        process call on.  With a period only where no block is open."""
+        a, b = np.ascontiguousarray(a, np.uint8), np.ascontiguousarray(b, np.uint8)
+        if a.shape != (4,) or b.shape != (4,):
+            raise ValueError(f"pairs: four channels each, not {a.shape} / {b.shape}")
+        _check(lib.mtr_engine_surround_set_pairs(self._h, a.ctypes.data, b.ctypes.data), "surround_set_pairs")
+
+    def surround_pairs(self):
+        """(a, b): two tuples of four channels, as clamped."""
+        a, b = np.zeros(4, np.uint8), np.zeros(4, np.uint8)
+        _check(lib.mtr_engine_surround_pairs(self._h, a.ctypes.data, b.ctypes.data), "surround_pairs")
+        return tuple(int(v) for v in a), tuple(int(v) for v in b)
+
+    def surround_set_period(self, period_frames, capacity_points=0):
+        """0: every call is one sur_run; P > 0: blocks of exactly P frames wherever the calls cut the audio, every port read after each and
+        appended to a series of `capacity_points` per stream.  Only before the first process call since create / reset."""
+        _check(lib.mtr_engine_surround_set_period(self._h, int(period_frames), int(capacity_points)), "surround_set_period")
+
+    def surround_read(self, first=0, count=None):
+        """(level [count, C], peak [count, C], corr [count, 4]): the ports after the most recent call (period 0; arms a new rms
+        maximum) or the last completed block."""
+        count = self.n_streams - first if count is None else count
+        level = np.zeros((count, self.n_channels), np.float32)
+        peak = np.zeros((count, self.n_channels), np.float32)
+        corr = np.zeros((count, 4), np.float32)
+        _check(lib.mtr_engine_surround_read(self._h, first, count, level.ctypes.data, peak.ctypes.data, corr.ctypes.data), "surround_read")
+        return level, peak, corr
+
+    def surround_pair_states(self, first=0, count=None):
+        """[count, 4, 5]: zl zr zlr zll zrr of every pair as they stand."""
+        count = self.n_streams - first if count is None else count
+        st = np.zeros((count, 4, 5), np.float32)
+        _check(lib.mtr_engine_surround_pair_states(self._h, first, count, st.ctypes.data), "surround_pair_states")
+        return st
+
+    def surround_series(self, first=0, count=None):
+        """(level [count, kept, C], peak [count, kept, C], corr [count, kept, 4], n_points, dropped): the ports after every completed
+        block since reset that the series holds."""
+        count = self.n_streams - first if count is None else count
+        n, d = C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_surround_series(self._h, first, count, None, None, None, 0, C.byref(n), C.byref(d)), "surround_series")
+        kept = n.value - d.value
+        cap = max(kept, 1)
+        level = np.zeros((count, cap, self.n_channels), np.float32)
+        peak = np.zeros((count, cap, self.n_channels), np.float32)
+        corr = np.zeros((count, cap, 4), np.float32)
+        _check(lib.mtr_engine_surround_series(self._h, first, count, level.ctypes.data, peak.ctypes.data, corr.ctypes.data, cap,
+                                              C.byref(n), C.byref(d)), "surround_series")
+        return level[:, :kept], peak[:, :kept], corr[:, :kept], n.value, d.value
+
+    def surround_reset(self):
+        _check(lib.mtr_engine_surround_reset(self._h), "surround_reset")
 
     def _need_loudlog(self):
         if not hasattr(lib, "mtr_engine_loudlog_series"):
