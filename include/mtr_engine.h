@@ -30,7 +30,7 @@ extern "C" {
  *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host; MTR_METER_STCORR, mtr_stcorr_coef,
  *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset; mtr_engine_loudlog_set_period, _loudlog_period,
  *    _loudlog_series, _loudlog_reset; MTR_METER_NEEDLE, mtr_needle_coef, mtr_engine_needle_configure, _needle_set_gain, _needle_read,
- *    _needle_series, _needle_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -188,6 +188,9 @@ int  mtr_engine_process_device_lengths (mtr_engine* e, const float* d_audio, uin
                                         uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);
 int  mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames,
                                       uint64_t stream_stride_frames, const uint64_t* frames);
+/* Track lengths — the same call for the meters whose answer is one per track (DR14, KMETER, BITSTATS, SIGDIST beside EBU / TRUEPEAK):
+ * mtr_engine_process_device_tracks / _host_tracks, declared in mtr_tracks.h */
+#include "mtr_tracks.h"
 /* Frames metered per stream since create / reset, and whether it is closed (either pointer may be NULL): [count] each.
  * (What the process calls queued so far: no synchronisation.  mtr_engine_state_import restarts the count of the streams it writes
  * at 0: a blob carries no frame count.) */

@@ -104,9 +104,20 @@ struct VCount {
 	}
 };
 
-__global__ __launch_bounds__ (256) void k_bitstats (const float* audio, uint64_t stride, uint64_t n_frames,
-                                                    mtr_bitstats_state* out, uint32_t n_streams)
+// LEN: the call carries per-stream ends (`ends`, call-relative: mtr_engine_process_*_tracks, or any call once a stream of its view is
+// closed).  The stream's own end takes the place of n_frames everywhere below — blocks, the wide / guarded split of `stage`, the
+// padding count — and is workgroup-uniform: one scalar load, every branch on it wave-uniform.  End 0 (a closed stream, frames[s] == 0):
+// the workgroup returns before it touches memory, the state keeps every bit.  An end moves the last block into the guarded path, never
+// the alignment of a block's start: the LDS-DMA path is the dense one's.  The dense instantiation is the kernel as it always was.
+template <bool LEN>
+__global__ __launch_bounds__ (256) void k_bitstats (const float* audio, uint64_t stride, uint64_t n_frames_call,
+                                                    mtr_bitstats_state* out, uint32_t n_streams, const uint32_t* ends)
 {
+	uint64_t n_frames = n_frames_call;
+	if constexpr (LEN) {
+		n_frames = ends[blockIdx.x];
+		if (n_frames == 0) return;
+	}
 	__shared__ uint4 ring[4][RING][256];   // per wave: RING blocks of 1024 samples, filled by LDS-DMA
 	__shared__ int32_t Oh[288];            // ones by position p = e + k (implicit one of a normal at k = 23)
 	__shared__ int32_t Eh[256];            // samples by (effective) exponent
@@ -386,8 +397,9 @@ __global__ __launch_bounds__ (256) void k_bitstats (const float* audio, uint64_t
 }  // namespace
 
 int mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
-                         uint32_t n_streams, void* stream)
+                         uint32_t n_streams, const uint32_t* ends, void* stream)
 {
-	hipLaunchKernelGGL (k_bitstats, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams);
+	if (ends) hipLaunchKernelGGL (k_bitstats<true>, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams, ends);
+	else      hipLaunchKernelGGL (k_bitstats<false>, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams, ends);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }

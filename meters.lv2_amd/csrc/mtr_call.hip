@@ -1,5 +1,5 @@
 // mtr_call.hip — one process call: every process entry point of the C ABI (device or host memory, f32 or integer PCM, frame layouts,
-// per-stream lengths, the LV2 block path) ends in process_call, which turns the call into a tiling plan (mtr_plan.cpp: tiles never
+// per-stream lengths and track lengths, the LV2 block path) ends in process_call, which turns the call into a tiling plan (mtr_plan.cpp: tiles never
 // cross 50 ms fragment boundaries; time segments give the fused kernel enough independent waves when the batch is small) and queues
 // the kernels on the caller's stream, in the order CallRun::run spells out.
 #include <hip/hip_runtime.h>
@@ -93,7 +93,7 @@ static hipEvent_t next_event (std::vector<Event>& ev, size_t idx)
 
 // Where a call goes (pure apart from reading the engine)
 struct Route {
-	bool    ragged = false;       // per-stream lengths: the LEN instantiations of the kernels; every other call the dense ones
+	bool    ragged = false;       // per-stream lengths: the LEN instantiations of the kernels (side meters included); every other call the dense ones
 	bool    defer = false;        // the tail (k_gate; the job's reduction if mtr_engine_reduce follows) on the side stream
 	SegPlan sp;                   // the whole fragments through k_seg?
 };
@@ -161,6 +161,7 @@ struct CallRun {
 	const uint32_t* d_ends = nullptr;
 	const uint32_t* d_lim = nullptr;
 	const uint32_t* d_from = nullptr;
+	const float*    d_fall = nullptr;  // KMETER: the fall-back factor of each stream that ends inside the call
 	bool         any_from = false;     // k_seg left a closing stream's last peaks to k_kwtp16
 	LenSlot*     ls = nullptr;
 	int          tb = 0;               // tile_power buffer of the call
@@ -209,10 +210,10 @@ struct CallRun {
 	Route route () const
 	{
 		Route o;
-		if (!ebu && !tp) return o;
 		// Per-stream lengths: a call with them, or any call once a stream of this view is closed (its end is then 0: untouched).
 		o.ragged = c.frames != nullptr;
 		for (uint32_t i = 0; !o.ragged && e->n_closed && i < c.cnt; ++i) o.ragged = e->closed[c.off + i] != 0;
+		if (!ebu && !tp) return o;
 		const PlanCtx pctx = plan_ctx (e);
 		o.sp = seg_plan (&pctx, c.audio, c.n_frames);
 		// (k_seg hands the peak of a closing stream's last segments to k_kwtp16, whose tiles hold at most 64 x 38 frames: a whole
@@ -230,22 +231,29 @@ struct CallRun {
 		return o;
 	}
 
-	// [ends S | frag_lim S | from_tile S] of a ragged call into the next slot of the lengths ring, uploaded on the call's stream
+	// [ends S | frag_lim S | from_tile S | km_fall S] of a ragged call into the next slot of the lengths ring, uploaded on the call's stream
+	// (an engine without EBU / TRUEPEAK has no plan: its frag_lim / from_tile are never read; km_fall: KMETER engines only)
 	int upload_lengths ()
 	{
 		const SegPlan& sp = r.sp;
 		const uint32_t S = c.cnt;
+		const bool fused = ebu || tp, km = e->cfg.meters & MTR_METER_KMETER;
+		const size_t words = (size_t) (km ? 4 : 3) * S;
 		const int slot = (e->len_cur + 1) % LEN_SLOTS;
 		ls = &e->len_slot[slot];
 		for (int i = 0; i < 2; ++i) if (ls->pending[i]) { HIPCHK (hipEventSynchronize (ls->done[i].v)); ls->pending[i] = false; }
 		for (int i = 0; i < 2; ++i) HIPCHK (ls->done[i].ensure ());
-		if (ls->dev.reserve ((size_t) 3 * S) || ls->pin.reserve ((size_t) 3 * S)) return fail (MTR_ERR_NOMEM, "per-stream lengths");
+		if (ls->dev.reserve (words) || ls->pin.reserve (words)) return fail (MTR_ERR_NOMEM, "per-stream lengths");
 		uint32_t* const h_end = ls->pin.p;
 		uint32_t* const h_lim = h_end + S;
 		uint32_t* const h_from = h_end + 2 * (size_t) S;
+		float* const h_fall = reinterpret_cast<float*> (h_end + 3 * (size_t) S);
 		for (uint32_t i = 0; i < S; ++i) {
 			const uint64_t f = e->closed[c.off + i] ? 0 : c.frames ? c.frames[i] : c.n_frames;
 			h_end[i] = (uint32_t) f;
+			// (a closing stream's process () is one of f frames: kmeterdsp.cc:60-65 with fpp = f; every other stream takes the cursor's)
+			if (km) h_fall[i] = f && f < c.n_frames ? kmeter_fall (e, f) : 0.f;
+			if (!fused) { h_lim[i] = h_from[i] = 0; continue; }
 			// fragments that end at or before the stream's end
 			const uint32_t nf = (uint32_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
 			h_lim[i] = f == 0 ? MTR_GATE_UNTOUCHED : f < c.n_frames ? (nf | MTR_GATE_CLOSING) : pl.n_frag;
@@ -258,9 +266,10 @@ struct CallRun {
 				}
 			}
 		}
-		HIPCHK (hipMemcpyAsync (ls->dev.p, ls->pin.p, (size_t) 3 * S * sizeof (uint32_t), hipMemcpyHostToDevice, c.st));
+		HIPCHK (hipMemcpyAsync (ls->dev.p, ls->pin.p, words * sizeof (uint32_t), hipMemcpyHostToDevice, c.st));
 		e->len_cur = slot;
 		d_ends = ls->dev.p; d_lim = d_ends + S; d_from = d_ends + 2 * (size_t) S;
+		if (km) d_fall = reinterpret_cast<const float*> (d_ends + 3 * (size_t) S);
 		return MTR_OK;
 	}
 
@@ -464,20 +473,22 @@ struct CallRun {
 			if ((rc = fused_kernels ())) return rc;
 			if ((rc = gate ())) return rc;
 		} else {
+			if (r.ragged && (rc = upload_lengths ())) return rc;       // (the side meters' steps read the ends)
 			for (int i = 1; i <= 3; ++i) if ((rc = mark (i, c.st))) return rc;
 		}
 		if ((rc = mark (4, c.st))) return rc;
 
 		if ((meters & MTR_METER_SPECTR30) && (rc = bank_step (e, c, nx))) return rc;
-		if ((meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) && (rc = intstat_step (e, c, nx))) return rc;
-		if ((meters & MTR_METER_DR14) && (rc = dr14_step (e, c, nx))) return rc;
-		if ((meters & MTR_METER_KMETER) && (rc = kmeter_step (e, c, nx))) return rc;
+		const StreamEnds se { d_ends, d_fall };                       // (null on a dense call)
+		if ((meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) && (rc = intstat_step (e, c, nx, se))) return rc;
+		if ((meters & MTR_METER_DR14) && (rc = dr14_step (e, c, nx, se))) return rc;
+		if ((meters & MTR_METER_KMETER) && (rc = kmeter_step (e, c, nx, se))) return rc;
 		if ((meters & MTR_METER_STCORR) && (rc = stcorr_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_NEEDLE) && (rc = needle_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_SURROUND) && (rc = surround_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
-		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, or the fused kernels)
+		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, a side meter's LEN kernel, or the fused kernels)
 			HIPCHK (hipEventRecord (ls->done[0].v, c.st));
 			ls->pending[0] = true;
 		}
@@ -658,6 +669,26 @@ int mtr_engine_process_device_lengths (mtr_engine* e, const float* d_audio, uint
 	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
 }
 
+// Track lengths: EBU / TRUEPEAK and the whole-track meters (DR14, KMETER, BITSTATS, SIGDIST), in any combination the engine was created with
+static int tracks_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
+{
+	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST;
+	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok))
+		return fail (MTR_ERR_UNSUPPORTED, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only");
+	for (uint32_t i = 0; i < n; ++i)
+		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "track lengths: frames[s] > n_frames");
+	return MTR_OK;
+}
+
+int mtr_engine_process_device_tracks (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
+                                      const uint64_t* frames, void* hip_stream)
+{
+	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_tracks: null argument");
+	const int crc = tracks_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+}
+
 int mtr_engine_stream_frames (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* frames, uint8_t* closed)
 {
 	if (!e) return fail (MTR_ERR_ARG, "null engine");
@@ -686,6 +717,14 @@ int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64
 {
 	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_lengths: null argument");
 	const int crc = lengths_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
+}
+
+int mtr_engine_process_host_tracks (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_tracks: null argument");
+	const int crc = tracks_check (e, n_frames, frames, e->cfg.n_streams);
 	if (crc) return crc;
 	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
 }

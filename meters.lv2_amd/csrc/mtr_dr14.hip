@@ -12,6 +12,14 @@
 // exactly as the reference does after its last window.  The reference sums the squares sequentially in f32;
 // here the partial sums are double (closer to the true value): a window's RMS can land in the neighbouring
 // 0.01 dB bin, which moves the score by at most that — tests/test_gpu_dr14.py states +-0.02 dB.
+//
+// LEN (both kernels): the call carries per-stream ends (a.ends, call-relative: mtr_engine_process_*_tracks, or any call once a stream of
+// its view is closed).  Stream s ends at frame E = ends [s], workgroup-uniform (one scalar load): its pieces end at min (b1, E), its
+// windows are (dr_scnt + E) / W, and the window E falls into stays open in the state, as the reference leaves it when run () is no
+// longer called.  A workgroup of k_dr14_sums whose piece starts at or past E returns before it touches memory and writes NO piece slot:
+// k_dr14_windows walks the stream's own pieces only — it never reads those slots.  E = 0 (a closed stream, frames [s] == 0): both
+// kernels return at once, the state keeps every bit.  E moves the tail of a piece, never its start: the 16-byte path's parity handling
+// is the dense one's.  The dense instantiations are the kernels as they always were.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,6 +44,7 @@ typedef struct mtr_dr14_args {
 	uint32_t*       hist;         /* [S][C][8000] */
 	double*         piece_sum;    /* [S][n_pieces][2] */
 	float*          piece_peak;   /* [S][n_pieces][2] */
+	const uint32_t* ends;         /* [S] per-stream ends of a ragged call (the LEN instantiations), NULL on a dense one */
 } mtr_dr14_args;
 
 namespace {
@@ -53,11 +62,16 @@ __device__ __forceinline__ uint64_t piece_start (uint32_t i, uint64_t e0, uint64
 	return b < N ? b : N;
 }
 
-template <int C>
+template <int C, bool LEN>
 __global__ __launch_bounds__ (NT) void k_dr14_sums (const mtr_dr14_args a)
 {
 	const uint32_t piece = blockIdx.x, s = blockIdx.y;
-	const uint64_t b0 = piece_start (piece, a.e0, a.window, a.n_frames), b1 = piece_start (piece + 1, a.e0, a.window, a.n_frames);
+	uint64_t N = a.n_frames;
+	if constexpr (LEN) {
+		N = a.ends[s];
+		if (N == 0 || (piece > 0 && a.e0 + (uint64_t) (piece - 1) * a.window >= N)) return;   // not one of the stream's own pieces
+	}
+	const uint64_t b0 = piece_start (piece, a.e0, a.window, N), b1 = piece_start (piece + 1, a.e0, a.window, N);
 	const float* const src = a.audio + (size_t) s * a.stride * C;
 	double sl = 0, sr = 0;
 	float pl = 0.f, pr = 0.f;                                  // dr14.c:401: max (peak_cur, v), signed v, from 0
@@ -108,11 +122,19 @@ __global__ __launch_bounds__ (NT) void k_dr14_sums (const mtr_dr14_args a)
 // one WAVE per stream: lane 0 does the window bookkeeping of dr14_calc_rms_score over this call's pieces (a
 // handful of windows), all 64 lanes look for the occupied histogram bins of the score (one thread walking
 // 8000 bins per channel took 0.37 ms for 8192 streams)
-template <int C>
+template <int C, bool LEN>
 __global__ __launch_bounds__ (64) void k_dr14_windows (const mtr_dr14_args a)
 {
 	const uint32_t s = blockIdx.x;
 	const int lane = threadIdx.x;
+	uint32_t n_pieces = a.n_pieces, n_windows = a.n_windows;        // the stream's own (LEN), the call's otherwise
+	if constexpr (LEN) {
+		const uint64_t E = a.ends[s];
+		if (E == 0) return;
+		const uint64_t tot = a.window - a.e0 + E;                  // dr_scnt + E
+		n_windows = (uint32_t) (tot / a.window);
+		n_pieces = n_windows + (tot % a.window ? 1 : 0);
+	}
 	__shared__ bool st_closed;
 	if (lane == 0) {
 	mtr_dr14_state* const st = a.state + s;
@@ -121,13 +143,13 @@ __global__ __launch_bounds__ (64) void k_dr14_windows (const mtr_dr14_args a)
 	float pk[2] = { st->peak_cur[0], st->peak_cur[1] };
 	const float nsc = (float) (a.window - 1);                  // n_sample_cnt
 	bool closed = false;
-	for (uint32_t i = 0; i < a.n_pieces; ++i) {
+	for (uint32_t i = 0; i < n_pieces; ++i) {
 		const size_t o = ((size_t) s * a.n_pieces + i) * 2;
 		for (int c = 0; c < C; ++c) {
 			rs[c] = (float) ((double) rs[c] + a.piece_sum[o + c]);
 			pk[c] = fmaxf (pk[c], a.piece_peak[o + c]);
 		}
-		if (i >= a.n_windows) break;                           // the last piece leaves an open window
+		if (i >= n_windows) break;                           // the last piece leaves an open window
 		// ---- a window closes (dr14.c:283-352) ----
 		bool silent = true;
 		for (int c = 0; c < C; ++c) if (rs[c] > 1e-9 * (double) nsc) silent = false;    // :290 (float > double product)
@@ -189,19 +211,27 @@ __global__ __launch_bounds__ (64) void k_dr14_windows (const mtr_dr14_args a)
 static int mtr_launch_dr14 (const mtr_dr14_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
-	if (a.n_channels == 2) {
-		hipLaunchKernelGGL (k_dr14_sums<2>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		hipLaunchKernelGGL (k_dr14_windows<2>, dim3 (a.n_streams), dim3 (64), 0, st, a);
+	if (a.ends) {
+		if (a.n_channels == 2) {
+			hipLaunchKernelGGL ((k_dr14_sums<2, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+			hipLaunchKernelGGL ((k_dr14_windows<2, true>), dim3 (a.n_streams), dim3 (64), 0, st, a);
+		} else {
+			hipLaunchKernelGGL ((k_dr14_sums<1, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+			hipLaunchKernelGGL ((k_dr14_windows<1, true>), dim3 (a.n_streams), dim3 (64), 0, st, a);
+		}
+	} else if (a.n_channels == 2) {
+		hipLaunchKernelGGL ((k_dr14_sums<2, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL ((k_dr14_windows<2, false>), dim3 (a.n_streams), dim3 (64), 0, st, a);
 	} else {
-		hipLaunchKernelGGL (k_dr14_sums<1>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		hipLaunchKernelGGL (k_dr14_windows<1>, dim3 (a.n_streams), dim3 (64), 0, st, a);
+		hipLaunchKernelGGL ((k_dr14_sums<1, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL ((k_dr14_windows<1, false>), dim3 (a.n_streams), dim3 (64), 0, st, a);
 	}
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 // ---- DR14 in the engine: the call's step, the blob's sections, reset, the results ------------------------------------------------------
 
-int dr14_step (mtr_engine* e, const Call& c, Cursors& nx)
+int dr14_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	mtr_dr14_args da;
@@ -211,7 +241,7 @@ int dr14_step (mtr_engine* e, const Call& c, Cursors& nx)
 	const uint64_t tot = e->pos.dr_scnt + c.n_frames;
 	da.n_windows = (uint32_t) (tot / da.window);
 	da.n_pieces = da.n_windows + (tot % da.window ? 1 : 0);
-	da.n_streams = c.cnt; da.n_channels = e->cfg.n_channels;
+	da.n_streams = c.cnt; da.n_channels = e->cfg.n_channels; da.ends = se.ends;
 	if (e->dr.sum.reserve ((size_t) e->cfg.n_streams * da.n_pieces * 2) || e->dr.peak.reserve ((size_t) e->cfg.n_streams * da.n_pieces * 2))
 		return fail (MTR_ERR_NOMEM, "hipMalloc DR14 pieces");
 	da.state = e->dr.state.p + vo; da.hist = e->dr.hist.p + vo * e->cfg.n_channels * MTR_DR_HISTBINS;

@@ -62,9 +62,10 @@ struct Stream {
 // 48 kHz — never overwrites arrays that kernels of an earlier call may still be reading, and never blocks the host.
 constexpr int PLAN_SLOTS = 4;
 
-// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths, or any call once a stream is closed) ride the same way:
-// [ends S | frag_lim S | from_tile S] in the next slot of their own ring, uploaded on the call's stream, busy until the call's last
-// readers (k_history_len on the call's stream, the gate on whichever stream it ran) have passed.
+// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks, or any call once a stream is closed) ride the same
+// way: [ends S | frag_lim S | from_tile S | km_fall S (KMETER engines)] in the next slot of their own ring, uploaded on the call's stream,
+// busy until the call's last readers (the last kernel of the call on its stream — the side meters' LEN kernels, k_history_len — and the
+// gate on whichever stream it ran) have passed.
 constexpr int LEN_SLOTS = 4;
 struct LenSlot {
 	DevBuf<uint32_t> dev;
@@ -311,6 +312,14 @@ struct Call {
 	bool            wave51 = false;
 };
 
+// The per-stream ends of a ragged call on the device, as the side meters' steps get them: ends[i] = the call frame at which stream i of the
+// view ends (0: closed, untouched), km_fall[i] = Kmeterdsp's fall-back factor for a stream that ends inside the call (KMETER engines).
+// Both null on a dense call: the steps then launch the dense instantiations.
+struct StreamEnds {
+	const uint32_t* ends = nullptr;
+	const float*    km_fall = nullptr;
+};
+
 struct StateSection { const void* base; size_t elem; };   // a per-stream array of the state blob: `elem` bytes per stream
 
 // ---- mtr_engine.hip -------------------------------------------------------------------------------------------------------------
@@ -331,11 +340,12 @@ int  bank_create (mtr_engine* e);
 int  bank_reset (mtr_engine* e, hipStream_t st);
 int  bank_step (mtr_engine* e, const Call& c, Cursors& nx);
 void bank_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  intstat_step (mtr_engine* e, const Call& c, Cursors& nx);
+int  intstat_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
 void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  dr14_step (mtr_engine* e, const Call& c, Cursors& nx);
+int  dr14_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
 void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  kmeter_step (mtr_engine* e, const Call& c, Cursors& nx);
+int  kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
+float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v);
 void stcorr_create (mtr_engine* e);
 int  stcorr_step (mtr_engine* e, const Call& c, Cursors& nx);

@@ -225,8 +225,9 @@ int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mt
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
 int  mtr_launch_tpb (const mtr_tpb_args& a, void* stream);
+/* ends != NULL: the LEN instantiation, stream s of the view ends at call frame ends[s] (0: untouched) */
 int  mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
-                          uint32_t n_streams, void* stream);
+                          uint32_t n_streams, const uint32_t* ends, void* stream);
 int  mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
                               float* hist_out, uint32_t n_streams, void* stream);
 int  mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint32_t n_streams, int32_t* d_hist, float* d_max, void* stream);

@@ -40,10 +40,21 @@ typedef struct mtr_sigdist_state {
 } mtr_sigdist_state;
 
 
-__global__ __launch_bounds__ (256) void k_sigdist (const float* audio, uint64_t stride, uint64_t n_frames,
-                                                   mtr_sigdist_state* out, uint32_t n_streams)
+// LEN: the call carries per-stream ends (`ends`, call-relative: mtr_engine_process_*_tracks, or any call once a stream of its view is
+// closed).  The stream's own end takes the place of n_frames everywhere: the wide / scalar split, the 256 per-lane chunks of the
+// second pass, count += end.  It is workgroup-uniform (one scalar load).  End 0 (a closed stream, frames[s] == 0): the workgroup returns
+// before it touches memory.  The end moves the tail of the 16-byte loop, never the alignment of its start.  The dense instantiation is
+// the kernel as it always was.
+template <bool LEN>
+__global__ __launch_bounds__ (256) void k_sigdist (const float* audio, uint64_t stride, uint64_t n_frames_call,
+                                                   mtr_sigdist_state* out, uint32_t n_streams, const uint32_t* ends)
 {
 #pragma clang fp contract(off)
+	uint64_t n_frames = n_frames_call;
+	if constexpr (LEN) {
+		n_frames = ends[blockIdx.x];
+		if (n_frames == 0) return;
+	}
 	__shared__ int32_t bins[MTR_DIST_BIN];
 	__shared__ uint32_t last[MTR_DIST_BIN];              // in-call index + 1 of the last sample that fell in the bin
 	__shared__ double mom[256][3];                       // n, mean, M2 per lane, then combined
@@ -160,9 +171,10 @@ __global__ __launch_bounds__ (256) void k_sigdist (const float* audio, uint64_t 
 }
 
 static int mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_frames, mtr_sigdist_state* out,
-                        uint32_t n_streams, void* stream)
+                        uint32_t n_streams, const uint32_t* ends, void* stream)
 {
-	hipLaunchKernelGGL (k_sigdist, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams);
+	if (ends) hipLaunchKernelGGL (k_sigdist<true>, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams, ends);
+	else      hipLaunchKernelGGL (k_sigdist<false>, dim3 (n_streams), dim3 (256), 0, (hipStream_t) stream, audio, stride, n_frames, out, n_streams, ends);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -170,12 +182,12 @@ static int mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_f
 
 // (the integer tables are int32, as the reference's, which stops counting at 2^31 - 1 samples; the kernels index
 // a call's samples with 32 bits: checked on entry)
-int intstat_step (mtr_engine* e, const Call& c, Cursors&)
+int intstat_step (mtr_engine* e, const Call& c, Cursors&, const StreamEnds& se)
 {
 	if (e->cfg.meters & MTR_METER_BITSTATS)
-		if (mtr_launch_bitstats (c.audio, c.stride, c.n_frames, e->is.bim.p + c.off, c.cnt, c.st)) return fail (MTR_ERR_HIP, "k_bitstats launch");
+		if (mtr_launch_bitstats (c.audio, c.stride, c.n_frames, e->is.bim.p + c.off, c.cnt, se.ends, c.st)) return fail (MTR_ERR_HIP, "k_bitstats launch");
 	if (e->cfg.meters & MTR_METER_SIGDIST)
-		if (mtr_launch_sigdist (c.audio, c.stride, c.n_frames, e->is.sdh.p + c.off, c.cnt, c.st)) return fail (MTR_ERR_HIP, "k_sigdist launch");
+		if (mtr_launch_sigdist (c.audio, c.stride, c.n_frames, e->is.sdh.p + c.off, c.cnt, se.ends, c.st)) return fail (MTR_ERR_HIP, "k_sigdist launch");
 	return MTR_OK;
 }
 

@@ -18,6 +18,15 @@
 // zero state, four groups per lane, and combined in a tree: each lane read its own 128 contiguous bytes — 8.1 ms
 // per 31.5 GB.)  The sums are re-associated and carried in double: tests/test_gpu_kmeter.py states 1e-5
 // relative against the restatement.
+//
+// LEN (both kernels): the call carries per-stream ends (a.ends, call-relative: mtr_engine_process_*_tracks, or any call once a stream of
+// its view is closed).  Stream s ends at frame E = ends [s], workgroup-uniform (one scalar load): a stream that ends inside the call sees
+// ONE process (p, E) — E / 4 groups, the weights A^k counted back from ITS last group, fpp = E with the fall-back factor the host
+// computed for that fpp (a.falls [s], the expression of kmeter_fall) — and a stream with E = n_frames exactly what the dense call gives it
+// (the cursor's fall).  A workgroup of k_kmeter_pieces whose chunk lies at or past the stream's groups returns before it touches memory
+// and writes NO piece slot: k_kmeter_final adds the stream's own chunks only — it never reads those slots.  E = 0 (a closed stream,
+// frames [s] == 0): nothing is written, not even the + 1e-20f.  Groups start on multiples of four frames whatever E is: the 16-byte
+// path is the dense one's.  The dense instantiations are the kernels as they always were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +52,8 @@ typedef struct mtr_kmeter_args {
 	mtr_kmeter_state* state;      /* [S][2] */
 	double*         piece_state;  /* [S][n_pieces][4]: each chunk's weighted sums (z1, z2 per channel), already carried to the call's end */
 	float*          piece_max;    /* [S][n_pieces][2] */
+	const uint32_t* ends;         /* [S] per-stream ends of a ragged call (the LEN instantiations), NULL on a dense one ... */
+	const float*    falls;        /* [S] ... and the fall-back factor of each stream that ends inside the call */
 } mtr_kmeter_args;
 
 namespace {
@@ -58,16 +69,21 @@ __host__ __device__ inline Mat mat_pow (double a1, double c1, double b1, double 
 	return Mat{ak, c1 * (ak - bk) / (a1 - b1), bk};
 }
 
-template <int C>
+template <int C, bool LEN>
 __global__ __launch_bounds__ (NT) void k_kmeter_pieces (const mtr_kmeter_args a)
 {
 	const uint32_t chunk = blockIdx.x, s = blockIdx.y;
+	uint64_t n_groups = a.n_groups;
+	if constexpr (LEN) {
+		n_groups = a.ends[s] / 4;
+		if ((uint64_t) chunk * CH >= n_groups) return;             // not one of the stream's own chunks
+	}
 	const float* const src = a.audio + (size_t) s * a.stride * C;
 	const float w = a.omega, r = 1.f - w;
 	const float u3 = w, u2 = w * r, u1 = u2 * r, u0 = u1 * r;             // weight of slot q inside its own group
 	// k = groups after this one; chunk c covers k in [c CH, (c + 1) CH)
 	uint64_t k = (uint64_t) chunk * CH + threadIdx.x;
-	const uint64_t k_end = min ((uint64_t) (chunk + 1) * CH, a.n_groups);
+	const uint64_t k_end = min ((uint64_t) (chunk + 1) * CH, n_groups);
 	Mat m = mat_pow (a.pw1[0], a.pw1[1], a.pw1[2], (double) k);
 	const Mat st = mat_pow (a.pw1[0], a.pw1[1], a.pw1[2], (double) NT);
 	const double w4 = 4.0 * (double) w;
@@ -76,7 +92,7 @@ __global__ __launch_bounds__ (NT) void k_kmeter_pieces (const mtr_kmeter_args a)
 	const bool wide = C == 2 ? ((((size_t) s * a.stride) & 1) == 0 && (reinterpret_cast<size_t> (a.audio) & 15) == 0)
 	                         : ((((size_t) s * a.stride) & 3) == 0 && (reinterpret_cast<size_t> (a.audio) & 15) == 0);
 	for (; k < k_end; k += NT) {
-		const float* const p = src + (size_t) (a.n_groups - 1 - k) * 4 * C;
+		const float* const p = src + (size_t) (n_groups - 1 - k) * 4 * C;
 		float v[4 * C];
 		if (wide) {
 #pragma unroll
@@ -129,25 +145,38 @@ __global__ __launch_bounds__ (NT) void k_kmeter_pieces (const mtr_kmeter_args a)
 }
 
 // one thread per (stream, channel): add the chunks and the carried state, then kmeterdsp.cc:108-138
+template <bool LEN>
 __global__ void k_kmeter_final (const mtr_kmeter_args a)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= a.n_streams * a.n_channels) return;
 	const uint32_t s = i / a.n_channels, c = i % a.n_channels;
+	uint64_t n_groups = a.n_groups;
+	uint32_t n_pieces = a.n_pieces, fpp = a.fpp;                       // the stream's own (LEN), the call's otherwise
+	float fall = a.fall;
+	if constexpr (LEN) {
+		const uint32_t E = a.ends[s];
+		if (E == 0) return;
+		if (E != a.fpp) {                                              // the stream ends inside the call: one process (p, E)
+			n_groups = E / 4;
+			n_pieces = (uint32_t) ((n_groups + CH - 1) / CH);
+			fpp = E; fall = a.falls[s];
+		}
+	}
 	mtr_kmeter_state* const st = a.state + (size_t) s * 2 + c;
 	float zi1 = st->z1 > 50 ? 50 : (st->z1 < 0 ? 0 : st->z1);         // :66-67 (a NaN state falls through, as there)
 	float zi2 = st->z2 > 50 ? 50 : (st->z2 < 0 ? 0 : st->z2);
 	double e1 = 0, e2 = 0;
 	float t = 0.f;
-	for (uint32_t p = 0; p < a.n_pieces; ++p) {                        // the weights already carry every chunk to the end
+	for (uint32_t p = 0; p < n_pieces; ++p) {                        // the weights already carry every chunk to the end
 		const size_t o = ((size_t) s * a.n_pieces + p) * 4 + 2 * c;
 		e1 += a.piece_state[o]; e2 += a.piece_state[o + 1];
 		t = fmaxf (t, a.piece_max[((size_t) s * a.n_pieces + p) * 2 + c]);
 	}
-	const Mat g = mat_pow (a.pw1[0], a.pw1[1], a.pw1[2], (double) a.n_groups);
+	const Mat g = mat_pow (a.pw1[0], a.pw1[1], a.pw1[2], (double) n_groups);
 	float z1 = (float) (g.a * (double) zi1 + e1);
 	float z2 = (float) (g.c * (double) zi1 + g.b * (double) zi2 + e2);
-	if (a.n_groups == 0) { z1 = zi1; z2 = zi2; }
+	if (n_groups == 0) { z1 = zi1; z2 = zi2; }
 	if (isnan (z1)) z1 = 0;                                            // :100-102
 	if (isnan (z2)) z2 = 0;
 	if (!isfinite (t)) t = 0;
@@ -158,8 +187,8 @@ __global__ void k_kmeter_final (const mtr_kmeter_args a)
 	if (st->flag) { st->rms = r; st->flag = 0; }                       // :112-118
 	else if (r > st->rms) st->rms = r;
 	if (t >= st->peak) { st->peak = t; st->cnt = a.hold; }             // :121-138
-	else if (st->cnt > 0) st->cnt -= (int32_t) a.fpp;
-	else { st->peak *= a.fall; st->peak += 1e-10f; }
+	else if (st->cnt > 0) st->cnt -= (int32_t) fpp;
+	else { st->peak *= fall; st->peak += 1e-10f; }
 }
 
 }  // namespace
@@ -176,26 +205,40 @@ static uint32_t mtr_kmeter_pieces (uint64_t n_groups) { return (uint32_t) ((n_gr
 static int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
-	if (a.n_pieces) {
-		if (a.n_channels == 2) hipLaunchKernelGGL (k_kmeter_pieces<2>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		else                   hipLaunchKernelGGL (k_kmeter_pieces<1>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-	}
 	const uint32_t n = a.n_streams * a.n_channels;
-	hipLaunchKernelGGL (k_kmeter_final, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	if (a.ends) {
+		if (a.n_pieces) {
+			if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_pieces<2, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+			else                   hipLaunchKernelGGL ((k_kmeter_pieces<1, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		}
+		hipLaunchKernelGGL (k_kmeter_final<true>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+		return hipGetLastError () == hipSuccess ? 0 : -1;
+	}
+	if (a.n_pieces) {
+		if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_pieces<2, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		else                   hipLaunchKernelGGL ((k_kmeter_pieces<1, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+	}
+	hipLaunchKernelGGL (k_kmeter_final<false>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 // ---- KMETER in the engine: the call's step, the blob's section, reset, the reading ------------------------------------------------------
 
-int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx)
+// kmeterdsp.cc:60-65: the fall-back factor of a process () of n frames (15 dB/s)
+float kmeter_fall (const mtr_engine* e, uint64_t n)
+{
+	return powf (10.0f, -0.05f * 15.0f * ((float) n / e->cfg.sample_rate));
+}
+
+int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	mtr_kmeter_args ka;
 	ka.audio = c.audio; ka.stride = c.stride; ka.n_groups = c.n_frames / 4;
-	ka.n_streams = c.cnt; ka.n_channels = e->cfg.n_channels;
+	ka.n_streams = c.cnt; ka.n_channels = e->cfg.n_channels; ka.ends = se.ends; ka.falls = se.km_fall;
 	ka.n_pieces = mtr_kmeter_pieces (ka.n_groups);
 	if (nx.km_fpp != (uint32_t) c.n_frames) {                          // kmeterdsp.cc:60-65
-		nx.km_fall = powf (10.0f, -0.05f * 15.0f * ((float) c.n_frames / e->cfg.sample_rate));
+		nx.km_fall = kmeter_fall (e, c.n_frames);
 		nx.km_fpp = (uint32_t) c.n_frames;
 	}
 	ka.fpp = nx.km_fpp; ka.fall = nx.km_fall;

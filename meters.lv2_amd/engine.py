@@ -119,6 +119,9 @@ def _load():
         L.mtr_engine_process_device_lengths.argtypes = [vp, vp, u64, u64, vp, vp]
         L.mtr_engine_process_host_lengths.argtypes = [vp, vp, u64, u64, vp]
         L.mtr_engine_stream_frames.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "mtr_engine_process_device_tracks"):         # (an addition inside ABI version 2: track lengths for the whole-track meters)
+        L.mtr_engine_process_device_tracks.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_tracks.argtypes = [vp, vp, u64, u64, vp]
     if hasattr(L, "mtr_engine_pcm_stats"):                     # (an addition inside ABI version 2: integer PCM in)
         L.mtr_engine_process_host_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp]
         L.mtr_engine_process_device_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp, vp]
@@ -507,6 +510,28 @@ class Engine:
         f = self._lengths(frames, x.shape[1])
         _check(lib.mtr_engine_process_host_lengths(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
                "process_host_lengths")
+
+    def _tracks(self, frames):
+        if not hasattr(lib, "mtr_engine_process_device_tracks"):
+            raise EngineError(f"{lib_path} has no track lengths: rebuild it")
+        f = np.ascontiguousarray(frames, np.uint64)
+        if f.shape != (self.n_streams,):
+            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
+        return f
+
+    def process_device_tracks(self, ptr, n_frames, frames, stride=None, stream=0):
+        """process_device_lengths() for engines of EBU, TRUEPEAK, DR14, KMETER, BITSTATS and SIGDIST in any combination: stream s is
+        metered up to frames[s] <= n_frames, as by a host that stops calling run() at the track's end; frames[s] < n_frames closes it."""
+        f = self._tracks(frames)
+        _check(lib.mtr_engine_process_device_tracks(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
+               "process_device_tracks")
+
+    def process_tracks(self, x, frames):
+        """process() with track lengths: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        x = self._frames_f32(x)
+        f = self._tracks(frames)
+        _check(lib.mtr_engine_process_host_tracks(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
+               "process_host_tracks")
 
     def process_pcm(self, x, format=None, frames=None):
         """process() for host integer PCM, decoded on the GPU: x int16 or int32 [S, T, C] (or [S, T] mono; the format is inferred),
