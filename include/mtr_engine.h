@@ -30,7 +30,8 @@ extern "C" {
  *    mtr_pcm_decode_host; mtr_engine_set_frame_layout, _frame_layout, _layout_stats, mtr_pick_decode_host; MTR_METER_STCORR, mtr_stcorr_coef,
  *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset; mtr_engine_loudlog_set_period, _loudlog_period,
  *    _loudlog_series, _loudlog_reset; MTR_METER_NEEDLE, mtr_needle_coef, mtr_engine_needle_configure, _needle_set_gain, _needle_read,
- *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks; MTR_METER_SCOPE, mtr_scope_window,
+ *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -61,6 +62,9 @@ extern "C" {
                                     * either (tests/test_stcorr_cpu.py holds both refused) */
 #define MTR_METER_SURROUND   0x2000u /* sur_run: C x Kmeterdsp + up to four Stcorrdsp on selectable pairs, 3 .. 8 channels (src/surmeter.c:115-147),
                                     * see mtr_surround.h; 0x1000 is no meter, like 0x100 and 0x400 (tests/test_needle_cpu.py holds it refused) */
+#define MTR_METER_SCOPE      0x8000u /* the stereo / frequency scope's and the phase wheel's analysis: windowed FFT, level, balance, phase per bin
+                                    * (gui/stereoscope.c:705-741, gui/phasewheel.c:1307-1339, gui/fft.c), stereo, see mtr_scope.h; 0x4000 is no
+                                    * meter (tests/test_surround_cpu.py holds it refused) */
 
 #define MTR_HIST_LEN   751          /* src/uris.h:45  HIST_LEN */
 #define MTR_NBANDS     30           /* src/spectrumlv2.c:33  FILTER_COUNT */
@@ -363,6 +367,11 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The surround meter for a batch (MTR_METER_SURROUND) — 3 .. 8 K-meters and up to four pair correlations from one read of the frames,
  * with a reading series: mtr_engine_surround_set_pairs / _pairs / _set_period / _read / _pair_states / _series / _reset */
 #include "mtr_surround.h"
+
+/* The stereo / frequency scope for a batch (MTR_METER_SCOPE) — a windowed FFT per hop and stream, the stereoscope's smoothed level and
+ * balance and the phase wheel's phase difference, level and peak per bin: mtr_scope_window and mtr_engine_scope_configure / _config /
+ * _read / _analyses / _reset */
+#include "mtr_scope.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

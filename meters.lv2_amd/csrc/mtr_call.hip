@@ -116,6 +116,7 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 		{ MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
 		{ MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
+		{ MTR_METER_SCOPE, 0x7fffffffull, "SCOPE: n_frames per call must be < 2^31 - 1" },
 		{ MTR_METER_TPBALLIST, 0x7ffff000ull, "TPBALLIST: n_frames per call must be < 2^31 - 4096" },
 		{ MTR_METER_EBU | MTR_METER_TRUEPEAK, 0xFFFFFFFFull, "n_frames per call must be < 2^32 - 1" },
 	};
@@ -486,6 +487,7 @@ struct CallRun {
 		if ((meters & MTR_METER_STCORR) && (rc = stcorr_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_NEEDLE) && (rc = needle_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_SURROUND) && (rc = surround_step (e, c, nx))) return rc;
+		if ((meters & MTR_METER_SCOPE) && (rc = scope_step (e, c, nx))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, a side meter's LEN kernel, or the fused kernels)

@@ -1,6 +1,6 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
 // EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
-// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip), and mtr_loudlog.hip (the host
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip, mtr_scope.hip), and mtr_loudlog.hip (the host
 // side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
 #ifndef MTR_ENGINE_IMPL_H
@@ -109,6 +109,8 @@ struct Cursors {
 	uint64_t su_points = 0;       // ... blocks completed since reset ...
 	uint32_t su_fpp = 0;          // ... and its Kmeterdsps' frames per period with the fall-back factor that goes with it
 	float    su_fall = 0.f;
+	uint32_t sp_fill = 0;         // SCOPE: frames since the last analysis ...
+	uint64_t sp_analyses = 0;     // ... and analyses completed since reset
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 };
@@ -278,6 +280,15 @@ struct mtr_engine {
 		double                     k[18];       // mtr_sur_consts: the pieces kernel's constants
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
 	} su;
+	struct Scope {                              // SCOPE (mtr_scope.hip)
+		DevBuf<float>              tail;        // [S][W][2] the last W frames of every stream
+		DevBuf<float>              level, lr, phase, plevel, power_l, power_r;   // [S][W / 2]
+		DevBuf<float>              peak;        // [S]
+		DevBuf<unsigned char>      hdr;         // [S] mtr_scope_hdr: the blob's copy of the configuration and the cursors (written at export)
+		DevBuf<float>              win, tw;     // [W] the window, [W][2] the twiddles
+		uint32_t                   W = 0, H = 0;   // frames per window and per hop (resolved: never 0): a control (it survives a reset)
+		float                      thresh = 0.f;   // the phase wheel's threshold on the powers
+	} sp;
 	struct LoudLog {                            // the loudness log of an EBU engine (mtr_loudlog.hip; the gate appends: mtr_gate.hip)
 		DevBuf<float>              M, S;        // [S][cap]
 		DevBuf<float>              run;         // [S][2] MAX: maxima of the period open between two calls
@@ -356,6 +367,9 @@ void needle_sections (const mtr_engine* e, std::vector<StateSection>& v);
 void surround_create (mtr_engine* e);
 int  surround_step (mtr_engine* e, const Call& c, Cursors& nx);
 void surround_sections (const mtr_engine* e, std::vector<StateSection>& v);
+int  scope_create (mtr_engine* e);
+int  scope_step (mtr_engine* e, const Call& c, Cursors& nx);
+void scope_sections (const mtr_engine* e, std::vector<StateSection>& v);
 // STCORR's section of a blob carries the period and the frames into the open one in every stream's entry (the header has no room for
 // them).  Export writes the host's copies into the `count` entries at `sec`; import checks the entries (MTR_ERR_STATE with the text set if
 // they are corrupt or — `fresh` false — not where the engine stands) and returns the two.
@@ -378,6 +392,11 @@ void surround_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t 
 int  surround_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, unsigned char* out);
 void surround_take_cursors (mtr_engine* e, const unsigned char* hdr);
 size_t surround_hdr_bytes (void);
+// SCOPE's sections are the blob's last scope_n_sections (); the first of them carries window, hop, threshold, the frames since the last
+// analysis and the analyses counted in every stream's entry.  The configuration must be the engine's; a fresh engine takes the cursors
+size_t scope_n_sections (void);
+void scope_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
+int  scope_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* fill, uint64_t* analyses);
 
 #pragma GCC visibility pop
 

@@ -193,6 +193,7 @@ int  mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst);  
 int  mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_t fc, const uint8_t* map, uint32_t C, float* dst);
 void mtr_setup_stcorr (float fsamp, float* out2);   /* w1, w2 of Stcorrdsp::init ((int) fsamp, 2e3f, 0.3f) */
 int  mtr_setup_needle (uint32_t kind, float fsamp, float* out4);   /* w1 w2 w3 g of the needle meters' init (VU: w, 4 w, 0, g); -1: unknown kind */
+void mtr_setup_scope_window (uint32_t n, float* out);   /* the Hann window of ft_gen_window (gui/fft.c): n floats */
 float mtr_setup_needle_gain (float db);             /* Msppmdsp::set_gain: powf (10, .05 * db) */
 #ifdef __cplusplus
 }

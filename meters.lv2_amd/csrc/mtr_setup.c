@@ -292,6 +292,20 @@ void mtr_setup_stcorr (float fsamp, float* out2)
 	out2[1] = 1 / (tcf * fs);
 }
 
+/* ft_gen_window with W_HANN (gui/fft.c:122-161): ft_hannhamm (window, n, .5, .5) (:69-79) — each value computed in double and stored as
+ * f32, the f32 values summed in double — then every value times 2 / sum, again through double into the f32 */
+void mtr_setup_scope_window (uint32_t n, float* window)
+{
+	double sum = 0.0;
+	const double c = 2.0 * M_PI / (n - 1.0);
+	for (uint32_t i = 0; i < n; ++i) {
+		window[i] = .5 - .5 * cos (c * i);
+		sum += window[i];
+	}
+	const double isum = 2.0 / sum;
+	for (uint32_t i = 0; i < n; ++i) window[i] *= isum;
+}
+
 /* w1 w2 w3 g of Iec1ppmdsp::init (kind 2, iec1ppmdsp.cc:89-95) / Iec2ppmdsp::init = Msppmdsp::init (kinds 4, 8; iec2ppmdsp.cc:89-95,
  * msppmdsp.cc:131-137); Vumeterdsp::init (kind 1, vumeterdsp.cc:82-86) as w, 4 w, 0, g.  -1: not one of the four kinds */
 int mtr_setup_needle (uint32_t kind, float fsamp, float* out4)

@@ -60,6 +60,9 @@ std::vector<StateSection> state_sections (const mtr_engine* e)
 	// (and the surround meter's — never beside those two, which meter one or two channels: period, cursor, _fpp and pairs in every stream's
 	// entry, surround_export_cursors / _import_cursors)
 	if (m & MTR_METER_SURROUND) surround_sections (e, v);
+	// (and the scope's — a stereo meter, so behind STCORR's and NEEDLE's: configuration and cursors in every stream's entry of the first of
+	// them, scope_export_cursors / _import_cursors)
+	if (m & MTR_METER_SCOPE) scope_sections (e, v);
 	return v;
 }
 
@@ -71,12 +74,17 @@ size_t section_offset (const std::vector<StateSection>& secs, size_t idx, uint32
 	return o;
 }
 
-// STCORR's and NEEDLE's sections are the last ones, in this order; SURROUND's (3 .. 8 channels: never in their engine) is the last one
+// SCOPE's sections are the last ones, STCORR's and NEEDLE's in front of them, in this order; SURROUND's (3 .. 8 channels: never in their
+// engine) is the last one
+size_t scope_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - scope_n_sections (); }
 size_t surround_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - 1; }
-size_t needle_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - 1; }
+size_t needle_section (const mtr_engine* e, const std::vector<StateSection>& secs)
+{
+	return secs.size () - 1 - ((e->cfg.meters & MTR_METER_SCOPE) ? scope_n_sections () : 0);
+}
 size_t stcorr_section (const mtr_engine* e, const std::vector<StateSection>& secs)
 {
-	return secs.size () - 1 - ((e->cfg.meters & MTR_METER_NEEDLE) ? 1 : 0);
+	return needle_section (e, secs) - ((e->cfg.meters & MTR_METER_NEEDLE) ? 1 : 0);
 }
 
 size_t state_per_stream (const mtr_engine* e)
@@ -131,6 +139,7 @@ int mtr_engine_state_export (mtr_engine* e, uint32_t first, uint32_t count, void
 	if (e->cfg.meters & MTR_METER_STCORR) stcorr_export_cursors (e, o0 + section_offset (secs, stcorr_section (e, secs), count), count);
 	if (e->cfg.meters & MTR_METER_NEEDLE) needle_export_cursors (e, o0 + section_offset (secs, needle_section (e, secs), count), count);
 	if (e->cfg.meters & MTR_METER_SURROUND) surround_export_cursors (e, o0 + section_offset (secs, surround_section (e, secs), count), count);
+	if (e->cfg.meters & MTR_METER_SCOPE) scope_export_cursors (e, o0 + section_offset (secs, scope_section (e, secs), count), count);
 	h.payload_fnv = fnv1a64 (o0, (size_t) (o - o0));
 	memcpy (blob, &h, sizeof (h));
 	return MTR_OK;
@@ -180,6 +189,12 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		rc = surround_import_cursors (e, i0 + section_offset (secs, surround_section (e, secs), h.count), h.count, fresh, su_hdr.data ());
 		if (rc) return rc;
 	}
+	uint32_t sp_fill = e->pos.sp_fill;
+	uint64_t sp_analyses = e->pos.sp_analyses;
+	if ((e->cfg.meters & MTR_METER_SCOPE) && h.count) {
+		rc = scope_import_cursors (e, i0 + section_offset (secs, scope_section (e, secs), h.count), h.count, fresh, &sp_fill, &sp_analyses);
+		if (rc) return rc;
+	}
 	if (!fresh && (e->pos.frcnt != h.frcnt || e->integr != (h.integr != 0) || e->bank.omega != h.omega || e->pos.dr_scnt != h.dr_scnt))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (fragment phase, integration, bank speed or DR-14 window)");
 	rc = mtr_engine_sync (e);
@@ -199,6 +214,7 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		e->sc.period = sc_period; e->pos.sc_fill = sc_fill;
 		if (nd_take) needle_take_cursors (e, reinterpret_cast<const mtr_needle_hdr*> (nd_hdr.data ()));
 		if (su_take) surround_take_cursors (e, su_hdr.data ());
+		e->pos.sp_fill = sp_fill; e->pos.sp_analyses = sp_analyses;
 		e->plan.valid = false;
 		e->advanced = true;
 	}

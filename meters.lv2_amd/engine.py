@@ -16,6 +16,7 @@ METER_BITSTATS, METER_SIGDIST, METER_DR14, METER_KMETER = 0x10, 0x20, 0x40, 0x80
 METER_STCORR = 0x200                       # (0x100 is no meter)
 METER_NEEDLE = 0x800                       # VU, IEC I / II PPM, M/S PPM: include/mtr_needle.h (0x400 is no meter either)
 METER_SURROUND = 0x2000                    # sur_run: C K-meters + four pair correlations, 3 .. 8 channels: include/mtr_surround.h (0x1000 is no meter)
+METER_SCOPE = 0x8000                       # the stereoscope's / phase wheel's FFT analysis, stereo: include/mtr_scope.h (0x4000 is no meter)
 NEEDLE_VU, NEEDLE_IEC1, NEEDLE_IEC2, NEEDLE_MS = 1, 2, 4, 8
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
@@ -171,6 +172,13 @@ def _load():
         L.mtr_engine_surround_pair_states.argtypes = [vp, u32, u32, vp]
         L.mtr_engine_surround_series.argtypes = [vp, u32, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_surround_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_scope_read"):                    # (an addition inside ABI version 2: the stereo / frequency scope)
+        L.mtr_scope_window.argtypes = [u32, vp]
+        L.mtr_engine_scope_configure.argtypes = [vp, u32, u32, f32]
+        L.mtr_engine_scope_config.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(f32)]
+        L.mtr_engine_scope_read.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.mtr_engine_scope_analyses.argtypes = [vp, C.POINTER(u64)]
+        L.mtr_engine_scope_reset.argtypes = [vp]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -258,6 +266,13 @@ def stcorr_coef(fs):
     """(w1, w2) of Stcorrdsp::init ((int) fs, 2e3f, 0.3f) as float32."""
     out = np.zeros(2, np.float32)
     _check(lib.mtr_stcorr_coef(fs, out.ctypes.data), "mtr_stcorr_coef")
+    return out
+
+
+def scope_window(window_frames):
+    """The Hann window of ft_gen_window (gui/fft.c) as float32 [window_frames], as MTR_METER_SCOPE applies it."""
+    out = np.zeros(int(window_frames), np.float32)
+    _check(lib.mtr_scope_window(int(window_frames), out.ctypes.data), "mtr_scope_window")
     return out
 
 
@@ -812,6 +827,36 @@ class Engine:
 
     def surround_reset(self):
         _check(lib.mtr_engine_surround_reset(self._h), "surround_reset")
+
+    def scope_configure(self, window_frames=1024, hop_frames=0, phase_thresh_power=1e-6):
+        """window: a power of two, 256 .. 16384; hop 0: ceil (sample_rate / 25), else 64 .. 2^20; the phase wheel's threshold on the
+        powers.  Only before the first process call since create / reset."""
+        _check(lib.mtr_engine_scope_configure(self._h, int(window_frames), int(hop_frames), float(phase_thresh_power)), "scope_configure")
+
+    def scope_config(self):
+        """(window_frames, hop_frames, phase_thresh_power) as configured, the hop resolved."""
+        w, h, t = C.c_uint32(), C.c_uint32(), C.c_float()
+        _check(lib.mtr_engine_scope_config(self._h, C.byref(w), C.byref(h), C.byref(t)), "scope_config")
+        return w.value, h.value, t.value
+
+    def scope_read(self, first=0, count=None):
+        """dict of float32 arrays after the most recent analysis: level, lr (the stereoscope's), phase, plevel (the phase wheel's),
+        power_l, power_r (the last |X|^2), each [count, W / 2], and peak [count]."""
+        count = self.n_streams - first if count is None else count
+        B = self.scope_config()[0] // 2
+        names = ("level", "lr", "phase", "plevel", "peak", "power_l", "power_r")
+        out = {n: np.zeros(count if n == "peak" else (count, B), np.float32) for n in names}
+        _check(lib.mtr_engine_scope_read(self._h, first, count, *[out[n].ctypes.data for n in names]), "scope_read")
+        return out
+
+    def scope_analyses(self):
+        """analyses completed since reset (the streams advance in lock step)."""
+        n = C.c_uint64()
+        _check(lib.mtr_engine_scope_analyses(self._h, C.byref(n)), "scope_analyses")
+        return n.value
+
+    def scope_reset(self):
+        _check(lib.mtr_engine_scope_reset(self._h), "scope_reset")
 
     def _need_loudlog(self):
         if not hasattr(lib, "mtr_engine_loudlog_series"):
