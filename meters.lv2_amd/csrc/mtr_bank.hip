@@ -258,11 +258,9 @@ int mtr_launch_synth (float* d_audio, uint32_t n_streams, uint64_t n_frames, uin
 
 // ---- SPECTR30 in the engine: set-up, reset, the call's step, the blob's sections, the getters ----------------------------------------
 
-int bank_create (mtr_engine* e)
+static int bank_create (mtr_engine* e)
 {
 	const mtr_config* const cfg = &e->cfg;
-	e->bank.omega = 1.0f - expf (-2.0 * M_PI * 1.0 / (double) cfg->sample_rate);   // spectrumlv2.c:98
-	if (!(cfg->meters & MTR_METER_SPECTR30)) return MTR_OK;
 	const uint32_t S = cfg->n_streams;
 	std::vector<double> c (MTR_NBANDS * 6 * 5);
 	for (uint32_t b = 0; b < MTR_NBANDS; ++b) {
@@ -283,8 +281,9 @@ int bank_create (mtr_engine* e)
 	return MTR_OK;
 }
 
-int bank_reset (mtr_engine* e, hipStream_t st)
+static int bank_reset (mtr_engine* e)
 {
+	const hipStream_t st = e->last_stream;
 	HIPCHK (hipMemsetAsync (e->bank.z.p, 0, e->bank.z.n * sizeof (double), st));
 	HIPCHK (hipMemsetAsync (e->bank.val.p, 0, e->bank.val.n * sizeof (float), st));
 	HIPCHK (hipMemsetAsync (e->bank.max.p, 0, e->bank.max.n * sizeof (float), st));
@@ -294,7 +293,7 @@ int bank_reset (mtr_engine* e, hipStream_t st)
 	return MTR_OK;
 }
 
-int bank_step (mtr_engine* e, const Call& c, Cursors& nx)
+static int bank_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
 {
 	const size_t vo = c.off;
 	mtr_bank_args ba;
@@ -307,13 +306,15 @@ int bank_step (mtr_engine* e, const Call& c, Cursors& nx)
 	return MTR_OK;
 }
 
-void bank_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void bank_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	v.push_back ({ e->bank.z.p, (size_t) MTR_NBANDS * 12 * sizeof (double) });
 	v.push_back ({ e->bank.val.p, (size_t) MTR_NBANDS * sizeof (float) });
 	v.push_back ({ e->bank.max.p, (size_t) MTR_NBANDS * sizeof (float) });
 	v.push_back ({ e->bank.ac[e->pos.bank_ac_cur].p, sizeof (int32_t) });
 }
+
+constinit SideMeter bank_meter = { MTR_METER_SPECTR30, 0, nullptr, bank_create, bank_reset, bank_step, bank_sections, nullptr };
 
 extern "C" {
 

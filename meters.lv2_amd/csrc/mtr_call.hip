@@ -107,21 +107,14 @@ template <typename A> static void set_kweight (const mtr_engine* e, A& a)
 	else for (int c = 0; c < MTR_MAX_CHANNELS; ++c) a.gain[c] = CHAN_GAIN[c];
 }
 
-// every per-meter limit is checked before anything is launched or any host-side state moves: the first row that applies answers
+// every per-meter limit is checked before anything is launched or any host-side state moves: the first that applies answers — the side
+// meters' in the order of their table, then the core's
 static int check_limits (const mtr_engine* e, uint64_t n_frames)
 {
-	static const struct { uint32_t meters; uint64_t limit; const char* text; } lim[] = {
-		{ MTR_METER_BITSTATS | MTR_METER_SIGDIST, 0x7fffffffull, "BITSTATS / SIGDIST: n_frames per call must be < 2^31 - 1" },
-		{ MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
-		{ MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
-		{ MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
-		{ MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)" },
-		{ MTR_METER_SCOPE, 0x7fffffffull, "SCOPE: n_frames per call must be < 2^31 - 1" },
-		{ MTR_METER_TPBALLIST, 0x7ffff000ull, "TPBALLIST: n_frames per call must be < 2^31 - 4096" },
-		{ MTR_METER_EBU | MTR_METER_TRUEPEAK, 0xFFFFFFFFull, "n_frames per call must be < 2^32 - 1" },
-	};
-	for (const auto& l : lim)
-		if ((e->cfg.meters & l.meters) && n_frames >= l.limit) return fail (MTR_ERR_ARG, l.text);
+	for (const SideMeter* m : SIDE_METERS)
+		if ((e->cfg.meters & m->bits) && m->max_frames && n_frames >= m->max_frames) return fail (MTR_ERR_ARG, m->max_text);
+	if ((e->cfg.meters & MTR_METER_TPBALLIST) && n_frames >= 0x7ffff000ull) return fail (MTR_ERR_ARG, "TPBALLIST: n_frames per call must be < 2^31 - 4096");
+	if ((e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)) && n_frames >= 0xFFFFFFFFull) return fail (MTR_ERR_ARG, "n_frames per call must be < 2^32 - 1");
 	return MTR_OK;
 }
 
@@ -479,15 +472,9 @@ struct CallRun {
 		}
 		if ((rc = mark (4, c.st))) return rc;
 
-		if ((meters & MTR_METER_SPECTR30) && (rc = bank_step (e, c, nx))) return rc;
 		const StreamEnds se { d_ends, d_fall };                       // (null on a dense call)
-		if ((meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) && (rc = intstat_step (e, c, nx, se))) return rc;
-		if ((meters & MTR_METER_DR14) && (rc = dr14_step (e, c, nx, se))) return rc;
-		if ((meters & MTR_METER_KMETER) && (rc = kmeter_step (e, c, nx, se))) return rc;
-		if ((meters & MTR_METER_STCORR) && (rc = stcorr_step (e, c, nx))) return rc;
-		if ((meters & MTR_METER_NEEDLE) && (rc = needle_step (e, c, nx))) return rc;
-		if ((meters & MTR_METER_SURROUND) && (rc = surround_step (e, c, nx))) return rc;
-		if ((meters & MTR_METER_SCOPE) && (rc = scope_step (e, c, nx))) return rc;
+		for (const SideMeter* m : SIDE_METERS)
+			if ((meters & m->bits) && (rc = m->step (e, c, nx, se))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, a side meter's LEN kernel, or the fused kernels)

@@ -231,7 +231,7 @@ static int mtr_launch_dr14 (const mtr_dr14_args& a, void* stream)
 
 // ---- DR14 in the engine: the call's step, the blob's sections, reset, the results ------------------------------------------------------
 
-int dr14_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
+static int dr14_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	mtr_dr14_args da;
@@ -251,11 +251,13 @@ int dr14_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 	return MTR_OK;
 }
 
-void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	v.push_back ({ e->dr.state.p, sizeof (mtr_dr14_state) });
 	v.push_back ({ e->dr.hist.p, (size_t) e->cfg.n_channels * MTR_DR_HISTBINS * sizeof (uint32_t) });
 }
+
+constinit SideMeter dr14_meter = { MTR_METER_DR14, 0, nullptr, nullptr, mtr_engine_dr14_reset, dr14_step, dr14_sections, nullptr };
 
 extern "C" {
 

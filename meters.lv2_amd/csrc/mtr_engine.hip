@@ -168,6 +168,35 @@ int wait_stream (mtr_engine* e)
 	return MTR_OK;
 }
 
+int series_configure_check (const mtr_engine* e, const char* who, uint32_t period, uint32_t min_period, const char* min_text)
+{
+	char text[160];
+	if (period && (period < min_period || period >= 0x7fffffffu)) {
+		snprintf (text, sizeof (text), "%s: a period is 0 or at least %s frames", who, min_text);
+		return fail (MTR_ERR_ARG, text);
+	}
+	if (e->advanced) {
+		snprintf (text, sizeof (text), "%s: only on an engine that has processed nothing since create / reset", who);
+		return fail (MTR_ERR_STATE, text);
+	}
+	return MTR_OK;
+}
+
+int series_ring (DevBuf<float>& ring, size_t n, const char* what)
+{
+	if (!n) return MTR_OK;
+	if (ring.reserve (n)) return fail (MTR_ERR_NOMEM, what);
+	HIPCHK (hipMemset (ring.p, 0, n * sizeof (float)));
+	return MTR_OK;
+}
+
+int series_fetch (float* out, const float* src, size_t width, uint32_t first, uint32_t cap, uint32_t capacity, size_t take, uint32_t count)
+{
+	HIPCHK (hipMemcpy2D (out, (size_t) capacity * width * sizeof (float), src + (size_t) first * cap * width, (size_t) cap * width * sizeof (float),
+	                     take * width * sizeof (float), count, hipMemcpyDeviceToHost));
+	return MTR_OK;
+}
+
 extern "C" {
 
 const char* mtr_last_error (void) { return g_err.c_str (); }
@@ -276,8 +305,7 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	e->fragm = (uint32_t) ((int) cfg->sample_rate / 20);     // ebu_r128_proc.cc:170
 	e->pos.frcnt = e->fragm;
 	mtr_setup_kweight (cfg->sample_rate, e->kw);
-	stcorr_create (e);
-	if (cfg->meters & MTR_METER_SURROUND) surround_create (e);
+	(void) mtr_engine_spectr_set_speed (e, 1.0f);              // (spectrumlv2.c:98; every engine has one: a state blob's header carries it)
 
 	const uint32_t S = cfg->n_streams;
 	int rc = MTR_OK;
@@ -297,9 +325,8 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 		if (e->gate_max.reserve (m.size ())) rc = fail (MTR_ERR_NOMEM, "hipMalloc gate scratch");
 		else if (hipMemcpy (e->gate_max.p, m.data (), m.size () * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail (MTR_ERR_HIP, "hipMemcpy gate scratch");
 	}
-	if (rc == MTR_OK) rc = bank_create (e);
-	if (rc == MTR_OK && (cfg->meters & MTR_METER_NEEDLE)) rc = needle_create (e);
-	if (rc == MTR_OK && (cfg->meters & MTR_METER_SCOPE)) rc = scope_create (e);
+	for (const SideMeter* m : SIDE_METERS)
+		if (rc == MTR_OK && (cfg->meters & m->bits) && m->create) rc = m->create (e);
 	if (rc != MTR_OK) { mtr_engine_destroy (e); return rc; }
 	rc = mtr_engine_reset (e);
 	if (rc != MTR_OK) { mtr_engine_destroy (e); return rc; }     // never an error code together with a live handle
@@ -333,7 +360,6 @@ int mtr_engine_reset (mtr_engine* e)
 		const int trc = mc_tp_clear (e, st);
 		if (trc) return trc;
 	}
-	if (e->cfg.meters & MTR_METER_SPECTR30) { const int brc = bank_reset (e, st); if (brc) return brc; }
 	e->pos.frcnt = e->fragm;
 	e->integr = false;
 	e->advanced = false;
@@ -343,14 +369,9 @@ int mtr_engine_reset (mtr_engine* e)
 	e->pos.hist_cur = 0;
 	e->last_n_frag = 0;
 	e->last_deferred = false;
-	if (e->cfg.meters & MTR_METER_DR14) { const int drc = mtr_engine_dr14_reset (e); if (drc) return drc; }
-	if (e->cfg.meters & MTR_METER_KMETER) { const int krc = mtr_engine_kmeter_reset (e); if (krc) return krc; e->pos.km_fpp = 0; e->pos.km_fall = 0.f; }
-	if (e->cfg.meters & MTR_METER_STCORR) { const int src = mtr_engine_stcorr_reset (e); if (src) return src; }
-	if (e->cfg.meters & MTR_METER_NEEDLE) { const int nrc = mtr_engine_needle_reset (e); if (nrc) return nrc; }
-	if (e->cfg.meters & MTR_METER_SURROUND) { const int urc = mtr_engine_surround_reset (e); if (urc) return urc; }
-	if (e->cfg.meters & MTR_METER_SCOPE) { const int prc = mtr_engine_scope_reset (e); if (prc) return prc; }
-	if (e->ll.period) { const int lrc = loudlog_reset (e, st); if (lrc) return lrc; }
-	if (e->cfg.meters & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) return mtr_engine_intstat_reset (e);
+	for (const SideMeter* m : SIDE_METERS)
+		if ((e->cfg.meters & m->bits) && (rc = m->reset (e))) return rc;
+	if (e->ll.period) return loudlog_reset (e, st);
 	return MTR_OK;
 }
 

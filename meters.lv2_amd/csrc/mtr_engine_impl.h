@@ -12,6 +12,7 @@
 
 #include "mtr_internal.h"
 #include "mtr_host.h"
+#include "mtr_series.h"
 
 #pragma GCC visibility push(hidden)   // (cross-TU helpers, not ABI)
 
@@ -93,7 +94,8 @@ struct Plan {
 
 // The lock-step cursors: where the streams of the engine stand between two process calls.  A call reads them, computes their
 // successors as it goes and stores them in ONE place, behind its last launch (CallRun::run) — a chunk of a host call that is
-// not the last stores nothing, nor does a call that fails.  A cursor added here needs no other book-keeping.
+// not the last stores nothing, nor does a call that fails.  That is all the CALL PATH needs of a cursor added here; whose it is — a side
+// meter's, as a rule — resets it in its reset hook and, if a state blob has to carry it, puts it into its blob header (struct SideMeter).
 struct Cursors {
 	uint32_t frcnt = 0;           // frames remaining in the open fragment
 	int      hist_cur = 0;        // which of fir_hist [2] / mc_hist [2] holds the 47 frames before the next call
@@ -101,13 +103,8 @@ struct Cursors {
 	uint64_t dr_scnt = 0;         // samples in the open DR-14 window
 	uint32_t km_fpp = 0;          // Kmeterdsp's frames per period and the fall-back factor that goes with it
 	float    km_fall = 0.f;
-	uint64_t sc_fill = 0;         // STCORR: frames in the open period of the reading series ...
-	uint64_t sc_points = 0;       // ... and periods completed since reset
-	uint32_t nd_fill = 0;         // NEEDLE: frames in the open period of the reading series ...
-	uint64_t nd_points = 0;       // ... and periods completed since reset (what the series does not hold of them is dropped)
-	uint64_t su_fill = 0;         // SURROUND: frames in the open block of the reading series ...
-	uint64_t su_points = 0;       // ... blocks completed since reset ...
-	uint32_t su_fpp = 0;          // ... and its Kmeterdsps' frames per period with the fall-back factor that goes with it
+	SeriesPos sc, nd, su;         // STCORR, NEEDLE, SURROUND: where their reading series stand (mtr_series.h)
+	uint32_t su_fpp = 0;          // SURROUND: its Kmeterdsps' frames per period with the fall-back factor that goes with it
 	float    su_fall = 0.f;
 	uint32_t sp_fill = 0;         // SCOPE: frames since the last analysis ...
 	uint64_t sp_analyses = 0;     // ... and analyses completed since reset
@@ -257,14 +254,15 @@ struct mtr_engine {
 		DevBuf<mtr_stcorr_state>   state;       // [S]
 		DevBuf<double>             piece;       // [S][pieces][MTR_STCORR_PIECE]
 		DevBuf<float>              series;      // [S][cap]
-		uint32_t                   period = 0, cap = 0;   // frames per process () of the series (0: the call), points per stream it holds
+		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
 		float                      w[2];        // w1, w2 of Stcorrdsp::init
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
 	} sc;
 	struct Needle {                             // NEEDLE (mtr_needle.hip)
 		DevBuf<unsigned char>      state;       // [S] of { mtr_needle_hdr, mtr_needle_state [kinds][C] }
 		DevBuf<float>              series;      // [kinds][S][cap][C]
-		uint32_t                   kinds = 0, period = 0, cap = 0;   // MTR_NEEDLE_* selected, frames per process () of the series (0: the call), points per stream and kind
+		uint32_t                   kinds = 0;   // MTR_NEEDLE_* selected
+		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream and kind
 		uint32_t                   kind[4] = { 0, 0, 0, 0 };         // the selected kinds in the order of their bits ...
 		float                      w[4][4];     // ... and their w1 w2 w3 g
 		float                      db[2], mv[2];   // Msppmdsp's gains, M and S: a control (it survives a reset)
@@ -273,7 +271,7 @@ struct mtr_engine {
 		DevBuf<mtr_sur_state>      state;       // [S]
 		DevBuf<double>             piece;       // [S][pieces][MTR_SUR_PIECE]
 		DevBuf<float>              s_level, s_peak, s_corr;   // [S][cap][C], [S][cap][C], [S][cap][4]
-		uint32_t                   period = 0, cap = 0;   // frames per sur_run of the series (0: the call), points per stream it holds
+		SeriesCfg                  ser;         // frames per sur_run of the series (0: the call), points per stream it holds
 		uint8_t                    pa[4] = { 0, 0, 0, 0 }, pb[4] = { 0, 0, 0, 0 };   // the pairs' channels: a control (it survives a reset)
 		float                      w[2];        // w1, w2 of Stcorrdsp::init
 		double                     pw[3];       // Kmeterdsp's A per group of four frames
@@ -345,58 +343,52 @@ int meter_range (const mtr_engine* e, bool has, const char* none, uint32_t first
 // ... then the engine's device selected and its stream waited for
 int wait_stream (mtr_engine* e);
 
-// ---- a side meter's hooks: create-time set-up (where it has one), its step of a call, its sections of the state blob --------------
-// A step queues the meter's kernels for the view of call `c` and moves the meter's cursors in `nx` (CallRun::run stores them).
-int  bank_create (mtr_engine* e);
-int  bank_reset (mtr_engine* e, hipStream_t st);
-int  bank_step (mtr_engine* e, const Call& c, Cursors& nx);
-void bank_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  intstat_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
-void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  dr14_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
-void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
+// ---- the reading series on the device (mtr_series.h has the part that needs no device) -----------------------------------------------
+// What `who` (an entry point that sets P) refuses: MTR_ERR_ARG unless `period` is 0 or min_period (in words: min_text) .. 2^31 - 2 frames,
+// MTR_ERR_STATE on an engine that has processed something since create / reset
+int series_configure_check (const mtr_engine* e, const char* who, uint32_t period, uint32_t min_period, const char* min_text);
+// a ring of n floats, zeroed (n = 0: nothing); `what`: the text of MTR_ERR_NOMEM
+int series_ring (DevBuf<float>& ring, size_t n, const char* what);
+// `take` points of `width` floats of each of `count` streams from `first` on: rows of `cap` points at `src` to rows of `capacity` at `out`
+int series_fetch (float* out, const float* src, size_t width, uint32_t first, uint32_t cap, uint32_t capacity, size_t take, uint32_t count);
+
+// ---- a side meter as the engine, a call and the state blob see it ------------------------------------------------------------------
+// The part of a meter's per-stream entry of the blob that the HOST owns (configuration and cursors: the blob's own header has no room
+// for them): `bytes` bytes at `offset` of every stream's entry of the meter's first section, the same in all of them.  mtr_state.hip
+// stages, compares and copies the bytes; the hooks give them their meaning.  `h`: `bytes` bytes of a buffer of the host's, aligned for
+// any type (write: zeroed), which a hook may read or fill as the struct they are.
+struct BlobHeader {
+	size_t      offset, bytes;
+	const char* corrupt;                                          // MTR_ERR_STATE text: the streams' headers differ
+	void (*write) (const mtr_engine* e, void* h);                 // export: the host's copies rule, not whatever the device's entry holds
+	int  (*check) (const mtr_engine* e, const void* h, bool fresh);   // import: MTR_ERR_STATE with the text set if `h` is corrupt, not the
+	                                                              // engine's configuration or — `fresh` false — not where the engine stands
+	void (*take) (mtr_engine* e, const void* h);                  // import into a fresh engine, after the copies succeeded
+};
+// One row per side meter, in the order of SIDE_METERS: the order of the blob's sections and of a call's steps.  A hook runs only in an
+// engine that has one of `bits`.
+struct SideMeter {
+	uint32_t    bits;                                             // MTR_METER_*
+	uint64_t    max_frames;                                       // a call of this many frames or more is refused (0: no limit of its own) ...
+	const char* max_text;                                         // ... with this text
+	int  (*create) (mtr_engine* e);                               // create-time set-up, or null
+	int  (*reset) (mtr_engine* e);                                // the meter's part of mtr_engine_reset: its state and its cursors in e->pos (where the
+	                                                              // meter has a reset of its own in the C ABI, that entry point)
+	// queues the meter's kernels for the view of call `c` and moves the meter's cursors in `nx` (CallRun::run stores them)
+	int  (*step) (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
+	void (*sections) (const mtr_engine* e, std::vector<StateSection>& v);   // appends the arrays a stream carries from call to call
+	const BlobHeader* hdr;                                        // in the first of them, or null
+};
+// (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
+// scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
+extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter;
+inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter };
+
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
-void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v);
-void stcorr_create (mtr_engine* e);
-int  stcorr_step (mtr_engine* e, const Call& c, Cursors& nx);
-void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  needle_create (mtr_engine* e);
-int  needle_step (mtr_engine* e, const Call& c, Cursors& nx);
-void needle_sections (const mtr_engine* e, std::vector<StateSection>& v);
-void surround_create (mtr_engine* e);
-int  surround_step (mtr_engine* e, const Call& c, Cursors& nx);
-void surround_sections (const mtr_engine* e, std::vector<StateSection>& v);
-int  scope_create (mtr_engine* e);
-int  scope_step (mtr_engine* e, const Call& c, Cursors& nx);
-void scope_sections (const mtr_engine* e, std::vector<StateSection>& v);
-// STCORR's section of a blob carries the period and the frames into the open one in every stream's entry (the header has no room for
-// them).  Export writes the host's copies into the `count` entries at `sec`; import checks the entries (MTR_ERR_STATE with the text set if
-// they are corrupt or — `fresh` false — not where the engine stands) and returns the two.
-// the loudness log: what the gate of a call that starts at cursors `pos` appends to, for the view [off, off + cnt) (false: the log is off);
-// its part of mtr_engine_reset
+// the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view
+// [off, off + cnt) (false: the log is off); its part of mtr_engine_reset
 bool loudlog_args (const mtr_engine* e, const Cursors& pos, uint32_t off, mtr_loudlog_args* out);
 int  loudlog_reset (mtr_engine* e, hipStream_t st);
-void stcorr_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
-int  stcorr_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* period, uint32_t* fill);
-// NEEDLE's section likewise: kinds, period, the frames into the open period and the two gains in front of every stream's detectors.  A blob
-// whose kinds or period are not the engine's is refused (MTR_ERR_STATE); a fresh engine takes the rest (needle_take_cursors)
-void needle_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
-int  needle_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, mtr_needle_hdr* out);
-void needle_take_cursors (mtr_engine* e, const mtr_needle_hdr* h);
-size_t needle_hdr_bytes (void);
-// SURROUND's section likewise: period, the frames into the open block, _fpp / _fall and the pairs in front of every stream's entry.  A
-// fresh engine takes them (surround_take_cursors, from the surround_hdr_bytes () that _import_cursors wrote to `out`); any other must
-// stand at the same period, fill and pairs
-void surround_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
-int  surround_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, unsigned char* out);
-void surround_take_cursors (mtr_engine* e, const unsigned char* hdr);
-size_t surround_hdr_bytes (void);
-// SCOPE's sections are the blob's last scope_n_sections (); the first of them carries window, hop, threshold, the frames since the last
-// analysis and the analyses counted in every stream's entry.  The configuration must be the engine's; a fresh engine takes the cursors
-size_t scope_n_sections (void);
-void scope_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count);
-int  scope_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* fill, uint64_t* analyses);
 
 #pragma GCC visibility pop
 

@@ -182,7 +182,7 @@ static int mtr_launch_sigdist (const float* audio, uint64_t stride, uint64_t n_f
 
 // (the integer tables are int32, as the reference's, which stops counting at 2^31 - 1 samples; the kernels index
 // a call's samples with 32 bits: checked on entry)
-int intstat_step (mtr_engine* e, const Call& c, Cursors&, const StreamEnds& se)
+static int intstat_step (mtr_engine* e, const Call& c, Cursors&, const StreamEnds& se)
 {
 	if (e->cfg.meters & MTR_METER_BITSTATS)
 		if (mtr_launch_bitstats (c.audio, c.stride, c.n_frames, e->is.bim.p + c.off, c.cnt, se.ends, c.st)) return fail (MTR_ERR_HIP, "k_bitstats launch");
@@ -191,12 +191,15 @@ int intstat_step (mtr_engine* e, const Call& c, Cursors&, const StreamEnds& se)
 	return MTR_OK;
 }
 
-void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	const uint32_t m = e->cfg.meters;
 	if (m & MTR_METER_BITSTATS) v.push_back ({ e->is.bim.p, sizeof (mtr_bitstats_state) });
 	if (m & MTR_METER_SIGDIST) v.push_back ({ e->is.sdh.p, sizeof (mtr_sigdist_state) });
 }
+
+constinit SideMeter intstat_meter = { MTR_METER_BITSTATS | MTR_METER_SIGDIST, 0x7fffffffull, "BITSTATS / SIGDIST: n_frames per call must be < 2^31 - 1",
+                                            nullptr, mtr_engine_intstat_reset, intstat_step, intstat_sections, nullptr };
 
 extern "C" {
 

@@ -230,7 +230,7 @@ float kmeter_fall (const mtr_engine* e, uint64_t n)
 	return powf (10.0f, -0.05f * 15.0f * ((float) n / e->cfg.sample_rate));
 }
 
-int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
+static int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	mtr_kmeter_args ka;
@@ -253,10 +253,13 @@ int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se
 	return MTR_OK;
 }
 
-void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	v.push_back ({ e->km.state.p, 2 * sizeof (mtr_kmeter_state) });
 }
+
+constinit SideMeter kmeter_meter = { MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                           nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr };
 
 extern "C" {
 
@@ -270,6 +273,8 @@ int mtr_engine_kmeter_reset (mtr_engine* e)
 	mtr_kmeter_powers (9.72f / e->cfg.sample_rate, e->km.pw1);           // kmeterdsp.cc:52
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemset (e->km.state.p, 0, n * sizeof (mtr_kmeter_state)));   // :142-146
+	e->pos.km_fpp = 0;                                                   // (the next process () works its fall-back factor out again)
+	e->pos.km_fall = 0.f;
 	return MTR_OK;
 }
 

@@ -392,6 +392,7 @@ static int mtr_launch_needle (const mtr_needle_args& a, uint32_t n_channels, voi
 
 // ---- NEEDLE in the engine: set-up, the call's step, the blob's section and the cursors in it, the C entry points ------------------------
 
+constexpr uint32_t NEEDLE_MIN_PERIOD = 16;                      // frames: the shortest period of the reading series
 static uint32_t needle_count (const mtr_engine* e) { return (uint32_t) __builtin_popcount (e->nd.kinds); }
 static size_t needle_pitch (const mtr_engine* e)
 {
@@ -406,10 +407,10 @@ static void needle_coefs (mtr_engine* e)
 		if (e->nd.kinds & k) { e->nd.kind[i] = k; mtr_setup_needle (k, e->cfg.sample_rate, e->nd.w[i]); ++i; }
 }
 
-int needle_create (mtr_engine* e)
+static int needle_create (mtr_engine* e)
 {
 	e->nd.kinds = MTR_NEEDLE_IEC2;
-	e->nd.period = 0; e->nd.cap = 0;
+	e->nd.ser = {};
 	e->nd.db[0] = e->nd.db[1] = 0.f; e->nd.mv[0] = e->nd.mv[1] = 1.0f;   // msppmdsp.cc:34-43 ...
 	needle_coefs (e);
 	int rc = mtr_engine_needle_set_gain (e, 0, -6.f);                     // ... and src/meters.cc:211-212
@@ -417,9 +418,9 @@ int needle_create (mtr_engine* e)
 	return rc;
 }
 
-int needle_step (mtr_engine* e, const Call& c, Cursors& nx)
+static int needle_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
 {
-	const uint32_t P = e->nd.period, C = e->cfg.n_channels;
+	const uint32_t P = e->nd.ser.period, cap = e->nd.ser.cap, C = e->cfg.n_channels;
 	mtr_needle_args a;
 	memset (&a, 0, sizeof (a));
 	a.audio = c.audio; a.stride = c.stride; a.n_frames = c.n_frames;
@@ -427,65 +428,56 @@ int needle_step (mtr_engine* e, const Call& c, Cursors& nx)
 	memcpy (a.kind, e->nd.kind, sizeof (a.kind));
 	memcpy (a.w, e->nd.w, sizeof (a.w));
 	a.mv[0] = e->nd.mv[0]; a.mv[1] = e->nd.mv[1];
-	a.period = P ? P : (uint32_t) c.n_frames; a.fill = P ? e->pos.nd_fill : 0; a.series = P != 0;
-	a.capacity = e->nd.cap; a.point0 = e->pos.nd_points;
+	a.period = P ? P : (uint32_t) c.n_frames; a.fill = P ? (uint32_t) e->pos.nd.fill : 0; a.series = P != 0;
+	a.capacity = cap; a.point0 = e->pos.nd.points;
 	a.state_pitch = (uint32_t) needle_pitch (e);
 	a.state = e->nd.state.p + (size_t) c.off * a.state_pitch;
-	a.kind_pitch = (uint64_t) e->cfg.n_streams * e->nd.cap * C;
-	a.points = P && e->nd.cap ? e->nd.series.p + (size_t) c.off * e->nd.cap * C : nullptr;
+	a.kind_pitch = (uint64_t) e->cfg.n_streams * cap * C;
+	a.points = P && cap ? e->nd.series.p + (size_t) c.off * cap * C : nullptr;
 	if (!a.points) a.capacity = 0;
 	if (mtr_launch_needle (a, C, c.st)) return fail (MTR_ERR_HIP, "k_needle launch");
-	const uint64_t tot = (uint64_t) e->pos.nd_fill + c.n_frames;
-	nx.nd_fill = P ? (uint32_t) (tot % P) : 0;
-	nx.nd_points = e->pos.nd_points + (P ? tot / P : 0);
+	nx.nd = series_advance (e->pos.nd, P, c.n_frames);
 	return MTR_OK;
 }
 
-void needle_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void needle_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	v.push_back ({ e->nd.state.p, needle_pitch (e) });
 }
 
-void needle_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
+// The blob header: mtr_needle_hdr in front of every stream's detectors.  A blob whose kinds or period are not the engine's is refused; a
+// fresh engine takes the rest
+constexpr const char* NEEDLE_CORRUPT = "mtr_engine_state_import: corrupt blob (cursors of the needle meters)";
+
+static void needle_hdr_write (const mtr_engine* e, void* out)
 {
-	const size_t pitch = needle_pitch (e);
-	for (uint32_t k = 0; k < count; ++k) {
-		mtr_needle_hdr h;
-		memset (&h, 0, sizeof (h));
-		h.kinds = e->nd.kinds; h.period = e->nd.period; h.fill = e->pos.nd_fill;
-		memcpy (h.db, e->nd.db, sizeof (h.db)); memcpy (h.mv, e->nd.mv, sizeof (h.mv));
-		memcpy (sec + (size_t) k * pitch, &h, sizeof (h));
-	}
+	mtr_needle_hdr& h = *static_cast<mtr_needle_hdr*> (out);       // (zeroed: so stays the pad)
+	h.kinds = e->nd.kinds; h.period = e->nd.ser.period; h.fill = (uint32_t) e->pos.nd.fill;
+	memcpy (h.db, e->nd.db, sizeof (h.db)); memcpy (h.mv, e->nd.mv, sizeof (h.mv));
 }
 
-int needle_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, mtr_needle_hdr* out)
+static int needle_hdr_check (const mtr_engine* e, const void* in, bool fresh)
 {
-	const size_t pitch = needle_pitch (e);
-	mtr_needle_hdr h0;
-	memset (&h0, 0, sizeof (h0));
-	for (uint32_t k = 0; k < count; ++k) {
-		mtr_needle_hdr h;
-		memcpy (&h, sec + (size_t) k * pitch, sizeof (h));
-		if (k == 0) h0 = h;
-		if (memcmp (&h, &h0, sizeof (h)) || (h.period ? h.fill >= h.period || h.period < 16 : h.fill != 0) || !h.kinds || (h.kinds & ~15u)
-		    || !(h.mv[0] >= 0.f) || !(h.mv[1] >= 0.f))
-			return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (cursors of the needle meters)");
-	}
-	if (h0.kinds != e->nd.kinds || h0.period != e->nd.period)
+	const mtr_needle_hdr& h = *static_cast<const mtr_needle_hdr*> (in);
+	if (!series_blob_ok (h.period, h.fill, NEEDLE_MIN_PERIOD, 0xFFFFFFFFu) || !h.kinds || (h.kinds & ~15u) || !(h.mv[0] >= 0.f) || !(h.mv[1] >= 0.f))
+		return fail (MTR_ERR_STATE, NEEDLE_CORRUPT);
+	if (h.kinds != e->nd.kinds || h.period != e->nd.ser.period)
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the blob's needle meters are configured otherwise (kinds or period)");
-	if (!fresh && (h0.fill != e->pos.nd_fill || memcmp (h0.db, e->nd.db, sizeof (h0.db)) || memcmp (h0.mv, e->nd.mv, sizeof (h0.mv))))
+	if (!fresh && (h.fill != e->pos.nd.fill || memcmp (h.db, e->nd.db, sizeof (h.db)) || memcmp (h.mv, e->nd.mv, sizeof (h.mv))))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period or gains of the needle meters)");
-	*out = h0;
 	return MTR_OK;
 }
 
-void needle_take_cursors (mtr_engine* e, const mtr_needle_hdr* h)
+static void needle_hdr_take (mtr_engine* e, const void* in)
 {
-	e->pos.nd_fill = h->fill;
-	memcpy (e->nd.db, h->db, sizeof (h->db)); memcpy (e->nd.mv, h->mv, sizeof (h->mv));
+	const mtr_needle_hdr& h = *static_cast<const mtr_needle_hdr*> (in);
+	e->pos.nd.fill = h.fill;
+	memcpy (e->nd.db, h.db, sizeof (h.db)); memcpy (e->nd.mv, h.mv, sizeof (h.mv));
 }
 
-size_t needle_hdr_bytes (void) { return sizeof (mtr_needle_hdr); }
+static constinit BlobHeader needle_hdr = { 0, sizeof (mtr_needle_hdr), NEEDLE_CORRUPT, needle_hdr_write, needle_hdr_check, needle_hdr_take };
+constinit SideMeter needle_meter = { MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                           needle_create, mtr_engine_needle_reset, needle_step, needle_sections, &needle_hdr };
 
 extern "C" {
 
@@ -516,8 +508,7 @@ int mtr_engine_needle_reset (mtr_engine* e)
 		}
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemcpy (e->nd.state.p, h.data (), h.size (), hipMemcpyHostToDevice));
-	e->pos.nd_fill = 0;
-	e->pos.nd_points = 0;
+	e->pos.nd = {};
 	return MTR_OK;
 }
 
@@ -528,16 +519,12 @@ int mtr_engine_needle_configure (mtr_engine* e, uint32_t kinds, uint32_t period_
 		return fail (MTR_ERR_ARG, "mtr_engine_needle_configure: kinds is a non-empty subset of MTR_NEEDLE_VU | _IEC1 | _IEC2 | _MS");
 	if ((kinds & MTR_NEEDLE_MS) && e->cfg.n_channels != 2)
 		return fail (MTR_ERR_UNSUPPORTED, "MTR_NEEDLE_MS meters the sum and the difference of a stereo pair: n_channels 2");
-	if (period_frames && (period_frames < 16 || period_frames >= 0x7fffffffu))
-		return fail (MTR_ERR_ARG, "mtr_engine_needle_configure: a period is 0 or at least 16 frames");
-	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_needle_configure: only on an engine that has processed nothing since create / reset");
-	{ const int rc = wait_stream (e); if (rc) return rc; }
-	const size_t n = period_frames ? (size_t) __builtin_popcount (kinds) * e->cfg.n_streams * capacity_points * e->cfg.n_channels : 0;
-	if (n && e->nd.series.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc NEEDLE series");
-	if (n) HIPCHK (hipMemset (e->nd.series.p, 0, n * sizeof (float)));
+	int rc = series_configure_check (e, "mtr_engine_needle_configure", period_frames, NEEDLE_MIN_PERIOD, "16");
+	if (rc || (rc = wait_stream (e))) return rc;
+	const uint32_t cap = period_frames ? capacity_points : 0;     // (no period, no series)
+	if ((rc = series_ring (e->nd.series, (size_t) __builtin_popcount (kinds) * e->cfg.n_streams * cap * e->cfg.n_channels, "hipMalloc NEEDLE series"))) return rc;
 	e->nd.kinds = kinds;
-	e->nd.period = period_frames;
-	e->nd.cap = period_frames ? capacity_points : 0;
+	e->nd.ser = { period_frames, cap };
 	needle_coefs (e);
 	return mtr_engine_needle_reset (e);
 }
@@ -569,7 +556,7 @@ int mtr_engine_needle_read (mtr_engine* e, uint32_t kind, uint32_t first, uint32
 			unsigned char* const at = h.data () + (size_t) i * pitch + sizeof (mtr_needle_hdr) + ((size_t) ki * C + c) * sizeof (mtr_needle_state);
 			mtr_needle_state v;
 			memcpy (&v, at, sizeof (v));
-			if (e->nd.period) level[(size_t) i * C + c] = v.last;
+			if (e->nd.ser.period) level[(size_t) i * C + c] = v.last;
 			else {
 				level[(size_t) i * C + c] = g * v.m;                      // read (): _res = true; return _g * _m
 				v.res = 1;
@@ -577,7 +564,7 @@ int mtr_engine_needle_read (mtr_engine* e, uint32_t kind, uint32_t first, uint32
 			}
 			if (state) { state[((size_t) i * C + c) * 2] = v.s1; state[((size_t) i * C + c) * 2 + 1] = v.s2; }
 		}
-	if (count && !e->nd.period) HIPCHK (hipMemcpy (e->nd.state.p + (size_t) first * pitch, h.data (), h.size (), hipMemcpyHostToDevice));
+	if (count && !e->nd.ser.period) HIPCHK (hipMemcpy (e->nd.state.p + (size_t) first * pitch, h.data (), h.size (), hipMemcpyHostToDevice));
 	return MTR_OK;
 }
 
@@ -587,17 +574,11 @@ int mtr_engine_needle_series (mtr_engine* e, uint32_t kind, uint32_t first, uint
 	if (rc) return rc;
 	const int ki = kind_index (e->nd.kinds, kind);
 	if (ki < 0) return fail (MTR_ERR_ARG, "mtr_engine_needle_series: kind is one of the engine's selected kinds");
-	const uint64_t n = e->pos.nd_points, kept = std::min<uint64_t> (n, e->nd.cap);
-	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
-	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
-	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	const size_t take = series_counts (e->pos.nd.points, e->nd.ser.cap, capacity, n_points, dropped);
 	if (!out || !count || !take) return MTR_OK;
 	if ((rc = wait_stream (e))) return rc;
 	const size_t C = e->cfg.n_channels;
-	const float* const src = e->nd.series.p + ((size_t) ki * e->cfg.n_streams + first) * e->nd.cap * C;
-	HIPCHK (hipMemcpy2D (out, (size_t) capacity * C * sizeof (float), src, (size_t) e->nd.cap * C * sizeof (float),
-	                     take * C * sizeof (float), count, hipMemcpyDeviceToHost));
-	return MTR_OK;
+	return series_fetch (out, e->nd.series.p + (size_t) ki * e->cfg.n_streams * e->nd.ser.cap * C, C, first, e->nd.ser.cap, capacity, take, count);
 }
 
 } // extern "C"

@@ -286,9 +286,9 @@ uint32_t default_hop (const mtr_engine* e) { return (uint32_t) ceil ((double) e-
 
 // ---- SCOPE in the engine: set-up, the call's step, the blob's sections and the cursors in them, the C entry points ------------------------
 
-int scope_create (mtr_engine* e) { return configure (e, W_DEFAULT, default_hop (e), 1e-6f); }   // stereoscope.c:641, phasewheel.c:1212
+static int scope_create (mtr_engine* e) { return configure (e, W_DEFAULT, default_hop (e), 1e-6f); }   // stereoscope.c:641, phasewheel.c:1212
 
-int scope_step (mtr_engine* e, const Call& c, Cursors& nx)
+static int scope_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
 {
 	const mtr_engine::Scope& sp = e->sp;
 	const size_t vo = c.off, B = sp.W / 2;
@@ -306,7 +306,7 @@ int scope_step (mtr_engine* e, const Call& c, Cursors& nx)
 	return MTR_OK;
 }
 
-void scope_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void scope_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	const mtr_engine::Scope& sp = e->sp;
 	const size_t B = sp.W / 2;
@@ -318,31 +318,35 @@ void scope_sections (const mtr_engine* e, std::vector<StateSection>& v)
 	v.push_back ({ sp.power_r.p, B * sizeof (float) });
 }
 
-size_t scope_n_sections (void) { return 9; }
+// The blob header: the whole entry of the first section — window, hop, threshold, the frames since the last analysis and the analyses
+// counted.  The configuration must be the engine's; a fresh engine takes the cursors
+constexpr const char* SCOPE_CORRUPT = "mtr_engine_state_import: corrupt blob (cursor of the SCOPE analyses)";
 
-void scope_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
+static void scope_hdr_write (const mtr_engine* e, void* out)
 {
-	const mtr_scope_hdr h = { e->sp.W, e->sp.H, e->sp.thresh, e->pos.sp_fill, e->pos.sp_analyses };
-	for (uint32_t k = 0; k < count; ++k) memcpy (sec + (size_t) k * sizeof (h), &h, sizeof (h));
+	*static_cast<mtr_scope_hdr*> (out) = { e->sp.W, e->sp.H, e->sp.thresh, e->pos.sp_fill, e->pos.sp_analyses };
 }
 
-int scope_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* fill, uint64_t* analyses)
+static int scope_hdr_check (const mtr_engine* e, const void* in, bool fresh)
 {
-	mtr_scope_hdr h0;
-	for (uint32_t k = 0; k < count; ++k) {
-		mtr_scope_hdr h;
-		memcpy (&h, sec + (size_t) k * sizeof (h), sizeof (h));
-		if (k == 0) h0 = h;
-		if (memcmp (&h, &h0, sizeof (h)) || h.hop < H_MIN || h.hop > H_MAX || h.fill >= h.hop)
-			return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (cursor of the SCOPE analyses)");
-	}
-	if (h0.window != e->sp.W || h0.hop != e->sp.H || memcmp (&h0.thresh, &e->sp.thresh, sizeof (float)))
+	const mtr_scope_hdr& h = *static_cast<const mtr_scope_hdr*> (in);
+	if (h.hop < H_MIN || h.hop > H_MAX || h.fill >= h.hop) return fail (MTR_ERR_STATE, SCOPE_CORRUPT);
+	if (h.window != e->sp.W || h.hop != e->sp.H || memcmp (&h.thresh, &e->sp.thresh, sizeof (float)))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the blob's SCOPE configuration (window, hop, threshold) is not the engine's");
-	if (!fresh && h0.fill != e->pos.sp_fill)
+	if (!fresh && h.fill != e->pos.sp_fill)
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (hop of the SCOPE analyses)");
-	*fill = h0.fill; *analyses = h0.analyses;
 	return MTR_OK;
 }
+
+static void scope_hdr_take (mtr_engine* e, const void* in)
+{
+	const mtr_scope_hdr& h = *static_cast<const mtr_scope_hdr*> (in);
+	e->pos.sp_fill = h.fill; e->pos.sp_analyses = h.analyses;
+}
+
+static constinit BlobHeader scope_hdr = { 0, sizeof (mtr_scope_hdr), SCOPE_CORRUPT, scope_hdr_write, scope_hdr_check, scope_hdr_take };
+constinit SideMeter scope_meter = { MTR_METER_SCOPE, 0x7fffffffull, "SCOPE: n_frames per call must be < 2^31 - 1",
+                                          scope_create, mtr_engine_scope_reset, scope_step, scope_sections, &scope_hdr };
 
 extern "C" {
 

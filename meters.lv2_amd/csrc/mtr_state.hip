@@ -1,6 +1,7 @@
 // mtr_state.hip — per-stream state as a blob: checkpoint / resume, re-sharding (mtr_engine_state_bytes / _export / _import,
 // mtr_state_blob_count).  The blob is a header with the engine's lock-step cursors and, per array a stream carries from call to call,
-// the streams' entries back to back; which arrays, and what is in them, is the meters' business (their *_sections hooks).
+// the streams' entries back to back; which arrays, and what is in them, is the meters' business (the sections hook of their rows in
+// SIDE_METERS), as is the meaning of the configuration and cursors that some of them keep in their entries (the rows' BlobHeader).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -32,59 +33,42 @@ uint64_t fnv1a64 (const unsigned char* p, size_t n)
 	return h;
 }
 
+constexpr size_t N_SIDE = sizeof (SIDE_METERS) / sizeof (SIDE_METERS[0]);
+
 // every array a stream carries from call to call, in the blob's order (a function of the configuration alone): the core's, then the
-// side meters' in the order the meters came to the engine
-std::vector<StateSection> state_sections (const mtr_engine* e)
+// side meters' in the order of SIDE_METERS — with the core's per-channel arrays of layout 8, which came to the blob before STCORR did,
+// in front of STCORR's.  first[i]: the index of the first section of side meter i, if the engine has it.
+std::vector<StateSection> state_sections (const mtr_engine* e, size_t* first = nullptr)
 {
 	std::vector<StateSection> v;
-	const uint32_t m = e->cfg.meters;
 	v.push_back ({ e->state.p, sizeof (mtr_stream_state) });
 	v.push_back ({ e->hist.p, (size_t) 2 * MTR_HIST_LEN * sizeof (int32_t) });
 	v.push_back ({ e->fir_hist[e->pos.hist_cur].p, (size_t) MTR_FIR_HALO * 2 * sizeof (float) });
-	if (m & MTR_METER_SPECTR30) bank_sections (e, v);
-	if (m & (MTR_METER_BITSTATS | MTR_METER_SIGDIST)) intstat_sections (e, v);
-	if (m & MTR_METER_DR14) dr14_sections (e, v);
-	if (m & MTR_METER_KMETER) kmeter_sections (e, v);
-	if (e->layout == 8) {                                      // the per-channel side buffers (stereo blobs are unchanged)
-		const size_t C = e->cfg.n_channels;
-		v.push_back ({ e->mc_kz.p, C * 4 * sizeof (float) });
-		v.push_back ({ e->mc_hist[e->pos.hist_cur].p, (size_t) MTR_FIR_HALO * C * sizeof (float) });
-		v.push_back ({ e->mc_tp_last.p, C * sizeof (float) });
-		v.push_back ({ e->mc_tp_hold.p, C * sizeof (float) });
+	for (size_t i = 0; i < N_SIDE; ++i) {
+		if (SIDE_METERS[i] == &stcorr_meter && e->layout == 8) {   // the per-channel side buffers (stereo blobs are unchanged)
+			const size_t C = e->cfg.n_channels;
+			v.push_back ({ e->mc_kz.p, C * 4 * sizeof (float) });
+			v.push_back ({ e->mc_hist[e->pos.hist_cur].p, (size_t) MTR_FIR_HALO * C * sizeof (float) });
+			v.push_back ({ e->mc_tp_last.p, C * sizeof (float) });
+			v.push_back ({ e->mc_tp_hold.p, C * sizeof (float) });
+		}
+		if (!(e->cfg.meters & SIDE_METERS[i]->bits)) continue;
+		if (first) first[i] = v.size ();
+		SIDE_METERS[i]->sections (e, v);
 	}
-	// (the LAST section, and only of an engine with the bit: every other blob is byte for byte what it was.  The header has no room
-	// for the period and the frames into the open one: they travel in every stream's entry, stcorr_export_cursors / _import_cursors)
-	if (m & MTR_METER_STCORR) stcorr_sections (e, v);
-	// (behind it, likewise: kinds, period, cursor and gains in every stream's entry, needle_export_cursors / _import_cursors)
-	if (m & MTR_METER_NEEDLE) needle_sections (e, v);
-	// (and the surround meter's — never beside those two, which meter one or two channels: period, cursor, _fpp and pairs in every stream's
-	// entry, surround_export_cursors / _import_cursors)
-	if (m & MTR_METER_SURROUND) surround_sections (e, v);
-	// (and the scope's — a stereo meter, so behind STCORR's and NEEDLE's: configuration and cursors in every stream's entry of the first of
-	// them, scope_export_cursors / _import_cursors)
-	if (m & MTR_METER_SCOPE) scope_sections (e, v);
 	return v;
 }
 
-// where the entries of section `idx` start in the payload of a blob of `count` streams
-size_t section_offset (const std::vector<StateSection>& secs, size_t idx, uint32_t count)
+// The host-owned headers of the side meters in a payload of `count` streams: where the first stream's header of meter i is, and the
+// pitch from one stream's to the next (null: the engine has no such meter, or the meter no header)
+struct HeaderAt { unsigned char* p; size_t pitch; };
+HeaderAt header_at (const mtr_engine* e, const std::vector<StateSection>& secs, const size_t* first, size_t i, uint32_t count, const unsigned char* payload)
 {
-	size_t o = 0;
-	for (size_t i = 0; i < idx; ++i) o += (size_t) count * secs[i].elem;
-	return o;
-}
-
-// SCOPE's sections are the last ones, STCORR's and NEEDLE's in front of them, in this order; SURROUND's (3 .. 8 channels: never in their
-// engine) is the last one
-size_t scope_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - scope_n_sections (); }
-size_t surround_section (const mtr_engine*, const std::vector<StateSection>& secs) { return secs.size () - 1; }
-size_t needle_section (const mtr_engine* e, const std::vector<StateSection>& secs)
-{
-	return secs.size () - 1 - ((e->cfg.meters & MTR_METER_SCOPE) ? scope_n_sections () : 0);
-}
-size_t stcorr_section (const mtr_engine* e, const std::vector<StateSection>& secs)
-{
-	return needle_section (e, secs) - ((e->cfg.meters & MTR_METER_NEEDLE) ? 1 : 0);
+	const BlobHeader* const hd = SIDE_METERS[i]->hdr;
+	if (!hd || !(e->cfg.meters & SIDE_METERS[i]->bits)) return { nullptr, 0 };
+	size_t o = hd->offset;
+	for (size_t k = 0; k < first[i]; ++k) o += (size_t) count * secs[k].elem;
+	return { const_cast<unsigned char*> (payload) + o, secs[first[i]].elem };
 }
 
 size_t state_per_stream (const mtr_engine* e)
@@ -130,16 +114,21 @@ int mtr_engine_state_export (mtr_engine* e, uint32_t first, uint32_t count, void
 	h.frcnt = e->pos.frcnt; h.integr = e->integr ? 1u : 0u; h.omega = e->bank.omega; h.dr_scnt = e->pos.dr_scnt;
 	unsigned char* const o0 = static_cast<unsigned char*> (blob) + sizeof (h);
 	unsigned char* o = o0;
-	const std::vector<StateSection> secs = state_sections (e);
+	size_t sec0[N_SIDE] = {};
+	const std::vector<StateSection> secs = state_sections (e, sec0);
 	for (const StateSection& s : secs) {
 		if (count) HIPCHK (hipMemcpy (o, static_cast<const unsigned char*> (s.base) + (size_t) first * s.elem, (size_t) count * s.elem, hipMemcpyDeviceToHost));
 		o += (size_t) count * s.elem;
 	}
-	// the host's cursors, not whatever the device copy holds
-	if (e->cfg.meters & MTR_METER_STCORR) stcorr_export_cursors (e, o0 + section_offset (secs, stcorr_section (e, secs), count), count);
-	if (e->cfg.meters & MTR_METER_NEEDLE) needle_export_cursors (e, o0 + section_offset (secs, needle_section (e, secs), count), count);
-	if (e->cfg.meters & MTR_METER_SURROUND) surround_export_cursors (e, o0 + section_offset (secs, surround_section (e, secs), count), count);
-	if (e->cfg.meters & MTR_METER_SCOPE) scope_export_cursors (e, o0 + section_offset (secs, scope_section (e, secs), count), count);
+	// the side meters' headers: the host's copies, not whatever the device's entries hold
+	std::vector<unsigned char> hb;
+	for (size_t i = 0; i < N_SIDE; ++i) {
+		const HeaderAt at = header_at (e, secs, sec0, i, count, o0);
+		if (!at.p) continue;
+		hb.assign (SIDE_METERS[i]->hdr->bytes, 0);
+		SIDE_METERS[i]->hdr->write (e, hb.data ());
+		for (uint32_t k = 0; k < count; ++k) memcpy (at.p + (size_t) k * at.pitch, hb.data (), hb.size ());
+	}
 	h.payload_fnv = fnv1a64 (o0, (size_t) (o - o0));
 	memcpy (blob, &h, sizeof (h));
 	return MTR_OK;
@@ -171,28 +160,17 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	// speed included, whatever integr_start / spectr_set_speed said before: they are part of where the streams stand — any other
 	// must stand at the same ones
 	const bool fresh = !e->advanced;
-	const std::vector<StateSection> secs = state_sections (e);
-	uint32_t sc_period = e->sc.period, sc_fill = (uint32_t) e->pos.sc_fill;
-	if ((e->cfg.meters & MTR_METER_STCORR) && h.count) {
-		rc = stcorr_import_cursors (e, i0 + section_offset (secs, stcorr_section (e, secs), h.count), h.count, fresh, &sc_period, &sc_fill);
-		if (rc) return rc;
-	}
-	std::vector<unsigned char> nd_hdr (needle_hdr_bytes ());
-	const bool nd_take = (e->cfg.meters & MTR_METER_NEEDLE) && h.count;
-	if (nd_take) {
-		rc = needle_import_cursors (e, i0 + section_offset (secs, needle_section (e, secs), h.count), h.count, fresh, reinterpret_cast<mtr_needle_hdr*> (nd_hdr.data ()));
-		if (rc) return rc;
-	}
-	std::vector<unsigned char> su_hdr (surround_hdr_bytes ());
-	const bool su_take = (e->cfg.meters & MTR_METER_SURROUND) && h.count;
-	if (su_take) {
-		rc = surround_import_cursors (e, i0 + section_offset (secs, surround_section (e, secs), h.count), h.count, fresh, su_hdr.data ());
-		if (rc) return rc;
-	}
-	uint32_t sp_fill = e->pos.sp_fill;
-	uint64_t sp_analyses = e->pos.sp_analyses;
-	if ((e->cfg.meters & MTR_METER_SCOPE) && h.count) {
-		rc = scope_import_cursors (e, i0 + section_offset (secs, scope_section (e, secs), h.count), h.count, fresh, &sp_fill, &sp_analyses);
+	size_t sec0[N_SIDE] = {};
+	const std::vector<StateSection> secs = state_sections (e, sec0);
+	// the side meters' headers, in the order of SIDE_METERS: every stream's equals the first's, and that one is one the engine can take
+	std::vector<unsigned char> staged[N_SIDE];
+	for (size_t i = 0; i < N_SIDE && h.count; ++i) {
+		const HeaderAt at = header_at (e, secs, sec0, i, h.count, i0);
+		if (!at.p) continue;
+		const BlobHeader* const hd = SIDE_METERS[i]->hdr;
+		staged[i].assign (at.p, at.p + hd->bytes);
+		if (!blob_headers_agree (at.p, at.pitch, hd->bytes, h.count)) return fail (MTR_ERR_STATE, hd->corrupt);
+		rc = hd->check (e, staged[i].data (), fresh);
 		if (rc) return rc;
 	}
 	if (!fresh && (e->pos.frcnt != h.frcnt || e->integr != (h.integr != 0) || e->bank.omega != h.omega || e->pos.dr_scnt != h.dr_scnt))
@@ -211,10 +189,8 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;
-		e->sc.period = sc_period; e->pos.sc_fill = sc_fill;
-		if (nd_take) needle_take_cursors (e, reinterpret_cast<const mtr_needle_hdr*> (nd_hdr.data ()));
-		if (su_take) surround_take_cursors (e, su_hdr.data ());
-		e->pos.sp_fill = sp_fill; e->pos.sp_analyses = sp_analyses;
+		for (size_t i = 0; i < N_SIDE; ++i)
+			if (!staged[i].empty ()) SIDE_METERS[i]->hdr->take (e, staged[i].data ());
 		e->plan.valid = false;
 		e->advanced = true;
 	}

@@ -320,65 +320,66 @@ static int mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream)
 
 // ---- STCORR in the engine: set-up, the call's step, the blob's section and the cursors in it, the C entry points -----------------------
 
-void stcorr_create (mtr_engine* e)
+static uint32_t stcorr_min_period (const mtr_engine* e) { return (uint32_t) e->cfg.sample_rate / 20; }
+
+static int stcorr_create (mtr_engine* e)
 {
 	mtr_setup_stcorr (e->cfg.sample_rate, e->sc.w);
 	mtr_stcorr_geometry (e->sc.w[0], &e->sc.warm, &e->sc.chunk);
-}
-
-// The periods of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
-int stcorr_step (mtr_engine* e, const Call& c, Cursors& nx)
-{
-	const size_t vo = c.off;
-	const uint64_t P = e->sc.period;
-	mtr_stcorr_args sa;
-	sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
-	sa.period = P; sa.e0 = P ? P - e->pos.sc_fill : c.n_frames;
-	sa.n_streams = c.cnt; sa.chunk = e->sc.chunk; sa.warm = e->sc.warm;
-	sa.n_pieces = mtr_sc::n_pieces (c.n_frames, sa.e0, P, sa.chunk);
-	sa.w1 = e->sc.w[0]; sa.w2 = e->sc.w[1];
-	sa.capacity = e->sc.cap; sa.point0 = e->pos.sc_points;
-	if (e->sc.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_STCORR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR pieces");
-	sa.state = e->sc.state.p + vo; sa.piece = e->sc.piece.p + vo * sa.n_pieces * MTR_STCORR_PIECE;
-	sa.series = e->sc.cap ? e->sc.series.p + vo * e->sc.cap : nullptr;
-	if (mtr_launch_stcorr (sa, c.st)) return fail (MTR_ERR_HIP, "k_stcorr launch");
-	const uint64_t tot = e->pos.sc_fill + c.n_frames;
-	nx.sc_fill = P ? tot % P : 0;
-	nx.sc_points = e->pos.sc_points + (P ? tot / P : 0);
 	return MTR_OK;
 }
 
-void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v)
+// The periods of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+static int stcorr_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
+{
+	const size_t vo = c.off;
+	const uint64_t P = e->sc.ser.period;
+	const uint32_t cap = e->sc.ser.cap;
+	mtr_stcorr_args sa;
+	sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
+	sa.period = P; sa.e0 = series_e0 (e->pos.sc, P, c.n_frames);
+	sa.n_streams = c.cnt; sa.chunk = e->sc.chunk; sa.warm = e->sc.warm;
+	sa.n_pieces = mtr_sc::n_pieces (c.n_frames, sa.e0, P, sa.chunk);
+	sa.w1 = e->sc.w[0]; sa.w2 = e->sc.w[1];
+	sa.capacity = cap; sa.point0 = e->pos.sc.points;
+	if (e->sc.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_STCORR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR pieces");
+	sa.state = e->sc.state.p + vo; sa.piece = e->sc.piece.p + vo * sa.n_pieces * MTR_STCORR_PIECE;
+	sa.series = cap ? e->sc.series.p + vo * cap : nullptr;
+	if (mtr_launch_stcorr (sa, c.st)) return fail (MTR_ERR_HIP, "k_stcorr launch");
+	nx.sc = series_advance (e->pos.sc, P, c.n_frames);
+	return MTR_OK;
+}
+
+static void stcorr_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	v.push_back ({ e->sc.state.p, sizeof (mtr_stcorr_state) });
 }
 
-void stcorr_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
-{
-	for (uint32_t k = 0; k < count; ++k) {
-		mtr_stcorr_state v;
-		unsigned char* const at = sec + (size_t) k * sizeof (v);
-		memcpy (&v, at, sizeof (v));
-		v.period = e->sc.period; v.fill = (uint32_t) e->pos.sc_fill;
-		memcpy (at, &v, sizeof (v));
-	}
-}
+// The blob header: the period and the frames into the open one, the last two fields of every stream's entry
+struct StcorrHdr { uint32_t period, fill; };
+static_assert (offsetof (mtr_stcorr_state, fill) == offsetof (mtr_stcorr_state, period) + 4 && sizeof (mtr_stcorr_state) == offsetof (mtr_stcorr_state, period) + sizeof (StcorrHdr), "StcorrHdr");
+constexpr const char* STCORR_CORRUPT = "mtr_engine_state_import: corrupt blob (period of the STCORR series)";
 
-int stcorr_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, uint32_t* period, uint32_t* fill)
+static void stcorr_hdr_write (const mtr_engine* e, void* out) { *static_cast<StcorrHdr*> (out) = { e->sc.ser.period, (uint32_t) e->pos.sc.fill }; }
+
+static int stcorr_hdr_check (const mtr_engine* e, const void* in, bool fresh)
 {
-	uint32_t sc_period = 0, sc_fill = 0;
-	for (uint32_t k = 0; k < count; ++k) {
-		mtr_stcorr_state v;
-		memcpy (&v, sec + (size_t) k * sizeof (v), sizeof (v));
-		if (k == 0) { sc_period = v.period; sc_fill = v.fill; }
-		if (v.period != sc_period || v.fill != sc_fill || (sc_period ? sc_fill >= sc_period || sc_period < (uint32_t) e->cfg.sample_rate / 20 : sc_fill != 0))
-			return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (period of the STCORR series)");
-	}
-	if (!fresh && (sc_period != e->sc.period || sc_fill != e->pos.sc_fill))
+	const StcorrHdr& h = *static_cast<const StcorrHdr*> (in);
+	if (!series_blob_ok (h.period, h.fill, stcorr_min_period (e), 0xFFFFFFFFu)) return fail (MTR_ERR_STATE, STCORR_CORRUPT);
+	if (!fresh && (h.period != e->sc.ser.period || h.fill != e->pos.sc.fill))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period of the STCORR series)");
-	*period = sc_period; *fill = sc_fill;
 	return MTR_OK;
 }
+
+static void stcorr_hdr_take (mtr_engine* e, const void* in)
+{
+	const StcorrHdr& h = *static_cast<const StcorrHdr*> (in);
+	e->sc.ser.period = h.period; e->pos.sc.fill = h.fill;
+}
+
+static constinit BlobHeader stcorr_hdr = { offsetof (mtr_stcorr_state, period), sizeof (StcorrHdr), STCORR_CORRUPT, stcorr_hdr_write, stcorr_hdr_check, stcorr_hdr_take };
+constinit SideMeter stcorr_meter = { MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                           stcorr_create, mtr_engine_stcorr_reset, stcorr_step, stcorr_sections, &stcorr_hdr };
 
 extern "C" {
 
@@ -400,26 +401,20 @@ int mtr_engine_stcorr_reset (mtr_engine* e)
 	if (e->sc.state.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR state");
 	std::vector<mtr_stcorr_state> h (S);
 	memset (h.data (), 0, S * sizeof (mtr_stcorr_state));          // stcorrdsp.cc:33-36
-	for (auto& v : h) v.period = e->sc.period;
+	for (auto& v : h) v.period = e->sc.ser.period;
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemcpy (e->sc.state.p, h.data (), S * sizeof (mtr_stcorr_state), hipMemcpyHostToDevice));
-	e->pos.sc_fill = 0;
-	e->pos.sc_points = 0;
+	e->pos.sc = {};
 	return MTR_OK;
 }
 
 int mtr_engine_stcorr_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
 {
 	if (no_stcorr (e)) return fail (MTR_ERR_ARG, "no STCORR in this engine");
-	if (period_frames && (period_frames < (uint32_t) e->cfg.sample_rate / 20 || period_frames >= 0x7fffffffu))
-		return fail (MTR_ERR_ARG, "mtr_engine_stcorr_set_period: a period is 0 or at least (uint32_t) sample_rate / 20 frames");
-	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_stcorr_set_period: only on an engine that has processed nothing since create / reset");
-	{ const int rc = wait_stream (e); if (rc) return rc; }
-	const size_t n = (size_t) e->cfg.n_streams * capacity_points;
-	if (n && e->sc.series.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR series");
-	if (n) HIPCHK (hipMemset (e->sc.series.p, 0, n * sizeof (float)));
-	e->sc.period = period_frames;
-	e->sc.cap = capacity_points;
+	int rc = series_configure_check (e, "mtr_engine_stcorr_set_period", period_frames, stcorr_min_period (e), "(uint32_t) sample_rate / 20");
+	if (rc || (rc = wait_stream (e))) return rc;
+	if ((rc = series_ring (e->sc.series, (size_t) e->cfg.n_streams * capacity_points, "hipMalloc STCORR series"))) return rc;
+	e->sc.ser = { period_frames, capacity_points };
 	return mtr_engine_stcorr_reset (e);
 }
 
@@ -440,15 +435,10 @@ int mtr_engine_stcorr_series (mtr_engine* e, uint32_t first, uint32_t count, flo
 {
 	int rc = meter_range (e, !no_stcorr (e), "no STCORR in this engine", first, count);
 	if (rc) return rc;
-	const uint64_t n = e->pos.sc_points, kept = std::min<uint64_t> (n, e->sc.cap);
-	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
-	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
-	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	const size_t take = series_counts (e->pos.sc.points, e->sc.ser.cap, capacity, n_points, dropped);
 	if (!out || !count || !take) return MTR_OK;
 	if ((rc = wait_stream (e))) return rc;
-	HIPCHK (hipMemcpy2D (out, (size_t) capacity * sizeof (float), e->sc.series.p + (size_t) first * e->sc.cap, (size_t) e->sc.cap * sizeof (float),
-	                     take * sizeof (float), count, hipMemcpyDeviceToHost));
-	return MTR_OK;
+	return series_fetch (out, e->sc.series.p, 1, first, e->sc.ser.cap, capacity, take, count);
 }
 
 } // extern "C"

@@ -522,7 +522,9 @@ static int mtr_launch_sur (const mtr_sur_args& a, void* stream)
 
 static uint32_t sur_pairs (const mtr_engine* e) { return e->cfg.n_channels > 3 ? 4u : 3u; }
 
-void surround_create (mtr_engine* e)
+static uint32_t sur_min_period (const mtr_engine* e) { return (uint32_t) e->cfg.sample_rate / 20; }
+
+static int surround_create (mtr_engine* e)
 {
 	const uint32_t C = e->cfg.n_channels;
 	mtr_setup_stcorr (e->cfg.sample_rate, e->su.w);
@@ -545,17 +547,19 @@ void surround_create (mtr_engine* e)
 	for (uint32_t p = 0; p < MTR_SUR_PAIRS; ++p) {                 // the surround8 port defaults (lv2ttl/surmeter.h), clamped
 		e->su.pa[p] = (uint8_t) std::min (2 * p, C - 1); e->su.pb[p] = (uint8_t) std::min (2 * p + 1, C - 1);
 	}
+	return MTR_OK;
 }
 
 // The blocks of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
-int surround_step (mtr_engine* e, const Call& c, Cursors& nx)
+static int surround_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
 {
 	const size_t vo = c.off;
-	const uint64_t P = e->su.period;
+	const uint64_t P = e->su.ser.period;
+	const uint32_t cap = e->su.ser.cap;
 	mtr_sur_args sa;
 	memset (&sa, 0, sizeof (sa));
 	sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
-	sa.period = P; sa.e0 = P ? P - e->pos.su_fill : c.n_frames;
+	sa.period = P; sa.e0 = series_e0 (e->pos.su, P, c.n_frames);
 	sa.block = P ? P : c.n_frames;
 	sa.n_streams = c.cnt; sa.n_channels = e->cfg.n_channels; sa.n_pairs = sur_pairs (e);
 	sa.chunk = e->su.chunk; sa.warm = e->su.warm;
@@ -572,68 +576,62 @@ int surround_step (mtr_engine* e, const Call& c, Cursors& nx)
 	memcpy (sa.pw, e->su.pw, sizeof (sa.pw));
 	memcpy (&sa.k, e->su.k, sizeof (sa.k));
 	memcpy (sa.pa, e->su.pa, sizeof (sa.pa)); memcpy (sa.pb, e->su.pb, sizeof (sa.pb));
-	sa.capacity = e->su.cap; sa.point0 = e->pos.su_points;
+	sa.capacity = cap; sa.point0 = e->pos.su.points;
 	if (e->su.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_SUR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND pieces");
 	sa.state = e->su.state.p + vo; sa.piece = e->su.piece.p + vo * sa.n_pieces * MTR_SUR_PIECE;
-	if (e->su.cap) {
-		sa.s_level = e->su.s_level.p + vo * e->su.cap * sa.n_channels;
-		sa.s_peak = e->su.s_peak.p + vo * e->su.cap * sa.n_channels;
-		sa.s_corr = e->su.s_corr.p + vo * e->su.cap * MTR_SUR_PAIRS;
+	if (cap) {
+		sa.s_level = e->su.s_level.p + vo * cap * sa.n_channels;
+		sa.s_peak = e->su.s_peak.p + vo * cap * sa.n_channels;
+		sa.s_corr = e->su.s_corr.p + vo * cap * MTR_SUR_PAIRS;
 	}
 	if (mtr_launch_sur (sa, c.st)) return fail (MTR_ERR_HIP, "k_sur launch");
-	const uint64_t tot = e->pos.su_fill + c.n_frames;
-	nx.su_fill = P ? tot % P : 0;
-	nx.su_points = e->pos.su_points + (P ? tot / P : 0);
+	nx.su = series_advance (e->pos.su, P, c.n_frames);
 	return MTR_OK;
 }
 
-void surround_sections (const mtr_engine* e, std::vector<StateSection>& v)
+static void surround_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
 	v.push_back ({ e->su.state.p, sizeof (mtr_sur_state) });
 }
 
-void surround_export_cursors (const mtr_engine* e, unsigned char* sec, uint32_t count)
+// The blob header: period, the frames into the open block, _fpp / _fall and the pairs — what stands in front of `ch` in every stream's
+// entry.  A fresh engine takes them; any other must stand at the same period, fill and pairs
+constexpr size_t SUR_HDR_BYTES = offsetof (mtr_sur_state, ch);
+constexpr const char* SUR_CORRUPT = "mtr_engine_state_import: corrupt blob (period or pairs of the SURROUND meter)";
+
+static void surround_hdr_write (const mtr_engine* e, void* out)
 {
-	for (uint32_t k = 0; k < count; ++k) {
-		unsigned char* const at = sec + (size_t) k * sizeof (mtr_sur_state);
-		mtr_sur_state h;
-		memcpy (&h, at, offsetof (mtr_sur_state, ch));
-		h.period = e->su.period; h.fill = (uint32_t) e->pos.su_fill; h.fpp = e->pos.su_fpp; h.fall = e->pos.su_fall;
-		memcpy (h.pa, e->su.pa, sizeof (h.pa)); memcpy (h.pb, e->su.pb, sizeof (h.pb));
-		memcpy (at, &h, offsetof (mtr_sur_state, ch));
-	}
+	mtr_sur_state h;
+	memset (&h, 0, SUR_HDR_BYTES);
+	h.period = e->su.ser.period; h.fill = (uint32_t) e->pos.su.fill; h.fpp = e->pos.su_fpp; h.fall = e->pos.su_fall;
+	memcpy (h.pa, e->su.pa, sizeof (h.pa)); memcpy (h.pb, e->su.pb, sizeof (h.pb));
+	memcpy (out, &h, SUR_HDR_BYTES);
 }
 
-// checks the entries (MTR_ERR_STATE if they are corrupt or — `fresh` false — not where the engine stands); a fresh engine takes them
-int surround_import_cursors (const mtr_engine* e, const unsigned char* sec, uint32_t count, bool fresh, unsigned char* out)
+static int surround_hdr_check (const mtr_engine* e, const void* in, bool fresh)
 {
-	const size_t hb = offsetof (mtr_sur_state, ch);
 	const uint32_t C = e->cfg.n_channels;
-	mtr_sur_state h0;
-	memset (&h0, 0, sizeof (h0));
-	for (uint32_t k = 0; k < count; ++k) {
-		mtr_sur_state h;
-		memcpy (&h, sec + (size_t) k * sizeof (mtr_sur_state), hb);
-		if (k == 0) memcpy (&h0, &h, hb);
-		bool ok = memcmp (&h, &h0, hb) == 0 && (h.period ? h.fill < h.period && h.period >= (uint32_t) e->cfg.sample_rate / 20 && h.period < 0x7fffffffu : h.fill == 0);
-		for (int p = 0; p < MTR_SUR_PAIRS; ++p) ok = ok && h.pa[p] < C && h.pb[p] < C;
-		if (!ok) return fail (MTR_ERR_STATE, "mtr_engine_state_import: corrupt blob (period or pairs of the SURROUND meter)");
-	}
-	if (!fresh && (h0.period != e->su.period || h0.fill != e->pos.su_fill || memcmp (h0.pa, e->su.pa, sizeof (h0.pa)) || memcmp (h0.pb, e->su.pb, sizeof (h0.pb))))
+	mtr_sur_state h;
+	memcpy (&h, in, SUR_HDR_BYTES);
+	bool ok = series_blob_ok (h.period, h.fill, sur_min_period (e), 0x7ffffffeu);
+	for (int p = 0; p < MTR_SUR_PAIRS; ++p) ok = ok && h.pa[p] < C && h.pb[p] < C;
+	if (!ok) return fail (MTR_ERR_STATE, SUR_CORRUPT);
+	if (!fresh && (h.period != e->su.ser.period || h.fill != e->pos.su.fill || memcmp (h.pa, e->su.pa, sizeof (h.pa)) || memcmp (h.pb, e->su.pb, sizeof (h.pb))))
 		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period or pairs of the SURROUND meter)");
-	memcpy (out, &h0, hb);
 	return MTR_OK;
 }
 
-size_t surround_hdr_bytes (void) { return offsetof (mtr_sur_state, ch); }
-
-void surround_take_cursors (mtr_engine* e, const unsigned char* hdr)
+static void surround_hdr_take (mtr_engine* e, const void* in)
 {
 	mtr_sur_state h;
-	memcpy (&h, hdr, offsetof (mtr_sur_state, ch));
-	e->su.period = h.period; e->pos.su_fill = h.fill; e->pos.su_fpp = h.fpp; e->pos.su_fall = h.fall;
+	memcpy (&h, in, SUR_HDR_BYTES);
+	e->su.ser.period = h.period; e->pos.su.fill = h.fill; e->pos.su_fpp = h.fpp; e->pos.su_fall = h.fall;
 	memcpy (e->su.pa, h.pa, sizeof (h.pa)); memcpy (e->su.pb, h.pb, sizeof (h.pb));
 }
+
+static constinit BlobHeader surround_hdr = { 0, SUR_HDR_BYTES, SUR_CORRUPT, surround_hdr_write, surround_hdr_check, surround_hdr_take };
+constinit SideMeter surround_meter = { MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                             surround_create, mtr_engine_surround_reset, surround_step, surround_sections, &surround_hdr };
 
 extern "C" {
 
@@ -649,8 +647,7 @@ int mtr_engine_surround_reset (mtr_engine* e)
 	if (e->su.state.reserve (S)) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND state");
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemset (e->su.state.p, 0, S * sizeof (mtr_sur_state)));   // kmeterdsp.cc:33-40, stcorrdsp.cc:33-36
-	e->pos.su_fill = 0;
-	e->pos.su_points = 0;
+	e->pos.su = {};
 	e->pos.su_fpp = 0;
 	e->pos.su_fall = 0.f;
 	return MTR_OK;
@@ -659,7 +656,7 @@ int mtr_engine_surround_reset (mtr_engine* e)
 int mtr_engine_surround_set_pairs (mtr_engine* e, const uint8_t* a4, const uint8_t* b4)
 {
 	if (no_sur (e) || !a4 || !b4) return fail (MTR_ERR_ARG, e && (e->cfg.meters & MTR_METER_SURROUND) ? "mtr_engine_surround_set_pairs: null argument" : NO_SUR);
-	if (e->su.period && e->pos.su_fill) return fail (MTR_ERR_STATE, "mtr_engine_surround_set_pairs: a block of the reading series is open");
+	if (e->su.ser.period && e->pos.su.fill) return fail (MTR_ERR_STATE, "mtr_engine_surround_set_pairs: a block of the reading series is open");
 	const uint8_t top = (uint8_t) (e->cfg.n_channels - 1);
 	for (int p = 0; p < MTR_SUR_PAIRS; ++p) {                      // surmeter.c:124-125
 		e->su.pa[p] = std::min (a4[p], top); e->su.pb[p] = std::min (b4[p], top);
@@ -678,19 +675,12 @@ int mtr_engine_surround_pairs (const mtr_engine* e, uint8_t* a4, uint8_t* b4)
 int mtr_engine_surround_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
 {
 	if (no_sur (e)) return fail (MTR_ERR_ARG, NO_SUR);
-	if (period_frames && (period_frames < (uint32_t) e->cfg.sample_rate / 20 || period_frames >= 0x7fffffffu))
-		return fail (MTR_ERR_ARG, "mtr_engine_surround_set_period: a period is 0 or at least (uint32_t) sample_rate / 20 frames");
-	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_surround_set_period: only on an engine that has processed nothing since create / reset");
-	{ const int rc = wait_stream (e); if (rc) return rc; }
+	int rc = series_configure_check (e, "mtr_engine_surround_set_period", period_frames, sur_min_period (e), "(uint32_t) sample_rate / 20");
+	if (rc || (rc = wait_stream (e))) return rc;
 	const size_t n = (size_t) e->cfg.n_streams * capacity_points, C = e->cfg.n_channels;
-	if (n && (e->su.s_level.reserve (n * C) || e->su.s_peak.reserve (n * C) || e->su.s_corr.reserve (n * MTR_SUR_PAIRS))) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND series");
-	if (n) {
-		HIPCHK (hipMemset (e->su.s_level.p, 0, n * C * sizeof (float)));
-		HIPCHK (hipMemset (e->su.s_peak.p, 0, n * C * sizeof (float)));
-		HIPCHK (hipMemset (e->su.s_corr.p, 0, n * MTR_SUR_PAIRS * sizeof (float)));
-	}
-	e->su.period = period_frames;
-	e->su.cap = capacity_points;
+	if ((rc = series_ring (e->su.s_level, n * C, "hipMalloc SURROUND series")) || (rc = series_ring (e->su.s_peak, n * C, "hipMalloc SURROUND series"))
+	    || (rc = series_ring (e->su.s_corr, n * MTR_SUR_PAIRS, "hipMalloc SURROUND series"))) return rc;
+	e->su.ser = { period_frames, capacity_points };
 	return mtr_engine_surround_reset (e);
 }
 
@@ -718,7 +708,7 @@ int mtr_engine_surround_read (mtr_engine* e, uint32_t first, uint32_t count, flo
 		if (corr) for (int p = 0; p < MTR_SUR_PAIRS; ++p) corr[(size_t) i * MTR_SUR_PAIRS + p] = h[i].pr[p].corr;
 	}
 	// (P = 0: Kmeterdsp::read arms the next process () to restart the rms maximum, kmeterdsp.cc:154)
-	if (!e->su.period && count) HIPCHK (hipMemcpy (e->su.state.p + first, h.data (), count * sizeof (mtr_sur_state), hipMemcpyHostToDevice));
+	if (!e->su.ser.period && count) HIPCHK (hipMemcpy (e->su.state.p + first, h.data (), count * sizeof (mtr_sur_state), hipMemcpyHostToDevice));
 	return MTR_OK;
 }
 
@@ -738,17 +728,13 @@ int mtr_engine_surround_series (mtr_engine* e, uint32_t first, uint32_t count, f
 {
 	int rc = meter_range (e, !no_sur (e), NO_SUR, first, count);
 	if (rc) return rc;
-	const uint64_t n = e->pos.su_points, kept = std::min<uint64_t> (n, e->su.cap);
-	if (n_points) *n_points = (uint32_t) std::min<uint64_t> (n, 0xFFFFFFFFull);
-	if (dropped) *dropped = (uint32_t) std::min<uint64_t> (n - kept, 0xFFFFFFFFull);
-	const size_t take = (size_t) std::min<uint64_t> (kept, capacity);
+	const size_t take = series_counts (e->pos.su.points, e->su.ser.cap, capacity, n_points, dropped);
 	if ((!level && !peak && !corr) || !count || !take) return MTR_OK;
 	if ((rc = wait_stream (e))) return rc;
 	const size_t C = e->cfg.n_channels;
 	const struct { float* out; const float* src; size_t w; } row[3] = { { level, e->su.s_level.p, C }, { peak, e->su.s_peak.p, C }, { corr, e->su.s_corr.p, MTR_SUR_PAIRS } };
 	for (const auto& q : row)
-		if (q.out) HIPCHK (hipMemcpy2D (q.out, (size_t) capacity * q.w * sizeof (float), q.src + (size_t) first * e->su.cap * q.w, (size_t) e->su.cap * q.w * sizeof (float),
-		                                take * q.w * sizeof (float), count, hipMemcpyDeviceToHost));
+		if (q.out && (rc = series_fetch (q.out, q.src, q.w, first, e->su.ser.cap, capacity, take, count))) return rc;
 	return MTR_OK;
 }
 

@@ -731,13 +731,20 @@ class Engine:
 
     def stcorr_series(self, first=0, count=None):
         """(points [count, kept], n_points, dropped): the readings after every completed period since reset that the series holds."""
+        (out,), n, d = self._series("stcorr_series", first, count, [()], lambda count, ptrs, *tail: lib.mtr_engine_stcorr_series(self._h, first, count, *ptrs, *tail))
+        return out, n, d
+
+    def _series(self, what, first, count, shapes, call):
+        """The two calls of a reading series' getter: ask for the counts, allocate one [count, kept] + shape array per entry of `shapes`,
+        fetch.  call (count, pointers, capacity, n_points, dropped) -> rc.  Returns ([arrays], n_points, dropped)."""
         count = self.n_streams - first if count is None else count
         n, d = C.c_uint32(), C.c_uint32()
-        _check(lib.mtr_engine_stcorr_series(self._h, first, count, None, 0, C.byref(n), C.byref(d)), "stcorr_series")
+        _check(call(count, [None] * len(shapes), 0, C.byref(n), C.byref(d)), what)
         kept = n.value - d.value
-        out = np.zeros((count, max(kept, 1)), np.float32)
-        _check(lib.mtr_engine_stcorr_series(self._h, first, count, out.ctypes.data, out.shape[1], C.byref(n), C.byref(d)), "stcorr_series")
-        return out[:, :kept], n.value, d.value
+        cap = max(kept, 1)
+        outs = [np.zeros((count, cap) + tuple(s), np.float32) for s in shapes]
+        _check(call(count, [o.ctypes.data for o in outs], cap, C.byref(n), C.byref(d)), what)
+        return [o[:, :kept] for o in outs], n.value, d.value
 
     def stcorr_reset(self):
         _check(lib.mtr_engine_stcorr_reset(self._h), "stcorr_reset")
@@ -763,13 +770,9 @@ class Engine:
 
     def needle_series(self, kind, first=0, count=None):
         """(points [count, kept, C], n_points, dropped): the readings of `kind` after every completed period since reset that the series holds."""
-        count = self.n_streams - first if count is None else count
-        n, d = C.c_uint32(), C.c_uint32()
-        _check(lib.mtr_engine_needle_series(self._h, int(kind), first, count, None, 0, C.byref(n), C.byref(d)), "needle_series")
-        kept = n.value - d.value
-        out = np.zeros((count, max(kept, 1), self.n_channels), np.float32)
-        _check(lib.mtr_engine_needle_series(self._h, int(kind), first, count, out.ctypes.data, out.shape[1], C.byref(n), C.byref(d)), "needle_series")
-        return out[:, :kept], n.value, d.value
+        (out,), n, d = self._series("needle_series", first, count, [(self.n_channels,)],
+                                    lambda count, ptrs, *tail: lib.mtr_engine_needle_series(self._h, int(kind), first, count, *ptrs, *tail))
+        return out, n, d
 
     def needle_reset(self):
         _check(lib.mtr_engine_needle_reset(self._h), "needle_reset")
@@ -813,17 +816,9 @@ class Engine:
     def surround_series(self, first=0, count=None):
         """(level [count, kept, C], peak [count, kept, C], corr [count, kept, 4], n_points, dropped): the ports after every completed
         block since reset that the series holds."""
-        count = self.n_streams - first if count is None else count
-        n, d = C.c_uint32(), C.c_uint32()
-        _check(lib.mtr_engine_surround_series(self._h, first, count, None, None, None, 0, C.byref(n), C.byref(d)), "surround_series")
-        kept = n.value - d.value
-        cap = max(kept, 1)
-        level = np.zeros((count, cap, self.n_channels), np.float32)
-        peak = np.zeros((count, cap, self.n_channels), np.float32)
-        corr = np.zeros((count, cap, 4), np.float32)
-        _check(lib.mtr_engine_surround_series(self._h, first, count, level.ctypes.data, peak.ctypes.data, corr.ctypes.data, cap,
-                                              C.byref(n), C.byref(d)), "surround_series")
-        return level[:, :kept], peak[:, :kept], corr[:, :kept], n.value, d.value
+        (level, peak, corr), n, d = self._series("surround_series", first, count, [(self.n_channels,), (self.n_channels,), (4,)],
+                                                 lambda count, ptrs, *tail: lib.mtr_engine_surround_series(self._h, first, count, *ptrs, *tail))
+        return level, peak, corr, n, d
 
     def surround_reset(self):
         _check(lib.mtr_engine_surround_reset(self._h), "surround_reset")

@@ -5,8 +5,10 @@ and processing continues BIT FOR BIT as if it had never stopped: every result of
 
 The reference has nothing like it (it persists one UI word, src/ebulv2.cc:514-553): this is what lets a multi-hour batch be
 checkpointed and the streams of a job be re-sharded between its ranks."""
+import hashlib
 import json
 import os
+import struct
 import subprocess
 import sys
 
@@ -218,6 +220,138 @@ def test_import_checks_the_blob_before_it_trusts_it(M):
     for k in want:
         assert np.array_equal(want[k], got[k], equal_nan=True), k
     assert want["counts"].sum() == 0                                       # integration stayed off, as in the blob
+
+
+# the blob's header: magic, version, header_bytes, meters, n_channels, rate, count, per_stream, stream_state_bytes, frcnt, integr, omega,
+# dr_scnt, and the FNV-1a (64 bit) of the payload behind it
+HDR = struct.Struct("<IIIIIfIIIIIfQQ")
+
+
+def _fnv1a64(b):
+    h = 0xcbf29ce484222325
+    for v in b:
+        h = ((h ^ v) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def _feed(e, x, calls, pos=0):
+    for n in calls:
+        e.process(np.ascontiguousarray(x[:, pos:pos + n]))
+        pos += n
+
+
+# The engine of the test below: three meters whose sections carry a host-owned header (STCORR at the end of its entry, NEEDLE in front
+# of a variable-pitch one, SCOPE as the whole entry of the first of nine sections) behind one that has none
+MIX_CALLS, MIX_STOP, MIX_KINDS = [5000, 7001, 9000, 4803], 2, ("NEEDLE_VU", "NEEDLE_IEC2")
+
+
+def _mix_engine(M, S=5):
+    e = M.Engine(S, 48000.0, M.METER_KMETER | M.METER_STCORR | M.METER_NEEDLE | M.METER_SCOPE)
+    e.stcorr_set_period(2400, 64)
+    e.needle_configure(M.NEEDLE_VU | M.NEEDLE_IEC2, 18, 4000)
+    e.scope_configure(256, 64)
+    return e
+
+
+def _mix_signal():
+    return np.stack([sig.g2(sum(MIX_CALLS), 900 + s) * np.float32(2.0 ** -(s % 3)) for s in range(5)])
+
+
+def _mix_record(M, e, first, count):
+    rec = {}
+    rec["sc_pts"], rec["sc_n"], _ = e.stcorr_series(first, count)
+    rec["sc_corr"], rec["sc_state"] = e.stcorr_read(first, count)
+    for k in MIX_KINDS:
+        rec[k + "_pts"], rec[k + "_n"], _ = e.needle_series(getattr(M, k), first, count)
+        rec[k + "_level"], rec[k + "_state"] = e.needle_read(getattr(M, k), first, count)
+    rec.update({"sp_" + k: v for k, v in e.scope_read(first, count).items()})
+    rec["sp_analyses"] = e.scope_analyses()
+    rec["km_rms"], rec["km_peak"] = e.kmeter_read(first, count)
+    return rec
+
+
+def test_several_header_carrying_meters_in_one_blob(M):
+    """KMETER | STCORR | NEEDLE | SCOPE in one engine: the blob's sections of the three meters that keep configuration and cursors in
+    their entries follow one another, so each must be found where it is.  Stopped inside a period of both series and inside a hop,
+    streams [2, 5) travel into slots [1, 4) of a fresh engine configured alike and go on bit for bit; a NEEDLE header that differs in
+    ONE stream is refused, by the checksum and — the checksum made to fit — by the comparison of the streams' headers."""
+    x = _mix_signal()
+    done = sum(MIX_CALLS[:MIX_STOP])
+    assert done % 2400 and done % 18 and done % 64                       # inside a period of each series, inside a hop
+    with _mix_engine(M) as e:
+        _feed(e, x, MIX_CALLS)
+        want = _mix_record(M, e, 2, 3)
+    with _mix_engine(M) as e:
+        _feed(e, x, MIX_CALLS[:MIX_STOP])
+        blob = e.state_export(2, 3)
+        assert e.state_bytes(3) == len(blob)
+    rest = np.zeros((5, x.shape[1] - done, 2), np.float32)
+    rest[1:4] = x[2:5, done:]
+    with _mix_engine(M) as e:
+        assert e.state_import(blob, first=1) == 3
+        assert e.state_export(1, 3) == blob                                # out again as it came in, before anything is processed
+        _feed(e, rest, MIX_CALLS[MIX_STOP:])
+        got = _mix_record(M, e, 1, 3)
+    assert want.keys() == got.keys()
+    for k, w in want.items():
+        if k.endswith("_n"):                                               # the points restart with the engine's
+            P = 2400 if k == "sc_n" else 18
+            assert got[k] == w - done // P, k
+        elif k.endswith("_pts"):
+            P = 2400 if k == "sc_pts" else 18
+            assert np.array_equal(got[k].view(np.uint32), w[:, done // P:].view(np.uint32)), k
+        else:
+            assert np.array_equal(np.asarray(got[k]).view(np.uint32), np.asarray(w).view(np.uint32)) if isinstance(w, np.ndarray) else got[k] == w, k
+    # NEEDLE's section stands behind the core's three arrays, KMETER's and STCORR's: what a KMETER | STCORR engine carries per stream
+    with M.Engine(1, 48000.0, M.METER_KMETER | M.METER_STCORR) as o:
+        before = o.state_bytes(1) - o.state_bytes(0)
+    pitch = 32 + 2 * 2 * 32                                                # mtr_needle_hdr + [kinds][channels] detectors
+    at = HDR.size + 3 * before + 1 * pitch                                 # stream 1's header: kinds, period, fill, pad
+    assert struct.unpack_from("<III", blob, at) == (M.NEEDLE_VU | M.NEEDLE_IEC2, 18, done % 18)
+    bad = bytearray(blob)
+    bad[at + 4] ^= 0x01                                                    # period 18 -> 19, in this stream's entry only
+    with _mix_engine(M) as e:
+        assert M.lib.mtr_engine_state_import(e._h, 1, bytes(bad), len(bad)) == M.engine.ERR_STATE
+        assert b"checksum" in M.lib.mtr_last_error()
+        f = list(HDR.unpack_from(bad))
+        f[-1] = _fnv1a64(bad[HDR.size:])
+        assert f[-1] != HDR.unpack_from(blob)[-1]
+        fit = HDR.pack(*f) + bytes(bad[HDR.size:])
+        assert M.lib.mtr_engine_state_import(e._h, 1, fit, len(fit)) == M.engine.ERR_STATE
+        assert b"needle" in M.lib.mtr_last_error()
+        assert e.state_import(blob, first=1) == 3                          # still a fresh engine: the good blob goes in
+
+
+def _blob_cases(M):
+    """name -> the state blob of a small engine after fixed input (tests/golden/golden_state_blobs_v1.json holds their SHA-256)."""
+    out = {}
+    with _mix_engine(M) as e:
+        _feed(e, _mix_signal(), MIX_CALLS[:MIX_STOP])
+        out["kmeter+stcorr+needle+scope"] = e.state_export(2, 3)
+    x = np.stack([sig.g2(12001, 300 + s) * np.float32(2.0 ** -(s % 3)) for s in range(3)])
+    x5 = np.ascontiguousarray(np.concatenate([x, np.roll(x, 1, 0), np.roll(x, 2, 0)[:, :, :1]], 2))
+    with M.Engine(3, 48000.0, M.METER_SURROUND, n_channels=5) as e:
+        e.surround_set_period(2400, 16)
+        _feed(e, x5, [5000, 7001])
+        out["surround, 5 channels"] = e.state_export()
+    with M.Engine(3, 48000.0, M.METER_EBU | M.METER_TRUEPEAK | M.METER_STCORR) as e:
+        e.integr_start()
+        e.stcorr_set_period(2400, 8)
+        _feed(e, x, [5000, 7001])
+        out["ebu+truepeak+stcorr"] = e.state_export()
+    with M.Engine(3, 48000.0, M.METER_SPECTR30 | M.METER_TPBALLIST | M.METER_DR14 | M.METER_KMETER) as e:
+        _feed(e, x, [5000, 7001])
+        out["spectr30+tpballist+dr14+kmeter"] = e.state_export()
+    return out
+
+
+def test_blobs_are_byte_for_byte_the_recorded_ones(M):
+    """The blob format is a contract with every checkpoint on disk: four small configurations, after fixed input, give the bytes whose
+    SHA-256 and length were recorded when the host side of the side meters moved behind one table."""
+    with open(os.path.join(ROOT, "tests", "golden", "golden_state_blobs_v1.json")) as f:
+        want = json.load(f)
+    got = {k: {"bytes": len(b), "sha256": hashlib.sha256(b).hexdigest()} for k, b in _blob_cases(M).items()}
+    assert got == want
 
 
 WORKER = r'''
