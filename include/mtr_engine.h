@@ -195,6 +195,9 @@ int  mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint6
 /* Track lengths — the same call for the meters whose answer is one per track (DR14, KMETER, BITSTATS, SIGDIST beside EBU / TRUEPEAK):
  * mtr_engine_process_device_tracks / _host_tracks, declared in mtr_tracks.h */
 #include "mtr_tracks.h"
+/* Ragged batches for the meters that report a reading over time (STCORR, NEEDLE) beside those: mtr_engine_process_device_ragged /
+ * _host_ragged, mtr_engine_series_points and mtr_series_cut, declared in mtr_ragged.h */
+#include "mtr_ragged.h"
 /* Frames metered per stream since create / reset, and whether it is closed (either pointer may be NULL): [count] each.
  * (What the process calls queued so far: no synchronisation.  mtr_engine_state_import restarts the count of the streams it writes
  * at 0: a blob carries no frame count.) */

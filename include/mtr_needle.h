@@ -17,7 +17,8 @@ extern "C" {
 #define MTR_NEEDLE_MS     8u       /* msppmdsp.cc:50-118: "channel" 0 = processM, 1 = processS; stereo engines only */
 
 /* The needle meters for a batch (MTR_METER_NEEDLE; engines of 1 or 2 channels, C = n_channels; MTR_NEEDLE_MS needs 2).  Combines with
- * every other meter of such an engine; not with the per-stream-lengths entry points.  n_frames per call < 2^31 - 1.  The arithmetic is
+ * every other meter of such an engine.  A batch of tracks that end where their audio ends: mtr_engine_process_device_ragged /
+ * _host_ragged (mtr_ragged.h; the _lengths and _tracks pairs refuse the meter).  n_frames per call < 2^31 - 1.  The arithmetic is
  * the reference's, operation for operation in f32: readings and states are bit for bit those of the reference's objects.
  * w1 w2 w3 g of Iec1ppmdsp::init / Iec2ppmdsp::init (= Msppmdsp::init) (iec1ppmdsp.cc:89-95, iec2ppmdsp.cc:89-95, msppmdsp.cc:131-137);
  * of Vumeterdsp::init (vumeterdsp.cc:82-86): w, 4 w, 0, g.  `kind` is ONE of the four bits, else MTR_ERR_ARG.  Host only, no device. */
@@ -41,7 +42,8 @@ int  mtr_engine_needle_set_gain (mtr_engine* e, int side, float db);
  * (may be NULL) = z1 z2 as the most recent completed process () stored them.  Synchronises. */
 int  mtr_engine_needle_read (mtr_engine* e, uint32_t kind, uint32_t first, uint32_t count, float* level, float* state);
 /* out [count][capacity][C] (may be NULL): the first min (*n_points, capacity, capacity_points) readings of `kind` of each stream;
- * *n_points = periods completed since reset, *dropped = points that did not fit the series (lock step: one number each). */
+ * *n_points = periods completed since reset, *dropped = points that did not fit the series (lock step: one number each; a stream that
+ * a ragged call closed has its own count, mtr_engine_series_points, and 0.0f behind its own points). */
 int  mtr_engine_needle_series (mtr_engine* e, uint32_t kind, uint32_t first, uint32_t count, float* out, uint32_t capacity,
                                uint32_t* n_points, uint32_t* dropped);
 /* The constructors' state; series emptied; kinds, period and gains kept.  Part of mtr_engine_reset. */

@@ -13,8 +13,9 @@ extern "C" {
 
 /* Stcorrdsp for a batch (MTR_METER_STCORR; stereo engines only — a pair of a wider frame: mtr_engine_set_frame_layout, e.g. 6, {4, 5}
  * for Ls / Rs of a 5.1 file; all four selectable pairs of the surround plugins, src/surmeter.c, with their K-meters from one read of
- * the wide frames: MTR_METER_SURROUND, mtr_surround.h).  Combines with every other stereo meter; not with
- * the per-stream-lengths entry points.  n_frames per call < 2^31 - 1.
+ * the wide frames: MTR_METER_SURROUND, mtr_surround.h).  Combines with every other stereo meter.  A batch of tracks that end where
+ * their audio ends: mtr_engine_process_device_ragged / _host_ragged (mtr_ragged.h; the _lengths and _tracks pairs refuse the meter).
+ * n_frames per call < 2^31 - 1.
  * w1, w2 of Stcorrdsp::init ((int) sample_rate, 2e3f, 0.3f) (stcorrdsp.cc:85-93; src/meters.cc:202-207) */
 int  mtr_stcorr_coef (float sample_rate, float* out2);
 /* period_frames 0 (default): every engine call is ONE Stcorrdsp::process () per stream (as MTR_METER_KMETER).
@@ -30,7 +31,8 @@ int  mtr_engine_stcorr_set_period (mtr_engine* e, uint32_t period_frames, uint32
  * (P > 0; 0.0f before the first).  state5 [count][5] = zl zr zlr zll zrr as they stand now, may be NULL.  Synchronises. */
 int  mtr_engine_stcorr_read (mtr_engine* e, uint32_t first, uint32_t count, float* corr, float* state5);
 /* out [count][capacity] (may be NULL): the first min (*n_points, capacity, capacity_points) readings of each stream; *n_points =
- * periods completed since reset, *dropped = points that did not fit the series (the streams advance in lock step: one number each). */
+ * periods completed since reset, *dropped = points that did not fit the series (the streams advance in lock step: one number each;
+ * a stream that a ragged call closed has its own count, mtr_engine_series_points, and 0.0f behind its own points). */
 int  mtr_engine_stcorr_series (mtr_engine* e, uint32_t first, uint32_t count, float* out, uint32_t capacity,
                                uint32_t* n_points, uint32_t* dropped);
 /* Stcorrdsp's constructor state (:33-36); series emptied, period kept.  Part of mtr_engine_reset. */

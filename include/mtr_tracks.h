@@ -28,7 +28,8 @@ extern "C" {
  * A stream with frames[s] == n_frames comes out bit for bit as mtr_engine_process_device leaves it.  Once a stream is closed, every later
  * call on the streams that hold it (mtr_engine_process_device / _host, an LV2 block) runs the length-masking kernels, end 0 for the
  * closed ones.  The per-meter resets (mtr_engine_dr14_reset, _kmeter_reset, _intstat_reset) reopen nothing.
- * Engines that hold SPECTR30, TPBALLIST, STCORR, NEEDLE or SURROUND: MTR_ERR_UNSUPPORTED, nothing queued, engine unchanged.
+ * Engines that hold SPECTR30, TPBALLIST, STCORR, NEEDLE or SURROUND: MTR_ERR_UNSUPPORTED, nothing queued, engine unchanged (STCORR and
+ * NEEDLE beside these meters: mtr_engine_process_device_ragged / _host_ragged, mtr_ragged.h).
  * replaces: a host that stops calling run() at the track's end. */
 int  mtr_engine_process_device_tracks (mtr_engine* e, const float* d_audio, uint64_t n_frames,
                                        uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);

@@ -492,6 +492,16 @@ struct CallRun {
 			if (e->closed[g]) continue;
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
+			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
+			for (int k = 0; k < 2; ++k) {
+				const bool sc = k == 0;
+				if (!(meters & (sc ? MTR_METER_STCORR : MTR_METER_NEEDLE))) continue;
+				const uint64_t P = sc ? e->sc.ser.period : e->nd.ser.period;
+				uint64_t whole = 0;
+				uint32_t partial = 0;
+				if (P && series_cut (sc ? e->pos.sc.fill : e->pos.nd.fill, P, c.n_frames, f, &whole, &partial))
+					(sc ? e->sc.points : e->nd.points)[g] += whole + partial;
+			}
 			if (log) {
 				// periods the stream completed: those that end within the fragments it ended (as upload_lengths counts them)
 				const uint64_t nf = f == c.n_frames ? pl.n_frag : (uint64_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
@@ -676,6 +686,53 @@ int mtr_engine_process_device_tracks (mtr_engine* e, const float* d_audio, uint6
 	const int crc = tracks_check (e, n_frames, frames, e->cfg.n_streams);
 	if (crc) return crc;
 	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+// Ragged batches: the meters of _tracks and the two that keep a reading series, STCORR and NEEDLE (mtr_ragged.h)
+static int ragged_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
+{
+	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST
+	                        | MTR_METER_STCORR | MTR_METER_NEEDLE;
+	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok))
+		return fail (MTR_ERR_UNSUPPORTED, "ragged batches: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE engines only");
+	for (uint32_t i = 0; i < n; ++i)
+		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "ragged batches: frames[s] > n_frames");
+	return MTR_OK;
+}
+
+int mtr_engine_process_device_ragged (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
+                                      const uint64_t* frames, void* hip_stream)
+{
+	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_ragged: null argument");
+	const int crc = ragged_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_host_ragged (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_ragged: null argument");
+	const int crc = ragged_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
+}
+
+int mtr_engine_series_points (mtr_engine* e, uint32_t meter, uint32_t first, uint32_t count, uint64_t* points)
+{
+	if (!e || !points) return fail (MTR_ERR_ARG, "mtr_engine_series_points: null argument");
+	if ((meter != MTR_METER_STCORR && meter != MTR_METER_NEEDLE) || !(e->cfg.meters & meter))
+		return fail (MTR_ERR_ARG, "mtr_engine_series_points: meter is MTR_METER_STCORR or MTR_METER_NEEDLE, one the engine holds");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
+	const std::vector<uint64_t>& v = meter == MTR_METER_STCORR ? e->sc.points : e->nd.points;
+	for (uint32_t i = 0; i < count; ++i) points[i] = v[first + i];
+	return MTR_OK;
+}
+
+int mtr_series_cut (uint64_t fill, uint64_t period, uint64_t n_frames, uint64_t frames, uint64_t* whole, uint32_t* partial)
+{
+	if (!whole || !partial || !series_cut (fill, period, n_frames, frames, whole, partial))
+		return fail (MTR_ERR_ARG, "mtr_series_cut: fill < period (or period 0), frames <= n_frames, two results");
+	return MTR_OK;
 }
 
 int mtr_engine_stream_frames (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* frames, uint8_t* closed)

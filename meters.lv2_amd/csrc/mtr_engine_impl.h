@@ -63,7 +63,7 @@ struct Stream {
 // 48 kHz — never overwrites arrays that kernels of an earlier call may still be reading, and never blocks the host.
 constexpr int PLAN_SLOTS = 4;
 
-// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks, or any call once a stream is closed) ride the same
+// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks / _ragged, or any call once a stream is closed) ride the same
 // way: [ends S | frag_lim S | from_tile S | km_fall S (KMETER engines)] in the next slot of their own ring, uploaded on the call's stream,
 // busy until the call's last readers (the last kernel of the call on its stream — the side meters' LEN kernels, k_history_len — and the
 // gate on whichever stream it ran) have passed.
@@ -257,6 +257,7 @@ struct mtr_engine {
 		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
 		float                      w[2];        // w1, w2 of Stcorrdsp::init
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
+		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (ragged calls: mtr_ragged.h)
 	} sc;
 	struct Needle {                             // NEEDLE (mtr_needle.hip)
 		DevBuf<unsigned char>      state;       // [S] of { mtr_needle_hdr, mtr_needle_state [kinds][C] }
@@ -266,6 +267,8 @@ struct mtr_engine {
 		uint32_t                   kind[4] = { 0, 0, 0, 0 };         // the selected kinds in the order of their bits ...
 		float                      w[4][4];     // ... and their w1 w2 w3 g
 		float                      db[2], mv[2];   // Msppmdsp's gains, M and S: a control (it survives a reset)
+		DevBuf<float>              back;        // [S][kinds][C][2] z1 z2 in front of the group of four frames that is open between two calls
+		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (ragged calls: mtr_ragged.h)
 	} nd;
 	struct Surround {                           // SURROUND (mtr_surround.hip)
 		DevBuf<mtr_sur_state>      state;       // [S]

@@ -69,6 +69,9 @@ typedef struct mtr_needle_args {
 	uint32_t        state_pitch;
 	float*          points;       /* [n_kinds][..][capacity][C], from the view's first stream */
 	uint64_t        kind_pitch;   /* floats from kind to kind */
+	/* the LEN instantiation only (`back` set): */
+	const uint32_t* ends;         /* [S] per-stream ends of a ragged call, or NULL: every stream takes the whole call */
+	float*          back;         /* [S][n_kinds][C][2] z1 z2 where the group of four frames stood that is open between two calls */
 } mtr_needle_args;
 
 namespace {
@@ -90,8 +93,9 @@ __device__ __forceinline__ float pair_other (float v)
 }
 
 // Iec1ppmdsp / Iec2ppmdsp / Msppmdsp: lane = (row, filter)
-template <int C, bool MS> struct Ppm {
-	float z, m, s, last, w, w3, g, mv;
+// (BACK: the chain keeps what z was in front of a group it entered frame by frame — the group a call may end in)
+template <int C, bool MS, bool BACK> struct Ppm {
+	float z, m, s, last, w, w3, g, mv, zb;
 	uint32_t res, sgn;
 	int   base;                                  // the lane's dword in a staged frame 0
 	bool  series;
@@ -128,7 +132,7 @@ template <int C, bool MS> struct Ppm {
 	}
 	__device__ __forceinline__ void step (const float* buf, int k, int q)
 	{
-		if (q == 0) one<true, false> (raw (buf, k));
+		if (q == 0) { if constexpr (BACK) zb = z; one<true, false> (raw (buf, k)); }
 		else if (q == 3) one<false, true> (raw (buf, k));
 		else one<false, false> (raw (buf, k));
 	}
@@ -136,6 +140,7 @@ template <int C, bool MS> struct Ppm {
 	{
 		one<true, false> (x.r[0]); one<false, false> (x.r[1]); one<false, false> (x.r[2]); one<false, true> (x.r[3]);
 	}
+	__device__ __forceinline__ void undo () { z = zb; }          // the open group never happened
 	__device__ __forceinline__ float end ()
 	{
 		z = z + 1e-10f;
@@ -146,8 +151,8 @@ template <int C, bool MS> struct Ppm {
 };
 
 // Vumeterdsp: lane = row
-template <int C> struct Vu {
-	float z1, z2, t2, m, s1, s2, last, w, w4, g;
+template <int C, bool BACK> struct Vu {
+	float z1, z2, t2, m, s1, s2, last, w, w4, g, zb;
 	uint32_t res;
 	int   base;
 	bool  series;
@@ -174,7 +179,7 @@ template <int C> struct Vu {
 	}
 	__device__ __forceinline__ void step (const float* buf, int k, int q)
 	{
-		if (q == 0) one<true, false> (raw (buf, k));
+		if (q == 0) { if constexpr (BACK) zb = z1; one<true, false> (raw (buf, k)); }
 		else if (q == 3) one<false, true> (raw (buf, k));
 		else one<false, false> (raw (buf, k));
 	}
@@ -182,6 +187,7 @@ template <int C> struct Vu {
 	{
 		one<true, false> (x.r[0]); one<false, false> (x.r[1]); one<false, false> (x.r[2]); one<false, true> (x.r[3]);
 	}
+	__device__ __forceinline__ void undo () { z1 = zb; }         // (z2 and m move with a group's last frame only)
 	__device__ __forceinline__ float end ()
 	{
 		if (!isfinite (z1)) { z1 = 0; m = INFINITY; }
@@ -229,7 +235,59 @@ __device__ __forceinline__ void walk (Chain& c, Walk& w, const float* buf, int n
 	}
 }
 
-template <int C>
+// A chunk of a ragged call in which not every lane of the wave takes every frame.  The lock-step walk stays scalar — where a block starts
+// and ends is the same for every stream that is still open — and a lane joins what its stream has of it: `lim` frames of the chunk's
+// `nf` (0: the stream ended in an earlier chunk, or was closed before the call); `closing`: the stream ends at chunk frame lim, inside
+// the call.  The block it ends in is truncated there: the frames from its j & ~3 on are dropped, then the chain's own end () and its
+// point, at the index of the open block.  A stream that ends exactly where a block does has completed it and gets nothing more.
+// A group that the chunk's first frames continue — the chain entered it frame by frame, in the chunk or the call before — and that the
+// lane's end leaves incomplete is undone: the chain kept what stood in front of it.
+// The lanes that share a stream (a detector's two filters, its channels) share lim: the pair sum sees both or neither.
+template <class Chain, class Put>
+__device__ __forceinline__ void walk_ragged (Chain& c, Walk& w, const float* buf, int nf, int lim, bool closing, Put put)
+{
+	int k = 0;
+	if (closing && w.j < w.P4 && (w.j & 3u) && (uint32_t) lim < 4u - (w.j & 3u)) c.undo ();
+	while (k < nf) {
+		const int ka = k;
+		if (w.j == 0 && lim > k) c.start ();
+		// the lane's frames of this block end at chunk frame `keep`: its end, less the frames behind the last whole group, if the block holds it
+		int keep = lim;
+		if (closing && lim > k && (uint32_t) (lim - k) <= w.P - w.j) keep = lim - (int) ((w.j + (uint32_t) (lim - k)) & 3u);
+		if (w.j < w.P4) {
+			int run = (int) min ((uint32_t) (nf - k), w.P4 - w.j);
+			int q = (int) (w.j & 3);
+			w.j += (uint32_t) run;
+			for (; run > 0 && q; --run, ++k, q = (q + 1) & 3) if (k < keep) c.step (buf, k, q);
+			for (; run >= 16; run -= 16, k += 16) {
+				if (k + 16 <= keep) {
+					const typename Chain::Quad x0 = c.load (buf, k), x1 = c.load (buf, k + 4), x2 = c.load (buf, k + 8), x3 = c.load (buf, k + 12);
+					c.group (x0); c.group (x1); c.group (x2); c.group (x3);
+				} else {
+					for (int g = 0; g < 16; g += 4) if (k + g + 4 <= keep) c.group (c.load (buf, k + g));
+				}
+			}
+			for (; run >= 4; run -= 4, k += 4) if (k + 4 <= keep) c.group (c.load (buf, k));
+			for (; run > 0; --run, ++k, ++q) if (k < keep) c.step (buf, k, q);
+		} else {
+			const uint32_t skip = min ((uint32_t) (nf - k), w.P - w.j);
+			k += (int) skip; w.j += skip;
+		}
+		// the block's end — every lane that had frames of [ka, k) — or, for a closing lane, its own end inside them
+		const bool done = w.j == w.P;
+		if (done ? lim > ka : (closing && lim > ka && lim <= k)) {
+			const float r = c.end ();
+			if (c.series) put (r, w.point);
+		}
+		if (done) { ++w.point; w.j = 0; }
+	}
+}
+
+// LEN: stream s ends at call frame a.ends[s] (0: not touched; no ends: every stream takes the whole call).  The workgroup runs to the
+// last end it holds — every wave, the helpers too, derives that from the same at most 32 ends, so they meet at the same barriers — and
+// fetches nothing at or past it.  It is also the kernel of every call that ends inside a group of four frames: what stood in front of
+// that group goes to a.back, for a stream that a later call ends before the group is complete.
+template <int C, bool LEN>
 __global__ __launch_bounds__ (64 * NW) void k_needle (const mtr_needle_args a)
 {
 	using G = Geo<C>;
@@ -239,7 +297,18 @@ __global__ __launch_bounds__ (64 * NW) void k_needle (const mtr_needle_args a)
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wid = __builtin_amdgcn_readfirstlane (tid >> 6);
 	const uint32_t s0 = blockIdx.x * G::NS;
-	const int64_t rowlen = (int64_t) a.n_frames * C;                  // dwords of a row that belong to the call
+	int64_t last_end = (int64_t) a.n_frames;                           // frames the workgroup walks: the call's, or (LEN) up to the last end it holds
+	if (LEN && a.ends) {
+		uint32_t m = 0;
+		for (int i = 0; i < G::NS; ++i) {                              // (uniform: the same scalar loads in every wave)
+			const uint32_t si = s0 + (uint32_t) i;
+			const uint32_t v = si < a.n_streams ? a.ends[si] : 0u;
+			m = v > m ? v : m;
+		}
+		last_end = (int64_t) __builtin_amdgcn_readfirstlane ((int) m);
+		if (last_end == 0) return;                                     // (the whole workgroup, before any barrier)
+	}
+	const int64_t rowlen = last_end * C;                              // dwords of a row that belong to the call
 	const bool al4 = (reinterpret_cast<size_t> (a.audio) & 3) == 0;
 	const uint64_t abase = reinterpret_cast<size_t> (a.audio) >> 2;
 
@@ -309,9 +378,18 @@ __global__ __launch_bounds__ (64 * NW) void k_needle (const mtr_needle_args a)
 	const int sl = row / C, ch = row % C;
 	const uint32_t s = s0 + (uint32_t) sl;
 	const bool live = s < a.n_streams;
-	const bool writer = live && (vu ? lane < 32 : true);
-	const int64_t N = (int64_t) a.n_frames;
+	bool writer = live && (vu ? lane < 32 : true);
+	if (LEN && a.ends) writer = writer && a.ends[live ? s : 0] != 0;  // (end 0: the stream's detectors and its series row are not written)
+	const int64_t N = last_end;
 	const int64_t nchunks = (N + CH - 1) / CH;
+	// LEN: the lane's own end (a lane without a stream walks as an open one would, on nothing, and writes nothing)
+	int64_t E = 0;
+	bool closes = false;
+	float* bk = nullptr;                                               // the lane's slot of a.back
+	if constexpr (LEN) {
+		E = live && a.ends ? (int64_t) a.ends[s] : N;
+		closes = live && E < (int64_t) a.n_frames;
+	}
 	if (wid >= (int) a.n_kinds) {                                      // no chain of its own: this wave only helps to stage
 		fetch (0);
 		for (int64_t c = 0; c < nchunks; ++c) {
@@ -325,6 +403,7 @@ __global__ __launch_bounds__ (64 * NW) void k_needle (const mtr_needle_args a)
 	float* const pts = a.points ? a.points + (size_t) wid * a.kind_pitch + (size_t) s * a.capacity * C + ch : nullptr;
 	const float w1 = a.w[wid][0], w2 = a.w[wid][1], w3 = a.w[wid][2], g = a.w[wid][3];
 	const uint32_t cap = a.capacity;
+	if constexpr (LEN) bk = a.back + (((size_t) (live ? s : 0) * a.n_kinds + wid) * C + ch) * 2 + (vu ? 0 : filt);
 	// the carried state, here before the first chunk is asked for: nothing in the loop below waits for it behind a chunk's loads
 	mtr_needle_state v0 = *st;
 	asm volatile ("" : "+v" (v0.z1), "+v" (v0.z2), "+v" (v0.m), "+v" (v0.last), "+v" (v0.s1), "+v" (v0.s2), "+v" (v0.res));
@@ -339,32 +418,47 @@ __global__ __launch_bounds__ (64 * NW) void k_needle (const mtr_needle_args a)
 			stash ((int) (c & 1), c * CH);
 			__syncthreads ();
 			if (c + 1 < nchunks) fetch ((c + 1) * CH);
-			walk (chain, wk, lds[c & 1], (int) min ((int64_t) CH, N - c * CH), put);
+			const int nf = (int) min ((int64_t) CH, N - c * CH);
+			if constexpr (LEN) {
+				// every lane of the wave takes the whole chunk and none ends with it: the lock-step walk
+				const int64_t ce = c * CH + nf;
+				const bool whole = closes ? E > ce : E >= ce;
+				if (__all (whole)) walk (chain, wk, lds[c & 1], nf, put);
+				else {
+					const int64_t left = E - c * CH;
+					const int lim = left <= 0 ? 0 : left >= nf ? nf : (int) left;
+					walk_ragged (chain, wk, lds[c & 1], nf, lim, closes && left > 0 && left <= nf, put);
+				}
+			} else walk (chain, wk, lds[c & 1], nf, put);
 		}
 	};
 	if (vu) {
-		Vu<C> p;
+		Vu<C, LEN> p;
+		if constexpr (LEN) p.zb = *bk;
 		p.z1 = v0.z1; p.z2 = v0.z2; p.m = v0.m; p.s1 = v0.s1; p.s2 = v0.s2; p.last = v0.last; p.res = v0.res;
 		p.t2 = p.z2 / 2;
 		p.w = w1; p.w4 = w2; p.g = g; p.base = sl * G::PITCH + ch; p.series = a.series != 0;
 		run (p, [&] (float r, uint64_t point) { if (writer && point < cap) pts[point * C] = r; });
 		if (writer) { st->z1 = p.z1; st->z2 = p.z2; st->m = p.m; st->s1 = p.s1; st->s2 = p.s2; st->last = p.last; st->res = p.res; }
+		if constexpr (LEN) if (writer) *bk = p.zb;
 		return;
 	}
 	auto ppm = [&] (auto& p) __attribute__ ((always_inline)) {
+		if constexpr (LEN) p.zb = *bk;
 		p.z = filt ? v0.z2 : v0.z1; p.m = v0.m; p.s = filt ? v0.s2 : v0.s1; p.last = v0.last; p.res = v0.res;
 		p.w = filt ? w2 : w1; p.w3 = w3; p.g = g; p.mv = a.mv[ch]; p.sgn = ch ? 0x80000000u : 0u; p.series = a.series != 0;
 		run (p, [&] (float r, uint64_t point) { if (writer && !filt && point < cap) pts[point * C] = r; });
 		if (!writer) return;
+		if constexpr (LEN) *bk = p.zb;
 		if (filt) { st->z2 = p.z; st->s2 = p.s; }
 		else { st->z1 = p.z; st->s1 = p.s; st->m = p.m; st->last = p.last; st->res = p.res; }
 	};
 	if (C == 2 && kind == MTR_NEEDLE_MS) {
-		Ppm<C, true> p;
+		Ppm<C, true, LEN> p;
 		p.base = sl * G::PITCH;
 		ppm (p);
 	} else {
-		Ppm<C, false> p;
+		Ppm<C, false, LEN> p;
 		p.base = sl * G::PITCH + ch;
 		ppm (p);
 	}
@@ -380,7 +474,9 @@ int kind_index (uint32_t kinds, uint32_t kind)
 
 template <int C> static void launch_c (const mtr_needle_args& a, hipStream_t st)
 {
-	hipLaunchKernelGGL ((k_needle<C>), dim3 ((a.n_streams + Geo<C>::NS - 1) / Geo<C>::NS), dim3 (64 * NW), 0, st, a);
+	const dim3 grid ((a.n_streams + Geo<C>::NS - 1) / Geo<C>::NS);
+	if (a.back) hipLaunchKernelGGL ((k_needle<C, true>), grid, dim3 (64 * NW), 0, st, a);
+	else hipLaunchKernelGGL ((k_needle<C, false>), grid, dim3 (64 * NW), 0, st, a);
 }
 
 static int mtr_launch_needle (const mtr_needle_args& a, uint32_t n_channels, void* stream)
@@ -418,7 +514,7 @@ static int needle_create (mtr_engine* e)
 	return rc;
 }
 
-static int needle_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
+static int needle_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const uint32_t P = e->nd.ser.period, cap = e->nd.ser.cap, C = e->cfg.n_channels;
 	mtr_needle_args a;
@@ -435,6 +531,11 @@ static int needle_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamE
 	a.kind_pitch = (uint64_t) e->cfg.n_streams * cap * C;
 	a.points = P && cap ? e->nd.series.p + (size_t) c.off * cap * C : nullptr;
 	if (!a.points) a.capacity = 0;
+	// The length-masking kernel takes a ragged call, and every call that ends inside a group of four frames: it alone keeps what stood in
+	// front of that group (e->nd.back), which a stream needs that a later call ends before the group is complete
+	const uint64_t jn = P ? (e->pos.nd.fill + c.n_frames) % P : 0;
+	a.ends = se.ends;
+	a.back = se.ends || (jn < (P & ~3u) && (jn & 3)) ? e->nd.back.p + (size_t) c.off * a.n_kinds * C * 2 : nullptr;
 	if (mtr_launch_needle (a, C, c.st)) return fail (MTR_ERR_HIP, "k_needle launch");
 	nx.nd = series_advance (e->pos.nd, P, c.n_frames);
 	return MTR_OK;
@@ -497,7 +598,7 @@ int mtr_engine_needle_reset (mtr_engine* e)
 	HIPCHK (hipSetDevice (e->cfg.device));
 	const uint32_t S = e->cfg.n_streams, per = needle_count (e) * e->cfg.n_channels;
 	const size_t pitch = needle_pitch (e);
-	if (e->nd.state.reserve ((size_t) S * pitch)) return fail (MTR_ERR_NOMEM, "hipMalloc NEEDLE state");
+	if (e->nd.state.reserve ((size_t) S * pitch) || e->nd.back.reserve ((size_t) S * per * 2)) return fail (MTR_ERR_NOMEM, "hipMalloc NEEDLE state");
 	std::vector<unsigned char> h ((size_t) S * pitch, 0);             // the constructors: z1 = z2 = m = 0, _res = true
 	for (uint32_t s = 0; s < S; ++s)
 		for (uint32_t i = 0; i < per; ++i) {
@@ -508,7 +609,11 @@ int mtr_engine_needle_reset (mtr_engine* e)
 		}
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemcpy (e->nd.state.p, h.data (), h.size (), hipMemcpyHostToDevice));
+	HIPCHK (hipMemset (e->nd.back.p, 0, (size_t) S * per * 2 * sizeof (float)));
+	// (the series: a stream that a ragged call closes early leaves 0.0f behind its own points)
+	if (e->nd.series.n) HIPCHK (hipMemset (e->nd.series.p, 0, e->nd.series.n * sizeof (float)));
 	e->pos.nd = {};
+	e->nd.points.assign (S, 0);
 	return MTR_OK;
 }
 

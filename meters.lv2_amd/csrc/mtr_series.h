@@ -24,6 +24,20 @@ inline SeriesPos series_advance (const SeriesPos& pos, uint64_t P, uint64_t n_fr
 	return { P ? tot % P : 0, pos.points + (P ? tot / P : 0) };
 }
 
+// A ragged call (mtr_ragged.h): a stream that takes `frames` of a call of n_frames which started `fill` frames into a block.  *whole:
+// blocks of P it completes; *partial: 1 if it ends inside the call and a truncated block follows them — its last process (), of
+// (fill + frames) mod P frames — else 0.  P = 0: the call is the block; no whole ones, and the closing call of a stream that got some frames is
+// the truncated one (an open stream's call is no series point).  false: fill >= P > 0 or frames > n_frames.
+inline bool series_cut (uint64_t fill, uint64_t P, uint64_t n_frames, uint64_t frames, uint64_t* whole, uint32_t* partial)
+{
+	if ((P && fill >= P) || frames > n_frames) return false;
+	const bool closes = frames > 0 && frames < n_frames;
+	const uint64_t tot = fill + frames;
+	*whole = P ? tot / P : 0;
+	*partial = closes && (P == 0 || tot % P) ? 1 : 0;
+	return true;
+}
+
 // a state blob's copy of (P, fill): P is 0 or min_period .. max_period, and fill is inside the block
 inline bool series_blob_ok (uint32_t period, uint32_t fill, uint32_t min_period, uint32_t max_period)
 {

@@ -68,6 +68,7 @@ typedef struct mtr_stcorr_args {
 	mtr_stcorr_state* state;      /* [S] */
 	double*         piece;        /* [S][n_pieces][MTR_STCORR_PIECE] */
 	float*          series;       /* [S][capacity], NULL if capacity == 0 */
+	const uint32_t* ends;         /* [S] per-stream ends of a ragged call (the LEN instantiations), NULL on a dense one */
 } mtr_stcorr_args;
 
 namespace {
@@ -89,12 +90,22 @@ __device__ __forceinline__ float2 frame_at (const float* src, int64_t f, int64_t
 	return float2{src[2 * f], src[2 * f + 1]};
 }
 
+// LEN: the stream ends at call frame a.ends[s].  Its piece is [b0, min (b1, end)): one that starts at or behind the end is empty — nothing
+// of it is loaded, nothing written, the walk skips it — and a truncated one has its tiles aligned to the stream's end, so that what it
+// reports (sums, zl, zr) stands there and nothing at or past the end is read.  end == n_frames: the dense kernel's piece, bit for bit.
+template <bool LEN>
 __global__ __launch_bounds__ (NT) void k_stcorr_pieces (const mtr_stcorr_args a)
 {
 	const uint32_t s = blockIdx.y;
 	const Piece pc = piece_of (a, blockIdx.x);
 	const float* const src = a.audio + (size_t) s * a.stride * 2;
-	const int64_t b0 = pc.b0, b1 = pc.b1;
+	int64_t pb1 = pc.b1;
+	if constexpr (LEN) {
+		const int64_t end = (int64_t) a.ends[s];
+		if (pc.b0 >= end) return;                                  // (uniform in the workgroup; end 0: every piece of the stream)
+		if (end < pb1) pb1 = end;
+	}
+	const int64_t b0 = pc.b0, b1 = pb1;
 	const int64_t warm = b0 == 0 ? 1 : (int64_t) a.warm;          // (the call's first piece: only the slot of frame -1)
 	const int nt = (int) ((b1 - b0 + warm + TILE - 1) / TILE);      // <= MAX_TILES: chunk + warm = MAX_TILES * TILE
 	const int64_t lo = b0 - warm > 0 ? b0 - warm : 0;              // the first frame that is read
@@ -238,10 +249,19 @@ __global__ __launch_bounds__ (NT) void k_stcorr_pieces (const mtr_stcorr_args a)
 }
 
 // one thread per stream: the pieces in order, and stcorrdsp.cc:65-75 + read () at every end of a process ()
+// LEN: the pieces up to the stream's end; the one that holds it is the stream's last, with its own length, and — if the stream ends inside
+// the call — it ends a process () whether a period ends there or not: the truncated block, appended at the stream's own point index.
+// end == 0: the stream is not touched.
+template <bool LEN>
 __global__ void k_stcorr_final (const mtr_stcorr_args a)
 {
 	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
 	if (s >= a.n_streams) return;
+	int64_t end = 0;
+	if constexpr (LEN) {
+		end = (int64_t) a.ends[s];
+		if (end == 0) return;
+	}
 	mtr_stcorr_state* const st = a.state + s;
 	const double q1 = 1.0 - (double) a.w2;
 	double z[3] = { (double) st->z[2], (double) st->z[3], (double) st->z[4] };
@@ -251,7 +271,16 @@ __global__ void k_stcorr_final (const mtr_stcorr_args a)
 	double qp = 1.0;
 	bool flushed[2] = { false, false };
 	for (uint32_t i = 0; i < a.n_pieces; ++i) {
-		const Piece pc = piece_of (a, i);
+		Piece pc = piece_of (a, i);
+		bool ends_here = false;                                        // (LEN: the stream's last piece)
+		if constexpr (LEN) {
+			if (pc.b0 >= end) break;
+			if (end <= pc.b1) {
+				ends_here = true;
+				if ((uint64_t) end < a.n_frames) pc.closes = true;         // one last process (), of what the stream has of the block
+				pc.b1 = end;
+			}
+		}
 		const int64_t len = pc.b1 - pc.b0;
 		if (len != len_of) { qp = pow (q1, (double) len); len_of = len; }
 		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_STCORR_PIECE;
@@ -271,7 +300,7 @@ __global__ void k_stcorr_final (const mtr_stcorr_args a)
 		}
 		if (pc.after_period) flushed[0] = flushed[1] = false;
 		for (int j = 0; j < 3; ++j) z[j] = fma (qp, z[j], sum[j]);
-		const bool last = i + 1 == a.n_pieces;
+		const bool last = i + 1 == a.n_pieces || ends_here;
 		if (last) { zl = (float) el; zr = (float) er; }
 		if (!pc.closes) continue;
 		float f[3] = { (float) z[0], (float) z[1], (float) z[2] };
@@ -313,8 +342,13 @@ static void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk)
 static int mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
-	hipLaunchKernelGGL (k_stcorr_pieces, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-	hipLaunchKernelGGL (k_stcorr_final, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
+	if (a.ends) {
+		hipLaunchKernelGGL (k_stcorr_pieces<true>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL (k_stcorr_final<true>, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
+	} else {
+		hipLaunchKernelGGL (k_stcorr_pieces<false>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL (k_stcorr_final<false>, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
+	}
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -330,7 +364,7 @@ static int stcorr_create (mtr_engine* e)
 }
 
 // The periods of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
-static int stcorr_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
+static int stcorr_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	const uint64_t P = e->sc.ser.period;
@@ -345,6 +379,7 @@ static int stcorr_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamE
 	if (e->sc.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_STCORR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc STCORR pieces");
 	sa.state = e->sc.state.p + vo; sa.piece = e->sc.piece.p + vo * sa.n_pieces * MTR_STCORR_PIECE;
 	sa.series = cap ? e->sc.series.p + vo * cap : nullptr;
+	sa.ends = se.ends;
 	if (mtr_launch_stcorr (sa, c.st)) return fail (MTR_ERR_HIP, "k_stcorr launch");
 	nx.sc = series_advance (e->pos.sc, P, c.n_frames);
 	return MTR_OK;
@@ -404,7 +439,10 @@ int mtr_engine_stcorr_reset (mtr_engine* e)
 	for (auto& v : h) v.period = e->sc.ser.period;
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemcpy (e->sc.state.p, h.data (), S * sizeof (mtr_stcorr_state), hipMemcpyHostToDevice));
+	// (the series: a stream that a ragged call closes early leaves 0.0f behind its own points)
+	if (e->sc.series.n) HIPCHK (hipMemset (e->sc.series.p, 0, e->sc.series.n * sizeof (float)));
 	e->pos.sc = {};
+	e->sc.points.assign (S, 0);
 	return MTR_OK;
 }
 

@@ -123,6 +123,11 @@ def _load():
     if hasattr(L, "mtr_engine_process_device_tracks"):         # (an addition inside ABI version 2: track lengths for the whole-track meters)
         L.mtr_engine_process_device_tracks.argtypes = [vp, vp, u64, u64, vp, vp]
         L.mtr_engine_process_host_tracks.argtypes = [vp, vp, u64, u64, vp]
+    if hasattr(L, "mtr_engine_process_device_ragged"):         # (an addition inside ABI version 2: ragged batches for STCORR and NEEDLE)
+        L.mtr_engine_process_device_ragged.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_ragged.argtypes = [vp, vp, u64, u64, vp]
+        L.mtr_engine_series_points.argtypes = [vp, u32, u32, u32, vp]
+        L.mtr_series_cut.argtypes = [u64, u64, u64, u64, C.POINTER(u64), C.POINTER(u32)]
     if hasattr(L, "mtr_engine_pcm_stats"):                     # (an addition inside ABI version 2: integer PCM in)
         L.mtr_engine_process_host_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp]
         L.mtr_engine_process_device_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp, vp]
@@ -274,6 +279,16 @@ def scope_window(window_frames):
     out = np.zeros(int(window_frames), np.float32)
     _check(lib.mtr_scope_window(int(window_frames), out.ctypes.data), "mtr_scope_window")
     return out
+
+
+def series_cut(fill, period, n_frames, frames):
+    """(whole, partial): of a call of n_frames that starts `fill` frames into a block of `period`, a stream that takes `frames` completes
+    `whole` blocks, and a truncated one follows them if partial == 1 (mtr_series_cut; no device)."""
+    if not hasattr(lib, "mtr_series_cut"):
+        raise EngineError(f"{lib_path} has no ragged batches: rebuild it")
+    whole, partial = C.c_uint64(), C.c_uint32()
+    _check(lib.mtr_series_cut(int(fill), int(period), int(n_frames), int(frames), C.byref(whole), C.byref(partial)), "mtr_series_cut")
+    return whole.value, partial.value
 
 
 def needle_coef(kind, fs):
@@ -547,6 +562,37 @@ class Engine:
         f = self._tracks(frames)
         _check(lib.mtr_engine_process_host_tracks(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
                "process_host_tracks")
+
+    def _ragged(self, frames):
+        if not hasattr(lib, "mtr_engine_process_device_ragged"):
+            raise EngineError(f"{lib_path} has no ragged batches: rebuild it")
+        f = np.ascontiguousarray(frames, np.uint64)
+        if f.shape != (self.n_streams,):
+            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
+        return f
+
+    def process_device_ragged(self, ptr, n_frames, frames, stride=None, stream=0):
+        """process_device_tracks() for engines that also hold STCORR or NEEDLE: stream s is metered up to frames[s] <= n_frames, the
+        block it ends in truncated there (one last process () and read (), the stream's last point); frames[s] < n_frames closes it."""
+        f = self._ragged(frames)
+        _check(lib.mtr_engine_process_device_ragged(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
+               "process_device_ragged")
+
+    def process_ragged(self, x, frames):
+        """process() as a ragged batch: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        x = self._frames_f32(x)
+        f = self._ragged(frames)
+        _check(lib.mtr_engine_process_host_ragged(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
+               "process_host_ragged")
+
+    def series_points(self, meter, first=0, count=None):
+        """[count] uint64: the points each stream's own STCORR or NEEDLE series (meter: METER_STCORR / METER_NEEDLE) has got since reset,
+        dropped ones included — of a stream that a ragged call closed, its whole blocks and the truncated one."""
+        self._ragged(np.zeros(self.n_streams, np.uint64))
+        count = self.n_streams - first if count is None else count
+        out = np.zeros(count, np.uint64)
+        _check(lib.mtr_engine_series_points(self._h, int(meter), first, count, out.ctypes.data), "series_points")
+        return out
 
     def process_pcm(self, x, format=None, frames=None):
         """process() for host integer PCM, decoded on the GPU: x int16 or int32 [S, T, C] (or [S, T] mono; the format is inferred),
