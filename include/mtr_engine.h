@@ -31,7 +31,8 @@ extern "C" {
  *    mtr_engine_stcorr_set_period, _stcorr_read, _stcorr_series, _stcorr_reset; mtr_engine_loudlog_set_period, _loudlog_period,
  *    _loudlog_series, _loudlog_reset; MTR_METER_NEEDLE, mtr_needle_coef, mtr_engine_needle_configure, _needle_set_gain, _needle_read,
  *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks; MTR_METER_SCOPE, mtr_scope_window,
- *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset; mtr_engine_kmeter_set_period, _kmeter_period,
+ *    _kmeter_series): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -351,10 +352,13 @@ int  mtr_engine_dr14_reset (mtr_engine* e);
 /* Kmeterdsp for a batch (MTR_METER_KMETER; 1 or 2 channels): every process call is one Kmeterdsp::process () per
  * channel (jmeters/kmeterdsp.cc:56-140; n mod 4 trailing frames are dropped as there).
  * replaces: Kmeterdsp::read (rms, peak) (:148-153) — rms, peak [count][2] linear; arms the "start a new maximum"
- * flag exactly as read () does */
+ * flag exactly as read () does.  (With a period — mtr_kmeter.h — the last completed block's pair, 0.0f before the first; nothing to arm.) */
 int  mtr_engine_kmeter_read (mtr_engine* e, uint32_t first, uint32_t count, float* rms, float* peak);
-/* replaces: Kmeterdsp::reset (:142-146) */
+/* replaces: Kmeterdsp::reset (:142-146); with a period also the series emptied and the open block gone, the period kept */
 int  mtr_engine_kmeter_reset (mtr_engine* e);
+
+/* The K-meter's reading series — (rms, peak) after every block of P frames: mtr_engine_kmeter_set_period / _period / _series */
+#include "mtr_kmeter.h"
 
 /* Stcorrdsp for a batch (MTR_METER_STCORR): mtr_stcorr_coef and mtr_engine_stcorr_set_period / _read / _series / _reset */
 #include "mtr_stcorr.h"

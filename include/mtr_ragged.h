@@ -24,7 +24,9 @@ extern "C" {
  *   period P   the blocks are the engine's lock-step blocks.  A stream that ends r frames into one, 0 < r < P, gets one last
  *              process (p, r) and one last read (): that reading is the stream's last point, at the index of the whole blocks it
  *              completed.  r = 0 adds nothing.  STCORR's lower bound on P does not apply to r; the needle meters drop the r mod 4
- *              trailing frames, and r < 4 is a process () of no group.
+ *              trailing frames, and r < 4 is a process () of no group.  KMETER with a period (mtr_kmeter.h) likewise: _fpp = r with the
+ *              fall-back factor of r, r / 4 groups; a group of four that an earlier call left open and the stream's end leaves
+ *              incomplete drops out whole.
  * mtr_engine_stcorr_read / _needle_read report where a closed stream stood at its end: the reading of its last block, truncated or not,
  * and its states there.  mtr_engine_stcorr_series / _needle_series keep their lock-step *n_points / *dropped — the counts of a stream
  * that was never closed — and the rows of a closed stream hold 0.0f behind its own points (mtr_engine_series_points); a truncated last
@@ -39,7 +41,7 @@ int  mtr_engine_process_device_ragged (mtr_engine* e, const float* d_audio, uint
                                        uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);
 int  mtr_engine_process_host_ragged (mtr_engine* e, const float* h_audio, uint64_t n_frames,
                                      uint64_t stream_stride_frames, const uint64_t* frames);
-/* points [count]: the points each stream's own series of `meter` (MTR_METER_STCORR or MTR_METER_NEEDLE; anything else, or a meter the
+/* points [count]: the points each stream's own series of `meter` (MTR_METER_STCORR, MTR_METER_NEEDLE or MTR_METER_KMETER; anything else, or a meter the
  * engine lacks: MTR_ERR_ARG) has got since reset, dropped ones included: the whole blocks it completed and, if it was closed inside
  * one, the truncated block.  Period 0: no series, 0.  Counted on the host: no device work, no synchronisation.  Zeroed by the meter's
  * reset and by mtr_engine_reset. */

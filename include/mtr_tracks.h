@@ -29,7 +29,8 @@ extern "C" {
  * call on the streams that hold it (mtr_engine_process_device / _host, an LV2 block) runs the length-masking kernels, end 0 for the
  * closed ones.  The per-meter resets (mtr_engine_dr14_reset, _kmeter_reset, _intstat_reset) reopen nothing.
  * Engines that hold SPECTR30, TPBALLIST, STCORR, NEEDLE or SURROUND: MTR_ERR_UNSUPPORTED, nothing queued, engine unchanged (STCORR and
- * NEEDLE beside these meters: mtr_engine_process_device_ragged / _host_ragged, mtr_ragged.h).
+ * NEEDLE beside these meters: mtr_engine_process_device_ragged / _host_ragged, mtr_ragged.h).  A KMETER engine with a period
+ * (mtr_engine_kmeter_set_period, mtr_kmeter.h) keeps a reading over time and is refused likewise: it takes the _ragged pair.
  * replaces: a host that stops calling run() at the track's end. */
 int  mtr_engine_process_device_tracks (mtr_engine* e, const float* d_audio, uint64_t n_frames,
                                        uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);

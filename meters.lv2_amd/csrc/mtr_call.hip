@@ -246,7 +246,9 @@ struct CallRun {
 			const uint64_t f = e->closed[c.off + i] ? 0 : c.frames ? c.frames[i] : c.n_frames;
 			h_end[i] = (uint32_t) f;
 			// (a closing stream's process () is one of f frames: kmeterdsp.cc:60-65 with fpp = f; every other stream takes the cursor's)
-			if (km) h_fall[i] = f && f < c.n_frames ? kmeter_fall (e, f) : 0.f;
+			// (with a period: one of the frames it has of the block it ends in, if it ends inside one)
+			const uint64_t kp = e->km.ser.period, kf = kp ? (e->pos.km.fill + f) % kp : f;
+			if (km) h_fall[i] = f && f < c.n_frames && kf ? kmeter_fall (e, kf) : 0.f;
 			if (!fused) { h_lim[i] = h_from[i] = 0; continue; }
 			// fragments that end at or before the stream's end
 			const uint32_t nf = (uint32_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
@@ -493,14 +495,13 @@ struct CallRun {
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
 			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
-			for (int k = 0; k < 2; ++k) {
-				const bool sc = k == 0;
-				if (!(meters & (sc ? MTR_METER_STCORR : MTR_METER_NEEDLE))) continue;
-				const uint64_t P = sc ? e->sc.ser.period : e->nd.ser.period;
+			const struct { uint32_t bit; uint64_t P, fill; std::vector<uint64_t>& points; } ser[3] = {
+				{ MTR_METER_STCORR, e->sc.ser.period, e->pos.sc.fill, e->sc.points }, { MTR_METER_NEEDLE, e->nd.ser.period, e->pos.nd.fill, e->nd.points },
+				{ MTR_METER_KMETER, e->km.ser.period, e->pos.km.fill, e->km.points } };
+			for (const auto& q : ser) {
 				uint64_t whole = 0;
 				uint32_t partial = 0;
-				if (P && series_cut (sc ? e->pos.sc.fill : e->pos.nd.fill, P, c.n_frames, f, &whole, &partial))
-					(sc ? e->sc.points : e->nd.points)[g] += whole + partial;
+				if ((meters & q.bit) && q.P && series_cut (q.fill, q.P, c.n_frames, f, &whole, &partial)) q.points[g] += whole + partial;
 			}
 			if (log) {
 				// periods the stream completed: those that end within the fragments it ended (as upload_lengths counts them)
@@ -674,6 +675,8 @@ static int tracks_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frame
 	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST;
 	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok))
 		return fail (MTR_ERR_UNSUPPORTED, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only");
+	if ((e->cfg.meters & MTR_METER_KMETER) && e->km.ser.period)
+		return fail (MTR_ERR_UNSUPPORTED, "track lengths: a KMETER engine with a period keeps a reading series (mtr_engine_process_*_ragged)");
 	for (uint32_t i = 0; i < n; ++i)
 		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "track lengths: frames[s] > n_frames");
 	return MTR_OK;
@@ -720,10 +723,10 @@ int mtr_engine_process_host_ragged (mtr_engine* e, const float* h_audio, uint64_
 int mtr_engine_series_points (mtr_engine* e, uint32_t meter, uint32_t first, uint32_t count, uint64_t* points)
 {
 	if (!e || !points) return fail (MTR_ERR_ARG, "mtr_engine_series_points: null argument");
-	if ((meter != MTR_METER_STCORR && meter != MTR_METER_NEEDLE) || !(e->cfg.meters & meter))
-		return fail (MTR_ERR_ARG, "mtr_engine_series_points: meter is MTR_METER_STCORR or MTR_METER_NEEDLE, one the engine holds");
+	if ((meter != MTR_METER_STCORR && meter != MTR_METER_NEEDLE && meter != MTR_METER_KMETER) || !(e->cfg.meters & meter))
+		return fail (MTR_ERR_ARG, "mtr_engine_series_points: meter is MTR_METER_STCORR, MTR_METER_NEEDLE or MTR_METER_KMETER, one the engine holds");
 	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
-	const std::vector<uint64_t>& v = meter == MTR_METER_STCORR ? e->sc.points : e->nd.points;
+	const std::vector<uint64_t>& v = meter == MTR_METER_STCORR ? e->sc.points : meter == MTR_METER_NEEDLE ? e->nd.points : e->km.points;
 	for (uint32_t i = 0; i < count; ++i) points[i] = v[first + i];
 	return MTR_OK;
 }

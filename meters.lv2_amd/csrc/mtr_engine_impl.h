@@ -103,6 +103,7 @@ struct Cursors {
 	uint64_t dr_scnt = 0;         // samples in the open DR-14 window
 	uint32_t km_fpp = 0;          // Kmeterdsp's frames per period and the fall-back factor that goes with it
 	float    km_fall = 0.f;
+	SeriesPos km;                 // KMETER with a period: where its reading series stands (km_fpp / km_fall are then the period's)
 	SeriesPos sc, nd, su;         // STCORR, NEEDLE, SURROUND: where their reading series stand (mtr_series.h)
 	uint32_t su_fpp = 0;          // SURROUND: its Kmeterdsps' frames per period with the fall-back factor that goes with it
 	float    su_fall = 0.f;
@@ -249,6 +250,13 @@ struct mtr_engine {
 		DevBuf<double>             piece;
 		DevBuf<float>              max;
 		double                     pw1[3];
+		// the reading series (mtr_engine_kmeter_set_period, P > 0): k_kmeter_blocks
+		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
+		DevBuf<unsigned char>      open;        // [S] mtr_kmeter_open: the blob's header and the open block's carry per channel
+		DevBuf<double>             bpiece;      // [S][pieces][C][MTR_KMB_PIECE]
+		DevBuf<float>              s_rms, s_peak;   // [S][cap][C]
+		double                     k[11];       // mtr_kmb_consts: the pieces kernel's constants
+		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (ragged calls: mtr_ragged.h)
 	} km;
 	struct Stcorr {                             // STCORR (mtr_stcorr.hip)
 		DevBuf<mtr_stcorr_state>   state;       // [S]
@@ -325,7 +333,8 @@ struct Call {
 };
 
 // The per-stream ends of a ragged call on the device, as the side meters' steps get them: ends[i] = the call frame at which stream i of the
-// view ends (0: closed, untouched), km_fall[i] = Kmeterdsp's fall-back factor for a stream that ends inside the call (KMETER engines).
+// view ends (0: closed, untouched), km_fall[i] = Kmeterdsp's fall-back factor for a stream that ends inside the call (KMETER engines: that of
+// its frames in the call, or — with a period — of its frames in the truncated block).
 // Both null on a dense call: the steps then launch the dense instantiations.
 struct StreamEnds {
 	const uint32_t* ends = nullptr;
@@ -384,8 +393,9 @@ struct SideMeter {
 };
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
-extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter;
-inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter };
+extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter;
+inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
+                                                    &kmeter_series_meter };   // (KMETER's second row: the blob section of its open block, behind every older one)
 
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view

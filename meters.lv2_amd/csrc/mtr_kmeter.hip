@@ -27,6 +27,24 @@
 // and writes NO piece slot: k_kmeter_final adds the stream's own chunks only — it never reads those slots.  E = 0 (a closed stream,
 // frames [s] == 0): nothing is written, not even the + 1e-20f.  Groups start on multiples of four frames whatever E is: the 16-byte
 // path is the dense one's.  The dense instantiations are the kernels as they always were.
+//
+// THE READING SERIES (mtr_engine_kmeter_set_period, P > 0: k_kmeter_blocks / k_kmeter_walk; the kernels above are then not launched).
+// The streams are metered as by a host that calls process (p, P) + read (rms, peak) on consecutive blocks of exactly P frames wherever
+// the engine calls cut the audio (kmeterdsp.cc:56-155).  A call is cut into PIECES as mtr_stcorr.hip and mtr_surround.hip cut it
+// (mtr_stcorr_scan.h: the open block's rest, whole blocks, what the call leaves open, each cut at `chunk` = 32768 frames), one workgroup
+// per (stream, piece), lane t on the four frames b0 + 4 t, + 4 (t + 256), ... of its piece: 16-byte loads where the piece's first frame
+// lies on 16 bytes of the buffer, 8- or 4-byte ones where an odd P or a block that starts mid-row leaves it elsewhere, and nothing outside
+// the piece's frames.  The weights are the pointwise ones of mtr_surround.hip on s = x^2: a frame at offset j of its
+// block gives w r^(E - 1 - j) s to z1 at the piece's end E and w r^(ge - 1 - j) (c_k + 4 w b^k) s to z2 — ge its group's end, k the group
+// ends behind it inside the piece; the groups of four restart at each block's start, so a piece may start and end inside one.  Frames at
+// j >= L - L mod 4 (L = P, or what a ragged call leaves a closing stream of its last block) weigh nothing and do not enter the maximum
+// (:79).  The powers come from exp () of logarithms the host computed, once per lane, and move by constants from there.  A square that is
+// not finite makes the reference's z1 NaN at the next frame (Inf - Inf) unless it is the block's last counted frame: a NaN is added for
+// it.  One thread per (stream, channel) walks the pieces in order, carries (z1, z2) in closed form (mat_pow) — also through a call that
+// ends inside a group — and at every block's end does :101-139 in f32, one rounding per operation, and appends (rms, peak).
+// Between two calls the open block's (z1, z2) stay doubles and its maximum an f32, with what they were IN FRONT OF the group of four that
+// the call left open (bz1, btmax; z2 moves at group ends only): a ragged call that closes the stream before that group completes drops
+// the whole group from filter and peak, as the n / 4 groups of the truncated block demand.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +53,7 @@
 #include <vector>
 
 #include "mtr_engine_impl.h"
+#include "mtr_stcorr_scan.h"
 
 /* Kmeterdsp per (stream, channel) state (jmeters/kmeterdsp.h) */
 typedef struct mtr_kmeter_state {
@@ -55,6 +74,54 @@ typedef struct mtr_kmeter_args {
 	const uint32_t* ends;         /* [S] per-stream ends of a ragged call (the LEN instantiations), NULL on a dense one ... */
 	const float*    falls;        /* [S] ... and the fall-back factor of each stream that ends inside the call */
 } mtr_kmeter_args;
+
+/* the reading series: per (stream, channel) the open block between two calls */
+typedef struct mtr_kmeter_carry {
+	double   z1, z2;              /* where the block stands: exact continuations inside a block, the f32 of :106-107 at its start */
+	double   bz1;                 /* z1 in front of the group of four that is open (= z1 where none is) */
+	float    tmax, btmax;         /* max x^2 of the open block so far; ... in front of the open group */
+} mtr_kmeter_carry;
+
+/* per stream: the section a state blob carries at P > 0.  In front, for the blob (whose header has no room for them): the engine's
+ * period, the frames into the open block, Kmeterdsp's _fpp / _fall — the host's copies rule, export writes them in */
+typedef struct mtr_kmeter_open {
+	uint32_t         period, fill;
+	uint32_t         fpp;
+	float            fall;
+	mtr_kmeter_carry ch[2];
+} mtr_kmeter_open;
+
+#define MTR_KMB_PIECE 5            /* doubles per (stream, piece, channel): what the piece's frames give to z1 and z2 at its end, max x^2; what
+                                    * those in front of its last group end give to z1 THERE, and their max x^2 */
+
+/* the constants of k_kmeter_blocks, computed once on the host in double (kr = 1 - omega, ka = kr^4, kb = 1 - 4 omega) */
+typedef struct mtr_kmb_consts {
+	double lkr, lkb;              /* log kr, log kb */
+	double kri, kai, kbi, kr3;    /* 1 / kr, 1 / ka, 1 / kb, kr^3 */
+	double ca, cb;                /* omega c / (ka - kb), omega (4 omega - c / (ka - kb)): the z2 weight of a frame is kr^(..) (ca ka^k + cb kb^k) */
+	double st1, sta, stb;         /* kr^-(4 NT), ka^-NT, kb^-NT: from one of a lane's groups of four frames to its next */
+} mtr_kmb_consts;
+
+typedef struct mtr_kmb_args {
+	const float*    audio;        /* [S][stride][C] */
+	uint64_t        stride, n_frames;
+	uint64_t        period;       /* P > 0 */
+	uint64_t        e0;           /* call frame at which the block open on entry ends */
+	uint32_t        n_streams, n_channels, n_pieces, chunk;
+	float           omega, fall;  /* 9.72f / fs, the fall-back factor of fpp = P */
+	int32_t         hold;
+	double          pw[3];        /* A = [[a, 0], [c, b]] per group of four frames */
+	mtr_kmb_consts  k;
+	uint32_t        capacity;     /* points per stream the series hold */
+	uint64_t        point0;       /* blocks completed before this call */
+	mtr_kmeter_state* state;      /* [S][2]: rms, peak of the last completed block, cnt (z1, z2: the carry's, as f32) */
+	mtr_kmeter_open* open;        /* [S] */
+	double*         piece;        /* [S][n_pieces][C][MTR_KMB_PIECE] */
+	float*          s_rms;        /* [S][capacity][C], NULL if capacity == 0 */
+	float*          s_peak;
+	const uint32_t* ends;         /* [S] per-stream ends of a ragged call (the LEN instantiations), NULL on a dense one ... */
+	const float*    falls;        /* [S] ... and the fall-back factor of the truncated block of each stream that ends inside one */
+} mtr_kmb_args;
 
 namespace {
 
@@ -191,6 +258,223 @@ __global__ void k_kmeter_final (const mtr_kmeter_args a)
 	else { st->peak *= fall; st->peak += 1e-10f; }
 }
 
+// ---- the reading series (P > 0) ----------------------------------------------------------------------------------------------------
+
+constexpr uint32_t KMB_CHUNK = 32768;    // frames per piece at most: a multiple of four
+
+using mtr_sc::Piece;
+using mtr_sc::piece_of;
+using mtr_sc::ipow;
+
+// the call frame at which the block of piece `pc` starts (negative: it started in an earlier call)
+__device__ __forceinline__ int64_t kmb_block_start (const mtr_kmb_args& a, const Piece& pc)
+{
+	if ((uint64_t) pc.b0 < a.e0) return (int64_t) a.e0 - (int64_t) a.period;
+	return (int64_t) (a.e0 + ((uint64_t) pc.b0 - a.e0) / a.period * a.period);
+}
+
+// LEN: the stream ends at call frame a.ends[s] (0: closed, untouched; n_frames: the dense call's stream).  A piece that starts at or
+// behind the end returns before it loads anything; the block an end inside the call cuts has L = the frames the stream has of it.
+template <int C, bool LEN>
+__global__ __launch_bounds__ (NT) void k_kmeter_blocks (const mtr_kmb_args a)
+{
+	const uint32_t s = blockIdx.y;
+	const Piece pc = piece_of (a, blockIdx.x);
+	const int64_t b0 = pc.b0;
+	int64_t b1 = pc.b1;
+	const int64_t blk0 = kmb_block_start (a, pc);
+	int64_t L = (int64_t) a.period;
+	if constexpr (LEN) {
+		const int64_t end = (int64_t) a.ends[s];
+		if (b0 >= end) return;                                     // (uniform in the workgroup; end 0: every piece of the stream)
+		if (end < (int64_t) a.n_frames && end < blk0 + L) L = end - blk0;   // one last process (p, L)
+		if (end < b1) b1 = end;
+	}
+	const float* const src = a.audio + (size_t) s * a.stride * C;
+	const int64_t Lg = L & ~(int64_t) 3;                           // frames of the block that count (kmeterdsp.cc:79)
+	// block offset at which the piece's z1 stands: its end, but never inside the block's dropped trailing frames
+	const int64_t E1 = b1 - blk0 < Lg ? b1 - blk0 : Lg;
+	const int64_t pe = E1 & ~(int64_t) 3;                           // ... and its last group end
+	const double up = ipow (a.k.kri, (uint64_t) (E1 - pe));         // from a weight at E1 to the weight at pe
+	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	// how wide the piece's loads may be: the address of its first frame (every lane's first frame lies 4 frames x a multiple behind it)
+	// — the address itself, not base and frame index apart: a call that continues a buffer at an odd frame keeps the wide path
+	const size_t a0 = reinterpret_cast<size_t> (src + (size_t) b0 * C);
+	const bool w16 = (a0 & 15) == 0;
+	const bool w8 = (a0 & 7) == 0;
+
+	// the powers of the lane's first frame — its distance to E1 for z1, inside its group and in group ends behind it for z2 — from exp ();
+	// from one of its groups of four frames to the next (4 NT frames = NT groups) they move by constants
+	int64_t f0 = b0 + 4 * (int64_t) tid;
+	const int64_t jt0 = f0 - blk0;
+	const int64_t gt0 = (jt0 | 3) + 1;                             // its group's end
+	int64_t kt = (pe - gt0) >> 2;                                  // group ends behind that one inside the piece; < 0: none
+	double pt1 = (double) a.omega * exp ((double) (E1 - 1 - jt0) * a.k.lkr);
+	double pta = a.k.ca * exp ((double) (4 * kt) * a.k.lkr), ptb = a.k.cb * exp ((double) kt * a.k.lkb);
+	const double pg0 = ipow (1.0 - (double) a.omega, (uint64_t) (gt0 - 1 - jt0));
+	double e1[C], e2[C], eb[C];
+	float tm[C], tb[C];
+#pragma unroll
+	for (int c = 0; c < C; ++c) { e1[c] = 0.0; e2[c] = 0.0; eb[c] = 0.0; tm[c] = 0.f; tb[c] = 0.f; }
+
+	for (; f0 < b1; f0 += 4 * NT) {
+		float v[4 * C];
+		const float* const p = src + (size_t) f0 * C;
+		if (f0 + 4 <= b1 && w16) {
+#pragma unroll
+			for (int i = 0; i < C; ++i) {
+				const float4 q = reinterpret_cast<const float4*> (p)[i];
+				v[4 * i] = q.x; v[4 * i + 1] = q.y; v[4 * i + 2] = q.z; v[4 * i + 3] = q.w;
+			}
+		} else if (f0 + 4 <= b1 && w8) {
+#pragma unroll
+			for (int i = 0; i < 2 * C; ++i) {
+				const float2 q = reinterpret_cast<const float2*> (p)[i];
+				v[2 * i] = q.x; v[2 * i + 1] = q.y;
+			}
+		} else {
+#pragma unroll
+			for (int k = 0; k < 4; ++k)
+#pragma unroll
+				for (int c = 0; c < C; ++c) v[k * C + c] = f0 + k < b1 ? p[k * C + c] : 0.f;
+		}
+		const int64_t j0 = f0 - blk0;
+		int64_t kk = kt;
+		double p1 = pt1, pa = pta, pb = ptb, pg = pg0;               // omega kr^(E1 - 1 - j), ca ka^k, cb kb^k, kr^(ge - 1 - j)
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int64_t jk = j0 + k;
+			if (f0 + k < b1 && jk < Lg) {                           // (jk < E1 with it: E1 = min (Lg, b1 - blk0))
+				const bool grp = kk >= 0, front = jk < pe;          // its group ends inside the piece; it lies in front of the last group end
+				const double wz1 = p1, wz2 = pg * (pa + pb), wzb = p1 * up;
+#pragma unroll
+				for (int c = 0; c < C; ++c) {
+					const float x = v[k * C + c];
+					float sq = x * x;
+					tm[c] = tm[c] < sq ? sq : tm[c];                 // kmeterdsp.cc:84: if (t < s) t = s (a NaN never enters)
+					if (front) tb[c] = tb[c] < sq ? sq : tb[c];
+					if (!isfinite (sq) && !(jk == Lg - 1 && sq == INFINITY)) sq = NAN;   // (see the head of the file)
+					e1[c] = fma (wz1, (double) sq, e1[c]);
+					if (grp) e2[c] = fma (wz2, (double) sq, e2[c]);   // (no 0 x NaN: a later ragged close may drop the open group whole)
+					if (front) eb[c] = fma (wzb, (double) sq, eb[c]);
+				}
+			}
+			p1 *= a.k.kri;
+			if (((jk + 1) & 3) == 0) { kk -= 1; pa *= a.k.kai; pb *= a.k.kbi; pg = a.k.kr3; }
+			else pg *= a.k.kri;
+		}
+		pt1 *= a.k.st1; pta *= a.k.sta; ptb *= a.k.stb; kt -= NT;
+	}
+
+	__shared__ double shd[NT / 64][C][3];
+	__shared__ float shf[NT / 64][C][2];
+#pragma unroll
+	for (int c = 0; c < C; ++c) {
+#pragma unroll
+		for (int d = 32; d >= 1; d >>= 1) {
+			e1[c] += __shfl_xor (e1[c], d, 64); e2[c] += __shfl_xor (e2[c], d, 64); eb[c] += __shfl_xor (eb[c], d, 64);
+			tm[c] = fmaxf (tm[c], __shfl_xor (tm[c], d, 64)); tb[c] = fmaxf (tb[c], __shfl_xor (tb[c], d, 64));
+		}
+		if (lane == 0) { shd[wid][c][0] = e1[c]; shd[wid][c][1] = e2[c]; shd[wid][c][2] = eb[c]; shf[wid][c][0] = tm[c]; shf[wid][c][1] = tb[c]; }
+	}
+	__syncthreads ();
+	if (tid < C) {
+		double x1 = 0.0, x2 = 0.0, xb = 0.0;
+		float m = 0.f, mb = 0.f;
+		for (int w = 0; w < NT / 64; ++w) {
+			x1 += shd[w][tid][0]; x2 += shd[w][tid][1]; xb += shd[w][tid][2];
+			m = fmaxf (m, shf[w][tid][0]); mb = fmaxf (mb, shf[w][tid][1]);
+		}
+		double* const out = a.piece + (((size_t) s * a.n_pieces + blockIdx.x) * C + tid) * MTR_KMB_PIECE;
+		out[0] = x1; out[1] = x2; out[2] = (double) m; out[3] = xb; out[4] = (double) mb;
+	}
+}
+
+// one thread per (stream, channel): the pieces in order, and kmeterdsp.cc:74-75, 101-139 + read (rms, peak) at every end of a block.
+// LEN: the pieces up to the stream's end; an end inside the call and inside a block closes that block there — fpp = its frames, the
+// fall-back factor a.falls[s] — as the stream's last point.  end == 0: the stream is not touched.
+template <bool LEN>
+__global__ void k_kmeter_walk (const mtr_kmb_args a)
+{
+#pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= a.n_streams * a.n_channels) return;
+	const uint32_t s = i / a.n_channels, c = i % a.n_channels, C = a.n_channels;
+	int64_t end = (int64_t) a.n_frames;
+	if constexpr (LEN) {
+		end = (int64_t) a.ends[s];
+		if (end == 0) return;
+	}
+	mtr_kmeter_state* const st = a.state + (size_t) s * 2 + c;
+	mtr_kmeter_carry* const cy = &a.open[s].ch[c];
+	const double kr = 1.0 - (double) a.omega;
+	double z1 = cy->z1, z2 = cy->z2, bz1 = cy->bz1;
+	float tmax = cy->tmax, btmax = cy->btmax;
+	float rms = st->rms, peak = st->peak;
+	int32_t cnt = st->cnt;
+	uint64_t point = a.point0;
+	for (uint32_t pi = 0; pi < a.n_pieces; ++pi) {
+		Piece pc = piece_of (a, pi);
+		const int64_t blk0 = kmb_block_start (a, pc);
+		int64_t L = (int64_t) a.period;
+		if constexpr (LEN) {
+			if (pc.b0 >= end) break;
+			if (end < (int64_t) a.n_frames && end < blk0 + L) L = end - blk0;
+			if (end <= pc.b1) {
+				pc.b1 = end;
+				if (L != (int64_t) a.period) pc.closes = true;         // one last process (), of what the stream has of the block
+			}
+		}
+		const int64_t Lg = L & ~(int64_t) 3;
+		const int64_t p0 = pc.b0 - blk0, E1 = pc.b1 - blk0 < Lg ? pc.b1 - blk0 : Lg, pe = E1 & ~(int64_t) 3;   // (as the pieces kernel's)
+		if (p0 == 0) {                                             // :74-75 (a NaN state falls through, as there; it is an f32 here)
+			z1 = z1 > 50 ? 50 : (z1 < 0 ? 0 : z1);
+			z2 = z2 > 50 ? 50 : (z2 < 0 ? 0 : z2);
+			tmax = 0.f;
+			bz1 = z1; btmax = 0.f;
+		}
+		const double* const pv = a.piece + (((size_t) s * a.n_pieces + pi) * C + c) * MTR_KMB_PIECE;
+		if (E1 > p0) {
+			if (pe >= p0) {                                        // the piece holds a group end: the state in front of its open group
+				bz1 = pow (kr, (double) (pe - p0)) * z1 + pv[3];
+				const float pb = (float) pv[4];
+				btmax = tmax < pb ? pb : tmax;
+			}
+			const int64_t m = (E1 >> 2) - (p0 >> 2);                   // group ends in (p0, E1]
+			if (m > 0) {
+				const Mat g = mat_pow (a.pw[0], a.pw[1], a.pw[2], (double) m);
+				z2 = g.b * z2 + g.c * ipow (a.k.kri, (uint64_t) (p0 & 3)) * z1 + pv[1];
+			}
+			z1 = pow (kr, (double) (E1 - p0)) * z1 + pv[0];
+			const float pm = (float) pv[2];
+			tmax = tmax < pm ? pm : tmax;
+		} else if (LEN && pc.closes && pc.b0 == 0 && Lg < p0) {
+			// the stream ends before the group that the call before left open completes: that group's frames drop out, all of them
+			z1 = bz1; tmax = btmax;
+		}
+		if (!pc.closes) continue;
+		float f1 = (float) z1, f2 = (float) z2, t = tmax;
+		if (isnan (f1)) f1 = 0;                                    // :101-103
+		if (isnan (f2)) f2 = 0;
+		if (!isfinite (t)) t = 0;
+		z1 = (double) (f1 + 1e-20f);                               // :106-107
+		z2 = (double) (f2 + 1e-20f);
+		bz1 = z1; btmax = 0.f; tmax = 0.f;
+		rms = sqrtf (2.0f * f2);                                   // :109, 112-121 (a read follows every block: the flag is always set)
+		t = sqrtf (t);
+		if (t >= peak) { peak = t; cnt = a.hold; }                 // :124-139
+		else if (cnt > 0) cnt -= (int32_t) L;
+		else { peak *= L == (int64_t) a.period ? a.fall : a.falls[s]; peak += 1e-10f; }
+		if (point < a.capacity) {
+			const size_t o = ((size_t) s * a.capacity + point) * C + c;
+			a.s_rms[o] = rms; a.s_peak[o] = peak;
+		}
+		++point;
+	}
+	cy->z1 = z1; cy->z2 = z2; cy->bz1 = bz1; cy->tmax = tmax; cy->btmax = btmax;
+	st->z1 = (float) z1; st->z2 = (float) z2; st->rms = rms; st->peak = peak; st->cnt = cnt;
+}
+
 }  // namespace
 
 static void mtr_kmeter_powers (float omega, double* pw1 /* [3] */)
@@ -222,6 +506,32 @@ static int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
+static void mtr_kmb_constants (float omega, const double* pw /* [3] */, mtr_kmb_consts* k)
+{
+	const double w = (double) omega, kr = 1.0 - w, ka = pw[0], kb = pw[2], cab = pw[1] / (ka - kb);
+	k->lkr = log (kr); k->lkb = log (kb);
+	k->kri = 1.0 / kr; k->kai = 1.0 / ka; k->kbi = 1.0 / kb; k->kr3 = kr * kr * kr;
+	k->ca = w * cab; k->cb = w * (4.0 * w - cab);
+	k->st1 = pow (kr, (double) (-4 * NT)); k->sta = pow (ka, (double) -NT); k->stb = pow (kb, (double) -NT);
+}
+
+static int mtr_launch_kmb (const mtr_kmb_args& a, void* stream)
+{
+	hipStream_t st = (hipStream_t) stream;
+	const dim3 g (a.n_pieces, a.n_streams), b (NT);
+	const uint32_t n = a.n_streams * a.n_channels;
+	if (a.ends) {
+		if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_blocks<2, true>), g, b, 0, st, a);
+		else                   hipLaunchKernelGGL ((k_kmeter_blocks<1, true>), g, b, 0, st, a);
+		hipLaunchKernelGGL (k_kmeter_walk<true>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	} else {
+		if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_blocks<2, false>), g, b, 0, st, a);
+		else                   hipLaunchKernelGGL ((k_kmeter_blocks<1, false>), g, b, 0, st, a);
+		hipLaunchKernelGGL (k_kmeter_walk<false>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	}
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
 // ---- KMETER in the engine: the call's step, the blob's section, reset, the reading ------------------------------------------------------
 
 // kmeterdsp.cc:60-65: the fall-back factor of a process () of n frames (15 dB/s)
@@ -230,8 +540,45 @@ float kmeter_fall (const mtr_engine* e, uint64_t n)
 	return powf (10.0f, -0.05f * 15.0f * ((float) n / e->cfg.sample_rate));
 }
 
+static uint32_t kmeter_min_period (const mtr_engine* e) { return (uint32_t) e->cfg.sample_rate / 20; }
+
+// P > 0.  The blocks of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+static int kmeter_blocks_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
+{
+	const size_t vo = c.off;
+	const uint64_t P = e->km.ser.period;
+	const uint32_t cap = e->km.ser.cap, C = e->cfg.n_channels;
+	mtr_kmb_args ka;
+	memset (&ka, 0, sizeof (ka));
+	ka.audio = c.audio; ka.stride = c.stride; ka.n_frames = c.n_frames;
+	ka.period = P; ka.e0 = series_e0 (e->pos.km, P, c.n_frames);
+	ka.n_streams = c.cnt; ka.n_channels = C; ka.chunk = KMB_CHUNK;
+	ka.n_pieces = mtr_sc::n_pieces (c.n_frames, ka.e0, P, ka.chunk);
+	if (nx.km_fpp != (uint32_t) P) {                                   // kmeterdsp.cc:65-70
+		nx.km_fall = kmeter_fall (e, P);
+		nx.km_fpp = (uint32_t) P;
+	}
+	ka.fall = nx.km_fall;
+	ka.hold = (int32_t) (0.5f * e->cfg.sample_rate + 0.5f);             // :52
+	ka.omega = 9.72f / e->cfg.sample_rate;
+	memcpy (ka.pw, e->km.pw1, sizeof (ka.pw));
+	static_assert (sizeof (mtr_kmb_consts) == sizeof (e->km.k), "mtr_kmb_consts");
+	memcpy (&ka.k, e->km.k, sizeof (ka.k));
+	ka.capacity = cap; ka.point0 = e->pos.km.points;
+	if (e->km.bpiece.reserve ((size_t) e->cfg.n_streams * ka.n_pieces * C * MTR_KMB_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc KMETER pieces");
+	ka.state = e->km.state.p + vo * 2;
+	ka.open = reinterpret_cast<mtr_kmeter_open*> (e->km.open.p) + vo;
+	ka.piece = e->km.bpiece.p + vo * ka.n_pieces * C * MTR_KMB_PIECE;
+	if (cap) { ka.s_rms = e->km.s_rms.p + vo * cap * C; ka.s_peak = e->km.s_peak.p + vo * cap * C; }
+	ka.ends = se.ends; ka.falls = se.km_fall;
+	if (mtr_launch_kmb (ka, c.st)) return fail (MTR_ERR_HIP, "k_kmeter_blocks launch");
+	nx.km = series_advance (e->pos.km, P, c.n_frames);
+	return MTR_OK;
+}
+
 static int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
+	if (e->km.ser.period) return kmeter_blocks_step (e, c, nx, se);
 	const size_t vo = c.off;
 	mtr_kmeter_args ka;
 	ka.audio = c.audio; ka.stride = c.stride; ka.n_groups = c.n_frames / 4;
@@ -258,6 +605,47 @@ static void kmeter_sections (const mtr_engine* e, std::vector<StateSection>& v)
 	v.push_back ({ e->km.state.p, 2 * sizeof (mtr_kmeter_state) });
 }
 
+// With a period the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): the open block.
+// Its header: period, the frames into the open block, _fpp / _fall.  An engine takes a blob of its own period only
+static void kmeter_open_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	if (e->km.ser.period) v.push_back ({ e->km.open.p, sizeof (mtr_kmeter_open) });
+}
+
+constexpr size_t KM_HDR_BYTES = offsetof (mtr_kmeter_open, ch);
+constexpr const char* KM_CORRUPT = "mtr_engine_state_import: corrupt blob (period of the KMETER series)";
+
+static void kmeter_hdr_write (const mtr_engine* e, void* out)
+{
+	mtr_kmeter_open h;
+	memset (&h, 0, KM_HDR_BYTES);
+	h.period = e->km.ser.period; h.fill = (uint32_t) e->pos.km.fill; h.fpp = e->pos.km_fpp; h.fall = e->pos.km_fall;
+	memcpy (out, &h, KM_HDR_BYTES);
+}
+
+static int kmeter_hdr_check (const mtr_engine* e, const void* in, bool fresh)
+{
+	mtr_kmeter_open h;
+	memcpy (&h, in, KM_HDR_BYTES);
+	if (!h.period || !series_blob_ok (h.period, h.fill, kmeter_min_period (e), 0x7ffffffeu) || (h.fpp && h.fpp != h.period)) return fail (MTR_ERR_STATE, KM_CORRUPT);
+	if (h.period != e->km.ser.period || (!fresh && h.fill != e->pos.km.fill))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period of the KMETER series)");
+	return MTR_OK;
+}
+
+static void kmeter_hdr_take (mtr_engine* e, const void* in)
+{
+	mtr_kmeter_open h;
+	memcpy (&h, in, KM_HDR_BYTES);
+	e->pos.km.fill = h.fill; e->pos.km_fpp = h.fpp; e->pos.km_fall = h.fall;
+}
+
+static int kmeter_open_reset (mtr_engine*) { return MTR_OK; }                                  // (the meter's first row resets all of it)
+static int kmeter_open_step (mtr_engine*, const Call&, Cursors&, const StreamEnds&) { return MTR_OK; }   // (... and queues all of it)
+
+static constinit BlobHeader kmeter_hdr = { 0, KM_HDR_BYTES, KM_CORRUPT, kmeter_hdr_write, kmeter_hdr_check, kmeter_hdr_take };
+constinit SideMeter kmeter_series_meter = { MTR_METER_KMETER, 0, nullptr, nullptr, kmeter_open_reset, kmeter_open_step, kmeter_open_sections, &kmeter_hdr };
+
 constinit SideMeter kmeter_meter = { MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)",
                                            nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr };
 
@@ -271,10 +659,57 @@ int mtr_engine_kmeter_reset (mtr_engine* e)
 	const size_t n = (size_t) e->cfg.n_streams * 2;
 	if (e->km.state.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc KMETER state");
 	mtr_kmeter_powers (9.72f / e->cfg.sample_rate, e->km.pw1);           // kmeterdsp.cc:52
+	{
+		mtr_kmb_consts k;
+		mtr_kmb_constants (9.72f / e->cfg.sample_rate, e->km.pw1, &k);
+		memcpy (e->km.k, &k, sizeof (k));
+	}
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemset (e->km.state.p, 0, n * sizeof (mtr_kmeter_state)));   // :142-146
 	e->pos.km_fpp = 0;                                                   // (the next process () works its fall-back factor out again)
 	e->pos.km_fall = 0.f;
+	// the reading series: emptied (a stream that a ragged call closes early leaves 0.0f behind its own points), the open block gone, P kept
+	if (e->km.open.n) HIPCHK (hipMemset (e->km.open.p, 0, e->km.open.n));
+	if (e->km.s_rms.n) HIPCHK (hipMemset (e->km.s_rms.p, 0, e->km.s_rms.n * sizeof (float)));
+	if (e->km.s_peak.n) HIPCHK (hipMemset (e->km.s_peak.p, 0, e->km.s_peak.n * sizeof (float)));
+	e->pos.km = {};
+	e->km.points.assign (e->cfg.n_streams, 0);
+	return MTR_OK;
+}
+
+static int no_kmeter (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_KMETER); }
+static const char* const NO_KMETER = "no KMETER in this engine";
+
+int mtr_engine_kmeter_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
+{
+	if (no_kmeter (e)) return fail (MTR_ERR_ARG, NO_KMETER);
+	int rc = series_configure_check (e, "mtr_engine_kmeter_set_period", period_frames, kmeter_min_period (e), "(uint32_t) sample_rate / 20");
+	if (rc || (rc = wait_stream (e))) return rc;
+	const size_t n = (size_t) e->cfg.n_streams * capacity_points * e->cfg.n_channels;
+	if ((rc = series_ring (e->km.s_rms, n, "hipMalloc KMETER series")) || (rc = series_ring (e->km.s_peak, n, "hipMalloc KMETER series"))) return rc;
+	if (period_frames && e->km.open.reserve ((size_t) e->cfg.n_streams * sizeof (mtr_kmeter_open))) return fail (MTR_ERR_NOMEM, "hipMalloc KMETER open blocks");
+	e->km.ser = { period_frames, capacity_points };
+	return mtr_engine_kmeter_reset (e);
+}
+
+int mtr_engine_kmeter_period (const mtr_engine* e, uint32_t* period_frames, uint32_t* capacity_points)
+{
+	if (no_kmeter (e)) return fail (MTR_ERR_ARG, NO_KMETER);
+	if (period_frames) *period_frames = e->km.ser.period;
+	if (capacity_points) *capacity_points = e->km.ser.cap;
+	return MTR_OK;
+}
+
+int mtr_engine_kmeter_series (mtr_engine* e, uint32_t first, uint32_t count, float* rms, float* peak, uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_kmeter (e), NO_KMETER, first, count);
+	if (rc) return rc;
+	const size_t take = series_counts (e->pos.km.points, e->km.ser.cap, capacity, n_points, dropped);
+	if ((!rms && !peak) || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	const size_t C = e->cfg.n_channels;
+	if (rms && (rc = series_fetch (rms, e->km.s_rms.p, C, first, e->km.ser.cap, capacity, take, count))) return rc;
+	if (peak && (rc = series_fetch (peak, e->km.s_peak.p, C, first, e->km.ser.cap, capacity, take, count))) return rc;
 	return MTR_OK;
 }
 
@@ -285,6 +720,7 @@ int mtr_engine_kmeter_read (mtr_engine* e, uint32_t first, uint32_t count, float
 	std::vector<mtr_kmeter_state> h ((size_t) count * 2);
 	HIPCHK (hipMemcpy (h.data (), e->km.state.p + (size_t) first * 2, h.size () * sizeof (mtr_kmeter_state), hipMemcpyDeviceToHost));
 	for (size_t i = 0; i < h.size (); ++i) { rms[i] = h[i].rms; peak[i] = h[i].peak; h[i].flag = 1; }
+	if (e->km.ser.period) return MTR_OK;                               // (the last completed block's: a read follows every block, nothing to arm)
 	HIPCHK (hipMemcpy (e->km.state.p + (size_t) first * 2, h.data (), h.size () * sizeof (mtr_kmeter_state), hipMemcpyHostToDevice));
 	return MTR_OK;
 }

@@ -37,7 +37,9 @@ constexpr size_t N_SIDE = sizeof (SIDE_METERS) / sizeof (SIDE_METERS[0]);
 
 // every array a stream carries from call to call, in the blob's order (a function of the configuration alone): the core's, then the
 // side meters' in the order of SIDE_METERS — with the core's per-channel arrays of layout 8, which came to the blob before STCORR did,
-// in front of STCORR's.  first[i]: the index of the first section of side meter i, if the engine has it.
+// in front of STCORR's.  first[i]: the index of the first section of side meter i, if the engine has it; NO_SECTION: the row pushed
+// none in this engine (KMETER's second row without a period), wherever the row stands in the table.
+constexpr size_t NO_SECTION = ~(size_t) 0;
 std::vector<StateSection> state_sections (const mtr_engine* e, size_t* first = nullptr)
 {
 	std::vector<StateSection> v;
@@ -53,8 +55,9 @@ std::vector<StateSection> state_sections (const mtr_engine* e, size_t* first = n
 			v.push_back ({ e->mc_tp_hold.p, C * sizeof (float) });
 		}
 		if (!(e->cfg.meters & SIDE_METERS[i]->bits)) continue;
-		if (first) first[i] = v.size ();
+		const size_t n0 = v.size ();
 		SIDE_METERS[i]->sections (e, v);
+		if (first) first[i] = v.size () > n0 ? n0 : NO_SECTION;
 	}
 	return v;
 }
@@ -66,6 +69,7 @@ HeaderAt header_at (const mtr_engine* e, const std::vector<StateSection>& secs, 
 {
 	const BlobHeader* const hd = SIDE_METERS[i]->hdr;
 	if (!hd || !(e->cfg.meters & SIDE_METERS[i]->bits)) return { nullptr, 0 };
+	if (first[i] == NO_SECTION) return { nullptr, 0 };             // (a header lives in the row's first section: no section, no header)
 	size_t o = hd->offset;
 	for (size_t k = 0; k < first[i]; ++k) o += (size_t) count * secs[k].elem;
 	return { const_cast<unsigned char*> (payload) + o, secs[first[i]].elem };
@@ -189,6 +193,7 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		// (... and it stands where the open streams do: its series has their points)
 		if (e->cfg.meters & MTR_METER_STCORR) e->sc.points[first + k] = e->pos.sc.points;
 		if (e->cfg.meters & MTR_METER_NEEDLE) e->nd.points[first + k] = e->pos.nd.points;
+		if (e->cfg.meters & MTR_METER_KMETER) e->km.points[first + k] = e->pos.km.points;
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;

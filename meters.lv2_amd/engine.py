@@ -156,6 +156,10 @@ def _load():
     L.mtr_engine_dr14_reset.argtypes = [vp]
     L.mtr_engine_kmeter_read.argtypes = [vp, u32, u32, vp, vp]
     L.mtr_engine_kmeter_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_kmeter_series"):                 # (an addition inside ABI version 2: the K-meter's reading series)
+        L.mtr_engine_kmeter_set_period.argtypes = [vp, u32, u32]
+        L.mtr_engine_kmeter_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_kmeter_series.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
     if hasattr(L, "mtr_engine_stcorr_read"):                   # (an addition inside ABI version 2: stereo phase correlation)
         L.mtr_stcorr_coef.argtypes = [f32, vp]
         L.mtr_engine_stcorr_set_period.argtypes = [vp, u32, u32]
@@ -586,7 +590,7 @@ class Engine:
                "process_host_ragged")
 
     def series_points(self, meter, first=0, count=None):
-        """[count] uint64: the points each stream's own STCORR or NEEDLE series (meter: METER_STCORR / METER_NEEDLE) has got since reset,
+        """[count] uint64: the points each stream's own STCORR, NEEDLE or KMETER series (meter: METER_STCORR / METER_NEEDLE / METER_KMETER) has got since reset,
         dropped ones included — of a stream that a ragged call closed, its whole blocks and the truncated one."""
         self._ragged(np.zeros(self.n_streams, np.uint64))
         count = self.n_streams - first if count is None else count
@@ -761,6 +765,31 @@ class Engine:
 
     def kmeter_reset(self):
         _check(lib.mtr_engine_kmeter_reset(self._h), "kmeter_reset")
+
+    def kmeter_set_period(self, period_frames, capacity_points=0):
+        """0: every call is one Kmeterdsp::process (); P > 0: blocks of exactly P frames wherever the calls cut the audio, read (rms, peak)
+        after each appended to a series of `capacity_points` per stream; kmeter_read() then returns the last completed block's and arms
+        nothing.  Only before the first process call since create / reset."""
+        if not hasattr(lib, "mtr_engine_kmeter_series"):
+            raise EngineError(f"{lib_path} has no K-meter reading series: rebuild it")
+        _check(lib.mtr_engine_kmeter_set_period(self._h, int(period_frames), int(capacity_points)), "kmeter_set_period")
+
+    def kmeter_period(self):
+        """(period_frames, capacity_points) as kmeter_set_period set them."""
+        if not hasattr(lib, "mtr_engine_kmeter_series"):
+            raise EngineError(f"{lib_path} has no K-meter reading series: rebuild it")
+        p, c = C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_kmeter_period(self._h, C.byref(p), C.byref(c)), "kmeter_period")
+        return p.value, c.value
+
+    def kmeter_series(self, first=0, count=None):
+        """(rms [count, kept, C], peak [count, kept, C], n_points, dropped): (rms, peak) after every completed block since reset that
+        the series holds."""
+        if not hasattr(lib, "mtr_engine_kmeter_series"):
+            raise EngineError(f"{lib_path} has no K-meter reading series: rebuild it")
+        (rms, peak), n, d = self._series("kmeter_series", first, count, [(self.n_channels,)] * 2,
+                                         lambda count, ptrs, *tail: lib.mtr_engine_kmeter_series(self._h, first, count, *ptrs, *tail))
+        return rms, peak, n, d
 
     def stcorr_set_period(self, period_frames, capacity_points=0):
         """0: every call is one Stcorrdsp::process (); P > 0: blocks of exactly P frames wherever the calls cut the audio, read () after
