@@ -66,6 +66,10 @@ constexpr int LDS_BYTES = XREF + 512;
 typedef unsigned char lds_u8;          // (generic pointers into the dynamic LDS block: the compiler infers the address space)
 
 __device__ __forceinline__ float max3abs (float m, float a, float b) { return fmaxf (fmaxf (m, fabsf (a)), fabsf (b)); }
+// The maximum of two floats that are neither negative nor NaN — such floats order as their bit patterns do, and the maximum is
+// the same bits (denormals are kept) — without the canonicalising v_max x, x that fmaxf puts in front of an operand it cannot
+// prove quiet.  For pk0, rml, rmr and the maxima of |x| they take: each comes out of a maximum seeded with +0, which drops NaNs.
+__device__ __forceinline__ float umaxf (float a, float b) { return __uint_as_float (max (__float_as_uint (a), __float_as_uint (b))); }
 __device__ __forceinline__ v2f fma2 (v2f a, v2f b, v2f c) { return __builtin_elementwise_fma (a, b, c); }
 __device__ __forceinline__ v2f scrub (v2f v) { return v2f{isfinite (v.x) ? v.x : 0.f, isfinite (v.y) ? v.y : 0.f}; }
 
@@ -113,8 +117,8 @@ constexpr float SCREEN_K_ABS = 0.0078125f;
 //     fl (F + eps) < max (pm, R')   =>   |Y| <= F + eps < R' (or pm)   =>   the dense peak is the same bits.
 //   * R holds only values of this launch that its final atomicMax counts for that (stream, channel) (pk0 and pkf only grow), never
 //     a hold or a previous call's peak, and no !peak_ok lane (LEN: those segments go to k_kwtp16_len) feeds it.
-//   * NaN: pk0 and pkf never hold one (fmaxf drops it, conservatively), and the vote's fmaxf would drop a NaN R too; a NaN in F
-//     still fails the vote.  The offers are non-negative floats, so their maximum is the unsigned one of their bit patterns.
+//   * NaN: pk0 and pkf never hold one (fmaxf drops it, conservatively), and the vote's fmaxf would drop a NaN R too; the vote's maximum of |F|
+//     drops NaNs as the dense fold does (a lane whose twelve values are all NaN votes with +0), and an Inf among them fails it.  The offers are non-negative floats, so their maximum is the unsigned one of their bit patterns.
 //   * An Inf sample: R becomes Inf (where its phase 0 counts), every finite chunk passes and Inf ones fail; the result is Inf
 //     either way.
 //   * R' overflows to +Inf where R * scale * 2^15 >= 2^128: a finite fl (F + eps) <= FLT_MAX lies below the true R', so a pass is
@@ -205,12 +209,16 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 // values (pm) or under its stream's reference (what the launch has already counted for the stream: above) cannot raise the
 // result, whatever the other two products add.  A step issues its eight chunks' first products back to back; each chunk's vote
 // runs behind the next chunk's MFMAs (chunk 7's behind its own tail), on complete accumulators, and leaves a lane mask, and the
-// step branches once, on the OR of the eight.  Every chunk one lane of which failed (a NaN or Inf fails) then runs MFMAs 0..17
+// step branches once, on the OR of the eight.  Every chunk one lane of which failed (an Inf fails; NaNs are dropped, as the dense fold drops them) then runs MFMAs 0..17
 // from zero on all four of its operands, read again from the ring — m16::block's order, so bit for bit the dense values — and
 // its maxima go into pm as in the dense form.  The step's ring stores (slot U: the oldest quarter of every window of its
 // products) come only behind that, so all of a step's windows are intact when a chunk completes, and no step leaves a chunk
 // pending: a rescale at the next step's head finds nothing to complete.  A vote reads pm and the bounds of its own step, which
 // only its own chunk's completion can change.  The peak is the dense form's on every input; only the time depends on the data.
+// The screened step issues no instruction its result does not need: the vote's maximum is six v_max3 (twelve values and a +0), pm
+// is one value per block and channel, the maxima of values that are never NaN (pk0, rml, rmr) are unsigned ones, and whether a
+// step lies in front of the call's last 24 frames is one scalar compare on the step's index (p0_steps) — 369 - 374 VALU
+// instructions per step where there were 395 - 397 (profiles/r23_kseg_trim/).
 //
 // LEN: the call carries per-stream lengths (a.ends, call-relative: mtr_engine_process_*_lengths).  Every frame at or past a stream's
 // end E is read as +0.0f — the global loads behind it are not issued — so the scale, the ring and the recurrence never see what the
@@ -345,7 +353,10 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	v2f pk0 = v2f{0.f, 0.f};                                           // phase 0: max |x[n - 24]|, exact
 	v2f pkf = v2f{0.f, 0.f};                                           // interpolated peaks that have left the scaled domain
 	float pm[4][2][2];                                                // running |max| of the accumulators, scaled, per block and channel: two
-	                                                                  // independent chains each (two dependent v_max3 in one MFMA's shadow cost 3 cycles)
+	                                                                  // independent chains each (two dependent v_max3 in one MFMA's shadow cost 3 cycles).
+	                                                                  // SCREEN folds only behind the step's branch, under no MFMA, and every reader
+	                                                                  // (the vote, flush_pm) takes the maximum of the two: the fold leaves that
+	                                                                  // maximum in [0] and +0 in [1] — the same bits, eight registers less
 #pragma unroll
 	for (int b = 0; b < 4; ++b) { pm[b][0][0] = 0.f; pm[b][0][1] = 0.f; pm[b][1][0] = 0.f; pm[b][1][1] = 0.f; }
 
@@ -499,7 +510,8 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		float ma = pm[bc >> 1][bc & 1][0], mb = pm[bc >> 1][bc & 1][1];
 #pragma unroll
 		for (int p = 0; p < 3; ++p) { ma = max3abs (ma, y[p][0], y[p][1]); mb = max3abs (mb, y[p][2], y[p][3]); }
-		pm[bc >> 1][bc & 1][0] = ma; pm[bc >> 1][bc & 1][1] = mb;
+		if constexpr (SCREEN) { pm[bc >> 1][bc & 1][0] = fmaxf (ma, mb); pm[bc >> 1][bc & 1][1] = 0.f; }   // (one value: see pm)
+		else { pm[bc >> 1][bc & 1][0] = ma; pm[bc >> 1][bc & 1][1] = mb; }
 	};
 	// ... of the launch's LAST step: lane (c, kg) holds rows (= frames of the step) 4 kg .. 4 kg + 3 of column 16 b + c; where that
 	// column is the last segment of its stream, only the rows in front of its tile's end count
@@ -514,7 +526,8 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 				ma = max3abs (ma, 4 * kg + 0 < rows ? y[p][0] : 0.f, 4 * kg + 1 < rows ? y[p][1] : 0.f);
 				mb = max3abs (mb, 4 * kg + 2 < rows ? y[p][2] : 0.f, 4 * kg + 3 < rows ? y[p][3] : 0.f);
 			}
-			pm[bc >> 1][bc & 1][0] = ma; pm[bc >> 1][bc & 1][1] = mb;
+			if constexpr (SCREEN) { pm[bc >> 1][bc & 1][0] = fmaxf (ma, mb); pm[bc >> 1][bc & 1][1] = 0.f; }
+			else { pm[bc >> 1][bc & 1][0] = ma; pm[bc >> 1][bc & 1][1] = mb; }
 		}
 	};
 	// the products of the call's last step (nothing left to run under them); every chunk folds its predecessor's accumulators
@@ -537,6 +550,11 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	int tile_left = spt;
 	uint32_t tile = p0;
 	int j = 0;
+	// Phase 0 counts a lane's whole step j where F0 + R (j + 1) <= p0_end.  No lane starts behind the launch's last segment,
+	// F0 <= (tiles of a stream - n_main) tile_frames, so in front of step p0_steps that holds for every lane of every wave:
+	// one scalar compare on j instead of a 64-bit compare per lane.
+	const int64_t p0_room = a.p0_end - (int64_t) (a.n_segs * a.seg_base + min (a.n_segs, a.seg_rem) - a.n_main) * a.tile_frames;
+	const int p0_steps = (int) min (max (p0_room, (int64_t) 0) / R, (int64_t) n_steps);
 
 	// max |x| per channel of buffer B: always computed one step early, under the products of the step before
 	float ml = 0.f, mr = 0.f;
@@ -556,7 +574,10 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		v2f (&x)[R] = xq[U];
 		SPROF_NOW (c0_);
 		// phase 0 = |x[n - 24]| for the frames of this call: everything but its last 24 frames
-		if (F0 + (int64_t) R * (j + 1) <= a.p0_end) pk0 = v2f{fmaxf (pk0.x, ml), fmaxf (pk0.y, mr)};
+		// (SCREEN: a scalar test on the step — in front of step p0_steps every lane's whole step counts, see p0_steps; behind it,
+		// the launch's last two steps, each lane tests its own frames as the dense form does on every step)
+		if (SCREEN && __builtin_expect (j < p0_steps, 1)) pk0 = v2f{umaxf (pk0.x, ml), umaxf (pk0.y, mr)};
+		else if (F0 + (int64_t) R * (j + 1) <= a.p0_end) pk0 = v2f{fmaxf (pk0.x, ml), fmaxf (pk0.y, mr)};
 		else {
 			const int64_t lim = a.p0_end - F0 - (int64_t) R * j;
 #pragma unroll
@@ -593,7 +614,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		// launch, their values are consumed at once, so a drain there costs nothing that could be hidden.
 		float eps[4][2], ref[4][2];
 		if constexpr (SCREEN) {
-			rml = fmaxf (rml, ml); rmr = fmaxf (rmr, mr);                // (step j's own samples too: a bound on more is still a bound)
+			rml = umaxf (rml, ml); rmr = umaxf (rmr, mr);                // (step j's own samples too: a bound on more is still a bound)
 			if constexpr (U == 0) {                                       // the stream reference, every fourth step
 				refl = ref_row (ref_own ? max (__float_as_uint (pk0.x), __float_as_uint (pkf.x)) : 0u);
 				refr = ref_row (ref_own ? max (__float_as_uint (pk0.y), __float_as_uint (pkf.y)) : 0u);
@@ -647,11 +668,16 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		// SCREEN: the vote on chunk K's first product y — the lanes that may reach the running peak, as a wave-uniform mask
 		uint64_t msk[8];
 		auto vote = [&]<int K> (const m16::f4 (&y)[3]) __attribute__ ((always_inline)) {
-			float ca = 0.f, cb = 0.f;
-#pragma unroll
-			for (int p = 0; p < 3; ++p) { ca = max3abs (ca, y[p][0], y[p][1]); cb = max3abs (cb, y[p][2], y[p][3]); }
+			// max (+0, |y| of the twelve values that are no NaN) as six v_max3: two chains of two, their merge with the eleventh value,
+			// and the twelfth with the +0.  fmaxf returns the operand that is no NaN and a NaN only where both are; the last one's +0
+			// is none, and a maximum of the same values does not depend on their order: c is, bit for bit, what two chains from +0
+			// give.  A lane all of whose values are NaN votes with c = +0 (the dense fold drops them too), one with an Inf with +Inf.
+			auto m3 = [] (float a, float b, float c) __attribute__ ((always_inline)) { return fmaxf (fmaxf (a, b), c); };
+			float ca = m3 (fabsf (y[0][0]), fabsf (y[0][1]), fabsf (y[0][2])), cb = m3 (fabsf (y[0][3]), fabsf (y[1][0]), fabsf (y[1][1]));
+			ca = m3 (ca, fabsf (y[1][2]), fabsf (y[1][3])); cb = m3 (cb, fabsf (y[2][0]), fabsf (y[2][1]));
+			const float c = m3 (m3 (ca, cb, fabsf (y[2][2])), fabsf (y[2][3]), 0.f);
 			const float pk = fmaxf (fmaxf (pm[K >> 1][K & 1][0], pm[K >> 1][K & 1][1]), ref[K >> 1][K & 1]);
-			const bool below = fmaxf (ca, cb) + eps[K >> 1][K & 1] < pk;           // (false for a NaN anywhere in it)
+			const bool below = c + eps[K >> 1][K & 1] < pk;                      // (false for a NaN in eps or in all of pk)
 			msk[K] = __ballot (!below);
 		};
 		auto chunk =[&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
