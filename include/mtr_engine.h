@@ -32,7 +32,7 @@ extern "C" {
  *    _loudlog_series, _loudlog_reset; MTR_METER_NEEDLE, mtr_needle_coef, mtr_engine_needle_configure, _needle_set_gain, _needle_read,
  *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks; MTR_METER_SCOPE, mtr_scope_window,
  *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset; mtr_engine_kmeter_set_period, _kmeter_period,
- *    _kmeter_series): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -320,6 +320,9 @@ int  mtr_engine_fragment_powers (mtr_engine* e, uint32_t first, uint32_t count, 
  * values written to ports 0-29 / 30-59; arrays are [count][30], any may be NULL */
 int  mtr_engine_spectrum (mtr_engine* e, uint32_t first, uint32_t count,
                           float* val, float* max, float* val_db, float* max_db);
+/* The bank's reading series — (val_f, max_f) of the 30 bands after every block of P frames: mtr_engine_spectr_set_period / _period /
+ * _series */
+#include "mtr_spectr.h"
 
 /* Integer paths (mono engines, n_channels == 1, as the reference's bitmeter / SigDistHist plugins).
  * replaces: float_stats' table and counters (src/bitmeter.c:63-105, layout src/uris.h:53-60):

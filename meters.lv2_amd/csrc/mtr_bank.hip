@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -35,16 +36,64 @@ struct mtr_bank_args {
 	float           omega;
 };
 
+// the reading series (mtr_spectr.h): what its instantiation of k_bank takes on top — a struct of its own, so that the dense kernel's
+// arguments stay what they were
+struct mtr_bank_series_args : mtr_bank_args {
+	float*          s_val;        /* [S][cap][30] (null with cap 0) */
+	float*          s_mx;
+	uint32_t        period;       /* P > 0 */
+	uint32_t        e0;           /* frames from the call's start to the end of the block open on entry: 1 .. P */
+	uint64_t        point0;       /* blocks completed before the call */
+	uint32_t        cap;
+	int32_t         peak_block;   /* MTR_SPECTR_PEAK_BLOCK: max = 0 behind every point */
+};
+
 #define BANK_ROWS  4      /* streams a wave of 64 lanes can touch: ceil (63 / 30) + 1 */
 #define BANK_CHUNK 128    /* frames staged per stream per iteration: two per lane */
 #define BANK_PITCH (BANK_CHUNK + 2)   /* doubles per row: rows four banks apart, so the <= 4 rows a wave reads never collide */
+
+// One frame of one band — the step both instantiations of k_bank share, on the kernel's W, z, val, mx and omega.  (A macro, not a function or
+// a lambda: either changes the order of operands in the dense kernel's code, and that kernel stays the one it was, instruction for instruction.)
+// six TDF-II sections (spectr.c:68-76).  Section 0 carries the normalisation g: numerator
+// g (1, 2, 1); sections 1-5 have (1, +-2, 1): b0 in = b2 in = in and b1 in = +-2 in are exact, so
+// sharing the product changes nothing but the operation count (25 instead of 31 fp64 ops).
+// `val > mx ? val : mx` (spectrumlv2.c:222) as one v_max_f32: a NaN val loses either way, mx is never NaN
+#define BANK_FRAME(in) \
+	{ \
+		double out = (in); \
+		{ \
+			const double gi = W[0][0] * out; \
+			const double y = gi + z[0]; \
+			z[0] = fma (-W[0][3], y, fma (2.0, gi, z[1])); \
+			z[1] = fma (-W[0][4], y, gi); \
+			out = y; \
+		} \
+		_Pragma ("unroll") \
+		for (int i = 1; i < 6; ++i) { \
+			const double y = out + z[2 * i]; \
+			z[2 * i]     = fma (-W[i][3], y, fma (W[i][1], out, z[2 * i + 1])); \
+			z[2 * i + 1] = fma (-W[i][4], y, out); \
+			out = y; \
+		} \
+		const float v = (float) out; \
+		const float q = v * v; \
+		val += omega * (q - val); \
+		mx = __builtin_fmaxf (mx, val); \
+	}
 
 // One wave per workgroup, NO barrier: the wave stages the chunks of the (up to four) streams it touches through its own
 // two LDS buffers — chunk c + 1 is written, and chunk c + 2's loads are in flight, while chunk c is computed — so nothing
 // in the loop ever waits for another wave (round 2's four-wave workgroups spent 17 % of the SIMD time outside the
 // arithmetic: two barriers per 256 frames, on a kernel whose waves do not run in lock step).
-__global__ __launch_bounds__ (64) void k_bank (const mtr_bank_args a)
+//
+// A = mtr_bank_series_args (SERIES, P > 0): the spectrum_runs are the blocks of exactly P frames counted from reset, not the calls.  Same mapping, same
+// staging, same per-frame step (BANK_FRAME: one piece of source); the loop over a chunk runs in pieces that end at the chunk's end or at the
+// block's, whichever comes first — where the blocks end follows from the arguments alone, so the split is scalar control flow — and at a
+// block's end the live lanes do spectrum_run's epilogue (spectrumlv2.c:230-238) and append their (val, max); the call's end stores the states
+// as they stand.
+template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 {
+	constexpr bool SERIES = std::is_same_v<A, mtr_bank_series_args>;
 	__shared__ double mix[2][BANK_ROWS][BANK_PITCH];    // mono mix + the +-1e-12 anti-denormal toggle, as double
 
 	const int lane = threadIdx.x;
@@ -120,6 +169,9 @@ __global__ __launch_bounds__ (64) void k_bank (const mtr_bank_args a)
 		__builtin_amdgcn_wave_barrier ();
 		__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "workgroup");
 	};
+	[[maybe_unused]] uint32_t to_end = 0;     // SERIES: frames to the end of the open block; blocks completed so far
+	[[maybe_unused]] uint64_t point = 0;
+	if constexpr (SERIES) { to_end = a.e0; point = a.point0; }
 	fetch (0);
 	stage (0, 0);
 	handover ();
@@ -136,44 +188,67 @@ __global__ __launch_bounds__ (64) void k_bank (const mtr_bank_args a)
 			fetch (base + 2 * BANK_CHUNK);
 		}
 		const double* const my = &mix[buf][row][0];
-		for (int n = 0; n < nf; ++n) {
-			// six TDF-II sections (spectr.c:68-76).  Section 0 carries the normalisation g: numerator
-			// g (1, 2, 1); sections 1-5 have (1, +-2, 1): b0 in = b2 in = in and b1 in = +-2 in are exact, so
-			// sharing the product changes nothing but the operation count (25 instead of 31 fp64 ops).
-			double out = my[n];
-			{
-				const double gi = W[0][0] * out;
-				const double y = gi + z[0];
-				z[0] = fma (-W[0][3], y, fma (2.0, gi, z[1]));
-				z[1] = fma (-W[0][4], y, gi);
-				out = y;
-			}
+		if constexpr (!SERIES) {
+			for (int n = 0; n < nf; ++n) BANK_FRAME (my[n])
+		} else {
+			// (the step behind a lambda: as the compiler stands, this instantiation then takes 120 VGPRs — four waves per SIMD like the dense
+			// kernel — against 130 and three waves with the macro spelled out at the four places below; profiles/r24_bank_series.md)
+			auto frame = [&] (const double in) { BANK_FRAME (in) };
+			for (int n = 0; n < nf; ) {
+				const int end = n + (int) min ((uint32_t) (nf - n), to_end);      // uniform: the chunk's end or the block's
+				to_end -= (uint32_t) (end - n);
+				// a frame to reach an even one, pairs (each one aligned 16-byte read of the row; unrolled twice: the dense loop's four frames per
+				// iteration, 28.75 VALU instructions per frame), a frame left over
+				if ((n & 1) && n < end) { frame (my[n]); ++n; }
+#pragma unroll 2
+				for (int j = n >> 1; j < end >> 1; ++j) {
+					frame (my[2 * j]);
+					frame (my[2 * j + 1]);
+				}
+				if (end > n && (end & 1)) frame (my[end - 1]);
+				n = end;
+				if (to_end == 0) {
+					// the block's last frame: spectrum_run's epilogue (spectrumlv2.c:230-238), the point, and — MTR_SPECTR_PEAK_BLOCK — the
+					// peak-reset handshake of the host that reads it (:191-198)
+					if (live) {
+						if (!isfinite (val)) val = 0;
+						if (!isfinite (mx))  mx = 0;
 #pragma unroll
-			for (int i = 1; i < 6; ++i) {
-				const double y = out + z[2 * i];
-				z[2 * i]     = fma (-W[i][3], y, fma (W[i][1], out, z[2 * i + 1]));
-				z[2 * i + 1] = fma (-W[i][4], y, out);
-				out = y;
+						for (int i = 0; i < 12; ++i) if (!isfinite (z[i])) z[i] = 0;
+						val += 1e-20f;
+						if (point < a.cap) {
+							const size_t o = ((size_t) s * a.cap + point) * MTR_NBANDS + band;
+							a.s_val[o] = val;
+							a.s_mx[o]  = mx;
+						}
+						if (a.peak_block) mx = 0;
+					}
+					++point;
+					to_end = a.period;
+				}
 			}
-			const float v = (float) out;
-			const float q = v * v;
-			val += omega * (q - val);
-			// `val > mx ? val : mx` (spectrumlv2.c:222) as one v_max_f32: a NaN val loses either way, mx is never NaN
-			mx = __builtin_fmaxf (mx, val);
 		}
 	}
 
 	if (live) {
-		// spectrum_run epilogue, state part (spectrumlv2.c:230-238)
-		if (!isfinite (val)) val = 0;
-		if (!isfinite (mx))  mx = 0;
+		if constexpr (!SERIES) {
+			// spectrum_run epilogue, state part (spectrumlv2.c:230-238)
+			if (!isfinite (val)) val = 0;
+			if (!isfinite (mx))  mx = 0;
 #pragma unroll
-		for (int i = 0; i < 12; ++i) {
-			if (!isfinite (z[i])) z[i] = 0;
-			a.z[((size_t) s * MTR_NBANDS + band) * 12 + i] = z[i];
+			for (int i = 0; i < 12; ++i) {
+				if (!isfinite (z[i])) z[i] = 0;
+				a.z[((size_t) s * MTR_NBANDS + band) * 12 + i] = z[i];
+			}
+			a.val[(size_t) s * MTR_NBANDS + band] = val + 1e-20f;
+			a.mx[(size_t) s * MTR_NBANDS + band]  = mx;
+		} else {
+			// the call ends where it ends: the states as they stand (the blocks' ends did the epilogue)
+#pragma unroll
+			for (int i = 0; i < 12; ++i) a.z[((size_t) s * MTR_NBANDS + band) * 12 + i] = z[i];
+			a.val[(size_t) s * MTR_NBANDS + band] = val;
+			a.mx[(size_t) s * MTR_NBANDS + band]  = mx;
 		}
-		a.val[(size_t) s * MTR_NBANDS + band] = val + 1e-20f;
-		a.mx[(size_t) s * MTR_NBANDS + band]  = mx;
 		// the parity of the next call goes to the OTHER buffer: a wave that starts late must not see this call's update
 		if (band == 0) a.ac_out[s] = my_par ^ (int) (a.n_frames & 1);
 	}
@@ -183,7 +258,15 @@ static int mtr_launch_bank (const mtr_bank_args& a, void* stream)
 {
 	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
 	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
-	hipLaunchKernelGGL (k_bank, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL (k_bank<mtr_bank_args>, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+static int mtr_launch_bank_series (const mtr_bank_series_args& a, void* stream)
+{
+	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
+	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
+	hipLaunchKernelGGL (k_bank<mtr_bank_series_args>, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -290,6 +373,10 @@ static int bank_reset (mtr_engine* e)
 	HIPCHK (hipMemsetAsync (e->bank.ac[0].p, 0, e->bank.ac[0].n * sizeof (int32_t), st));
 	HIPCHK (hipMemsetAsync (e->bank.ac[1].p, 0, e->bank.ac[1].n * sizeof (int32_t), st));
 	e->pos.bank_ac_cur = 0;
+	// the reading series: emptied, the open block gone, P, the capacity and the mode kept
+	if (e->bank.s_val.n) HIPCHK (hipMemsetAsync (e->bank.s_val.p, 0, e->bank.s_val.n * sizeof (float), st));
+	if (e->bank.s_max.n) HIPCHK (hipMemsetAsync (e->bank.s_max.p, 0, e->bank.s_max.n * sizeof (float), st));
+	e->pos.bk = {};
 	return MTR_OK;
 }
 
@@ -301,7 +388,18 @@ static int bank_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnd
 	ba.coef = e->bank.coef.p; ba.z = e->bank.z.p + vo * MTR_NBANDS * 12; ba.val = e->bank.val.p + vo * MTR_NBANDS; ba.mx = e->bank.max.p + vo * MTR_NBANDS;
 	ba.ac_in = e->bank.ac[e->pos.bank_ac_cur].p + vo; ba.ac_out = e->bank.ac[e->pos.bank_ac_cur ^ 1].p + vo;
 	ba.n_streams = c.cnt; ba.n_channels = e->cfg.n_channels; ba.omega = e->bank.omega;
-	if (mtr_launch_bank (ba, c.st)) return fail (MTR_ERR_HIP, "k_bank launch");
+	if (const uint32_t P = e->bank.ser.period) {
+		// the blocks are cut from where the CALL started (e->pos): every view of a host call sees the same cuts and appends at the same points
+		const uint32_t cap = e->bank.ser.cap;
+		mtr_bank_series_args sa;
+		static_cast<mtr_bank_args&> (sa) = ba;
+		sa.s_val = cap ? e->bank.s_val.p + vo * cap * MTR_NBANDS : nullptr;
+		sa.s_mx  = cap ? e->bank.s_max.p + vo * cap * MTR_NBANDS : nullptr;
+		sa.period = P; sa.e0 = (uint32_t) series_e0 (e->pos.bk, P, c.n_frames); sa.point0 = e->pos.bk.points;
+		sa.cap = cap; sa.peak_block = e->bank.peak_mode == MTR_SPECTR_PEAK_BLOCK;
+		if (mtr_launch_bank_series (sa, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series)");
+		nx.bk = series_advance (e->pos.bk, P, c.n_frames);
+	} else if (mtr_launch_bank (ba, c.st)) return fail (MTR_ERR_HIP, "k_bank launch");
 	nx.bank_ac_cur = e->pos.bank_ac_cur ^ 1;
 	return MTR_OK;
 }
@@ -315,6 +413,64 @@ static void bank_sections (const mtr_engine* e, std::vector<StateSection>& v)
 }
 
 constinit SideMeter bank_meter = { MTR_METER_SPECTR30, 0, nullptr, bank_create, bank_reset, bank_step, bank_sections, nullptr };
+
+// With a period the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): where the open block
+// stands.  All of an entry is its host-owned header — period, peak mode, the frames into the open block; the block's levels and filter states are
+// the first row's, stored as they stand.  An engine takes a blob of its own period and mode only.  The ring is not part of the blob.
+struct mtr_bank_open { uint32_t period, peak_mode, fill; };
+
+static void bank_open_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	if (e->bank.ser.period) v.push_back ({ e->bank.open.p, sizeof (mtr_bank_open) });
+}
+
+constexpr const char* BANK_CORRUPT = "mtr_engine_state_import: corrupt blob (period of the SPECTR30 series)";
+
+static void bank_hdr_write (const mtr_engine* e, void* out)
+{
+	const mtr_bank_open h = { e->bank.ser.period, (uint32_t) e->bank.peak_mode, (uint32_t) e->pos.bk.fill };
+	memcpy (out, &h, sizeof (h));
+}
+
+static int bank_hdr_check (const mtr_engine* e, const void* in, bool fresh)
+{
+	mtr_bank_open h;
+	memcpy (&h, in, sizeof (h));
+	if (!h.period || !series_blob_ok (h.period, h.fill, 1, 0x7ffffffeu) || h.peak_mode > MTR_SPECTR_PEAK_BLOCK) return fail (MTR_ERR_STATE, BANK_CORRUPT);
+	if (h.period != e->bank.ser.period || (int) h.peak_mode != e->bank.peak_mode || (!fresh && h.fill != e->pos.bk.fill))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period or peak mode of the SPECTR30 series)");
+	return MTR_OK;
+}
+
+static void bank_hdr_take (mtr_engine* e, const void* in)
+{
+	mtr_bank_open h;
+	memcpy (&h, in, sizeof (h));
+	e->pos.bk.fill = h.fill;
+}
+
+static int bank_open_reset (mtr_engine*) { return MTR_OK; }                                  // (the meter's first row resets all of it)
+static int bank_open_step (mtr_engine*, const Call&, Cursors&, const StreamEnds&) { return MTR_OK; }   // (... and queues all of it)
+
+static constinit BlobHeader bank_hdr = { 0, sizeof (mtr_bank_open), BANK_CORRUPT, bank_hdr_write, bank_hdr_check, bank_hdr_take };
+constinit SideMeter bank_series_meter = { MTR_METER_SPECTR30, 0, nullptr, nullptr, bank_open_reset, bank_open_step, bank_open_sections, &bank_hdr };
+
+// spectrumlv2.c:240-247 for n levels: the raw val_f / max_f and the dB values of ports 0-29 / 30-59 (any output may be null).  The stored val
+// carries the +1e-20f of :237; above the -100 dB floor (val > 5e-11) that addition does not change the float, so the port value is unaffected.
+static void bank_ports (const float* v, const float* m, size_t n, float* val, float* mx, float* val_db, float* max_db)
+{
+	for (size_t i = 0; i < n; ++i) {
+		const float vs = sqrtf (2. * v[i]);
+		const float ms = sqrtf (2. * m[i]);
+		if (val) val[i] = v[i];
+		if (mx) mx[i] = m[i];
+		if (val_db) val_db[i] = vs > .00001f ? 20.0 * log10f (vs) : -100.0;
+		if (max_db) max_db[i] = ms > .00001f ? 20.0 * log10f (ms) : -100.0;
+	}
+}
+
+static int no_bank (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_SPECTR30); }
+static const char* const NO_BANK = "no SPECTR30 in this engine";
 
 extern "C" {
 
@@ -356,15 +512,61 @@ int mtr_engine_spectrum (mtr_engine* e, uint32_t first, uint32_t count, float* v
 		HIPCHK (hipMemcpy (hv.data () + n, e->bank.max.p + (size_t) first * MTR_NBANDS, n * 4, hipMemcpyDeviceToHost));
 		v = hv.data (); m = hv.data () + n;
 	}
-	for (size_t i = 0; i < n; ++i) {
-		// spectrumlv2.c:240-247.  The stored val carries the +1e-20f of :237; above the -100 dB floor
-		// (val > 5e-11) that addition does not change the float, so the port value is unaffected.
-		const float vs = sqrtf (2. * v[i]);
-		const float ms = sqrtf (2. * m[i]);
-		if (val) val[i] = v[i];
-		if (mx) mx[i] = m[i];
-		if (val_db) val_db[i] = vs > .00001f ? 20.0 * log10f (vs) : -100.0;
-		if (max_db) max_db[i] = ms > .00001f ? 20.0 * log10f (ms) : -100.0;
+	bank_ports (v, m, n, val, mx, val_db, max_db);
+	return MTR_OK;
+}
+
+int mtr_engine_spectr_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points, int peak_mode)
+{
+	if (no_bank (e)) return fail (MTR_ERR_ARG, NO_BANK);
+	if (peak_mode != MTR_SPECTR_PEAK_HOLD && peak_mode != MTR_SPECTR_PEAK_BLOCK)
+		return fail (MTR_ERR_ARG, "mtr_engine_spectr_set_period: peak_mode is MTR_SPECTR_PEAK_HOLD or MTR_SPECTR_PEAK_BLOCK");
+	if (period_frames >= 0x7fffffffu) return fail (MTR_ERR_ARG, "mtr_engine_spectr_set_period: a period is at most 2^31 - 2 frames");
+	int rc = series_configure_check (e, "mtr_engine_spectr_set_period", period_frames, 1, "1");
+	if (rc || (rc = wait_stream (e))) return rc;
+	mtr_engine::Bank& b = e->bank;
+	b.ser = {};                                                        // (off until everything below has succeeded)
+	b.peak_mode = MTR_SPECTR_PEAK_HOLD;
+	e->pos.bk = {};
+	b.s_val.drop (); b.s_max.drop (); b.open.drop ();
+	if (!period_frames) return MTR_OK;
+	const size_t n = (size_t) e->cfg.n_streams * capacity_points * MTR_NBANDS;
+	if ((rc = series_ring (b.s_val, n, "hipMalloc SPECTR30 series")) || (rc = series_ring (b.s_max, n, "hipMalloc SPECTR30 series"))) { b.s_val.drop (); b.s_max.drop (); return rc; }
+	if (b.open.reserve ((size_t) e->cfg.n_streams * sizeof (mtr_bank_open))) { b.s_val.drop (); b.s_max.drop (); return fail (MTR_ERR_NOMEM, "hipMalloc SPECTR30 open blocks"); }
+	HIPCHK (hipMemset (b.open.p, 0, b.open.n));
+	b.ser = { period_frames, capacity_points };
+	b.peak_mode = peak_mode;
+	return MTR_OK;
+}
+
+int mtr_engine_spectr_period (const mtr_engine* e, uint32_t* period_frames, uint32_t* capacity_points, int* peak_mode)
+{
+	if (no_bank (e)) return fail (MTR_ERR_ARG, NO_BANK);
+	if (period_frames) *period_frames = e->bank.ser.period;
+	if (capacity_points) *capacity_points = e->bank.ser.cap;
+	if (peak_mode) *peak_mode = e->bank.peak_mode;
+	return MTR_OK;
+}
+
+int mtr_engine_spectr_series (mtr_engine* e, uint32_t first, uint32_t count, float* val, float* mx, float* val_db, float* max_db,
+                              uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_bank (e), NO_BANK, first, count);
+	if (rc) return rc;
+	if (!e->bank.ser.period) return fail (MTR_ERR_ARG, "mtr_engine_spectr_series: the series is off (mtr_engine_spectr_set_period)");
+	const uint32_t cap = e->bank.ser.cap;
+	const size_t take = series_counts (e->pos.bk.points, cap, capacity, n_points, dropped);
+	if ((!val && !mx && !val_db && !max_db) || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	// the kept points of the streams, rows of `take` points; then the ports' arithmetic row by row into the caller's rows of `capacity`
+	const size_t w = take * MTR_NBANDS;
+	std::vector<float> hv (2 * (size_t) count * w);
+	float* const hm = hv.data () + (size_t) count * w;
+	if ((rc = series_fetch (hv.data (), e->bank.s_val.p, MTR_NBANDS, first, cap, (uint32_t) take, take, count))) return rc;
+	if ((rc = series_fetch (hm, e->bank.s_max.p, MTR_NBANDS, first, cap, (uint32_t) take, take, count))) return rc;
+	for (uint32_t k = 0; k < count; ++k) {
+		const size_t o = (size_t) k * capacity * MTR_NBANDS;
+		bank_ports (hv.data () + k * w, hm + k * w, w, val ? val + o : nullptr, mx ? mx + o : nullptr, val_db ? val_db + o : nullptr, max_db ? max_db + o : nullptr);
 	}
 	return MTR_OK;
 }

@@ -100,6 +100,7 @@ struct Cursors {
 	uint32_t frcnt = 0;           // frames remaining in the open fragment
 	int      hist_cur = 0;        // which of fir_hist [2] / mc_hist [2] holds the 47 frames before the next call
 	int      bank_ac_cur = 0;     // ... and which of bank.ac [2] the dither parity
+	SeriesPos bk;                 // SPECTR30 with a period: where its reading series stands (mtr_series.h)
 	uint64_t dr_scnt = 0;         // samples in the open DR-14 window
 	uint32_t km_fpp = 0;          // Kmeterdsp's frames per period and the fall-back factor that goes with it
 	float    km_fall = 0.f;
@@ -234,6 +235,11 @@ struct mtr_engine {
 		DevBuf<float>    val, max;
 		DevBuf<int32_t>  ac[2];                 // ping-pong (pos.bank_ac_cur): k_bank reads one, writes the other
 		float            omega = 0.f;
+		// the reading series (mtr_engine_spectr_set_period, P > 0): k_bank_series
+		SeriesCfg        ser;                   // frames per spectrum_run of the series (0: the call), points per stream it holds
+		int              peak_mode = 0;         // MTR_SPECTR_PEAK_*
+		DevBuf<float>    s_val, s_max;          // [S][cap][30]
+		DevBuf<unsigned char> open;             // [S] mtr_bank_open: the blob's copy of (period, peak mode, frames into the open block)
 	} bank;
 	struct IntStat {                            // BITSTATS, SIGDIST (mtr_intstat.hip)
 		DevBuf<mtr_bitstats_state> bim;
@@ -393,9 +399,11 @@ struct SideMeter {
 };
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
-extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter;
+extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
+                 bank_series_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
-                                                    &kmeter_series_meter };   // (KMETER's second row: the blob section of its open block, behind every older one)
+                                                    &kmeter_series_meter,     // (KMETER's second row: the blob section of its open block, behind every older one)
+                                                    &bank_series_meter };     // (SPECTR30's second row, likewise)
 
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view

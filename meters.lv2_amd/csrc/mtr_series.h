@@ -1,8 +1,8 @@
-// mtr_series.h — the reading series of STCORR, NEEDLE, SURROUND and KMETER: blocks of exactly P frames, cut wherever the calls cut the audio, one
+// mtr_series.h — the reading series of STCORR, NEEDLE, SURROUND, KMETER and SPECTR30: blocks of exactly P frames, cut wherever the calls cut the audio, one
 // reading per block appended to a ring of `cap` points per stream (P = 0: the call is the block and nothing is appended).  Here is what
-// the three share of it on the host that needs neither the engine nor the HIP runtime; series_configure_check, series_ring and
+// they share of it on the host that needs neither the engine nor the HIP runtime; series_configure_check, series_ring and
 // series_fetch, which need both, are in mtr_engine_impl.h.  What a block IS — a process () of Stcorrdsp, of the needle meters' detectors, of
-// the surround meter's — and the smallest P it takes stay the meters' own.  Not installed.
+// the surround meter's, a spectrum_run of the bank — and the smallest P it takes stay the meters' own.  Not installed.
 #ifndef MTR_SERIES_H
 #define MTR_SERIES_H
 

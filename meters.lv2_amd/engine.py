@@ -21,6 +21,7 @@ NEEDLE_VU, NEEDLE_IEC1, NEEDLE_IEC2, NEEDLE_MS = 1, 2, 4, 8
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
 PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3        # MTR_PCM_*: little-endian int16 / packed 3-byte / int32 samples
+SPECTR_PEAK_HOLD, SPECTR_PEAK_BLOCK = 0, 1   # MTR_SPECTR_PEAK_*: max as held since reset / reset_peak, or zeroed behind every point
 LOUDLOG_SAMPLE, LOUDLOG_MAX = 0, 1         # MTR_LOUDLOG_*: a point is the period's last (M, S) / the maxima over the period
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -160,6 +161,10 @@ def _load():
         L.mtr_engine_kmeter_set_period.argtypes = [vp, u32, u32]
         L.mtr_engine_kmeter_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_kmeter_series.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+    if hasattr(L, "mtr_engine_spectr_series"):                 # (an addition inside ABI version 2: the 30-band bank's reading series)
+        L.mtr_engine_spectr_set_period.argtypes = [vp, u32, u32, C.c_int]
+        L.mtr_engine_spectr_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
+        L.mtr_engine_spectr_series.argtypes = [vp, u32, u32, vp, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
     if hasattr(L, "mtr_engine_stcorr_read"):                   # (an addition inside ABI version 2: stereo phase correlation)
         L.mtr_stcorr_coef.argtypes = [f32, vp]
         L.mtr_engine_stcorr_set_period.argtypes = [vp, u32, u32]
@@ -740,6 +745,31 @@ class Engine:
         a = [np.zeros((count, NBANDS), np.float32) for _ in range(4)]
         _check(lib.mtr_engine_spectrum(self._h, first, count, *[x.ctypes.data for x in a]), "spectrum")
         return dict(val=a[0], max=a[1], val_db=a[2], max_db=a[3])
+
+    def spectr_set_period(self, period_frames, capacity_points=0, peak_mode=SPECTR_PEAK_HOLD):
+        """0: every call is one spectrum_run; P > 0: blocks of exactly P frames wherever the calls cut the audio, (val, max) of the 30
+        bands after each appended to a series of `capacity_points` per stream; SPECTR_PEAK_BLOCK zeroes max behind every point.  Only
+        before the first process call since create / reset."""
+        if not hasattr(lib, "mtr_engine_spectr_series"):
+            raise EngineError(f"{lib_path} has no SPECTR30 reading series: rebuild it")
+        _check(lib.mtr_engine_spectr_set_period(self._h, int(period_frames), int(capacity_points), int(peak_mode)), "spectr_set_period")
+
+    def spectr_period(self):
+        """(period_frames, capacity_points, peak_mode) as spectr_set_period set them."""
+        if not hasattr(lib, "mtr_engine_spectr_series"):
+            raise EngineError(f"{lib_path} has no SPECTR30 reading series: rebuild it")
+        p, c, m = C.c_uint32(), C.c_uint32(), C.c_int()
+        _check(lib.mtr_engine_spectr_period(self._h, C.byref(p), C.byref(c), C.byref(m)), "spectr_period")
+        return p.value, c.value, m.value
+
+    def spectr_series(self, first=0, count=None):
+        """(dict(val, max, val_db, max_db) of [count, kept, 30] arrays, n_points, dropped): the readings after every completed block
+        since reset that the series holds."""
+        if not hasattr(lib, "mtr_engine_spectr_series"):
+            raise EngineError(f"{lib_path} has no SPECTR30 reading series: rebuild it")
+        a, n, d = self._series("spectr_series", first, count, [(NBANDS,)] * 4,
+                               lambda count, ptrs, *tail: lib.mtr_engine_spectr_series(self._h, first, count, *ptrs, *tail))
+        return dict(val=a[0], max=a[1], val_db=a[2], max_db=a[3]), n, d
 
     def bitstats(self, first=0, count=None):
         count = self.n_streams - first if count is None else count
