@@ -32,7 +32,8 @@ extern "C" {
  *    _loudlog_series, _loudlog_reset; MTR_METER_NEEDLE, mtr_needle_coef, mtr_engine_needle_configure, _needle_set_gain, _needle_read,
  *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks; MTR_METER_SCOPE, mtr_scope_window,
  *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset; mtr_engine_kmeter_set_period, _kmeter_period,
- *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series; mtr_engine_process_device_ends, _process_host_ends,
+ *    _spectr_points): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -199,6 +200,9 @@ int  mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint6
 /* Ragged batches for the meters that report a reading over time (STCORR, NEEDLE) beside those: mtr_engine_process_device_ragged /
  * _host_ragged, mtr_engine_series_points and mtr_series_cut, declared in mtr_ragged.h */
 #include "mtr_ragged.h"
+/* Track lengths for the 30-band bank (SPECTR30) beside all of those: mtr_engine_process_device_ends / _host_ends and
+ * mtr_engine_spectr_points, declared in mtr_ends.h */
+#include "mtr_ends.h"
 /* Frames metered per stream since create / reset, and whether it is closed (either pointer may be NULL): [count] each.
  * (What the process calls queued so far: no synchronisation.  mtr_engine_state_import restarts the count of the streams it writes
  * at 0: a blob carries no frame count.) */

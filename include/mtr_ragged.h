@@ -33,7 +33,8 @@ extern "C" {
  * point at index *n_points or beyond comes into their reach once the open streams have completed that block.
  * Once a stream is closed, every later call on the streams that hold it (mtr_engine_process_device / _host, an LV2 block) runs the
  * length-masking kernels, end 0 for the closed ones.  The per-meter resets (mtr_engine_stcorr_reset, _needle_reset, ...) reopen nothing.
- * Engines that hold SPECTR30, TPBALLIST, SURROUND or SCOPE: MTR_ERR_UNSUPPORTED, nothing queued, engine unchanged.  (SURROUND is left
+ * Engines that hold SPECTR30, TPBALLIST, SURROUND or SCOPE: MTR_ERR_UNSUPPORTED, nothing queued, engine unchanged (SPECTR30 has a pair of
+ * its own that takes these meters beside it: mtr_engine_process_device_ends / _host_ends, mtr_ends.h).  (SURROUND is left
  * out on purpose: its K-meters' weights depend on the block length, which would become per-stream, and its pieces kernel has no
  * registers to spare for a second set of them.)
  * replaces: a host that stops calling run() at the track's end. */

@@ -32,7 +32,8 @@ extern "C" {
  * started), integer PCM, frame layouts, mono and stereo engines.  mtr_engine_process_*_lengths / _tracks / _ragged refuse a SPECTR30
  * engine as before.  That costs little: the bank is causal and the streams run in lock step, so of a zero-padded track every point that
  * ends at or before the track's own last frame is already exact — the first frames / P points of its row; the host knows that number.
- * mtr_engine_series_points does not know this series (the points are lock-step: *n_points below).
+ * mtr_engine_series_points does not know this series (the points are lock-step: *n_points below).  Tracks that end where their audio
+ * ends, exactly and at the cost of their own frames: mtr_engine_process_device_ends / _host_ends and mtr_engine_spectr_points, mtr_ends.h.
  * mtr_engine_spectr_set_speed works as before (the omega of the next call); mtr_engine_spectr_reset_peak zeroes max wherever the open
  * block stands; mtr_engine_reset empties the series, the counts and the open block and keeps P, the capacity and the mode.
  * MTR_ERR_ARG: an unknown peak_mode, P > 2^31 - 2, no SPECTR30 in the engine.  Only on an engine that has processed nothing since create /

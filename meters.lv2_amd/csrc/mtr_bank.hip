@@ -48,6 +48,15 @@ struct mtr_bank_series_args : mtr_bank_args {
 	int32_t         peak_block;   /* MTR_SPECTR_PEAK_BLOCK: max = 0 behind every point */
 };
 
+// track lengths (mtr_ends.h): what the two ENDS instantiations of k_bank take on top of the dense and the series form — structs of their own again,
+// so that those two kernels' arguments, and with them their code, stay what they were
+struct mtr_bank_ends_args : mtr_bank_args {
+	const uint32_t* ends;         /* [S] the call frame at which each stream ends: 0 (closed, untouched) .. n_frames */
+};
+struct mtr_bank_series_ends_args : mtr_bank_series_args {
+	const uint32_t* ends;
+};
+
 #define BANK_ROWS  4      /* streams a wave of 64 lanes can touch: ceil (63 / 30) + 1 */
 #define BANK_CHUNK 128    /* frames staged per stream per iteration: two per lane */
 #define BANK_PITCH (BANK_CHUNK + 2)   /* doubles per row: rows four banks apart, so the <= 4 rows a wave reads never collide */
@@ -91,9 +100,17 @@ struct mtr_bank_series_args : mtr_bank_args {
 // block's, whichever comes first — where the blocks end follows from the arguments alone, so the split is scalar control flow — and at a
 // block's end the live lanes do spectrum_run's epilogue (spectrumlv2.c:230-238) and append their (val, max); the call's end stores the states
 // as they stand.
+//
+// A = mtr_bank_ends_args / mtr_bank_series_ends_args (ENDS): every stream ends at its own frame of the call, ends[s] <= n_frames.  The (up to) four
+// ends a wave meets are uniform values, read with scalar loads.  fetch takes no frame at or behind its row's end; the wave's chunk loop runs to the
+// LAST end among its rows and stops there; a chunk runs in pieces that end at the chunk's end, a block's end (SERIES) or any row's end, so the set
+// of live lanes is constant inside a piece and the per-frame code carries no per-lane compare.  At a row's end its lanes do the epilogue — in the
+// series form, r frames into a block with 0 < r < P, with the truncated point — and drop out: nothing behind changes their registers, which the
+// kernel's end stores as they stand.  A row with end 0 is neither computed nor stored; its dither parity is COPIED to the other buffer.
 template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 {
-	constexpr bool SERIES = std::is_same_v<A, mtr_bank_series_args>;
+	constexpr bool SERIES = std::is_base_of_v<mtr_bank_series_args, A>;
+	constexpr bool ENDS = requires { a.ends; };
 	__shared__ double mix[2][BANK_ROWS][BANK_PITCH];    // mono mix + the +-1e-12 anti-denormal toggle, as double
 
 	const int lane = threadIdx.x;
@@ -131,6 +148,20 @@ template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 #pragma unroll
 	for (int g = 0; g < BANK_ROWS; ++g) par0[g] = (s0 + g < a.n_streams) ? a.ac_in[s0 + g] : 0;
 	const int my_par = live ? a.ac_in[s] : 0;
+	// ENDS: the rows' ends (uniform; 0 for a row past the batch), the last of them, and the lane's own
+	[[maybe_unused]] uint32_t rend[BANK_ROWS] = { 0, 0, 0, 0 };
+	[[maybe_unused]] uint32_t my_end = 0;
+	uint64_t stop = a.n_frames;                  // where the wave's chunk loop ends
+	if constexpr (ENDS) {
+		uint32_t last = 0;
+#pragma unroll
+		for (int g = 0; g < BANK_ROWS; ++g) {
+			rend[g] = (s0 + g < a.n_streams) ? min (a.ends[s0 + g], (uint32_t) a.n_frames) : 0;
+			last = max (last, rend[g]);
+		}
+		stop = last;
+		my_end = live ? min (a.ends[s], (uint32_t) a.n_frames) : 0;
+	}
 
 	// lane t stages frames 2 t, 2 t + 1 of every row
 	float2 raw[BANK_ROWS][2];
@@ -142,7 +173,10 @@ template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 			for (int k = 0; k < 2; ++k) {
 				const uint64_t f = base + 2 * lane + k;
 				float2 v = make_float2 (0.f, 0.f);
-				if (sg < a.n_streams && f < a.n_frames) {
+				bool in;
+				if constexpr (ENDS) in = f < rend[g];
+				else                in = sg < a.n_streams && f < a.n_frames;
+				if (in) {
 					if (a.n_channels == 2) v = reinterpret_cast<const float2*> (a.audio)[(size_t) sg * a.stride + f];
 					else                   v.x = a.audio[(size_t) sg * a.stride + f];
 				}
@@ -177,18 +211,65 @@ template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 	handover ();
 	fetch (BANK_CHUNK);
 	int buf = 0;
-	for (uint64_t base = 0; base < a.n_frames; base += BANK_CHUNK, buf ^= 1) {
-		const int nf = (int) min ((uint64_t) BANK_CHUNK, a.n_frames - base);
+	for (uint64_t base = 0; base < stop; base += BANK_CHUNK, buf ^= 1) {
+		const int nf = (int) min ((uint64_t) BANK_CHUNK, stop - base);
 		// the next chunk into the other buffer (its previous readers are behind us in this wave's own instruction stream),
 		// the one after it into the registers: both land under this chunk's arithmetic
-		if (base + BANK_CHUNK < a.n_frames) {
+		if (base + BANK_CHUNK < stop) {
 			handover ();                                  // (the other buffer's readers of the chunk before are done)
 			stage (buf ^ 1, base + BANK_CHUNK);
 			handover ();
 			fetch (base + 2 * BANK_CHUNK);
 		}
 		const double* const my = &mix[buf][row][0];
-		if constexpr (!SERIES) {
+		if constexpr (ENDS) {
+			auto frame = [&] (const double in) { BANK_FRAME (in) };
+			// spectrum_run's epilogue (spectrumlv2.c:230-238) and, SERIES, the point with the host's peak-reset handshake behind it (:191-198)
+			auto epilogue = [&] () {
+				if (!isfinite (val)) val = 0;
+				if (!isfinite (mx))  mx = 0;
+#pragma unroll
+				for (int i = 0; i < 12; ++i) if (!isfinite (z[i])) z[i] = 0;
+				val += 1e-20f;
+				if constexpr (SERIES) {
+					if (point < a.cap) {
+						const size_t o = ((size_t) s * a.cap + point) * MTR_NBANDS + band;
+						a.s_val[o] = val;
+						a.s_mx[o]  = mx;
+					}
+					if (a.peak_block) mx = 0;
+				}
+			};
+			for (int n = 0; n < nf; ) {
+				// the piece: to the chunk's end, the block's or the next end of a row, whichever comes first — all uniform
+				const uint32_t cur = (uint32_t) base + (uint32_t) n;
+				uint32_t len = (uint32_t) (nf - n);
+#pragma unroll
+				for (int g = 0; g < BANK_ROWS; ++g) if (rend[g] > cur) len = min (len, rend[g] - cur);
+				if constexpr (SERIES) { len = min (len, to_end); to_end -= len; }
+				const int end = n + (int) len;
+				const bool on = cur < my_end;                 // the lane's row has not ended: true or false for the whole piece
+				if (on) {
+					if ((n & 1) && n < end) { frame (my[n]); ++n; }
+#pragma unroll 2
+					for (int j = n >> 1; j < end >> 1; ++j) {
+						frame (my[2 * j]);
+						frame (my[2 * j + 1]);
+					}
+					if (end > n && (end & 1)) frame (my[end - 1]);
+				}
+				n = end;
+				const bool ended = on && my_end == cur + len;  // the row's last frame
+				if constexpr (SERIES) {
+					if (to_end == 0) {
+						// the block's last frame (a row that ends with it ends there: r = 0, no second epilogue)
+						if (on) epilogue ();
+						++point;
+						to_end = a.period;
+					} else if (ended && my_end < (uint32_t) a.n_frames) epilogue ();   // closed r frames into a block: the truncated point (an open stream's call just ends)
+				} else if (ended) epilogue ();                    // the stream's spectrum_run of the call ends here
+			}
+		} else if constexpr (!SERIES) {
 			for (int n = 0; n < nf; ++n) BANK_FRAME (my[n])
 		} else {
 			// (the step behind a lambda: as the compiler stands, this instantiation then takes 120 VGPRs — four waves per SIMD like the dense
@@ -230,7 +311,17 @@ template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 		}
 	}
 
-	if (live) {
+	if constexpr (ENDS) {
+		// every row did its epilogue where it ended: the states as they stand; a row with end 0 is not written at all
+		if (live && my_end) {
+#pragma unroll
+			for (int i = 0; i < 12; ++i) a.z[((size_t) s * MTR_NBANDS + band) * 12 + i] = z[i];
+			a.val[(size_t) s * MTR_NBANDS + band] = val;
+			a.mx[(size_t) s * MTR_NBANDS + band]  = mx;
+		}
+		// the parity advances by the stream's own frames; the buffers swap with every call, so end 0 copies it
+		if (live && band == 0) a.ac_out[s] = my_par ^ (int) (my_end & 1);
+	} else if (live) {
 		if constexpr (!SERIES) {
 			// spectrum_run epilogue, state part (spectrumlv2.c:230-238)
 			if (!isfinite (val)) val = 0;
@@ -267,6 +358,15 @@ static int mtr_launch_bank_series (const mtr_bank_series_args& a, void* stream)
 	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
 	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
 	hipLaunchKernelGGL (k_bank<mtr_bank_series_args>, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// the ENDS instantiations: same grid, same lane map
+template <typename A> static int mtr_launch_bank_ends (const A& a, void* stream)
+{
+	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
+	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
+	hipLaunchKernelGGL (k_bank<A>, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -361,6 +461,7 @@ static int bank_create (mtr_engine* e)
 		return fail (MTR_ERR_NOMEM, "hipMalloc bank state");
 	if (hipMemcpy (e->bank.coef.p, c.data (), c.size () * sizeof (double), hipMemcpyHostToDevice) != hipSuccess)
 		return fail (MTR_ERR_HIP, "hipMemcpy bank_coef");
+	e->bank.points.assign (S, 0);
 	return MTR_OK;
 }
 
@@ -377,10 +478,11 @@ static int bank_reset (mtr_engine* e)
 	if (e->bank.s_val.n) HIPCHK (hipMemsetAsync (e->bank.s_val.p, 0, e->bank.s_val.n * sizeof (float), st));
 	if (e->bank.s_max.n) HIPCHK (hipMemsetAsync (e->bank.s_max.p, 0, e->bank.s_max.n * sizeof (float), st));
 	e->pos.bk = {};
+	e->bank.points.assign (e->cfg.n_streams, 0);
 	return MTR_OK;
 }
 
-static int bank_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
+static int bank_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	mtr_bank_args ba;
@@ -397,8 +499,19 @@ static int bank_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnd
 		sa.s_mx  = cap ? e->bank.s_max.p + vo * cap * MTR_NBANDS : nullptr;
 		sa.period = P; sa.e0 = (uint32_t) series_e0 (e->pos.bk, P, c.n_frames); sa.point0 = e->pos.bk.points;
 		sa.cap = cap; sa.peak_block = e->bank.peak_mode == MTR_SPECTR_PEAK_BLOCK;
-		if (mtr_launch_bank_series (sa, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series)");
+		if (se.ends) {
+			// (the ends of the view's own streams: upload_lengths fills them from the view's first stream on, as the kernel indexes them)
+			mtr_bank_series_ends_args ea;
+			static_cast<mtr_bank_series_args&> (ea) = sa;
+			ea.ends = se.ends;
+			if (mtr_launch_bank_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series, ends)");
+		} else if (mtr_launch_bank_series (sa, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series)");
 		nx.bk = series_advance (e->pos.bk, P, c.n_frames);
+	} else if (se.ends) {
+		mtr_bank_ends_args ea;
+		static_cast<mtr_bank_args&> (ea) = ba;
+		ea.ends = se.ends;
+		if (mtr_launch_bank_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (ends)");
 	} else if (mtr_launch_bank (ba, c.st)) return fail (MTR_ERR_HIP, "k_bank launch");
 	nx.bank_ac_cur = e->pos.bank_ac_cur ^ 1;
 	return MTR_OK;
@@ -536,6 +649,16 @@ int mtr_engine_spectr_set_period (mtr_engine* e, uint32_t period_frames, uint32_
 	HIPCHK (hipMemset (b.open.p, 0, b.open.n));
 	b.ser = { period_frames, capacity_points };
 	b.peak_mode = peak_mode;
+	return MTR_OK;
+}
+
+// mtr_ends.h: counted on the host by CallRun::run
+int mtr_engine_spectr_points (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* points)
+{
+	if (no_bank (e)) return fail (MTR_ERR_ARG, NO_BANK);
+	if (!points) return fail (MTR_ERR_ARG, "mtr_engine_spectr_points: null argument");
+	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
+	for (uint32_t i = 0; i < count; ++i) points[i] = e->bank.points[first + i];
 	return MTR_OK;
 }
 

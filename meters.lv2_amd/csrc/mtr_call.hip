@@ -113,6 +113,9 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 {
 	for (const SideMeter* m : SIDE_METERS)
 		if ((e->cfg.meters & m->bits) && m->max_frames && n_frames >= m->max_frames) return fail (MTR_ERR_ARG, m->max_text);
+	// (once a stream is closed every call runs the bank's ENDS kernels, whose ends are 32 bits: mtr_ends.h)
+	if ((e->cfg.meters & MTR_METER_SPECTR30) && e->n_closed && n_frames > 0xFFFFFFFEull)
+		return fail (MTR_ERR_ARG, "SPECTR30 with a closed stream: n_frames per call must be < 2^32 - 1");
 	if ((e->cfg.meters & MTR_METER_TPBALLIST) && n_frames >= 0x7ffff000ull) return fail (MTR_ERR_ARG, "TPBALLIST: n_frames per call must be < 2^31 - 4096");
 	if ((e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)) && n_frames >= 0xFFFFFFFFull) return fail (MTR_ERR_ARG, "n_frames per call must be < 2^32 - 1");
 	return MTR_OK;
@@ -495,9 +498,9 @@ struct CallRun {
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
 			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
-			const struct { uint32_t bit; uint64_t P, fill; std::vector<uint64_t>& points; } ser[3] = {
+			const struct { uint32_t bit; uint64_t P, fill; std::vector<uint64_t>& points; } ser[4] = {
 				{ MTR_METER_STCORR, e->sc.ser.period, e->pos.sc.fill, e->sc.points }, { MTR_METER_NEEDLE, e->nd.ser.period, e->pos.nd.fill, e->nd.points },
-				{ MTR_METER_KMETER, e->km.ser.period, e->pos.km.fill, e->km.points } };
+				{ MTR_METER_KMETER, e->km.ser.period, e->pos.km.fill, e->km.points }, { MTR_METER_SPECTR30, e->bank.ser.period, e->pos.bk.fill, e->bank.points } };
 			for (const auto& q : ser) {
 				uint64_t whole = 0;
 				uint32_t partial = 0;
@@ -716,6 +719,37 @@ int mtr_engine_process_host_ragged (mtr_engine* e, const float* h_audio, uint64_
 {
 	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_ragged: null argument");
 	const int crc = ragged_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
+}
+
+// Track lengths for the 30-band bank (mtr_ends.h): the meters of _ragged and SPECTR30, whose ends on the device are 32 bits
+static int ends_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
+{
+	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST
+	                        | MTR_METER_STCORR | MTR_METER_NEEDLE | MTR_METER_SPECTR30;
+	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok) || e->cfg.n_channels > 2)
+		return fail (MTR_ERR_UNSUPPORTED, "track lengths for the bank: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 engines of one or two channels only");
+	if ((e->cfg.meters & MTR_METER_SPECTR30) && n_frames > 0xFFFFFFFEull)
+		return fail (MTR_ERR_ARG, "track lengths for the bank: n_frames per call must be < 2^32 - 1");
+	for (uint32_t i = 0; i < n; ++i)
+		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "track lengths for the bank: frames[s] > n_frames");
+	return MTR_OK;
+}
+
+int mtr_engine_process_device_ends (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
+                                    const uint64_t* frames, void* hip_stream)
+{
+	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_ends: null argument");
+	const int crc = ends_check (e, n_frames, frames, e->cfg.n_streams);
+	if (crc) return crc;
+	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_host_ends (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_ends: null argument");
+	const int crc = ends_check (e, n_frames, frames, e->cfg.n_streams);
 	if (crc) return crc;
 	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
 }

@@ -63,7 +63,7 @@ struct Stream {
 // 48 kHz — never overwrites arrays that kernels of an earlier call may still be reading, and never blocks the host.
 constexpr int PLAN_SLOTS = 4;
 
-// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks / _ragged, or any call once a stream is closed) ride the same
+// The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks / _ragged / _ends, or any call once a stream is closed) ride the same
 // way: [ends S | frag_lim S | from_tile S | km_fall S (KMETER engines)] in the next slot of their own ring, uploaded on the call's stream,
 // busy until the call's last readers (the last kernel of the call on its stream — the side meters' LEN kernels, k_history_len — and the
 // gate on whichever stream it ran) have passed.
@@ -240,6 +240,7 @@ struct mtr_engine {
 		int              peak_mode = 0;         // MTR_SPECTR_PEAK_*
 		DevBuf<float>    s_val, s_max;          // [S][cap][30]
 		DevBuf<unsigned char> open;             // [S] mtr_bank_open: the blob's copy of (period, peak mode, frames into the open block)
+		std::vector<uint64_t> points;           // [S] points of each stream's own series since reset (mtr_engine_process_*_ends: mtr_ends.h)
 	} bank;
 	struct IntStat {                            // BITSTATS, SIGDIST (mtr_intstat.hip)
 		DevBuf<mtr_bitstats_state> bim;

@@ -194,6 +194,7 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		if (e->cfg.meters & MTR_METER_STCORR) e->sc.points[first + k] = e->pos.sc.points;
 		if (e->cfg.meters & MTR_METER_NEEDLE) e->nd.points[first + k] = e->pos.nd.points;
 		if (e->cfg.meters & MTR_METER_KMETER) e->km.points[first + k] = e->pos.km.points;
+		if (e->cfg.meters & MTR_METER_SPECTR30) e->bank.points[first + k] = e->pos.bk.points;
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;

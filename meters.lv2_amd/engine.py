@@ -129,6 +129,10 @@ def _load():
         L.mtr_engine_process_host_ragged.argtypes = [vp, vp, u64, u64, vp]
         L.mtr_engine_series_points.argtypes = [vp, u32, u32, u32, vp]
         L.mtr_series_cut.argtypes = [u64, u64, u64, u64, C.POINTER(u64), C.POINTER(u32)]
+    if hasattr(L, "mtr_engine_process_device_ends"):           # (an addition inside ABI version 2: track lengths for the 30-band bank)
+        L.mtr_engine_process_device_ends.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_ends.argtypes = [vp, vp, u64, u64, vp]
+        L.mtr_engine_spectr_points.argtypes = [vp, u32, u32, vp]
     if hasattr(L, "mtr_engine_pcm_stats"):                     # (an addition inside ABI version 2: integer PCM in)
         L.mtr_engine_process_host_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp]
         L.mtr_engine_process_device_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp, vp]
@@ -601,6 +605,41 @@ class Engine:
         count = self.n_streams - first if count is None else count
         out = np.zeros(count, np.uint64)
         _check(lib.mtr_engine_series_points(self._h, int(meter), first, count, out.ctypes.data), "series_points")
+        return out
+
+    @staticmethod
+    def _need_ends():
+        if not hasattr(lib, "mtr_engine_process_device_ends"):
+            raise EngineError(f"{lib_path} has no track lengths for the 30-band bank: rebuild it")
+
+    def _ends(self, frames):
+        self._need_ends()
+        f = np.ascontiguousarray(frames, np.uint64)
+        if f.shape != (self.n_streams,):
+            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
+        return f
+
+    def process_device_ends(self, ptr, n_frames, frames, stride=None, stream=0):
+        """process_device_ragged() for engines that also hold SPECTR30: stream s is metered up to frames[s] <= n_frames — the bank's
+        spectrum_run ends there with its epilogue and, with a period, a truncated last point; frames[s] < n_frames closes it."""
+        f = self._ends(frames)
+        _check(lib.mtr_engine_process_device_ends(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
+               "process_device_ends")
+
+    def process_ends(self, x, frames):
+        """process() with track lengths for the bank: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        x = self._frames_f32(x)
+        f = self._ends(frames)
+        _check(lib.mtr_engine_process_host_ends(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
+               "process_host_ends")
+
+    def spectr_points(self, first=0, count=None):
+        """[count] uint64: the points each stream's own SPECTR30 series has got since reset, dropped ones included — of a stream that
+        process_*_ends closed, its whole blocks and the truncated one."""
+        self._need_ends()
+        count = self.n_streams - first if count is None else count
+        out = np.zeros(count, np.uint64)
+        _check(lib.mtr_engine_spectr_points(self._h, first, count, out.ctypes.data), "spectr_points")
         return out
 
     def process_pcm(self, x, format=None, frames=None):
