@@ -33,7 +33,8 @@ extern "C" {
  *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks; MTR_METER_SCOPE, mtr_scope_window,
  *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset; mtr_engine_kmeter_set_period, _kmeter_period,
  *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series; mtr_engine_process_device_ends, _process_host_ends,
- *    _spectr_points): + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
+ *    _spectr_points; mtr_engine_scope_set_series, _scope_series_config, _scope_series, mtr_scope_series_cut):
+ *    + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
  *    mtr_abi_version () >= the version it was written against before it binds anything newer. */
@@ -384,7 +385,8 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 
 /* The stereo / frequency scope for a batch (MTR_METER_SCOPE) — a windowed FFT per hop and stream, the stereoscope's smoothed level and
  * balance and the phase wheel's phase difference, level and peak per bin: mtr_scope_window and mtr_engine_scope_configure / _config /
- * _read / _analyses / _reset */
+ * _read / _analyses / _reset; with a reading series (mtr_scope_series.h, included from there): mtr_engine_scope_set_series /
+ * _series_config / _series and mtr_scope_series_cut */
 #include "mtr_scope.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */

@@ -56,4 +56,7 @@ int  mtr_engine_scope_reset (mtr_engine* e);
 }
 #endif
 
+/* The reading series — a point per stream after every K-th analysis, what the two GUIs paint over time — has a header of its own */
+#include "mtr_scope_series.h"
+
 #endif

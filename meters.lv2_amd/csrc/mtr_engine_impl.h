@@ -110,6 +110,8 @@ struct Cursors {
 	float    su_fall = 0.f;
 	uint32_t sp_fill = 0;         // SCOPE: frames since the last analysis ...
 	uint64_t sp_analyses = 0;     // ... and analyses completed since reset
+	uint32_t sp_since = 0;        // SCOPE with a series: analyses since the last point ...
+	uint64_t sp_points = 0;       // ... and points completed since reset (what the rings do not hold of them is dropped)
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 };
@@ -304,6 +306,12 @@ struct mtr_engine {
 		DevBuf<float>              win, tw;     // [W] the window, [W][2] the twiddles
 		uint32_t                   W = 0, H = 0;   // frames per window and per hop (resolved: never 0): a control (it survives a reset)
 		float                      thresh = 0.f;   // the phase wheel's threshold on the powers
+		// the reading series (mtr_engine_scope_set_series, K > 0): the SERIES instantiation of k_scope
+		struct Series {
+			uint32_t               every = 0, cap = 0, fields = 0;   // K (0: off), points per stream a ring holds, MTR_SCOPE_F_*: a control
+			DevBuf<float>          ring[7];     // per selected field, in the order of the bits: [S][cap][B]; peak: [S][cap]
+			DevBuf<unsigned char>  open;        // [S] mtr_scope_open: the blob's copy of (K, analyses since the last point)
+		} ser;
 	} sp;
 	struct LoudLog {                            // the loudness log of an EBU engine (mtr_loudlog.hip; the gate appends: mtr_gate.hip)
 		DevBuf<float>              M, S;        // [S][cap]
@@ -401,10 +409,11 @@ struct SideMeter {
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
 extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
-                 bank_series_meter;
+                 bank_series_meter, scope_series_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
                                                     &kmeter_series_meter,     // (KMETER's second row: the blob section of its open block, behind every older one)
-                                                    &bank_series_meter };     // (SPECTR30's second row, likewise)
+                                                    &bank_series_meter,       // (SPECTR30's second row, likewise)
+                                                    &scope_series_meter };    // (SCOPE's second row, likewise)
 
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view

@@ -22,11 +22,20 @@
 //   * an analysis reads its W frames from the call's buffer, the frames in front of the call from the stream's tail (the last W frames,
 //     kept in device memory and rewritten at the end of every call through LDS).  H > W: the frames between two windows are never read.
 // Each analysis is a function of its W frames and the carried state alone: the result does not depend on where the calls cut the audio.
+//
+// The reading series (mtr_scope_series.h; what the GUIs' queue_draw after every analysis shows over time: stereoscope.c:738,
+// phasewheel.c:1339): k_scope<LOGW, true>, launched only by an engine with K > 0.  Every K-th analysis, counted from reset, is a POINT: it
+// does what otherwise only the call's last analysis does — the second pass over the split with atan2f — and writes the selected fields to
+// point p of the stream's rings, [S][cap][B] per field (a thread's bins are t + r NT: a wave's stores are contiguous), if p is below the
+// capacity: level and lr from the registers they live in, peak by one thread behind its update, the rest from the pass.  A point is what
+// mtr_engine_scope_read answers after that analysis, bins 0 and B - 1 included.  k_scope<LOGW, false> is the kernel as it was: another
+// argument struct, no instruction of the series.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -57,8 +66,23 @@ typedef struct mtr_scope_args {
 	float*          peak;         /* [S] */
 } mtr_scope_args;
 
+// the reading series: what its instantiation of k_scope takes on top — a struct of its own, so that the kernel without a series keeps its
+// arguments
+typedef struct mtr_scope_series_args : mtr_scope_args {
+	float*          ring[7];      /* per field in the order of MTR_SCOPE_F_*: [S][cap][B], peak [S][cap], from the view's first stream; null: not selected */
+	uint64_t        point0;       /* the index of the call's first point: min (points since reset, cap) */
+	uint32_t        every, since; /* K; analyses since the last point when the call starts, < K */
+	uint32_t        cap, fields;
+} mtr_scope_series_args;
+
+/* SCOPE's second section of the blob: all of an entry is its host-owned header */
+typedef struct mtr_scope_open { uint32_t every, since; } mtr_scope_open;
+
 namespace {
 
+constexpr uint32_t K_MAX = 1u << 20;
+constexpr int F_PEAK_AT = 4;      // MTR_SCOPE_F_PEAK's bit: the one ring with one float per point
+constexpr uint32_t F_PASS = MTR_SCOPE_F_PHASE | MTR_SCOPE_F_PLEVEL | MTR_SCOPE_F_POWER_L | MTR_SCOPE_F_POWER_R;   // the fields the second pass makes
 constexpr uint32_t W_MIN = 256, W_MAX = 16384, W_DEFAULT = 1024;
 constexpr uint32_t H_MIN = 64, H_MAX = 1u << 20;
 
@@ -90,7 +114,8 @@ template <int LOGW> __device__ __forceinline__ Bin bin_of (const float2* z, uint
 	return b;
 }
 
-template <int LOGW> __global__ __launch_bounds__ (threads_of (LOGW)) void k_scope (const mtr_scope_args a)
+template <int LOGW, bool SERIES> __global__ __launch_bounds__ (threads_of (LOGW))
+void k_scope (const std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_args> a)
 {
 	constexpr int W = 1 << LOGW, B = W / 2, NT = threads_of (LOGW), BPT = B / NT;
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem[];
@@ -109,10 +134,23 @@ template <int LOGW> __global__ __launch_bounds__ (threads_of (LOGW)) void k_scop
 		for (int r = 0; r < BPT; ++r) { level[r] = a.level[so + t + r * NT]; lr[r] = a.lr[so + t + r * NT]; }
 		peak = a.peak[s];
 	}
+	[[maybe_unused]] uint32_t since = 0;                               // SERIES: analyses since the last point; the next point's index
+	[[maybe_unused]] uint64_t pidx = 0;
+	if constexpr (SERIES) { since = a.since; pidx = a.point0; }
 
 	for (uint32_t j = 0; j < a.n_an; ++j) {
 		const int64_t f0 = (int64_t) (a.first + (uint64_t) j * a.hop) - W;   // the analysis' first frame
 		const bool last = j + 1 == a.n_an;
+		[[maybe_unused]] bool keep = false;                            // SERIES: the analysis is a point the rings have room for, row `at` of them
+		[[maybe_unused]] size_t at = 0;
+		if constexpr (SERIES) {
+			if (++since == a.every) {
+				since = 0;
+				keep = pidx < a.cap;
+				at = (size_t) s * a.cap + (size_t) pidx;
+				++pidx;
+			}
+		}
 		// ---- the windowed frames, L + iR ----
 #pragma unroll 2
 		for (int r = 0; r < W / NT; ++r) {
@@ -177,6 +215,48 @@ template <int LOGW> __global__ __launch_bounds__ (threads_of (LOGW)) void k_scop
 			const float pv = pl > pr ? pl : pr;
 			if (!below && pv > pk) pk = pv;
 		}
+		if constexpr (SERIES) {
+			// a point's level and lr: the registers, bins 0 and B - 1 with them (they hold what the state arrays do)
+			if (keep && (a.fields & (MTR_SCOPE_F_LEVEL | MTR_SCOPE_F_LR))) {
+#pragma unroll
+				for (int r = 0; r < BPT; ++r) {
+					const size_t o = at * B + t + r * NT;
+					if (a.fields & MTR_SCOPE_F_LEVEL) a.ring[0][o] = level[r];
+					if (a.fields & MTR_SCOPE_F_LR) a.ring[1][o] = lr[r];
+				}
+			}
+			// ... and the pass below on every point that keeps one of its fields, not on the call's last analysis alone
+			if (last || (keep && (a.fields & F_PASS))) {
+#pragma unroll 1
+				for (int r = 0; r < BPT; ++r) {
+					const uint32_t i = t + r * NT;
+					const size_t o = at * B + i;
+					if (i < 1 || i > B - 2) {                              // (never written: a point gets what mtr_engine_scope_read would)
+						if (keep) {
+							if (a.fields & MTR_SCOPE_F_PHASE) a.ring[2][o] = a.phase[so + i];
+							if (a.fields & MTR_SCOPE_F_PLEVEL) a.ring[3][o] = a.plevel[so + i];
+							if (a.fields & MTR_SCOPE_F_POWER_L) a.ring[5][o] = a.power_l[so + i];
+							if (a.fields & MTR_SCOPE_F_POWER_R) a.ring[6][o] = a.power_r[so + i];
+						}
+						continue;
+					}
+					const Bin b = bin_of<LOGW> (z, i);
+					const bool below = b.pl < a.thresh || b.pr < a.thresh;
+					const float ph = below ? 0.f : __fsub_rn (atan2f (b.rim, b.rre), atan2f (b.lim, b.lre));
+					const float pv = below ? -100.f : b.pl > b.pr ? b.pl : b.pr;
+					if (last) {
+						a.phase[so + i] = ph; a.plevel[so + i] = pv;
+						a.power_l[so + i] = b.pl; a.power_r[so + i] = b.pr;
+					}
+					if (keep) {
+						if (a.fields & MTR_SCOPE_F_PHASE) a.ring[2][o] = ph;
+						if (a.fields & MTR_SCOPE_F_PLEVEL) a.ring[3][o] = pv;
+						if (a.fields & MTR_SCOPE_F_POWER_L) a.ring[5][o] = b.pl;
+						if (a.fields & MTR_SCOPE_F_POWER_R) a.ring[6][o] = b.pr;
+					}
+				}
+			}
+		} else
 		// what only the call's last analysis leaves: the phase wheel's bins and the powers (the split once more: atan2f stays out of the loop above)
 		if (last) {
 #pragma unroll 1
@@ -200,6 +280,9 @@ template <int LOGW> __global__ __launch_bounds__ (threads_of (LOGW)) void k_scop
 		peak = (float) __dadd_rn ((double) peak, __dadd_rn (__dmul_rn (.04, (double) __fsub_rn (pk, peak)), 1e-15));
 		if (isnan (peak)) peak = 0.f;
 		if (peak > 1000.f) peak = 1000.f;
+		if constexpr (SERIES) {
+			if (keep && (a.fields & MTR_SCOPE_F_PEAK) && t == 0) a.ring[F_PEAK_AT][at] = peak;
+		}
 	}
 
 	if (a.n_an) {
@@ -218,18 +301,20 @@ template <int LOGW> __global__ __launch_bounds__ (threads_of (LOGW)) void k_scop
 	for (int i = t; i < W; i += NT) *reinterpret_cast<float2*> (tail + 2 * i) = z[pad (i)];
 }
 
-template <int LOGW> int launch (const mtr_scope_args& a, hipStream_t st)
+// A: mtr_scope_args — the kernel without a series — or mtr_scope_series_args
+template <int LOGW, typename A> int launch (const A& a, hipStream_t st)
 {
+	constexpr bool SERIES = std::is_same_v<A, mtr_scope_series_args>;
 	constexpr uint32_t bytes = lds_slots (1u << LOGW) * sizeof (float2);
 	if (bytes > 48 * 1024) {
-		static const hipError_t once = hipFuncSetAttribute ((const void*) k_scope<LOGW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+		static const hipError_t once = hipFuncSetAttribute ((const void*) k_scope<LOGW, SERIES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
 		(void) once;
 	}
-	hipLaunchKernelGGL (k_scope<LOGW>, dim3 (a.n_streams), dim3 (threads_of (LOGW)), bytes, st, a);
+	hipLaunchKernelGGL ((k_scope<LOGW, SERIES>), dim3 (a.n_streams), dim3 (threads_of (LOGW)), bytes, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-int mtr_launch_scope (uint32_t W, const mtr_scope_args& a, hipStream_t st)
+template <typename A> int mtr_launch_scope (uint32_t W, const A& a, hipStream_t st)
 {
 	switch (W) {
 	case 256:   return launch<8> (a, st);
@@ -241,6 +326,35 @@ int mtr_launch_scope (uint32_t W, const mtr_scope_args& a, hipStream_t st)
 	case 16384: return launch<14> (a, st);
 	}
 	return -1;
+}
+
+// how a call cuts the series (mtr_scope_series_cut): the arguments have been checked
+void series_cut (uint32_t fill, uint32_t hop, uint32_t since, uint32_t every, uint64_t n_frames, uint64_t* analyses, uint64_t* points)
+{
+	*analyses = n_frames / hop + (fill + n_frames % hop) / hop;       // (fill + n_frames) / hop without the sum's overflow
+	*points = every ? (since + *analyses) / every : 0;
+}
+
+// K, the capacity and the fields into the engine, with rings for its window (K = 0: none); the series empty.  On failure it is off
+int series_set (mtr_engine* e, uint32_t K, uint32_t cap, uint32_t fields)
+{
+	mtr_engine::Scope::Series& sr = e->sp.ser;
+	const auto off = [&sr] { for (auto& r : sr.ring) r.drop (); sr.open.drop (); sr.every = sr.cap = sr.fields = 0; };
+	off ();
+	e->pos.sp_since = 0; e->pos.sp_points = 0;
+	if (!K) return MTR_OK;
+	const size_t S = e->cfg.n_streams, B = e->sp.W / 2;
+	size_t rows, n;
+	if (__builtin_mul_overflow (S, (size_t) cap, &rows) || __builtin_mul_overflow (rows, B, &n) || n > SIZE_MAX / sizeof (float))
+		return fail (MTR_ERR_NOMEM, "mtr_engine_scope_set_series: the rings' size overflows size_t");
+	for (int k = 0; k < 7; ++k) {
+		if (!(fields >> k & 1)) continue;
+		if (const int rc = series_ring (sr.ring[k], k == F_PEAK_AT ? rows : n, "hipMalloc SCOPE series")) { off (); return rc; }
+	}
+	if (sr.open.reserve (S * sizeof (mtr_scope_open))) { off (); return fail (MTR_ERR_NOMEM, "hipMalloc SCOPE series (open groups)"); }
+	if (hipMemset (sr.open.p, 0, sr.open.n) != hipSuccess) { off (); return fail (MTR_ERR_HIP, "hipMemset SCOPE series", hipGetLastError ()); }
+	sr.every = K; sr.cap = cap; sr.fields = fields;
+	return MTR_OK;
 }
 
 // 0: a window the engine takes; MTR_ERR_UNSUPPORTED: one only the reference takes (reinitialize_fft, stereoscope.c:123-131: 64 .. 8192 bins,
@@ -277,6 +391,8 @@ int configure (mtr_engine* e, uint32_t W, uint32_t H, float thresh)
 	HIPCHK (hipMemcpy (sp.tw.p, tw.data (), tw.size () * sizeof (float), hipMemcpyHostToDevice));
 	HIPCHK (hipMemset (sp.hdr.p, 0, S * sizeof (mtr_scope_hdr)));
 	sp.W = W; sp.H = H; sp.thresh = thresh;
+	// the series keeps its settings; its rings are those of the new window
+	if (const int rc = series_set (e, sp.ser.every, sp.ser.cap, sp.ser.fields)) return rc;
 	return mtr_engine_scope_reset (e);
 }
 
@@ -293,14 +409,28 @@ static int scope_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 	const mtr_engine::Scope& sp = e->sp;
 	const size_t vo = c.off, B = sp.W / 2;
 	const uint64_t tot = (uint64_t) e->pos.sp_fill + c.n_frames;
+	const uint32_t K = sp.ser.every;
+	uint64_t n_an, n_pt;
+	series_cut (e->pos.sp_fill, sp.H, e->pos.sp_since, K, c.n_frames, &n_an, &n_pt);
 	mtr_scope_args sa;
 	sa.audio = c.audio; sa.stride = c.stride; sa.n_frames = c.n_frames;
-	sa.first = sp.H - e->pos.sp_fill; sa.n_streams = c.cnt; sa.n_an = (uint32_t) (tot / sp.H); sa.hop = sp.H; sa.thresh = sp.thresh;
+	sa.first = sp.H - e->pos.sp_fill; sa.n_streams = c.cnt; sa.n_an = (uint32_t) n_an; sa.hop = sp.H; sa.thresh = sp.thresh;
 	sa.win = sp.win.p; sa.tw = reinterpret_cast<const float2*> (sp.tw.p);
 	sa.tail = sp.tail.p + vo * sp.W * 2;
 	sa.level = sp.level.p + vo * B; sa.lr = sp.lr.p + vo * B; sa.phase = sp.phase.p + vo * B; sa.plevel = sp.plevel.p + vo * B;
 	sa.power_l = sp.power_l.p + vo * B; sa.power_r = sp.power_r.p + vo * B; sa.peak = sp.peak.p + vo;
-	if (mtr_launch_scope (sp.W, sa, c.st)) return fail (MTR_ERR_HIP, "k_scope launch", hipGetLastError ());
+	if (K) {
+		// the groups of K are counted from where the CALL started (e->pos): every view of a host call sees the same cuts and appends at the same points
+		const uint32_t cap = sp.ser.cap;
+		mtr_scope_series_args ss;
+		static_cast<mtr_scope_args&> (ss) = sa;
+		for (int k = 0; k < 7; ++k) ss.ring[k] = sp.ser.ring[k].p ? sp.ser.ring[k].p + vo * cap * (k == F_PEAK_AT ? 1 : B) : nullptr;
+		ss.point0 = std::min<uint64_t> (e->pos.sp_points, cap);
+		ss.every = K; ss.since = e->pos.sp_since; ss.cap = cap; ss.fields = cap ? sp.ser.fields : 0;
+		if (mtr_launch_scope (sp.W, ss, c.st)) return fail (MTR_ERR_HIP, "k_scope launch (series)", hipGetLastError ());
+		nx.sp_since = (uint32_t) ((e->pos.sp_since + n_an) % K);
+		nx.sp_points = e->pos.sp_points + n_pt;
+	} else if (mtr_launch_scope (sp.W, sa, c.st)) return fail (MTR_ERR_HIP, "k_scope launch", hipGetLastError ());
 	nx.sp_fill = (uint32_t) (tot % sp.H);
 	nx.sp_analyses = e->pos.sp_analyses + sa.n_an;
 	return MTR_OK;
@@ -347,6 +477,45 @@ static void scope_hdr_take (mtr_engine* e, const void* in)
 static constinit BlobHeader scope_hdr = { 0, sizeof (mtr_scope_hdr), SCOPE_CORRUPT, scope_hdr_write, scope_hdr_check, scope_hdr_take };
 constinit SideMeter scope_meter = { MTR_METER_SCOPE, 0x7fffffffull, "SCOPE: n_frames per call must be < 2^31 - 1",
                                           scope_create, mtr_engine_scope_reset, scope_step, scope_sections, &scope_hdr };
+
+// With a series the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): where the open group
+// of K analyses stands.  All of an entry is its host-owned header — K and the analyses since the last point.  An engine takes a blob of its
+// own K only; fields and capacity need not match, and the points are not part of the blob.
+static void scope_open_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	if (e->sp.ser.every) v.push_back ({ e->sp.ser.open.p, sizeof (mtr_scope_open) });
+}
+
+constexpr const char* SCOPE_SERIES_CORRUPT = "mtr_engine_state_import: corrupt blob (the SCOPE series' analyses per point)";
+
+static void scope_open_write (const mtr_engine* e, void* out)
+{
+	const mtr_scope_open h = { e->sp.ser.every, e->pos.sp_since };
+	memcpy (out, &h, sizeof (h));
+}
+
+static int scope_open_check (const mtr_engine* e, const void* in, bool fresh)
+{
+	mtr_scope_open h;
+	memcpy (&h, in, sizeof (h));
+	if (!h.every || h.every > K_MAX || h.since >= h.every) return fail (MTR_ERR_STATE, SCOPE_SERIES_CORRUPT);
+	if (h.every != e->sp.ser.every || (!fresh && h.since != e->pos.sp_since))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (analyses per point of the SCOPE series, or since the last one)");
+	return MTR_OK;
+}
+
+static void scope_open_take (mtr_engine* e, const void* in)
+{
+	mtr_scope_open h;
+	memcpy (&h, in, sizeof (h));
+	e->pos.sp_since = h.since;
+}
+
+static int scope_open_reset (mtr_engine*) { return MTR_OK; }                                  // (the meter's first row resets all of it)
+static int scope_open_step (mtr_engine*, const Call&, Cursors&, const StreamEnds&) { return MTR_OK; }   // (... and queues all of it)
+
+static constinit BlobHeader scope_open_hdr = { 0, sizeof (mtr_scope_open), SCOPE_SERIES_CORRUPT, scope_open_write, scope_open_check, scope_open_take };
+constinit SideMeter scope_series_meter = { MTR_METER_SCOPE, 0, nullptr, nullptr, scope_open_reset, scope_open_step, scope_open_sections, &scope_open_hdr };
 
 extern "C" {
 
@@ -399,6 +568,9 @@ int mtr_engine_scope_reset (mtr_engine* e)
 	HIPCHK (hipMemset (sp.tail.p, 0, (size_t) e->cfg.n_streams * sp.W * 2 * sizeof (float)));
 	e->pos.sp_fill = 0;
 	e->pos.sp_analyses = 0;
+	// the reading series: emptied (what a ring holds past its count is never handed out), the open group gone, the settings kept
+	e->pos.sp_since = 0;
+	e->pos.sp_points = 0;
 	return MTR_OK;
 }
 
@@ -422,6 +594,61 @@ int mtr_engine_scope_analyses (mtr_engine* e, uint64_t* n)
 {
 	if (no_scope (e) || !n) return fail (MTR_ERR_ARG, "mtr_engine_scope_analyses: no SCOPE in this engine, or a null argument");
 	*n = e->pos.sp_analyses;
+	return MTR_OK;
+}
+
+// ---- the reading series (mtr_scope_series.h) ----
+
+int mtr_scope_series_cut (uint32_t fill, uint32_t hop, uint32_t since, uint32_t every, uint64_t n_frames, uint64_t* analyses, uint64_t* points)
+{
+	if (!analyses || !points) return fail (MTR_ERR_ARG, "mtr_scope_series_cut: null argument");
+	if (hop < H_MIN || hop > H_MAX) return fail (MTR_ERR_ARG, "mtr_scope_series_cut: hop is 64 .. 2^20");
+	if (fill >= hop) return fail (MTR_ERR_ARG, "mtr_scope_series_cut: fill must be < hop");
+	if (every && since >= every) return fail (MTR_ERR_ARG, "mtr_scope_series_cut: since must be < every");
+	series_cut (fill, hop, since, every, n_frames, analyses, points);
+	return MTR_OK;
+}
+
+int mtr_engine_scope_set_series (mtr_engine* e, uint32_t every_analyses, uint32_t capacity_points, uint32_t fields)
+{
+	if (no_scope (e)) return fail (MTR_ERR_ARG, "no SCOPE in this engine");
+	if (every_analyses > K_MAX) return fail (MTR_ERR_ARG, "mtr_engine_scope_set_series: every_analyses is 0 or 1 .. 2^20");
+	if (every_analyses && (!fields || (fields & ~MTR_SCOPE_F_ALL)))
+		return fail (MTR_ERR_ARG, "mtr_engine_scope_set_series: fields is a non-empty subset of MTR_SCOPE_F_ALL");
+	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_scope_set_series: only on an engine that has processed nothing since create / reset");
+	const int rc = wait_stream (e);
+	if (rc) return rc;
+	return series_set (e, every_analyses, every_analyses ? capacity_points : 0, every_analyses ? fields : 0);
+}
+
+int mtr_engine_scope_series_config (const mtr_engine* e, uint32_t* every_analyses, uint32_t* capacity_points, uint32_t* fields)
+{
+	if (no_scope (e)) return fail (MTR_ERR_ARG, "no SCOPE in this engine");
+	if (every_analyses) *every_analyses = e->sp.ser.every;
+	if (capacity_points) *capacity_points = e->sp.ser.cap;
+	if (fields) *fields = e->sp.ser.fields;
+	return MTR_OK;
+}
+
+int mtr_engine_scope_series (mtr_engine* e, uint32_t first, uint32_t count, float* level, float* lr, float* phase, float* plevel, float* peak,
+                             float* power_l, float* power_r, uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_scope (e), "no SCOPE in this engine", first, count);
+	if (rc) return rc;
+	const mtr_engine::Scope::Series& sr = e->sp.ser;
+	if (!sr.every) return fail (MTR_ERR_ARG, "mtr_engine_scope_series: the series is off (mtr_engine_scope_set_series)");
+	float* const out[7] = { level, lr, phase, plevel, peak, power_l, power_r };
+	bool any = false;
+	for (int k = 0; k < 7; ++k) {
+		if (out[k] && !(sr.fields >> k & 1)) return fail (MTR_ERR_ARG, "mtr_engine_scope_series: a pointer for a field the series does not keep");
+		any |= out[k] != nullptr;
+	}
+	const size_t take = series_counts (e->pos.sp_points, sr.cap, capacity, n_points, dropped);
+	if (!any || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	const size_t B = e->sp.W / 2;
+	for (int k = 0; k < 7; ++k)
+		if (out[k] && (rc = series_fetch (out[k], sr.ring[k].p, k == F_PEAK_AT ? 1 : B, first, sr.cap, capacity, take, count))) return rc;
 	return MTR_OK;
 }
 

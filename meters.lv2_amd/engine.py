@@ -21,6 +21,9 @@ NEEDLE_VU, NEEDLE_IEC1, NEEDLE_IEC2, NEEDLE_MS = 1, 2, 4, 8
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
 PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3        # MTR_PCM_*: little-endian int16 / packed 3-byte / int32 samples
+# MTR_SCOPE_F_*: the fields of a point of the scope's reading series (include/mtr_scope_series.h), in the order of mtr_engine_scope_series' outputs
+SCOPE_F_LEVEL, SCOPE_F_LR, SCOPE_F_PHASE, SCOPE_F_PLEVEL, SCOPE_F_PEAK, SCOPE_F_POWER_L, SCOPE_F_POWER_R, SCOPE_F_ALL = 1, 2, 4, 8, 16, 32, 64, 127
+SCOPE_FIELDS = ("level", "lr", "phase", "plevel", "peak", "power_l", "power_r")
 SPECTR_PEAK_HOLD, SPECTR_PEAK_BLOCK = 0, 1   # MTR_SPECTR_PEAK_*: max as held since reset / reset_peak, or zeroed behind every point
 LOUDLOG_SAMPLE, LOUDLOG_MAX = 0, 1         # MTR_LOUDLOG_*: a point is the period's last (M, S) / the maxima over the period
 
@@ -197,6 +200,11 @@ def _load():
         L.mtr_engine_scope_read.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
         L.mtr_engine_scope_analyses.argtypes = [vp, C.POINTER(u64)]
         L.mtr_engine_scope_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_scope_series"):                  # (an addition inside ABI version 2: the scope's reading series)
+        L.mtr_engine_scope_set_series.argtypes = [vp, u32, u32, u32]
+        L.mtr_engine_scope_series_config.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_scope_series.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_scope_series_cut.argtypes = [u32, u32, u32, u32, u64, C.POINTER(u64), C.POINTER(u64)]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -292,6 +300,17 @@ def scope_window(window_frames):
     out = np.zeros(int(window_frames), np.float32)
     _check(lib.mtr_scope_window(int(window_frames), out.ctypes.data), "mtr_scope_window")
     return out
+
+
+def scope_series_cut(fill, hop, since, every, n_frames):
+    """(analyses, points): a call of n_frames to a SCOPE stream that stands `fill` frames behind its last analysis and `since` analyses
+    behind its last series point completes `analyses` analyses of `hop` frames and appends `points` points, one per `every` analyses
+    (every 0: the series is off, 0 points) (mtr_scope_series_cut; no device)."""
+    if not hasattr(lib, "mtr_scope_series_cut"):
+        raise EngineError(f"{lib_path} has no SCOPE reading series: rebuild it")
+    an, pt = C.c_uint64(), C.c_uint64()
+    _check(lib.mtr_scope_series_cut(int(fill), int(hop), int(since), int(every), int(n_frames), C.byref(an), C.byref(pt)), "mtr_scope_series_cut")
+    return an.value, pt.value
 
 
 def series_cut(fill, period, n_frames, frames):
@@ -996,6 +1015,40 @@ class Engine:
 
     def scope_reset(self):
         _check(lib.mtr_engine_scope_reset(self._h), "scope_reset")
+
+    def _need_scope_series(self):
+        if not hasattr(lib, "mtr_engine_scope_series"):
+            raise EngineError(f"{lib_path} has no SCOPE reading series: rebuild it")
+
+    def scope_set_series(self, every_analyses, capacity_points=0, fields=SCOPE_F_ALL):
+        """0: off.  K = 1 .. 2^20: after every K-th analysis since reset, wherever the calls cut the audio, what scope_read would answer
+        at that moment — the fields of `fields`, SCOPE_F_* bits — is appended to a series of `capacity_points` per stream.  Only before
+        the first process call since create / reset."""
+        self._need_scope_series()
+        _check(lib.mtr_engine_scope_set_series(self._h, int(every_analyses), int(capacity_points), int(fields)), "scope_set_series")
+
+    def scope_series_config(self):
+        """(every_analyses, capacity_points, fields) as scope_set_series set them; every_analyses 0: the series is off."""
+        self._need_scope_series()
+        k, c, f = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_scope_series_config(self._h, C.byref(k), C.byref(c), C.byref(f)), "scope_series_config")
+        return k.value, c.value, f.value
+
+    def scope_series(self, first=0, count=None):
+        """(dict of the selected fields: [count, kept, W / 2] float32 arrays and peak [count, kept], n_points, dropped): the points since
+        reset that the series holds."""
+        self._need_scope_series()
+        fields = self.scope_series_config()[2]
+        B = self.scope_config()[0] // 2
+        sel = [k for k in range(7) if fields >> k & 1]
+
+        def call(count, ptrs, *tail):
+            slots = [None] * 7
+            for k, p in zip(sel, ptrs):
+                slots[k] = p
+            return lib.mtr_engine_scope_series(self._h, first, count, *slots, *tail)
+        a, n, d = self._series("scope_series", first, count, [() if SCOPE_FIELDS[k] == "peak" else (B,) for k in sel], call)
+        return {SCOPE_FIELDS[k]: v for k, v in zip(sel, a)}, n, d
 
     def _need_loudlog(self):
         if not hasattr(lib, "mtr_engine_loudlog_series"):
