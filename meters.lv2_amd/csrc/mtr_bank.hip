@@ -345,24 +345,8 @@ template <typename A> __global__ __launch_bounds__ (64) void k_bank (const A a)
 	}
 }
 
-static int mtr_launch_bank (const mtr_bank_args& a, void* stream)
-{
-	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
-	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
-	hipLaunchKernelGGL (k_bank<mtr_bank_args>, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-static int mtr_launch_bank_series (const mtr_bank_series_args& a, void* stream)
-{
-	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
-	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
-	hipLaunchKernelGGL (k_bank<mtr_bank_series_args>, dim3 (nb), dim3 (64), 0, (hipStream_t) stream, a);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-// the ENDS instantiations: same grid, same lane map
-template <typename A> static int mtr_launch_bank_ends (const A& a, void* stream)
+// the four instantiations (dense or series, with ends or without): same grid, same lane map
+template <typename A> static int mtr_launch_bank (const A& a, void* stream)
 {
 	const uint64_t pairs = (uint64_t) a.n_streams * MTR_NBANDS;
 	const uint32_t nb = (uint32_t) ((pairs + 63) / 64);
@@ -504,14 +488,14 @@ static int bank_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnd
 			mtr_bank_series_ends_args ea;
 			static_cast<mtr_bank_series_args&> (ea) = sa;
 			ea.ends = se.ends;
-			if (mtr_launch_bank_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series, ends)");
-		} else if (mtr_launch_bank_series (sa, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series)");
+			if (mtr_launch_bank (ea, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series, ends)");
+		} else if (mtr_launch_bank (sa, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (series)");
 		nx.bk = series_advance (e->pos.bk, P, c.n_frames);
 	} else if (se.ends) {
 		mtr_bank_ends_args ea;
 		static_cast<mtr_bank_args&> (ea) = ba;
 		ea.ends = se.ends;
-		if (mtr_launch_bank_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (ends)");
+		if (mtr_launch_bank (ea, c.st)) return fail (MTR_ERR_HIP, "k_bank launch (ends)");
 	} else if (mtr_launch_bank (ba, c.st)) return fail (MTR_ERR_HIP, "k_bank launch");
 	nx.bank_ac_cur = e->pos.bank_ac_cur ^ 1;
 	return MTR_OK;
@@ -525,7 +509,9 @@ static void bank_sections (const mtr_engine* e, std::vector<StateSection>& v)
 	v.push_back ({ e->bank.ac[e->pos.bank_ac_cur].p, sizeof (int32_t) });
 }
 
-constinit SideMeter bank_meter = { MTR_METER_SPECTR30, 0, nullptr, bank_create, bank_reset, bank_step, bank_sections, nullptr };
+static SeriesView bank_series (mtr_engine* e) { return { &e->bank.ser, &Cursors::bk, &e->bank.points }; }
+
+constinit SideMeter bank_meter = { MTR_METER_SPECTR30, 0, nullptr, bank_create, bank_reset, bank_step, bank_sections, nullptr, bank_series };
 
 // With a period the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): where the open block
 // stands.  All of an entry is its host-owned header — period, peak mode, the frames into the open block; the block's levels and filter states are
@@ -562,11 +548,9 @@ static void bank_hdr_take (mtr_engine* e, const void* in)
 	e->pos.bk.fill = h.fill;
 }
 
-static int bank_open_reset (mtr_engine*) { return MTR_OK; }                                  // (the meter's first row resets all of it)
-static int bank_open_step (mtr_engine*, const Call&, Cursors&, const StreamEnds&) { return MTR_OK; }   // (... and queues all of it)
-
 static constinit BlobHeader bank_hdr = { 0, sizeof (mtr_bank_open), BANK_CORRUPT, bank_hdr_write, bank_hdr_check, bank_hdr_take };
-constinit SideMeter bank_series_meter = { MTR_METER_SPECTR30, 0, nullptr, nullptr, bank_open_reset, bank_open_step, bank_open_sections, &bank_hdr };
+// (no reset and no step: the meter's first row resets and queues all of it)
+constinit SideMeter bank_series_meter = { MTR_METER_SPECTR30, 0, nullptr, nullptr, nullptr, nullptr, bank_open_sections, &bank_hdr };
 
 // spectrumlv2.c:240-247 for n levels: the raw val_f / max_f and the dB values of ports 0-29 / 30-59 (any output may be null).  The stored val
 // carries the +1e-20f of :237; above the -100 dB floor (val > 5e-11) that addition does not change the float, so the port value is unaffected.
@@ -658,7 +642,7 @@ int mtr_engine_spectr_points (mtr_engine* e, uint32_t first, uint32_t count, uin
 	if (no_bank (e)) return fail (MTR_ERR_ARG, NO_BANK);
 	if (!points) return fail (MTR_ERR_ARG, "mtr_engine_spectr_points: null argument");
 	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
-	for (uint32_t i = 0; i < count; ++i) points[i] = e->bank.points[first + i];
+	series_points_of (e, MTR_METER_SPECTR30, first, count, points);
 	return MTR_OK;
 }
 

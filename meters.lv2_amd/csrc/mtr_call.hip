@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -479,7 +480,7 @@ struct CallRun {
 
 		const StreamEnds se { d_ends, d_fall };                       // (null on a dense call)
 		for (const SideMeter* m : SIDE_METERS)
-			if ((meters & m->bits) && (rc = m->step (e, c, nx, se))) return rc;
+			if ((meters & m->bits) && m->step && (rc = m->step (e, c, nx, se))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, a side meter's LEN kernel, or the fused kernels)
@@ -498,13 +499,12 @@ struct CallRun {
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
 			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
-			const struct { uint32_t bit; uint64_t P, fill; std::vector<uint64_t>& points; } ser[4] = {
-				{ MTR_METER_STCORR, e->sc.ser.period, e->pos.sc.fill, e->sc.points }, { MTR_METER_NEEDLE, e->nd.ser.period, e->pos.nd.fill, e->nd.points },
-				{ MTR_METER_KMETER, e->km.ser.period, e->pos.km.fill, e->km.points }, { MTR_METER_SPECTR30, e->bank.ser.period, e->pos.bk.fill, e->bank.points } };
-			for (const auto& q : ser) {
+			for (const SideMeter* m : SIDE_METERS) {
+				if (!(meters & m->bits) || !m->series) continue;
+				const SeriesView v = m->series (e);
 				uint64_t whole = 0;
 				uint32_t partial = 0;
-				if ((meters & q.bit) && q.P && series_cut (q.fill, q.P, c.n_frames, f, &whole, &partial)) q.points[g] += whole + partial;
+				if (v.cfg->period && series_cut ((e->pos.*v.pos).fill, v.cfg->period, c.n_frames, f, &whole, &partial)) (*v.points)[g] += whole + partial;
 			}
 			if (log) {
 				// periods the stream completed: those that end within the fragments it ended (as upload_lengths counts them)
@@ -644,6 +644,16 @@ static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frame
 	return rc;
 }
 
+// the counts of the one row of SIDE_METERS that has `bit` and keeps them (mtr_engine_series_points, mtr_engine_spectr_points)
+void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points)
+{
+	for (const SideMeter* m : SIDE_METERS) {
+		if (!(m->bits & bit) || !m->series) continue;
+		const std::vector<uint64_t>& v = *m->series (e).points;
+		for (uint32_t i = 0; i < count; ++i) points[i] = v[first + i];
+	}
+}
+
 extern "C" {
 
 int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_frames,
@@ -653,105 +663,98 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 	return process_device (e, d_audio, n_frames, stride, nullptr, hip_stream);
 }
 
-// Per-stream lengths need EBU / TRUEPEAK alone (every layout, 2 .. 5 channels)
-static int lengths_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
-{
-	if ((e->cfg.meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK)) || !(e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)))
-		return fail (MTR_ERR_UNSUPPORTED, "per-stream lengths: EBU / TRUEPEAK engines only");
-	for (uint32_t i = 0; i < n; ++i)
-		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "per-stream lengths: frames[s] > n_frames");
-	return MTR_OK;
-}
+// The four families of calls with per-stream ends (mtr_engine_process_{device,host}_*): which meters a family admits — an engine of some
+// of them and of no other — and what else it refuses.  frames_ends: applies a row, then takes the call.
+// _lengths: EBU / TRUEPEAK alone (every layout, 2 .. 5 channels); _tracks: and the whole-track meters (DR14, KMETER, BITSTATS, SIGDIST);
+// _ragged: and the two that keep a reading series, STCORR and NEEDLE (mtr_ragged.h); _ends: and the 30-band bank (mtr_ends.h)
+constexpr uint32_t LENGTHS_METERS = MTR_METER_EBU | MTR_METER_TRUEPEAK;
+constexpr uint32_t TRACKS_METERS = LENGTHS_METERS | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST;
+constexpr uint32_t RAGGED_METERS = TRACKS_METERS | MTR_METER_STCORR | MTR_METER_NEEDLE;
+constexpr uint32_t ENDS_METERS = RAGGED_METERS | MTR_METER_SPECTR30;
+struct Family {
+	const char* name;            // of its entry points: "<name>: null argument"
+	uint32_t    meters;
+	const char* unsupported;     // MTR_ERR_UNSUPPORTED: the engine holds another meter, or none of these
+	const char* too_long;        // MTR_ERR_ARG: frames[s] > n_frames
+	bool        no_km_series;    // _tracks: a KMETER engine with a period is refused
+	bool        bank_ends;       // _ends: at most two channels; 32-bit ends with SPECTR30
+};
+enum { LENGTHS, TRACKS, RAGGED, ENDS };
+constexpr Family FAMILIES[] = {
+	{ "lengths", LENGTHS_METERS, "per-stream lengths: EBU / TRUEPEAK engines only", "per-stream lengths: frames[s] > n_frames", false, false },
+	{ "tracks", TRACKS_METERS, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only", "track lengths: frames[s] > n_frames", true, false },
+	{ "ragged", RAGGED_METERS, "ragged batches: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE engines only",
+	  "ragged batches: frames[s] > n_frames", false, false },
+	{ "ends", ENDS_METERS,
+	  "track lengths for the bank: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 engines of one or two channels only",
+	  "track lengths for the bank: frames[s] > n_frames", false, true },
+};
 
-int mtr_engine_process_device_lengths (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
-                                       const uint64_t* frames, void* hip_stream)
+static int family_check (const mtr_engine* e, const Family& fam, uint64_t n_frames, const uint64_t* frames)
 {
-	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_lengths: null argument");
-	const int crc = lengths_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
-}
-
-// Track lengths: EBU / TRUEPEAK and the whole-track meters (DR14, KMETER, BITSTATS, SIGDIST), in any combination the engine was created with
-static int tracks_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
-{
-	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST;
-	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok))
-		return fail (MTR_ERR_UNSUPPORTED, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only");
-	if ((e->cfg.meters & MTR_METER_KMETER) && e->km.ser.period)
+	const uint32_t meters = e->cfg.meters;
+	if ((meters & ~fam.meters) || !(meters & fam.meters) || (fam.bank_ends && e->cfg.n_channels > 2)) return fail (MTR_ERR_UNSUPPORTED, fam.unsupported);
+	if (fam.no_km_series && (meters & MTR_METER_KMETER) && e->km.ser.period)
 		return fail (MTR_ERR_UNSUPPORTED, "track lengths: a KMETER engine with a period keeps a reading series (mtr_engine_process_*_ragged)");
-	for (uint32_t i = 0; i < n; ++i)
-		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "track lengths: frames[s] > n_frames");
+	if (fam.bank_ends && (meters & MTR_METER_SPECTR30) && n_frames > 0xFFFFFFFEull)
+		return fail (MTR_ERR_ARG, "track lengths for the bank: n_frames per call must be < 2^32 - 1");
+	for (uint32_t i = 0; i < e->cfg.n_streams; ++i)
+		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, fam.too_long);
 	return MTR_OK;
 }
 
-int mtr_engine_process_device_tracks (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
-                                      const uint64_t* frames, void* hip_stream)
+// what the eight entry points of the families are: `audio` in host memory (`host`) or in device memory, on `hip_stream`
+static int frames_ends (mtr_engine* e, int family, bool host, const float* audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
-	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_tracks: null argument");
-	const int crc = tracks_check (e, n_frames, frames, e->cfg.n_streams);
+	const Family& fam = FAMILIES[family];
+	if (!e || !audio || !frames) {
+		char who[64];
+		snprintf (who, sizeof (who), "mtr_engine_process_%s_%s: null argument", host ? "host" : "device", fam.name);
+		return fail (MTR_ERR_ARG, who);
+	}
+	const int crc = family_check (e, fam, n_frames, frames);
 	if (crc) return crc;
-	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+	return host ? process_chunked (e, { audio, 0, true, nullptr }, n_frames, stride, frames) : process_device (e, audio, n_frames, stride, frames, hip_stream);
 }
 
-// Ragged batches: the meters of _tracks and the two that keep a reading series, STCORR and NEEDLE (mtr_ragged.h)
-static int ragged_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
+int mtr_engine_process_device_lengths (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
-	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST
-	                        | MTR_METER_STCORR | MTR_METER_NEEDLE;
-	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok))
-		return fail (MTR_ERR_UNSUPPORTED, "ragged batches: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE engines only");
-	for (uint32_t i = 0; i < n; ++i)
-		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "ragged batches: frames[s] > n_frames");
-	return MTR_OK;
+	return frames_ends (e, LENGTHS, false, d_audio, n_frames, stride, frames, hip_stream);
 }
 
-int mtr_engine_process_device_ragged (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
-                                      const uint64_t* frames, void* hip_stream)
+int mtr_engine_process_device_tracks (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
-	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_ragged: null argument");
-	const int crc = ragged_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+	return frames_ends (e, TRACKS, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_device_ragged (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
+{
+	return frames_ends (e, RAGGED, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_device_ends (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
+{
+	return frames_ends (e, ENDS, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	return frames_ends (e, LENGTHS, true, h_audio, n_frames, stride, frames, nullptr);
+}
+
+int mtr_engine_process_host_tracks (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	return frames_ends (e, TRACKS, true, h_audio, n_frames, stride, frames, nullptr);
 }
 
 int mtr_engine_process_host_ragged (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
-	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_ragged: null argument");
-	const int crc = ragged_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
-}
-
-// Track lengths for the 30-band bank (mtr_ends.h): the meters of _ragged and SPECTR30, whose ends on the device are 32 bits
-static int ends_check (mtr_engine* e, uint64_t n_frames, const uint64_t* frames, uint32_t n)
-{
-	constexpr uint32_t ok = MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST
-	                        | MTR_METER_STCORR | MTR_METER_NEEDLE | MTR_METER_SPECTR30;
-	if ((e->cfg.meters & ~ok) || !(e->cfg.meters & ok) || e->cfg.n_channels > 2)
-		return fail (MTR_ERR_UNSUPPORTED, "track lengths for the bank: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 engines of one or two channels only");
-	if ((e->cfg.meters & MTR_METER_SPECTR30) && n_frames > 0xFFFFFFFEull)
-		return fail (MTR_ERR_ARG, "track lengths for the bank: n_frames per call must be < 2^32 - 1");
-	for (uint32_t i = 0; i < n; ++i)
-		if (frames[i] > n_frames) return fail (MTR_ERR_ARG, "track lengths for the bank: frames[s] > n_frames");
-	return MTR_OK;
-}
-
-int mtr_engine_process_device_ends (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride,
-                                    const uint64_t* frames, void* hip_stream)
-{
-	if (!e || !d_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_device_ends: null argument");
-	const int crc = ends_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_device (e, d_audio, n_frames, stride, frames, hip_stream);
+	return frames_ends (e, RAGGED, true, h_audio, n_frames, stride, frames, nullptr);
 }
 
 int mtr_engine_process_host_ends (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
-	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_ends: null argument");
-	const int crc = ends_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
+	return frames_ends (e, ENDS, true, h_audio, n_frames, stride, frames, nullptr);
 }
 
 int mtr_engine_series_points (mtr_engine* e, uint32_t meter, uint32_t first, uint32_t count, uint64_t* points)
@@ -760,8 +763,7 @@ int mtr_engine_series_points (mtr_engine* e, uint32_t meter, uint32_t first, uin
 	if ((meter != MTR_METER_STCORR && meter != MTR_METER_NEEDLE && meter != MTR_METER_KMETER) || !(e->cfg.meters & meter))
 		return fail (MTR_ERR_ARG, "mtr_engine_series_points: meter is MTR_METER_STCORR, MTR_METER_NEEDLE or MTR_METER_KMETER, one the engine holds");
 	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
-	const std::vector<uint64_t>& v = meter == MTR_METER_STCORR ? e->sc.points : meter == MTR_METER_NEEDLE ? e->nd.points : e->km.points;
-	for (uint32_t i = 0; i < count; ++i) points[i] = v[first + i];
+	series_points_of (e, meter, first, count, points);
 	return MTR_OK;
 }
 
@@ -796,28 +798,12 @@ int mtr_engine_process_host (mtr_engine* e, const float* h_audio, uint64_t n_fra
 	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, nullptr);
 }
 
-int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
-{
-	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_lengths: null argument");
-	const int crc = lengths_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
-}
-
-int mtr_engine_process_host_tracks (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
-{
-	if (!e || !h_audio || !frames) return fail (MTR_ERR_ARG, "mtr_engine_process_host_tracks: null argument");
-	const int crc = tracks_check (e, n_frames, frames, e->cfg.n_streams);
-	if (crc) return crc;
-	return process_chunked (e, { h_audio, 0, true, nullptr }, n_frames, stride, frames);
-}
-
 // Integer PCM: what every PCM entry point checks before anything is queued
 static int pcm_check (mtr_engine* e, const void* pcm, int format, uint64_t n_frames, const uint64_t* frames, const char* who)
 {
 	if (!e || !pcm) return fail (MTR_ERR_ARG, who);
 	if (!mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown PCM format (MTR_PCM_S16, _S24, _S32)");
-	return frames ? lengths_check (e, n_frames, frames, e->cfg.n_streams) : MTR_OK;
+	return frames ? family_check (e, FAMILIES[LENGTHS], n_frames, frames) : MTR_OK;
 }
 
 int mtr_engine_process_host_pcm (mtr_engine* e, const void* h_pcm, int format, uint64_t n_frames, uint64_t stride, const uint64_t* frames)

@@ -26,6 +26,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -213,21 +214,15 @@ __global__ __launch_bounds__ (64) void k_dr14_windows (const mtr_dr14_args a)
 static int mtr_launch_dr14 (const mtr_dr14_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
-	if (a.ends) {
-		if (a.n_channels == 2) {
-			hipLaunchKernelGGL ((k_dr14_sums<2, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-			hipLaunchKernelGGL ((k_dr14_windows<2, true>), dim3 (a.n_streams), dim3 (64), 0, st, a);
-		} else {
-			hipLaunchKernelGGL ((k_dr14_sums<1, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-			hipLaunchKernelGGL ((k_dr14_windows<1, true>), dim3 (a.n_streams), dim3 (64), 0, st, a);
-		}
-	} else if (a.n_channels == 2) {
-		hipLaunchKernelGGL ((k_dr14_sums<2, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		hipLaunchKernelGGL ((k_dr14_windows<2, false>), dim3 (a.n_streams), dim3 (64), 0, st, a);
-	} else {
-		hipLaunchKernelGGL ((k_dr14_sums<1, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		hipLaunchKernelGGL ((k_dr14_windows<1, false>), dim3 (a.n_streams), dim3 (64), 0, st, a);
-	}
+	// (n_channels, per-stream ends or none) to the kernels' template arguments, once
+	const auto launch = [&] (auto C, auto LEN) {
+		hipLaunchKernelGGL ((k_dr14_sums<C.value, LEN.value>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL ((k_dr14_windows<C.value, LEN.value>), dim3 (a.n_streams), dim3 (64), 0, st, a);
+	};
+	using One = std::integral_constant<int, 1>;
+	using Two = std::integral_constant<int, 2>;
+	if (a.n_channels == 2) { if (a.ends) launch (Two {}, std::true_type {}); else launch (Two {}, std::false_type {}); }
+	else                   { if (a.ends) launch (One {}, std::true_type {}); else launch (One {}, std::false_type {}); }
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

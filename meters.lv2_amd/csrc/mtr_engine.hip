@@ -370,7 +370,7 @@ int mtr_engine_reset (mtr_engine* e)
 	e->last_n_frag = 0;
 	e->last_deferred = false;
 	for (const SideMeter* m : SIDE_METERS)
-		if ((e->cfg.meters & m->bits) && (rc = m->reset (e))) return rc;
+		if ((e->cfg.meters & m->bits) && m->reset && (rc = m->reset (e))) return rc;
 	if (e->ll.period) return loudlog_reset (e, st);
 	return MTR_OK;
 }

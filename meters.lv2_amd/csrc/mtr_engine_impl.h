@@ -394,26 +394,36 @@ struct BlobHeader {
 };
 // One row per side meter, in the order of SIDE_METERS: the order of the blob's sections and of a call's steps.  A hook runs only in an
 // engine that has one of `bits`.
+// A reading series that counts its points per stream (streams end at their own lengths: mtr_ragged.h, mtr_ends.h), as the call path,
+// the state import and the points getters see it: P and the capacity, the series' cursor in Cursors, the counts since reset [S]
+struct SeriesView {
+	const SeriesCfg*       cfg;
+	SeriesPos Cursors::*   pos;
+	std::vector<uint64_t>* points;
+};
 struct SideMeter {
 	uint32_t    bits;                                             // MTR_METER_*
 	uint64_t    max_frames;                                       // a call of this many frames or more is refused (0: no limit of its own) ...
 	const char* max_text;                                         // ... with this text
 	int  (*create) (mtr_engine* e);                               // create-time set-up, or null
 	int  (*reset) (mtr_engine* e);                                // the meter's part of mtr_engine_reset: its state and its cursors in e->pos (where the
-	                                                              // meter has a reset of its own in the C ABI, that entry point)
-	// queues the meter's kernels for the view of call `c` and moves the meter's cursors in `nx` (CallRun::run stores them)
+	                                                              // meter has a reset of its own in the C ABI, that entry point), or null
+	// queues the meter's kernels for the view of call `c` and moves the meter's cursors in `nx` (CallRun::run stores them), or null
 	int  (*step) (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se);
 	void (*sections) (const mtr_engine* e, std::vector<StateSection>& v);   // appends the arrays a stream carries from call to call
 	const BlobHeader* hdr;                                        // in the first of them, or null
+	SeriesView (*series) (mtr_engine* e);                         // the meter's reading series, if it counts its points per stream, or null
 };
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
 extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
                  bank_series_meter, scope_series_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
-                                                    &kmeter_series_meter,     // (KMETER's second row: the blob section of its open block, behind every older one)
+                                                    &kmeter_series_meter,     // (KMETER's second row: nothing but the blob section of its open block, behind every older one)
                                                     &bank_series_meter,       // (SPECTR30's second row, likewise)
                                                     &scope_series_meter };    // (SCOPE's second row, likewise)
+// the points of each of streams [first, first + count) in the series of the meter with `bit`, which the engine holds and which keeps such counts
+void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points);
 
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view

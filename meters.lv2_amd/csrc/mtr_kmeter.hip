@@ -50,6 +50,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -486,23 +487,23 @@ static void mtr_kmeter_powers (float omega, double* pw1 /* [3] */)
 
 static uint32_t mtr_kmeter_pieces (uint64_t n_groups) { return (uint32_t) ((n_groups + CH - 1) / CH); }
 
+// f (C, LEN): the kernels' template arguments for a call of n_channels (2, or 1), with per-stream ends or without, as integral constants
+template <typename F> static void with_c_len (uint32_t n_channels, bool ends, F f)
+{
+	using One = std::integral_constant<int, 1>;
+	using Two = std::integral_constant<int, 2>;
+	if (n_channels == 2) { if (ends) f (Two {}, std::true_type {}); else f (Two {}, std::false_type {}); }
+	else                 { if (ends) f (One {}, std::true_type {}); else f (One {}, std::false_type {}); }
+}
+
 static int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
 	const uint32_t n = a.n_streams * a.n_channels;
-	if (a.ends) {
-		if (a.n_pieces) {
-			if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_pieces<2, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-			else                   hipLaunchKernelGGL ((k_kmeter_pieces<1, true>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		}
-		hipLaunchKernelGGL (k_kmeter_final<true>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
-		return hipGetLastError () == hipSuccess ? 0 : -1;
-	}
-	if (a.n_pieces) {
-		if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_pieces<2, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		else                   hipLaunchKernelGGL ((k_kmeter_pieces<1, false>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-	}
-	hipLaunchKernelGGL (k_kmeter_final<false>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	with_c_len (a.n_channels, a.ends != nullptr, [&] (auto C, auto LEN) {
+		if (a.n_pieces) hipLaunchKernelGGL ((k_kmeter_pieces<C.value, LEN.value>), dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL (k_kmeter_final<LEN.value>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	});
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -520,15 +521,10 @@ static int mtr_launch_kmb (const mtr_kmb_args& a, void* stream)
 	hipStream_t st = (hipStream_t) stream;
 	const dim3 g (a.n_pieces, a.n_streams), b (NT);
 	const uint32_t n = a.n_streams * a.n_channels;
-	if (a.ends) {
-		if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_blocks<2, true>), g, b, 0, st, a);
-		else                   hipLaunchKernelGGL ((k_kmeter_blocks<1, true>), g, b, 0, st, a);
-		hipLaunchKernelGGL (k_kmeter_walk<true>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
-	} else {
-		if (a.n_channels == 2) hipLaunchKernelGGL ((k_kmeter_blocks<2, false>), g, b, 0, st, a);
-		else                   hipLaunchKernelGGL ((k_kmeter_blocks<1, false>), g, b, 0, st, a);
-		hipLaunchKernelGGL (k_kmeter_walk<false>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
-	}
+	with_c_len (a.n_channels, a.ends != nullptr, [&] (auto C, auto LEN) {
+		hipLaunchKernelGGL ((k_kmeter_blocks<C.value, LEN.value>), g, b, 0, st, a);
+		hipLaunchKernelGGL (k_kmeter_walk<LEN.value>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	});
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -640,14 +636,14 @@ static void kmeter_hdr_take (mtr_engine* e, const void* in)
 	e->pos.km.fill = h.fill; e->pos.km_fpp = h.fpp; e->pos.km_fall = h.fall;
 }
 
-static int kmeter_open_reset (mtr_engine*) { return MTR_OK; }                                  // (the meter's first row resets all of it)
-static int kmeter_open_step (mtr_engine*, const Call&, Cursors&, const StreamEnds&) { return MTR_OK; }   // (... and queues all of it)
-
 static constinit BlobHeader kmeter_hdr = { 0, KM_HDR_BYTES, KM_CORRUPT, kmeter_hdr_write, kmeter_hdr_check, kmeter_hdr_take };
-constinit SideMeter kmeter_series_meter = { MTR_METER_KMETER, 0, nullptr, nullptr, kmeter_open_reset, kmeter_open_step, kmeter_open_sections, &kmeter_hdr };
+// (no reset and no step: the meter's first row resets and queues all of it)
+constinit SideMeter kmeter_series_meter = { MTR_METER_KMETER, 0, nullptr, nullptr, nullptr, nullptr, kmeter_open_sections, &kmeter_hdr };
+
+static SeriesView kmeter_series (mtr_engine* e) { return { &e->km.ser, &Cursors::km, &e->km.points }; }
 
 constinit SideMeter kmeter_meter = { MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr };
+                                           nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr, kmeter_series };
 
 extern "C" {
 

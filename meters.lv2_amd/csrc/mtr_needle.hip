@@ -577,8 +577,10 @@ static void needle_hdr_take (mtr_engine* e, const void* in)
 }
 
 static constinit BlobHeader needle_hdr = { 0, sizeof (mtr_needle_hdr), NEEDLE_CORRUPT, needle_hdr_write, needle_hdr_check, needle_hdr_take };
+static SeriesView needle_series (mtr_engine* e) { return { &e->nd.ser, &Cursors::nd, &e->nd.points }; }
+
 constinit SideMeter needle_meter = { MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           needle_create, mtr_engine_needle_reset, needle_step, needle_sections, &needle_hdr };
+                                           needle_create, mtr_engine_needle_reset, needle_step, needle_sections, &needle_hdr, needle_series };
 
 extern "C" {
 

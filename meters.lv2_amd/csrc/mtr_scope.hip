@@ -511,11 +511,9 @@ static void scope_open_take (mtr_engine* e, const void* in)
 	e->pos.sp_since = h.since;
 }
 
-static int scope_open_reset (mtr_engine*) { return MTR_OK; }                                  // (the meter's first row resets all of it)
-static int scope_open_step (mtr_engine*, const Call&, Cursors&, const StreamEnds&) { return MTR_OK; }   // (... and queues all of it)
-
 static constinit BlobHeader scope_open_hdr = { 0, sizeof (mtr_scope_open), SCOPE_SERIES_CORRUPT, scope_open_write, scope_open_check, scope_open_take };
-constinit SideMeter scope_series_meter = { MTR_METER_SCOPE, 0, nullptr, nullptr, scope_open_reset, scope_open_step, scope_open_sections, &scope_open_hdr };
+// (no reset and no step: the meter's first row resets and queues all of it)
+constinit SideMeter scope_series_meter = { MTR_METER_SCOPE, 0, nullptr, nullptr, nullptr, nullptr, scope_open_sections, &scope_open_hdr };
 
 extern "C" {
 

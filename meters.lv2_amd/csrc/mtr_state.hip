@@ -190,11 +190,12 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	for (uint32_t k = 0; k < h.count; ++k) {                     // (an imported stream is open — closure is not part of the blob — and
 		if (e->closed[first + k]) { e->closed[first + k] = 0; e->n_closed--; }   // its count starts again: the blob does not carry one)
 		e->metered[first + k] = 0;
-		// (... and it stands where the open streams do: its series has their points)
-		if (e->cfg.meters & MTR_METER_STCORR) e->sc.points[first + k] = e->pos.sc.points;
-		if (e->cfg.meters & MTR_METER_NEEDLE) e->nd.points[first + k] = e->pos.nd.points;
-		if (e->cfg.meters & MTR_METER_KMETER) e->km.points[first + k] = e->pos.km.points;
-		if (e->cfg.meters & MTR_METER_SPECTR30) e->bank.points[first + k] = e->pos.bk.points;
+		// (... and it stands where the open streams do: its series have their points)
+		for (const SideMeter* m : SIDE_METERS) {
+			if (!(e->cfg.meters & m->bits) || !m->series) continue;
+			const SeriesView v = m->series (e);
+			(*v.points)[first + k] = (e->pos.*v.pos).points;
+		}
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;

@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -342,13 +343,11 @@ static void mtr_stcorr_geometry (float w1, uint32_t* warm, uint32_t* chunk)
 static int mtr_launch_stcorr (const mtr_stcorr_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
-	if (a.ends) {
-		hipLaunchKernelGGL (k_stcorr_pieces<true>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		hipLaunchKernelGGL (k_stcorr_final<true>, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
-	} else {
-		hipLaunchKernelGGL (k_stcorr_pieces<false>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
-		hipLaunchKernelGGL (k_stcorr_final<false>, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
-	}
+	const auto launch = [&] (auto LEN) {                              // (per-stream ends or none: the kernels' template argument)
+		hipLaunchKernelGGL (k_stcorr_pieces<LEN.value>, dim3 (a.n_pieces, a.n_streams), dim3 (NT), 0, st, a);
+		hipLaunchKernelGGL (k_stcorr_final<LEN.value>, dim3 ((a.n_streams + 63) / 64), dim3 (64), 0, st, a);
+	};
+	if (a.ends) launch (std::true_type {}); else launch (std::false_type {});
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -412,9 +411,11 @@ static void stcorr_hdr_take (mtr_engine* e, const void* in)
 	e->sc.ser.period = h.period; e->pos.sc.fill = h.fill;
 }
 
+static SeriesView stcorr_series (mtr_engine* e) { return { &e->sc.ser, &Cursors::sc, &e->sc.points }; }
+
 static constinit BlobHeader stcorr_hdr = { offsetof (mtr_stcorr_state, period), sizeof (StcorrHdr), STCORR_CORRUPT, stcorr_hdr_write, stcorr_hdr_check, stcorr_hdr_take };
 constinit SideMeter stcorr_meter = { MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           stcorr_create, mtr_engine_stcorr_reset, stcorr_step, stcorr_sections, &stcorr_hdr };
+                                           stcorr_create, mtr_engine_stcorr_reset, stcorr_step, stcorr_sections, &stcorr_hdr, stcorr_series };
 
 extern "C" {
 

@@ -551,111 +551,81 @@ class Engine:
         x = self._frames_f32(x)
         _check(lib.mtr_engine_process_host(self._h, x.ctypes.data, x.shape[1], x.shape[1]), "process_host")
 
-    def _lengths(self, frames, n_frames):
-        if not hasattr(lib, "mtr_engine_stream_frames"):
-            raise EngineError(f"{lib_path} has no per-stream lengths: rebuild it")
+    # the families of calls with per-stream ends: the symbol whose absence means "rebuild the library", and what the library then lacks
+    _FAMILY = {"lengths": ("mtr_engine_stream_frames", "per-stream lengths"), "tracks": ("mtr_engine_process_device_tracks", "track lengths"),
+               "ragged": ("mtr_engine_process_device_ragged", "ragged batches"),
+               "ends": ("mtr_engine_process_device_ends", "track lengths for the 30-band bank")}
+
+    def _frames(self, frames, family):
+        """frames as contiguous uint64 [S], for a call of `family`"""
+        symbol, what = self._FAMILY[family]
+        if not hasattr(lib, symbol):
+            raise EngineError(f"{lib_path} has no {what}: rebuild it")
         f = np.ascontiguousarray(frames, np.uint64)
         if f.shape != (self.n_streams,):
             raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
         return f
+
+    def _device_frames(self, family, ptr, n_frames, frames, stride, stream):
+        f = self._frames(frames, family)
+        _check(getattr(lib, "mtr_engine_process_device_" + family)(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
+               "process_device_" + family)
+
+    def _host_frames(self, family, x, frames):
+        x = self._frames_f32(x)
+        f = self._frames(frames, family)
+        _check(getattr(lib, "mtr_engine_process_host_" + family)(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
+               "process_host_" + family)
 
     def process_device_lengths(self, ptr, n_frames, frames, stride=None, stream=0):
         """Advance stream s by frames[s] <= n_frames frames of the device buffer at `ptr`; a stream with frames[s] < n_frames
         is closed by the call (its results are final until reset()), frames[s] == n_frames leaves it open."""
-        f = self._lengths(frames, n_frames)
-        _check(lib.mtr_engine_process_device_lengths(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
-               "process_device_lengths")
+        self._device_frames("lengths", ptr, n_frames, frames, stride, stream)
 
     def process_lengths(self, x, frames):
         """process() with per-stream lengths: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
-        x = self._frames_f32(x)
-        f = self._lengths(frames, x.shape[1])
-        _check(lib.mtr_engine_process_host_lengths(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
-               "process_host_lengths")
-
-    def _tracks(self, frames):
-        if not hasattr(lib, "mtr_engine_process_device_tracks"):
-            raise EngineError(f"{lib_path} has no track lengths: rebuild it")
-        f = np.ascontiguousarray(frames, np.uint64)
-        if f.shape != (self.n_streams,):
-            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
-        return f
+        self._host_frames("lengths", x, frames)
 
     def process_device_tracks(self, ptr, n_frames, frames, stride=None, stream=0):
         """process_device_lengths() for engines of EBU, TRUEPEAK, DR14, KMETER, BITSTATS and SIGDIST in any combination: stream s is
         metered up to frames[s] <= n_frames, as by a host that stops calling run() at the track's end; frames[s] < n_frames closes it."""
-        f = self._tracks(frames)
-        _check(lib.mtr_engine_process_device_tracks(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
-               "process_device_tracks")
+        self._device_frames("tracks", ptr, n_frames, frames, stride, stream)
 
     def process_tracks(self, x, frames):
         """process() with track lengths: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
-        x = self._frames_f32(x)
-        f = self._tracks(frames)
-        _check(lib.mtr_engine_process_host_tracks(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
-               "process_host_tracks")
-
-    def _ragged(self, frames):
-        if not hasattr(lib, "mtr_engine_process_device_ragged"):
-            raise EngineError(f"{lib_path} has no ragged batches: rebuild it")
-        f = np.ascontiguousarray(frames, np.uint64)
-        if f.shape != (self.n_streams,):
-            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
-        return f
+        self._host_frames("tracks", x, frames)
 
     def process_device_ragged(self, ptr, n_frames, frames, stride=None, stream=0):
         """process_device_tracks() for engines that also hold STCORR or NEEDLE: stream s is metered up to frames[s] <= n_frames, the
         block it ends in truncated there (one last process () and read (), the stream's last point); frames[s] < n_frames closes it."""
-        f = self._ragged(frames)
-        _check(lib.mtr_engine_process_device_ragged(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
-               "process_device_ragged")
+        self._device_frames("ragged", ptr, n_frames, frames, stride, stream)
 
     def process_ragged(self, x, frames):
         """process() as a ragged batch: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
-        x = self._frames_f32(x)
-        f = self._ragged(frames)
-        _check(lib.mtr_engine_process_host_ragged(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
-               "process_host_ragged")
+        self._host_frames("ragged", x, frames)
 
     def series_points(self, meter, first=0, count=None):
         """[count] uint64: the points each stream's own STCORR, NEEDLE or KMETER series (meter: METER_STCORR / METER_NEEDLE / METER_KMETER) has got since reset,
         dropped ones included — of a stream that a ragged call closed, its whole blocks and the truncated one."""
-        self._ragged(np.zeros(self.n_streams, np.uint64))
+        self._frames(np.zeros(self.n_streams, np.uint64), "ragged")
         count = self.n_streams - first if count is None else count
         out = np.zeros(count, np.uint64)
         _check(lib.mtr_engine_series_points(self._h, int(meter), first, count, out.ctypes.data), "series_points")
         return out
 
-    @staticmethod
-    def _need_ends():
-        if not hasattr(lib, "mtr_engine_process_device_ends"):
-            raise EngineError(f"{lib_path} has no track lengths for the 30-band bank: rebuild it")
-
-    def _ends(self, frames):
-        self._need_ends()
-        f = np.ascontiguousarray(frames, np.uint64)
-        if f.shape != (self.n_streams,):
-            raise ValueError(f"frames: one length per stream, shape ({self.n_streams},), not {f.shape}")
-        return f
-
     def process_device_ends(self, ptr, n_frames, frames, stride=None, stream=0):
         """process_device_ragged() for engines that also hold SPECTR30: stream s is metered up to frames[s] <= n_frames — the bank's
         spectrum_run ends there with its epilogue and, with a period, a truncated last point; frames[s] < n_frames closes it."""
-        f = self._ends(frames)
-        _check(lib.mtr_engine_process_device_ends(self._h, ptr, n_frames, stride or n_frames, f.ctypes.data, stream),
-               "process_device_ends")
+        self._device_frames("ends", ptr, n_frames, frames, stride, stream)
 
     def process_ends(self, x, frames):
         """process() with track lengths for the bank: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
-        x = self._frames_f32(x)
-        f = self._ends(frames)
-        _check(lib.mtr_engine_process_host_ends(self._h, x.ctypes.data, x.shape[1], x.shape[1], f.ctypes.data),
-               "process_host_ends")
+        self._host_frames("ends", x, frames)
 
     def spectr_points(self, first=0, count=None):
         """[count] uint64: the points each stream's own SPECTR30 series has got since reset, dropped ones included — of a stream that
         process_*_ends closed, its whole blocks and the truncated one."""
-        self._need_ends()
+        self._frames(np.zeros(self.n_streams, np.uint64), "ends")
         count = self.n_streams - first if count is None else count
         out = np.zeros(count, np.uint64)
         _check(lib.mtr_engine_spectr_points(self._h, first, count, out.ctypes.data), "spectr_points")
@@ -676,14 +646,14 @@ class Engine:
             if x.shape[:1] != (self.n_streams,) or not (x.shape[2:] == (C_,) and x.ndim == 3 or (C_ == 1 and x.ndim == 2)):
                 raise ValueError(f"integer PCM: [{self.n_streams}, T, {C_}]" + (" or [S, T]" if C_ == 1 else "") + f", not {x.shape}")
             n = x.shape[1]
-        f = None if frames is None else self._lengths(frames, n)
+        f = None if frames is None else self._frames(frames, "lengths")
         _check(lib.mtr_engine_process_host_pcm(self._h, x.ctypes.data, fmt, n, n, None if f is None else f.ctypes.data), "process_host_pcm")
 
     def process_device_pcm(self, ptr, format, n_frames, stride=None, frames=None, stream=0):
         """process_device() for integer PCM in device memory at `ptr` (stream s at ptr + s * stride * n_channels * sample bytes): one
         decode pass on top of the meters.  frames: per-stream lengths as process_device_lengths()."""
         _need_pcm()
-        f = None if frames is None else self._lengths(frames, n_frames)
+        f = None if frames is None else self._frames(frames, "lengths")
         _check(lib.mtr_engine_process_device_pcm(self._h, ptr, int(format), n_frames, stride or n_frames,
                                                  None if f is None else f.ctypes.data, stream), "process_device_pcm")
 
