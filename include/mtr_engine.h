@@ -114,8 +114,9 @@ typedef struct {
 	uint32_t tune_fir;       /* layout 3 only: 0 = mirror-symmetric form (120 ops / frame), 1 = dense 3 x 48 taps */
 	uint32_t tune_prune;     /* 1 = exact true-peak pruning (branch and bound on L1 * max|x| per tile): identical result,
 	                          * data-dependent speed; off by default.  (Layout 7's k_seg screens its products with the first one
-	                          * regardless — the same bits, always on: MTR_SEG_SCREEN=0, read by mtr_engine_create, is the test knob
-	                          * that forces its dense form.)
+	                          * regardless — the same bits, always on: MTR_SEG_SCREEN, read by mtr_engine_create, is the test knob:
+	                          * 0 forces its dense form, 1 the screen whose stream reference sees completed interpolated peaks only
+	                          * at a flush, 2 (the default) the screen that feeds them to the reference as they are found.)
 	                          * 2 (layout 6) = the same, and inside a tile every 256-frame block is screened with the first of
 	                          * the three f16 products and completed only if it can still hold the maximum: also identical.
 	                          * (Pruning is a layout 6 feature: with tune_prune set, layout 7 is not used.) */
@@ -482,7 +483,7 @@ int  mtr_engine_timing_calls (mtr_engine* e, float* out, uint32_t cap, uint32_t*
 int  mtr_engine_prune_stats (mtr_engine* e, uint64_t* considered, uint64_t* skipped);
 /* Products screened with the first of the three f16 products / completed with the other two, since the engine was created:
  * with tune_prune = 2 (layout 6) 256-frame channel-blocks of k_kwtp16; in layout 7 also k_seg's 16-column chunks (screened
- * always, unless MTR_SEG_SCREEN=0).  Layout 6 engines without tune_prune = 2 count nothing. */
+ * always, unless MTR_SEG_SCREEN=0; MTR_SEG_SCREEN=1 and 2, the default, screen the same chunks and complete different numbers of them).  Layout 6 engines without tune_prune = 2 count nothing. */
 int  mtr_engine_refine_stats (mtr_engine* e, uint64_t* screened, uint64_t* completed);
 /* The kernel layout the engine resolved to (tune_layout = 0 picks one from the meters mask): 3, 4, 6 or 7. */
 int  mtr_engine_layout (const mtr_engine* e);

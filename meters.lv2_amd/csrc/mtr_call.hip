@@ -292,7 +292,7 @@ struct CallRun {
 		sa.n_streams = S; sa.n_segs = sp.n_segs; sa.n_tiles = pl.n_tiles; sa.tile_frames = e->fragm;
 		sa.seg_base = sp.base; sa.seg_rem = sp.rem; sa.n_main = sp.n_main; sa.warm_steps = sp.warm_steps;
 		sa.p0_end = (int64_t) c.n_frames - 24 - (int64_t) sp.head;
-		sa.screen = e->seg_screen ? 1u : 0u; sa.seg_stats = e->prune_cnt.p + 2;
+		sa.screen = e->seg_screen; sa.seg_stats = e->prune_cnt.p + 2;
 		set_kweight (e, sa);
 		sa.ends = d_ends;
 		const uint64_t units = (uint64_t) S * sp.n_segs;

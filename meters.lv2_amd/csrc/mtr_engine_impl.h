@@ -156,7 +156,9 @@ struct mtr_engine {
 	DevBuf<uint32_t> prune_cnt;     // [4] interpolator tile passes considered / skipped, channel-blocks screened / completed
 	uint64_t         prune_tot[4] = { 0, 0, 0, 0 };
 	float            tpb_w[4];      // w1 w2 w3 g of TruePeakdsp::init
-	bool             seg_screen = true;      // k_seg's products screened by the first of the three (mtr_seg.hip: SCREEN); MTR_SEG_SCREEN=0 forces the dense form
+	uint32_t         seg_screen = 2;         // k_seg's products screened by the first of the three (mtr_seg.hip: SCREEN): 0 = the dense form, 1 = screened, the stream
+	                                         // reference fed by sample peaks until a flush, 2 = screened, completed interpolated peaks fed into it as they are found
+	                                         // (the peek; the default).  MTR_SEG_SCREEN=0 / 1 / 2 selects one
 	uint32_t         last_n_frag = 0;
 	// Per-stream lengths: frames metered per stream since create / reset, and which streams a call with lengths has closed (a closed
 	// stream is left untouched by every later call until mtr_engine_reset; neither is part of the state blob).

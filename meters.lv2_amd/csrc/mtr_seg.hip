@@ -128,6 +128,35 @@ constexpr float SCREEN_K_ABS = 0.0078125f;
 //     there (a step votes on all eight of its chunks and completes the failing ones itself: none is pending at the next rescale).
 // A wave in the bench's shape (8 segments per stream) holds 8 streams; their quiet segments stop completing against their own
 // small records.  tests/test_gpu_seg_stream_reference.py holds the screened form to the dense one bit for bit.
+//
+// Completed interpolated peaks in the reference (a.screen == 2, the default; 1 is the rule without them).  pkf receives
+// interpolated values only in flush_pm, at a rescale and at the end of the launch, so under rule 1 R is in effect the stream's SAMPLE
+// peak: what completed chunks have found lives in pm, per accumulator lane (one column, four rows of the step), and every chunk
+// of the stream with a first product between the sample peak and the true peak found so far completes again, lane by lane, until
+// each of the 64 accumulator lanes has met such a value itself.  Rule 2: a step that has completed chunks runs flush_pm's exchange
+// without clearing pm (peek_pm), in front of its ring stores, so the owners' pkf — and with it R, at its next refresh — holds what the
+// stream's completed chunks have found so far.  Why the launch's result is still the dense bits:
+//   * The same final value.  pkf only ever receives fl (pm * un); pm only grows until a flush clears it, and x -> fl (x * un) is
+//     monotone (un a power of two), so an early peek adds nothing that the next flush_pm — there is always one behind it, at a
+//     rescale or at the end of the launch — would not deliver: max (pk0, pkf) at the end is the same float, subnormal results
+//     included.  pm is left as it is because a cleared pm would be wrong for the lanes that offer nothing — the shadow lanes of a
+//     partly filled last wave and the !peak_ok lanes: with pm = 0 and R = 0 they would fail every vote from then on.
+//   * R still holds only values this launch counts for that (stream, channel).  pm of column 16 b + c holds outputs of that column
+//     alone (completed chunks fold in the dense order, the launch's last step masks its rows as the dense form does), and they are
+//     what the column's final atomicMax counts.  The offer stays gated by live && peak_ok: a !peak_ok lane's peeked pkf (its
+//     chunk completes where a neighbouring column fails) is neither offered nor stored.  pkf, pm and R start every launch at zero.
+//   * The scale.  pm is always in the column's current scale (a rescale flushes and clears it first, and the peek runs behind the
+//     step's rescale, in the step that completed the chunks); the owner converts with its own current un.  Every lane writes all
+//     eight of its exchange words in every peek, so no word of an older scale or of an earlier flush_pm is read.
+//   * NaN, Inf: pm and pkf never hold a NaN (the folds' and the peek's fmaxf drop it); an Inf in pm makes pkf and R Inf, which the
+//     argument above already covers.
+//   * The conversion: R' = R * scale * 2^15 against pm of the same column — equal where nothing underflows (powers of two).  Where
+//     pm * un is a subnormal, pkf is its rounding, a value the launch counts, and the pass is exact as for any R: |Y| < R' gives
+//     fl (|Y| un) <= fl (R' un) = R by monotonicity.  Where R' itself underflows it is smaller than the true one or cannot decide
+//     a vote (eps >= 2^-7, above): more completions, never fewer.
+// tests/test_gpu_seg_ref_completed.py holds rules 2 and 1 to the dense form bit for bit on streams whose peaks are inter-sample values;
+// tools/seg_screen_model.py is the host model the rule was chosen with (completions 4.35 / 7.84 / 3.90 % -> 0.43 / 0.51 / 1.30 % of
+// the chunks on the bench's three signals, profiles/r28_kseg_ref_completed/).
 
 struct KCoef { v2f a0, a1, a2, b1, b2, c3, c4, eps; };
 struct KState { v2f z1, z2, z3, z4, sj; };
@@ -446,6 +475,29 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 #pragma unroll
 		for (int g = 0; g < 4; ++g) {
 			fl = fmaxf (fl, X[((0 * 4 + kg) * 4 + g) * 16 + cc]);         // column `lane` = block lane >> 4 (= kg), c = lane & 15
+			fr = fmaxf (fr, X[((1 * 4 + kg) * 4 + g) * 16 + cc]);
+		}
+		pkf = v2f{fmaxf (pkf.x, fl * scl.un), fmaxf (pkf.y, fr * scr.un)};
+		__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
+		__builtin_amdgcn_wave_barrier ();
+	};
+	// The peek of screen rule 2: flush_pm's exchange with pm left as it is, so that what the chunks completed so far have found
+	// reaches the owner's pkf, and with it the stream's reference, while the launch is still running (the stream reference, above).
+	// Every lane writes all eight of its words, so the owners read nothing an older exchange left there.
+	auto peek_pm = [&] () __attribute__ ((always_inline)) {
+		float* const X = reinterpret_cast<float*> (smem_ + XCHG);
+#pragma unroll
+		for (int b = 0; b < 4; ++b) {
+			X[((0 * 4 + b) * 4 + kg) * 16 + cc] = fmaxf (pm[b][0][0], pm[b][0][1]);
+			X[((1 * 4 + b) * 4 + kg) * 16 + cc] = fmaxf (pm[b][1][0], pm[b][1][1]);
+		}
+		__builtin_amdgcn_fence (__ATOMIC_RELEASE, "workgroup");
+		__builtin_amdgcn_wave_barrier ();
+		__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "workgroup");
+		float fl = 0.f, fr = 0.f;
+#pragma unroll
+		for (int g = 0; g < 4; ++g) {
+			fl = fmaxf (fl, X[((0 * 4 + kg) * 4 + g) * 16 + cc]);
 			fr = fmaxf (fr, X[((1 * 4 + kg) * 4 + g) * 16 + cc]);
 		}
 		pkf = v2f{fmaxf (pkf.x, fl * scl.un), fmaxf (pkf.y, fr * scr.un)};
@@ -781,6 +833,9 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 							if (msk[Ks] != 0) { fetch.template operator()<U> (B1, Ks); m16::block (A, B1, y0); fold (y0, Ks); ++n_fin; }
 						} (), ...);
 					} (std::make_integer_sequence<int, 8>{});
+					// rule 2: what the chunks completed so far have found goes into the owners' pkf now, and from there into the
+					// stream's reference at its next refresh (a launch argument, wave-uniform: no further instantiation)
+					if (a.screen == 2u) peek_pm ();
 				}
 			}
 			// the step's ring stores (slot U), then the next step's first operands, which read them (Bn of chunk 7 = B0 of the next step)

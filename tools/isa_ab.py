@@ -5,9 +5,14 @@ the VGPR / SGPR / scratch of the kernel metadata.  A kernel that gained a traili
 argument type became std::conditional<false, ...>) is matched with its dense instantiation.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++20 -Iinclude -Imeters.lv2_amd/csrc <the TU's flags from csrc/Makefile> -save-temps -c TU.hip
-    python3 tools/isa_ab.py old/mtr_seg-hip-amdgcn-amd-amdhsa-gfx950.s new/mtr_seg-hip-amdgcn-amd-amdhsa-gfx950.s
+    python3 tools/isa_ab.py old/mtr_seg-hip-amdgcn-amd-amdhsa-gfx950.s new/mtr_seg-hip-amdgcn-amd-amdhsa-gfx950.s [--hunks]
+
+--hunks: for every kernel that differs, also where: the two instruction streams with register numbers and label names taken out,
+aligned, and each stretch that was inserted, deleted or replaced with its position, its length and its opcodes by count — a change
+confined to a cold branch shows as a few long insertions, one per copy of the branch, and nothing else.
 """
 import collections
+import difflib
 import re
 import subprocess
 import sys
@@ -51,6 +56,30 @@ def resources(path):
     return res
 
 
+def stream(path):
+    """{kernel: [instruction lines, registers and labels anonymous]}"""
+    out, cur = {}, None
+    for l in open(path):
+        if re.match(r"^_Z\S+:", l):
+            cur = l.split(":")[0]; out[cur] = []; continue
+        s = l.strip()
+        if cur and s.startswith(".Lfunc_end"): cur = None; continue
+        if cur and s and not s.startswith((".", ";", "//")) and not s.endswith(":"):
+            s = re.sub(r"\s*;.*$", "", s)
+            s = re.sub(r"\.LBB\d+_\d+", "LBB", s)
+            s = re.sub(r"\b([vsa])\[\d+:\d+\]", r"\1[]", s)
+            out[cur].append(re.sub(r"\b([vsa])\d+\b", r"\1", s))
+    return out
+
+
+def hunks(a, b):
+    sm = difflib.SequenceMatcher(None, a, b, autojunk=False)
+    for tag, i1, i2, j1, j2 in sm.get_opcodes():
+        if tag == "equal": continue
+        ops = collections.Counter(["- " + x.split()[0] for x in a[i1:i2]] + ["+ " + x.split()[0] for x in b[j1:j2]])
+        print("     %-7s old[%d:%d] (%d)  new[%d:%d] (%d)  %s" % (tag, i1, i2, i2 - i1, j1, j2, j2 - j1, dict(ops)))
+
+
 def demangle(n):
     return subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip()
 
@@ -61,8 +90,9 @@ def dense_name(n):
     return re.sub(r"(, false>|<false>)\(", lambda m: ">(" if m.group(1) == ", false>" else "(", d)
 
 
-def main(old, new):
+def main(old, new, with_hunks=False):
     co, cn, ro, rn = census(old), census(new), resources(old), resources(new)
+    so, sn = (stream(old), stream(new)) if with_hunks else ({}, {})
     by_dense = {dense_name(k): k for k in cn}
     same_all = True
     for k in co:
@@ -72,9 +102,10 @@ def main(old, new):
         print("%-4s %-60s %s" % ("SAME" if same else "DIFF", re.sub(r"\(anonymous namespace\)::", "", demangle(k))[:60], ro.get(k)))
         if not same:
             print("     old", dict(co[k]), "\n     new", dict(cn.get(kn, {})), rn.get(kn))
+            if with_hunks and kn in sn: hunks(so[k], sn[kn])
     print("every kernel of the old build compiles to the same code" if same_all else "DIFFERENCES")
     return 0 if same_all else 1
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], "--hunks" in sys.argv[3:]))
