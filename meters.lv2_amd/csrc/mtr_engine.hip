@@ -300,8 +300,9 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	// (test knobs: the whole -m gpu suite and the fuzzers run green with MTR_TAIL_MODE=2 — every call of every test with its tail on the side stream)
 	if (const char* v = getenv ("MTR_TAIL_MODE")) { const int m = atoi (v); if (m >= 0 && m <= 2) e->tail_mode = m; }
 	// (test knob: 0 = k_seg's dense form, the screened ones' bit-for-bit yardstick; 1 = the screen without the peek, whose completed-chunk
-	// counts tests pin; 2 = the screen with the peek, the default — mtr_seg.hip: the stream reference)
-	if (const char* v = getenv ("MTR_SEG_SCREEN")) { const int m = atoi (v); e->seg_screen = m == 0 ? 0u : (m == 2 ? 2u : 1u); }
+	// counts tests pin; 2 = the screen with the peek — mtr_seg.hip: the stream reference; 3 = rule 2 with the lo words of
+	// the split built only where a chunk completes, the default — mtr_seg.hip: LAZY; calls with per-stream ends run form 2)
+	if (const char* v = getenv ("MTR_SEG_SCREEN")) { const int m = atoi (v); e->seg_screen = m == 0 ? 0u : (m == 2 ? 2u : (m == 3 ? 3u : 1u)); }
 	if (const char* v = getenv ("MTR_TAIL_DELAY_US")) e->tail_delay_us = (uint32_t) atoi (v);
 	if (const char* v = getenv ("MTR_TAIL_GATE_GRID")) e->tail_gate_grid = (uint32_t) atoi (v);   // (tools/r06_tail_probe.py: the experiment behind the default)
 	e->fragm = (uint32_t) ((int) cfg->sample_rate / 20);     // ebu_r128_proc.cc:170

@@ -83,7 +83,9 @@ typedef struct mtr_seg_args {
 	uint32_t        warm_steps;   /* K-filter warm-up in front of a segment that does not start the call: steps of 16 frames, multiple of 4 */
 	int64_t         p0_end;       /* phase 0 (|x[n - 24]|) of this call covers the frames below n_frames - 24: that frame, counted from the first tile */
 	uint32_t        screen;       /* 0: dense.  1: each 16-column chunk gets its first product and the other two only where they may reach the peak (bit for bit the dense peak).
-	                               * 2: the same, and a step that completes chunks hands their peaks to the stream's reference at once (the peek: fewer completions, the same bits) */
+	                               * 2: the same, and a step that completes chunks hands their peaks to the stream's reference at once (the peek: fewer completions, the same bits).
+	                               * 3: rule 2 without the lo halves of the f16 split in the step: a completing chunk builds them from the stream's samples (the lazy form:
+	                               *    the same chunks, the same bits; a call with `ends` runs form 2) */
 	uint32_t*       seg_stats;    /* screen: [2] chunks screened / completed (device counters), may be NULL */
 	float           a0, a1, a2, b1, b2, c3, c4;
 	float           gain_l, gain_r;

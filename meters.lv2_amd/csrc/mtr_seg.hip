@@ -129,7 +129,7 @@ constexpr float SCREEN_K_ABS = 0.0078125f;
 // A wave in the bench's shape (8 segments per stream) holds 8 streams; their quiet segments stop completing against their own
 // small records.  tests/test_gpu_seg_stream_reference.py holds the screened form to the dense one bit for bit.
 //
-// Completed interpolated peaks in the reference (a.screen == 2, the default; 1 is the rule without them).  pkf receives
+// Completed interpolated peaks in the reference (a.screen == 2 and 3 — the default, LAZY below; 1 is the rule without them).  pkf receives
 // interpolated values only in flush_pm, at a rescale and at the end of the launch, so under rule 1 R is in effect the stream's SAMPLE
 // peak: what completed chunks have found lives in pm, per accumulator lane (one column, four rows of the step), and every chunk
 // of the stream with a first product between the sample peak and the true peak found so far completes again, lane by lane, until
@@ -229,6 +229,15 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 	asm ("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lw) : "v"(hw), "v"(x1));
 }
 
+// The factor a rescale multiplies a lane's ring words with, and the multiplication itself (two f16 words of one 32-bit word):
+// `rescale` below and the lazy form's replay of it (LAZY: lazy_lo) share them, so that a word built late is the ring word bit for bit.
+typedef _Float16 seg_h2 __attribute__ ((ext_vector_type (2)));
+__device__ __forceinline__ _Float16 rescale_ratio (float sc_new, float sc_old) { return (_Float16) (sc_new / sc_old); }   // 1 or 2^-12 and below (0 under 2^-24)
+__device__ __forceinline__ uint32_t rescale_word (uint32_t w, seg_h2 r2)
+{
+	return __builtin_bit_cast (uint32_t, (seg_h2) (__builtin_bit_cast (seg_h2, w) * r2));
+}
+
 // ALIGNED: the tile (a 50 ms fragment) is a whole number of steps — 48, 96, 192, 32 kHz; otherwise (44.1, 88.2 kHz: 2205, 4410 frames)
 // the step in which a tile ends is followed by a second run of its recurrence, frame by frame from the state the step started with,
 // with the reference's end-of-fragment actions at the exact frame (every other step is the aligned kernel's code).
@@ -255,9 +264,15 @@ __device__ __forceinline__ void lo_second (uint32_t& lw, uint32_t hw, float x1)
 // that reaches further on a stream the call closes (E < n_frames) keeps its peak to itself, and the engine hands exactly those
 // segments' peaks to k_kwtp16_len (a.from_tile: from the first such segment's first tile, masked at E).  A stream the call does not
 // touch (E == 0) keeps its K-filter state.  The dense instantiation (LEN false) is the kernel's code as it always was.
-template <bool EBU, bool ALIGNED, bool SCREEN, bool LEN>
+//
+// LAZY (a.screen == 3, the default; SCREEN without LEN): the screened form without the lo words in its hot path.  Only a chunk that completes
+// and the launch's last, dense step read the lo halves of the split, 0.4 - 1.3 % of the chunks, so a step computes and stores
+// the hi words alone — no v_fma_mix, no LL / LR store, sixteen registers less — and a completing block builds its lo operands
+// on the spot, in the MFMA operand layout, from the stream's f32 samples (lazy_lo, below, with the reason it is exact).
+template <bool EBU, bool ALIGNED, bool SCREEN, bool LEN, bool LAZY = false>
 __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 {
+	static_assert (!LAZY || (SCREEN && !LEN), "the lazy form is a screened one, and calls with per-stream ends stay on form 2");
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem_[];
 	lds_u8* const smem = smem_;
 	const int lane = threadIdx.x;
@@ -379,6 +394,9 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	for (int sl = 0; sl < 4; ++sl) WS[sl] = WA + (((2 * sl) ^ (lane & 7)) * 16);
 
 	Scale scl, scr;
+	// LAZY: the scales' exponent fields, and those of the last four steps (byte k = the scale step j - 1 - k split its words in, as
+	// seen from step j's completions; pushed at the end of every step: one v_lshl_or_b32 per channel)
+	uint32_t sel_ = 0, ser_ = 0, shl_ = 0, shr_ = 0;
 	v2f pk0 = v2f{0.f, 0.f};                                           // phase 0: max |x[n - 24]|, exact
 	v2f pkf = v2f{0.f, 0.f};                                           // interpolated peaks that have left the scaled domain
 	float pm[4][2][2];                                                // running |max| of the accumulators, scaled, per block and channel: two
@@ -428,6 +446,24 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		*reinterpret_cast<uint4*> (w1 + 3 * ARRB) = uint4{lr[4], lr[5], lr[6], lr[7]};
 	};
 
+	// LAZY: the hi words alone (no lo word is built or stored outside lazy_lo)
+	auto split_store_hi = [&] (const v2f (&x)[R], int slot) __attribute__ ((always_inline)) {
+		const v2f sc = v2f{scl.sc, scr.sc};
+		uint32_t hl[R / 2], hr[R / 2];
+#pragma unroll
+		for (int i = 0; i < R / 2; ++i) {
+			const v2f u = x[2 * i] * sc, v = x[2 * i + 1] * sc;
+			hl[i] = m16::hi_pair (u.x, v.x);
+			hr[i] = m16::hi_pair (u.y, v.y);
+		}
+		lds_u8* const w0 = smem + WS[slot];
+		lds_u8* const w1 = smem + (WS[slot] ^ 16);
+		*reinterpret_cast<uint4*> (w0)        = uint4{hl[0], hl[1], hl[2], hl[3]};
+		*reinterpret_cast<uint4*> (w1)        = uint4{hl[4], hl[5], hl[6], hl[7]};
+		*reinterpret_cast<uint4*> (w0 + ARRB) = uint4{hr[0], hr[1], hr[2], hr[3]};
+		*reinterpret_cast<uint4*> (w1 + ARRB) = uint4{hr[4], hr[5], hr[6], hr[7]};
+	};
+
 	{
 		const v2f* const hst = reinterpret_cast<const v2f*> (a.hist) + (size_t) s * MTR_FIR_HALO;
 		v2f px[3][R];
@@ -446,7 +482,13 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			for (int n = 0; n < R; n += 2) { ml = max3abs (ml, px[k][n].x, px[k][n + 1].x); mr = max3abs (mr, px[k][n].y, px[k][n + 1].y); }
 		scl.set (ml); scr.set (mr);
 		rml = ml; rmr = mr;
+		if constexpr (LAZY) {
+			sel_ = __float_as_uint (scl.sc) >> 23; ser_ = __float_as_uint (scr.sc) >> 23;
+			shl_ = sel_ * 0x01010101u; shr_ = ser_ * 0x01010101u;
+			split_store_hi (px[0], 1); split_store_hi (px[1], 2); split_store_hi (px[2], 3);
+		} else {
 		split_store (px[0], 1); split_store (px[1], 2); split_store (px[2], 3);
+		}
 		if (F0 == 0) {
 			// phase 0 of the launch's first outputs is frames -24 .. -1: the history of a launch that starts the call, else the
 			// call's own frames in front of it (whose owner, the kernel of the call's head, stops 24 frames short of them)
@@ -514,20 +556,21 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		if (el) scl.set (ml);
 		if (er) scr.set (mr);
 		if (el || er) {
-			typedef _Float16 h2v __attribute__ ((ext_vector_type (2)));
-			const _Float16 rl = (_Float16) (scl.sc / ol), rr = (_Float16) (scr.sc / orr);      // 1 or 2^-12 and below (0 under 2^-24)
+			typedef seg_h2 h2v;
+			const _Float16 rl = rescale_ratio (scl.sc, ol), rr = rescale_ratio (scr.sc, orr);
+			if constexpr (LAZY) { sel_ = __float_as_uint (scl.sc) >> 23; ser_ = __float_as_uint (scr.sc) >> 23; }
 #pragma unroll 1
-			for (int arr = 0; arr < 4; ++arr) {
+			for (int arr = 0; arr < (LAZY ? 2 : 4); ++arr) {                 // (LAZY: the ring holds hi words only)
 				const _Float16 r = (arr & 1) ? rr : rl;
 				const h2v r2 = h2v{r, r};
 #pragma unroll 1
 				for (int i = 0; i < 8; ++i) {
 					uint4* const p = reinterpret_cast<uint4*> (smem + arr * ARRB + WA + 16 * i);
 					uint4 v = *p;
-					v.x = __builtin_bit_cast (uint32_t, (h2v) (__builtin_bit_cast (h2v, v.x) * r2));
-					v.y = __builtin_bit_cast (uint32_t, (h2v) (__builtin_bit_cast (h2v, v.y) * r2));
-					v.z = __builtin_bit_cast (uint32_t, (h2v) (__builtin_bit_cast (h2v, v.z) * r2));
-					v.w = __builtin_bit_cast (uint32_t, (h2v) (__builtin_bit_cast (h2v, v.w) * r2));
+					v.x = rescale_word (v.x, r2);
+					v.y = rescale_word (v.y, r2);
+					v.z = rescale_word (v.z, r2);
+					v.w = rescale_word (v.w, r2);
 					*p = v;
 				}
 			}
@@ -597,6 +640,145 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			fold_last (y0, bc);
 		}
 		fold_last (y1, 7);
+	};
+
+	// ---- LAZY: the lo operands of a completing block, built where they are needed -------------------------------------------
+	// Lane (c, kg) of block b multiplies window samples [8 kg, 8 kg + 8) and [32 + 8 kg, 32 + 8 kg + 8) of column 16 b + c (the two
+	// ds_read_b128 of `fetch`: B.l0, B.l1).  The window of the products that step jj completes is frames [F0 + 16 (jj - 4), F0 + 16 jj)
+	// of the column's lane: two 64-byte pieces of its stream per lane, for both channels.  Why the words are the eager form's bits:
+	//   1. A ring word is a pure function of its two samples and of the column's scales since.  The samples: the launch never
+	//      writes the buffer or a.hist, and `sample` below is the rule the ring was filled by — the prologue's (the call's own frames,
+	//      a.hist in front of them, +0 in front of that; frames below F0 are the previous segment's, read from the buffer) and, for the
+	//      launch's last step where tiles are unaligned, last_frames' (+0 behind a last segment's tile end, never read).  The scale: a
+	//      word of step m was split under the scale in force behind step m's head, S_m, by x * S_m -> v_cvt_pk_f16_f32 -> v_fma_mix —
+	//      the instructions used here, on the same f32 operands, so Inf and NaN samples give the same halves — and every rescale
+	//      since, at the heads of steps m + 1 .. jj, multiplied it in f16 by rescale_ratio (S_k, S_k-1) (1 where the channel kept
+	//      its scale: the identity on every f16 that is no NaN, and NaNs stay NaNs; 0 for a ratio under 2^-24, which makes an Inf
+	//      word a NaN — replayed like every other).  The owner keeps S_jj-4 .. S_jj-1 as bytes (shl_, shr_: pushed once per step) and
+	//      S_jj is its current scale; the prologue's words (steps -3 .. -1) were split under the first scale, which is what the bytes
+	//      start with.  A wave none of whose lanes changed a scale in those steps skips the replay (every factor is 1).
+	//   2. The votes read hi products, pm, eps and R, none of which a lo word reaches except through a completed chunk's values —
+	//      which are the eager ones by 1 — so the lazy form screens and completes the chunks form 2 does; pm, pkf and R evolve alike.
+	//   3. The hi operands still come from the ring, whose stores stay behind the completions.
+	// The column's parameters come from its owner lane 16 b + c by ds_bpermute.  NaN payloads may differ from the ring's where a
+	// factor of 1 was skipped or applied; no result depends on them (the folds drop NaNs).
+	// (the column's first frame as an offset into a.audio, not as a pointer: an integer made from a pointer would cost every load of
+	// the kernel its address space — flat loads, which the main loop would wait for with its LDS reads)
+	const int64_t coff = (int64_t) ((uint64_t) s * a.stride + a.head) + F0;
+	auto lazy_lo = [&]<bool FINAL> (int b, int jj, uint32_t (&lo)[2][2][4]) __attribute__ ((always_inline)) {
+		const int o = 16 * b + cc;
+		const uint64_t cpw = (uint64_t) coff;
+		const v2f* const xp = reinterpret_cast<const v2f*> (a.audio)
+			+ (int64_t) (((uint64_t) (uint32_t) __shfl ((int) (cpw >> 32), o) << 32) | (uint32_t) __shfl ((int) (uint32_t) cpw, o))
+			+ (int64_t) R * (jj - 4);                                       // the column's window
+		// frames of the owner's window in front of the call (its history or +0): 0 but in the first steps of a lane that starts the call
+		const int64_t fc0 = F0 + (int64_t) a.head + (int64_t) R * (jj - 4);
+		const int front_own = (int) min (max (-fc0, (int64_t) 0), (int64_t) 64);
+		const bool plain = __ballot (front_own != 0) == 0 && !(FINAL && cut);
+		const bool flat = __ballot (shl_ != sel_ * 0x01010101u || shr_ != ser_ * 0x01010101u) == 0;
+		const int qv = kg >> 1;
+		v2f xs[2][8];
+		if (__builtin_expect (plain, 1)) {
+#pragma unroll
+			for (int h = 0; h < 2; ++h) {
+				const float4_a8* const pp = reinterpret_cast<const float4_a8*> (xp + 32 * h + 8 * kg);
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const f4v_ v = pp[i];
+					xs[h][2 * i] = v2f{v.x, v.y}; xs[h][2 * i + 1] = v2f{v.z, v.w};
+				}
+			}
+		} else {
+			// sample (f), frame by frame: the prologue's rule and last_frames'
+			const int front = __shfl (front_own, o);
+			const v2f* const hs = reinterpret_cast<const v2f*> (a.hist) + (size_t) (uint32_t) __shfl ((int) s, o) * MTR_FIR_HALO;
+			const bool clast = __shfl ((int) lastq, o) != 0;
+#pragma unroll
+			for (int h = 0; h < 2; ++h)
+#pragma unroll
+				for (int i = 0; i < 8; ++i) {
+					const int w = 32 * h + 8 * kg + i;
+					v2f v = v2f{0.f, 0.f};
+					if (w >= front) { if (!(FINAL && clast && w - 48 >= last_rows)) v = xp[w]; }
+					else if (w - front + MTR_FIR_HALO >= 0) v = hs[w - front + MTR_FIR_HALO];
+					xs[h][i] = v;
+				}
+		}
+		// the scales: e[i] = the exponent field of S_(jj - 4 + i)
+		const uint32_t hl_ = (uint32_t) __shfl ((int) shl_, o), hr_ = (uint32_t) __shfl ((int) shr_, o);
+		const uint32_t cl_ = (uint32_t) __shfl ((int) sel_, o), cr_ = (uint32_t) __shfl ((int) ser_, o);
+		float sl[5], sr[5];
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			sl[i] = __uint_as_float (((hl_ >> (8 * (3 - i))) & 255u) << 23);
+			sr[i] = __uint_as_float (((hr_ >> (8 * (3 - i))) & 255u) << 23);
+		}
+		sl[4] = __uint_as_float (cl_ << 23); sr[4] = __uint_as_float (cr_ << 23);
+		// piece h holds frames of step jj - 4 + 2 h + qv
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const v2f sc = v2f{qv ? sl[2 * h + 1] : sl[2 * h], qv ? sr[2 * h + 1] : sr[2 * h]};
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const v2f u = xs[h][2 * i] * sc, v = xs[h][2 * i + 1] * sc;
+				lo[0][h][i] = m16::lo_pair (m16::hi_pair (u.x, v.x), u.x, v.x);
+				lo[1][h][i] = m16::lo_pair (m16::hi_pair (u.y, v.y), u.y, v.y);
+			}
+		}
+		if (__builtin_expect (!flat, 0)) {
+			// the rescales at the heads of steps jj - 4 + i, i = 1 .. 4, in their order; a piece takes part in those behind its own step
+			const seg_h2 one = seg_h2{(_Float16) 1.0f, (_Float16) 1.0f};
+#pragma unroll
+			for (int i = 1; i <= 4; ++i) {
+				const _Float16 rl = rescale_ratio (sl[i], sl[i - 1]), rr = rescale_ratio (sr[i], sr[i - 1]);
+#pragma unroll
+				for (int h = 0; h < 2; ++h) {
+					if (i <= 2 * h) continue;                            // (piece 1: steps jj - 2 and jj - 1)
+					const bool in = i > 2 * h + qv;
+					const seg_h2 r2l = in ? seg_h2{rl, rl} : one, r2r = in ? seg_h2{rr, rr} : one;
+#pragma unroll
+					for (int k = 0; k < 4; ++k) { lo[0][h][k] = rescale_word (lo[0][h][k], r2l); lo[1][h][k] = rescale_word (lo[1][h][k], r2r); }
+				}
+			}
+		}
+	};
+	// ... and the completions of a step (fail8: bit bc = chunk bc completes) or, FINAL, of the launch's last, dense step: m16::block
+	// on the ring's hi words and the lo words built here, folded into pm as `fold` / `fold_last` do.  One loop over the blocks, not
+	// unrolled: every copy of the step carries one copy of this.
+	auto complete = [&]<int U, bool FINAL> (uint32_t fail8, int jj) __attribute__ ((always_inline)) {
+#pragma unroll 1
+		for (int b = 0; b < 4; ++b) {
+			const uint32_t f2 = (fail8 >> (2 * b)) & 3u;
+			if (f2 == 0) continue;
+			uint32_t lo[2][2][4];
+			lazy_lo.template operator()<FINAL> (b, jj, lo);
+			int rows = R;
+			if constexpr (FINAL && !ALIGNED) {
+				const uint32_t ucol = min (blockIdx.x * 64u + 16u * (uint32_t) b + (uint32_t) cc, n_units - 1);
+				rows = (ucol % a.n_segs == a.n_segs - 1) ? last_rows : R;
+			}
+#pragma unroll
+			for (int ch = 0; ch < 2; ++ch) {
+				if (!((f2 >> ch) & 1u)) continue;
+				const lds_u8* const h = smem + ch * ARRB + b * BLKB;
+				B1.h0 = *reinterpret_cast<const uint4*> (h + RA[U]);
+				B1.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
+				B1.l0 = uint4{lo[ch][0][0], lo[ch][0][1], lo[ch][0][2], lo[ch][0][3]};
+				B1.l1 = uint4{lo[ch][1][0], lo[ch][1][1], lo[ch][1][2], lo[ch][1][3]};
+				m16::block (A, B1, y0);
+				float ma = 0.f, mb = 0.f;
+#pragma unroll
+				for (int p = 0; p < 3; ++p) {
+					ma = max3abs (ma, 4 * kg + 0 < rows ? y0[p][0] : 0.f, 4 * kg + 1 < rows ? y0[p][1] : 0.f);
+					mb = max3abs (mb, 4 * kg + 2 < rows ? y0[p][2] : 0.f, 4 * kg + 3 < rows ? y0[p][3] : 0.f);
+				}
+				const float f = fmaxf (ma, mb);
+				// (the same maximum as fold's, whose chains start from pm: pm[..][1] is +0 in every screened form)
+#pragma unroll
+				for (int bb = 0; bb < 4; ++bb) pm[bb][ch][0] = bb == b ? fmaxf (pm[bb][ch][0], f) : pm[bb][ch][0];
+				++n_fin;
+			}
+		}
 	};
 
 	int tile_left = spt;
@@ -808,8 +990,33 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			kseq.template operator()<KGAP * BC + 5> ();
 			if constexpr (BC == 7) if (PROD) vote.template operator()<7> (yc);
 		};
+		// The lazy chunk: chunk_s without the lo words.  The shadows of MFMAs 4 and 5, which carried their first halves, take the
+		// next step's maxima, and nothing of the split is left to issue bare.
+		auto chunk_z = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
+			const v2f xa = x[2 * BC], xb = x[2 * BC + 1];
+			if (PROD && BC < 7) fetch_hi.template operator()<U> (Bn, BC + 1);
+#define MTR_M(I) if (PROD) m16::block_mfma<I> (A, Bc, yc)
+			MTR_M (0);  v2f um = xa * sc2;
+			MTR_M (1);  v2f vm = xb * sc2;
+			MTR_M (2);  hl[BC] = m16::hi_pair (um.x, vm.x);
+			MTR_M (3);  hr[BC] = m16::hi_pair (um.y, vm.y);
+			MTR_M (4);  nl = max3abs (nl, xn[2 * BC].x, xn[2 * BC + 1].x);
+			MTR_M (5);  nr = max3abs (nr, xn[2 * BC].y, xn[2 * BC + 1].y);
+#undef MTR_M
+			// (computed HERE, behind the six MFMAs: otherwise the compiler sinks them towards their uses)
+			asm volatile ("" : "+v"(hl[BC]), "+v"(hr[BC]), "+v"(nl), "+v"(nr));
+			if constexpr (BC > 0) if (PROD) vote.template operator()<BC - 1> (yp);
+			kseq.template operator()<KGAP * BC + 0> ();
+			kseq.template operator()<KGAP * BC + 1> ();
+			kseq.template operator()<KGAP * BC + 2> ();
+			kseq.template operator()<KGAP * BC + 3> ();
+			kseq.template operator()<KGAP * BC + 4> ();
+			kseq.template operator()<KGAP * BC + 5> ();
+			if constexpr (BC == 7) if (PROD) vote.template operator()<7> (yc);
+		};
 		auto any_chunk = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
-			if constexpr (SCREEN) chunk_s.template operator()<BC> (Bc, Bn, yc, yp);
+			if constexpr (LAZY) chunk_z.template operator()<BC> (Bc, Bn, yc, yp);
+			else if constexpr (SCREEN) chunk_s.template operator()<BC> (Bc, Bn, yc, yp);
 			else chunk.template operator()<BC> (Bc, Bn, yc, yp);
 		};
 		any_chunk.template operator()<0> (B0, B1, y0, y1);
@@ -828,6 +1035,14 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			if (PROD) {
 				n_scr += 8;
 				if (__builtin_expect ((msk[0] | msk[1] | msk[2] | msk[3] | msk[4] | msk[5] | msk[6] | msk[7]) != 0, 0)) {
+#if !(defined (MTR_TIMING_ONLY_BUILD) && defined (MTR_SEG_DBG_NOLO))    /* (elimination run of a timing-only library, wrong results: the lazy hot path, completions on stale lo words) */
+					if constexpr (LAZY) {
+						uint32_t fail8 = 0;
+#pragma unroll
+						for (int k = 0; k < 8; ++k) fail8 |= msk[k] != 0 ? 1u << k : 0u;
+						complete.template operator()<U, false> (fail8, j);
+					} else
+#endif
 					[&]<int... Ks> (std::integer_sequence<int, Ks...>) __attribute__ ((always_inline)) {
 						([&] () __attribute__ ((always_inline)) {
 							if (msk[Ks] != 0) { fetch.template operator()<U> (B1, Ks); m16::block (A, B1, y0); fold (y0, Ks); ++n_fin; }
@@ -835,7 +1050,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 					} (std::make_integer_sequence<int, 8>{});
 					// rule 2: what the chunks completed so far have found goes into the owners' pkf now, and from there into the
 					// stream's reference at its next refresh (a launch argument, wave-uniform: no further instantiation)
-					if (a.screen == 2u) peek_pm ();
+					if (LAZY || a.screen == 2u) peek_pm ();                       // (the lazy form is rule 2's)
 				}
 			}
 			// the step's ring stores (slot U), then the next step's first operands, which read them (Bn of chunk 7 = B0 of the next step)
@@ -845,10 +1060,14 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			*reinterpret_cast<uint4*> (w1)            = uint4{hl[4], hl[5], hl[6], hl[7]};
 			*reinterpret_cast<uint4*> (w0 + ARRB)     = uint4{hr[0], hr[1], hr[2], hr[3]};
 			*reinterpret_cast<uint4*> (w1 + ARRB)     = uint4{hr[4], hr[5], hr[6], hr[7]};
+			if constexpr (LAZY) {
+				shl_ = (shl_ << 8) | sel_; shr_ = (shr_ << 8) | ser_;        // the scale this step's words were split in
+			} else {
 			*reinterpret_cast<uint4*> (w0 + 2 * ARRB) = uint4{ll[0], ll[1], ll[2], ll[3]};
 			*reinterpret_cast<uint4*> (w1 + 2 * ARRB) = uint4{ll[4], ll[5], ll[6], ll[7]};
 			*reinterpret_cast<uint4*> (w0 + 3 * ARRB) = uint4{lr[0], lr[1], lr[2], lr[3]};
 			*reinterpret_cast<uint4*> (w1 + 3 * ARRB) = uint4{lr[4], lr[5], lr[6], lr[7]};
+			}
 			fetch_hi.template operator()<(U + 1) & 3> (B0, 0);
 		}
 		SPROF_NOW (c5_); SPROF_ADD (4, c5_ - c4_);
@@ -936,6 +1155,16 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	if (j < n_steps) do_step.template operator()<1, true> ();
 	if (j < n_steps) do_step.template operator()<2, true> ();
 	if (j < n_steps) do_step.template operator()<3, true> ();
+	if constexpr (LAZY) {
+		// the products of the last step: dense, so all four blocks build their lo words first (once per launch)
+		n_scr += 8;
+		switch (n_steps & 3) {
+		case 0:  complete.template operator()<0, true> (0xffu, j); break;
+		case 1:  complete.template operator()<1, true> (0xffu, j); break;
+		case 2:  complete.template operator()<2, true> (0xffu, j); break;
+		default: complete.template operator()<3, true> (0xffu, j); break;
+		}
+	} else
 	switch (n_steps & 3) {                                           // the products of the last step
 	case 0:  products.template operator()<0> (); break;
 	case 1:  products.template operator()<1> (); break;
@@ -976,7 +1205,18 @@ int mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* str
 {
 	hipStream_t st = (hipStream_t) stream;
 	const bool aligned = a.tile_frames % R == 0;
-	if (a.ends) {
+	if (a.screen == 3u && a.ends) {
+		// calls with per-stream ends stay on form 2: the LEN instantiations sit at their SGPR limit
+		mtr_seg_args a2 = a;
+		a2.screen = 2u;
+		return mtr_launch_seg (ebu, a2, n_waves, stream);
+	}
+	if (a.screen == 3u) {
+		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else              hipLaunchKernelGGL ((k_seg<true, false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+	} else if (a.ends) {
 		if (a.screen) {
 			if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
 			else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);

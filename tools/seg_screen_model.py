@@ -17,7 +17,11 @@ What it models, on bench.py's shape (10 s at 48 kHz, 8 segments per stream, EBU 
   * rule 1: pkf stays zero during the launch (it receives pm only at a flush).  Rule 2: a completed chunk's pm goes into
     the owners' pkf at once (the peek), and reaches R at its next refresh.  Rule 3 (not built): ... and R is refreshed at once.
 
-It prints the share of screened chunks that complete.  16 streams take about a second per signal and rule.  The model decides
+Per wave (k_seg's lazy form, MTR_SEG_SCREEN=3, pays per wave and step, not per chunk: a step of a wave with at least one completing
+chunk takes the cold branch and builds lo words there): a wave = 8 streams x 8 segments = 4 pairs of streams x 2 channels = 8
+chunks; wave_steps () counts the steps of the main loop in which a wave completes at least one chunk, and the chunks per such step.
+
+It prints the share of screened chunks that complete and, for rule 2, the per-wave figures.  16 streams take about a second per signal and rule.  The model decides
 no test of the kernel: tests/test_seg_screen_model_cpu.py holds rule 1 to the measured rates of
 profiles/r23_kseg_trim/completion_rates.txt."""
 import sys
@@ -96,8 +100,10 @@ def lanes(x, g):
     return ml, v, h
 
 
-def run(kind, streams, rule, g=None):
-    """(chunks screened, chunks completed) of `streams` streams (an even number) of signal `kind` under `rule`."""
+def run(kind, streams, rule, g=None, waves=None):
+    """(chunks screened, chunks completed) of `streams` streams (an even number) of signal `kind` under `rule`.  waves: a dict that
+    receives `steps` (wave-steps of the main loop), `cold` (those with at least one completing chunk) and `chunks` (completed there);
+    `streams` must then be a multiple of 8."""
     g = taps() if g is None else g
     per = [lanes(synth(kind, 777 + s), g) for s in range(streams)]
     ml = np.stack([p[0] for p in per])                           # [S, 2, 8, n]
@@ -111,6 +117,7 @@ def run(kind, streams, rule, g=None):
     pk0 = np.maximum(pk0, ml[:, :, :, 0]); M = np.maximum(M, ml[:, :, :, 0])     # step 0: no products in front of it
     R = np.maximum(pk0, pkf).max(2)
     done = 0
+    w_cold = w_chunks = 0
     for j in range(1, n):
         pk0 = np.maximum(pk0, ml[:, :, :, j]); M = np.maximum(M, ml[:, :, :, j])
         if j % 4 == 0 or rule == 3:
@@ -120,12 +127,24 @@ def run(kind, streams, rule, g=None):
         chunk = fail.reshape(S // 2, 2, 2, SEGS, 4).any(axis=(1, 3, 4))                    # [S / 2, 2]: pair of streams, channel
         if chunk.any():
             done += int(chunk.sum())
+            if waves is not None:
+                per_wave = chunk.reshape(S // 8, 8).sum(1)                                      # 4 pairs x 2 channels
+                w_cold += int((per_wave > 0).sum()); w_chunks += int(per_wave.sum())
             lane = np.repeat(chunk, 2, axis=0)[:, :, None, None]                            # back to [S, 2, 1, 1]
             pm = np.where(lane, np.maximum(pm, vj), pm)
             if rule >= 2:
                 pkf = np.where(lane[..., 0], np.maximum(pkf, pm.max(3)), pkf)
     done += S // 2 * 2                                           # the launch's last step runs dense
+    if waves is not None:
+        waves.update(steps=S // 8 * (n - 1), cold=w_cold, chunks=w_chunks)
     return S // 2 * 2 * n, done
+
+
+def wave_steps(kind, streams=16, rule=2, g=None):
+    """(share of a wave's steps with at least one completing chunk, chunks per such step): what the lazy form's cold path costs."""
+    w = {}
+    run(kind, streams, rule, g, waves=w)
+    return w["cold"] / w["steps"], w["chunks"] / max(w["cold"], 1)
 
 
 def main(argv):
@@ -136,6 +155,9 @@ def main(argv):
         for rule in (1, 2, 3):
             scr, fin = run(kind, streams, rule, g)
             print("signal %d rule %d: streams %d chunks screened %d completed %d rate %.4f" % (kind, rule, streams, scr, fin, fin / scr))
+        if streams % 8 == 0:
+            share, per = wave_steps(kind, streams, 2, g)
+            print("signal %d rule 2: a wave of 8 streams completes in %.4f of its steps, %.2f chunks per such step" % (kind, share, per))
 
 
 if __name__ == "__main__":
