@@ -116,8 +116,10 @@ typedef struct {
 	                          * data-dependent speed; off by default.  (Layout 7's k_seg screens its products with the first one
 	                          * regardless — the same bits, always on: MTR_SEG_SCREEN, read by mtr_engine_create, is the test knob:
 	                          * 0 forces its dense form, 1 the screen whose stream reference sees completed interpolated peaks only
-	                          * at a flush, 2 the screen that feeds them to the reference as they are found, 3 (the default) rule 2
-	                          * with the lo halves of the f16 split built only where a chunk completes (calls with per-stream ends: 2).)
+	                          * at a flush, 2 the screen that feeds them to the reference as they are found, 3 rule 2
+	                          * with the lo halves of the f16 split built only where a chunk completes, 4 (the default) form 3 with
+	                          * each chunk screened by the taps' 32-sample core: three MFMAs in place of six, a wider bound, more chunks
+	                          * completed, the same bits (calls with per-stream ends run 2 under 3 and 4).)
 	                          * 2 (layout 6) = the same, and inside a tile every 256-frame block is screened with the first of
 	                          * the three f16 products and completed only if it can still hold the maximum: also identical.
 	                          * (Pruning is a layout 6 feature: with tune_prune set, layout 7 is not used.) */
@@ -484,7 +486,7 @@ int  mtr_engine_timing_calls (mtr_engine* e, float* out, uint32_t cap, uint32_t*
 int  mtr_engine_prune_stats (mtr_engine* e, uint64_t* considered, uint64_t* skipped);
 /* Products screened with the first of the three f16 products / completed with the other two, since the engine was created:
  * with tune_prune = 2 (layout 6) 256-frame channel-blocks of k_kwtp16; in layout 7 also k_seg's 16-column chunks (screened
- * always, unless MTR_SEG_SCREEN=0; MTR_SEG_SCREEN=1 and 2 screen the same chunks and complete different numbers of them; 3, the default, completes exactly what 2 does).  Layout 6 engines without tune_prune = 2 count nothing. */
+ * always, unless MTR_SEG_SCREEN=0; MTR_SEG_SCREEN=1 and 2 screen the same chunks and complete different numbers of them; 3 completes exactly what 2 does; 4, the default, screens the same chunks with the taps' core and completes more of them).  Layout 6 engines without tune_prune = 2 count nothing. */
 int  mtr_engine_refine_stats (mtr_engine* e, uint64_t* screened, uint64_t* completed);
 /* The kernel layout the engine resolved to (tune_layout = 0 picks one from the meters mask): 3, 4, 6 or 7. */
 int  mtr_engine_layout (const mtr_engine* e);

@@ -93,8 +93,10 @@ static int upload_consts (mtr_engine* e)
 	HIPCHK (hipMemcpy (e->fir_g.p, g, sizeof (g), hipMemcpyHostToDevice));
 	{
 		// and as A fragments of the matrix-pipe interpolator
-		std::vector<uint16_t> a16 (MTR_M16_A_HALVES);
+		// (behind the twelve: the three core fragments of k_seg's core screen, which alone reads them)
+		std::vector<uint16_t> a16 (MTR_M16_A_HALVES + MTR_M16_CORE_HALVES);
 		mtr_m16_build_a (&g[0][0], a16.data ());
+		mtr_m16_build_core (&g[0][0], a16.data () + MTR_M16_A_HALVES);
 		if (e->m16_a.reserve (a16.size ())) return fail (MTR_ERR_NOMEM, "hipMalloc m16_a");
 		HIPCHK (hipMemcpy (e->m16_a.p, a16.data (), a16.size () * sizeof (uint16_t), hipMemcpyHostToDevice));
 	}
@@ -223,6 +225,20 @@ int mtr_fir_table (float* out120)
 	return MTR_OK;
 }
 
+// (for tests/test_seg_core_bound.py, which pins the core fragments k_seg's core screen multiplies with to its own rebuild of them
+// from mtr_fir_table: what mtr_m16_build_core makes of the engine's taps, [3][64][8] f16 bit patterns; not part of the ABI header)
+extern "C" int mtr_debug_m16_core (uint16_t* out1536)
+{
+	if (!out1536) return fail (MTR_ERR_ARG, "mtr_debug_m16_core");
+	float tab[120], g[3][48];
+	mtr_setup_fir_table (tab);
+	for (int ph = 1; ph <= 3; ++ph)
+		for (int i = 0; i < 48; ++i)
+			g[ph - 1][i] = (i < 24) ? tab[24 * ph + i] : tab[24 * (4 - ph) + (47 - i)];
+	mtr_m16_build_core (&g[0][0], out1536);
+	return MTR_OK;
+}
+
 int mtr_band_coef (double rate, uint32_t band, double* out36)
 {
 	if (!out36 || band >= MTR_NBANDS || !(rate > 0)) return fail (MTR_ERR_ARG, "mtr_band_coef");
@@ -301,8 +317,9 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	if (const char* v = getenv ("MTR_TAIL_MODE")) { const int m = atoi (v); if (m >= 0 && m <= 2) e->tail_mode = m; }
 	// (test knob: 0 = k_seg's dense form, the screened ones' bit-for-bit yardstick; 1 = the screen without the peek, whose completed-chunk
 	// counts tests pin; 2 = the screen with the peek — mtr_seg.hip: the stream reference; 3 = rule 2 with the lo words of
-	// the split built only where a chunk completes, the default — mtr_seg.hip: LAZY; calls with per-stream ends run form 2)
-	if (const char* v = getenv ("MTR_SEG_SCREEN")) { const int m = atoi (v); e->seg_screen = m == 0 ? 0u : (m == 2 ? 2u : (m == 3 ? 3u : 1u)); }
+	// the split built only where a chunk completes — mtr_seg.hip: LAZY; 4 = form 3 screening with the taps' 32-sample core, three
+	// MFMAs per chunk, the default — mtr_seg.hip: CORE; calls with per-stream ends run form 2)
+	if (const char* v = getenv ("MTR_SEG_SCREEN")) { const int m = atoi (v); e->seg_screen = m == 0 ? 0u : (m == 2 ? 2u : (m == 3 ? 3u : (m == 4 ? 4u : 1u))); }
 	if (const char* v = getenv ("MTR_TAIL_DELAY_US")) e->tail_delay_us = (uint32_t) atoi (v);
 	if (const char* v = getenv ("MTR_TAIL_GATE_GRID")) e->tail_gate_grid = (uint32_t) atoi (v);   // (tools/r06_tail_probe.py: the experiment behind the default)
 	e->fragm = (uint32_t) ((int) cfg->sample_rate / 20);     // ebu_r128_proc.cc:170

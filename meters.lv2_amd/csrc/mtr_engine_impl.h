@@ -156,10 +156,11 @@ struct mtr_engine {
 	DevBuf<uint32_t> prune_cnt;     // [4] interpolator tile passes considered / skipped, channel-blocks screened / completed
 	uint64_t         prune_tot[4] = { 0, 0, 0, 0 };
 	float            tpb_w[4];      // w1 w2 w3 g of TruePeakdsp::init
-	uint32_t         seg_screen = 3;         // k_seg's products screened by the first of the three (mtr_seg.hip: SCREEN): 0 = the dense form, 1 = screened, the stream
+	uint32_t         seg_screen = 4;         // k_seg's products screened by the first of the three (mtr_seg.hip: SCREEN): 0 = the dense form, 1 = screened, the stream
 	                                         // reference fed by sample peaks until a flush, 2 = screened, completed interpolated peaks fed into it as they are found
 	                                         // (the peek), 3 = rule 2 with the lo words of the split built only where a chunk completes
-	                                         // (the lazy form, the default; calls with per-stream ends run 2).  MTR_SEG_SCREEN=0 / 1 / 2 / 3 selects one
+	                                         // (the lazy form; calls with per-stream ends run 2), 4 = form 3 with each chunk screened by the taps' 32-sample
+	                                         // core, three MFMAs in place of six (the core form, the default; ends: 2).  MTR_SEG_SCREEN=0 .. 4 selects one
 	uint32_t         last_n_frag = 0;
 	// Per-stream lengths: frames metered per stream since create / reset, and which streams a call with lengths has closed (a closed
 	// stream is left untouched by every later call until mtr_engine_reset; neither is part of the state blob).

@@ -77,7 +77,7 @@ typedef struct mtr_seg_args {
 	uint32_t        tile0;        /* ... and how many tiles of the plan they are: tile_power index of the launch's first tile */
 	mtr_stream_state* state;      /* [S] */
 	float*          tile_power;   /* [S][n_tiles] */
-	const uint16_t* mfma_a;       /* [12][64][8] hi / lo A fragments (mtr_mfma16_fir.h) */
+	const uint16_t* mfma_a;       /* [12][64][8] hi / lo A fragments and, behind them, the [3][64][8] core fragments (mtr_mfma16_fir.h) */
 	uint32_t        n_streams, n_segs, n_tiles, tile_frames;
 	uint32_t        seg_base, seg_rem, n_main;
 	uint32_t        warm_steps;   /* K-filter warm-up in front of a segment that does not start the call: steps of 16 frames, multiple of 4 */
@@ -85,7 +85,9 @@ typedef struct mtr_seg_args {
 	uint32_t        screen;       /* 0: dense.  1: each 16-column chunk gets its first product and the other two only where they may reach the peak (bit for bit the dense peak).
 	                               * 2: the same, and a step that completes chunks hands their peaks to the stream's reference at once (the peek: fewer completions, the same bits).
 	                               * 3: rule 2 without the lo halves of the f16 split in the step: a completing chunk builds them from the stream's samples (the lazy form:
-	                               *    the same chunks, the same bits; a call with `ends` runs form 2) */
+	                               *    the same chunks, the same bits; a call with `ends` runs form 2)
+	                               * 4: form 3 with the screen's product cut to the taps' 32-sample core: three MFMAs per chunk on the three fragments behind
+	                               *    mfma_a's twelve, a larger bound (the core form: more chunks complete, the same bits; a call with `ends` runs form 2) */
 	uint32_t*       seg_stats;    /* screen: [2] chunks screened / completed (device counters), may be NULL */
 	float           a0, a1, a2, b1, b2, c3, c4;
 	float           gain_l, gain_r;

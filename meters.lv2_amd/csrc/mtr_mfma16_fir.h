@@ -90,6 +90,26 @@ static inline void mtr_m16_build_a (const float* g /* [3][48] */, uint16_t* out 
 				}
 }
 
+/* The taps' 32-sample core, for k_seg's core screen (mtr_seg.hip: CORE): three fragments of hi halves alone, each one MFMA deep.
+ * The 48 rows (16 frames x 3 phases) in frame-major order, n = 3 f + p, fall into three groups of 16; fragment w holds rows
+ * 16 w .. 16 w + 15 over window positions [8 (w + 1), 8 (w + 1) + 32) — the 8-aligned stretch closest to the middle of those
+ * rows' taps.  out[w * 512 + lane * 8 + e] = Ghi of row n = 16 w + (lane & 15) at t = 8 (w + 1) + 8 (lane >> 4) + e, the halves
+ * mtr_m16_build_a gives A[m = f][t] of phase p; what a row keeps outside its stretch is dropped (the screen's bound pays for it). */
+#define MTR_M16_CORE_FRAGS  3
+#define MTR_M16_CORE_HALVES (MTR_M16_CORE_FRAGS * 64 * 8)
+static inline void mtr_m16_build_core (const float* g /* [3][48] */, uint16_t* out /* [MTR_M16_CORE_HALVES] */)
+{
+	for (int w = 0; w < MTR_M16_CORE_FRAGS; ++w)
+		for (int lane = 0; lane < 64; ++lane)
+			for (int e = 0; e < 8; ++e) {
+				const int n = 16 * w + (lane & 15), f = n / 3, p = n % 3;
+				const int t = 8 * (w + 1) + 8 * (lane >> 4) + e, i = t - 1 - f;
+				float h = (i >= 0 && i < 48) ? g[48 * p + i] : 0.f;
+				h *= (float) (1 << MTR_M16_TAP_SHIFT);                    /* exact */
+				out[w * 512 + lane * 8 + e] = mtr_f32_to_f16 (h);
+			}
+}
+
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 

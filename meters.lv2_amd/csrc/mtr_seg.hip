@@ -106,6 +106,37 @@ struct Scale {
 constexpr float SCREEN_K_REL = 56.0f;
 constexpr float SCREEN_K_ABS = 0.0078125f;
 
+// The core screen (CORE below, a.screen == 4): the screen's product is F' = sum over the row's CORE of Ghi Xhi — the taps of a row that
+// lie inside one 32-sample stretch of the window (mtr_mfma16_fir.h: mtr_m16_build_core; the interpolator is a windowed sinc, its mass
+// sits in the middle of the 48 taps) — one MFMA from a zero accumulator per row, and the bound is |Y - F'| <= eps' = CORE_K_REL * M +
+// CORE_K_ABS, with Y = m16::block's computed value on the same ring words and M as above.  F' is no prefix of the dense
+// accumulation any more, so the bound is built from the exact sums: with Ye = sum Ghi Xhi + sum Ghi Xlo + sum Glo Xhi and Fe = the
+// core's exact sum,  |Y - F'| <= |Y - Ye| + |Ye - Fe| + |Fe - F'|.
+//   * |Ye - Fe| is the exact rest, above: 52.53 M + 0.00503, plus the dropped taps' share of the first product: with LT = the largest
+//     row sum of |Ghi| outside the row's stretch, 854.62 in tap units (0.02608 of a full-scale sample; tests/test_seg_core_bound.py
+//     recomputes it from mtr_setup's table) and the bound on |Xhi| above,  LT ((1 + 2^-11) M + 2^-24) = 855.04 M + 0.000051.
+//   * |Y - Ye|: all SIX dense MFMAs round, each by at most 2^-17 (|C| + sum |products|) as above, and |C| + sum |products| <=
+//     (LH + LL) ((1 + 2^-11) M + 2^-24) + 52.6 M = 84262.1 M + 0.00502:  6 x 2^-17 x that = 3.858 M + 2.3e-7.
+//   * |Fe - F'|: an output lies in ONE of a chunk's three core MFMAs, which starts from zero over at most LH ((1 + 2^-11) M + 2^-24):
+//     2^-17 x that = 0.643 M + 4e-8.
+// In all 912.06 M + 0.00508, rounded up to 920 M + 2^-7 (0.87 % and 2^-7 - 0.0051: the f32 rounding of eps' itself, one fmaf and
+// the product M = rml * sc before it, is 2^-23 relative).  What was said of the screen and of its reference, re-read against F':
+//   * the per-word bounds hold for every ring word, fresh or rescaled, so they hold for the words under the dropped taps: a rescale
+//     inside a window changes nothing (M is in the column's current scale and bounds all 64 samples of the window).
+//   * Products of f16 are exact in f32 and none of their partial sums is subnormal, for 32 products as for 64.
+//   * NaN: a NaN word under a row's dropped taps leaves that row's F' finite where Y is NaN (every row of the dense product
+//     multiplies every word of the window, by a zero tap if by no other).  The dense fold drops that Y, so a pass loses nothing; a
+//     fail completes the chunk as the dense form computes it.  A NaN inside the stretch is dropped from the vote's maximum, as before.
+//   * Inf: an Inf sample makes M, and with it eps', Inf for the rest of the lane's segment — fl (c + eps') < pk is false whatever
+//     pk — so every chunk of a column that has seen one completes, as with eps; what F' holds does not matter.
+//   * R': fl (F' + eps') <= (LH + 920) 2^27 stays far below FLT_MAX, and >= eps' >= 2^-7, so the two remarks on an R' that
+//     overflows or is subnormal stand.  pm, pkf and R never receive F' — only completed chunks' dense values — so nothing else moves.
+// The vote does not care which rows a lane holds: lane (c, kg) votes with rows 16 w + 4 kg .. + 3 (w = 0..2) of column c against
+// pm of its own lane and R' of the column, both values the launch counts for the column's (stream, channel), and a chunk
+// completes where any lane of any of its columns fails.  The core form screens the chunks form 3 does and completes more of them.
+constexpr float CORE_K_REL = 920.0f;
+constexpr float CORE_K_ABS = 0.0078125f;
+
 // The screen's stream reference.  k_seg's result is the maximum per (stream, channel) of what its lanes count (tp_call, at the
 // end): a chunk none of whose outputs can exceed a value already counted for the same (stream, channel) cannot change it, even
 // where it would set a record of its own accumulator lane.  So the vote takes, besides the lane's own pm, R = the largest value
@@ -129,7 +160,7 @@ constexpr float SCREEN_K_ABS = 0.0078125f;
 // A wave in the bench's shape (8 segments per stream) holds 8 streams; their quiet segments stop completing against their own
 // small records.  tests/test_gpu_seg_stream_reference.py holds the screened form to the dense one bit for bit.
 //
-// Completed interpolated peaks in the reference (a.screen == 2 and 3 — the default, LAZY below; 1 is the rule without them).  pkf receives
+// Completed interpolated peaks in the reference (a.screen == 2, 3 and 4 — LAZY and CORE below, the latter the default; 1 is the rule without them).  pkf receives
 // interpolated values only in flush_pm, at a rescale and at the end of the launch, so under rule 1 R is in effect the stream's SAMPLE
 // peak: what completed chunks have found lives in pm, per accumulator lane (one column, four rows of the step), and every chunk
 // of the stream with a first product between the sample peak and the true peak found so far completes again, lane by lane, until
@@ -265,14 +296,22 @@ __device__ __forceinline__ uint32_t rescale_word (uint32_t w, seg_h2 r2)
 // segments' peaks to k_kwtp16_len (a.from_tile: from the first such segment's first tile, masked at E).  A stream the call does not
 // touch (E == 0) keeps its K-filter state.  The dense instantiation (LEN false) is the kernel's code as it always was.
 //
-// LAZY (a.screen == 3, the default; SCREEN without LEN): the screened form without the lo words in its hot path.  Only a chunk that completes
+// LAZY (a.screen == 3, and 4: CORE below; SCREEN without LEN): the screened form without the lo words in its hot path.  Only a chunk that completes
 // and the launch's last, dense step read the lo halves of the split, 0.4 - 1.3 % of the chunks, so a step computes and stores
 // the hi words alone — no v_fma_mix, no LL / LR store, sixteen registers less — and a completing block builds its lo operands
 // on the spot, in the MFMA operand layout, from the stream's f32 samples (lazy_lo, below, with the reason it is exact).
-template <bool EBU, bool ALIGNED, bool SCREEN, bool LEN, bool LAZY = false>
+//
+// CORE (a.screen == 4, the default; a LAZY form): a chunk's screen is three MFMAs, not six — the taps' 32-sample core, one MFMA per
+// 16 of the chunk's 48 rows, each from a zero accumulator and none waiting for another (the core screen, above: F' and eps').  Lane
+// (c, kg) multiplies the window's 16-byte chunks kg + 1, kg + 2 and kg + 3: the middle one is fetch_hi's address RA[(U + 1) & 3],
+// the two odd ones come from a second address array, RB.  Completions, the launch's last step, the ring, lazy_lo, peek_pm, rescale
+// and the scale history are the lazy form's, untouched: only what is multiplied for the vote, and the bound it is held against, differ.
+template <bool EBU, bool ALIGNED, bool SCREEN, bool LEN, bool LAZY = false, bool CORE = false>
 __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 {
 	static_assert (!LAZY || (SCREEN && !LEN), "the lazy form is a screened one, and calls with per-stream ends stay on form 2");
+	static_assert (!CORE || LAZY, "the core form is a lazy one");
+	constexpr float KREL = CORE ? CORE_K_REL : SCREEN_K_REL, KABS = CORE ? CORE_K_ABS : SCREEN_K_ABS;   // the vote's bound: eps or eps'
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem_[];
 	lds_u8* const smem = smem_;
 	const int lane = threadIdx.x;
@@ -360,6 +399,15 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	// parks some fragments in AGPRs anyway and copies one back per chunk: 32 v_accvgpr_read per step; measured -1.5 %)
 #pragma unroll
 	for (int f = 0; f < MTR_M16_FRAGS; ++f) asm volatile ("" : "+a"(A.a[f]));
+	// CORE: the three core fragments, which sit behind the twelve in the table, live there too
+	m16::h8 AC[MTR_M16_CORE_FRAGS];
+	if constexpr (CORE) {
+#pragma unroll
+		for (int w = 0; w < MTR_M16_CORE_FRAGS; ++w) {
+			AC[w] = *reinterpret_cast<const m16::h8*> (a.mfma_a + (MTR_M16_FRAGS + w) * 512 + lane * 8);
+			asm volatile ("" : "+a"(AC[w]));
+		}
+	}
 
 	// ---- K-filter warm-up of the segments that do not start the call (warm_steps is a multiple of 4) -------------------------
 	if (warm) {
@@ -388,6 +436,13 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 	int RA[4];                                                        // operand read address of window quarter v, this lane
 #pragma unroll
 	for (int v = 0; v < 4; ++v) RA[v] = cc * COLB + ((((kg & 1) + 2 * ((v + (kg >> 1)) & 3)) ^ (cc & 7)) * 16);
+	// CORE: ... and of the window's 16-byte chunk 2 v + kg + 1, the odd neighbours of the core's middle chunk (RA[v + 1] is chunk
+	// 2 v + kg + 2): the same swizzle, and a b128 lane group shares kg, so these reads are conflict-free as well
+	int RB[4];
+	if constexpr (CORE) {
+#pragma unroll
+		for (int v = 0; v < 4; ++v) RB[v] = cc * COLB + (((((kg + 1) & 1) + 2 * ((v + ((kg + 1) >> 1)) & 3)) ^ (cc & 7)) * 16);
+	}
 	const int WA = lane * COLB;                                       // this lane's column
 	int WS[4];                                                        // ... and where the first half of ring slot s sits in it (the second: ^ 16)
 #pragma unroll
@@ -599,6 +654,13 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 		const lds_u8* const h = smem + (bc & 1) * ARRB + (bc >> 1) * BLKB;
 		B.h0 = *reinterpret_cast<const uint4*> (h + RA[U]);
 		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 2) & 3]);
+	};
+	// CORE: the hi words under the three core fragments — window chunks kg + 1, kg + 2, kg + 3 — in B.h0, B.h1 and B.l0
+	auto fetch_core = [&]<int U> (m16::BFrag& B, int bc) __attribute__ ((always_inline)) {
+		const lds_u8* const h = smem + (bc & 1) * ARRB + (bc >> 1) * BLKB;
+		B.h0 = *reinterpret_cast<const uint4*> (h + RB[U]);
+		B.h1 = *reinterpret_cast<const uint4*> (h + RA[(U + 1) & 3]);
+		B.l0 = *reinterpret_cast<const uint4*> (h + RB[(U + 1) & 3]);
 	};
 	// |max| of the accumulators of (block, channel) bc into pm
 	auto fold = [&] (const m16::f4 (&y)[3], int bc) __attribute__ ((always_inline)) {
@@ -827,7 +889,8 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 				for (int p = 0; p < 3; ++p) y1[p] = m16::f4{0.f, 0.f, 0.f, 0.f};
 			}
 			rescale (ml, mr);
-			if constexpr (SCREEN) { if (PROD) fetch_hi.template operator()<U> (B0, 0); }
+			if constexpr (CORE) { if (PROD) fetch_core.template operator()<U> (B0, 0); }
+			else if constexpr (SCREEN) { if (PROD) fetch_hi.template operator()<U> (B0, 0); }
 			else if (PROD) fetch.template operator()<U> (B0, 0);          // (fetched before the ring was rescaled: again)
 		}
 
@@ -858,7 +921,7 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 				// (LEN: a column whose peak does not count passes the screen whatever its values — eps = -inf — so that the zeros
 				// behind a stream's end, which never pass it, do not complete every chunk of their waves)
 				*reinterpret_cast<float2*> (E + (cc * 4 + kg) * 2) = (LEN && !peak_ok) ? float2{-INFINITY, -INFINITY} :
-					float2{fmaf (SCREEN_K_REL, rml * scl.sc, SCREEN_K_ABS), fmaf (SCREEN_K_REL, rmr * scr.sc, SCREEN_K_ABS)};
+					float2{fmaf (KREL, rml * scl.sc, KABS), fmaf (KREL, rmr * scr.sc, KABS)};
 				float* const Q = reinterpret_cast<float*> (smem_ + XREF);
 				*reinterpret_cast<float2*> (Q + (cc * 4 + kg) * 2) =
 					float2{__uint_as_float (refl) * (scl.sc * 32768.f), __uint_as_float (refr) * (scr.sc * 32768.f)};
@@ -1014,8 +1077,37 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			kseq.template operator()<KGAP * BC + 5> ();
 			if constexpr (BC == 7) if (PROD) vote.template operator()<7> (yc);
 		};
+		// The core chunk: three MFMAs, each one row group's core product from zero — yc[w] = rows 16 w .. 16 w + 15, of which this lane
+		// holds 4 kg .. 4 kg + 3 — on the operands fetched a chunk ahead (three ds_read_b128).  Their shadows take the scale of the
+		// chunk's two frames (two full-rate instructions each) and one of its hi words (one half-rate instruction); the other hi
+		// word, the next step's maxima, the previous chunk's vote on its twelve values and six operations of the recurrence issue bare.
+		auto chunk_c = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
+			const v2f xa = x[2 * BC], xb = x[2 * BC + 1];
+			if (PROD && BC < 7) fetch_core.template operator()<U> (Bn, BC + 1);
+			const m16::f4 z4 = m16::f4{0.f, 0.f, 0.f, 0.f};
+			if (PROD) yc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16 (AC[0], __builtin_bit_cast (m16::h8, Bc.h0), z4, 0, 0, 0);
+			v2f um = xa * sc2;
+			if (PROD) yc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16 (AC[1], __builtin_bit_cast (m16::h8, Bc.h1), z4, 0, 0, 0);
+			v2f vm = xb * sc2;
+			if (PROD) yc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16 (AC[2], __builtin_bit_cast (m16::h8, Bc.l0), z4, 0, 0, 0);
+			hl[BC] = m16::hi_pair (um.x, vm.x);
+			// (computed HERE, behind the three MFMAs: otherwise the compiler sinks them towards their uses)
+			asm volatile ("" : "+v"(um), "+v"(vm), "+v"(hl[BC]));
+			hr[BC] = m16::hi_pair (um.y, vm.y);
+			nl = max3abs (nl, xn[2 * BC].x, xn[2 * BC + 1].x); nr = max3abs (nr, xn[2 * BC].y, xn[2 * BC + 1].y);
+			asm volatile ("" : "+v"(hr[BC]), "+v"(nl), "+v"(nr));
+			if constexpr (BC > 0) if (PROD) vote.template operator()<BC - 1> (yp);
+			kseq.template operator()<KGAP * BC + 0> ();
+			kseq.template operator()<KGAP * BC + 1> ();
+			kseq.template operator()<KGAP * BC + 2> ();
+			kseq.template operator()<KGAP * BC + 3> ();
+			kseq.template operator()<KGAP * BC + 4> ();
+			kseq.template operator()<KGAP * BC + 5> ();
+			if constexpr (BC == 7) if (PROD) vote.template operator()<7> (yc);
+		};
 		auto any_chunk = [&]<int BC> (m16::BFrag& Bc, m16::BFrag& Bn, m16::f4 (&yc)[3], m16::f4 (&yp)[3]) __attribute__ ((always_inline)) {
-			if constexpr (LAZY) chunk_z.template operator()<BC> (Bc, Bn, yc, yp);
+			if constexpr (CORE) chunk_c.template operator()<BC> (Bc, Bn, yc, yp);
+			else if constexpr (LAZY) chunk_z.template operator()<BC> (Bc, Bn, yc, yp);
 			else if constexpr (SCREEN) chunk_s.template operator()<BC> (Bc, Bn, yc, yp);
 			else chunk.template operator()<BC> (Bc, Bn, yc, yp);
 		};
@@ -1068,7 +1160,8 @@ __global__ __launch_bounds__ (64, 1) void k_seg (const mtr_seg_args a)
 			*reinterpret_cast<uint4*> (w0 + 3 * ARRB) = uint4{lr[0], lr[1], lr[2], lr[3]};
 			*reinterpret_cast<uint4*> (w1 + 3 * ARRB) = uint4{lr[4], lr[5], lr[6], lr[7]};
 			}
-			fetch_hi.template operator()<(U + 1) & 3> (B0, 0);
+			if constexpr (CORE) fetch_core.template operator()<(U + 1) & 3> (B0, 0);
+			else fetch_hi.template operator()<(U + 1) & 3> (B0, 0);
 		}
 		SPROF_NOW (c5_); SPROF_ADD (4, c5_ - c4_);
 		// the rest of the recurrence's sequence: one packed block (SCREEN: the ring stores and the fetch above drain under it)
@@ -1205,13 +1298,18 @@ int mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* str
 {
 	hipStream_t st = (hipStream_t) stream;
 	const bool aligned = a.tile_frames % R == 0;
-	if (a.screen == 3u && a.ends) {
+	if ((a.screen == 3u || a.screen == 4u) && a.ends) {
 		// calls with per-stream ends stay on form 2: the LEN instantiations sit at their SGPR limit
 		mtr_seg_args a2 = a;
 		a2.screen = 2u;
 		return mtr_launch_seg (ebu, a2, n_waves, stream);
 	}
-	if (a.screen == 3u) {
+	if (a.screen == 4u) {
+		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+		else              hipLaunchKernelGGL ((k_seg<true, false, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
+	} else if (a.screen == 3u) {
 		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
 		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
 		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);

@@ -1111,8 +1111,9 @@ class Engine:
         """(products screened with the first f16 product, completed with the other two): k_kwtp16's channel-blocks with
         tune_prune = 2, k_seg's 16-column chunks (layout 7, unless MTR_SEG_SCREEN=0; MTR_SEG_SCREEN=1 is the screen whose stream
         reference takes completed interpolated peaks only at a flush, 2 the one that takes them as they
-        are found: the same chunks screened, fewer completed, the same peaks; 3 — the default — is rule 2 with the lo halves
-        of the f16 split built only where a chunk completes: the counts of 2)"""
+        are found: the same chunks screened, fewer completed, the same peaks; 3 is rule 2 with the lo halves
+        of the f16 split built only where a chunk completes: the counts of 2; 4 — the default — is form 3 with each chunk screened by
+        the taps' 32-sample core, three MFMAs in place of six: the same chunks screened, more completed, the same peaks)"""
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib.mtr_engine_refine_stats(self._h, C.byref(a), C.byref(b)), "refine_stats")
         return a.value, b.value

@@ -16,6 +16,9 @@ What it models, on bench.py's shape (10 s at 48 kHz, 8 segments per stream, EBU 
     their values into pm; the launch's last step completes every chunk;
   * rule 1: pkf stays zero during the launch (it receives pm only at a flush).  Rule 2: a completed chunk's pm goes into
     the owners' pkf at once (the peek), and reaches R at its next refresh.  Rule 3 (not built): ... and R is refreshed at once.
+    Rule 4 (the core form, MTR_SEG_SCREEN=4): rule 2 with the vote on the core products themselves — each row's taps inside the
+    32-sample stretch of its fragment (core_matrix), twelve values per lane in the core's row layout (rows 16 w + 4 kg .. + 3) —
+    and eps' = 920 / 32768 M; completed chunks fold their exact outputs into pm as under every rule.
 
 Per wave (k_seg's lazy form, MTR_SEG_SCREEN=3, pays per wave and step, not per chunk: a step of a wave with at least one completing
 chunk takes the cold branch and builds lo words there): a wave = 8 streams x 8 segments = 4 pairs of streams x 2 channels = 8
@@ -30,6 +33,7 @@ import numpy as np
 
 FS, T, SEGS, STEP = 48000.0, 480000, 8, 16
 K_REL = 56.0 / 32768.0
+K_REL_CORE = 920.0 / 32768.0                                     # CORE_K_REL (mtr_seg.hip: the core screen)
 
 
 def lcg_noise(T, seed):
@@ -78,6 +82,33 @@ def taps():
     return g
 
 
+def core_matrix(g):
+    """[48, 64]: row n = 3 f + p of the frame-major list over the step's 64-sample window, its taps (A[f][t] = g_p[t - 1 - f]) kept
+    inside the stretch [8 (w + 1), 8 (w + 1) + 32) of its fragment w = n // 16 and zero outside (mtr_mfma16_fir.h: mtr_m16_build_core)."""
+    c = np.zeros((48, 64))
+    for n in range(48):
+        f, p, w = n // 3, n % 3, n // 16
+        for t in range(8 * (w + 1), 8 * (w + 1) + 32):
+            if 0 <= t - 1 - f < 48:
+                c[n, t] = g[p][t - 1 - f]
+    return c
+
+
+def core_lanes(x, g):
+    """For one stream x[T, 2]: per (channel, segment, step, kg) the max |F'| of the twelve core products lane (c, kg) votes with — rows
+    16 w + 4 kg .. + 3, w = 0 .. 2, of the step whose outputs are the step's frames [2, 8, n, 4]."""
+    seg = x.shape[0] // SEGS
+    n = seg // STEP
+    cm = core_matrix(g)
+    out = np.zeros((2, SEGS, n, 4))
+    for ch in range(2):
+        xp = np.concatenate([np.zeros(48), x[:, ch].astype(np.float64)])
+        win = np.lib.stride_tricks.sliding_window_view(xp, 64)[::STEP]          # window of step s: frames 16 s - 48 .. 16 s + 15
+        f = np.abs(win @ cm.T)                                                  # [steps, 48]
+        out[ch] = f.reshape(-1, 3, 4, 4).max(axis=(1, 3)).reshape(SEGS, n, 4)
+    return out
+
+
 def lanes(x, g):
     """For one stream x[T, 2]: per (channel, segment, step) the step's max |x| [2, 8, n] and per (channel, segment, step, row
     group) the max |Y| over 4 rows x 3 phases of the outputs whose windows end in the step's frames [2, 8, n, 4]; and the
@@ -105,9 +136,13 @@ def run(kind, streams, rule, g=None, waves=None):
     receives `steps` (wave-steps of the main loop), `cold` (those with at least one completing chunk) and `chunks` (completed there);
     `streams` must then be a multiple of 8."""
     g = taps() if g is None else g
-    per = [lanes(synth(kind, 777 + s), g) for s in range(streams)]
+    sigs = [synth(kind, 777 + s) for s in range(streams)]
+    per = [lanes(x, g) for x in sigs]
     ml = np.stack([p[0] for p in per])                           # [S, 2, 8, n]
     v = np.stack([p[1] for p in per])                            # [S, 2, 8, n, 4]
+    core = rule == 4
+    k_rel = K_REL_CORE if core else K_REL
+    vc = np.stack([core_lanes(x, g) for x in sigs]) if core else v   # what the vote sees: the truncated product itself under the core rule
     S, n = streams, ml.shape[3]
     M = np.stack([p[2] for p in per])                            # [S, 2, 8]
     pk0 = np.zeros((S, 2, SEGS))
@@ -123,7 +158,7 @@ def run(kind, streams, rule, g=None, waves=None):
         if j % 4 == 0 or rule == 3:
             R = np.maximum(pk0, pkf).max(2)
         vj = v[:, :, :, j - 1, :]
-        fail = vj + (K_REL * M)[..., None] >= np.maximum(pm, R[:, :, None, None])      # [S, 2, 8, 4]
+        fail = vc[:, :, :, j - 1, :] + (k_rel * M)[..., None] >= np.maximum(pm, R[:, :, None, None])      # [S, 2, 8, 4]
         chunk = fail.reshape(S // 2, 2, 2, SEGS, 4).any(axis=(1, 3, 4))                    # [S / 2, 2]: pair of streams, channel
         if chunk.any():
             done += int(chunk.sum())
@@ -152,12 +187,13 @@ def main(argv):
     kinds = [int(k) for k in argv[1:]] or [1, 0, 2]
     g = taps()
     for kind in kinds:
-        for rule in (1, 2, 3):
+        for rule in (1, 2, 3, 4):
             scr, fin = run(kind, streams, rule, g)
             print("signal %d rule %d: streams %d chunks screened %d completed %d rate %.4f" % (kind, rule, streams, scr, fin, fin / scr))
         if streams % 8 == 0:
-            share, per = wave_steps(kind, streams, 2, g)
-            print("signal %d rule 2: a wave of 8 streams completes in %.4f of its steps, %.2f chunks per such step" % (kind, share, per))
+            for rule in (2, 4):
+                share, per = wave_steps(kind, streams, rule, g)
+                print("signal %d rule %d: a wave of 8 streams completes in %.4f of its steps, %.2f chunks per such step" % (kind, rule, share, per))
 
 
 if __name__ == "__main__":
