@@ -372,6 +372,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The K-meter's reading series — (rms, peak) after every block of P frames: mtr_engine_kmeter_set_period / _period / _series */
 #include "mtr_kmeter.h"
 
+/* The reading series of MTR_METER_TPBALLIST — TruePeakdsp::read (m, p) after every block of P frames: mtr_engine_tpb_set_period /
+ * _period / _series */
+#include "mtr_tpb.h"
+
 /* Stcorrdsp for a batch (MTR_METER_STCORR): mtr_stcorr_coef and mtr_engine_stcorr_set_period / _read / _series / _reset */
 #include "mtr_stcorr.h"
 

@@ -410,14 +410,31 @@ struct CallRun {
 		return MTR_OK;
 	}
 
-	int tpb () const
+	int tpb ()
 	{
-		mtr_tpb_args ta;
+		mtr_tpb_series_args ta;
 		ta.audio = c.audio; ta.stride = c.stride; ta.n_frames = c.n_frames;
 		ta.hist = fir_hist (0); ta.mfma_a = e->m16_a.p; ta.state = e->state.p + c.off;
 		ta.n_streams = c.cnt; ta.n_channels = e->cfg.n_channels;
 		ta.w1 = e->tpb_w[0]; ta.w2 = e->tpb_w[1]; ta.w3 = e->tpb_w[2]; ta.g = e->tpb_w[3];
-		if (mtr_launch_tpb (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch");
+		const uint32_t P = e->tb.ser.period;
+		if (!P) {
+			if (mtr_launch_tpb (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch");
+			return MTR_OK;
+		}
+		// the reading series (mtr_tpb.h).  The blocks are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+		const SeriesPos& at = e->pos.tb;
+		const uint32_t cap = e->tb.ser.cap;
+		const size_t C = e->cfg.n_channels;
+		ta.period = P; ta.fill = (uint32_t) at.fill; ta.e0 = (uint32_t) series_e0 (at, P, c.n_frames);
+		ta.capacity = cap;
+		ta.point0 = at.points < cap ? (uint32_t) at.points : 0;
+		ta.room = at.points < cap ? cap - (uint32_t) at.points : 0;
+		ta.open = e->tb.open.p + c.off;
+		ta.s_level = cap ? e->tb.s_level.p + (size_t) c.off * cap * C : nullptr;
+		ta.s_peak = cap ? e->tb.s_peak.p + (size_t) c.off * cap * C : nullptr;
+		if (mtr_launch_tpb_series (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series)");
+		nx.tb = series_advance (at, P, c.n_frames);
 		return MTR_OK;
 	}
 

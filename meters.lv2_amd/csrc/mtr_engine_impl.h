@@ -1,6 +1,6 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
 // EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
-// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip, mtr_scope.hip), and mtr_loudlog.hip (the host
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip, mtr_scope.hip, mtr_tpb.hip), and mtr_loudlog.hip (the host
 // side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
 #ifndef MTR_ENGINE_IMPL_H
@@ -114,6 +114,7 @@ struct Cursors {
 	uint64_t sp_points = 0;       // ... and points completed since reset (what the rings do not hold of them is dropped)
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
+	SeriesPos tb;                 // TPBALLIST with a period: where its reading series stands (mtr_series.h)
 };
 
 // per-stream state of the side meters: defined where their kernels are
@@ -325,6 +326,11 @@ struct mtr_engine {
 		int                        mode = 0;
 		std::vector<uint64_t>      points;      // [S] periods each stream has completed (streams end at their own lengths)
 	} ll;
+	struct Tpb {                                // the reading series of TPBALLIST (mtr_tpb.hip; the meter's states are the stream state's)
+		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
+		DevBuf<mtr_tpb_open>       open;        // [S] the blob's header and the open block's maxima per channel
+		DevBuf<float>              s_level, s_peak;   // [S][cap][C]
+	} tb;
 };
 
 constexpr int EV_PER_CALL = 7;
@@ -421,11 +427,12 @@ struct SideMeter {
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
 extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
-                 bank_series_meter, scope_series_meter;
+                 bank_series_meter, scope_series_meter, tpb_series_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
                                                     &kmeter_series_meter,     // (KMETER's second row: nothing but the blob section of its open block, behind every older one)
                                                     &bank_series_meter,       // (SPECTR30's second row, likewise)
-                                                    &scope_series_meter };    // (SCOPE's second row, likewise)
+                                                    &scope_series_meter,      // (SCOPE's second row, likewise)
+                                                    &tpb_series_meter };      // (TPBALLIST, whose kernel the call launches itself: the series' reset and the open block's section)
 // the points of each of streams [first, first + count) in the series of the meter with `bit`, which the engine holds and which keeps such counts
 void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points);
 

@@ -231,6 +231,25 @@ int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mt
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
 int  mtr_launch_tpb (const mtr_tpb_args& a, void* stream);
+/* TPBALLIST with a period (mtr_tpb.h): per (stream, channel) the block that is open between two calls — the running maxima of
+ * truepeakdsp.cc:58-84; the states themselves stay in mtr_stream_state, raw.  In front, for the state blob: the engine's period and the
+ * frames into the open block (the host's copies rule, export writes them in) */
+struct mtr_tpb_open {
+	uint32_t period, fill;
+	float    zm[2], pk[2];        /* max (z1 + z2) and max |v| of the open block so far */
+};
+/* what the SERIES instantiations of k_tpb take beside the dense call's arguments (the dense ones' kernarg segment stays as it is) */
+struct mtr_tpb_series_args : mtr_tpb_args {
+	uint32_t        period;       /* P: 16 .. 8192 */
+	uint32_t        fill;         /* frames of the open block in front of the call: 0 = the call starts a block */
+	uint32_t        e0;           /* call frame at which the block open on entry ends: P - fill */
+	uint32_t        capacity;     /* points per stream the series hold */
+	uint32_t        point0, room; /* index of the call's first point; points the series still take, from that one on */
+	mtr_tpb_open*   open;         /* [S] */
+	float*          s_level;      /* [S][capacity][C], NULL if capacity == 0 */
+	float*          s_peak;
+};
+int  mtr_launch_tpb_series (const mtr_tpb_series_args& a, void* stream);
 /* ends != NULL: the LEN instantiation, stream s of the view ends at call frame ends[s] (0: untouched) */
 int  mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
                           uint32_t n_streams, const uint32_t* ends, void* stream);

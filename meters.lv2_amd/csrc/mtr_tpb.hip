@@ -43,6 +43,8 @@
 //     22.9 -> 17.9 - 19.3 ms per 8192 streams x 10 s across boxes (profiles/r05_tpb.md).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mtr_internal.h"
 #include "mtr_mfma16_fir.h"
 
@@ -117,6 +119,10 @@ constexpr int LDS_BYTES = RING_B + 2 * HRING_B + AUX_B + 2 * CBUF_B + STG_B;
 constexpr int NTHREADS = 64 * NW;
 static_assert (RING % 8 == 0 && (RSTRIDE * 4) % 16 == 0, "operand slices never wrap inside the ring");
 static_assert (LDS_BYTES <= 160 * 1024, "one workgroup per CU");
+constexpr int PKX_B = 2 * NCOL * 4;            // the SERIES instantiations: uint32_t pkx [parity][NCOL], a closed block's raw peak on its way from
+                                               // the products to the chains — behind everything the dense kernel has
+constexpr int LDS_BYTES_SERIES = LDS_BYTES + PKX_B;
+static_assert (LDS_BYTES_SERIES <= 160 * 1024, "one workgroup per CU");
 
 // Where piece q of a column sits in its 256 bytes of the f16 ring.  ds_read_b128 is served in the lane groups
 // {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, {32-35, 44-47, 52-59}, {36-43, 48-51, 60-63} (MI355X_MICROARCH.md, LDS), one cycle each
@@ -161,8 +167,20 @@ struct ColScale {
 	}
 };
 
-template <int C>   // channels: 2 = interleaved stereo (column = stream + 32 channel), 1 = mono (column = stream)
-__global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
+// SERIES (mtr_engine_tpb_set_period, P > 0; the dense instantiations are the kernel as it always was): the reading series.  Blocks of
+// exactly P frames end at call frames e0, e0 + P, ... whatever the call's length; all streams stand in lock step, so which chunk holds
+// a block end is uniform, and with P >= 16 a chunk holds one at most.  Such a chunk — the end behind its frame r - 1, 1 <= r <= 16 —
+// takes a cold path in the two roles that keep something per block:
+//   * the products split a lane's running peak there: the frames < r close the block — its peak goes, by atomicMax on the bits, into
+//     pkx [parity of the iteration][column] — and the frames >= r open the next;
+//   * the chains walk that chunk frame by frame (chain_cold: a rolled loop, the maps read as they are needed), and behind frame r - 1
+//     do what the reference does between two process () calls with a read () in between (block_end, truepeakdsp.cc:52-55, 86-89):
+//     the point (m g, p) is stored, z <- clamp (z + 1e-20f), m <- 0.  They read and clear the pkx entry the products wrote one
+//     iteration earlier, behind the barrier that already separates a chunk's maps from the chain that reads them.
+// Between two calls the states stay raw in mtr_stream_state and the open block's maxima in mtr_tpb_open; a call that starts a block
+// (fill == 0) clamps on entry, any other takes the open maxima up.  tpb_m / tpb_p are written where a block completes.
+template <int C, bool SERIES>   // channels: 2 = interleaved stereo (column = stream + 32 channel), 1 = mono (column = stream)
+__global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SERIES, mtr_tpb_series_args, mtr_tpb_args> a)
 {
 	constexpr int NSTR = NCOL / C;                                       // streams per workgroup
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem[];
@@ -191,9 +209,21 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 	const bool cowner = csl < a.n_streams;
 	mtr_stream_state* const cst = a.state + (cowner ? csl : 0);
 	float z = 0.f, zm = 0.f;
+	bool opens = true;                                                   // the call starts a block (the dense kernel: the call IS the block)
+	if constexpr (SERIES) opens = a.fill == 0;
 	if (wid < 2 && cowner) {
 		z = phi ? cst->tpb_z2[cch] : cst->tpb_z1[cch];
-		z = z > 20 ? 20 : (z < 0 ? 0 : z);                                 // truepeakdsp.cc:54-55
+		if (opens) z = z > 20 ? 20 : (z < 0 ? 0 : z);                      // truepeakdsp.cc:54-55
+	}
+	// SERIES: the block ends of the call, counted by every role that needs them for itself (next_end: the call frame at which the block
+	// that is open where the role stands ends); what the chain lanes carry of the open block beside z and zm — the raw peak the calls
+	// before gave it (pko) — and the points the call has completed (npt)
+	uint32_t* const pkx = reinterpret_cast<uint32_t*> (smem + LDS_BYTES);
+	int next_end = 0, npt = 0;
+	float pko = 0.f;
+	if constexpr (SERIES) {
+		next_end = (int) a.e0;
+		if (wid < 2 && cowner && !opens) { zm = a.open[csl].zm[cch]; pko = a.open[csl].pk[cch]; }
 	}
 	// slopes of the frame's two pair maps: w3, a w3, a^2 w3 (the release folded into the first one) | a, a^2
 	const float a1 = 1.0f - a.w1, a2 = 1.0f - a.w2;
@@ -451,6 +481,34 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 			mprev = mk;
 		}
 	};
+	// SERIES, a chunk that holds a block end: the same maps, and the lane's peak split there — its first rl frames (rl <= 0: none,
+	// >= 4: all four) and everything it has gathered since the block's start close the block, the rest open the next
+	auto unit_maps_cold = [&]<bool UB> (int par, const float4& x0, float un, const m16::f4 (&y)[2], int nfl, int rl) __attribute__ ((always_inline)) {
+		constexpr int NPH = UB ? 2 : 1;
+		const float xr[4] = { x0.x, x0.y, x0.z, x0.w };
+		const v2f W = v2f{a.w1, a.w2}, WA = v2f{a.w1 * a1, a.w2 * a2};
+		unsigned char* const row = cbuf + par * CBUF_B + ((UB ? F : 0) + 4 * kg) * CROW + blk * 256 + cc * 8;
+		float pnew = 0.f;
+#pragma unroll
+		for (int r = 0; r < 4; ++r) {
+			unsigned char* const cd = row + r * CROW;
+			const float va = UB ? fabsf (y[0][r]) * un : xr[r], vb = fabsf (y[NPH - 1][r]) * un;
+			const float mx = max_abs_plain (va, vb);
+			const v2f bb = W * vb;
+			float g1x, g1y, g2x, g2y;                                       // (instruction for instruction unit_maps': the same bits)
+			asm ("v_mul_f32 %0, %1, %2" : "=v"(g1x) : "v"(W.x), "v"(mx));
+			asm ("v_mul_f32 %0, %1, %2" : "=v"(g1y) : "v"(W.y), "v"(mx));
+			asm ("v_fma_f32 %0, %1, |%2|, %3" : "=v"(g2x) : "v"(WA.x), "v"(va), "v"(bb.x));
+			asm ("v_fma_f32 %0, %1, |%2|, %3" : "=v"(g2y) : "v"(WA.y), "v"(va), "v"(bb.y));
+			*reinterpret_cast<v2f*> (cd) = v2f{g1x, g2x};
+			*reinterpret_cast<v2f*> (cd + 128) = v2f{g1y, g2y};
+			const float mk = mx * (r < nfl ? 1.f : 0.f);
+			if (r < rl) pk = max3_plain (pk, mk, mk);
+			else pnew = max3_plain (pnew, mk, mk);
+		}
+		atomicMax (&pkx[par * NCOL + ucol], __float_as_uint (pk));
+		pk = pnew;
+	};
 
 	// ---- prologue: the 48 frames before the call (47 of history; frame -48 is never multiplied by a non-zero tap), chunks 0 and 1 ----
 	for (int e = threadIdx.x; e < NCOL * 48; e += NTHREADS) {
@@ -462,6 +520,7 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 		ring[col * RSTRIDE + i] = x;
 	}
 	if (threadIdx.x < 2) flag_sh[threadIdx.x] = 0;
+	if constexpr (SERIES) { if (threadIdx.x < 2 * NCOL) pkx[threadIdx.x] = 0u; }
 	float xc0[8], xc1[8];
 	if (wid == 2 || wid == 3) { take_ragged (0, xc0); take_ragged (1, xc1); }
 	__syncthreads ();
@@ -537,6 +596,49 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 	};
 #undef TPB_RD
 #undef TPB_WAIT8
+	// SERIES.  A block ends behind the frame the chain has just walked: read (m, p) — the level m g from the lane of filter 1, the raw
+	// peak from what the products left in pkx [PARITY] an iteration ago (taken and cleared) and what the calls before gave the block —
+	// as the series' next point (if it has room) and as what mtr_engine_results reports; then the states as the next process () finds
+	// them, + 1e-20f (truepeakdsp.cc:86-87) and clamped (:54-55), and the maxima from zero (:133-138)
+	auto block_end = [&]<int PARITY> () __attribute__ ((always_inline)) {
+		if constexpr (SERIES) {
+			if (phi == 0) {
+				const uint32_t pb = pkx[PARITY * NCOL + ccol];
+				pkx[PARITY * NCOL + ccol] = 0u;
+				if (cowner) {
+					const float m = zm * a.g, p = __builtin_fmaxf (__uint_as_float (pb), pko);
+					cst->tpb_m[cch] = m;
+					cst->tpb_p[cch] = p;
+					if ((uint32_t) npt < a.room) {
+						const size_t o = ((size_t) csl * a.capacity + a.point0 + (uint32_t) npt) * C + cch;
+						a.s_level[o] = m;
+						a.s_peak[o] = p;
+					}
+				}
+			}
+			z += 1e-20f;
+			z = z > 20 ? 20 : (z < 0 ? 0 : z);
+			zm = 0.f; pko = 0.f;
+			++npt;
+		}
+	};
+	// ... and the chunk that holds the end, behind its frame r - 1: frame by frame, each frame's maps read where it needs them (a
+	// rolled loop: one chunk in P / 16 comes here), the arithmetic of `chain` operation for operation
+	auto chain_cold = [&]<int PARITY> (int nf, int r) __attribute__ ((always_inline)) {
+		const unsigned char* const src = cbuf + PARITY * CBUF_B + (2 * hw_ + (ci >> 4)) * 256 + phi * 128 + (ci & 15) * 8;
+#pragma unroll 1
+		for (int f = 0; f < nf; ++f) {
+			const v2f q1 = *reinterpret_cast<const v2f*> (src + f * CROW), q2 = *reinterpret_cast<const v2f*> (src + (F + f) * CROW);
+			const float u0 = sl0 * z;
+			const v2f u12 = __builtin_elementwise_fma (SL12, v2f{z, z}, q1);
+			const float zh = max3f (u0, u12.x, u12.y);
+			const v2f v12 = __builtin_elementwise_fma (AP12, v2f{zh, zh}, q2);
+			z = max3f (zh, v12.x, v12.y);
+			const float zo = __uint_as_float (__builtin_amdgcn_update_dpp (0, __float_as_uint (z), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+			zm = __builtin_fmaxf (zm, z + zo);
+			if (f + 1 == r) block_end.template operator()<PARITY> ();
+		}
+	};
 	// THE LOOP, once per role: every wave runs the same iterations and the same barriers, but each role's copy of the loop has
 	// its own registers (in ONE loop with the roles as branches the compiler re-fetched the products' twelve tap fragments from
 	// global memory in every iteration).
@@ -590,7 +692,14 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 		run ([&]<int PAR, int> (int t, auto&& moved) __attribute__ ((always_inline)) {
 			if (t >= 1 && !MTR_TPB_DBG_NOCHAIN) {
 				const int left = n_frames - (t - 1) * F;
-				if (left >= F) chain.template operator()<true, PAR ^ 1> (F);
+				bool cold = false;
+				if constexpr (SERIES) {                                          // a block ends inside chunk t - 1, behind its frame r - 1
+					const int nf = left >= F ? F : left, r = next_end - (t - 1) * F;
+					cold = __builtin_expect (r <= nf, 0);
+					if (cold) { chain_cold.template operator()<PAR ^ 1> (nf, r); next_end += (int) a.period; }
+				}
+				if (cold) {}
+				else if (left >= F) chain.template operator()<true, PAR ^ 1> (F);
 				else chain.template operator()<false, PAR ^ 1> ((int) left);
 			}
 			if (moved ()) __syncthreads ();
@@ -655,7 +764,18 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 					__builtin_amdgcn_sched_barrier (0);                            // (the wait for the flag stays BEHIND the MFMAs)
 					if (moved ()) __syncthreads ();
 					fetch_ops.template operator()<UB, (SW + 1) % NSLOT> (ops[PAR ^ 1]);
-					if ((t + 1) * F <= n_frames) unit_maps.template operator()<UB, true> (PAR, ops[PAR].x0, ops[PAR].un, y, 4);
+					bool cold = false;
+					if constexpr (SERIES) {                                        // a block ends inside chunk t, behind its frame r - 1
+						const int left_c = n_frames - t * F, r = next_end - t * F;
+						cold = __builtin_expect (r <= (left_c >= F ? F : left_c), 0);
+						if (cold) {
+							const int left = left_c - 4 * kg;
+							unit_maps_cold.template operator()<UB> (PAR, ops[PAR].x0, ops[PAR].un, y, left >= 4 ? 4 : (left > 0 ? left : 0), r - 4 * kg);
+							next_end += (int) a.period;
+						}
+					}
+					if (cold) {}
+					else if ((t + 1) * F <= n_frames) unit_maps.template operator()<UB, true> (PAR, ops[PAR].x0, ops[PAR].un, y, 4);
 					else {
 						const int left = n_frames - t * F - 4 * kg;           // this lane's frames are 4 kg .. 4 kg + 3 of the chunk
 						unit_maps.template operator()<UB, false> (PAR, ops[PAR].x0, ops[PAR].un, y, left >= 4 ? 4 : (left > 0 ? (int) left : 0));
@@ -677,6 +797,20 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const mtr_tpb_args a)
 	__syncthreads ();
 	if (prod_wave) atomicMax (&pk_sh[ucol], __float_as_uint (pk));
 	__syncthreads ();
+	if constexpr (SERIES) {
+		// the states raw — a block that ended with the call got its + 1e-20f in block_end — and the open block's maxima: what the products
+		// found in the call's frames behind its last block end, and in front of the call if it held none
+		if (wid < 2 && cowner) {
+			if (phi) cst->tpb_z2[cch] = z;
+			else {
+				cst->tpb_z1[cch] = z;
+				a.open[csl].zm[cch] = zm;
+				a.open[csl].pk[cch] = __builtin_fmaxf (__uint_as_float (pk_sh[ccol]), pko);
+				if (C == 1) { cst->tpb_z1[1] = 1e-20f; cst->tpb_z2[1] = 1e-20f; cst->tpb_m[1] = 0.f; cst->tpb_p[1] = 0.f; a.open[csl].zm[1] = 0.f; a.open[csl].pk[1] = 0.f; }
+			}
+		}
+		return;
+	}
 	if (wid < 2 && cowner) {
 		if (phi) cst->tpb_z2[cch] = z + 1e-20f;                            // truepeakdsp.cc:86-87
 		else {
@@ -708,15 +842,36 @@ int mtr_launch_tpb (const mtr_tpb_args& a, void* stream)
 	if (a.n_frames >= 0x7ffff000ull) return -1;                        // (the kernel counts frames and chunks in 32 bits, a few chunks ahead)
 	static bool raised = false;
 	if (!raised) {
-		(void) hipFuncSetAttribute ((const void*) k_tpb<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-		(void) hipFuncSetAttribute ((const void*) k_tpb<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+		(void) hipFuncSetAttribute ((const void*) k_tpb<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+		(void) hipFuncSetAttribute ((const void*) k_tpb<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 		raised = true;
 	}
 	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
 	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
 	hipStream_t st = (hipStream_t) stream;
-	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2>), grid, dim3 (NTHREADS), LDS_BYTES, st, a);
-	else                   hipLaunchKernelGGL ((k_tpb<1>), grid, dim3 (NTHREADS), LDS_BYTES, st, a);
+	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, false>), grid, dim3 (NTHREADS), LDS_BYTES, st, a);
+	else                   hipLaunchKernelGGL ((k_tpb<1, false>), grid, dim3 (NTHREADS), LDS_BYTES, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// P > 0: the SERIES instantiations.  What the kernel relies on is refused here: a period outside 16 .. 8192, an open block that is not
+// shorter than the period, series without their memory
+int mtr_launch_tpb_series (const mtr_tpb_series_args& a, void* stream)
+{
+	if (a.n_frames >= 0x7ffff000ull) return -1;
+	if (a.period < (uint32_t) F || a.period > 8192u || a.fill >= a.period || a.e0 != a.period - a.fill || !a.open) return -1;
+	if (a.room && (!a.s_level || !a.s_peak || a.point0 >= a.capacity || a.room > a.capacity - a.point0)) return -1;
+	static bool raised = false;
+	if (!raised) {
+		(void) hipFuncSetAttribute ((const void*) k_tpb<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_SERIES);
+		(void) hipFuncSetAttribute ((const void*) k_tpb<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_SERIES);
+		raised = true;
+	}
+	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
+	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
+	hipStream_t st = (hipStream_t) stream;
+	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, true>), grid, dim3 (NTHREADS), LDS_BYTES_SERIES, st, a);
+	else                   hipLaunchKernelGGL ((k_tpb<1, true>), grid, dim3 (NTHREADS), LDS_BYTES_SERIES, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -728,3 +883,110 @@ int mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_fra
 	                    audio, stride, n_frames, hist_in, hist_out, n_streams);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+
+// ---- TPBALLIST's reading series in the engine: the blob's section, reset, the entry points of mtr_tpb.h -------------------------------
+// (the call's step is CallRun::tpb, mtr_call.hip; tools/tpb_prof.hip builds the kernels alone)
+#ifndef MTR_TPB_PROF
+#include <cstddef>
+#include <cstring>
+
+#include "mtr_engine_impl.h"
+
+constexpr uint32_t TPB_MIN_PERIOD = F;         // the kernel's chunk: at most one block end in any of them
+constexpr uint32_t TPB_MAX_PERIOD = 8192;      // truepeakdsp.cc:44: a block is one process ()
+
+// With a period the blob carries one more section, behind every older one: the open block.  Its header: period, the frames into the
+// open block.  An engine takes a blob of its own period only
+static void tpb_open_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	if (e->tb.ser.period) v.push_back ({ e->tb.open.p, sizeof (mtr_tpb_open) });
+}
+
+constexpr size_t TPB_HDR_BYTES = offsetof (mtr_tpb_open, zm);
+constexpr const char* TPB_CORRUPT = "mtr_engine_state_import: corrupt blob (period of the TPBALLIST series)";
+
+static void tpb_hdr_write (const mtr_engine* e, void* out)
+{
+	mtr_tpb_open h;
+	memset (&h, 0, TPB_HDR_BYTES);
+	h.period = e->tb.ser.period; h.fill = (uint32_t) e->pos.tb.fill;
+	memcpy (out, &h, TPB_HDR_BYTES);
+}
+
+static int tpb_hdr_check (const mtr_engine* e, const void* in, bool fresh)
+{
+	mtr_tpb_open h;
+	memcpy (&h, in, TPB_HDR_BYTES);
+	if (!h.period || !series_blob_ok (h.period, h.fill, TPB_MIN_PERIOD, TPB_MAX_PERIOD)) return fail (MTR_ERR_STATE, TPB_CORRUPT);
+	if (h.period != e->tb.ser.period || (!fresh && h.fill != e->pos.tb.fill))
+		return fail (MTR_ERR_STATE, "mtr_engine_state_import: the engine does not stand where the blob's streams do (period of the TPBALLIST series)");
+	return MTR_OK;
+}
+
+static void tpb_hdr_take (mtr_engine* e, const void* in)
+{
+	mtr_tpb_open h;
+	memcpy (&h, in, TPB_HDR_BYTES);
+	e->pos.tb.fill = h.fill;
+}
+
+// the series emptied, the open block gone, P kept (the states and tpb_m / tpb_p are the stream state's: mtr_engine_reset zeroes them)
+static int tpb_series_reset (mtr_engine* e)
+{
+	e->pos.tb = {};
+	if (!e->tb.open.n && !e->tb.s_level.n && !e->tb.s_peak.n) return MTR_OK;
+	e->snap_valid = false;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	hipStream_t st = e->last_stream;
+	if (e->tb.open.n) HIPCHK (hipMemsetAsync (e->tb.open.p, 0, e->tb.open.n * sizeof (mtr_tpb_open), st));
+	if (e->tb.s_level.n) HIPCHK (hipMemsetAsync (e->tb.s_level.p, 0, e->tb.s_level.n * sizeof (float), st));
+	if (e->tb.s_peak.n) HIPCHK (hipMemsetAsync (e->tb.s_peak.p, 0, e->tb.s_peak.n * sizeof (float), st));
+	HIPCHK (hipStreamSynchronize (st));
+	return MTR_OK;
+}
+
+static constinit BlobHeader tpb_hdr = { 0, TPB_HDR_BYTES, TPB_CORRUPT, tpb_hdr_write, tpb_hdr_check, tpb_hdr_take };
+// (no step: CallRun::tpb launches the kernel, with the series or without)
+constinit SideMeter tpb_series_meter = { MTR_METER_TPBALLIST, 0, nullptr, nullptr, tpb_series_reset, nullptr, tpb_open_sections, &tpb_hdr };
+
+static int no_tpb (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_TPBALLIST); }
+static const char* const NO_TPB = "no TPBALLIST in this engine";
+
+extern "C" {
+
+int mtr_engine_tpb_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points)
+{
+	if (no_tpb (e)) return fail (MTR_ERR_ARG, NO_TPB);
+	if (period_frames > TPB_MAX_PERIOD) return fail (MTR_ERR_ARG, "mtr_engine_tpb_set_period: a period is 0 or 16 .. 8192 frames (one TruePeakdsp::process ())");
+	int rc = series_configure_check (e, "mtr_engine_tpb_set_period", period_frames, TPB_MIN_PERIOD, "16");
+	if (rc || (rc = wait_stream (e))) return rc;
+	const size_t n = (size_t) e->cfg.n_streams * capacity_points * e->cfg.n_channels;
+	if ((rc = series_ring (e->tb.s_level, n, "hipMalloc TPBALLIST series")) || (rc = series_ring (e->tb.s_peak, n, "hipMalloc TPBALLIST series"))) return rc;
+	if (period_frames && e->tb.open.reserve (e->cfg.n_streams)) return fail (MTR_ERR_NOMEM, "hipMalloc TPBALLIST open blocks");
+	e->tb.ser = { period_frames, capacity_points };
+	return tpb_series_reset (e);
+}
+
+int mtr_engine_tpb_period (const mtr_engine* e, uint32_t* period_frames, uint32_t* capacity_points)
+{
+	if (no_tpb (e)) return fail (MTR_ERR_ARG, NO_TPB);
+	if (period_frames) *period_frames = e->tb.ser.period;
+	if (capacity_points) *capacity_points = e->tb.ser.cap;
+	return MTR_OK;
+}
+
+int mtr_engine_tpb_series (mtr_engine* e, uint32_t first, uint32_t count, float* level, float* peak, uint32_t capacity, uint32_t* n_points, uint32_t* dropped)
+{
+	int rc = meter_range (e, !no_tpb (e), NO_TPB, first, count);
+	if (rc) return rc;
+	const size_t take = series_counts (e->pos.tb.points, e->tb.ser.cap, capacity, n_points, dropped);
+	if ((!level && !peak) || !count || !take) return MTR_OK;
+	if ((rc = wait_stream (e))) return rc;
+	const size_t C = e->cfg.n_channels;
+	if (level && (rc = series_fetch (level, e->tb.s_level.p, C, first, e->tb.ser.cap, capacity, take, count))) return rc;
+	if (peak && (rc = series_fetch (peak, e->tb.s_peak.p, C, first, e->tb.ser.cap, capacity, take, count))) return rc;
+	return MTR_OK;
+}
+
+} // extern "C"
+#endif

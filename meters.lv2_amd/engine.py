@@ -168,6 +168,10 @@ def _load():
         L.mtr_engine_kmeter_set_period.argtypes = [vp, u32, u32]
         L.mtr_engine_kmeter_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_kmeter_series.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+    if hasattr(L, "mtr_engine_tpb_series"):                    # (an addition inside ABI version 2: the true-peak bar's reading series)
+        L.mtr_engine_tpb_set_period.argtypes = [vp, u32, u32]
+        L.mtr_engine_tpb_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_tpb_series.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
     if hasattr(L, "mtr_engine_spectr_series"):                 # (an addition inside ABI version 2: the 30-band bank's reading series)
         L.mtr_engine_spectr_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_spectr_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -848,6 +852,31 @@ class Engine:
         (rms, peak), n, d = self._series("kmeter_series", first, count, [(self.n_channels,)] * 2,
                                          lambda count, ptrs, *tail: lib.mtr_engine_kmeter_series(self._h, first, count, *ptrs, *tail))
         return rms, peak, n, d
+
+    def tpb_set_period(self, period_frames, capacity_points=0):
+        """0: every call is one TruePeakdsp::process () + read (m, p); P in 16 .. 8192: blocks of exactly P frames wherever the calls cut
+        the audio, read (m, p) after each appended to a series of `capacity_points` per stream; results() then reports the last completed
+        block's tpb_level / tpb_peak.  Only before the first process call since create / reset."""
+        if not hasattr(lib, "mtr_engine_tpb_series"):
+            raise EngineError(f"{lib_path} has no true-peak reading series: rebuild it")
+        _check(lib.mtr_engine_tpb_set_period(self._h, int(period_frames), int(capacity_points)), "tpb_set_period")
+
+    def tpb_period(self):
+        """(period_frames, capacity_points) as tpb_set_period set them."""
+        if not hasattr(lib, "mtr_engine_tpb_series"):
+            raise EngineError(f"{lib_path} has no true-peak reading series: rebuild it")
+        p, c = C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_tpb_period(self._h, C.byref(p), C.byref(c)), "tpb_period")
+        return p.value, c.value
+
+    def tpb_series(self, first=0, count=None):
+        """(level [count, kept, C], peak [count, kept, C], n_points, dropped): read (m, p) after every completed block since reset that
+        the series holds."""
+        if not hasattr(lib, "mtr_engine_tpb_series"):
+            raise EngineError(f"{lib_path} has no true-peak reading series: rebuild it")
+        (level, peak), n, d = self._series("tpb_series", first, count, [(self.n_channels,)] * 2,
+                                           lambda count, ptrs, *tail: lib.mtr_engine_tpb_series(self._h, first, count, *ptrs, *tail))
+        return level, peak, n, d
 
     def stcorr_set_period(self, period_frames, capacity_points=0):
         """0: every call is one Stcorrdsp::process (); P > 0: blocks of exactly P frames wherever the calls cut the audio, read () after
