@@ -208,6 +208,9 @@ int  mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint6
 /* Track lengths for the 30-band bank (SPECTR30) beside all of those: mtr_engine_process_device_ends / _host_ends and
  * mtr_engine_spectr_points, declared in mtr_ends.h */
 #include "mtr_ends.h"
+/* Track lengths for the true-peak bar (TPBALLIST) beside all of those: mtr_engine_process_device_tpb / _host_tpb and
+ * mtr_engine_tpb_points, declared in mtr_tpb_ends.h */
+#include "mtr_tpb_ends.h"
 /* Frames metered per stream since create / reset, and whether it is closed (either pointer may be NULL): [count] each.
  * (What the process calls queued so far: no synchronisation.  mtr_engine_state_import restarts the count of the streams it writes
  * at 0: a blob carries no frame count.) */

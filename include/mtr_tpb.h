@@ -26,9 +26,9 @@ extern "C" {
  * may hold, and only on an engine that has processed nothing since create / reset (else MTR_ERR_STATE).
  * With P > 0 mtr_engine_results' tpb_level / tpb_peak are the last completed block's — 0.0f before the first; mtr_engine_reset
  * empties the series and the open block and keeps P; the calls with per-stream lengths (mtr_engine_process_*_lengths / _tracks /
- * _ragged / _ends) refuse a TPBALLIST engine as they do without a period (MTR_ERR_UNSUPPORTED).  A state blob of such an engine
- * carries the open block in one more section behind every older one: it goes into an engine of the same period only (else
- * MTR_ERR_STATE); the blob of an engine with P = 0 is what it always was. */
+ * _ragged / _ends) refuse a TPBALLIST engine as they do without a period (MTR_ERR_UNSUPPORTED; mtr_engine_process_*_tpb takes it).
+ * A state blob of such an engine carries the open block in one more section behind every older one: it goes into an engine of the
+ * same period only (else MTR_ERR_STATE); the blob of an engine with P = 0 is what it always was. */
 int  mtr_engine_tpb_set_period (mtr_engine* e, uint32_t period_frames, uint32_t capacity_points);
 /* what set_period set; either pointer may be NULL */
 int  mtr_engine_tpb_period (const mtr_engine* e, uint32_t* period_frames, uint32_t* capacity_points);
@@ -37,6 +37,12 @@ int  mtr_engine_tpb_period (const mtr_engine* e, uint32_t* period_frames, uint32
  * one number each). */
 int  mtr_engine_tpb_series (mtr_engine* e, uint32_t first, uint32_t count, float* level, float* peak, uint32_t capacity,
                             uint32_t* n_points, uint32_t* dropped);
+
+/* Track lengths for the true-peak bar — tracks that end where their audio ends, exactly and at the cost of their own frames, with a period as
+ * without: mtr_engine_process_device_tpb / _host_tpb and mtr_engine_tpb_points, declared in mtr_tpb_ends.h (included by mtr_engine.h next
+ * to mtr_ends.h).  Per (stream, channel) the reference's TruePeakdsp after exactly the stream's own frames (jmeters/truepeakdsp.cc:41-99,
+ * 133-138): a stream that ends r frames into a block, 0 < r < P, gets one last process (p, r) and read (); the series getter above keeps
+ * its lock-step counts, and the rows of a closed stream hold 0.0f behind its own points. */
 
 #ifdef __cplusplus
 }

@@ -418,8 +418,14 @@ struct CallRun {
 		ta.n_streams = c.cnt; ta.n_channels = e->cfg.n_channels;
 		ta.w1 = e->tpb_w[0]; ta.w2 = e->tpb_w[1]; ta.w3 = e->tpb_w[2]; ta.g = e->tpb_w[3];
 		const uint32_t P = e->tb.ser.period;
+		// (a call with ends — mtr_engine_process_*_tpb, or any call once a stream of the view is closed — takes the ENDS instantiations)
 		if (!P) {
-			if (mtr_launch_tpb (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch");
+			if (d_ends) {
+				mtr_tpb_ends_args ea;
+				static_cast<mtr_tpb_args&> (ea) = ta;
+				ea.ends = d_ends;
+				if (mtr_launch_tpb_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (ends)");
+			} else if (mtr_launch_tpb (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch");
 			return MTR_OK;
 		}
 		// the reading series (mtr_tpb.h).  The blocks are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
@@ -433,7 +439,12 @@ struct CallRun {
 		ta.open = e->tb.open.p + c.off;
 		ta.s_level = cap ? e->tb.s_level.p + (size_t) c.off * cap * C : nullptr;
 		ta.s_peak = cap ? e->tb.s_peak.p + (size_t) c.off * cap * C : nullptr;
-		if (mtr_launch_tpb_series (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series)");
+		if (d_ends) {
+			mtr_tpb_series_ends_args ea;
+			static_cast<mtr_tpb_series_args&> (ea) = ta;
+			ea.ends = d_ends;
+			if (mtr_launch_tpb_series_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series, ends)");
+		} else if (mtr_launch_tpb_series (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series)");
 		nx.tb = series_advance (at, P, c.n_frames);
 		return MTR_OK;
 	}
@@ -445,7 +456,11 @@ struct CallRun {
 		mtr_stream_state* const state = e->state.p + c.off;
 		// (deferred: the fold of this call's peaks rides here — behind the reduction of the previous call, which reads the holds)
 		if (fold_in_history && e->red_pending) { HIPCHK (hipStreamWaitEvent (c.st, e->ev_red.v, 0)); e->red_pending = false; }
-		if (e->layout != 8) {
+		if (e->layout != 8 && d_ends && (e->cfg.meters & MTR_METER_TPBALLIST)) {
+			// (beside the true-peak bar a stream that ends inside the call leaves the frames in front of its OWN end: mtr_tpb.hip)
+			if (mtr_launch_history_ends (C, c.audio, c.stride, fir_hist (0), fir_hist (1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st))
+				return fail (MTR_ERR_HIP, "k_history launch (ends)");
+		} else if (e->layout != 8) {
 			const int hrc = C == 2 ? mtr_launch_history (c.audio, c.stride, c.n_frames, fir_hist (0), fir_hist (1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st)
 			                       : mtr_launch_history_mono (c.audio, c.stride, c.n_frames, fir_hist (0), fir_hist (1), c.cnt, c.st);
 			if (hrc) return fail (MTR_ERR_HIP, "k_history launch");
@@ -680,14 +695,16 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 	return process_device (e, d_audio, n_frames, stride, nullptr, hip_stream);
 }
 
-// The four families of calls with per-stream ends (mtr_engine_process_{device,host}_*): which meters a family admits — an engine of some
+// The five families of calls with per-stream ends (mtr_engine_process_{device,host}_*): which meters a family admits — an engine of some
 // of them and of no other — and what else it refuses.  frames_ends: applies a row, then takes the call.
 // _lengths: EBU / TRUEPEAK alone (every layout, 2 .. 5 channels); _tracks: and the whole-track meters (DR14, KMETER, BITSTATS, SIGDIST);
-// _ragged: and the two that keep a reading series, STCORR and NEEDLE (mtr_ragged.h); _ends: and the 30-band bank (mtr_ends.h)
+// _ragged: and the two that keep a reading series, STCORR and NEEDLE (mtr_ragged.h); _ends: and the 30-band bank (mtr_ends.h);
+// _tpb: and the true-peak bar (mtr_tpb.h)
 constexpr uint32_t LENGTHS_METERS = MTR_METER_EBU | MTR_METER_TRUEPEAK;
 constexpr uint32_t TRACKS_METERS = LENGTHS_METERS | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST;
 constexpr uint32_t RAGGED_METERS = TRACKS_METERS | MTR_METER_STCORR | MTR_METER_NEEDLE;
 constexpr uint32_t ENDS_METERS = RAGGED_METERS | MTR_METER_SPECTR30;
+constexpr uint32_t TPB_METERS = ENDS_METERS | MTR_METER_TPBALLIST;
 struct Family {
 	const char* name;            // of its entry points: "<name>: null argument"
 	uint32_t    meters;
@@ -696,7 +713,7 @@ struct Family {
 	bool        no_km_series;    // _tracks: a KMETER engine with a period is refused
 	bool        bank_ends;       // _ends: at most two channels; 32-bit ends with SPECTR30
 };
-enum { LENGTHS, TRACKS, RAGGED, ENDS };
+enum { LENGTHS, TRACKS, RAGGED, ENDS, TPB };
 constexpr Family FAMILIES[] = {
 	{ "lengths", LENGTHS_METERS, "per-stream lengths: EBU / TRUEPEAK engines only", "per-stream lengths: frames[s] > n_frames", false, false },
 	{ "tracks", TRACKS_METERS, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only", "track lengths: frames[s] > n_frames", true, false },
@@ -705,6 +722,9 @@ constexpr Family FAMILIES[] = {
 	{ "ends", ENDS_METERS,
 	  "track lengths for the bank: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 engines of one or two channels only",
 	  "track lengths for the bank: frames[s] > n_frames", false, true },
+	{ "tpb", TPB_METERS,
+	  "track lengths for the true-peak bar: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 / TPBALLIST engines of one or two channels only",
+	  "track lengths for the true-peak bar: frames[s] > n_frames", false, true },
 };
 
 static int family_check (const mtr_engine* e, const Family& fam, uint64_t n_frames, const uint64_t* frames)
@@ -720,7 +740,7 @@ static int family_check (const mtr_engine* e, const Family& fam, uint64_t n_fram
 	return MTR_OK;
 }
 
-// what the eight entry points of the families are: `audio` in host memory (`host`) or in device memory, on `hip_stream`
+// what the ten entry points of the families are: `audio` in host memory (`host`) or in device memory, on `hip_stream`
 static int frames_ends (mtr_engine* e, int family, bool host, const float* audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
 	const Family& fam = FAMILIES[family];
@@ -752,6 +772,16 @@ int mtr_engine_process_device_ragged (mtr_engine* e, const float* d_audio, uint6
 int mtr_engine_process_device_ends (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
 	return frames_ends (e, ENDS, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_device_tpb (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
+{
+	return frames_ends (e, TPB, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_host_tpb (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	return frames_ends (e, TPB, true, h_audio, n_frames, stride, frames, nullptr);
 }
 
 int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)

@@ -330,6 +330,7 @@ struct mtr_engine {
 		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
 		DevBuf<mtr_tpb_open>       open;        // [S] the blob's header and the open block's maxima per channel
 		DevBuf<float>              s_level, s_peak;   // [S][cap][C]
+		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (mtr_engine_process_*_tpb: mtr_tpb.h)
 	} tb;
 };
 

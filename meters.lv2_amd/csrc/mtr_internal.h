@@ -250,6 +250,21 @@ struct mtr_tpb_series_args : mtr_tpb_args {
 	float*          s_peak;
 };
 int  mtr_launch_tpb_series (const mtr_tpb_series_args& a, void* stream);
+/* ... and the ENDS instantiations (mtr_engine_process_*_tpb, or any call once a stream of the view is closed): structs of their own again, the
+ * existing kernels' arguments stay as they are.  ends [S] = the call frame at which stream s of the view ends (<= n_frames; < n_frames: the call
+ * closes it there; 0: untouched) */
+struct mtr_tpb_ends_args : mtr_tpb_args {
+	const uint32_t* ends;
+};
+struct mtr_tpb_series_ends_args : mtr_tpb_series_args {
+	const uint32_t* ends;
+};
+int  mtr_launch_tpb_ends (const mtr_tpb_ends_args& a, void* stream);
+int  mtr_launch_tpb_series_ends (const mtr_tpb_series_ends_args& a, void* stream);
+/* the 47-frame history of a TPBALLIST engine's call with ends (n_channels 1 or 2): the frames in front of each stream's OWN end; a stream
+ * with ends [s] == 0 keeps its row (copied across the ping-pong) and is not folded */
+int  mtr_launch_history_ends (uint32_t n_channels, const float* audio, uint64_t stride, const float* hist_in, float* hist_out,
+                              uint32_t n_streams, mtr_stream_state* fold_state /* stereo; NULL: k_gate folds the peaks */, const uint32_t* ends, void* stream);
 /* ends != NULL: the LEN instantiation, stream s of the view ends at call frame ends[s] (0: untouched) */
 int  mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
                           uint32_t n_streams, const uint32_t* ends, void* stream);

@@ -123,6 +123,12 @@ constexpr int PKX_B = 2 * NCOL * 4;            // the SERIES instantiations: uin
                                                // the products to the chains — behind everything the dense kernel has
 constexpr int LDS_BYTES_SERIES = LDS_BYTES + PKX_B;
 static_assert (LDS_BYTES_SERIES <= 160 * 1024, "one workgroup per CU");
+constexpr int PKE_B = NCOL * 4;                // the ENDS instantiations: uint32_t pke [NCOL], the raw peak of a column's last (truncated) block on the same
+                                               // way, behind pkx (which the dense + ends form leaves unused): a column ends once per call, and a column
+                                               // that ends behind a block end of the same chunk hands over two peaks, one in each
+constexpr int LDS_BYTES_ENDS = LDS_BYTES_SERIES + PKE_B;
+static_assert (LDS_BYTES_ENDS <= 160 * 1024, "one workgroup per CU");
+constexpr int END_NONE = 0x7fffffff;           // the end of a column that the call does not close: behind every frame
 
 // Where piece q of a column sits in its 256 bytes of the f16 ring.  ds_read_b128 is served in the lane groups
 // {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, {32-35, 44-47, 52-59}, {36-43, 48-51, 60-63} (MI355X_MICROARCH.md, LDS), one cycle each
@@ -167,6 +173,25 @@ struct ColScale {
 	}
 };
 
+// the maximum / minimum of a value over the wave, uniform (prologue and cold paths only: six ds_bpermute steps)
+__device__ __forceinline__ int wave_max_i (int v)
+{
+#pragma unroll
+	for (int o = 32; o; o >>= 1) v = max (v, __shfl_xor (v, o));
+	return __builtin_amdgcn_readfirstlane (v);
+}
+__device__ __forceinline__ int wave_min_i (int v)
+{
+#pragma unroll
+	for (int o = 32; o; o >>= 1) v = min (v, __shfl_xor (v, o));
+	return __builtin_amdgcn_readfirstlane (v);
+}
+// the first of a wave's column ends behind call frame `pos` (END_NONE: none)
+__device__ __forceinline__ int next_end_behind (int end, int pos) { return wave_min_i (end > pos ? end : END_NONE); }
+
+template <bool SERIES, bool ENDS> using tpb_args_t = std::conditional_t<ENDS, std::conditional_t<SERIES, mtr_tpb_series_ends_args, mtr_tpb_ends_args>,
+                                                                        std::conditional_t<SERIES, mtr_tpb_series_args, mtr_tpb_args>>;
+
 // SERIES (mtr_engine_tpb_set_period, P > 0; the dense instantiations are the kernel as it always was): the reading series.  Blocks of
 // exactly P frames end at call frames e0, e0 + P, ... whatever the call's length; all streams stand in lock step, so which chunk holds
 // a block end is uniform, and with P >= 16 a chunk holds one at most.  Such a chunk — the end behind its frame r - 1, 1 <= r <= 16 —
@@ -179,8 +204,20 @@ struct ColScale {
 //     iteration earlier, behind the barrier that already separates a chunk's maps from the chain that reads them.
 // Between two calls the states stay raw in mtr_stream_state and the open block's maxima in mtr_tpb_open; a call that starts a block
 // (fill == 0) clamps on entry, any other takes the open maxima up.  tpb_m / tpb_p are written where a block completes.
-template <int C, bool SERIES>   // channels: 2 = interleaved stereo (column = stream + 32 channel), 1 = mono (column = stream)
-__global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SERIES, mtr_tpb_series_args, mtr_tpb_args> a)
+//
+// ENDS (mtr_engine_process_*_tpb, or any call once a stream is closed; the four instantiations without it are the kernels as they were): stream s
+// of the view ends at call frame a.ends [s].  A column whose end lies inside the call is CLOSED there — the reference's process (p, frames) and
+// read (m, p) after exactly its own frames — and whatever its lanes compute afterwards is stored nowhere; a column with end 0 stores nothing at all.
+//   * the workgroup runs to the LAST end among its streams (every wave derives it from the same loads) as if that were the call's length:
+//     loop bound, LDS-DMA and ragged last chunk follow from it, and a workgroup whose ends are all 0 returns in front of the first barrier;
+//   * the split zeroes a column's samples at and behind its end before anything is made of them (a select: a NaN there reaches nothing);
+//   * every role keeps, beside next_end, a scalar cursor to the first end among its own columns that it has not passed: a chunk that holds
+//     none (and no block end) runs the bodies of the dense kernel; one that does takes the cold path of the series form with a per-lane cut —
+//     the products split the lane's peak at the column's end (pke) as at a block end (pkx), the chains walk the chunk frame by frame and
+//     store the column's reading, its states + 1e-20f and (with a period) its truncated block's point behind its last frame (column_end).
+//     No barrier is added: which chunks are cold differs between the roles, and nothing in a cold path waits for another wave.
+template <int C, bool SERIES, bool ENDS = false>   // channels: 2 = interleaved stereo (column = stream + 32 channel), 1 = mono (column = stream)
+__global__ __launch_bounds__ (NTHREADS) void k_tpb (const tpb_args_t<SERIES, ENDS> a)
 {
 	constexpr int NSTR = NCOL / C;                                       // streams per workgroup
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem[];
@@ -195,7 +232,18 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	const uint32_t s0 = blockIdx.x * NSTR;
 	// (32-bit: gfx950 has no scalar 64-bit signed compare, and every `t < n_chunks` of every wave and iteration was two or three
 	// VALU instructions — ~80 of a workgroup's ~850 per chunk.  mtr_launch_tpb refuses calls of 2^31 - 4096 frames or more.)
-	const int n_frames = (int) a.n_frames;
+	const int n_call = (int) a.n_frames;
+	// ENDS: the workgroup's last end stands in for the call's length.  Every wave takes it from the same loads, so all twelve run the same
+	// iterations and meet at the same barriers; nothing at or behind it is read
+	int wg_end = n_call;
+	if constexpr (ENDS) {
+		const uint32_t sl = s0 + (uint32_t) lane;
+		int e = 0;
+		if (lane < NSTR && sl < a.n_streams) e = (int) min (a.ends[sl], (uint32_t) n_call);
+		wg_end = wave_max_i (e);
+		if (wg_end == 0) return;                                           // (in front of the first barrier: nothing of these streams changes)
+	}
+	const int n_frames = wg_end;
 	const int n_chunks = (n_frames + F - 1) / F;
 
 	// ---- the chains (waves 0, 1): lane = (column ci of the wave's 32, filter phi) ------------------------------------------
@@ -208,8 +256,18 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	const int cch = C == 2 ? hw_ : 0;
 	const bool cowner = csl < a.n_streams;
 	mtr_stream_state* const cst = a.state + (cowner ? csl : 0);
+	// ENDS: cend = the end of the lane's column if the call closes it there (0: it was closed before — nothing of it is stored), END_NONE if it
+	// runs to the call's end: then the epilogue stores it (cstore), as ever; c_next = the first of the wave's ends the chains have not passed
+	int cend = END_NONE, c_next = END_NONE;
+	bool cstore = cowner;
+	if constexpr (ENDS) {
+		const int e = cowner ? (int) min (a.ends[csl], (uint32_t) n_call) : 0;
+		cend = e < n_call ? e : END_NONE;
+		cstore = cowner && e == n_call;
+		if (wid < 2) c_next = next_end_behind (cend, 0);
+	}
 	float z = 0.f, zm = 0.f;
-	bool opens = true;                                                   // the call starts a block (the dense kernel: the call IS the block)
+	bool opens = true;                                                  // the call starts a block (the dense kernel: the call IS the block)
 	if constexpr (SERIES) opens = a.fill == 0;
 	if (wid < 2 && cowner) {
 		z = phi ? cst->tpb_z2[cch] : cst->tpb_z1[cch];
@@ -219,6 +277,7 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	// that is open where the role stands ends); what the chain lanes carry of the open block beside z and zm — the raw peak the calls
 	// before gave it (pko) — and the points the call has completed (npt)
 	uint32_t* const pkx = reinterpret_cast<uint32_t*> (smem + LDS_BYTES);
+	uint32_t* const pke = pkx + 2 * NCOL;                                // ENDS: [NCOL]
 	int next_end = 0, npt = 0;
 	float pko = 0.f;
 	if constexpr (SERIES) {
@@ -240,6 +299,9 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	const bool sowner = ssl < a.n_streams;
 	const float* const srow = a.audio + (size_t) (sowner ? ssl : s0) * a.stride * C;
 	const int srot = f16_rot (scol);
+	// ENDS: the column's own end — the samples at and behind it are zeros to everything downstream (a column past the batch: all of them)
+	int send = n_frames;
+	if constexpr (ENDS) send = sowner ? (int) min (a.ends[ssl], (uint32_t) n_call) : 0;
 
 	// A WHOLE chunk travels HBM -> LDS by LDS-DMA (global_load_lds_dwordx4: no register holds data in flight, so nothing
 	// makes the wave wait for it but the one s_waitcnt below), issued by wave 2, AHEAD (= 5) iterations ahead of the barrier behind
@@ -313,7 +375,16 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 #pragma unroll
 		for (int i = 0; i < 8; ++i) {
 			const int f = j * F + 8 * hp + i;
-			x[i] = (sowner && f < n_frames) ? srow[(size_t) f * C + sch] : 0.f;
+			x[i] = (sowner && f < send) ? srow[(size_t) f * C + sch] : 0.f;
+		}
+	};
+	// ENDS: a staged chunk's samples at and behind the column's end become zeros (selects, per lane and only where the lane's eight
+	// samples reach the end: what lies there may be anything)
+	auto cut_staged = [&] (int j, float (&x)[8]) __attribute__ ((always_inline)) {
+		const int rem = send - (j * F + 8 * hp);
+		if (rem < 8) {
+#pragma unroll
+			for (int i = 0; i < 8; ++i) x[i] = i < rem ? x[i] : 0.f;
 		}
 	};
 
@@ -396,6 +467,14 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	const int urot = f16_rot (ucol);
 	const bool prod_wave = unit_a || unit_b;
 	float pk = 0.f;                                                      // raw peak of the values this lane produced (column cc of its block)
+	// ENDS: the end of the lane's column as the chains have it (cend), and the products' cursor to the first end of the block's sixteen columns
+	int uend = END_NONE, u_next = END_NONE;
+	if constexpr (ENDS) {
+		const uint32_t usl = s0 + (uint32_t) (C == 2 ? (ucol & 31) : ucol);
+		const int e = usl < a.n_streams ? (int) min (a.ends[usl], (uint32_t) n_call) : 0;
+		uend = e < n_call ? e : END_NONE;
+		if (prod_wave) u_next = next_end_behind (uend, 0);
+	}
 	// the operands of a chunk: read from the rings one iteration AHEAD of the products, behind the MFMAs of the chunk before and
 	// under its maps (round 4 read them at the top of the iteration they were used in: ~200 cycles of LDS latency per chunk on
 	// every unit's critical path)
@@ -509,6 +588,42 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 		atomicMax (&pkx[par * NCOL + ucol], __float_as_uint (pk));
 		pk = pnew;
 	};
+	// ENDS, a chunk (from call frame `base` on) that holds an end of one of the block's columns, a block end (behind its frame rb - 1; rb > 16:
+	// none) or both: the same maps again.  Of the lane's four frames those in front of its column's end count, the others are stored nowhere; a
+	// block end that lies at or in front of the column's end closes the column's block as ever (pkx), and the column's end hands over what
+	// has been gathered since (pke) — the peak of the truncated block, or of the whole call without a period
+	auto unit_maps_ends = [&]<bool UB> (int par, const float4& x0, float un, const m16::f4 (&y)[2], int nfl, int rb, int base) __attribute__ ((always_inline)) {
+		constexpr int NPH = UB ? 2 : 1;
+		const float xr[4] = { x0.x, x0.y, x0.z, x0.w };
+		const v2f W = v2f{a.w1, a.w2}, WA = v2f{a.w1 * a1, a.w2 * a2};
+		unsigned char* const row = cbuf + par * CBUF_B + ((UB ? F : 0) + 4 * kg) * CROW + blk * 256 + cc * 8;
+		const int re = uend - base;                                         // the column's end in the chunk: <= 0 closed, > 16 open behind it
+		const int rle = re - 4 * kg, rlb = rb - 4 * kg;
+		float pnew = 0.f;
+#pragma unroll
+		for (int r = 0; r < 4; ++r) {
+			unsigned char* const cd = row + r * CROW;
+			const float va = UB ? fabsf (y[0][r]) * un : xr[r], vb = fabsf (y[NPH - 1][r]) * un;
+			const float mx = max_abs_plain (va, vb);
+			const v2f bb = W * vb;
+			float g1x, g1y, g2x, g2y;                                       // (instruction for instruction unit_maps': the same bits)
+			asm ("v_mul_f32 %0, %1, %2" : "=v"(g1x) : "v"(W.x), "v"(mx));
+			asm ("v_mul_f32 %0, %1, %2" : "=v"(g1y) : "v"(W.y), "v"(mx));
+			asm ("v_fma_f32 %0, %1, |%2|, %3" : "=v"(g2x) : "v"(WA.x), "v"(va), "v"(bb.x));
+			asm ("v_fma_f32 %0, %1, |%2|, %3" : "=v"(g2y) : "v"(WA.y), "v"(va), "v"(bb.y));
+			*reinterpret_cast<v2f*> (cd) = v2f{g1x, g2x};
+			*reinterpret_cast<v2f*> (cd + 128) = v2f{g1y, g2y};
+			const float mk = mx * (r < nfl ? 1.f : 0.f);
+			if (r < rle) {
+				if (r < rlb) pk = max3_plain (pk, mk, mk);
+				else pnew = max3_plain (pnew, mk, mk);
+			}
+		}
+		if (rb <= F) {                                                       // (uniform)
+			if (rb <= re) { atomicMax (&pkx[par * NCOL + ucol], __float_as_uint (pk)); pk = pnew; }
+		}
+		if (re >= 1 && re <= F) atomicMax (&pke[ucol], __float_as_uint (pk));
+	};
 
 	// ---- prologue: the 48 frames before the call (47 of history; frame -48 is never multiplied by a non-zero tap), chunks 0 and 1 ----
 	for (int e = threadIdx.x; e < NCOL * 48; e += NTHREADS) {
@@ -521,6 +636,7 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	}
 	if (threadIdx.x < 2) flag_sh[threadIdx.x] = 0;
 	if constexpr (SERIES) { if (threadIdx.x < 2 * NCOL) pkx[threadIdx.x] = 0u; }
+	if constexpr (ENDS) { if (threadIdx.x < NCOL) pke[threadIdx.x] = 0u; }
 	float xc0[8], xc1[8];
 	if (wid == 2 || wid == 3) { take_ragged (0, xc0); take_ragged (1, xc1); }
 	__syncthreads ();
@@ -602,10 +718,13 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	// them, + 1e-20f (truepeakdsp.cc:86-87) and clamped (:54-55), and the maxima from zero (:133-138)
 	auto block_end = [&]<int PARITY> () __attribute__ ((always_inline)) {
 		if constexpr (SERIES) {
+			// (ENDS: a column whose end lies in front of this block end takes no part in it — next_end is the end the chain stands at)
+			bool alive = true;
+			if constexpr (ENDS) alive = next_end <= cend;
 			if (phi == 0) {
 				const uint32_t pb = pkx[PARITY * NCOL + ccol];
 				pkx[PARITY * NCOL + ccol] = 0u;
-				if (cowner) {
+				if (cowner && alive) {
 					const float m = zm * a.g, p = __builtin_fmaxf (__uint_as_float (pb), pko);
 					cst->tpb_m[cch] = m;
 					cst->tpb_p[cch] = p;
@@ -637,6 +756,65 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 			const float zo = __uint_as_float (__builtin_amdgcn_update_dpp (0, __float_as_uint (z), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
 			zm = __builtin_fmaxf (zm, z + zo);
 			if (f + 1 == r) block_end.template operator()<PARITY> ();
+		}
+	};
+	// ENDS.  A column ends behind the frame its chain has just walked, inside the call: what the reference holds after process (p, frames)
+	// and read (m, p) on exactly those frames (truepeakdsp.cc:86-89, 133-138) goes to memory here, and the epilogue leaves the column alone.
+	// Without a period: the reading and the states + 1e-20f.  With one: if the column stands r frames into a block, 0 < r < P, that block
+	// is truncated — its point is appended where the next whole block's would have been, the states get their + 1e-20f; r = 0: the block
+	// end that has just passed was the column's, and did all that.  Either way the open block is left as behind a block's end.  The peak
+	// of the products' frames in front of the end is in pke: they wrote it an iteration ago, as they write pkx.
+	auto column_end = [&] () __attribute__ ((always_inline)) {
+		if constexpr (ENDS) {
+			if (!cowner) return;
+			float zs = z + 1e-20f;
+			if constexpr (SERIES) {
+				const bool partial = cend + (int) a.period != next_end;          // (next_end: the end of the block the chain stands in)
+				if (!partial) zs = z;
+				if (partial && phi == 0) {
+					const float m = zm * a.g, p = __builtin_fmaxf (__uint_as_float (pke[ccol]), pko);
+					cst->tpb_m[cch] = m;
+					cst->tpb_p[cch] = p;
+					if ((uint32_t) npt < a.room) {
+						const size_t o = ((size_t) csl * a.capacity + a.point0 + (uint32_t) npt) * C + cch;
+						a.s_level[o] = m;
+						a.s_peak[o] = p;
+					}
+				}
+				if (phi == 0) {
+					a.open[csl].zm[cch] = 0.f; a.open[csl].pk[cch] = 0.f;
+					if (C == 1) { a.open[csl].zm[1] = 0.f; a.open[csl].pk[1] = 0.f; }
+				}
+			} else if (phi == 0) {
+				cst->tpb_m[cch] = zm * a.g;
+				cst->tpb_p[cch] = __uint_as_float (pke[ccol]);
+			}
+			if (phi) cst->tpb_z2[cch] = zs;
+			else {
+				cst->tpb_z1[cch] = zs;
+				if (C == 1) { cst->tpb_z1[1] = 1e-20f; cst->tpb_z2[1] = 1e-20f; cst->tpb_m[1] = 0.f; cst->tpb_p[1] = 0.f; }
+			}
+		}
+	};
+	// ... and the chunk (from call frame `base` on) that holds such an end, a block end (behind its frame rb - 1; 0: none) or both: chain_cold's
+	// walk, the column's end per lane.  A block end that coincides with a column's end comes first
+	auto chain_cold_ends = [&]<int PARITY> (int nf, int rb, int base) __attribute__ ((always_inline)) {
+		const unsigned char* const src = cbuf + PARITY * CBUF_B + (2 * hw_ + (ci >> 4)) * 256 + phi * 128 + (ci & 15) * 8;
+		const int re = cend - base;
+#pragma unroll 1
+		for (int f = 0; f < nf; ++f) {
+			const v2f q1 = *reinterpret_cast<const v2f*> (src + f * CROW), q2 = *reinterpret_cast<const v2f*> (src + (F + f) * CROW);
+			const float u0 = sl0 * z;
+			const v2f u12 = __builtin_elementwise_fma (SL12, v2f{z, z}, q1);
+			const float zh = max3f (u0, u12.x, u12.y);
+			const v2f v12 = __builtin_elementwise_fma (AP12, v2f{zh, zh}, q2);
+			z = max3f (zh, v12.x, v12.y);
+			const float zo = __uint_as_float (__builtin_amdgcn_update_dpp (0, __float_as_uint (z), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+			zm = __builtin_fmaxf (zm, z + zo);
+			if constexpr (SERIES) {
+				if (f + 1 == rb) { block_end.template operator()<PARITY> (); next_end += (int) a.period; }
+			}
+			if (f + 1 == re) column_end ();
 		}
 	};
 	// THE LOOP, once per role: every wave runs the same iterations and the same barriers, but each role's copy of the loop has
@@ -693,7 +871,18 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 			if (t >= 1 && !MTR_TPB_DBG_NOCHAIN) {
 				const int left = n_frames - (t - 1) * F;
 				bool cold = false;
-				if constexpr (SERIES) {                                          // a block ends inside chunk t - 1, behind its frame r - 1
+				if constexpr (ENDS) {                                            // an end of one of the wave's columns inside chunk t - 1, a block end, or both
+					const int nf = left >= F ? F : left;
+					int rb = 0;
+					if constexpr (SERIES) { rb = next_end - (t - 1) * F; rb = rb <= nf ? rb : 0; }
+					const bool has_e = c_next <= t * F;
+					cold = __builtin_expect (has_e || rb != 0, 0);
+					if (cold) {
+						chain_cold_ends.template operator()<PAR ^ 1> (nf, rb, (t - 1) * F);
+						if (has_e) c_next = next_end_behind (cend, t * F);
+					}
+				} else
+				if constexpr (SERIES) {                                        // a block ends inside chunk t - 1, behind its frame r - 1
 					const int nf = left >= F ? F : left, r = next_end - (t - 1) * F;
 					cold = __builtin_expect (r <= nf, 0);
 					if (cold) { chain_cold.template operator()<PAR ^ 1> (nf, r); next_end += (int) a.period; }
@@ -717,6 +906,7 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 				if (SENDER && (t + AHEAD + 1) * F <= n_frames && !MTR_TPB_DBG_NODMA) dma (t + AHEAD);
 				float x[8];
 				take_staged.template operator()<CH> (t + 2, x);
+				if constexpr (ENDS) cut_staged (t + 2, x);
 				if (moved ()) { rescale (16 * sw); __syncthreads (); if (lane == 0) flag_sh[PAR] = 0; }
 				if (!MTR_TPB_DBG_NOSPLIT) {
 					int sp = sw + 5; sp -= sp >= NSLOT ? NSLOT : 0;              // chunk t + 2's slot
@@ -765,6 +955,19 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 					if (moved ()) __syncthreads ();
 					fetch_ops.template operator()<UB, (SW + 1) % NSLOT> (ops[PAR ^ 1]);
 					bool cold = false;
+					if constexpr (ENDS) {                                          // an end of one of the block's columns inside chunk t, a block end, or both
+						const int left_c = n_frames - t * F;
+						int rb = 99;
+						if constexpr (SERIES) { rb = next_end - t * F; rb = rb <= (left_c >= F ? F : left_c) ? rb : 99; }
+						const bool has_e = u_next <= (t + 1) * F;
+						cold = __builtin_expect (has_e || rb <= F, 0);
+						if (cold) {
+							const int left = left_c - 4 * kg;
+							unit_maps_ends.template operator()<UB> (PAR, ops[PAR].x0, ops[PAR].un, y, left >= 4 ? 4 : (left > 0 ? left : 0), rb, t * F);
+							if constexpr (SERIES) { if (rb <= F) next_end += (int) a.period; }
+							if (has_e) u_next = next_end_behind (uend, (t + 1) * F);
+						}
+					} else
 					if constexpr (SERIES) {                                        // a block ends inside chunk t, behind its frame r - 1
 						const int left_c = n_frames - t * F, r = next_end - t * F;
 						cold = __builtin_expect (r <= (left_c >= F ? F : left_c), 0);
@@ -800,7 +1003,7 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 	if constexpr (SERIES) {
 		// the states raw — a block that ended with the call got its + 1e-20f in block_end — and the open block's maxima: what the products
 		// found in the call's frames behind its last block end, and in front of the call if it held none
-		if (wid < 2 && cowner) {
+		if (wid < 2 && cstore) {
 			if (phi) cst->tpb_z2[cch] = z;
 			else {
 				cst->tpb_z1[cch] = z;
@@ -811,7 +1014,7 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const std::conditional_t<SER
 		}
 		return;
 	}
-	if (wid < 2 && cowner) {
+	if (wid < 2 && cstore) {
 		if (phi) cst->tpb_z2[cch] = z + 1e-20f;                            // truepeakdsp.cc:86-87
 		else {
 			cst->tpb_z1[cch] = z + 1e-20f;
@@ -833,6 +1036,27 @@ __global__ void k_history_mono (const float* audio, uint64_t stride, uint64_t n_
 	const float v = (f >= 0) ? audio[(size_t) s * stride + f] : hist_in[((size_t) s * MTR_FIR_HALO + MTR_FIR_HALO + f) * 2];
 	hist_out[((size_t) s * MTR_FIR_HALO + i) * 2] = v;
 	hist_out[((size_t) s * MTR_FIR_HALO + i) * 2 + 1] = 0.f;
+}
+
+// ... of a call with ends (the LEN form of k_history_mono, and of k_history for the engines of this meter): a stream that ends inside the
+// call leaves the 47 frames in front of its OWN end — what lies behind it has no influence on anything — and a stream with end 0 keeps its
+// row, copied across (the buffers ping-pong: its part of the state blob must not flip with every later call), and is not folded
+template <int C>
+__global__ void k_history_ends (const float* audio, uint64_t stride, const float* hist_in, float* hist_out, uint32_t n_streams,
+                                mtr_stream_state* fold_state, const uint32_t* ends)
+{
+	const uint32_t gidx = blockIdx.x * blockDim.x + threadIdx.x;
+	if (gidx >= n_streams * MTR_FIR_HALO) return;
+	const uint32_t s = gidx / MTR_FIR_HALO, i = gidx % MTR_FIR_HALO;
+	const int64_t f = (int64_t) ends[s] - MTR_FIR_HALO + i;              // (end 0: every f < 0, the old row)
+	const size_t h = ((size_t) s * MTR_FIR_HALO + i) * 2;
+#pragma unroll
+	for (int c = 0; c < 2; ++c) {
+		float v = 0.f;                                                      // (mono: the right channel stays zero)
+		if (c < C) v = f >= 0 ? audio[((size_t) s * stride + (size_t) f) * C + c] : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * 2 + c];
+		hist_out[h + c] = v;
+	}
+	if (C == 2 && fold_state && ends[s] != 0 && i == 0) mtr_fold_truepeak (fold_state + s);
 }
 
 }  // namespace
@@ -872,6 +1096,53 @@ int mtr_launch_tpb_series (const mtr_tpb_series_args& a, void* stream)
 	hipStream_t st = (hipStream_t) stream;
 	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, true>), grid, dim3 (NTHREADS), LDS_BYTES_SERIES, st, a);
 	else                   hipLaunchKernelGGL ((k_tpb<1, true>), grid, dim3 (NTHREADS), LDS_BYTES_SERIES, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// The ENDS instantiations: the same checks; the ends are 32 bits, which the 31 of the call's length cover
+int mtr_launch_tpb_ends (const mtr_tpb_ends_args& a, void* stream)
+{
+	if (a.n_frames >= 0x7ffff000ull || !a.ends) return -1;
+	static bool raised = false;
+	if (!raised) {
+		(void) hipFuncSetAttribute ((const void*) k_tpb<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
+		(void) hipFuncSetAttribute ((const void*) k_tpb<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
+		raised = true;
+	}
+	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
+	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
+	hipStream_t st = (hipStream_t) stream;
+	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, false, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
+	else                   hipLaunchKernelGGL ((k_tpb<1, false, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+int mtr_launch_tpb_series_ends (const mtr_tpb_series_ends_args& a, void* stream)
+{
+	if (a.n_frames >= 0x7ffff000ull || !a.ends) return -1;
+	if (a.period < (uint32_t) F || a.period > 8192u || a.fill >= a.period || a.e0 != a.period - a.fill || !a.open) return -1;
+	if (a.room && (!a.s_level || !a.s_peak || a.point0 >= a.capacity || a.room > a.capacity - a.point0)) return -1;
+	static bool raised = false;
+	if (!raised) {
+		(void) hipFuncSetAttribute ((const void*) k_tpb<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
+		(void) hipFuncSetAttribute ((const void*) k_tpb<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
+		raised = true;
+	}
+	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
+	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
+	hipStream_t st = (hipStream_t) stream;
+	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, true, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
+	else                   hipLaunchKernelGGL ((k_tpb<1, true, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+int mtr_launch_history_ends (uint32_t n_channels, const float* audio, uint64_t stride, const float* hist_in, float* hist_out,
+                             uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream)
+{
+	if (!ends || (n_channels != 1 && n_channels != 2)) return -1;
+	const uint32_t n = n_streams * MTR_FIR_HALO;
+	if (n_channels == 2) hipLaunchKernelGGL (k_history_ends<2>, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream, audio, stride, hist_in, hist_out, n_streams, fold_state, ends);
+	else                 hipLaunchKernelGGL (k_history_ends<1>, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream, audio, stride, hist_in, hist_out, n_streams, fold_state, ends);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -934,6 +1205,7 @@ static void tpb_hdr_take (mtr_engine* e, const void* in)
 static int tpb_series_reset (mtr_engine* e)
 {
 	e->pos.tb = {};
+	e->tb.points.assign (e->cfg.n_streams, 0);
 	if (!e->tb.open.n && !e->tb.s_level.n && !e->tb.s_peak.n) return MTR_OK;
 	e->snap_valid = false;
 	HIPCHK (hipSetDevice (e->cfg.device));
@@ -947,7 +1219,9 @@ static int tpb_series_reset (mtr_engine* e)
 
 static constinit BlobHeader tpb_hdr = { 0, TPB_HDR_BYTES, TPB_CORRUPT, tpb_hdr_write, tpb_hdr_check, tpb_hdr_take };
 // (no step: CallRun::tpb launches the kernel, with the series or without)
-constinit SideMeter tpb_series_meter = { MTR_METER_TPBALLIST, 0, nullptr, nullptr, tpb_series_reset, nullptr, tpb_open_sections, &tpb_hdr };
+static int tpb_series_create (mtr_engine* e) { e->tb.points.assign (e->cfg.n_streams, 0); return MTR_OK; }
+static SeriesView tpb_series (mtr_engine* e) { return { &e->tb.ser, &Cursors::tb, &e->tb.points }; }
+constinit SideMeter tpb_series_meter = { MTR_METER_TPBALLIST, 0, nullptr, tpb_series_create, tpb_series_reset, nullptr, tpb_open_sections, &tpb_hdr, tpb_series };
 
 static int no_tpb (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_TPBALLIST); }
 static const char* const NO_TPB = "no TPBALLIST in this engine";
@@ -985,6 +1259,15 @@ int mtr_engine_tpb_series (mtr_engine* e, uint32_t first, uint32_t count, float*
 	const size_t C = e->cfg.n_channels;
 	if (level && (rc = series_fetch (level, e->tb.s_level.p, C, first, e->tb.ser.cap, capacity, take, count))) return rc;
 	if (peak && (rc = series_fetch (peak, e->tb.s_peak.p, C, first, e->tb.ser.cap, capacity, take, count))) return rc;
+	return MTR_OK;
+}
+
+int mtr_engine_tpb_points (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* points)
+{
+	int rc = meter_range (e, !no_tpb (e), NO_TPB, first, count);
+	if (rc) return rc;
+	if (!points) return fail (MTR_ERR_ARG, "mtr_engine_tpb_points: null argument");
+	series_points_of (e, MTR_METER_TPBALLIST, first, count, points);
 	return MTR_OK;
 }
 

@@ -136,6 +136,10 @@ def _load():
         L.mtr_engine_process_device_ends.argtypes = [vp, vp, u64, u64, vp, vp]
         L.mtr_engine_process_host_ends.argtypes = [vp, vp, u64, u64, vp]
         L.mtr_engine_spectr_points.argtypes = [vp, u32, u32, vp]
+    if hasattr(L, "mtr_engine_process_device_tpb"):            # (an addition inside ABI version 2: track lengths for the true-peak bar)
+        L.mtr_engine_process_device_tpb.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_tpb.argtypes = [vp, vp, u64, u64, vp]
+        L.mtr_engine_tpb_points.argtypes = [vp, u32, u32, vp]
     if hasattr(L, "mtr_engine_pcm_stats"):                     # (an addition inside ABI version 2: integer PCM in)
         L.mtr_engine_process_host_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp]
         L.mtr_engine_process_device_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp, vp]
@@ -558,7 +562,8 @@ class Engine:
     # the families of calls with per-stream ends: the symbol whose absence means "rebuild the library", and what the library then lacks
     _FAMILY = {"lengths": ("mtr_engine_stream_frames", "per-stream lengths"), "tracks": ("mtr_engine_process_device_tracks", "track lengths"),
                "ragged": ("mtr_engine_process_device_ragged", "ragged batches"),
-               "ends": ("mtr_engine_process_device_ends", "track lengths for the 30-band bank")}
+               "ends": ("mtr_engine_process_device_ends", "track lengths for the 30-band bank"),
+               "tpb": ("mtr_engine_process_device_tpb", "track lengths for the true-peak bar")}
 
     def _frames(self, frames, family):
         """frames as contiguous uint64 [S], for a call of `family`"""
@@ -633,6 +638,24 @@ class Engine:
         count = self.n_streams - first if count is None else count
         out = np.zeros(count, np.uint64)
         _check(lib.mtr_engine_spectr_points(self._h, first, count, out.ctypes.data), "spectr_points")
+        return out
+
+    def process_device_tpb(self, ptr, n_frames, frames, stride=None, stream=0):
+        """process_device_ends() for engines that also hold TPBALLIST: stream s is metered up to frames[s] <= n_frames — the true-peak
+        bar's process () ends there with its read () and, with a period, a truncated last point; frames[s] < n_frames closes it."""
+        self._device_frames("tpb", ptr, n_frames, frames, stride, stream)
+
+    def process_tpb(self, x, frames):
+        """process() with track lengths for the true-peak bar: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        self._host_frames("tpb", x, frames)
+
+    def tpb_points(self, first=0, count=None):
+        """[count] uint64: the points each stream's own TPBALLIST series has got since reset, dropped ones included — of a stream that
+        process_*_tpb closed, its whole blocks and the truncated one."""
+        self._frames(np.zeros(self.n_streams, np.uint64), "tpb")
+        count = self.n_streams - first if count is None else count
+        out = np.zeros(count, np.uint64)
+        _check(lib.mtr_engine_tpb_points(self._h, first, count, out.ctypes.data), "tpb_points")
         return out
 
     def process_pcm(self, x, format=None, frames=None):
