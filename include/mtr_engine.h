@@ -33,7 +33,8 @@ extern "C" {
  *    _needle_series, _needle_reset; mtr_engine_process_device_tracks, _process_host_tracks; MTR_METER_SCOPE, mtr_scope_window,
  *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset; mtr_engine_kmeter_set_period, _kmeter_period,
  *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series; mtr_engine_process_device_ends, _process_host_ends,
- *    _spectr_points; mtr_engine_scope_set_series, _scope_series_config, _scope_series, mtr_scope_series_cut):
+ *    _spectr_points; mtr_engine_scope_set_series, _scope_series_config, _scope_series, mtr_scope_series_cut; mtr_engine_process_device_any,
+ *    _process_host_any, _scope_points):
  *    + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
@@ -211,6 +212,9 @@ int  mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint6
 /* Track lengths for the true-peak bar (TPBALLIST) beside all of those: mtr_engine_process_device_tpb / _host_tpb and
  * mtr_engine_tpb_points, declared in mtr_tpb_ends.h */
 #include "mtr_tpb_ends.h"
+/* Track lengths for the scope (SCOPE) beside all of those, and for the surround meter (SURROUND) on 3 .. 8 channels: mtr_engine_process_device_any / _host_any and
+ * mtr_engine_scope_points, declared in mtr_any.h */
+#include "mtr_any.h"
 /* Frames metered per stream since create / reset, and whether it is closed (either pointer may be NULL): [count] each.
  * (What the process calls queued so far: no synchronisation.  mtr_engine_state_import restarts the count of the streams it writes
  * at 0: a blob carries no frame count.) */

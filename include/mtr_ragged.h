@@ -34,15 +34,16 @@ extern "C" {
  * Once a stream is closed, every later call on the streams that hold it (mtr_engine_process_device / _host, an LV2 block) runs the
  * length-masking kernels, end 0 for the closed ones.  The per-meter resets (mtr_engine_stcorr_reset, _needle_reset, ...) reopen nothing.
  * Engines that hold SPECTR30, TPBALLIST, SURROUND or SCOPE: MTR_ERR_UNSUPPORTED, nothing queued, engine unchanged (SPECTR30 has a pair of
- * its own that takes these meters beside it: mtr_engine_process_device_ends / _host_ends, mtr_ends.h).  (SURROUND is left
- * out on purpose: its K-meters' weights depend on the block length, which would become per-stream, and its pieces kernel has no
- * registers to spare for a second set of them.)
+ * its own that takes these meters beside it: mtr_engine_process_device_ends / _host_ends, mtr_ends.h; SCOPE is taken by
+ * mtr_engine_process_device_any / _host_any, mtr_any.h).  (SURROUND is taken by that pair too, but for one call with a period: a stream that ends before the
+ * group of four frames completes which the call before left open needs its K-meters' state in front of that group, as KMETER's series
+ * carries it, and the surround meter's kernel and state do not make it.)
  * replaces: a host that stops calling run() at the track's end. */
 int  mtr_engine_process_device_ragged (mtr_engine* e, const float* d_audio, uint64_t n_frames,
                                        uint64_t stream_stride_frames, const uint64_t* frames, void* hip_stream);
 int  mtr_engine_process_host_ragged (mtr_engine* e, const float* h_audio, uint64_t n_frames,
                                      uint64_t stream_stride_frames, const uint64_t* frames);
-/* points [count]: the points each stream's own series of `meter` (MTR_METER_STCORR, MTR_METER_NEEDLE or MTR_METER_KMETER; anything else, or a meter the
+/* points [count]: the points each stream's own series of `meter` (MTR_METER_STCORR, MTR_METER_NEEDLE, MTR_METER_KMETER or MTR_METER_SURROUND; anything else, or a meter the
  * engine lacks: MTR_ERR_ARG) has got since reset, dropped ones included: the whole blocks it completed and, if it was closed inside
  * one, the truncated block.  Period 0: no series, 0.  Counted on the host: no device work, no synchronisation.  Zeroed by the meter's
  * reset and by mtr_engine_reset. */

@@ -12,8 +12,9 @@ extern "C" {
 #endif
 
 /* The analysis under the reference's two FFT views of a stereo programme, for a batch (MTR_METER_SCOPE; stereo engines only — a pair of
- * a wider frame: mtr_engine_set_frame_layout, as for STCORR).  Combines with every other stereo meter; not with the per-stream-lengths
- * and track-lengths entry points (MTR_ERR_UNSUPPORTED, nothing queued).  n_frames per call < 2^31 - 1.
+ * a wider frame: mtr_engine_set_frame_layout, as for STCORR).  Combines with every other stereo meter.  Of the per-stream-lengths
+ * and track-lengths entry points mtr_engine_process_device_any / _host_any take it (mtr_any.h); the five older pairs refuse it
+ * (MTR_ERR_UNSUPPORTED, nothing queued).  n_frames per call < 2^31 - 1.
  *
  * W = window frames, B = W / 2 bins, H = hop.  After every H frames of a stream, counted across the process calls wherever they cut the
  * audio (a lock-step cursor like STCORR's period), one analysis runs on the stream's last W frames, zeros in front of its start: what

@@ -15,8 +15,9 @@ extern "C" {
  * Kmeterdsp::process + read (m, p) (jmeters/kmeterdsp.cc:56-153) and n_pairs = C > 3 ? 4 : 3 x Stcorrdsp::process + read ()
  * (jmeters/stcorrdsp.cc:47-93, init (rate, 2e3f, 0.3f)), pair p on the channels (a [p], b [p]).  One kernel reads the frames once for
  * all of them.  3 .. 5 channels combine it with MTR_METER_EBU / MTR_METER_TRUEPEAK; 6 .. 8 channels take it alone (anything else:
- * MTR_ERR_ARG, as every engine of more than 5 channels without it); 1 or 2 channels: MTR_ERR_UNSUPPORTED.  Not with the
- * per-stream-lengths entry points.  n_frames per call < 2^31 - 1.
+ * MTR_ERR_ARG, as every engine of more than 5 channels without it); 1 or 2 channels: MTR_ERR_UNSUPPORTED.  Of the
+ * per-stream-lengths and track-lengths entry points mtr_engine_process_device_any / _host_any take it (mtr_any.h); the
+ * five older pairs refuse it.  n_frames per call < 2^31 - 1.
  *
  * The pairs: a control, like the plugin's cor?A / cor?B ports.  a4, b4: four entries each; an entry >= C is clamped to C - 1
  * (surmeter.c:124-125), a == b is legal.  After create: pair p = (2 p, 2 p + 1), clamped (the surround8 port defaults).  Applies from

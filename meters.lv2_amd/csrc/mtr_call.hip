@@ -230,13 +230,14 @@ struct CallRun {
 	}
 
 	// [ends S | frag_lim S | from_tile S | km_fall S] of a ragged call into the next slot of the lengths ring, uploaded on the call's stream
-	// (an engine without EBU / TRUEPEAK has no plan: its frag_lim / from_tile are never read; km_fall: KMETER engines only)
+	// (an engine without EBU / TRUEPEAK has no plan: its frag_lim / from_tile are never read; km_fall: KMETER and SURROUND engines only —
+	// no engine holds both)
 	int upload_lengths ()
 	{
 		const SegPlan& sp = r.sp;
 		const uint32_t S = c.cnt;
-		const bool fused = ebu || tp, km = e->cfg.meters & MTR_METER_KMETER;
-		const size_t words = (size_t) (km ? 4 : 3) * S;
+		const bool fused = ebu || tp, km = e->cfg.meters & MTR_METER_KMETER, su = e->cfg.meters & MTR_METER_SURROUND;
+		const size_t words = (size_t) (km || su ? 4 : 3) * S;
 		const int slot = (e->len_cur + 1) % LEN_SLOTS;
 		ls = &e->len_slot[slot];
 		for (int i = 0; i < 2; ++i) if (ls->pending[i]) { HIPCHK (hipEventSynchronize (ls->done[i].v)); ls->pending[i] = false; }
@@ -253,6 +254,9 @@ struct CallRun {
 			// (with a period: one of the frames it has of the block it ends in, if it ends inside one)
 			const uint64_t kp = e->km.ser.period, kf = kp ? (e->pos.km.fill + f) % kp : f;
 			if (km) h_fall[i] = f && f < c.n_frames && kf ? kmeter_fall (e, kf) : 0.f;
+			// (the surround meter's K-meters likewise, from their own cursor)
+			const uint64_t sup = e->su.ser.period, sf = sup ? (e->pos.su.fill + f) % sup : f;
+			if (su) h_fall[i] = f && f < c.n_frames && sf ? kmeter_fall (e, sf) : 0.f;
 			if (!fused) { h_lim[i] = h_from[i] = 0; continue; }
 			// fragments that end at or before the stream's end
 			const uint32_t nf = (uint32_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
@@ -269,7 +273,7 @@ struct CallRun {
 		HIPCHK (hipMemcpyAsync (ls->dev.p, ls->pin.p, words * sizeof (uint32_t), hipMemcpyHostToDevice, c.st));
 		e->len_cur = slot;
 		d_ends = ls->dev.p; d_lim = d_ends + S; d_from = d_ends + 2 * (size_t) S;
-		if (km) d_fall = reinterpret_cast<const float*> (d_ends + 3 * (size_t) S);
+		if (km || su) d_fall = reinterpret_cast<const float*> (d_ends + 3 * (size_t) S);
 		return MTR_OK;
 	}
 
@@ -530,6 +534,7 @@ struct CallRun {
 			if (e->closed[g]) continue;
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
+			if (meters & MTR_METER_SCOPE) scope_count (e, g, f);
 			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
 			for (const SideMeter* m : SIDE_METERS) {
 				if (!(meters & m->bits) || !m->series) continue;
@@ -695,16 +700,20 @@ int mtr_engine_process_device (mtr_engine* e, const float* d_audio, uint64_t n_f
 	return process_device (e, d_audio, n_frames, stride, nullptr, hip_stream);
 }
 
-// The five families of calls with per-stream ends (mtr_engine_process_{device,host}_*): which meters a family admits — an engine of some
+// The six families of calls with per-stream ends (mtr_engine_process_{device,host}_*): which meters a family admits — an engine of some
 // of them and of no other — and what else it refuses.  frames_ends: applies a row, then takes the call.
 // _lengths: EBU / TRUEPEAK alone (every layout, 2 .. 5 channels); _tracks: and the whole-track meters (DR14, KMETER, BITSTATS, SIGDIST);
 // _ragged: and the two that keep a reading series, STCORR and NEEDLE (mtr_ragged.h); _ends: and the 30-band bank (mtr_ends.h);
-// _tpb: and the true-peak bar (mtr_tpb.h)
+// _tpb: and the true-peak bar (mtr_tpb.h); _any: and the scope and the surround meter, with no limit on the channels of its own
+// (mtr_any.h).  What is left outside is one call of the surround meter with a period: a stream that ends before the group of four completes
+// which the call before left open needs its K-meters' state in front of that group, as KMETER's series carries it (mtr_kmeter.hip: bz1,
+// btmax), and the surround meter's dense kernel and state do not make it (family_check)
 constexpr uint32_t LENGTHS_METERS = MTR_METER_EBU | MTR_METER_TRUEPEAK;
 constexpr uint32_t TRACKS_METERS = LENGTHS_METERS | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_BITSTATS | MTR_METER_SIGDIST;
 constexpr uint32_t RAGGED_METERS = TRACKS_METERS | MTR_METER_STCORR | MTR_METER_NEEDLE;
 constexpr uint32_t ENDS_METERS = RAGGED_METERS | MTR_METER_SPECTR30;
 constexpr uint32_t TPB_METERS = ENDS_METERS | MTR_METER_TPBALLIST;
+constexpr uint32_t ANY_METERS = TPB_METERS | MTR_METER_SCOPE | MTR_METER_SURROUND;
 struct Family {
 	const char* name;            // of its entry points: "<name>: null argument"
 	uint32_t    meters;
@@ -712,8 +721,9 @@ struct Family {
 	const char* too_long;        // MTR_ERR_ARG: frames[s] > n_frames
 	bool        no_km_series;    // _tracks: a KMETER engine with a period is refused
 	bool        bank_ends;       // _ends: at most two channels; 32-bit ends with SPECTR30
+	bool        wide = false;    // _any: ... but the channels are whatever mtr_engine_create accepted for the engine's meters
 };
-enum { LENGTHS, TRACKS, RAGGED, ENDS, TPB };
+enum { LENGTHS, TRACKS, RAGGED, ENDS, TPB, ANY };
 constexpr Family FAMILIES[] = {
 	{ "lengths", LENGTHS_METERS, "per-stream lengths: EBU / TRUEPEAK engines only", "per-stream lengths: frames[s] > n_frames", false, false },
 	{ "tracks", TRACKS_METERS, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only", "track lengths: frames[s] > n_frames", true, false },
@@ -725,14 +735,24 @@ constexpr Family FAMILIES[] = {
 	{ "tpb", TPB_METERS,
 	  "track lengths for the true-peak bar: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 / TPBALLIST engines of one or two channels only",
 	  "track lengths for the true-peak bar: frames[s] > n_frames", false, true },
+	{ "any", ANY_METERS,
+	  "track lengths for every meter: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 / TPBALLIST / SCOPE / SURROUND engines only",
+	  "track lengths for every meter: frames[s] > n_frames", false, true, true },
 };
 
 static int family_check (const mtr_engine* e, const Family& fam, uint64_t n_frames, const uint64_t* frames)
 {
 	const uint32_t meters = e->cfg.meters;
-	if ((meters & ~fam.meters) || !(meters & fam.meters) || (fam.bank_ends && e->cfg.n_channels > 2)) return fail (MTR_ERR_UNSUPPORTED, fam.unsupported);
+	if ((meters & ~fam.meters) || !(meters & fam.meters) || (fam.bank_ends && !fam.wide && e->cfg.n_channels > 2)) return fail (MTR_ERR_UNSUPPORTED, fam.unsupported);
 	if (fam.no_km_series && (meters & MTR_METER_KMETER) && e->km.ser.period)
 		return fail (MTR_ERR_UNSUPPORTED, "track lengths: a KMETER engine with a period keeps a reading series (mtr_engine_process_*_ragged)");
+	// (SURROUND with a period, a block open on entry that stands inside a group of four frames, and a stream that ends before that group
+	// completes: its last sur_run would have to drop the whole group from the K-meters' filter and peak, and the state in front of the
+	// group is not kept — mtr_any.h.  The one call _any cannot take)
+	if (fam.wide && (meters & MTR_METER_SURROUND) && e->su.ser.period && (e->pos.su.fill & 3))
+		for (uint32_t i = 0; i < e->cfg.n_streams; ++i)
+			if (!e->closed[i] && frames[i] && frames[i] < n_frames && frames[i] < 4 - (e->pos.su.fill & 3))
+				return fail (MTR_ERR_UNSUPPORTED, "track lengths for every meter: SURROUND with a period: a stream ends before the group of four frames completes that the call before left open");
 	if (fam.bank_ends && (meters & MTR_METER_SPECTR30) && n_frames > 0xFFFFFFFEull)
 		return fail (MTR_ERR_ARG, "track lengths for the bank: n_frames per call must be < 2^32 - 1");
 	for (uint32_t i = 0; i < e->cfg.n_streams; ++i)
@@ -740,7 +760,7 @@ static int family_check (const mtr_engine* e, const Family& fam, uint64_t n_fram
 	return MTR_OK;
 }
 
-// what the ten entry points of the families are: `audio` in host memory (`host`) or in device memory, on `hip_stream`
+// what the twelve entry points of the families are: `audio` in host memory (`host`) or in device memory, on `hip_stream`
 static int frames_ends (mtr_engine* e, int family, bool host, const float* audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
 	const Family& fam = FAMILIES[family];
@@ -784,6 +804,16 @@ int mtr_engine_process_host_tpb (mtr_engine* e, const float* h_audio, uint64_t n
 	return frames_ends (e, TPB, true, h_audio, n_frames, stride, frames, nullptr);
 }
 
+int mtr_engine_process_device_any (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
+{
+	return frames_ends (e, ANY, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_host_any (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	return frames_ends (e, ANY, true, h_audio, n_frames, stride, frames, nullptr);
+}
+
 int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
 	return frames_ends (e, LENGTHS, true, h_audio, n_frames, stride, frames, nullptr);
@@ -807,8 +837,8 @@ int mtr_engine_process_host_ends (mtr_engine* e, const float* h_audio, uint64_t 
 int mtr_engine_series_points (mtr_engine* e, uint32_t meter, uint32_t first, uint32_t count, uint64_t* points)
 {
 	if (!e || !points) return fail (MTR_ERR_ARG, "mtr_engine_series_points: null argument");
-	if ((meter != MTR_METER_STCORR && meter != MTR_METER_NEEDLE && meter != MTR_METER_KMETER) || !(e->cfg.meters & meter))
-		return fail (MTR_ERR_ARG, "mtr_engine_series_points: meter is MTR_METER_STCORR, MTR_METER_NEEDLE or MTR_METER_KMETER, one the engine holds");
+	if ((meter != MTR_METER_STCORR && meter != MTR_METER_NEEDLE && meter != MTR_METER_KMETER && meter != MTR_METER_SURROUND) || !(e->cfg.meters & meter))
+		return fail (MTR_ERR_ARG, "mtr_engine_series_points: meter is MTR_METER_STCORR, MTR_METER_NEEDLE, MTR_METER_KMETER or MTR_METER_SURROUND, one the engine holds");
 	if ((uint64_t) first + count > e->cfg.n_streams) return fail (MTR_ERR_ARG, "stream range");
 	series_points_of (e, meter, first, count, points);
 	return MTR_OK;

@@ -302,6 +302,7 @@ struct mtr_engine {
 		double                     pw[3];       // Kmeterdsp's A per group of four frames
 		double                     k[18];       // mtr_sur_consts: the pieces kernel's constants
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
+		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (mtr_engine_process_*_any: mtr_any.h)
 	} su;
 	struct Scope {                              // SCOPE (mtr_scope.hip)
 		DevBuf<float>              tail;        // [S][W][2] the last W frames of every stream
@@ -317,6 +318,7 @@ struct mtr_engine {
 			DevBuf<float>          ring[7];     // per selected field, in the order of the bits: [S][cap][B]; peak: [S][cap]
 			DevBuf<unsigned char>  open;        // [S] mtr_scope_open: the blob's copy of (K, analyses since the last point)
 		} ser;
+		std::vector<uint64_t>      analyses, points;   // [S] each stream's own analyses and series points since reset (mtr_engine_process_*_any: mtr_any.h)
 	} sp;
 	struct LoudLog {                            // the loudness log of an EBU engine (mtr_loudlog.hip; the gate appends: mtr_gate.hip)
 		DevBuf<float>              M, S;        // [S][cap]
@@ -360,7 +362,7 @@ struct Call {
 
 // The per-stream ends of a ragged call on the device, as the side meters' steps get them: ends[i] = the call frame at which stream i of the
 // view ends (0: closed, untouched), km_fall[i] = Kmeterdsp's fall-back factor for a stream that ends inside the call (KMETER engines: that of
-// its frames in the call, or — with a period — of its frames in the truncated block).
+// its frames in the call, or — with a period — of its frames in the truncated block; SURROUND engines: that of its frames in the call).
 // Both null on a dense call: the steps then launch the dense instantiations.
 struct StreamEnds {
 	const uint32_t* ends = nullptr;
@@ -437,6 +439,9 @@ inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter,
 // the points of each of streams [first, first + count) in the series of the meter with `bit`, which the engine holds and which keeps such counts
 void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points);
 
+// SCOPE counts analyses and the points among them, not blocks of a period: stream g's own counts move by those of `frames` frames of a
+// call that starts at e->pos (no `series` hook: that one is the periods')
+void scope_count (mtr_engine* e, size_t g, uint64_t frames);
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view
 // [off, off + cnt) (false: the log is off); its part of mtr_engine_reset

@@ -30,6 +30,9 @@
 // capacity: level and lr from the registers they live in, peak by one thread behind its update, the rest from the pass.  A point is what
 // mtr_engine_scope_read answers after that analysis, bins 0 and B - 1 included.  k_scope<LOGW, false> is the kernel as it was: another
 // argument struct, no instruction of the series.
+//
+// Track lengths (mtr_any.h): k_scope<LOGW, SERIES, true>, launched only by a call that carries per-stream ends.  A workgroup is a stream, so
+// the stream's end is one scalar: it bounds the analyses, names the stream's own last one and places the tail; see the kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,6 +78,15 @@ typedef struct mtr_scope_series_args : mtr_scope_args {
 	uint32_t        cap, fields;
 } mtr_scope_series_args;
 
+// per-stream ends (mtr_any.h): what the ENDS instantiations take on top of either struct — again structs of their own, so that the two
+// kernels of a dense call keep their arguments
+typedef struct mtr_scope_ends_args : mtr_scope_args {
+	const uint32_t* ends;         /* [S] call frame at which the stream ends, <= n_frames; 0: closed, nothing of it is touched */
+} mtr_scope_ends_args;
+typedef struct mtr_scope_series_ends_args : mtr_scope_series_args {
+	const uint32_t* ends;
+} mtr_scope_series_ends_args;
+
 /* SCOPE's second section of the blob: all of an entry is its host-owned header */
 typedef struct mtr_scope_open { uint32_t every, since; } mtr_scope_open;
 
@@ -114,14 +126,28 @@ template <int LOGW> __device__ __forceinline__ Bin bin_of (const float2* z, uint
 	return b;
 }
 
-template <int LOGW, bool SERIES> __global__ __launch_bounds__ (threads_of (LOGW))
-void k_scope (const std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_args> a)
+template <bool SERIES, bool ENDS> using scope_args_of = std::conditional_t<ENDS, std::conditional_t<SERIES, mtr_scope_series_ends_args, mtr_scope_ends_args>,
+                                                                            std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_args>>;
+
+// ENDS: stream s ends at call frame a.ends[s] (mtr_any.h).  Its analyses are those that end at or before its end — a hop that is not full
+// runs none, as fftx_run when the host stops feeding it (gui/fft.c:308-311) — `last` is its OWN last one, its tail the W frames in front of
+// its end, and no frame at or behind the end is read.  End 0: the workgroup returns before it touches anything.  The stream is the
+// workgroup's, so everything this changes is uniform; the instantiations without ENDS are the kernels as they were.
+template <int LOGW, bool SERIES, bool ENDS = false> __global__ __launch_bounds__ (threads_of (LOGW))
+void k_scope (const scope_args_of<SERIES, ENDS> a)
 {
 	constexpr int W = 1 << LOGW, B = W / 2, NT = threads_of (LOGW), BPT = B / NT;
 	extern __shared__ __attribute__ ((aligned (16))) unsigned char smem[];
 	float2* const z = reinterpret_cast<float2*> (smem);
 	__shared__ float red[NT / 64];
 	const uint32_t s = blockIdx.x, t = threadIdx.x;
+	uint64_t end = a.n_frames;                                         // the stream's frames in the call ...
+	uint32_t n_an = a.n_an;                                            // ... and the analyses that end inside them
+	if constexpr (ENDS) {
+		end = a.ends[s];
+		if (end == 0) return;
+		n_an = end < a.first ? 0 : (uint32_t) ((end - a.first) / a.hop) + 1;
+	}
 	const float* const src = a.audio + (size_t) s * a.stride * 2;
 	float* const tail = a.tail + (size_t) s * W * 2;
 	const bool al8 = (reinterpret_cast<uintptr_t> (src) & 7) == 0;
@@ -129,7 +155,7 @@ void k_scope (const std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_
 
 	float level[BPT] = {}, lr[BPT] = {};
 	float peak = 0.f;
-	if (a.n_an) {
+	if (n_an) {
 #pragma unroll
 		for (int r = 0; r < BPT; ++r) { level[r] = a.level[so + t + r * NT]; lr[r] = a.lr[so + t + r * NT]; }
 		peak = a.peak[s];
@@ -138,9 +164,9 @@ void k_scope (const std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_
 	[[maybe_unused]] uint64_t pidx = 0;
 	if constexpr (SERIES) { since = a.since; pidx = a.point0; }
 
-	for (uint32_t j = 0; j < a.n_an; ++j) {
+	for (uint32_t j = 0; j < n_an; ++j) {
 		const int64_t f0 = (int64_t) (a.first + (uint64_t) j * a.hop) - W;   // the analysis' first frame
-		const bool last = j + 1 == a.n_an;
+		const bool last = j + 1 == n_an;
 		[[maybe_unused]] bool keep = false;                            // SERIES: the analysis is a point the rings have room for, row `at` of them
 		[[maybe_unused]] size_t at = 0;
 		if constexpr (SERIES) {
@@ -285,7 +311,7 @@ void k_scope (const std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_
 		}
 	}
 
-	if (a.n_an) {
+	if (n_an) {
 #pragma unroll
 		for (int r = 0; r < BPT; ++r) {
 			const uint32_t i = t + r * NT;
@@ -295,22 +321,24 @@ void k_scope (const std::conditional_t<SERIES, mtr_scope_series_args, mtr_scope_
 		if (t == 0) a.peak[s] = peak;
 	}
 	// ---- the stream's last W frames, for the calls to come (through LDS: the old tail is read before it is overwritten) ----
-	const int64_t t0 = (int64_t) a.n_frames - W;
+	const int64_t t0 = (int64_t) end - W;
 	for (int i = t; i < W; i += NT) z[pad (i)] = frame_at<W> (src, tail, t0 + i, al8);
 	__syncthreads ();
 	for (int i = t; i < W; i += NT) *reinterpret_cast<float2*> (tail + 2 * i) = z[pad (i)];
 }
 
-// A: mtr_scope_args — the kernel without a series — or mtr_scope_series_args
+// A: mtr_scope_args — the kernel without a series — or mtr_scope_series_args, or the struct with ends on top of either
 template <int LOGW, typename A> int launch (const A& a, hipStream_t st)
 {
-	constexpr bool SERIES = std::is_same_v<A, mtr_scope_series_args>;
+	constexpr bool SERIES = std::is_base_of_v<mtr_scope_series_args, A>;
+	constexpr bool ENDS = !std::is_same_v<A, mtr_scope_args> && !std::is_same_v<A, mtr_scope_series_args>;
+	static_assert (std::is_same_v<A, scope_args_of<SERIES, ENDS>>, "k_scope's arguments");
 	constexpr uint32_t bytes = lds_slots (1u << LOGW) * sizeof (float2);
-	if (bytes > 48 * 1024) {
-		static const hipError_t once = hipFuncSetAttribute ((const void*) k_scope<LOGW, SERIES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+	if (bytes > 48 * 1024) {                                           // (per instantiation: each is a kernel of its own)
+		static const hipError_t once = hipFuncSetAttribute ((const void*) k_scope<LOGW, SERIES, ENDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
 		(void) once;
 	}
-	hipLaunchKernelGGL ((k_scope<LOGW, SERIES>), dim3 (a.n_streams), dim3 (threads_of (LOGW)), bytes, st, a);
+	hipLaunchKernelGGL ((k_scope<LOGW, SERIES, ENDS>), dim3 (a.n_streams), dim3 (threads_of (LOGW)), bytes, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -342,6 +370,7 @@ int series_set (mtr_engine* e, uint32_t K, uint32_t cap, uint32_t fields)
 	const auto off = [&sr] { for (auto& r : sr.ring) r.drop (); sr.open.drop (); sr.every = sr.cap = sr.fields = 0; };
 	off ();
 	e->pos.sp_since = 0; e->pos.sp_points = 0;
+	e->sp.points.assign (e->cfg.n_streams, 0);
 	if (!K) return MTR_OK;
 	const size_t S = e->cfg.n_streams, B = e->sp.W / 2;
 	size_t rows, n;
@@ -404,7 +433,9 @@ uint32_t default_hop (const mtr_engine* e) { return (uint32_t) ceil ((double) e-
 
 static int scope_create (mtr_engine* e) { return configure (e, W_DEFAULT, default_hop (e), 1e-6f); }   // stereoscope.c:641, phasewheel.c:1212
 
-static int scope_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
+// A call with ends (mtr_engine_process_*_any, or any call once a stream of the view is closed: se.ends is then the view's ends, 0 for a closed
+// stream) takes the ENDS instantiations; every other call the dense ones, as ever.
+static int scope_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const mtr_engine::Scope& sp = e->sp;
 	const size_t vo = c.off, B = sp.W / 2;
@@ -427,13 +458,31 @@ static int scope_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 		for (int k = 0; k < 7; ++k) ss.ring[k] = sp.ser.ring[k].p ? sp.ser.ring[k].p + vo * cap * (k == F_PEAK_AT ? 1 : B) : nullptr;
 		ss.point0 = std::min<uint64_t> (e->pos.sp_points, cap);
 		ss.every = K; ss.since = e->pos.sp_since; ss.cap = cap; ss.fields = cap ? sp.ser.fields : 0;
-		if (mtr_launch_scope (sp.W, ss, c.st)) return fail (MTR_ERR_HIP, "k_scope launch (series)", hipGetLastError ());
+		if (se.ends) {
+			mtr_scope_series_ends_args es;
+			static_cast<mtr_scope_series_args&> (es) = ss;
+			es.ends = se.ends;
+			if (mtr_launch_scope (sp.W, es, c.st)) return fail (MTR_ERR_HIP, "k_scope launch (series, ends)", hipGetLastError ());
+		} else if (mtr_launch_scope (sp.W, ss, c.st)) return fail (MTR_ERR_HIP, "k_scope launch (series)", hipGetLastError ());
 		nx.sp_since = (uint32_t) ((e->pos.sp_since + n_an) % K);
 		nx.sp_points = e->pos.sp_points + n_pt;
+	} else if (se.ends) {
+		mtr_scope_ends_args ea;
+		static_cast<mtr_scope_args&> (ea) = sa;
+		ea.ends = se.ends;
+		if (mtr_launch_scope (sp.W, ea, c.st)) return fail (MTR_ERR_HIP, "k_scope launch (ends)", hipGetLastError ());
 	} else if (mtr_launch_scope (sp.W, sa, c.st)) return fail (MTR_ERR_HIP, "k_scope launch", hipGetLastError ());
 	nx.sp_fill = (uint32_t) (tot % sp.H);
 	nx.sp_analyses = e->pos.sp_analyses + sa.n_an;
 	return MTR_OK;
+}
+
+// stream g's own analyses and points (mtr_engine_scope_points): those of its `frames` frames of a call that starts at e->pos
+void scope_count (mtr_engine* e, size_t g, uint64_t frames)
+{
+	uint64_t an, pt;
+	series_cut (e->pos.sp_fill, e->sp.H, e->pos.sp_since, e->sp.ser.every, frames, &an, &pt);
+	e->sp.analyses[g] += an; e->sp.points[g] += pt;
 }
 
 static void scope_sections (const mtr_engine* e, std::vector<StateSection>& v)
@@ -569,6 +618,8 @@ int mtr_engine_scope_reset (mtr_engine* e)
 	// the reading series: emptied (what a ring holds past its count is never handed out), the open group gone, the settings kept
 	e->pos.sp_since = 0;
 	e->pos.sp_points = 0;
+	sp.analyses.assign (e->cfg.n_streams, 0);
+	sp.points.assign (e->cfg.n_streams, 0);
 	return MTR_OK;
 }
 
@@ -592,6 +643,17 @@ int mtr_engine_scope_analyses (mtr_engine* e, uint64_t* n)
 {
 	if (no_scope (e) || !n) return fail (MTR_ERR_ARG, "mtr_engine_scope_analyses: no SCOPE in this engine, or a null argument");
 	*n = e->pos.sp_analyses;
+	return MTR_OK;
+}
+
+int mtr_engine_scope_points (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* analyses, uint64_t* points)
+{
+	const int rc = meter_range (e, !no_scope (e), "no SCOPE in this engine", first, count);
+	if (rc) return rc;
+	for (uint32_t i = 0; i < count; ++i) {
+		if (analyses) analyses[i] = e->sp.analyses[first + i];
+		if (points) points[i] = e->sp.points[first + i];
+	}
 	return MTR_OK;
 }
 
@@ -645,8 +707,16 @@ int mtr_engine_scope_series (mtr_engine* e, uint32_t first, uint32_t count, floa
 	if (!any || !count || !take) return MTR_OK;
 	if ((rc = wait_stream (e))) return rc;
 	const size_t B = e->sp.W / 2;
-	for (int k = 0; k < 7; ++k)
-		if (out[k] && (rc = series_fetch (out[k], sr.ring[k].p, k == F_PEAK_AT ? 1 : B, first, sr.cap, capacity, take, count))) return rc;
+	for (int k = 0; k < 7; ++k) {
+		if (!out[k]) continue;
+		const size_t w = k == F_PEAK_AT ? 1 : B;
+		if ((rc = series_fetch (out[k], sr.ring[k].p, w, first, sr.cap, capacity, take, count))) return rc;
+		// (a stream that was closed has fewer points of its own than the open ones: 0.0f behind them, whatever the ring still holds there)
+		for (uint32_t i = 0; i < count; ++i) {
+			const uint64_t own = e->sp.points[first + i];
+			if (own < take) memset (out[k] + ((size_t) i * capacity + (size_t) own) * w, 0, (take - (size_t) own) * w * sizeof (float));
+		}
+	}
 	return MTR_OK;
 }
 

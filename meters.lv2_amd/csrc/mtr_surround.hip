@@ -31,11 +31,16 @@
 //    instead of holding them: with the constants every lane would compute alike passed from the host (scalar registers), every pair's
 //    carried first-stage state in LDS and the rare "owes" sums reduced where they arise, the kernel holds 223 .. 248 VGPRs, no
 //    scratch, and two workgroups fit a CU.
+//
+// Track lengths (mtr_any.h): k_sur_pieces<C, true> and k_sur_final<true>, launched only by a call that carries
+// per-stream ends.  A workgroup is one (stream, piece), so the stream's end is one scalar: it cuts the piece, and the block it cuts has
+// the length the K-meters count their groups and weights from; see the kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -107,6 +112,13 @@ typedef struct mtr_sur_args {
 	float*          s_corr;       /* [S][capacity][4] */
 } mtr_sur_args;
 
+// per-stream ends (mtr_any.h): what the LEN instantiations take on top — a struct of its own, so that the dense kernels
+// keep their arguments
+typedef struct mtr_sur_len_args : mtr_sur_args {
+	const uint32_t* ends;         /* [S] call frame at which the stream ends, <= n_frames; 0: closed, nothing of it is touched */
+	const float*    falls;        /* [S] Kmeterdsp's fall-back factor of each stream that ends inside the call: that of the frames it has of its last block */
+} mtr_sur_len_args;
+
 namespace {
 
 using namespace mtr_sc;
@@ -123,13 +135,28 @@ __device__ __forceinline__ int64_t block_start (const mtr_sur_args& a, const Pie
 	return (int64_t) (a.e0 + ((uint64_t) pc.b0 - a.e0) / a.period * a.period);
 }
 
-template <int C>
-__global__ __launch_bounds__ (NT, 2) void k_sur_pieces (const mtr_sur_args a)
+template <bool LEN> using sur_args_of = std::conditional_t<LEN, mtr_sur_len_args, mtr_sur_args>;
+
+// LEN: the stream ends at call frame a.ends[s] (0: closed, untouched; n_frames: the dense call's stream).  Its piece is [b0, min (b1, end)):
+// one that starts at or behind the end returns before it touches memory, as k_stcorr_pieces<LEN>; a truncated one has its tiles aligned
+// to the stream's end, so that nothing at or behind it is read.  The block an end inside the call cuts has L = the frames the stream has
+// of it, as in k_kmeter_blocks: the K-meters take L & ~3 of them, the weights counted back from the stream's own last group.  A workgroup
+// is one (stream, piece): all of this is uniform, no lane holds a second set of weights.
+template <int C, bool LEN = false>
+__global__ __launch_bounds__ (NT, 2) void k_sur_pieces (const sur_args_of<LEN> a)
 {
 	const uint32_t s = blockIdx.y;
 	const Piece pc = piece_of (a, blockIdx.x);
 	const float* const src = a.audio + (size_t) s * a.stride * C;
-	const int64_t b0 = pc.b0, b1 = pc.b1;
+	int64_t pb1 = pc.b1, L = (int64_t) a.block;
+	if constexpr (LEN) {
+		const int64_t end = (int64_t) a.ends[s];
+		if (pc.b0 >= end) return;                                  // (uniform in the workgroup; end 0: every piece of the stream)
+		const int64_t bs = block_start (a, pc);
+		if (end < (int64_t) a.n_frames && end < bs + L) L = end - bs;   // one last sur_run, of the frames the stream has of the block
+		if (end < pb1) pb1 = end;
+	}
+	const int64_t b0 = pc.b0, b1 = pb1;
 	const int64_t warm = b0 == 0 ? 1 : (int64_t) a.warm;          // (the call's first piece: only the slot of frame -1)
 	const int nt = (int) ((b1 - b0 + warm + TILE - 1) / TILE);      // <= MAX_TILES: chunk + warm <= MAX_TILES * TILE
 	const int64_t lo = b0 - warm > 0 ? b0 - warm : 0;              // the first frame that is read
@@ -147,7 +174,7 @@ __global__ __launch_bounds__ (NT, 2) void k_sur_pieces (const mtr_sur_args a)
 
 	// ---- the K-meters' geometry: block offsets ----
 	const int64_t blk0 = block_start (a, pc);
-	const int64_t Lg = (int64_t) (a.block & ~(uint64_t) 3);        // frames of a block the K-meters take
+	const int64_t Lg = LEN ? L & ~(int64_t) 3 : (int64_t) (a.block & ~(uint64_t) 3);   // frames of a block the K-meters take
 	// block offset at which the piece's z1 stands: its end, but never inside the block's dropped trailing frames — a call may end there
 	// (P mod 4 != 0), and Kmeterdsp never runs z1 over them
 	const int64_t E1 = b1 - blk0 < Lg ? b1 - blk0 : Lg;
@@ -366,19 +393,31 @@ __global__ __launch_bounds__ (NT, 2) void k_sur_pieces (const mtr_sur_args a)
 }
 
 // one thread per (stream, channel): the pieces in order, and kmeterdsp.cc:74-75, 101-138 + read (m, p) at every end of a block
-__device__ void final_channel (const mtr_sur_args& a, uint32_t s, uint32_t c)
+// LEN: the pieces up to the stream's end; an end inside the call closes the block there — one Kmeterdsp::process (p, L) of the L frames the
+// stream has of it: L & ~3 frames, fpp = L with the fall-back factor a.falls[s] (kmeterdsp.cc:65-70, 79)
+template <bool LEN>
+__device__ void final_channel (const sur_args_of<LEN>& a, uint32_t s, uint32_t c, int64_t end)
 {
 #pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
 	mtr_sur_chan* const st = &a.state[s].ch[c];
 	const double kw = (double) a.omega, kr = 1.0 - kw, ka = a.pw[0], kb = a.pw[2];
-	const int64_t Lg = (int64_t) (a.block & ~(uint64_t) 3);
 	double z1 = st->z1, z2 = st->z2;
 	float level = st->level, peak = st->peak, tmax = st->tmax;
 	int32_t cnt = st->cnt, flag = st->flag;
 	uint64_t point = a.point0;
 	for (uint32_t i = 0; i < a.n_pieces; ++i) {
-		const Piece pc = piece_of (a, i);
+		Piece pc = piece_of (a, i);
 		const int64_t blk0 = block_start (a, pc);
+		int64_t L = (int64_t) a.block;
+		if constexpr (LEN) {
+			if (pc.b0 >= end) break;
+			if (end < (int64_t) a.n_frames && end < blk0 + L) L = end - blk0;
+			if (end <= pc.b1) {
+				pc.b1 = end;
+				if (L != (int64_t) a.block) pc.closes = true;          // one last process (), of what the stream has of the block
+			}
+		}
+		const int64_t Lg = L & ~(int64_t) 3;
 		const int64_t p0 = pc.b0 - blk0, E1 = pc.b1 - blk0 < Lg ? pc.b1 - blk0 : Lg;   // (as the pieces kernel's: z1 stops at Lg)
 		if (p0 == 0) {                                             // :74-75 (a NaN state falls through, as there; it is an f32 here)
 			z1 = z1 > 50 ? 50 : (z1 < 0 ? 0 : z1);
@@ -407,9 +446,14 @@ __device__ void final_channel (const mtr_sur_args& a, uint32_t s, uint32_t c)
 		t = sqrtf (t);
 		if (a.period || flag) { level = rms; flag = 0; }           // :112-121 (a host that reads after every block always finds the flag set)
 		else if (rms > level) level = rms;
+		uint32_t fpp = a.fpp;
+		float fall = a.fall;
+		if constexpr (LEN) {
+			if (L != (int64_t) a.block) { fpp = (uint32_t) L; fall = a.falls[s]; }
+		}
 		if (t >= peak) { peak = t; cnt = a.hold; }                 // :124-139
-		else if (cnt > 0) cnt -= (int32_t) a.fpp;
-		else { peak *= a.fall; peak += 1e-10f; }
+		else if (cnt > 0) cnt -= (int32_t) fpp;
+		else { peak *= fall; peak += 1e-10f; }
 		if (a.period) {
 			if (point < a.capacity) {
 				const size_t o = ((size_t) s * a.capacity + point) * a.n_channels + c;
@@ -421,8 +465,10 @@ __device__ void final_channel (const mtr_sur_args& a, uint32_t s, uint32_t c)
 	st->z1 = z1; st->z2 = z2; st->level = level; st->peak = peak; st->tmax = tmax; st->cnt = cnt; st->flag = flag;
 }
 
-// one thread per (stream, pair): k_stcorr_final
-__device__ void final_pair (const mtr_sur_args& a, uint32_t s, uint32_t p)
+// one thread per (stream, pair): k_stcorr_final, LEN as there — the piece that holds the stream's end is its last, with its own length, and
+// an end inside the call ends a process () there
+template <bool LEN>
+__device__ void final_pair (const sur_args_of<LEN>& a, uint32_t s, uint32_t p, int64_t end)
 {
 #pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
 	mtr_sur_pair* const st = &a.state[s].pr[p];
@@ -434,7 +480,16 @@ __device__ void final_pair (const mtr_sur_args& a, uint32_t s, uint32_t p)
 	double qp = 1.0;
 	bool flushed[2] = { false, false };
 	for (uint32_t i = 0; i < a.n_pieces; ++i) {
-		const Piece pc = piece_of (a, i);
+		Piece pc = piece_of (a, i);
+		bool ends_here = false;                                        // (LEN: the stream's last piece)
+		if constexpr (LEN) {
+			if (pc.b0 >= end) break;
+			if (end <= pc.b1) {
+				ends_here = true;
+				if ((uint64_t) end < a.n_frames) pc.closes = true;
+				pc.b1 = end;
+			}
+		}
 		const int64_t len = pc.b1 - pc.b0;
 		if (len != len_of) { qp = pow (q1, (double) len); len_of = len; }
 		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_SUR_PIECE + p * MTR_SUR_PIECE_PAIR;
@@ -454,7 +509,7 @@ __device__ void final_pair (const mtr_sur_args& a, uint32_t s, uint32_t p)
 		}
 		if (pc.after_period) flushed[0] = flushed[1] = false;
 		for (int j = 0; j < 3; ++j) z[j] = fma (qp, z[j], sum[j]);
-		const bool last = i + 1 == a.n_pieces;
+		const bool last = i + 1 == a.n_pieces || ends_here;
 		if (last) { zl = (float) el; zr = (float) er; }
 		if (!pc.closes) continue;
 		float f[3] = { (float) z[0], (float) z[1], (float) z[2] };
@@ -477,13 +532,19 @@ __device__ void final_pair (const mtr_sur_args& a, uint32_t s, uint32_t p)
 	st->corr = corr;
 }
 
-__global__ void k_sur_final (const mtr_sur_args a)
+template <bool LEN>
+__global__ void k_sur_final (const sur_args_of<LEN> a)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, per = a.n_channels + a.n_pairs;
 	if (i >= a.n_streams * per) return;
 	const uint32_t s = i / per, u = i % per;
-	if (u < a.n_channels) final_channel (a, s, u);
-	else final_pair (a, s, u - a.n_channels);
+	int64_t end = (int64_t) a.n_frames;
+	if constexpr (LEN) {
+		end = (int64_t) a.ends[s];
+		if (end == 0) return;                                          // closed, or closed by this call untouched
+	}
+	if (u < a.n_channels) final_channel<LEN> (a, s, u, end);
+	else final_pair<LEN> (a, s, u - a.n_channels, end);
 }
 
 }  // namespace
@@ -500,21 +561,23 @@ static void mtr_sur_geometry (float w1, uint32_t* warm, uint32_t* chunk)
 	*chunk = (MAX_TILES * TILE - *warm) & ~3u;
 }
 
-static int mtr_launch_sur (const mtr_sur_args& a, void* stream)
+// A: mtr_sur_args — the dense kernels — or mtr_sur_len_args
+template <typename A> static int mtr_launch_sur (const A& a, void* stream)
 {
+	constexpr bool LEN = std::is_same_v<A, mtr_sur_len_args>;
 	hipStream_t st = (hipStream_t) stream;
 	const dim3 g (a.n_pieces, a.n_streams), b (NT);
 	switch (a.n_channels) {
-	case 3: hipLaunchKernelGGL (k_sur_pieces<3>, g, b, 0, st, a); break;
-	case 4: hipLaunchKernelGGL (k_sur_pieces<4>, g, b, 0, st, a); break;
-	case 5: hipLaunchKernelGGL (k_sur_pieces<5>, g, b, 0, st, a); break;
-	case 6: hipLaunchKernelGGL (k_sur_pieces<6>, g, b, 0, st, a); break;
-	case 7: hipLaunchKernelGGL (k_sur_pieces<7>, g, b, 0, st, a); break;
-	case 8: hipLaunchKernelGGL (k_sur_pieces<8>, g, b, 0, st, a); break;
+	case 3: hipLaunchKernelGGL ((k_sur_pieces<3, LEN>), g, b, 0, st, a); break;
+	case 4: hipLaunchKernelGGL ((k_sur_pieces<4, LEN>), g, b, 0, st, a); break;
+	case 5: hipLaunchKernelGGL ((k_sur_pieces<5, LEN>), g, b, 0, st, a); break;
+	case 6: hipLaunchKernelGGL ((k_sur_pieces<6, LEN>), g, b, 0, st, a); break;
+	case 7: hipLaunchKernelGGL ((k_sur_pieces<7, LEN>), g, b, 0, st, a); break;
+	case 8: hipLaunchKernelGGL ((k_sur_pieces<8, LEN>), g, b, 0, st, a); break;
 	default: return -1;
 	}
 	const uint32_t n = a.n_streams * (a.n_channels + a.n_pairs);
-	hipLaunchKernelGGL (k_sur_final, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
+	hipLaunchKernelGGL (k_sur_final<LEN>, dim3 ((n + 63) / 64), dim3 (64), 0, st, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -551,7 +614,9 @@ static int surround_create (mtr_engine* e)
 }
 
 // The blocks of the reading series are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
-static int surround_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds&)
+// A call with ends (mtr_engine_process_*_any, or any call once a stream of the view is closed) takes the LEN instantiations; every other
+// call the dense ones, as ever.
+static int surround_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	const size_t vo = c.off;
 	const uint64_t P = e->su.ser.period;
@@ -584,7 +649,12 @@ static int surround_step (mtr_engine* e, const Call& c, Cursors& nx, const Strea
 		sa.s_peak = e->su.s_peak.p + vo * cap * sa.n_channels;
 		sa.s_corr = e->su.s_corr.p + vo * cap * MTR_SUR_PAIRS;
 	}
-	if (mtr_launch_sur (sa, c.st)) return fail (MTR_ERR_HIP, "k_sur launch");
+	if (se.ends) {
+		mtr_sur_len_args la;
+		static_cast<mtr_sur_args&> (la) = sa;
+		la.ends = se.ends; la.falls = se.km_fall;
+		if (mtr_launch_sur (la, c.st)) return fail (MTR_ERR_HIP, "k_sur launch (ends)");
+	} else if (mtr_launch_sur (sa, c.st)) return fail (MTR_ERR_HIP, "k_sur launch");
 	nx.su = series_advance (e->pos.su, P, c.n_frames);
 	return MTR_OK;
 }
@@ -630,8 +700,9 @@ static void surround_hdr_take (mtr_engine* e, const void* in)
 }
 
 static constinit BlobHeader surround_hdr = { 0, SUR_HDR_BYTES, SUR_CORRUPT, surround_hdr_write, surround_hdr_check, surround_hdr_take };
+static SeriesView surround_series (mtr_engine* e) { return { &e->su.ser, &Cursors::su, &e->su.points }; }
 constinit SideMeter surround_meter = { MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                             surround_create, mtr_engine_surround_reset, surround_step, surround_sections, &surround_hdr };
+                                             surround_create, mtr_engine_surround_reset, surround_step, surround_sections, &surround_hdr, surround_series };
 
 extern "C" {
 
@@ -648,6 +719,7 @@ int mtr_engine_surround_reset (mtr_engine* e)
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemset (e->su.state.p, 0, S * sizeof (mtr_sur_state)));   // kmeterdsp.cc:33-40, stcorrdsp.cc:33-36
 	e->pos.su = {};
+	e->su.points.assign (S, 0);
 	e->pos.su_fpp = 0;
 	e->pos.su_fall = 0.f;
 	return MTR_OK;
@@ -733,8 +805,15 @@ int mtr_engine_surround_series (mtr_engine* e, uint32_t first, uint32_t count, f
 	if ((rc = wait_stream (e))) return rc;
 	const size_t C = e->cfg.n_channels;
 	const struct { float* out; const float* src; size_t w; } row[3] = { { level, e->su.s_level.p, C }, { peak, e->su.s_peak.p, C }, { corr, e->su.s_corr.p, MTR_SUR_PAIRS } };
-	for (const auto& q : row)
-		if (q.out && (rc = series_fetch (q.out, q.src, q.w, first, e->su.ser.cap, capacity, take, count))) return rc;
+	for (const auto& q : row) {
+		if (!q.out) continue;
+		if ((rc = series_fetch (q.out, q.src, q.w, first, e->su.ser.cap, capacity, take, count))) return rc;
+		// (a stream that was closed has fewer points of its own than the open ones: 0.0f behind them, whatever the ring still holds there)
+		for (uint32_t i = 0; i < count; ++i) {
+			const uint64_t own = e->su.points[first + i];
+			if (own < take) memset (q.out + ((size_t) i * capacity + (size_t) own) * q.w, 0, (take - (size_t) own) * q.w * sizeof (float));
+		}
+	}
 	return MTR_OK;
 }
 

@@ -140,6 +140,10 @@ def _load():
         L.mtr_engine_process_device_tpb.argtypes = [vp, vp, u64, u64, vp, vp]
         L.mtr_engine_process_host_tpb.argtypes = [vp, vp, u64, u64, vp]
         L.mtr_engine_tpb_points.argtypes = [vp, u32, u32, vp]
+    if hasattr(L, "mtr_engine_process_device_any"):            # (an addition inside ABI version 2: track lengths for the scope and the surround meter)
+        L.mtr_engine_process_device_any.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_any.argtypes = [vp, vp, u64, u64, vp]
+        L.mtr_engine_scope_points.argtypes = [vp, u32, u32, vp, vp]
     if hasattr(L, "mtr_engine_pcm_stats"):                     # (an addition inside ABI version 2: integer PCM in)
         L.mtr_engine_process_host_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp]
         L.mtr_engine_process_device_pcm.argtypes = [vp, vp, C.c_int, u64, u64, vp, vp]
@@ -563,7 +567,8 @@ class Engine:
     _FAMILY = {"lengths": ("mtr_engine_stream_frames", "per-stream lengths"), "tracks": ("mtr_engine_process_device_tracks", "track lengths"),
                "ragged": ("mtr_engine_process_device_ragged", "ragged batches"),
                "ends": ("mtr_engine_process_device_ends", "track lengths for the 30-band bank"),
-               "tpb": ("mtr_engine_process_device_tpb", "track lengths for the true-peak bar")}
+               "tpb": ("mtr_engine_process_device_tpb", "track lengths for the true-peak bar"),
+               "any": ("mtr_engine_process_device_any", "track lengths for the scope and the surround meter")}
 
     def _frames(self, frames, family):
         """frames as contiguous uint64 [S], for a call of `family`"""
@@ -614,8 +619,9 @@ class Engine:
         self._host_frames("ragged", x, frames)
 
     def series_points(self, meter, first=0, count=None):
-        """[count] uint64: the points each stream's own STCORR, NEEDLE or KMETER series (meter: METER_STCORR / METER_NEEDLE / METER_KMETER) has got since reset,
-        dropped ones included — of a stream that a ragged call closed, its whole blocks and the truncated one."""
+        """[count] uint64: the points each stream's own STCORR, NEEDLE, KMETER or SURROUND series (meter: METER_STCORR / METER_NEEDLE / METER_KMETER /
+        METER_SURROUND) has got since reset, dropped ones included — of a stream that a call with track lengths closed, its whole blocks and
+        the truncated one."""
         self._frames(np.zeros(self.n_streams, np.uint64), "ragged")
         count = self.n_streams - first if count is None else count
         out = np.zeros(count, np.uint64)
@@ -657,6 +663,29 @@ class Engine:
         out = np.zeros(count, np.uint64)
         _check(lib.mtr_engine_tpb_points(self._h, first, count, out.ctypes.data), "tpb_points")
         return out
+
+    def process_device_any(self, ptr, n_frames, frames, stride=None, stream=0):
+        """process_device_tpb() for engines that also hold SCOPE, and for SURROUND engines (3 .. 8 channels, beside EBU / TRUEPEAK up to
+        5): stream s is metered up to frames[s] <= n_frames — the scope runs the analyses that end at or before its last frame, the
+        surround meter one last sur_run of the frames the stream has of its block — as under a host that stops feeding it there;
+        frames[s] < n_frames closes it.  (One call is refused: SURROUND with a period, the open block inside a group of four frames, and
+        a stream that ends before that group completes.)"""
+        self._device_frames("any", ptr, n_frames, frames, stride, stream)
+
+    def process_any(self, x, frames):
+        """process() with track lengths for the scope and the surround meter: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        self._host_frames("any", x, frames)
+
+    def scope_points(self, first=0, count=None):
+        """(analyses, points), [count] uint64 each: the analyses each stream's own SCOPE has run since reset and the points its own
+        series has got (dropped ones included; 0 without a series) — of a stream that process_*_any closed, those that end at or
+        before its last frame."""
+        if not hasattr(lib, "mtr_engine_scope_points"):
+            raise EngineError(f"{lib_path} has no {self._FAMILY['any'][1]}: rebuild it")
+        count = self.n_streams - first if count is None else count
+        an, pt = np.zeros(count, np.uint64), np.zeros(count, np.uint64)
+        _check(lib.mtr_engine_scope_points(self._h, first, count, an.ctypes.data, pt.ctypes.data), "scope_points")
+        return an, pt
 
     def process_pcm(self, x, format=None, frames=None):
         """process() for host integer PCM, decoded on the GPU: x int16 or int32 [S, T, C] (or [S, T] mono; the format is inferred),
