@@ -34,7 +34,8 @@ extern "C" {
  *    mtr_engine_scope_configure, _scope_config, _scope_read, _scope_analyses, _scope_reset; mtr_engine_kmeter_set_period, _kmeter_period,
  *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series; mtr_engine_process_device_ends, _process_host_ends,
  *    _spectr_points; mtr_engine_scope_set_series, _scope_series_config, _scope_series, mtr_scope_series_cut; mtr_engine_process_device_any,
- *    _process_host_any, _scope_points):
+ *    _process_host_any, _scope_points; MTR_METER_GONIO, mtr_gonio_derive, mtr_engine_gonio_configure, _gonio_config, _gonio_set_gain,
+ *    _gonio_image, _gonio_read, _gonio_blocks, _gonio_series, _gonio_image_clear, _gonio_reset):
  *    + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
@@ -69,6 +70,8 @@ extern "C" {
 #define MTR_METER_SCOPE      0x8000u /* the stereo / frequency scope's and the phase wheel's analysis: windowed FFT, level, balance, phase per bin
                                     * (gui/stereoscope.c:705-741, gui/phasewheel.c:1307-1339, gui/fft.c), stereo, see mtr_scope.h; 0x4000 is no
                                     * meter (tests/test_surround_cpu.py holds it refused) */
+#define MTR_METER_GONIO      0x20000u /* the goniometer's M/S point image, auto gain and reading series (gui/goniometer.c:299-538), stereo, see
+                                    * mtr_gonio.h; 0x10000 is no meter (tests/test_scope_cpu.py holds it refused) */
 
 #define MTR_HIST_LEN   751          /* src/uris.h:45  HIST_LEN */
 #define MTR_NBANDS     30           /* src/spectrumlv2.c:33  FILTER_COUNT */
@@ -403,6 +406,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
  * _read / _analyses / _reset; with a reading series (mtr_scope_series.h, included from there): mtr_engine_scope_set_series /
  * _series_config / _series and mtr_scope_series_cut */
 #include "mtr_scope.h"
+
+/* The goniometer for a batch (MTR_METER_GONIO) — the M/S point image of draw_rb as counts per cell, its auto gain, and a point per display
+ * update: mtr_gonio_derive and mtr_engine_gonio_configure / _config / _set_gain / _image / _read / _blocks / _series / _image_clear / _reset */
+#include "mtr_gonio.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

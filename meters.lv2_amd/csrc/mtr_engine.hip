@@ -266,7 +266,7 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 	if (cfg->n_streams == 0 || !(cfg->sample_rate >= 8000.f) || cfg->meters == 0) return fail (MTR_ERR_ARG, "mtr_engine_create: n_streams / sample_rate / meters");
 	if (cfg->n_channels < 1 || cfg->n_channels > MTR_MAX_ENGINE_CHANNELS) return fail (MTR_ERR_ARG, "n_channels must be 1 .. 5 (6 .. 8: MTR_METER_SURROUND alone)");
 	if (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_SPECTR30 | MTR_METER_TPBALLIST | MTR_METER_BITSTATS
-	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_STCORR | MTR_METER_NEEDLE | MTR_METER_SURROUND | MTR_METER_SCOPE))
+	                               | MTR_METER_SIGDIST | MTR_METER_DR14 | MTR_METER_KMETER | MTR_METER_STCORR | MTR_METER_NEEDLE | MTR_METER_SURROUND | MTR_METER_SCOPE | MTR_METER_GONIO))
 		return fail (MTR_ERR_ARG, "unknown bits in the meters mask");
 	// 6 .. 8 channels: the surround meter alone (no other meter has a kernel that wide; with EBU / TRUEPEAK it stays the argument
 	// error it was: Ebu_r128_proc::MAXCH)
@@ -280,6 +280,8 @@ int mtr_engine_create (const mtr_config* cfg, mtr_engine** out)
 		return fail (MTR_ERR_UNSUPPORTED, "STCORR is the correlation of a stereo pair: n_channels 2");
 	if (cfg->n_channels == 1 && (cfg->meters & MTR_METER_SCOPE))
 		return fail (MTR_ERR_UNSUPPORTED, "SCOPE is the analysis of a stereo pair: n_channels 2");
+	if (cfg->n_channels != 2 && (cfg->meters & MTR_METER_GONIO))
+		return fail (MTR_ERR_UNSUPPORTED, "GONIO is the M/S picture of a stereo pair: n_channels 2");
 	// 3 .. 5 channels: EBU R128 and true peak (Ebu_r128_proc::init takes up to five, ebumeter/ebu_r128_proc.h:26), and the surround meter
 	if (cfg->n_channels > 2 && (cfg->meters & ~(uint32_t) (MTR_METER_EBU | MTR_METER_TRUEPEAK | MTR_METER_SURROUND)))
 		return fail (MTR_ERR_UNSUPPORTED, "3 .. 5 channels: only EBU, TRUEPEAK and SURROUND meter them");

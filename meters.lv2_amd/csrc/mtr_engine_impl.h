@@ -1,6 +1,6 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
 // EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
-// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip, mtr_scope.hip, mtr_tpb.hip), and mtr_loudlog.hip (the host
+// lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip, mtr_scope.hip, mtr_tpb.hip, mtr_gonio.hip), and mtr_loudlog.hip (the host
 // side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
 #ifndef MTR_ENGINE_IMPL_H
@@ -115,6 +115,7 @@ struct Cursors {
 	uint64_t seg_calls = 0, seg_frames = 0;   // calls / frames k_seg took
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 	SeriesPos tb;                 // TPBALLIST with a period: where its reading series stands (mtr_series.h)
+	SeriesPos go;                 // GONIO: frames into the open display update, updates completed since reset (mtr_series.h)
 };
 
 // per-stream state of the side meters: defined where their kernels are
@@ -334,6 +335,18 @@ struct mtr_engine {
 		DevBuf<float>              s_level, s_peak;   // [S][cap][C]
 		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (mtr_engine_process_*_tpb: mtr_tpb.h)
 	} tb;
+	struct Gonio {                              // GONIO (mtr_gonio.hip)
+		DevBuf<unsigned char>      state;       // [S] of { mtr_gonio_state, uint32 image [G][G] }, `pitch` bytes each
+		DevBuf<float>              series;      // [3][S][cap]: gain (f32), drawn, clipped (u32) per display update
+		DevBuf<uint16_t>           codes;       // [S][code_pitch] the cell codes of one piece of a call: k_gonio_points writes, k_gonio_image reads
+		mtr_gonio_config           cfg;         // resolved: no zeros left
+		mtr_gonio_derived          der;
+		SeriesCfg                  ser;         // P (never 0), points per stream the series holds
+		size_t                     pitch = 0;
+		uint32_t                   code_pitch = 0;
+		std::vector<Event>         ev;          // while mtr_engine_gonio_timing is on: three per piece, around its two kernels
+		bool                       timed = false;
+	} go;
 };
 
 constexpr int EV_PER_CALL = 7;
@@ -430,12 +443,13 @@ struct SideMeter {
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
 extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
-                 bank_series_meter, scope_series_meter, tpb_series_meter;
+                 bank_series_meter, scope_series_meter, tpb_series_meter, gonio_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
                                                     &kmeter_series_meter,     // (KMETER's second row: nothing but the blob section of its open block, behind every older one)
                                                     &bank_series_meter,       // (SPECTR30's second row, likewise)
                                                     &scope_series_meter,      // (SCOPE's second row, likewise)
-                                                    &tpb_series_meter };      // (TPBALLIST, whose kernel the call launches itself: the series' reset and the open block's section)
+                                                    &tpb_series_meter,        // (TPBALLIST, whose kernel the call launches itself: the series' reset and the open block's section)
+                                                    &gonio_meter };
 // the points of each of streams [first, first + count) in the series of the meter with `bit`, which the engine holds and which keeps such counts
 void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points);
 

@@ -17,6 +17,7 @@ METER_STCORR = 0x200                       # (0x100 is no meter)
 METER_NEEDLE = 0x800                       # VU, IEC I / II PPM, M/S PPM: include/mtr_needle.h (0x400 is no meter either)
 METER_SURROUND = 0x2000                    # sur_run: C K-meters + four pair correlations, 3 .. 8 channels: include/mtr_surround.h (0x1000 is no meter)
 METER_SCOPE = 0x8000                       # the stereoscope's / phase wheel's FFT analysis, stereo: include/mtr_scope.h (0x4000 is no meter)
+METER_GONIO = 0x20000                      # the goniometer's M/S point image, auto gain and series, stereo: include/mtr_gonio.h (0x10000 is no meter)
 NEEDLE_VU, NEEDLE_IEC1, NEEDLE_IEC2, NEEDLE_MS = 1, 2, 4, 8
 BIM_LAST, DIST_BIN = 584, 361
 HIST_LEN, NBANDS = 751, 30
@@ -47,6 +48,19 @@ class _Config(C.Structure):
                 ("n_channels", C.c_uint32), ("sample_rate", C.c_float), ("device", C.c_int32),
                 ("max_frames", C.c_uint32), ("tune_run", C.c_uint32), ("tune_segments", C.c_uint32),
                 ("tune_layout", C.c_uint32), ("tune_fir", C.c_uint32), ("tune_prune", C.c_uint32)]
+
+
+class GonioConfig(C.Structure):
+    """mtr_gonio_config (include/mtr_gonio.h); zeros select the defaults"""
+    _fields_ = [("struct_size", C.c_uint32), ("period_frames", C.c_uint32), ("capacity", C.c_uint32), ("shift", C.c_uint32),
+                ("autogain", C.c_uint32), ("gain", C.c_float), ("point_width", C.c_float), ("g_attack", C.c_float), ("g_decay", C.c_float),
+                ("g_target", C.c_float), ("g_rms", C.c_float), ("tune_piece", C.c_uint32)]
+
+
+class GonioDerived(C.Structure):
+    """mtr_gonio_derived (include/mtr_gonio.h)"""
+    _fields_ = [("period_frames", C.c_uint32), ("G", C.c_uint32), ("hpw", C.c_float), ("attack", C.c_float * 2), ("g_target", C.c_float),
+                ("g_rms", C.c_float)]
 
 
 class PlanInfo(C.Structure):
@@ -217,6 +231,18 @@ def _load():
         L.mtr_engine_scope_series_config.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.mtr_engine_scope_series.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.mtr_scope_series_cut.argtypes = [u32, u32, u32, u32, u64, C.POINTER(u64), C.POINTER(u64)]
+    if hasattr(L, "mtr_engine_gonio_image"):                   # (an addition inside ABI version 2: the goniometer)
+        L.mtr_gonio_derive.argtypes = [C.POINTER(GonioConfig), C.c_double, C.POINTER(GonioDerived)]
+        L.mtr_engine_gonio_configure.argtypes = [vp, C.POINTER(GonioConfig)]
+        L.mtr_engine_gonio_config.argtypes = [vp, C.POINTER(GonioConfig), C.POINTER(GonioDerived)]
+        L.mtr_engine_gonio_set_gain.argtypes = [vp, f32]
+        L.mtr_engine_gonio_image.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+        L.mtr_engine_gonio_read.argtypes = [vp, u32, u32, vp, vp, vp]
+        L.mtr_engine_gonio_blocks.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.mtr_engine_gonio_series.argtypes = [vp, u32, u32, u64, u32, vp, vp, vp]
+        L.mtr_engine_gonio_image_clear.argtypes = [vp]
+        L.mtr_engine_gonio_reset.argtypes = [vp]
+        L.mtr_engine_gonio_timing.argtypes = [vp, C.c_int, C.POINTER(f32), C.POINTER(f32), C.POINTER(u32)]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -333,6 +359,32 @@ def series_cut(fill, period, n_frames, frames):
     whole, partial = C.c_uint64(), C.c_uint32()
     _check(lib.mtr_series_cut(int(fill), int(period), int(n_frames), int(frames), C.byref(whole), C.byref(partial)), "mtr_series_cut")
     return whole.value, partial.value
+
+
+def _need_gonio():
+    if not hasattr(lib, "mtr_engine_gonio_image"):
+        raise EngineError(f"{lib_path} has no goniometer (MTR_METER_GONIO): rebuild it")
+
+
+def gonio_config(period_frames=0, capacity=0, shift=0, autogain=0, gain=0.0, point_width=0.0, dials=None, tune_piece=0):
+    """A GonioConfig; zeros select the defaults.  autogain: False / 0 off, True / 1 on with the reference's dials; dials = (attack, decay,
+    target, rms), 0 .. 100 each, selects autogain 2."""
+    c = GonioConfig(struct_size=C.sizeof(GonioConfig), period_frames=int(period_frames), capacity=int(capacity), shift=int(shift),
+                    autogain=int(autogain), gain=float(gain), point_width=float(point_width), tune_piece=int(tune_piece))
+    if dials is not None:
+        c.autogain = 2
+        c.g_attack, c.g_decay, c.g_target, c.g_rms = [float(v) for v in dials]
+    return c
+
+
+def gonio_derive(rate, config=None, **kw):
+    """GonioDerived for `config` (or gonio_config (**kw)) at `rate`: P, G, hpw, the two attack factors, g_target, g_rms
+    (mtr_gonio_derive; no engine, no device)."""
+    _need_gonio()
+    c = config if config is not None else gonio_config(**kw)
+    d = GonioDerived()
+    _check(lib.mtr_gonio_derive(C.byref(c), float(rate), C.byref(d)), "mtr_gonio_derive")
+    return d
 
 
 def needle_coef(kind, fs):
@@ -1153,6 +1205,72 @@ class Engine:
 
     def state_bytes(self, count):
         return int(lib.mtr_engine_state_bytes(self._h, count))
+
+    # ---- the goniometer (METER_GONIO, include/mtr_gonio.h) ----
+    def gonio_configure(self, config=None, **kw):
+        """config: a GonioConfig, or the keywords of gonio_config ().  Only before the first process call; resets the meter."""
+        _need_gonio()
+        c = config if config is not None else gonio_config(**kw)
+        _check(lib.mtr_engine_gonio_configure(self._h, C.byref(c)), "gonio_configure")
+
+    def gonio_config(self):
+        """(GonioConfig with every zero resolved, GonioDerived)"""
+        _need_gonio()
+        c, d = GonioConfig(), GonioDerived()
+        _check(lib.mtr_engine_gonio_config(self._h, C.byref(c), C.byref(d)), "gonio_config")
+        return c, d
+
+    def gonio_set_gain(self, gain):
+        _need_gonio()
+        _check(lib.mtr_engine_gonio_set_gain(self._h, float(gain)), "gonio_set_gain")
+
+    def gonio_image(self, first=0, count=None):
+        """(img uint32 [count, G, G], drawn, clipped, skipped uint64 [count])"""
+        count = self.n_streams - first if count is None else count
+        G = self.gonio_config()[1].G
+        img = np.zeros((count, G, G), np.uint32)
+        cnt = [np.zeros(count, np.uint64) for _ in range(3)]
+        _check(lib.mtr_engine_gonio_image(self._h, first, count, img.ctypes.data, *[c.ctypes.data for c in cnt]), "gonio_image")
+        return (img, *cnt)
+
+    def gonio_read(self, first=0, count=None):
+        """(gain [count], lp [count, 2], last [count, 2] = last_x, last_y), float32"""
+        _need_gonio()
+        count = self.n_streams - first if count is None else count
+        g, lp, last = np.zeros(count, np.float32), np.zeros((count, 2), np.float32), np.zeros((count, 2), np.float32)
+        _check(lib.mtr_engine_gonio_read(self._h, first, count, g.ctypes.data, lp.ctypes.data, last.ctypes.data), "gonio_read")
+        return g, lp, last
+
+    def gonio_blocks(self):
+        """(display updates completed since reset, those of them the series holds)"""
+        _need_gonio()
+        b, h = C.c_uint64(), C.c_uint64()
+        _check(lib.mtr_engine_gonio_blocks(self._h, C.byref(b), C.byref(h)), "gonio_blocks")
+        return b.value, h.value
+
+    def gonio_series(self, first=0, count=None, start=0, n=None):
+        """(gain float32, drawn uint32, clipped uint32), each [count, n]: points [start, start + n) of the series (n None: all it holds
+        from `start` on)"""
+        count = self.n_streams - first if count is None else count
+        n = self.gonio_blocks()[1] - start if n is None else n
+        g, d, c = np.zeros((count, n), np.float32), np.zeros((count, n), np.uint32), np.zeros((count, n), np.uint32)
+        _check(lib.mtr_engine_gonio_series(self._h, first, count, int(start), int(n), g.ctypes.data, d.ctypes.data, c.ctypes.data), "gonio_series")
+        return g, d, c
+
+    def gonio_image_clear(self):
+        _need_gonio()
+        _check(lib.mtr_engine_gonio_image_clear(self._h), "gonio_image_clear")
+
+    def gonio_reset(self):
+        _need_gonio()
+        _check(lib.mtr_engine_gonio_reset(self._h), "gonio_reset")
+
+    def gonio_timing(self, enable):
+        """(k_gonio_points ms, k_gonio_image ms, pieces) summed since the last query; enable: go on timing or stop"""
+        _need_gonio()
+        p, i, n = C.c_float(), C.c_float(), C.c_uint32()
+        _check(lib.mtr_engine_gonio_timing(self._h, int(bool(enable)), C.byref(p), C.byref(i), C.byref(n)), "gonio_timing")
+        return p.value, i.value, n.value
 
     def state_export(self, first=0, count=None):
         """Everything streams [first, first + count) carry from call to call, as one opaque blob (bytes)."""
