@@ -410,6 +410,9 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The goniometer for a batch (MTR_METER_GONIO) — the M/S point image of draw_rb as counts per cell, its auto gain, and a point per display
  * update: mtr_gonio_derive and mtr_engine_gonio_configure / _config / _set_gain / _image / _read / _blocks / _series / _image_clear / _reset */
 #include "mtr_gonio.h"
+/* Track lengths for the goniometer, beside the stereo meters of _any: mtr_engine_process_device_gonio_ends / _host_gonio_ends, mtr_gonio_cut
+ * and mtr_engine_gonio_points, declared in mtr_gonio_ends.h */
+#include "mtr_gonio_ends.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

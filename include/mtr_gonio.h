@@ -14,7 +14,8 @@ extern "C" {
 #define MTR_GONIO_BOUNDS 373       /* gui/goniometer.c:56  GM_BOUNDS: the surface is 373 x 373 */
 
 /* The goniometer for a batch (MTR_METER_GONIO; stereo engines only — a pair of a wider frame goes through mtr_engine_set_frame_layout).
- * Combines with every other stereo meter.  The calls with per-stream ends (mtr_engine_process_*_lengths .. _any) refuse the meter.
+ * Combines with every other stereo meter.  Track lengths: mtr_engine_process_device_gonio_ends / _host_gonio_ends (mtr_gonio_ends.h); the six
+ * older pairs of calls with per-stream ends (mtr_engine_process_*_lengths .. _any) refuse the meter.
  * What is reproduced is draw_rb in points mode (s_line false), without oversampling (src_fact 1), with infinite persistence
  * (persist >= 1.0, gui/goniometer.c:327) and without inflate, in the reference's f32 / double operations and their order: per frame
  * (:401-449) the one-pole per channel, lp += hpw (d - lp), lp += 1e-12f; ax = lp0 - lp1, ay = lp0 + lp1; x = 186.5f - gain ax 100.f, y

@@ -117,6 +117,8 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 	// (once a stream is closed every call runs the bank's ENDS kernels, whose ends are 32 bits: mtr_ends.h)
 	if ((e->cfg.meters & MTR_METER_SPECTR30) && e->n_closed && n_frames > 0xFFFFFFFEull)
 		return fail (MTR_ERR_ARG, "SPECTR30 with a closed stream: n_frames per call must be < 2^32 - 1");
+	if ((e->cfg.meters & MTR_METER_GONIO) && e->n_closed && n_frames > 0xFFFFFFFEull)   // (likewise: mtr_gonio_ends.h)
+		return fail (MTR_ERR_ARG, "GONIO with a closed stream: n_frames per call must be < 2^32 - 1");
 	if ((e->cfg.meters & MTR_METER_TPBALLIST) && n_frames >= 0x7ffff000ull) return fail (MTR_ERR_ARG, "TPBALLIST: n_frames per call must be < 2^31 - 4096");
 	if ((e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)) && n_frames >= 0xFFFFFFFFull) return fail (MTR_ERR_ARG, "n_frames per call must be < 2^32 - 1");
 	return MTR_OK;
@@ -160,6 +162,8 @@ struct CallRun {
 	const uint32_t* d_lim = nullptr;
 	const uint32_t* d_from = nullptr;
 	const float*    d_fall = nullptr;  // KMETER: the fall-back factor of each stream that ends inside the call
+	const uint32_t* d_gcut = nullptr;  // GONIO: [cut S | closing S | attack S x 2] (StreamEnds) ...
+	uint64_t        go_last = 0;       // ... and the last call frame any stream of the view draws
 	bool         any_from = false;     // k_seg left a closing stream's last peaks to k_kwtp16
 	LenSlot*     ls = nullptr;
 	int          tb = 0;               // tile_power buffer of the call
@@ -231,13 +235,14 @@ struct CallRun {
 
 	// [ends S | frag_lim S | from_tile S | km_fall S] of a ragged call into the next slot of the lengths ring, uploaded on the call's stream
 	// (an engine without EBU / TRUEPEAK has no plan: its frag_lim / from_tile are never read; km_fall: KMETER and SURROUND engines only —
-	// no engine holds both)
+	// no engine holds both; GONIO engines: [cut S | closing S | attack S x 2] behind those, gonio_cut's answers per stream)
 	int upload_lengths ()
 	{
 		const SegPlan& sp = r.sp;
 		const uint32_t S = c.cnt;
-		const bool fused = ebu || tp, km = e->cfg.meters & MTR_METER_KMETER, su = e->cfg.meters & MTR_METER_SURROUND;
-		const size_t words = (size_t) (km || su ? 4 : 3) * S;
+		const bool fused = ebu || tp, km = e->cfg.meters & MTR_METER_KMETER, su = e->cfg.meters & MTR_METER_SURROUND, go = e->cfg.meters & MTR_METER_GONIO;
+		const size_t gw = (size_t) (km || su ? 4 : 3) * S;            // GONIO's four arrays lie behind the older ones
+		const size_t words = gw + (go ? (size_t) 4 * S : 0);
 		const int slot = (e->len_cur + 1) % LEN_SLOTS;
 		ls = &e->len_slot[slot];
 		for (int i = 0; i < 2; ++i) if (ls->pending[i]) { HIPCHK (hipEventSynchronize (ls->done[i].v)); ls->pending[i] = false; }
@@ -247,9 +252,18 @@ struct CallRun {
 		uint32_t* const h_lim = h_end + S;
 		uint32_t* const h_from = h_end + 2 * (size_t) S;
 		float* const h_fall = reinterpret_cast<float*> (h_end + 3 * (size_t) S);
+		uint32_t* const h_gcut = h_end + gw;
 		for (uint32_t i = 0; i < S; ++i) {
 			const uint64_t f = e->closed[c.off + i] ? 0 : c.frames ? c.frames[i] : c.n_frames;
 			h_end[i] = (uint32_t) f;
+			if (go) {
+				// (the cuts are taken from where the CALL started, e->pos: every chunk of a host call sees the same ones)
+				const GonioCut k = gonio_cut (e->pos.go.fill, e->go.cfg.period_frames, (double) e->cfg.sample_rate, c.n_frames, f, e->go.cfg);
+				h_gcut[i] = f == c.n_frames ? 0xFFFFFFFFu : (uint32_t) k.drawn;     // (MTR_GONIO_OPEN: the stream does not end in this call)
+				h_gcut[S + i] = k.closing;
+				memcpy (h_gcut + 2 * (size_t) S + 2 * (size_t) i, k.attack, sizeof (k.attack));
+				go_last = std::max (go_last, k.drawn);
+			}
 			// (a closing stream's process () is one of f frames: kmeterdsp.cc:60-65 with fpp = f; every other stream takes the cursor's)
 			// (with a period: one of the frames it has of the block it ends in, if it ends inside one)
 			const uint64_t kp = e->km.ser.period, kf = kp ? (e->pos.km.fill + f) % kp : f;
@@ -274,6 +288,7 @@ struct CallRun {
 		e->len_cur = slot;
 		d_ends = ls->dev.p; d_lim = d_ends + S; d_from = d_ends + 2 * (size_t) S;
 		if (km || su) d_fall = reinterpret_cast<const float*> (d_ends + 3 * (size_t) S);
+		if (go) d_gcut = d_ends + gw;
 		return MTR_OK;
 	}
 
@@ -514,7 +529,8 @@ struct CallRun {
 		}
 		if ((rc = mark (4, c.st))) return rc;
 
-		const StreamEnds se { d_ends, d_fall };                       // (null on a dense call)
+		const uint32_t* const gclose = d_gcut ? d_gcut + c.cnt : nullptr;
+		const StreamEnds se { d_ends, d_fall, d_gcut, gclose, d_gcut ? reinterpret_cast<const float*> (d_gcut + 2 * (size_t) c.cnt) : nullptr, go_last };   // (null on a dense call)
 		for (const SideMeter* m : SIDE_METERS)
 			if ((meters & m->bits) && m->step && (rc = m->step (e, c, nx, se))) return rc;
 		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
@@ -535,6 +551,7 @@ struct CallRun {
 			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
 			e->metered[g] += f;
 			if (meters & MTR_METER_SCOPE) scope_count (e, g, f);
+			if (meters & MTR_METER_GONIO) gonio_count (e, g, c.n_frames, f);
 			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
 			for (const SideMeter* m : SIDE_METERS) {
 				if (!(meters & m->bits) || !m->series) continue;
@@ -722,8 +739,9 @@ struct Family {
 	bool        no_km_series;    // _tracks: a KMETER engine with a period is refused
 	bool        bank_ends;       // _ends: at most two channels; 32-bit ends with SPECTR30
 	bool        wide = false;    // _any: ... but the channels are whatever mtr_engine_create accepted for the engine's meters
+	uint32_t    need = 0;        // _gonio_ends: the engine holds this meter; its cuts are 32 bits whatever else it holds
 };
-enum { LENGTHS, TRACKS, RAGGED, ENDS, TPB, ANY };
+enum { LENGTHS, TRACKS, RAGGED, ENDS, TPB, ANY, GONIO_ENDS };
 constexpr Family FAMILIES[] = {
 	{ "lengths", LENGTHS_METERS, "per-stream lengths: EBU / TRUEPEAK engines only", "per-stream lengths: frames[s] > n_frames", false, false },
 	{ "tracks", TRACKS_METERS, "track lengths: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST engines only", "track lengths: frames[s] > n_frames", true, false },
@@ -738,12 +756,18 @@ constexpr Family FAMILIES[] = {
 	{ "any", ANY_METERS,
 	  "track lengths for every meter: EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 / TPBALLIST / SCOPE / SURROUND engines only",
 	  "track lengths for every meter: frames[s] > n_frames", false, true, true },
+	// (the seventh, mtr_gonio_ends.h: the goniometer beside the stereo meters of _any — SURROUND needs three channels, GONIO two)
+	{ "gonio_ends", ANY_METERS | MTR_METER_GONIO,
+	  "track lengths for the goniometer: stereo engines that hold GONIO, beside EBU / TRUEPEAK / DR14 / KMETER / BITSTATS / SIGDIST / STCORR / NEEDLE / SPECTR30 / TPBALLIST / SCOPE only",
+	  "track lengths for the goniometer: frames[s] > n_frames", false, true, true, MTR_METER_GONIO },
 };
 
 static int family_check (const mtr_engine* e, const Family& fam, uint64_t n_frames, const uint64_t* frames)
 {
 	const uint32_t meters = e->cfg.meters;
-	if ((meters & ~fam.meters) || !(meters & fam.meters) || (fam.bank_ends && !fam.wide && e->cfg.n_channels > 2)) return fail (MTR_ERR_UNSUPPORTED, fam.unsupported);
+	if ((meters & ~fam.meters) || !(meters & fam.meters) || (fam.bank_ends && !fam.wide && e->cfg.n_channels > 2) || (fam.need && !(meters & fam.need)))
+		return fail (MTR_ERR_UNSUPPORTED, fam.unsupported);
+	if (fam.need && n_frames > 0xFFFFFFFEull) return fail (MTR_ERR_ARG, "track lengths for the goniometer: n_frames per call must be < 2^32 - 1");
 	if (fam.no_km_series && (meters & MTR_METER_KMETER) && e->km.ser.period)
 		return fail (MTR_ERR_UNSUPPORTED, "track lengths: a KMETER engine with a period keeps a reading series (mtr_engine_process_*_ragged)");
 	// (SURROUND with a period, a block open on entry that stands inside a group of four frames, and a stream that ends before that group
@@ -812,6 +836,16 @@ int mtr_engine_process_device_any (mtr_engine* e, const float* d_audio, uint64_t
 int mtr_engine_process_host_any (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
 	return frames_ends (e, ANY, true, h_audio, n_frames, stride, frames, nullptr);
+}
+
+int mtr_engine_process_device_gonio_ends (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
+{
+	return frames_ends (e, GONIO_ENDS, false, d_audio, n_frames, stride, frames, hip_stream);
+}
+
+int mtr_engine_process_host_gonio_ends (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
+{
+	return frames_ends (e, GONIO_ENDS, true, h_audio, n_frames, stride, frames, nullptr);
 }
 
 int mtr_engine_process_host_lengths (mtr_engine* e, const float* h_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames)

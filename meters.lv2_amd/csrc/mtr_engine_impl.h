@@ -346,6 +346,7 @@ struct mtr_engine {
 		uint32_t                   code_pitch = 0;
 		std::vector<Event>         ev;          // while mtr_engine_gonio_timing is on: three per piece, around its two kernels
 		bool                       timed = false;
+		std::vector<uint64_t>      updates;     // [S] each stream's own display updates since reset, closing ones included (mtr_gonio_ends.h)
 	} go;
 };
 
@@ -377,9 +378,15 @@ struct Call {
 // view ends (0: closed, untouched), km_fall[i] = Kmeterdsp's fall-back factor for a stream that ends inside the call (KMETER engines: that of
 // its frames in the call, or — with a period — of its frames in the truncated block; SURROUND engines: that of its frames in the call).
 // Both null on a dense call: the steps then launch the dense instantiations.
+// GONIO engines: go_cut[i] = the call frame at which the stream's drawing ends (MTR_GONIO_OPEN: not in this call), go_closing[i] = the frames
+// of its closing display update or 0, go_attack[i][2] = that update's attack pair (gonio_cut); go_last: the last call frame any stream draws.
 struct StreamEnds {
 	const uint32_t* ends = nullptr;
 	const float*    km_fall = nullptr;
+	const uint32_t* go_cut = nullptr;
+	const uint32_t* go_closing = nullptr;
+	const float*    go_attack = nullptr;
+	uint64_t        go_last = 0;
 };
 
 struct StateSection { const void* base; size_t elem; };   // a per-stream array of the state blob: `elem` bytes per stream
@@ -456,6 +463,13 @@ void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t cou
 // SCOPE counts analyses and the points among them, not blocks of a period: stream g's own counts move by those of `frames` frames of a
 // call that starts at e->pos (no `series` hook: that one is the periods')
 void scope_count (mtr_engine* e, size_t g, uint64_t frames);
+// GONIO: what a stream that takes `frames` of a call of n_frames draws, the call starting `fill` frames into a display update of P
+// (mtr_gonio_cut is this): *whole updates of P frames it completes, a closing one of `closing` frames (0: none; else >= 64) with its
+// attack pair, and `drawn`: the call frame at which its drawing ends.  `c`: a resolved configuration (its dials are read)
+struct GonioCut { uint64_t whole = 0, drawn = 0; uint32_t closing = 0; float attack[2] = { 0.f, 0.f }; };
+GonioCut gonio_cut (uint64_t fill, uint32_t P, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config& c);
+// ... and stream g's own count of display updates moves by those of `frames` frames of a call of n_frames that starts at e->pos
+void gonio_count (mtr_engine* e, size_t g, uint64_t n_frames, uint64_t frames);
 float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view
 // [off, off + cnt) (false: the log is off); its part of mtr_engine_reset

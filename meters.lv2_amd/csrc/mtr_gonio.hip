@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -76,10 +77,31 @@ typedef struct mtr_gonio_args {
 	uint16_t*      codes;        /* [S][code_pitch] */
 } mtr_gonio_args;
 
+/* per-stream ends (mtr_gonio_ends.h): what the ENDS instantiations take on top — a struct of its own, so that the dense kernels' arguments
+ * stay what they were.  All three from the view's first stream, written by CallRun::upload_lengths */
+typedef struct mtr_gonio_ends_args : mtr_gonio_args {
+	const uint32_t* cut;         /* [S] the call frame at which the stream's drawing ends; MTR_GONIO_OPEN: not in this call; 0: closed, untouched */
+	const uint32_t* closing;     /* [S] r, the frames of the closing display update behind the cut (>= 64), or 0: none */
+	const float*    c_attack;    /* [S][2] `attack` of :524 for elapsed = r / rate */
+} mtr_gonio_ends_args;
+constexpr uint32_t MTR_GONIO_OPEN = 0xFFFFFFFFu;
+
 namespace {
 
-template <int NS, bool AG>
-__global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
+// the frames of the piece in front of a stream's cut: 0 .. n
+__device__ inline int gonio_limit (uint32_t cut, uint64_t f0, int n)
+{
+	return cut == MTR_GONIO_OPEN ? n : (uint64_t) cut <= f0 ? 0 : (int) min ((uint64_t) cut - f0, (uint64_t) n);
+}
+
+// ENDS (mtr_gonio_ends.h): stream s draws the frames in front of call frame a.cut[s] and no other.  The streams still stand in lock step —
+// j and point go on for every lane — so a chunk in which no live lane's cut falls runs the dense body as it is: a lane whose cut lies
+// behind it (a DEAD lane: it stored its state at its cut and stores nothing any more) computes on the zeros its row was staged with, and
+// nothing of that is kept.  A chunk that holds a cut takes the cold path: frame by frame, each lane up to its own limit, code 0xFFFF
+// behind it; then the lanes that end here run their closing update (its own count r and attack pair), store their point and their state
+// and die.  A workgroup (one wave) whose lanes are all dead leaves the chunk loop.  Staging never loads a frame at or behind its row's cut.
+template <int NS, bool AG, bool ENDS = false>
+__global__ __launch_bounds__ (64) void k_gonio_points (const std::conditional_t<ENDS, mtr_gonio_ends_args, mtr_gonio_args> a)
 {
 	constexpr int CH = 2048 / NS;                // frames per staged chunk
 	constexpr int PITCH = 2 * CH + 2;            // dwords of a row's chunk, padded by one frame
@@ -89,12 +111,25 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 	constexpr int CQ = CH / 8;                   // 16-byte quads of a row of cell codes
 	constexpr int CPER = NS * CQ / 64;           // ... per lane: 4
 	__shared__ float lds[NS * PITCH];
-	__shared__ uint32_t cds[NS * CP];
+	__shared__ uint32_t cds[(NS + (ENDS && NS < 64 ? 1 : 0)) * CP];   // (ENDS: a row behind the last for the idle lanes, which no longer mirror lane 0)
+	__shared__ int rlim[ENDS ? NS : 1];          // ENDS: the rows' frame limits in the piece
 
 	const int lane = threadIdx.x;
 	const uint32_t s0 = blockIdx.x * NS;
 	const int n = (int) a.n;
 	const int nchunks = (n + CH - 1) / CH;
+	int lim = n;                                 // ENDS: the lane's own
+	bool ends_here = false;                      // ... and whether its drawing ends in this piece
+	if constexpr (ENDS) {
+		const uint32_t sl = s0 + (uint32_t) lane;
+		if (lane < NS) {
+			const uint32_t cut = sl < a.n_streams ? a.cut[sl] : 0u;
+			lim = gonio_limit (cut, a.f0, n);
+			ends_here = cut != MTR_GONIO_OPEN && (uint64_t) cut <= a.f0 + (uint64_t) n;
+			rlim[lane] = lim;
+		}
+		__syncthreads ();
+	}
 
 	// ---- staging: item i = (row, quad) ----
 	float4 pre[PER];
@@ -105,12 +140,14 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 			const uint32_t s = s0 + (uint32_t) r;
 			const int f = T + 2 * q;                                   // the quad's first frame in the piece
 			float4 v = float4{0.f, 0.f, 0.f, 0.f};
-			if (s < a.n_streams && f < n) {
+			int rn = n;                                                // (ENDS: no frame at or behind the row's cut is loaded)
+			if constexpr (ENDS) rn = rlim[r];
+			if (s < a.n_streams && f < rn) {
 				const float* const p = a.audio + ((uint64_t) s * a.stride + a.f0 + (uint64_t) f) * 2;
-				if (f + 1 < n && (reinterpret_cast<size_t> (p) & 15) == 0) v = *reinterpret_cast<const float4*> (p);
+				if (f + 1 < rn && (reinterpret_cast<size_t> (p) & 15) == 0) v = *reinterpret_cast<const float4*> (p);
 				else {
 					v.x = p[0]; v.y = p[1];
-					if (f + 1 < n) { v.z = p[2]; v.w = p[3]; }
+					if (f + 1 < rn) { v.z = p[2]; v.w = p[3]; }
 				}
 			}
 			pre[j] = v;
@@ -128,7 +165,11 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 
 	// ---- the chain: lane = stream ----
 	const uint32_t s = s0 + (uint32_t) lane;
-	const bool live = lane < NS && s < a.n_streams;
+	bool live = lane < NS && s < a.n_streams;
+	if constexpr (ENDS) {
+		live = live && lim > 0;                                        // (a closed stream, or one whose cut lies in front of the piece)
+		if (!__any (live)) return;                                     // (the workgroup is one wave: uniform)
+	}
 	mtr_gonio_state* const st = reinterpret_cast<mtr_gonio_state*> (a.state + (size_t) (live ? s : s0) * a.pitch);
 	float lp0 = st->lp0, lp1 = st->lp1, last_x = st->last_x, last_y = st->last_y, gain = st->gain;
 	float xmax = st->xmax, xmin = st->xmin, ymax = st->ymax, ymin = st->ymin, rms0 = st->rms0, rms1 = st->rms1;
@@ -142,7 +183,7 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 	uint32_t j = a.fill;
 	uint64_t point = a.point0;
 	const float* const row = &lds[(lane < NS ? lane : 0) * PITCH];
-	uint16_t* const crow = reinterpret_cast<uint16_t*> (&cds[(lane < NS ? lane : 0) * CP]);
+	uint16_t* const crow = reinterpret_cast<uint16_t*> (&cds[(lane < NS ? lane : ENDS ? NS : 0) * CP]);
 
 	// one frame: branch-free, so that the scheduler can run frame k + 1's filters under frame k's point
 	auto frame = [&] (float2 d, int k) __attribute__ ((always_inline)) {
@@ -181,11 +222,69 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 
 	fetch (0);
 	for (int c = 0; c < nchunks; ++c) {
+		if constexpr (ENDS) if (!__any (live)) break;
 		stash ();
 		__syncthreads ();
 		if (c + 1 < nchunks) fetch ((c + 1) * CH);
 		const int nf = min (CH, n - c * CH);
 		int k = 0;
+		if constexpr (ENDS) {
+			// the cold path's block end (:494-537 for the lane itself): `cnt` frames, its attack pair, its point at index `pt`.  (Defined here: a closure
+			// in the dense instantiations, used or not, moves their register allocation — they are the parent's instruction streams)
+			auto update = [&] (float cnt, float att0, float att1, uint64_t pt) __attribute__ ((always_inline)) {
+				if (!isfinite (lp0)) lp0 = 0.f;
+				if (!isfinite (lp1)) lp1 = 0.f;
+				if constexpr (AG) {
+					const float xdif = xmax - xmin, ydif = ymax - ymin;
+					float mx = (float) sqrt ((double) (xdif * xdif + ydif * ydif));
+					mx = (float) ((double) mx * .707);
+					if (a.g_rms > 0.f && isfinite (a.g_rms)) {
+						const float r = rms0 > rms1 ? sqrtf (rms0 / cnt) : sqrtf (rms1 / cnt);
+						const float rms = (float) (5.436 * (double) r);
+						mx = (float) ((double) mx * (1.0 - (double) a.g_rms) + (double) rms * (double) a.g_rms);
+					}
+					mx *= a.g_target;
+					if (!isfinite (mx)) mx = 0.f;
+					float tg;
+					if ((double) mx < .01) tg = 100.0f;
+					else if (mx > 100.0f) tg = .02f;
+					else tg = (float) (2.0 / (double) mx);
+					const float attack = tg < gain ? att0 : att1;
+					tg = gain + attack * (tg - gain);
+					if ((double) tg < .001) tg = .001f;
+					gain = tg;
+					xmax = xmin = ymax = ymin = rms0 = rms1 = 0.f;
+				}
+				if (pt < a.capacity) {
+					const size_t slot = (size_t) s * a.capacity + pt;
+					a.s_gain[slot] = gain; a.s_drawn[slot] = bd; a.s_clipped[slot] = bc;
+				}
+				td += bd; tc += bc;
+				bd = bc = 0;
+			};
+			if (__any (live && ends_here && lim <= c * CH + nf)) {         // the cold path: some live lane's cut falls in this chunk
+				for (; k < nf; ++k) {
+					const bool on = live && c * CH + k < lim;
+					if (on) frame (at (k), k);
+					else crow[k] = (uint16_t) 0xFFFFu;
+					if (++j == P) {                                        // (a block that ends at the lane's cut is still a whole one)
+						if (on) update ((float) P, a.attack[0], a.attack[1], point);
+						++point;
+						j = 0;
+					}
+				}
+				if (live && ends_here && lim <= c * CH + nf) {
+					const uint32_t r = a.closing[s];
+					if (r) update ((float) r, a.c_attack[2 * (size_t) s], a.c_attack[2 * (size_t) s + 1], a.point0 + ((uint64_t) a.fill + (uint32_t) lim) / P);
+					st->lp0 = lp0; st->lp1 = lp1; st->last_x = last_x; st->last_y = last_y; st->gain = gain;
+					st->xmax = xmax; st->xmin = xmin; st->ymax = ymax; st->ymin = ymin; st->rms0 = rms0; st->rms1 = rms1;
+					st->b_drawn = bd; st->b_clipped = bc;
+					const uint32_t dd = td + bd - bd_in, dc = tc + bc - bc_in;
+					st->drawn += dd; st->clipped += dc; st->skipped += (uint32_t) lim - dd - dc;
+					live = false;
+				}
+			}
+		}
 		while (k < nf) {
 			int run = (int) min ((uint32_t) (nf - k), P - j);
 			j += (uint32_t) run;
@@ -236,7 +335,9 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 		for (int jj = 0; jj < CPER; ++jj) {
 			const int i = lane + jj * 64, r = i / CQ, q = i - r * CQ;
 			const uint32_t sr = s0 + (uint32_t) r;
-			if (sr < a.n_streams && c * CH + 8 * q < n) {
+			int rn = n;                                                    // (ENDS: nor what lies behind the row's cut)
+			if constexpr (ENDS) rn = rlim[r];
+			if (sr < a.n_streams && c * CH + 8 * q < rn) {
 				const uint32_t* const src = &cds[r * CP + 4 * q];
 				*reinterpret_cast<uint4*> (a.codes + (size_t) sr * a.code_pitch + (size_t) c * CH + 8 * q) = uint4{src[0], src[1], src[2], src[3]};
 			}
@@ -253,18 +354,24 @@ __global__ __launch_bounds__ (64) void k_gonio_points (const mtr_gonio_args a)
 
 // NT threads own one stream.  The image is walked in uint4: the LDS copy is padded to a multiple of four cells, and so is the stream's
 // entry in global memory (its pitch is a multiple of 16 bytes behind a 96-byte state) — the pad cells stay zero: no code names them
-template <int G, int NT>
-__global__ __launch_bounds__ (NT) void k_gonio_image (const mtr_gonio_args a)
+// ENDS: the stream's frames of the piece in front of its cut take the place of n — one scalar load, the workgroup is a stream: what an
+// earlier piece left in the scratch behind the cut is not added, and a stream with nothing in the piece returns before it clears its image
+template <int G, int NT, bool ENDS = false>
+__global__ __launch_bounds__ (NT) void k_gonio_image (const std::conditional_t<ENDS, mtr_gonio_ends_args, mtr_gonio_args> a)
 {
 	constexpr int CELLS = G * G, QUADS = (CELLS + 3) / 4;
 	__shared__ uint4 img4[QUADS];
 	uint32_t* const img = reinterpret_cast<uint32_t*> (img4);
 	const int tid = threadIdx.x;
 	const uint32_t s = blockIdx.x;
+	int n = (int) a.n;
+	if constexpr (ENDS) {
+		n = gonio_limit (a.cut[s], a.f0, n);
+		if (n == 0) return;
+	}
 	for (int i = tid; i < QUADS; i += NT) img4[i] = uint4{0u, 0u, 0u, 0u};
 	__syncthreads ();
 	const uint16_t* const row = a.codes + (size_t) s * a.code_pitch;
-	const int n = (int) a.n;
 	for (int i = tid * 8; i < n; i += NT * 8) {
 		const uint4 v = *reinterpret_cast<const uint4*> (row + i);
 		const uint32_t w[4] = { v.x, v.y, v.z, v.w };
@@ -308,7 +415,40 @@ static int mtr_launch_gonio (const mtr_gonio_args& a, bool autogain, hipStream_t
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
+// a piece of a call with per-stream ends: the ENDS instantiations, the same grids
+static int mtr_launch_gonio_ends (const mtr_gonio_ends_args& a, bool autogain, hipStream_t st, hipEvent_t* ev)
+{
+	const auto points = [&] (auto NS) {
+		const dim3 grid ((a.n_streams + NS.value - 1) / NS.value);
+		if (autogain) hipLaunchKernelGGL ((k_gonio_points<NS.value, true, true>), grid, dim3 (64), 0, st, a);
+		else hipLaunchKernelGGL ((k_gonio_points<NS.value, false, true>), grid, dim3 (64), 0, st, a);
+	};
+	if (ev && hipEventRecord (ev[0], st) != hipSuccess) return -1;
+	if (a.n_streams >= 16384) points (std::integral_constant<int, 64> {}); else points (std::integral_constant<int, 16> {});
+	if (ev && hipEventRecord (ev[1], st) != hipSuccess) return -1;
+	const dim3 grid (a.n_streams);
+	if (a.shift == 1) hipLaunchKernelGGL ((k_gonio_image<cells_of (1), 1024, true>), grid, dim3 (1024), 0, st, a);
+	else if (a.shift == 2) hipLaunchKernelGGL ((k_gonio_image<cells_of (2), 256, true>), grid, dim3 (256), 0, st, a);
+	else hipLaunchKernelGGL ((k_gonio_image<cells_of (3), 256, true>), grid, dim3 (256), 0, st, a);
+	if (ev && hipEventRecord (ev[2], st) != hipSuccess) return -1;
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
 // ---- GONIO in the engine: set-up, the call's step, the blob's section and the cursor in it, the C entry points ---------------------------
+
+// `attack` of :524 for a display update of `frames` frames (elapsed of :499), from the dials of a resolved configuration (:897-904):
+// [0] where the target is below the gain, [1] otherwise.  The block's (P frames) and a closing update's (r frames) alike
+static void gonio_attack (const mtr_gonio_config& c, double rate, uint64_t frames, float out[2])
+{
+	float g_attack = c.g_attack, g_decay = c.g_decay;
+	g_attack = 0.1 * exp (0.06 * g_attack) - .09;
+	g_decay = 0.1 * exp (0.06 * g_decay) - .09;
+	if (g_attack < .01) g_attack = .01;
+	if (g_decay < .01) g_decay = .01;
+	const float elapsed = (size_t) frames / rate;                                    // :499
+	out[0] = g_attack * (.31 + .1 * log10f (elapsed));                               // :524
+	out[1] = g_decay * (.03 + .007 * logf (elapsed));
+}
 
 static int gonio_resolve (const mtr_gonio_config* in, double rate, mtr_gonio_config* c, mtr_gonio_derived* d)
 {
@@ -342,18 +482,11 @@ static int gonio_resolve (const mtr_gonio_config* in, double rate, mtr_gonio_con
 	d->period_frames = c->period_frames;
 	d->G = cells_of (c->shift);
 	d->hpw = expf (-2.0 * M_PI * 20 / rate);                                         // :165
-	float g_attack = c->g_attack, g_decay = c->g_decay;                              // :897-912
-	g_attack = 0.1 * exp (0.06 * g_attack) - .09;
-	g_decay = 0.1 * exp (0.06 * g_decay) - .09;
-	if (g_attack < .01) g_attack = .01;
-	if (g_decay < .01) g_decay = .01;
-	const float g_rms = .01 * c->g_rms;
+	const float g_rms = .01 * c->g_rms;                                              // :906-912
 	float g_target = c->g_target;
 	g_target = exp (1.8 * (-.02 * g_target + 1.0));
 	if (g_target < .15) g_target = .15;
-	const float elapsed = (size_t) c->period_frames / rate;                          // :499
-	d->attack[0] = g_attack * (.31 + .1 * log10f (elapsed));                         // :524
-	d->attack[1] = g_decay * (.03 + .007 * logf (elapsed));
+	gonio_attack (*c, rate, c->period_frames, d->attack);
 	d->g_target = g_target; d->g_rms = g_rms;
 	return MTR_OK;
 }
@@ -394,15 +527,37 @@ static hipError_t gonio_states (mtr_engine* e, uint32_t first, uint32_t count, m
 	          : hipMemcpy2D (h, sizeof (*h), dev, e->go.pitch, sizeof (*h), count, hipMemcpyDeviceToHost);
 }
 
+// Track lengths (mtr_gonio_ends.h).  draw_rb returns at n_samples < 64 (:302): a closing stream gets one last update of the r frames it has
+// of its open block if r >= 64, and stands where its last whole block left it otherwise — but never in front of the call's first frame:
+// what earlier calls drew of the open block stays drawn
+GonioCut gonio_cut (uint64_t fill, uint32_t P, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config& c)
+{
+	GonioCut o;
+	const uint64_t tot = fill + frames, r = tot % P;
+	o.whole = tot / P;
+	o.drawn = frames;
+	if (!(frames > 0 && frames < n_frames) || r == 0) return o;
+	if (r < 64) { o.drawn = frames - std::min (frames, r); return o; }
+	o.closing = (uint32_t) r;
+	gonio_attack (c, rate, r, o.attack);
+	return o;
+}
+
+void gonio_count (mtr_engine* e, size_t g, uint64_t n_frames, uint64_t frames)
+{
+	const GonioCut k = gonio_cut (e->pos.go.fill, e->go.cfg.period_frames, (double) e->cfg.sample_rate, n_frames, frames, e->go.cfg);
+	e->go.updates[g] += k.whole + (k.closing ? 1 : 0);
+}
+
 static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
-	if (se.ends) return fail (MTR_ERR_UNSUPPORTED, "GONIO: calls with per-stream ends are not taken");
 	const mtr_gonio_config& g = e->go.cfg;
 	const mtr_gonio_derived& d = e->go.der;
 	const uint32_t P = g.period_frames, cap = g.capacity;
 	const size_t S = e->cfg.n_streams;
-	mtr_gonio_args a;
-	memset (&a, 0, sizeof (a));
+	mtr_gonio_ends_args a;                                             // (a dense call launches on its base)
+	memset (static_cast<void*> (&a), 0, sizeof (a));
+	a.cut = se.go_cut; a.closing = se.go_closing; a.c_attack = se.go_attack;
 	a.audio = c.audio; a.stride = c.stride; a.n_streams = c.cnt;
 	a.P = P; a.capacity = cap; a.shift = g.shift; a.G = d.G; a.code_pitch = e->go.code_pitch;
 	a.hpw = d.hpw; a.attack[0] = d.attack[0]; a.attack[1] = d.attack[1]; a.g_target = d.g_target; a.g_rms = d.g_rms;
@@ -419,6 +574,8 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 		a.f0 = f0;
 		a.n = (uint32_t) std::min<uint64_t> (g.tune_piece, c.n_frames - f0);
 		a.fill = (uint32_t) pos.fill; a.point0 = pos.points;
+		// (per-stream ends: only the pieces in which some stream of the view still draws are launched; the cursor moves on regardless)
+		if (se.ends && f0 >= se.go_last) { pos = series_advance (pos, P, a.n); continue; }
 		hipEvent_t ev[3];
 		const bool tm = e->go.timed && c.commit;
 		if (tm) {
@@ -428,7 +585,8 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 				ev[i] = e->go.ev.back ().v;
 			}
 		}
-		if (mtr_launch_gonio (a, g.autogain != 0, c.st, tm ? ev : nullptr)) return fail (MTR_ERR_HIP, "k_gonio launch");
+		if (se.ends ? mtr_launch_gonio_ends (a, g.autogain != 0, c.st, tm ? ev : nullptr) : mtr_launch_gonio (a, g.autogain != 0, c.st, tm ? ev : nullptr))
+			return fail (MTR_ERR_HIP, "k_gonio launch");
 		pos = series_advance (pos, P, a.n);
 	}
 	nx.go = pos;
@@ -489,6 +647,7 @@ int mtr_engine_gonio_reset (mtr_engine* e)
 	HIPCHK (gonio_states (e, 0, S, h.data (), true));
 	if (e->go.series.n) HIPCHK (hipMemset (e->go.series.p, 0, e->go.series.n * sizeof (float)));
 	e->pos.go = {};
+	e->go.updates.assign (S, 0);
 	e->go.ev.clear ();
 	return MTR_OK;
 }
@@ -582,6 +741,34 @@ int mtr_engine_gonio_series (mtr_engine* e, uint32_t first, uint32_t count, uint
 	void* const out[3] = { gain, drawn, clipped };
 	for (int k = 0; k < 3; ++k)
 		if (out[k]) HIPCHK (hipMemcpy2D (out[k], (size_t) n * 4, e->go.series.p + (size_t) k * S * cap + (size_t) first * cap + from, (size_t) cap * 4, (size_t) n * 4, count, hipMemcpyDeviceToHost));
+	return MTR_OK;
+}
+
+int mtr_gonio_cut (uint64_t fill, uint32_t period, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config* cfg,
+                   uint64_t* whole, uint32_t* closing_frames, uint64_t* drawn_frames, float attack[2])
+{
+	if (!cfg || !whole || !closing_frames || !drawn_frames || !attack) return fail (MTR_ERR_ARG, "mtr_gonio_cut: null argument");
+	if (!period || fill >= period || frames > n_frames) return fail (MTR_ERR_ARG, "mtr_gonio_cut: fill < period, frames <= n_frames");
+	mtr_gonio_config in = *cfg, c;
+	mtr_gonio_derived d;
+	in.period_frames = period;                                         // (the period is the argument's, whatever the configuration names)
+	if (!in.capacity) in.capacity = 1;
+	const int rc = gonio_resolve (&in, rate, &c, &d);
+	if (rc) return rc;
+	const GonioCut k = gonio_cut (fill, period, rate, n_frames, frames, c);
+	*whole = k.whole; *closing_frames = k.closing; *drawn_frames = k.drawn;
+	attack[0] = k.attack[0]; attack[1] = k.attack[1];
+	return MTR_OK;
+}
+
+int mtr_engine_gonio_points (mtr_engine* e, uint32_t first, uint32_t count, uint64_t* updates, uint64_t* points)
+{
+	const int rc = meter_range (e, !no_gonio (e), NO_GONIO, first, count);
+	if (rc) return rc;
+	for (uint32_t i = 0; i < count; ++i) {
+		if (updates) updates[i] = e->go.updates[first + i];
+		if (points) points[i] = e->go.updates[first + i];               // (every update appends a point, written or dropped)
+	}
 	return MTR_OK;
 }
 

@@ -207,6 +207,9 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	// (SCOPE counts analyses, not frames: its per-stream counts are its own.  An imported stream takes the lock-step numbers)
 	if (e->cfg.meters & MTR_METER_SCOPE)
 		for (uint32_t k = 0; k < h.count; ++k) { e->sp.analyses[first + k] = e->pos.sp_analyses; e->sp.points[first + k] = e->pos.sp_points; }
+	// (GONIO counts display updates with draw_rb's 64-frame floor, not every partial block: likewise)
+	if (e->cfg.meters & MTR_METER_GONIO)
+		for (uint32_t k = 0; k < h.count; ++k) e->go.updates[first + k] = e->pos.go.points;
 	return MTR_OK;
 }
 

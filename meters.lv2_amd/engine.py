@@ -243,6 +243,12 @@ def _load():
         L.mtr_engine_gonio_image_clear.argtypes = [vp]
         L.mtr_engine_gonio_reset.argtypes = [vp]
         L.mtr_engine_gonio_timing.argtypes = [vp, C.c_int, C.POINTER(f32), C.POINTER(f32), C.POINTER(u32)]
+    if hasattr(L, "mtr_engine_process_device_gonio_ends"):     # (an addition inside ABI version 2: track lengths for the goniometer)
+        L.mtr_engine_process_device_gonio_ends.argtypes = [vp, vp, u64, u64, vp, vp]
+        L.mtr_engine_process_host_gonio_ends.argtypes = [vp, vp, u64, u64, vp]
+        L.mtr_gonio_cut.argtypes = [u64, u32, C.c_double, u64, u64, C.POINTER(GonioConfig), C.POINTER(u64), C.POINTER(u32), C.POINTER(u64),
+                                    C.POINTER(f32)]
+        L.mtr_engine_gonio_points.argtypes = [vp, u32, u32, vp, vp]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -385,6 +391,23 @@ def gonio_derive(rate, config=None, **kw):
     d = GonioDerived()
     _check(lib.mtr_gonio_derive(C.byref(c), float(rate), C.byref(d)), "mtr_gonio_derive")
     return d
+
+
+def _need_gonio_ends():
+    if not hasattr(lib, "mtr_engine_process_device_gonio_ends"):
+        raise EngineError(f"{lib_path} has no track lengths for the goniometer: rebuild it")
+
+
+def gonio_cut(fill, period, rate, n_frames, frames, config=None, **kw):
+    """(whole, closing_frames, drawn_frames, (attack0, attack1)) of a stream that takes `frames` of a call of n_frames which starts `fill`
+    frames into a display update of `period` frames: the updates it completes, the frames of its closing update (0: none), the call frame
+    at which its drawing ends, and the closing update's attack pair as float32 (mtr_gonio_cut; no engine, no device)."""
+    _need_gonio_ends()
+    c = config if config is not None else gonio_config(**kw)
+    whole, closing, drawn, att = C.c_uint64(), C.c_uint32(), C.c_uint64(), (C.c_float * 2)()
+    _check(lib.mtr_gonio_cut(int(fill), int(period), float(rate), int(n_frames), int(frames), C.byref(c), C.byref(whole), C.byref(closing),
+                             C.byref(drawn), att), "mtr_gonio_cut")
+    return whole.value, closing.value, drawn.value, (np.float32(att[0]), np.float32(att[1]))
 
 
 def needle_coef(kind, fs):
@@ -620,7 +643,8 @@ class Engine:
                "ragged": ("mtr_engine_process_device_ragged", "ragged batches"),
                "ends": ("mtr_engine_process_device_ends", "track lengths for the 30-band bank"),
                "tpb": ("mtr_engine_process_device_tpb", "track lengths for the true-peak bar"),
-               "any": ("mtr_engine_process_device_any", "track lengths for the scope and the surround meter")}
+               "any": ("mtr_engine_process_device_any", "track lengths for the scope and the surround meter"),
+               "gonio_ends": ("mtr_engine_process_device_gonio_ends", "track lengths for the goniometer")}
 
     def _frames(self, frames, family):
         """frames as contiguous uint64 [S], for a call of `family`"""
@@ -1256,6 +1280,25 @@ class Engine:
         g, d, c = np.zeros((count, n), np.float32), np.zeros((count, n), np.uint32), np.zeros((count, n), np.uint32)
         _check(lib.mtr_engine_gonio_series(self._h, first, count, int(start), int(n), g.ctypes.data, d.ctypes.data, c.ctypes.data), "gonio_series")
         return g, d, c
+
+    def process_device_gonio_ends(self, ptr, n_frames, frames, stride=None, stream=0):
+        """process_device_any() for stereo engines that hold GONIO: stream s is metered up to frames[s] <= n_frames — the goniometer
+        draws the whole display updates that end at or before its last frame and one closing update of the r frames it has of the
+        open one if r >= 64 (draw_rb's floor); frames[s] < n_frames closes it."""
+        self._device_frames("gonio_ends", ptr, n_frames, frames, stride, stream)
+
+    def process_gonio_ends(self, x, frames):
+        """process() with track lengths for the goniometer: x host float32 [S, T, W] as process() takes it, frames [S] <= T."""
+        self._host_frames("gonio_ends", x, frames)
+
+    def gonio_points(self, first=0, count=None):
+        """(updates, points), [count] uint64 each: each stream's own display updates since reset, closing ones included, and the points
+        its series has got, dropped ones included."""
+        _need_gonio_ends()
+        count = self.n_streams - first if count is None else count
+        up, pt = np.zeros(count, np.uint64), np.zeros(count, np.uint64)
+        _check(lib.mtr_engine_gonio_points(self._h, first, count, up.ctypes.data, pt.ctypes.data), "gonio_points")
+        return up, pt
 
     def gonio_image_clear(self):
         _need_gonio()

@@ -8,6 +8,16 @@ Times are the engine's own device events around each call (mtr_engine_timing_cal
 k_gonio_points and k_gonio_image apart, summed over the call's pieces (mtr_engine_gonio_timing: events around each launch).  Printed:
 median, min and max per form, the ratio to the K-meter's median, and the bytes a form reads and writes.
     python tools/gonio_rate.py [reps] [tune_piece]
+
+    python tools/gonio_rate.py --ends [reps] [tune_piece]
+what track lengths (mtr_engine_process_device_gonio_ends: the ENDS instantiations of the two kernels) cost and save, auto gain on, shift 2:
+five forms on the same buffer in rotating order, each from a reset engine, device events around the call — (a) the dense call; (b) the new
+call with every stream open; (c) every end at a quarter of the call, next to (d) the dense call of that quarter; (e) lengths uniform in
+[0, 10 s] — with the chunks of 128 frames each form must walk (16 lanes share a wave's loop: a workgroup walks up to its last cut).
+
+    python tools/gonio_rate.py --pairs [N] [reps] [tune_piece]
+the dense call of this build against the parent's library (tools/build_ab.sh -> meters.lv2_amd/lib_ab): N pairs of child processes
+alternating on the same box (--dense, with MTR_LIB naming the library), a table row per child.
 """
 import os
 import sys
@@ -98,5 +108,130 @@ def main(reps, piece):
         e.close()
 
 
+# ---- track lengths (mtr_gonio_ends.h): --ends, --pairs -----------------------------------------------------------------------------------
+FORMS = ["a", "b", "c", "d", "e"]
+NAMES = {"a": "(a) dense call", "b": "(b) `_gonio_ends`, every stream open", "c": "(c) `_gonio_ends`, every end at T / 4",
+         "d": "(d) dense call of T / 4 frames", "e": "(e) `_gonio_ends`, lengths uniform in [0, T]"}
+LIB_AB = os.path.join(ROOT, "meters.lv2_amd", "lib_ab", "libmtr_engine.so")
+ENDS_CFG = dict(shift=2, autogain=1)
+
+
+def chunks(frames, piece, P=1920):
+    """chunks of 128 frames that k_gonio_points must walk (NS = 16: a workgroup is 16 streams in lock step and walks a piece up to the last
+    cut among them), and the frames its lanes draw there"""
+    cut = np.array([M.gonio_cut(0, P, FS, T + 1, int(f), **ENDS_CFG)[2] for f in frames], np.int64)
+    last = cut.reshape(-1, 16).max(axis=1)
+    n = 0
+    for f0 in range(0, T, piece):
+        n += int(((np.clip(last - f0, 0, min(piece, T - f0)) + 127) // 128).sum())
+    return n, int(cut.sum())
+
+
+def ends(reps, piece):
+    """five forms on one buffer in rotating order, each from a reset engine (auto gain on, shift 2); device events around the call"""
+    buf = buffer()
+    st = torch.cuda.current_stream().cuda_stream
+    piece = piece or 4096
+    rng = np.random.default_rng(35)
+    frames = {"a": np.full(S, T, np.uint64), "b": np.full(S, T, np.uint64), "c": np.full(S, T // 4, np.uint64), "d": np.full(S, T // 4, np.uint64),
+              "e": rng.integers(0, T + 1, S).astype(np.uint64)}
+    must = {k: chunks(frames[k], piece) for k in FORMS}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    dev = {k: [] for k in FORMS}
+    e = M.Engine(S, FS, M.METER_GONIO)
+    e.gonio_configure(tune_piece=piece, **ENDS_CFG)
+
+    def one(key):
+        e.reset()
+        torch.cuda.synchronize()
+        ev[0].record()
+        if key == "a":
+            e.process_device(buf.data_ptr(), T, T, st)
+        elif key == "d":
+            e.process_device(buf.data_ptr(), T // 4, T, st)
+        else:
+            e.process_device_gonio_ends(buf.data_ptr(), T, frames[key], T, st)
+        ev[1].record()
+        e.sync()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1])
+
+    for it in range(WARM + reps):
+        r = it % len(FORMS)
+        for key in FORMS[r:] + FORMS[:r]:
+            d = one(key)
+            if it >= WARM:
+                dev[key].append(d)
+    one("e")
+    assert int(e.stream_frames()[0].sum()) == int(frames["e"].sum())
+    # the two kernels apart for (a) and (b), in three more turns with events around every launch
+    split = {"a": [], "b": []}
+    e.gonio_timing(True)
+    for it in range(3):
+        for key in ("a", "b") if it % 2 == 0 else ("b", "a"):
+            one(key)
+            split[key].append(e.gonio_timing(True)[:2])
+    e.gonio_timing(False)
+    e.close()
+    med = {k: float(np.median(dev[k])) for k in FORMS}
+    print("GONIO auto gain, shift 2, pieces of %d: %d streams x %d s, %d turns after %d warm ones, rotating order" % (piece, S, T // int(FS), reps, WARM))
+    print("| form | chunks to walk | share of the dense call's | frames drawn, share | device ms (median) | min – max |\n|---|---|---|---|---|---|")
+    for k in FORMS:
+        print("| %s | %d | %.3f | %.3f | %.3f | %.3f – %.3f |" % (NAMES[k], must[k][0], must[k][0] / must["a"][0], must[k][1] / must["a"][1], med[k],
+                                                                  min(dev[k]), max(dev[k])), flush=True)
+    print("(b) / (a) = %.3f; (c) / (d) = %.3f; (e) / (a) = %.3f at %.3f of the chunks and %.3f of the frames; (a) max / min = %.3f"
+          % (med["b"] / med["a"], med["c"] / med["d"], med["e"] / med["a"], must["e"][0] / must["a"][0], must["e"][1] / must["a"][1],
+             max(dev["a"]) / min(dev["a"])), flush=True)
+    for k in ("a", "b"):
+        v = np.median(np.asarray(split[k]), axis=0)
+        print("%s: k_gonio_points %.3f ms, k_gonio_image %.3f ms (medians of 3, summed over the call's pieces)" % (NAMES[k], v[0], v[1]), flush=True)
+
+
+def dense(reps, piece):
+    """the dense call alone, of whichever library MTR_LIB names: one table row"""
+    buf = buffer()
+    st = torch.cuda.current_stream().cuda_stream
+    t = []
+    with M.Engine(S, FS, M.METER_GONIO) as e:
+        e.gonio_configure(tune_piece=piece, **ENDS_CFG)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for it in range(WARM + reps):
+            e.reset()
+            torch.cuda.synchronize()
+            ev0.record()
+            e.process_device(buf.data_ptr(), T, T, st)
+            ev1.record()
+            e.sync()
+            torch.cuda.synchronize()
+            if it >= WARM:
+                t.append(ev0.elapsed_time(ev1))
+    v = np.asarray(t)
+    print("| %s | %.3f | %.3f | %.3f |" % ("parent" if os.environ.get("MTR_LIB") else "this build", np.median(v), v.min(), v.max()), flush=True)
+
+
+def pairs(n, reps, piece):
+    """the dense call of this build against the parent's library (tools/build_ab.sh -> meters.lv2_amd/lib_ab) in alternating child processes"""
+    import subprocess
+    if not os.path.exists(LIB_AB):
+        sys.exit("no meters.lv2_amd/lib_ab: tools/build_ab.sh")
+    print("| library (dense call, GONIO auto gain, shift 2) | median ms | min | max |\n|---|---|---|---|", flush=True)
+    for _ in range(n):
+        for lib in (None, LIB_AB):                                          # a fresh child each: nothing of one library's session is left for the other
+            env = {k: v for k, v in os.environ.items() if k != "MTR_LIB"}
+            if lib:
+                env["MTR_LIB"] = lib
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--dense", str(reps), str(piece)], env=env, check=True, timeout=300)
+
+
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 7, int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+    args = sys.argv[1:]
+    mode = args.pop(0) if args and args[0] in ("--ends", "--pairs", "--dense") else None
+    num = [int(v) for v in args]
+    if mode == "--ends":
+        ends(num[0] if num else 7, num[1] if len(num) > 1 else 0)
+    elif mode == "--pairs":
+        pairs(num[0] if num else 3, num[1] if len(num) > 1 else 7, num[2] if len(num) > 2 else 0)
+    elif mode == "--dense":
+        dense(num[0] if num else 7, num[1] if len(num) > 1 else 0)
+    else:
+        main(num[0] if num else 7, num[1] if len(num) > 1 else 0)
