@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <vector>
 
 #include "mtr_engine_impl.h"
@@ -161,18 +162,12 @@ struct CallRun {
 	const uint32_t* d_ends = nullptr;
 	const uint32_t* d_lim = nullptr;
 	const uint32_t* d_from = nullptr;
-	const float*    d_fall = nullptr;  // KMETER: the fall-back factor of each stream that ends inside the call
-	const uint32_t* d_gcut = nullptr;  // GONIO: [cut S | closing S | attack S x 2] (StreamEnds) ...
-	uint64_t        go_last = 0;       // ... and the last call frame any stream of the view draws
+	StreamEnds   se[std::size (SIDE_METERS)];   // ... and what each row's step gets of them: the ends, the row's own words behind them (all null otherwise)
 	bool         any_from = false;     // k_seg left a closing stream's last peaks to k_kwtp16
 	LenSlot*     ls = nullptr;
 	int          tb = 0;               // tile_power buffer of the call
 	float*       tile_power = nullptr;
 	bool         fold_in_history = false;   // (deferred gate: k_history folds the call's true peak in its place)
-
-	// the ping-pong histories of the view: flip = 0 what the call reads, 1 what k_history writes for the next one
-	float* fir_hist (int flip) const { return e->fir_hist[e->pos.hist_cur ^ flip].p + (size_t) c.off * MTR_FIR_HALO * 2; }
-	float* mc_hist (int flip) const { return e->mc_hist[e->pos.hist_cur ^ flip].p + (size_t) c.off * MTR_FIR_HALO * e->cfg.n_channels; }
 
 	// timing event `idx` of the call on stream `s`, if the call is timed
 	int mark (int idx, hipStream_t s) const
@@ -233,16 +228,16 @@ struct CallRun {
 		return o;
 	}
 
-	// [ends S | frag_lim S | from_tile S | km_fall S] of a ragged call into the next slot of the lengths ring, uploaded on the call's stream
-	// (an engine without EBU / TRUEPEAK has no plan: its frag_lim / from_tile are never read; km_fall: KMETER and SURROUND engines only —
-	// no engine holds both; GONIO engines: [cut S | closing S | attack S x 2] behind those, gonio_cut's answers per stream)
+	// [ends S | frag_lim S | from_tile S] of a ragged call into the next slot of the lengths ring, behind them the own words of every row of
+	// the engine that has some (SideMeter::ends_words per stream, filled by its ends_fill), in the order of the table; uploaded on the
+	// call's stream (an engine without EBU / TRUEPEAK has no plan: its frag_lim / from_tile are never read)
 	int upload_lengths ()
 	{
 		const SegPlan& sp = r.sp;
 		const uint32_t S = c.cnt;
-		const bool fused = ebu || tp, km = e->cfg.meters & MTR_METER_KMETER, su = e->cfg.meters & MTR_METER_SURROUND, go = e->cfg.meters & MTR_METER_GONIO;
-		const size_t gw = (size_t) (km || su ? 4 : 3) * S;            // GONIO's four arrays lie behind the older ones
-		const size_t words = gw + (go ? (size_t) 4 * S : 0);
+		const bool fused = ebu || tp;
+		size_t words = (size_t) 3 * S;
+		for (const SideMeter* m : SIDE_METERS) if (e->cfg.meters & m->bits) words += (size_t) m->ends_words * S;
 		const int slot = (e->len_cur + 1) % LEN_SLOTS;
 		ls = &e->len_slot[slot];
 		for (int i = 0; i < 2; ++i) if (ls->pending[i]) { HIPCHK (hipEventSynchronize (ls->done[i].v)); ls->pending[i] = false; }
@@ -251,26 +246,9 @@ struct CallRun {
 		uint32_t* const h_end = ls->pin.p;
 		uint32_t* const h_lim = h_end + S;
 		uint32_t* const h_from = h_end + 2 * (size_t) S;
-		float* const h_fall = reinterpret_cast<float*> (h_end + 3 * (size_t) S);
-		uint32_t* const h_gcut = h_end + gw;
 		for (uint32_t i = 0; i < S; ++i) {
-			const uint64_t f = e->closed[c.off + i] ? 0 : c.frames ? c.frames[i] : c.n_frames;
+			const uint64_t f = call_frames (e, c, i);
 			h_end[i] = (uint32_t) f;
-			if (go) {
-				// (the cuts are taken from where the CALL started, e->pos: every chunk of a host call sees the same ones)
-				const GonioCut k = gonio_cut (e->pos.go.fill, e->go.cfg.period_frames, (double) e->cfg.sample_rate, c.n_frames, f, e->go.cfg);
-				h_gcut[i] = f == c.n_frames ? 0xFFFFFFFFu : (uint32_t) k.drawn;     // (MTR_GONIO_OPEN: the stream does not end in this call)
-				h_gcut[S + i] = k.closing;
-				memcpy (h_gcut + 2 * (size_t) S + 2 * (size_t) i, k.attack, sizeof (k.attack));
-				go_last = std::max (go_last, k.drawn);
-			}
-			// (a closing stream's process () is one of f frames: kmeterdsp.cc:60-65 with fpp = f; every other stream takes the cursor's)
-			// (with a period: one of the frames it has of the block it ends in, if it ends inside one)
-			const uint64_t kp = e->km.ser.period, kf = kp ? (e->pos.km.fill + f) % kp : f;
-			if (km) h_fall[i] = f && f < c.n_frames && kf ? kmeter_fall (e, kf) : 0.f;
-			// (the surround meter's K-meters likewise, from their own cursor)
-			const uint64_t sup = e->su.ser.period, sf = sup ? (e->pos.su.fill + f) % sup : f;
-			if (su) h_fall[i] = f && f < c.n_frames && sf ? kmeter_fall (e, sf) : 0.f;
 			if (!fused) { h_lim[i] = h_from[i] = 0; continue; }
 			// fragments that end at or before the stream's end
 			const uint32_t nf = (uint32_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
@@ -284,11 +262,19 @@ struct CallRun {
 				}
 			}
 		}
+		d_ends = ls->dev.p; d_lim = d_ends + S; d_from = d_ends + 2 * (size_t) S;
+		size_t at = (size_t) 3 * S;                                   // where the next row's own words begin
+		for (size_t k = 0; k < std::size (SIDE_METERS); ++k) {
+			const SideMeter* const m = SIDE_METERS[k];
+			if (!(e->cfg.meters & m->bits)) continue;
+			se[k].ends = d_ends;
+			if (!m->ends_words) continue;
+			se[k].own = d_ends + at;
+			se[k].note = m->ends_fill (e, c, h_end + at);
+			at += (size_t) m->ends_words * S;
+		}
 		HIPCHK (hipMemcpyAsync (ls->dev.p, ls->pin.p, words * sizeof (uint32_t), hipMemcpyHostToDevice, c.st));
 		e->len_cur = slot;
-		d_ends = ls->dev.p; d_lim = d_ends + S; d_from = d_ends + 2 * (size_t) S;
-		if (km || su) d_fall = reinterpret_cast<const float*> (d_ends + 3 * (size_t) S);
-		if (go) d_gcut = d_ends + gw;
 		return MTR_OK;
 	}
 
@@ -305,7 +291,7 @@ struct CallRun {
 			lrc = mtr_launch_kwtp16 (e->run, ebu, fa, S, c.st);
 		}
 		mtr_seg_args sa;
-		sa.audio = c.audio; sa.stride = c.stride; sa.hist = fir_hist (0); sa.state = fa.state; sa.tile_power = tile_power;
+		sa.audio = c.audio; sa.stride = c.stride; sa.hist = fir_hist (e, c, 0); sa.state = fa.state; sa.tile_power = tile_power;
 		sa.head = sp.head; sa.tile0 = pl.head_tiles;
 		sa.mfma_a = e->m16_a.p;
 		sa.n_streams = S; sa.n_segs = sp.n_segs; sa.n_tiles = pl.n_tiles; sa.tile_frames = e->fragm;
@@ -335,7 +321,7 @@ struct CallRun {
 	{
 		const size_t C = e->cfg.n_channels;
 		mtr_kwmc_args ma;
-		ma.audio = c.audio; ma.stride = c.stride; ma.hist = mc_hist (0);
+		ma.audio = c.audio; ma.stride = c.stride; ma.hist = mc_hist (e, c, 0);
 		ma.tile_start = e->tile_start; ma.seg_tile = e->seg_tile; ma.scan_m = e->scan_m.p;
 		ma.kz = e->mc_kz.p + c.off * C * 4; ma.tp_call = e->mc_tp_call.p + c.off * C;
 		ma.tile_power = tile_power; ma.mfma_a = e->m16_a.p;
@@ -361,7 +347,7 @@ struct CallRun {
 		if (e->layout == 8) lrc = kwmc (warm_tiles);
 		else {
 			mtr_fused_args fa;
-			fa.audio = c.audio; fa.stride = c.stride; fa.hist = fir_hist (0);
+			fa.audio = c.audio; fa.stride = c.stride; fa.hist = fir_hist (e, c, 0);
 			fa.tile_start = e->tile_start; fa.seg_tile = e->seg_tile; fa.scan_m = e->scan_m.p;
 			fa.state = e->state.p + c.off; fa.tile_power = tile_power;
 			fa.n_streams = S; fa.n_segs = pl.n_segs; fa.n_tiles = pl.n_tiles; fa.warm_tiles = warm_tiles;
@@ -429,45 +415,6 @@ struct CallRun {
 		return MTR_OK;
 	}
 
-	int tpb ()
-	{
-		mtr_tpb_series_args ta;
-		ta.audio = c.audio; ta.stride = c.stride; ta.n_frames = c.n_frames;
-		ta.hist = fir_hist (0); ta.mfma_a = e->m16_a.p; ta.state = e->state.p + c.off;
-		ta.n_streams = c.cnt; ta.n_channels = e->cfg.n_channels;
-		ta.w1 = e->tpb_w[0]; ta.w2 = e->tpb_w[1]; ta.w3 = e->tpb_w[2]; ta.g = e->tpb_w[3];
-		const uint32_t P = e->tb.ser.period;
-		// (a call with ends — mtr_engine_process_*_tpb, or any call once a stream of the view is closed — takes the ENDS instantiations)
-		if (!P) {
-			if (d_ends) {
-				mtr_tpb_ends_args ea;
-				static_cast<mtr_tpb_args&> (ea) = ta;
-				ea.ends = d_ends;
-				if (mtr_launch_tpb_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (ends)");
-			} else if (mtr_launch_tpb (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch");
-			return MTR_OK;
-		}
-		// the reading series (mtr_tpb.h).  The blocks are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
-		const SeriesPos& at = e->pos.tb;
-		const uint32_t cap = e->tb.ser.cap;
-		const size_t C = e->cfg.n_channels;
-		ta.period = P; ta.fill = (uint32_t) at.fill; ta.e0 = (uint32_t) series_e0 (at, P, c.n_frames);
-		ta.capacity = cap;
-		ta.point0 = at.points < cap ? (uint32_t) at.points : 0;
-		ta.room = at.points < cap ? cap - (uint32_t) at.points : 0;
-		ta.open = e->tb.open.p + c.off;
-		ta.s_level = cap ? e->tb.s_level.p + (size_t) c.off * cap * C : nullptr;
-		ta.s_peak = cap ? e->tb.s_peak.p + (size_t) c.off * cap * C : nullptr;
-		if (d_ends) {
-			mtr_tpb_series_ends_args ea;
-			static_cast<mtr_tpb_series_args&> (ea) = ta;
-			ea.ends = d_ends;
-			if (mtr_launch_tpb_series_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series, ends)");
-		} else if (mtr_launch_tpb_series (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series)");
-		nx.tb = series_advance (at, P, c.n_frames);
-		return MTR_OK;
-	}
-
 	// the 47 frames before the next call; after every consumer of the current history
 	int history ()
 	{
@@ -477,17 +424,17 @@ struct CallRun {
 		if (fold_in_history && e->red_pending) { HIPCHK (hipStreamWaitEvent (c.st, e->ev_red.v, 0)); e->red_pending = false; }
 		if (e->layout != 8 && d_ends && (e->cfg.meters & MTR_METER_TPBALLIST)) {
 			// (beside the true-peak bar a stream that ends inside the call leaves the frames in front of its OWN end: mtr_tpb.hip)
-			if (mtr_launch_history_ends (C, c.audio, c.stride, fir_hist (0), fir_hist (1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st))
+			if (mtr_launch_history_ends (C, c.audio, c.stride, fir_hist (e, c, 0), fir_hist (e, c, 1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st))
 				return fail (MTR_ERR_HIP, "k_history launch (ends)");
 		} else if (e->layout != 8) {
-			const int hrc = C == 2 ? mtr_launch_history (c.audio, c.stride, c.n_frames, fir_hist (0), fir_hist (1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st)
-			                       : mtr_launch_history_mono (c.audio, c.stride, c.n_frames, fir_hist (0), fir_hist (1), c.cnt, c.st);
+			const int hrc = C == 2 ? mtr_launch_history (c.audio, c.stride, c.n_frames, fir_hist (e, c, 0), fir_hist (e, c, 1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st)
+			                       : mtr_launch_history_mono (c.audio, c.stride, c.n_frames, fir_hist (e, c, 0), fir_hist (e, c, 1), c.cnt, c.st);
 			if (hrc) return fail (MTR_ERR_HIP, "k_history launch");
 		} else if (tp) {
 			const size_t vc = (size_t) c.off * C;
-			if (c.wave51 ? mtr_launch_history_mc51 (c.audio, c.stride, c.n_frames, mc_hist (0), mc_hist (1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc,
+			if (c.wave51 ? mtr_launch_history_mc51 (c.audio, c.stride, c.n_frames, mc_hist (e, c, 0), mc_hist (e, c, 1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc,
 			                                        e->mc_tp_hold.p + vc, state, d_ends, c.st)
-			             : mtr_launch_history_mc (c.audio, c.stride, c.n_frames, C, mc_hist (0), mc_hist (1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc, e->mc_tp_hold.p + vc,
+			             : mtr_launch_history_mc (c.audio, c.stride, c.n_frames, C, mc_hist (e, c, 0), mc_hist (e, c, 1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc, e->mc_tp_hold.p + vc,
 			                           state, d_ends, c.st))
 				return fail (MTR_ERR_HIP, "k_history_mc launch");
 		}
@@ -529,11 +476,10 @@ struct CallRun {
 		}
 		if ((rc = mark (4, c.st))) return rc;
 
-		const uint32_t* const gclose = d_gcut ? d_gcut + c.cnt : nullptr;
-		const StreamEnds se { d_ends, d_fall, d_gcut, gclose, d_gcut ? reinterpret_cast<const float*> (d_gcut + 2 * (size_t) c.cnt) : nullptr, go_last };   // (null on a dense call)
-		for (const SideMeter* m : SIDE_METERS)
-			if ((meters & m->bits) && m->step && (rc = m->step (e, c, nx, se))) return rc;
-		if ((meters & MTR_METER_TPBALLIST) && (rc = tpb ())) return rc;
+		for (size_t k = 0; k < std::size (SIDE_METERS); ++k) {
+			const SideMeter* const m = SIDE_METERS[k];
+			if ((meters & m->bits) && m->step && (rc = m->step (e, c, nx, se[k]))) return rc;
+		}
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
 		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, a side meter's LEN kernel, or the fused kernels)
 			HIPCHK (hipEventRecord (ls->done[0].v, c.st));
@@ -548,18 +494,9 @@ struct CallRun {
 		for (uint32_t i = 0; i < c.cnt; ++i) {
 			const size_t g = (size_t) c.off + i;
 			if (e->closed[g]) continue;
-			const uint64_t f = c.frames ? c.frames[i] : c.n_frames;
+			const uint64_t f = call_frames (e, c, i);
 			e->metered[g] += f;
-			if (meters & MTR_METER_SCOPE) scope_count (e, g, f);
-			if (meters & MTR_METER_GONIO) gonio_count (e, g, c.n_frames, f);
-			// points of the stream's own reading series: the blocks it completed and, closed inside one, the truncated block
-			for (const SideMeter* m : SIDE_METERS) {
-				if (!(meters & m->bits) || !m->series) continue;
-				const SeriesView v = m->series (e);
-				uint64_t whole = 0;
-				uint32_t partial = 0;
-				if (v.cfg->period && series_cut ((e->pos.*v.pos).fill, v.cfg->period, c.n_frames, f, &whole, &partial)) (*v.points)[g] += whole + partial;
-			}
+			stream_counts (e, g, &c, f);
 			if (log) {
 				// periods the stream completed: those that end within the fragments it ended (as upload_lengths counts them)
 				const uint64_t nf = f == c.n_frames ? pl.n_frag : (uint64_t) (std::upper_bound (pl.frag_end.begin (), pl.frag_end.end (), (uint32_t) f) - pl.frag_end.begin ());
@@ -696,6 +633,20 @@ static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frame
 	const int rc = process_call (e, c);
 	if (!rc && direct) e->lay_direct++;
 	return rc;
+}
+
+void stream_counts (mtr_engine* e, size_t g, const Call* c, uint64_t frames)
+{
+	for (const SideMeter* m : SIDE_METERS) {
+		if (!(e->cfg.meters & m->bits)) continue;
+		if (m->count) m->count (e, g, c, frames);
+		if (!m->series) continue;
+		const SeriesView v = m->series (e);
+		uint64_t whole = 0;
+		uint32_t partial = 0;
+		if (!c) (*v.points)[g] = (e->pos.*v.pos).points;
+		else if (v.cfg->period && series_cut ((e->pos.*v.pos).fill, v.cfg->period, c->n_frames, frames, &whole, &partial)) (*v.points)[g] += whole + partial;
+	}
 }
 
 // the counts of the one row of SIDE_METERS that has `bit` and keeps them (mtr_engine_series_points, mtr_engine_spectr_points)

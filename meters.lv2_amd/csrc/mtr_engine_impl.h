@@ -64,7 +64,8 @@ struct Stream {
 constexpr int PLAN_SLOTS = 4;
 
 // The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks / _ragged / _ends, or any call once a stream is closed) ride the same
-// way: [ends S | frag_lim S | from_tile S | km_fall S (KMETER engines)] in the next slot of their own ring, uploaded on the call's stream,
+// way: [ends S | frag_lim S | from_tile S], then the words of every side meter of the engine that has some of its own (SideMeter::ends_words
+// per stream, in the order of SIDE_METERS), in the next slot of their own ring, uploaded on the call's stream,
 // busy until the call's last readers (the last kernel of the call on its stream — the side meters' LEN kernels, k_history_len — and the
 // gate on whichever stream it ran) have passed.
 constexpr int LEN_SLOTS = 4;
@@ -374,19 +375,22 @@ struct Call {
 	bool            wave51 = false;
 };
 
-// The per-stream ends of a ragged call on the device, as the side meters' steps get them: ends[i] = the call frame at which stream i of the
-// view ends (0: closed, untouched), km_fall[i] = Kmeterdsp's fall-back factor for a stream that ends inside the call (KMETER engines: that of
-// its frames in the call, or — with a period — of its frames in the truncated block; SURROUND engines: that of its frames in the call).
-// Both null on a dense call: the steps then launch the dense instantiations.
-// GONIO engines: go_cut[i] = the call frame at which the stream's drawing ends (MTR_GONIO_OPEN: not in this call), go_closing[i] = the frames
-// of its closing display update or 0, go_attack[i][2] = that update's attack pair (gonio_cut); go_last: the last call frame any stream draws.
+// the frames stream i of the view takes of call `c`: its own length or the call's, 0 for a closed stream (every call leaves it untouched)
+inline uint64_t call_frames (const mtr_engine* e, const Call& c, uint32_t i)
+{
+	return e->closed[c.off + i] ? 0 : c.frames ? c.frames[i] : c.n_frames;
+}
+// the ping-pong histories of the view: flip = 0 what the call reads, 1 what k_history writes for the next one
+inline float* fir_hist (const mtr_engine* e, const Call& c, int flip) { return e->fir_hist[e->pos.hist_cur ^ flip].p + (size_t) c.off * MTR_FIR_HALO * 2; }
+inline float* mc_hist (const mtr_engine* e, const Call& c, int flip) { return e->mc_hist[e->pos.hist_cur ^ flip].p + (size_t) c.off * MTR_FIR_HALO * e->cfg.n_channels; }
+
+// The per-stream ends of a ragged call on the device, as a side meter's step gets them: ends[i] = the call frame at which stream i of the
+// view ends (0: closed, untouched); own = the meter's own words of the call (SideMeter::ends_words per stream, as its ends_fill laid them
+// out), null if it has none; note = what that fill returned.  All null / 0 on a dense call: the steps then launch the dense instantiations.
 struct StreamEnds {
 	const uint32_t* ends = nullptr;
-	const float*    km_fall = nullptr;
-	const uint32_t* go_cut = nullptr;
-	const uint32_t* go_closing = nullptr;
-	const float*    go_attack = nullptr;
-	uint64_t        go_last = 0;
+	const uint32_t* own = nullptr;
+	uint64_t        note = 0;
 };
 
 struct StateSection { const void* base; size_t elem; };   // a per-stream array of the state blob: `elem` bytes per stream
@@ -446,31 +450,36 @@ struct SideMeter {
 	void (*sections) (const mtr_engine* e, std::vector<StateSection>& v);   // appends the arrays a stream carries from call to call
 	const BlobHeader* hdr;                                        // in the first of them, or null
 	SeriesView (*series) (mtr_engine* e);                         // the meter's reading series, if it counts its points per stream, or null
+	// what stream g counts that is no block of a `series`, or null.  With a call: g took `frames` of call *c, which starts at e->pos;
+	// c == nullptr: g was imported and takes the lock-step numbers
+	void (*count) (mtr_engine* e, size_t g, const Call* c, uint64_t frames);
+	// The meter's own per-stream words of a ragged call: ends_words per stream in the lengths ring (0: none), in an engine that holds the
+	// meter.  ends_fill writes the ends_words * c.cnt host words of the view at `own` — laid out as the meter likes, read by its step at
+	// StreamEnds::own — from call_frames and e->pos, where the CALL started (every chunk of a host call sees the same cuts), and returns
+	// one host-side note for that step (StreamEnds::note)
+	uint32_t ends_words;
+	uint64_t (*ends_fill) (const mtr_engine* e, const Call& c, uint32_t* own);
 };
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
 extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
-                 bank_series_meter, scope_series_meter, tpb_series_meter, gonio_meter;
+                 bank_series_meter, scope_series_meter, tpb_meter, gonio_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
                                                     &kmeter_series_meter,     // (KMETER's second row: nothing but the blob section of its open block, behind every older one)
                                                     &bank_series_meter,       // (SPECTR30's second row, likewise)
                                                     &scope_series_meter,      // (SCOPE's second row, likewise)
-                                                    &tpb_series_meter,        // (TPBALLIST, whose kernel the call launches itself: the series' reset and the open block's section)
+                                                    &tpb_meter,               // (TPBALLIST: its states are the stream state's; the section is its series' open block)
                                                     &gonio_meter };
 // the points of each of streams [first, first + count) in the series of the meter with `bit`, which the engine holds and which keeps such counts
 void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points);
+// Stream g's own counts, every meter's of the engine: the points of the reading series (the blocks the stream completed and, closed inside one,
+// the truncated block) and what the `count` hooks keep.  With a call: g took `frames` of call *c, which starts at e->pos; c == nullptr:
+// g was imported and stands where the open streams do
+void stream_counts (mtr_engine* e, size_t g, const Call* c, uint64_t frames);
 
-// SCOPE counts analyses and the points among them, not blocks of a period: stream g's own counts move by those of `frames` frames of a
-// call that starts at e->pos (no `series` hook: that one is the periods')
-void scope_count (mtr_engine* e, size_t g, uint64_t frames);
-// GONIO: what a stream that takes `frames` of a call of n_frames draws, the call starting `fill` frames into a display update of P
-// (mtr_gonio_cut is this): *whole updates of P frames it completes, a closing one of `closing` frames (0: none; else >= 64) with its
-// attack pair, and `drawn`: the call frame at which its drawing ends.  `c`: a resolved configuration (its dials are read)
-struct GonioCut { uint64_t whole = 0, drawn = 0; uint32_t closing = 0; float attack[2] = { 0.f, 0.f }; };
-GonioCut gonio_cut (uint64_t fill, uint32_t P, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config& c);
-// ... and stream g's own count of display updates moves by those of `frames` frames of a call of n_frames that starts at e->pos
-void gonio_count (mtr_engine* e, size_t g, uint64_t n_frames, uint64_t frames);
-float kmeter_fall (const mtr_engine* e, uint64_t n);        // Kmeterdsp's fall-back factor for a process () of n frames
+// Kmeterdsp's fall-back factor for each stream of the view that ends inside call `c`, 0.f for every other, as floats at own [c.cnt]: the
+// ends_fill of KMETER and of SURROUND's K-meters, each with its own cursor's fill and its period (mtr_kmeter.hip)
+void kmeter_falls (const mtr_engine* e, const Call& c, uint64_t fill, uint64_t P, uint32_t* own);
 // the loudness log (no side meter: the gate writes it): what the gate of a call that starts at cursors `pos` appends to, for the view
 // [off, off + cnt) (false: the log is off); its part of mtr_engine_reset
 bool loudlog_args (const mtr_engine* e, const Cursors& pos, uint32_t off, mtr_loudlog_args* out);

@@ -529,8 +529,12 @@ static hipError_t gonio_states (mtr_engine* e, uint32_t first, uint32_t count, m
 
 // Track lengths (mtr_gonio_ends.h).  draw_rb returns at n_samples < 64 (:302): a closing stream gets one last update of the r frames it has
 // of its open block if r >= 64, and stands where its last whole block left it otherwise — but never in front of the call's first frame:
-// what earlier calls drew of the open block stays drawn
-GonioCut gonio_cut (uint64_t fill, uint32_t P, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config& c)
+// what earlier calls drew of the open block stays drawn.
+// What a stream that takes `frames` of a call of n_frames draws, the call starting `fill` frames into a display update of P (mtr_gonio_cut
+// is this): `whole` updates of P frames it completes, a closing one of `closing` frames (0: none; else >= 64) with its attack pair, and
+// `drawn`: the call frame at which its drawing ends.  `c`: a resolved configuration (its dials are read)
+struct GonioCut { uint64_t whole = 0, drawn = 0; uint32_t closing = 0; float attack[2] = { 0.f, 0.f }; };
+static GonioCut gonio_cut (uint64_t fill, uint32_t P, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config& c)
 {
 	GonioCut o;
 	const uint64_t tot = fill + frames, r = tot % P;
@@ -543,10 +547,37 @@ GonioCut gonio_cut (uint64_t fill, uint32_t P, double rate, uint64_t n_frames, u
 	return o;
 }
 
-void gonio_count (mtr_engine* e, size_t g, uint64_t n_frames, uint64_t frames)
+// the cut of a stream that takes `frames` of call `c`, taken from where the CALL started (e->pos): every chunk of a host call sees the same ones
+static GonioCut gonio_cut (const mtr_engine* e, const Call& c, uint64_t frames)
 {
-	const GonioCut k = gonio_cut (e->pos.go.fill, e->go.cfg.period_frames, (double) e->cfg.sample_rate, n_frames, frames, e->go.cfg);
+	return gonio_cut (e->pos.go.fill, e->go.cfg.period_frames, (double) e->cfg.sample_rate, c.n_frames, frames, e->go.cfg);
+}
+
+// stream g's own display updates (SideMeter::count — with draw_rb's 64-frame floor, not every partial block: no `series` hook): those of
+// its `frames` frames of the call, the closing one included; an imported stream takes the lock-step number
+static void gonio_count (mtr_engine* e, size_t g, const Call* c, uint64_t frames)
+{
+	if (!c) { e->go.updates[g] = e->pos.go.points; return; }
+	const GonioCut k = gonio_cut (e, *c, frames);
 	e->go.updates[g] += k.whole + (k.closing ? 1 : 0);
+}
+
+// The meter's words of a ragged call (SideMeter::ends_fill): [cut S | closing S | attack S x 2], per stream of the view the call frame at
+// which its drawing ends (MTR_GONIO_OPEN: not in this call), the frames of its closing display update or 0, that update's attack pair.
+// The note: the last call frame any stream of the view draws
+static uint64_t gonio_ends_fill (const mtr_engine* e, const Call& c, uint32_t* own)
+{
+	const size_t S = c.cnt;
+	uint64_t last = 0;
+	for (uint32_t i = 0; i < S; ++i) {
+		const uint64_t f = call_frames (e, c, i);
+		const GonioCut k = gonio_cut (e, c, f);
+		own[i] = f == c.n_frames ? 0xFFFFFFFFu : (uint32_t) k.drawn;     // (MTR_GONIO_OPEN: the stream does not end in this call)
+		own[S + i] = k.closing;
+		memcpy (own + 2 * S + 2 * (size_t) i, k.attack, sizeof (k.attack));
+		last = std::max (last, k.drawn);
+	}
+	return last;
 }
 
 static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
@@ -557,7 +588,7 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 	const size_t S = e->cfg.n_streams;
 	mtr_gonio_ends_args a;                                             // (a dense call launches on its base)
 	memset (static_cast<void*> (&a), 0, sizeof (a));
-	a.cut = se.go_cut; a.closing = se.go_closing; a.c_attack = se.go_attack;
+	if (se.own) { a.cut = se.own; a.closing = se.own + c.cnt; a.c_attack = reinterpret_cast<const float*> (se.own + 2 * (size_t) c.cnt); }   // (gonio_ends_fill)
 	a.audio = c.audio; a.stride = c.stride; a.n_streams = c.cnt;
 	a.P = P; a.capacity = cap; a.shift = g.shift; a.G = d.G; a.code_pitch = e->go.code_pitch;
 	a.hpw = d.hpw; a.attack[0] = d.attack[0]; a.attack[1] = d.attack[1]; a.g_target = d.g_target; a.g_rms = d.g_rms;
@@ -575,7 +606,7 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 		a.n = (uint32_t) std::min<uint64_t> (g.tune_piece, c.n_frames - f0);
 		a.fill = (uint32_t) pos.fill; a.point0 = pos.points;
 		// (per-stream ends: only the pieces in which some stream of the view still draws are launched; the cursor moves on regardless)
-		if (se.ends && f0 >= se.go_last) { pos = series_advance (pos, P, a.n); continue; }
+		if (se.ends && f0 >= se.note) { pos = series_advance (pos, P, a.n); continue; }
 		hipEvent_t ev[3];
 		const bool tm = e->go.timed && c.commit;
 		if (tm) {
@@ -620,7 +651,7 @@ static void gonio_hdr_take (mtr_engine* e, const void* in) { e->pos.go.fill = st
 
 static constinit BlobHeader gonio_hdr = { 0, sizeof (mtr_gonio_hdr), GONIO_CORRUPT, gonio_hdr_write, gonio_hdr_check, gonio_hdr_take };
 
-constinit SideMeter gonio_meter = { MTR_METER_GONIO, 0, nullptr, gonio_create, mtr_engine_gonio_reset, gonio_step, gonio_sections, &gonio_hdr, nullptr };
+constinit SideMeter gonio_meter = { MTR_METER_GONIO, 0, nullptr, gonio_create, mtr_engine_gonio_reset, gonio_step, gonio_sections, &gonio_hdr, nullptr, gonio_count, 4, gonio_ends_fill };
 
 extern "C" {
 

@@ -531,10 +531,23 @@ static int mtr_launch_kmb (const mtr_kmb_args& a, void* stream)
 // ---- KMETER in the engine: the call's step, the blob's section, reset, the reading ------------------------------------------------------
 
 // kmeterdsp.cc:60-65: the fall-back factor of a process () of n frames (15 dB/s)
-float kmeter_fall (const mtr_engine* e, uint64_t n)
+static float kmeter_fall (const mtr_engine* e, uint64_t n)
 {
 	return powf (10.0f, -0.05f * 15.0f * ((float) n / e->cfg.sample_rate));
 }
+
+// A K-meter's word of a ragged call: the fall-back factor of each stream of the view that ends inside the call.  Its process () is one of
+// f frames (kmeterdsp.cc:60-65 with fpp = f; every other stream takes the cursor's) — with a period P: one of the frames it has of the
+// block it ends in, if it ends inside one; `fill`: the frames into the open block where the call started
+void kmeter_falls (const mtr_engine* e, const Call& c, uint64_t fill, uint64_t P, uint32_t* own)
+{
+	float* const fall = reinterpret_cast<float*> (own);
+	for (uint32_t i = 0; i < c.cnt; ++i) {
+		const uint64_t f = call_frames (e, c, i), kf = P ? (fill + f) % P : f;
+		fall[i] = f && f < c.n_frames && kf ? kmeter_fall (e, kf) : 0.f;
+	}
+}
+static uint64_t kmeter_ends_fill (const mtr_engine* e, const Call& c, uint32_t* own) { kmeter_falls (e, c, e->pos.km.fill, e->km.ser.period, own); return 0; }
 
 static uint32_t kmeter_min_period (const mtr_engine* e) { return (uint32_t) e->cfg.sample_rate / 20; }
 
@@ -566,7 +579,7 @@ static int kmeter_blocks_step (mtr_engine* e, const Call& c, Cursors& nx, const 
 	ka.open = reinterpret_cast<mtr_kmeter_open*> (e->km.open.p) + vo;
 	ka.piece = e->km.bpiece.p + vo * ka.n_pieces * C * MTR_KMB_PIECE;
 	if (cap) { ka.s_rms = e->km.s_rms.p + vo * cap * C; ka.s_peak = e->km.s_peak.p + vo * cap * C; }
-	ka.ends = se.ends; ka.falls = se.km_fall;
+	ka.ends = se.ends; ka.falls = reinterpret_cast<const float*> (se.own);
 	if (mtr_launch_kmb (ka, c.st)) return fail (MTR_ERR_HIP, "k_kmeter_blocks launch");
 	nx.km = series_advance (e->pos.km, P, c.n_frames);
 	return MTR_OK;
@@ -578,7 +591,7 @@ static int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamE
 	const size_t vo = c.off;
 	mtr_kmeter_args ka;
 	ka.audio = c.audio; ka.stride = c.stride; ka.n_groups = c.n_frames / 4;
-	ka.n_streams = c.cnt; ka.n_channels = e->cfg.n_channels; ka.ends = se.ends; ka.falls = se.km_fall;
+	ka.n_streams = c.cnt; ka.n_channels = e->cfg.n_channels; ka.ends = se.ends; ka.falls = reinterpret_cast<const float*> (se.own);
 	ka.n_pieces = mtr_kmeter_pieces (ka.n_groups);
 	if (nx.km_fpp != (uint32_t) c.n_frames) {                          // kmeterdsp.cc:60-65
 		nx.km_fall = kmeter_fall (e, c.n_frames);
@@ -643,7 +656,7 @@ constinit SideMeter kmeter_series_meter = { MTR_METER_KMETER, 0, nullptr, nullpt
 static SeriesView kmeter_series (mtr_engine* e) { return { &e->km.ser, &Cursors::km, &e->km.points }; }
 
 constinit SideMeter kmeter_meter = { MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr, kmeter_series };
+                                           nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr, kmeter_series, nullptr, 1, kmeter_ends_fill };
 
 extern "C" {
 

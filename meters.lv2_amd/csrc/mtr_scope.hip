@@ -477,9 +477,11 @@ static int scope_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 	return MTR_OK;
 }
 
-// stream g's own analyses and points (mtr_engine_scope_points): those of its `frames` frames of a call that starts at e->pos
-void scope_count (mtr_engine* e, size_t g, uint64_t frames)
+// stream g's own analyses and points (mtr_engine_scope_points; SideMeter::count — analyses and the points among them, not blocks of a period:
+// no `series` hook): those of its `frames` frames of a call that starts at e->pos; an imported stream takes the lock-step numbers
+static void scope_count (mtr_engine* e, size_t g, const Call* c, uint64_t frames)
 {
+	if (!c) { e->sp.analyses[g] = e->pos.sp_analyses; e->sp.points[g] = e->pos.sp_points; return; }
 	uint64_t an, pt;
 	series_cut (e->pos.sp_fill, e->sp.H, e->pos.sp_since, e->sp.ser.every, frames, &an, &pt);
 	e->sp.analyses[g] += an; e->sp.points[g] += pt;
@@ -525,7 +527,7 @@ static void scope_hdr_take (mtr_engine* e, const void* in)
 
 static constinit BlobHeader scope_hdr = { 0, sizeof (mtr_scope_hdr), SCOPE_CORRUPT, scope_hdr_write, scope_hdr_check, scope_hdr_take };
 constinit SideMeter scope_meter = { MTR_METER_SCOPE, 0x7fffffffull, "SCOPE: n_frames per call must be < 2^31 - 1",
-                                          scope_create, mtr_engine_scope_reset, scope_step, scope_sections, &scope_hdr };
+                                          scope_create, mtr_engine_scope_reset, scope_step, scope_sections, &scope_hdr, nullptr, scope_count };
 
 // With a series the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): where the open group
 // of K analyses stands.  All of an entry is its host-owned header — K and the analyses since the last point.  An engine takes a blob of its

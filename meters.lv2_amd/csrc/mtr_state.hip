@@ -190,12 +190,6 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 	for (uint32_t k = 0; k < h.count; ++k) {                     // (an imported stream is open — closure is not part of the blob — and
 		if (e->closed[first + k]) { e->closed[first + k] = 0; e->n_closed--; }   // its count starts again: the blob does not carry one)
 		e->metered[first + k] = 0;
-		// (... and it stands where the open streams do: its series have their points)
-		for (const SideMeter* m : SIDE_METERS) {
-			if (!(e->cfg.meters & m->bits) || !m->series) continue;
-			const SeriesView v = m->series (e);
-			(*v.points)[first + k] = (e->pos.*v.pos).points;
-		}
 	}
 	if (fresh) {                                                 // (only now: a failed sync or copy has not moved the engine)
 		e->pos.frcnt = h.frcnt; e->integr = h.integr != 0; e->bank.omega = h.omega; e->pos.dr_scnt = h.dr_scnt;
@@ -204,12 +198,9 @@ int mtr_engine_state_import (mtr_engine* e, uint32_t first, const void* blob, si
 		e->plan.valid = false;
 		e->advanced = true;
 	}
-	// (SCOPE counts analyses, not frames: its per-stream counts are its own.  An imported stream takes the lock-step numbers)
-	if (e->cfg.meters & MTR_METER_SCOPE)
-		for (uint32_t k = 0; k < h.count; ++k) { e->sp.analyses[first + k] = e->pos.sp_analyses; e->sp.points[first + k] = e->pos.sp_points; }
-	// (GONIO counts display updates with draw_rb's 64-frame floor, not every partial block: likewise)
-	if (e->cfg.meters & MTR_METER_GONIO)
-		for (uint32_t k = 0; k < h.count; ++k) e->go.updates[first + k] = e->pos.go.points;
+	// (... and an imported stream stands where the open streams do, a fresh engine's at the cursors it just took: its own counts — the
+	// points of its series, what the meters' count hooks keep — are the lock-step numbers)
+	for (uint32_t k = 0; k < h.count; ++k) stream_counts (e, first + k, nullptr, 0);
 	return MTR_OK;
 }
 

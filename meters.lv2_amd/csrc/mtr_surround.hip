@@ -652,12 +652,15 @@ static int surround_step (mtr_engine* e, const Call& c, Cursors& nx, const Strea
 	if (se.ends) {
 		mtr_sur_len_args la;
 		static_cast<mtr_sur_args&> (la) = sa;
-		la.ends = se.ends; la.falls = se.km_fall;
+		la.ends = se.ends; la.falls = reinterpret_cast<const float*> (se.own);
 		if (mtr_launch_sur (la, c.st)) return fail (MTR_ERR_HIP, "k_sur launch (ends)");
 	} else if (mtr_launch_sur (sa, c.st)) return fail (MTR_ERR_HIP, "k_sur launch");
 	nx.su = series_advance (e->pos.su, P, c.n_frames);
 	return MTR_OK;
 }
+
+// the meter's word of a ragged call (SideMeter::ends_fill): its K-meters' fall-back factor, as KMETER's from the meter's own cursor
+static uint64_t surround_ends_fill (const mtr_engine* e, const Call& c, uint32_t* own) { kmeter_falls (e, c, e->pos.su.fill, e->su.ser.period, own); return 0; }
 
 static void surround_sections (const mtr_engine* e, std::vector<StateSection>& v)
 {
@@ -702,7 +705,7 @@ static void surround_hdr_take (mtr_engine* e, const void* in)
 static constinit BlobHeader surround_hdr = { 0, SUR_HDR_BYTES, SUR_CORRUPT, surround_hdr_write, surround_hdr_check, surround_hdr_take };
 static SeriesView surround_series (mtr_engine* e) { return { &e->su.ser, &Cursors::su, &e->su.points }; }
 constinit SideMeter surround_meter = { MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                             surround_create, mtr_engine_surround_reset, surround_step, surround_sections, &surround_hdr, surround_series };
+                                             surround_create, mtr_engine_surround_reset, surround_step, surround_sections, &surround_hdr, surround_series, nullptr, 1, surround_ends_fill };
 
 extern "C" {
 

@@ -1155,8 +1155,8 @@ int mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_fra
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-// ---- TPBALLIST's reading series in the engine: the blob's section, reset, the entry points of mtr_tpb.h -------------------------------
-// (the call's step is CallRun::tpb, mtr_call.hip; tools/tpb_prof.hip builds the kernels alone)
+// ---- TPBALLIST in the engine: the call's step, the blob's section, reset, the entry points of mtr_tpb.h --------------------------------
+// (tools/tpb_prof.hip builds the kernels alone)
 #ifndef MTR_TPB_PROF
 #include <cstddef>
 #include <cstring>
@@ -1165,6 +1165,46 @@ int mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_fra
 
 constexpr uint32_t TPB_MIN_PERIOD = F;         // the kernel's chunk: at most one block end in any of them
 constexpr uint32_t TPB_MAX_PERIOD = 8192;      // truepeakdsp.cc:44: a block is one process ()
+
+// (the 47 frames in front of the call are the call path's: CallRun::history moves them on behind every step, for TRUEPEAK as for this meter)
+static int tpb_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
+{
+	mtr_tpb_series_args ta;
+	ta.audio = c.audio; ta.stride = c.stride; ta.n_frames = c.n_frames;
+	ta.hist = fir_hist (e, c, 0); ta.mfma_a = e->m16_a.p; ta.state = e->state.p + c.off;
+	ta.n_streams = c.cnt; ta.n_channels = e->cfg.n_channels;
+	ta.w1 = e->tpb_w[0]; ta.w2 = e->tpb_w[1]; ta.w3 = e->tpb_w[2]; ta.g = e->tpb_w[3];
+	const uint32_t P = e->tb.ser.period;
+	// (a call with ends — mtr_engine_process_*_tpb, or any call once a stream of the view is closed — takes the ENDS instantiations)
+	if (!P) {
+		if (se.ends) {
+			mtr_tpb_ends_args ea;
+			static_cast<mtr_tpb_args&> (ea) = ta;
+			ea.ends = se.ends;
+			if (mtr_launch_tpb_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (ends)");
+		} else if (mtr_launch_tpb (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch");
+		return MTR_OK;
+	}
+	// the reading series (mtr_tpb.h).  The blocks are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
+	const SeriesPos& at = e->pos.tb;
+	const uint32_t cap = e->tb.ser.cap;
+	const size_t C = e->cfg.n_channels;
+	ta.period = P; ta.fill = (uint32_t) at.fill; ta.e0 = (uint32_t) series_e0 (at, P, c.n_frames);
+	ta.capacity = cap;
+	ta.point0 = at.points < cap ? (uint32_t) at.points : 0;
+	ta.room = at.points < cap ? cap - (uint32_t) at.points : 0;
+	ta.open = e->tb.open.p + c.off;
+	ta.s_level = cap ? e->tb.s_level.p + (size_t) c.off * cap * C : nullptr;
+	ta.s_peak = cap ? e->tb.s_peak.p + (size_t) c.off * cap * C : nullptr;
+	if (se.ends) {
+		mtr_tpb_series_ends_args ea;
+		static_cast<mtr_tpb_series_args&> (ea) = ta;
+		ea.ends = se.ends;
+		if (mtr_launch_tpb_series_ends (ea, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series, ends)");
+	} else if (mtr_launch_tpb_series (ta, c.st)) return fail (MTR_ERR_HIP, "k_tpb launch (series)");
+	nx.tb = series_advance (at, P, c.n_frames);
+	return MTR_OK;
+}
 
 // With a period the blob carries one more section, behind every older one: the open block.  Its header: period, the frames into the
 // open block.  An engine takes a blob of its own period only
@@ -1218,10 +1258,9 @@ static int tpb_series_reset (mtr_engine* e)
 }
 
 static constinit BlobHeader tpb_hdr = { 0, TPB_HDR_BYTES, TPB_CORRUPT, tpb_hdr_write, tpb_hdr_check, tpb_hdr_take };
-// (no step: CallRun::tpb launches the kernel, with the series or without)
 static int tpb_series_create (mtr_engine* e) { e->tb.points.assign (e->cfg.n_streams, 0); return MTR_OK; }
 static SeriesView tpb_series (mtr_engine* e) { return { &e->tb.ser, &Cursors::tb, &e->tb.points }; }
-constinit SideMeter tpb_series_meter = { MTR_METER_TPBALLIST, 0, nullptr, tpb_series_create, tpb_series_reset, nullptr, tpb_open_sections, &tpb_hdr, tpb_series };
+constinit SideMeter tpb_meter = { MTR_METER_TPBALLIST, 0, nullptr, tpb_series_create, tpb_series_reset, tpb_step, tpb_open_sections, &tpb_hdr, tpb_series };
 
 static int no_tpb (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_TPBALLIST); }
 static const char* const NO_TPB = "no TPBALLIST in this engine";

@@ -280,6 +280,70 @@ def test_beside_the_other_meters(M):
         assert bytes(b.results()) == res and bytes(a.results()) == ra
 
 
+KM_P, TPB_P = 2500, 64                      # KMETER's and TPBALLIST's periods: planted ends on a block's edge (2500; 64, 128, 1024, 2048) and inside one
+
+
+def beside(e, M):
+    """what the meters beside the goniometer report, floats as bits()"""
+    o = dict(results=np.frombuffer(bytes(e.results()), np.uint8), km_points=e.series_points(M.METER_KMETER), tpb_points=e.tpb_points())
+    groups = dict(km_read=e.kmeter_read(), km_series=e.kmeter_series(), tpb_series=e.tpb_series(), scope_points=e.scope_points(),
+                  scope_read=tuple(v for _, v in sorted(e.scope_read().items())))
+    for name, vals in groups.items():
+        for i, v in enumerate(vals):
+            v = np.asarray(v)
+            o[f"{name}[{i}]"] = bits(v) if v.dtype == np.float32 else v
+    return o
+
+
+def test_beside_kmeter_tpb_and_scope(M):
+    """Two rows of the side meters' table with words of their own in the lengths ring (KMETER, GONIO) in one engine, TPBALLIST's kernel
+    queued in front of the goniometer's, SCOPE's and GONIO's per-stream counts: engine b (with GONIO) gives every other meter what engine a
+    (without) gives it, byte for byte, and the goniometer what it draws alone — through the device and the host entry points, the latter
+    in two views of the batch"""
+    ends, x, more = ENDS(), signal(S, T), signal(S, 1000, 7)
+    one = ref_planted(0)
+    GE.coverage_ends(one, 0)
+    closing = ends[(ends > 0) & (ends < T)].astype(np.int64)
+    for p in (KM_P, TPB_P):
+        assert (closing % p == 0).any() and (closing % p != 0).any(), p        # an end on a block's edge, an end inside a block
+    closed = np.nonzero(ends < T)[0]
+    base = M.METER_EBU | M.METER_TRUEPEAK | M.METER_KMETER | M.METER_TPBALLIST | M.METER_SCOPE
+    dev, dev2 = device(x), device(more)
+    for host in (False, True):
+        with M.Engine(S, FS, base) as a, M.Engine(S, FS, base | M.METER_GONIO) as b:
+            b.gonio_configure(**CFG)
+            for e in (a, b):
+                e.kmeter_set_period(KM_P, 4)
+                e.tpb_set_period(TPB_P, 96)
+                e.scope_configure(256, 100)
+                e.scope_set_series(3, 8)
+                e.integr_start()
+                if host:
+                    e.set_host_chunk_bytes(40 * T * 8)                             # two views of the batch: the second starts at stream 34
+            if host:
+                a.process_any(x, ends)
+                b.process_gonio_ends(x, ends)
+            else:
+                a.process_device_any(dev.data_ptr(), T, ends)
+                b.process_device_gonio_ends(dev.data_ptr(), T, ends)
+            a.sync(), b.sync()
+            same(beside(a, M), beside(b, M))
+            got = snap(b)
+            same(got, want(one))
+            # a second call on the partly closed batch: the ends ride along without a family call
+            for e in (a, b):
+                if host:
+                    e.process(more)
+                else:
+                    e.process_device(dev2.data_ptr(), 1000)
+                e.sync()
+            wa, wb = beside(a, M), beside(b, M)
+            same(wa, wb)
+            assert (wa["tpb_points"] > np.uint64(T // TPB_P)).any() and (wa["scope_points[0]"][closed] <= np.uint64(T // 100)).all()
+            assert np.array_equal(a.stream_frames()[0], b.stream_frames()[0]) and np.array_equal(b.stream_frames()[1].astype(bool), ends < T)
+            same(snap(b), got, rows=closed, skip=("blocks", "s_gain", "s_drawn", "s_clipped"))
+
+
 # ---- 6: the state blob --------------------------------------------------------------------------------------------------------------------
 def test_a_closed_stream_travels_open(M):
     """export behind a closing call, import into a fresh engine: the closed streams are open, stand at the lock-step fill and go on as the
