@@ -395,7 +395,7 @@ struct CallRun {
 		ga.tail_tile = ebu ? pl.tail_tile : 0;
 		ga.fragm = (float) e->fragm; ga.integr = e->integr ? 1 : 0;
 		ga.max_scratch = e->gate_max.p + (size_t) c.off * 2;
-		ga.fold_tp = (fold_in_history || e->layout == 8) ? 0 : 1;   // (layout 8: k_history_mc folds the per-channel peaks)
+		ga.fold_tp = (fold_in_history || e->layout == 8) ? 0 : 1;   // (layout 8: k_history folds the per-channel peaks)
 		ga.polite_grid = r.defer ? e->tail_gate_grid : 0;
 		// (the loudness log: where the streams stand in it is an argument, computed here — the gate may run a call late)
 		mtr_loudlog_args la;
@@ -422,22 +422,21 @@ struct CallRun {
 		mtr_stream_state* const state = e->state.p + c.off;
 		// (deferred: the fold of this call's peaks rides here — behind the reduction of the previous call, which reads the holds)
 		if (fold_in_history && e->red_pending) { HIPCHK (hipStreamWaitEvent (c.st, e->ev_red.v, 0)); e->red_pending = false; }
-		if (e->layout != 8 && d_ends && (e->cfg.meters & MTR_METER_TPBALLIST)) {
-			// (beside the true-peak bar a stream that ends inside the call leaves the frames in front of its OWN end: mtr_tpb.hip)
-			if (mtr_launch_history_ends (C, c.audio, c.stride, fir_hist (e, c, 0), fir_hist (e, c, 1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st))
-				return fail (MTR_ERR_HIP, "k_history launch (ends)");
-		} else if (e->layout != 8) {
-			const int hrc = C == 2 ? mtr_launch_history (c.audio, c.stride, c.n_frames, fir_hist (e, c, 0), fir_hist (e, c, 1), c.cnt, fold_in_history ? state : nullptr, d_ends, c.st)
-			                       : mtr_launch_history_mono (c.audio, c.stride, c.n_frames, fir_hist (e, c, 0), fir_hist (e, c, 1), c.cnt, c.st);
-			if (hrc) return fail (MTR_ERR_HIP, "k_history launch");
-		} else if (tp) {
+		mtr_history_args ha = {};
+		ha.audio = c.audio; ha.stride = c.stride; ha.n_frames = c.n_frames; ha.n_streams = c.cnt; ha.ends = d_ends;
+		ha.C = C; ha.FC = c.wave51 ? 6 : C;
+		if (e->layout != 8) {
+			ha.HC = 2; ha.hist_in = fir_hist (e, c, 0); ha.hist_out = fir_hist (e, c, 1);
+			ha.fold_state = fold_in_history ? state : nullptr;
+		} else {
 			const size_t vc = (size_t) c.off * C;
-			if (c.wave51 ? mtr_launch_history_mc51 (c.audio, c.stride, c.n_frames, mc_hist (e, c, 0), mc_hist (e, c, 1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc,
-			                                        e->mc_tp_hold.p + vc, state, d_ends, c.st)
-			             : mtr_launch_history_mc (c.audio, c.stride, c.n_frames, C, mc_hist (e, c, 0), mc_hist (e, c, 1), c.cnt, e->mc_tp_call.p + vc, e->mc_tp_last.p + vc, e->mc_tp_hold.p + vc,
-			                           state, d_ends, c.st))
-				return fail (MTR_ERR_HIP, "k_history_mc launch");
+			ha.HC = C; ha.hist_in = mc_hist (e, c, 0); ha.hist_out = mc_hist (e, c, 1);
+			ha.tp_call = e->mc_tp_call.p + vc; ha.tp_last = e->mc_tp_last.p + vc; ha.tp_hold = e->mc_tp_hold.p + vc; ha.state = state;
 		}
+		// (beside the true-peak bar a stream that ends inside the call leaves the frames in front of its OWN end; everywhere else a call with
+		// lengths leaves those in front of the call's end: the two rules of mtr_history.hip)
+		const HistCut cut = !d_ends ? HIST_CALL_END : e->layout != 8 && (e->cfg.meters & MTR_METER_TPBALLIST) ? HIST_OWN_END : HIST_CALL_END_IF_TOUCHED;
+		if ((e->layout != 8 || tp) && mtr_launch_history (cut, ha, c.st)) return fail (MTR_ERR_HIP, "k_history launch");
 		nx.hist_cur = e->pos.hist_cur ^ 1;
 		return MTR_OK;
 	}
@@ -481,7 +480,7 @@ struct CallRun {
 			if ((meters & m->bits) && m->step && (rc = m->step (e, c, nx, se[k]))) return rc;
 		}
 		if ((meters & (MTR_METER_TRUEPEAK | MTR_METER_TPBALLIST)) && (rc = history ())) return rc;
-		if (ls) {                                                     // (the lengths' last reader on this stream: k_history_len, a side meter's LEN kernel, or the fused kernels)
+		if (ls) {                                                     // (the lengths' last reader on this stream: k_history under one of its ends rules, a side meter's LEN kernel, or the fused kernels)
 			HIPCHK (hipEventRecord (ls->done[0].v, c.st));
 			ls->pending[0] = true;
 		}
@@ -619,7 +618,7 @@ done:
 
 static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frames, uint64_t stride, const uint64_t* frames, void* hip_stream)
 {
-	// A frame layout.  WAVE 5.1 on a 5-channel engine: k_kwmc51 and k_history_mc51 read the 6-channel frames where they lie (a pick pass
+	// A frame layout.  WAVE 5.1 on a 5-channel engine: k_kwmc51 and k_history (FC = 6) read the 6-channel frames where they lie (a pick pass
 	// in front of an HBM-bound kernel would read 6/5 and write 5/5 of the batch on top).  Every other map: the wide rows are picked chunk
 	// by chunk into the staging buffers, as device PCM is decoded.
 	// (not beside the surround meter, whose kernel takes frames of the engine's five channels: that engine stages the call like any other map)

@@ -66,7 +66,7 @@ constexpr int PLAN_SLOTS = 4;
 // The per-stream arrays of a call with lengths (mtr_engine_process_*_lengths / _tracks / _ragged / _ends, or any call once a stream is closed) ride the same
 // way: [ends S | frag_lim S | from_tile S], then the words of every side meter of the engine that has some of its own (SideMeter::ends_words
 // per stream, in the order of SIDE_METERS), in the next slot of their own ring, uploaded on the call's stream,
-// busy until the call's last readers (the last kernel of the call on its stream — the side meters' LEN kernels, k_history_len — and the
+// busy until the call's last readers (the last kernel of the call on its stream — the side meters' LEN kernels, k_history under an ends rule — and the
 // gate on whichever stream it ran) have passed.
 constexpr int LEN_SLOTS = 4;
 struct LenSlot {
@@ -149,7 +149,7 @@ struct mtr_engine {
 	DevBuf<float>    fir_hist[2];   // ping-pong 47-frame history (pos.hist_cur)
 	DevBuf<float>    scan_m, bin_power, tile_power[2], frag_power, stage;
 	// layout 8 (n_channels 1, 3, 4, 5 with EBU / TRUEPEAK, mtr_kwmc.hip): per-channel side buffers; the stream state's kz / tp_* stay unused
-	// by the kernel, its tp_last / tp_hold [0..1] carry the max over the channels (k_history_mc)
+	// by the kernel, its tp_last / tp_hold [0..1] carry the max over the channels (mtr_fold_truepeak_mc in k_history)
 	DevBuf<float>    mc_kz;         // [S][C][4]
 	DevBuf<float>    mc_hist[2];    // [S][47][C] ping-pong with hist_cur
 	DevBuf<uint32_t> mc_tp_call;    // [S][C]
@@ -371,7 +371,7 @@ struct Call {
 	hipEvent_t      pcm_read = nullptr;
 	// frame layout: the rows at `pcm` (format 0: f32) hold frames of pick_fc samples, k_pick decodes and picks them (0: k_pcm on frames of C)
 	uint32_t        pick_fc = 0;
-	// ... or `audio` itself holds WAVE 5.1 frames, [cnt][stride][6], which the 5-channel kernels read themselves (k_kwmc51, k_history_mc51)
+	// ... or `audio` itself holds WAVE 5.1 frames, [cnt][stride][6], which the 5-channel kernels read themselves (k_kwmc51, k_history with FC = 6)
 	bool            wave51 = false;
 };
 

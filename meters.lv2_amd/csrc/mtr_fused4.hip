@@ -490,51 +490,6 @@ extern "C" int mtr_debug_f4_prof (unsigned long long* out)
 }
 #endif
 
-// New 47-frame history = the last 47 frames of (old history ++ this call's audio): what Resampler::process keeps in its
-// window between calls (zita-resampler/resampler.cc:229-262).
-// With a deferred gate (mtr_engine.hip) it also folds the call's true peak, in the gate's place: one lane per stream.
-__global__ void k_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                           float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state)
-{
-	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-	if (g >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
-	const int64_t f = (int64_t) n_frames - MTR_FIR_HALO + i;   // frame index in this call, may be < 0
-	const v2f* src = reinterpret_cast<const v2f*> (audio) + (size_t) s * stride;
-	const v2f* hin = reinterpret_cast<const v2f*> (hist_in) + (size_t) s * MTR_FIR_HALO;
-	v2f* hout = reinterpret_cast<v2f*> (hist_out) + (size_t) s * MTR_FIR_HALO;
-	hout[i] = (f >= 0) ? src[f] : hin[MTR_FIR_HALO + f];
-	if (fold_state && i == 0) mtr_fold_truepeak (fold_state + s);
-}
-
-// The same for a call with per-stream lengths: a stream the call does not touch (ends [s] == 0) keeps its history bit for bit
-// (the buffers ping-pong) and is not folded.  A stream that closes keeps whatever follows its end: nothing reads it again.
-__global__ void k_history_len (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                               float* hist_out, uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends)
-{
-	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-	if (g >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
-	const bool touched = ends[s] != 0;
-	const int64_t f = touched ? (int64_t) n_frames - MTR_FIR_HALO + i : (int64_t) i - MTR_FIR_HALO;
-	const v2f* src = reinterpret_cast<const v2f*> (audio) + (size_t) s * stride;
-	const v2f* hin = reinterpret_cast<const v2f*> (hist_in) + (size_t) s * MTR_FIR_HALO;
-	v2f* hout = reinterpret_cast<v2f*> (hist_out) + (size_t) s * MTR_FIR_HALO;
-	hout[i] = (f >= 0) ? src[f] : hin[MTR_FIR_HALO + f];
-	if (fold_state && touched && i == 0) mtr_fold_truepeak (fold_state + s);
-}
-
-int mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
-                        uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream)
-{
-	const dim3 grid ((n_streams * MTR_FIR_HALO + 255) / 256);
-	if (ends) hipLaunchKernelGGL (k_history_len, grid, dim3 (256), 0, (hipStream_t) stream,
-	                              audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state, ends);
-	else      hipLaunchKernelGGL (k_history, grid, dim3 (256), 0, (hipStream_t) stream,
-	                              audio, stride, n_frames, hist_in, hist_out, n_streams, fold_state);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
 int mtr_launch_kwtp16 (int run, bool ebu, const mtr_fused_args& a, uint32_t n_units, void* stream)
 {
 	switch (run) {

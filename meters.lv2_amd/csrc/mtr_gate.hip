@@ -313,7 +313,7 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN, LOG> a)
 		st->div2 = a.integr ? (div2_0 + (int) NFRAG) % 10 : div2_0;
 		st->cnt_M = sh_cnt[0]; st->cnt_S = sh_cnt[1]; st->err_M = sh_cnt[2]; st->err_S = sh_cnt[3];
 		// true-peak hold (a deferred gate runs beside the next call's fused kernel, which is already raising tp_call:
-		// then k_history has folded it on the caller's stream — mtr_fold_truepeak, mtr_internal.h)
+		// then k_history, mtr_history.hip, has folded it on the caller's stream — mtr_fold_truepeak, mtr_internal.h; layout 8: always)
 		if (a.fold_tp) mtr_fold_truepeak (st);
 		if constexpr (LOG) if (a.log.mode == MTR_LOUDLOG_MAX) { a.log.run[2 * s] = run_M; a.log.run[2 * s + 1] = run_S; }
 	}
@@ -710,122 +710,5 @@ int mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint3
 	hipLaunchKernelGGL (k_aggregate_init, dim3 (1), dim3 (256), 0, (hipStream_t) stream, d_hist, d_max);
 	hipLaunchKernelGGL (k_aggregate, dim3 ((n_streams + AGG_SPB - 1) / AGG_SPB), dim3 (256), 0, (hipStream_t) stream,
 	                    st, hist, n_streams, d_hist, d_max);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-// ---- the multichannel engines (layout 8): FIR history and the per-channel true-peak fold ------------------------------
-
-// New 47-frame history = the last 47 frames of (old history ++ this call's audio), C channels (zita-resampler/resampler.cc:229-262);
-// lane i == 0 of a stream also folds the call's peaks (src/ebulv2.cc:361-365, per channel) and reports the programme's true peak,
-// the max over the channels, in the stream state's two slots — what mtr_engine_results, k_aggregate and the reduction read.
-__global__ void k_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in,
-                              float* hist_out, uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state)
-{
-	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-	if (g >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
-	const int64_t f = (int64_t) n_frames - MTR_FIR_HALO + i;
-	for (uint32_t c = 0; c < C; ++c)
-		hist_out[((size_t) s * MTR_FIR_HALO + i) * C + c] = (f >= 0) ? audio[((size_t) s * stride + (size_t) f) * C + c]
-		                                                            : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * C + c];
-	if (!tp_call || i != 0) return;
-	float last = 0.f, hold = 0.f;
-	for (uint32_t c = 0; c < C; ++c) {
-		const size_t k = (size_t) s * C + c;
-		const float v = __uint_as_float (tp_call[k]);
-		tp_last[k] = v;
-		if (v > tp_hold[k]) tp_hold[k] = v;
-		tp_call[k] = 0;
-		last = fmaxf (last, v);
-		hold = fmaxf (hold, tp_hold[k]);
-	}
-	mtr_stream_state* const st = state + s;
-	st->tp_last[0] = st->tp_last[1] = last;
-	st->tp_hold[0] = st->tp_hold[1] = hold;
-	st->tp_call[0] = st->tp_call[1] = 0;
-}
-
-// The same for a call with per-stream lengths: a stream the call does not touch (ends [s] == 0) keeps its history bit for bit (the
-// buffers ping-pong) and its peaks are not folded.  A stream that closes keeps whatever follows its end: nothing reads it again.
-__global__ void k_history_mc_len (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in,
-                                  float* hist_out, uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                                  const uint32_t* ends)
-{
-	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-	if (g >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
-	const bool touched = ends[s] != 0;
-	const int64_t f = touched ? (int64_t) n_frames - MTR_FIR_HALO + i : (int64_t) i - MTR_FIR_HALO;
-	for (uint32_t c = 0; c < C; ++c)
-		hist_out[((size_t) s * MTR_FIR_HALO + i) * C + c] = (f >= 0) ? audio[((size_t) s * stride + (size_t) f) * C + c]
-		                                                            : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * C + c];
-	if (!tp_call || !touched || i != 0) return;
-	float last = 0.f, hold = 0.f;
-	for (uint32_t c = 0; c < C; ++c) {
-		const size_t k = (size_t) s * C + c;
-		const float v = __uint_as_float (tp_call[k]);
-		tp_last[k] = v;
-		if (v > tp_hold[k]) tp_hold[k] = v;
-		tp_call[k] = 0;
-		last = fmaxf (last, v);
-		hold = fmaxf (hold, tp_hold[k]);
-	}
-	mtr_stream_state* const st = state + s;
-	st->tp_last[0] = st->tp_last[1] = last;
-	st->tp_hold[0] = st->tp_hold[1] = hold;
-	st->tp_call[0] = st->tp_call[1] = 0;
-}
-
-// The same two for five channels read from WAVE 5.1 frames (audio [S][stride][6]: L R C LFE Ls Rs, the call k_kwmc51 served): the
-// history itself stays [S][47][5].  ends == NULL: the dense call.
-__global__ void k_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                                float* hist_out, uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                                const uint32_t* ends)
-{
-	constexpr uint32_t C = 5, FC = 6;
-	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-	if (g >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = g / MTR_FIR_HALO, i = g % MTR_FIR_HALO;
-	const bool touched = !ends || ends[s] != 0;
-	const int64_t f = touched ? (int64_t) n_frames - MTR_FIR_HALO + i : (int64_t) i - MTR_FIR_HALO;
-	for (uint32_t c = 0; c < C; ++c)
-		hist_out[((size_t) s * MTR_FIR_HALO + i) * C + c] = (f >= 0) ? audio[((size_t) s * stride + (size_t) f) * FC + (c < 3 ? c : c + 1)]
-		                                                            : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * C + c];
-	if (!tp_call || !touched || i != 0) return;
-	float last = 0.f, hold = 0.f;
-	for (uint32_t c = 0; c < C; ++c) {
-		const size_t k = (size_t) s * C + c;
-		const float v = __uint_as_float (tp_call[k]);
-		tp_last[k] = v;
-		if (v > tp_hold[k]) tp_hold[k] = v;
-		tp_call[k] = 0;
-		last = fmaxf (last, v);
-		hold = fmaxf (hold, tp_hold[k]);
-	}
-	mtr_stream_state* const st = state + s;
-	st->tp_last[0] = st->tp_last[1] = last;
-	st->tp_hold[0] = st->tp_hold[1] = hold;
-	st->tp_call[0] = st->tp_call[1] = 0;
-}
-
-int mtr_launch_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
-                             uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                             const uint32_t* ends, void* stream)
-{
-	const dim3 grid ((n_streams * MTR_FIR_HALO + 255) / 256);
-	hipLaunchKernelGGL (k_history_mc51, grid, dim3 (256), 0, (hipStream_t) stream,
-	                    audio, stride, n_frames, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state, ends);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-int mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
-                           uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                           const uint32_t* ends, void* stream)
-{
-	const dim3 grid ((n_streams * MTR_FIR_HALO + 255) / 256);
-	if (ends) hipLaunchKernelGGL (k_history_mc_len, grid, dim3 (256), 0, (hipStream_t) stream,
-	                              audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state, ends);
-	else      hipLaunchKernelGGL (k_history_mc, grid, dim3 (256), 0, (hipStream_t) stream,
-	                              audio, stride, n_frames, C, hist_in, hist_out, n_streams, tp_call, tp_last, tp_hold, state);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }

@@ -211,21 +211,34 @@ int  mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* st
 size_t mtr_seg_lds_bytes (void);
 int  mtr_fused2_upload_taps (const float* g144);
 /* A trailing `ends` / `frag_lim` (per stream, device memory) selects the instantiation of a call with per-stream lengths; NULL the
- * dense one.  With lengths a stream with ends [s] == 0 keeps its history and is not folded. */
-int  mtr_launch_history (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
-                         uint32_t n_streams, mtr_stream_state* fold_state /* NULL: k_gate folds the peaks */, const uint32_t* ends, void* stream);
+ * dense one. */
 int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
-/* [S][47][C] history of the multichannel engines; tp_call != NULL: also TruePeakdsp::read () per channel (tp_call -> tp_last,
- * tp_hold, all [S][C]) and the max over the channels into the stream state's tp_last[0..1] / tp_hold[0..1] */
-int  mtr_launch_history_mc (const float* audio, uint64_t stride, uint64_t n_frames, uint32_t C, const float* hist_in, float* hist_out,
-                            uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                            const uint32_t* ends, void* stream);
-/* ... and the two for a 5-channel engine whose call's buffer holds WAVE 5.1 frames (a.audio / audio: [S][stride][6], L R C LFE Ls Rs;
- * mtr_engine_set_frame_layout with 6, {0, 1, 2, 4, 5} on device f32): the kernels read the wide frames themselves */
+/* ... and for a 5-channel engine whose call's buffer holds WAVE 5.1 frames (a.audio: [S][stride][6], L R C LFE Ls Rs;
+ * mtr_engine_set_frame_layout with 6, {0, 1, 2, 4, 5} on device f32): the kernel reads the wide frames itself */
 int  mtr_launch_kwmc51 (bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
-int  mtr_launch_history_mc51 (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in, float* hist_out,
-                              uint32_t n_streams, uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* state,
-                              const uint32_t* ends, void* stream);
+/* The 47-frame interpolator history for the next call, the last step of a call (mtr_history.hip).  Which 47 frames a stream leaves: */
+enum HistCut {
+	HIST_CALL_END,             /* the frames in front of the call's end, every stream touched: the dense call */
+	HIST_CALL_END_IF_TOUCHED,  /* ... of a stream with ends [s] != 0, one that closes included (it keeps what follows its end); ends [s] == 0: its row stays */
+	HIST_OWN_END               /* the frames in front of the stream's OWN end, ends [s]; ends [s] == 0: its row stays */
+};
+struct mtr_history_args {
+	const float*    audio;        /* [S][stride][FC] */
+	uint64_t        stride, n_frames;
+	const float*    hist_in;      /* [S][47][HC]: what the call read */
+	float*          hist_out;     /* ... and what the next one reads (the buffers ping-pong: a row that stays is copied across) */
+	uint32_t        n_streams;
+	const uint32_t* ends;         /* [S] frames of stream s in this call (<= n_frames; 0: untouched, not folded either), NULL: HIST_CALL_END */
+	uint32_t        C, FC, HC;    /* channels of the engine (1 .. 5), samples per frame of `audio` (C; 6: WAVE 5.1 frames, C == 5), channels per
+	                               * frame of the history (2 for C <= 2 — mono keeps a zero right channel —, else C) */
+	mtr_stream_state* fold_state; /* [S] stereo, deferred gate: mtr_fold_truepeak here (NULL: k_gate folds the peaks) */
+	uint32_t*       tp_call;      /* layout 8, all [S][C]: mtr_fold_truepeak_mc on these and `state` (NULL: no fold of this kind) */
+	float*          tp_last;
+	float*          tp_hold;
+	mtr_stream_state* state;      /* [S] */
+};
+/* -1: an ends rule without ends, C outside 1 .. 5, FC neither C nor 6 with C == 5 */
+int  mtr_launch_history (HistCut cut, const mtr_history_args& a, void* stream);
 /* log != NULL: the instantiations that append the call's points to the loudness log; NULL: the kernels as they are without it */
 int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
@@ -261,15 +274,9 @@ struct mtr_tpb_series_ends_args : mtr_tpb_series_args {
 };
 int  mtr_launch_tpb_ends (const mtr_tpb_ends_args& a, void* stream);
 int  mtr_launch_tpb_series_ends (const mtr_tpb_series_ends_args& a, void* stream);
-/* the 47-frame history of a TPBALLIST engine's call with ends (n_channels 1 or 2): the frames in front of each stream's OWN end; a stream
- * with ends [s] == 0 keeps its row (copied across the ping-pong) and is not folded */
-int  mtr_launch_history_ends (uint32_t n_channels, const float* audio, uint64_t stride, const float* hist_in, float* hist_out,
-                              uint32_t n_streams, mtr_stream_state* fold_state /* stereo; NULL: k_gate folds the peaks */, const uint32_t* ends, void* stream);
 /* ends != NULL: the LEN instantiation, stream s of the view ends at call frame ends[s] (0: untouched) */
 int  mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
                           uint32_t n_streams, const uint32_t* ends, void* stream);
-int  mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                              float* hist_out, uint32_t n_streams, void* stream);
 int  mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint32_t n_streams, int32_t* d_hist, float* d_max, void* stream);
 /* rows of packed integer PCM (format MTR_PCM_*, n_samples per row, pitch in bytes) to rows of f32 (pitch in floats): mtr_pcm.hip */
 int  mtr_launch_pcm (int format, const void* src, uint64_t src_pitch, float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_samples, void* stream);
@@ -291,6 +298,24 @@ __device__ __forceinline__ void mtr_fold_truepeak (mtr_stream_state* st)
 	if (cl > st->tp_hold[0]) st->tp_hold[0] = cl;
 	if (cr > st->tp_hold[1]) st->tp_hold[1] = cr;
 	st->tp_call[0] = 0; st->tp_call[1] = 0;
+}
+/* ... and per channel for stream s of a multichannel engine (layout 8; tp_call, tp_last, tp_hold: [S][C]); the programme's true peak, the
+ * max over the channels, goes to the stream state's two slots — what mtr_engine_results, k_aggregate and the reduction read */
+__device__ __forceinline__ void mtr_fold_truepeak_mc (uint32_t* tp_call, float* tp_last, float* tp_hold, mtr_stream_state* st, uint32_t s, uint32_t C)
+{
+	float last = 0.f, hold = 0.f;
+	for (uint32_t c = 0; c < C; ++c) {
+		const size_t k = (size_t) s * C + c;
+		const float v = __uint_as_float (tp_call[k]);
+		tp_last[k] = v;
+		if (v > tp_hold[k]) tp_hold[k] = v;
+		tp_call[k] = 0;
+		last = fmaxf (last, v);
+		hold = fmaxf (hold, tp_hold[k]);
+	}
+	st->tp_last[0] = st->tp_last[1] = last;
+	st->tp_hold[0] = st->tp_hold[1] = hold;
+	st->tp_call[0] = st->tp_call[1] = 0;
 }
 #endif
 

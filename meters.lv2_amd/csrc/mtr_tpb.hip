@@ -1025,135 +1025,40 @@ __global__ __launch_bounds__ (NTHREADS) void k_tpb (const tpb_args_t<SERIES, END
 	}
 }
 
-// the 47-frame history for mono input is stored as [f][2] with the right channel zero
-__global__ void k_history_mono (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                                float* hist_out, uint32_t n_streams)
+// One launcher body for the four forms of k_tpb.  What the kernel relies on is refused here: a call too long for its 32-bit counts; SERIES: a
+// period outside 16 .. 8192, an open block that is not shorter than the period, series without their memory; ENDS: no ends (they are 32
+// bits, which the 31 of the call's length cover)
+template <bool SERIES, bool ENDS>
+int launch_tpb (const tpb_args_t<SERIES, ENDS>& a, void* stream)
 {
-	const uint32_t gidx = blockIdx.x * blockDim.x + threadIdx.x;
-	if (gidx >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = gidx / MTR_FIR_HALO, i = gidx % MTR_FIR_HALO;
-	const int64_t f = (int64_t) n_frames - MTR_FIR_HALO + i;
-	const float v = (f >= 0) ? audio[(size_t) s * stride + f] : hist_in[((size_t) s * MTR_FIR_HALO + MTR_FIR_HALO + f) * 2];
-	hist_out[((size_t) s * MTR_FIR_HALO + i) * 2] = v;
-	hist_out[((size_t) s * MTR_FIR_HALO + i) * 2 + 1] = 0.f;
-}
-
-// ... of a call with ends (the LEN form of k_history_mono, and of k_history for the engines of this meter): a stream that ends inside the
-// call leaves the 47 frames in front of its OWN end — what lies behind it has no influence on anything — and a stream with end 0 keeps its
-// row, copied across (the buffers ping-pong: its part of the state blob must not flip with every later call), and is not folded
-template <int C>
-__global__ void k_history_ends (const float* audio, uint64_t stride, const float* hist_in, float* hist_out, uint32_t n_streams,
-                                mtr_stream_state* fold_state, const uint32_t* ends)
-{
-	const uint32_t gidx = blockIdx.x * blockDim.x + threadIdx.x;
-	if (gidx >= n_streams * MTR_FIR_HALO) return;
-	const uint32_t s = gidx / MTR_FIR_HALO, i = gidx % MTR_FIR_HALO;
-	const int64_t f = (int64_t) ends[s] - MTR_FIR_HALO + i;              // (end 0: every f < 0, the old row)
-	const size_t h = ((size_t) s * MTR_FIR_HALO + i) * 2;
-#pragma unroll
-	for (int c = 0; c < 2; ++c) {
-		float v = 0.f;                                                      // (mono: the right channel stays zero)
-		if (c < C) v = f >= 0 ? audio[((size_t) s * stride + (size_t) f) * C + c] : hist_in[((size_t) s * MTR_FIR_HALO + (size_t) (MTR_FIR_HALO + f)) * 2 + c];
-		hist_out[h + c] = v;
+	if (a.n_frames >= 0x7ffff000ull) return -1;                        // (the kernel counts frames and chunks in 32 bits, a few chunks ahead)
+	if constexpr (SERIES) {
+		if (a.period < (uint32_t) F || a.period > 8192u || a.fill >= a.period || a.e0 != a.period - a.fill || !a.open) return -1;
+		if (a.room && (!a.s_level || !a.s_peak || a.point0 >= a.capacity || a.room > a.capacity - a.point0)) return -1;
 	}
-	if (C == 2 && fold_state && ends[s] != 0 && i == 0) mtr_fold_truepeak (fold_state + s);
+	if constexpr (ENDS) if (!a.ends) return -1;
+	constexpr int lds = ENDS ? LDS_BYTES_ENDS : SERIES ? LDS_BYTES_SERIES : LDS_BYTES;
+	static bool raised = false;                                        // (one per instantiation)
+	if (!raised) {
+		(void) hipFuncSetAttribute ((const void*) k_tpb<1, SERIES, ENDS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+		(void) hipFuncSetAttribute ((const void*) k_tpb<2, SERIES, ENDS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+		raised = true;
+	}
+	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
+	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
+	hipStream_t st = (hipStream_t) stream;
+	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, SERIES, ENDS>), grid, dim3 (NTHREADS), lds, st, a);
+	else                   hipLaunchKernelGGL ((k_tpb<1, SERIES, ENDS>), grid, dim3 (NTHREADS), lds, st, a);
+	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 }  // namespace
 
-int mtr_launch_tpb (const mtr_tpb_args& a, void* stream)
-{
-	if (a.n_frames >= 0x7ffff000ull) return -1;                        // (the kernel counts frames and chunks in 32 bits, a few chunks ahead)
-	static bool raised = false;
-	if (!raised) {
-		(void) hipFuncSetAttribute ((const void*) k_tpb<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-		(void) hipFuncSetAttribute ((const void*) k_tpb<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-		raised = true;
-	}
-	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
-	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
-	hipStream_t st = (hipStream_t) stream;
-	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, false>), grid, dim3 (NTHREADS), LDS_BYTES, st, a);
-	else                   hipLaunchKernelGGL ((k_tpb<1, false>), grid, dim3 (NTHREADS), LDS_BYTES, st, a);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-// P > 0: the SERIES instantiations.  What the kernel relies on is refused here: a period outside 16 .. 8192, an open block that is not
-// shorter than the period, series without their memory
-int mtr_launch_tpb_series (const mtr_tpb_series_args& a, void* stream)
-{
-	if (a.n_frames >= 0x7ffff000ull) return -1;
-	if (a.period < (uint32_t) F || a.period > 8192u || a.fill >= a.period || a.e0 != a.period - a.fill || !a.open) return -1;
-	if (a.room && (!a.s_level || !a.s_peak || a.point0 >= a.capacity || a.room > a.capacity - a.point0)) return -1;
-	static bool raised = false;
-	if (!raised) {
-		(void) hipFuncSetAttribute ((const void*) k_tpb<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_SERIES);
-		(void) hipFuncSetAttribute ((const void*) k_tpb<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_SERIES);
-		raised = true;
-	}
-	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
-	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
-	hipStream_t st = (hipStream_t) stream;
-	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, true>), grid, dim3 (NTHREADS), LDS_BYTES_SERIES, st, a);
-	else                   hipLaunchKernelGGL ((k_tpb<1, true>), grid, dim3 (NTHREADS), LDS_BYTES_SERIES, st, a);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-// The ENDS instantiations: the same checks; the ends are 32 bits, which the 31 of the call's length cover
-int mtr_launch_tpb_ends (const mtr_tpb_ends_args& a, void* stream)
-{
-	if (a.n_frames >= 0x7ffff000ull || !a.ends) return -1;
-	static bool raised = false;
-	if (!raised) {
-		(void) hipFuncSetAttribute ((const void*) k_tpb<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
-		(void) hipFuncSetAttribute ((const void*) k_tpb<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
-		raised = true;
-	}
-	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
-	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
-	hipStream_t st = (hipStream_t) stream;
-	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, false, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
-	else                   hipLaunchKernelGGL ((k_tpb<1, false, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-int mtr_launch_tpb_series_ends (const mtr_tpb_series_ends_args& a, void* stream)
-{
-	if (a.n_frames >= 0x7ffff000ull || !a.ends) return -1;
-	if (a.period < (uint32_t) F || a.period > 8192u || a.fill >= a.period || a.e0 != a.period - a.fill || !a.open) return -1;
-	if (a.room && (!a.s_level || !a.s_peak || a.point0 >= a.capacity || a.room > a.capacity - a.point0)) return -1;
-	static bool raised = false;
-	if (!raised) {
-		(void) hipFuncSetAttribute ((const void*) k_tpb<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
-		(void) hipFuncSetAttribute ((const void*) k_tpb<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ENDS);
-		raised = true;
-	}
-	const uint32_t nstr = NCOL / (a.n_channels == 2 ? 2 : 1);
-	const dim3 grid ((a.n_streams + nstr - 1) / nstr);
-	hipStream_t st = (hipStream_t) stream;
-	if (a.n_channels == 2) hipLaunchKernelGGL ((k_tpb<2, true, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
-	else                   hipLaunchKernelGGL ((k_tpb<1, true, true>), grid, dim3 (NTHREADS), LDS_BYTES_ENDS, st, a);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-int mtr_launch_history_ends (uint32_t n_channels, const float* audio, uint64_t stride, const float* hist_in, float* hist_out,
-                             uint32_t n_streams, mtr_stream_state* fold_state, const uint32_t* ends, void* stream)
-{
-	if (!ends || (n_channels != 1 && n_channels != 2)) return -1;
-	const uint32_t n = n_streams * MTR_FIR_HALO;
-	if (n_channels == 2) hipLaunchKernelGGL (k_history_ends<2>, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream, audio, stride, hist_in, hist_out, n_streams, fold_state, ends);
-	else                 hipLaunchKernelGGL (k_history_ends<1>, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream, audio, stride, hist_in, hist_out, n_streams, fold_state, ends);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-int mtr_launch_history_mono (const float* audio, uint64_t stride, uint64_t n_frames, const float* hist_in,
-                             float* hist_out, uint32_t n_streams, void* stream)
-{
-	const uint32_t n = n_streams * MTR_FIR_HALO;
-	hipLaunchKernelGGL (k_history_mono, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream,
-	                    audio, stride, n_frames, hist_in, hist_out, n_streams);
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
+// dense; P > 0: the SERIES instantiations; the ENDS ones of either
+int mtr_launch_tpb (const mtr_tpb_args& a, void* stream) { return launch_tpb<false, false> (a, stream); }
+int mtr_launch_tpb_series (const mtr_tpb_series_args& a, void* stream) { return launch_tpb<true, false> (a, stream); }
+int mtr_launch_tpb_ends (const mtr_tpb_ends_args& a, void* stream) { return launch_tpb<false, true> (a, stream); }
+int mtr_launch_tpb_series_ends (const mtr_tpb_series_ends_args& a, void* stream) { return launch_tpb<true, true> (a, stream); }
 
 // ---- TPBALLIST in the engine: the call's step, the blob's section, reset, the entry points of mtr_tpb.h --------------------------------
 // (tools/tpb_prof.hip builds the kernels alone)

@@ -205,8 +205,8 @@ def test_garbage_past_the_end_changes_nothing(M, name, fs):
         sa, sb = _snap(M, a), _snap(M, b)
         if meters & M.METER_TRUEPEAK:
             # (the blob of a stream that CLOSES holds, by the _lengths contract, the 47 frames of the buffer in front of the call's end as
-            # its interpolator history — k_history_len: "a stream that closes keeps whatever follows its end: nothing reads it again" —
-            # so beside EBU / TRUEPEAK the blobs of the open streams are compared, and every getter of every stream)
+            # its interpolator history — k_history under HIST_CALL_END_IF_TOUCHED: "a stream that closes keeps whatever follows its end in
+            # the buffer: nothing reads it again" — so beside EBU / TRUEPEAK the blobs of the open streams are compared, and every getter of every stream)
             opened = [s for s, L in enumerate(Ls) if L == T]
             sa["blob"], sb["blob"] = sa["blob"][opened], sb["blob"][opened]
         _same(sa, sb, "garbage behind the ends")
