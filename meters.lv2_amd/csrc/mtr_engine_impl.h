@@ -13,6 +13,7 @@
 #include "mtr_internal.h"
 #include "mtr_host.h"
 #include "mtr_series.h"
+#include "mtr_km_consts.h"
 
 #pragma GCC visibility push(hidden)   // (cross-TU helpers, not ABI)
 
@@ -265,13 +266,12 @@ struct mtr_engine {
 		DevBuf<mtr_kmeter_state>   state;       // [S][2]
 		DevBuf<double>             piece;
 		DevBuf<float>              max;
-		double                     pw1[3];
+		mtr_km_consts              k;           // Kmeterdsp's constants (mtr_km_consts.h), the lane step that of k_kmeter_blocks
 		// the reading series (mtr_engine_kmeter_set_period, P > 0): k_kmeter_blocks
 		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
 		DevBuf<unsigned char>      open;        // [S] mtr_kmeter_open: the blob's header and the open block's carry per channel
 		DevBuf<double>             bpiece;      // [S][pieces][C][MTR_KMB_PIECE]
 		DevBuf<float>              s_rms, s_peak;   // [S][cap][C]
-		double                     k[11];       // mtr_kmb_consts: the pieces kernel's constants
 		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (ragged calls: mtr_ragged.h)
 	} km;
 	struct Stcorr {                             // STCORR (mtr_stcorr.hip)
@@ -301,8 +301,7 @@ struct mtr_engine {
 		SeriesCfg                  ser;         // frames per sur_run of the series (0: the call), points per stream it holds
 		uint8_t                    pa[4] = { 0, 0, 0, 0 }, pb[4] = { 0, 0, 0, 0 };   // the pairs' channels: a control (it survives a reset)
 		float                      w[2];        // w1, w2 of Stcorrdsp::init
-		double                     pw[3];       // Kmeterdsp's A per group of four frames
-		double                     k[18];       // mtr_sur_consts: the pieces kernel's constants
+		mtr_sur_consts             k;           // Kmeterdsp's constants and the pieces kernel's own (mtr_km_consts.h)
 		uint32_t                   warm = 0, chunk = 0;   // the pieces' geometry
 		std::vector<uint64_t>      points;      // [S] points of each stream's own series since reset (mtr_engine_process_*_any: mtr_any.h)
 	} su;

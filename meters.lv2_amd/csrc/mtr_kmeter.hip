@@ -22,7 +22,7 @@
 // LEN (both kernels): the call carries per-stream ends (a.ends, call-relative: mtr_engine_process_*_tracks, or any call once a stream of
 // its view is closed).  Stream s ends at frame E = ends [s], workgroup-uniform (one scalar load): a stream that ends inside the call sees
 // ONE process (p, E) — E / 4 groups, the weights A^k counted back from ITS last group, fpp = E with the fall-back factor the host
-// computed for that fpp (a.falls [s], the expression of kmeter_fall) — and a stream with E = n_frames exactly what the dense call gives it
+// computed for that fpp (a.falls [s], km_fall) — and a stream with E = n_frames exactly what the dense call gives it
 // (the cursor's fall).  A workgroup of k_kmeter_pieces whose chunk lies at or past the stream's groups returns before it touches memory
 // and writes NO piece slot: k_kmeter_final adds the stream's own chunks only — it never reads those slots.  E = 0 (a closed stream,
 // frames [s] == 0): nothing is written, not even the + 1e-20f.  Groups start on multiples of four frames whatever E is: the 16-byte
@@ -34,14 +34,11 @@
 // (mtr_stcorr_scan.h: the open block's rest, whole blocks, what the call leaves open, each cut at `chunk` = 32768 frames), one workgroup
 // per (stream, piece), lane t on the four frames b0 + 4 t, + 4 (t + 256), ... of its piece: 16-byte loads where the piece's first frame
 // lies on 16 bytes of the buffer, 8- or 4-byte ones where an odd P or a block that starts mid-row leaves it elsewhere, and nothing outside
-// the piece's frames.  The weights are the pointwise ones of mtr_surround.hip on s = x^2: a frame at offset j of its
-// block gives w r^(E - 1 - j) s to z1 at the piece's end E and w r^(ge - 1 - j) (c_k + 4 w b^k) s to z2 — ge its group's end, k the group
-// ends behind it inside the piece; the groups of four restart at each block's start, so a piece may start and end inside one.  Frames at
+// the piece's frames.  The weights are the pointwise ones on s = x^2, and the geometry, the lane's powers, the rule for a square that is
+// not finite and the walk's arithmetic are mtr_kmeter_dsp.h's, which derives them (SURROUND's walk takes them from there too).  Frames at
 // j >= L - L mod 4 (L = P, or what a ragged call leaves a closing stream of its last block) weigh nothing and do not enter the maximum
-// (:79).  The powers come from exp () of logarithms the host computed, once per lane, and move by constants from there.  A square that is
-// not finite makes the reference's z1 NaN at the next frame (Inf - Inf) unless it is the block's last counted frame: a NaN is added for
-// it.  One thread per (stream, channel) walks the pieces in order, carries (z1, z2) in closed form (mat_pow) — also through a call that
-// ends inside a group — and at every block's end does :101-139 in f32, one rounding per operation, and appends (rms, peak).
+// (:79).  One thread per (stream, channel) walks the pieces in order, carries (z1, z2) in closed form (km_carry) — also through a call
+// that ends inside a group — and at every block's end does :101-139 in f32, one rounding per operation, and appends (rms, peak).
 // Between two calls the open block's (z1, z2) stay doubles and its maximum an f32, with what they were IN FRONT OF the group of four that
 // the call left open (bz1, btmax; z2 moves at group ends only): a ragged call that closes the stream before that group completes drops
 // the whole group from filter and peak, as the n / 4 groups of the truncated block demand.
@@ -54,6 +51,7 @@
 #include <vector>
 
 #include "mtr_engine_impl.h"
+#include "mtr_kmeter_dsp.h"
 #include "mtr_stcorr_scan.h"
 
 /* Kmeterdsp per (stream, channel) state (jmeters/kmeterdsp.h) */
@@ -95,24 +93,14 @@ typedef struct mtr_kmeter_open {
 #define MTR_KMB_PIECE 5            /* doubles per (stream, piece, channel): what the piece's frames give to z1 and z2 at its end, max x^2; what
                                     * those in front of its last group end give to z1 THERE, and their max x^2 */
 
-/* the constants of k_kmeter_blocks, computed once on the host in double (kr = 1 - omega, ka = kr^4, kb = 1 - 4 omega) */
-typedef struct mtr_kmb_consts {
-	double lkr, lkb;              /* log kr, log kb */
-	double kri, kai, kbi, kr3;    /* 1 / kr, 1 / ka, 1 / kb, kr^3 */
-	double ca, cb;                /* omega c / (ka - kb), omega (4 omega - c / (ka - kb)): the z2 weight of a frame is kr^(..) (ca ka^k + cb kb^k) */
-	double st1, sta, stb;         /* kr^-(4 NT), ka^-NT, kb^-NT: from one of a lane's groups of four frames to its next */
-} mtr_kmb_consts;
-
 typedef struct mtr_kmb_args {
 	const float*    audio;        /* [S][stride][C] */
 	uint64_t        stride, n_frames;
 	uint64_t        period;       /* P > 0 */
 	uint64_t        e0;           /* call frame at which the block open on entry ends */
 	uint32_t        n_streams, n_channels, n_pieces, chunk;
-	float           omega, fall;  /* 9.72f / fs, the fall-back factor of fpp = P */
-	int32_t         hold;
-	double          pw[3];        /* A = [[a, 0], [c, b]] per group of four frames */
-	mtr_kmb_consts  k;
+	float           fall;         /* the fall-back factor of fpp = P */
+	mtr_km_consts   k;            /* (st1 / sta / stb: a lane's next group of four frames is 4 NT frames on) */
 	uint32_t        capacity;     /* points per stream the series hold */
 	uint64_t        point0;       /* blocks completed before this call */
 	mtr_kmeter_state* state;      /* [S][2]: rms, peak of the last completed block, cnt (z1, z2: the carry's, as f32) */
@@ -129,13 +117,7 @@ namespace {
 constexpr int NT = 256;                  // threads per workgroup
 constexpr int CH = 32 * NT;              // groups (of four samples) per workgroup: 32768 frames
 
-struct Mat { double a, c, b; };          // [[a, 0], [c, b]]
-__host__ __device__ inline Mat mat_pow (double a1, double c1, double b1, double k)
-{
-	// A^k for A = [[a1, 0], [c1, b1]]: c_k = c1 (a1^k - b1^k) / (a1 - b1)
-	const double ak = pow (a1, k), bk = pow (b1, k);
-	return Mat{ak, c1 * (ak - bk) / (a1 - b1), bk};
-}
+using namespace mtr_km;                  // Mat / mat_pow, and the reading series' geometry, weights and walk (mtr_kmeter_dsp.h)
 
 template <int C, bool LEN>
 __global__ __launch_bounds__ (NT) void k_kmeter_pieces (const mtr_kmeter_args a)
@@ -242,37 +224,22 @@ __global__ void k_kmeter_final (const mtr_kmeter_args a)
 		t = fmaxf (t, a.piece_max[((size_t) s * a.n_pieces + p) * 2 + c]);
 	}
 	const Mat g = mat_pow (a.pw1[0], a.pw1[1], a.pw1[2], (double) n_groups);
-	float z1 = (float) (g.a * (double) zi1 + e1);
-	float z2 = (float) (g.c * (double) zi1 + g.b * (double) zi2 + e2);
-	if (n_groups == 0) { z1 = zi1; z2 = zi2; }
-	if (isnan (z1)) z1 = 0;                                            // :100-102
-	if (isnan (z2)) z2 = 0;
-	if (!isfinite (t)) t = 0;
-	st->z1 = z1 + 1e-20f;
-	st->z2 = z2 + 1e-20f;
-	const float r = sqrtf (2.0f * z2);
-	t = sqrtf (t);
-	if (st->flag) { st->rms = r; st->flag = 0; }                       // :112-118
-	else if (r > st->rms) st->rms = r;
-	if (t >= st->peak) { st->peak = t; st->cnt = a.hold; }             // :121-138
-	else if (st->cnt > 0) st->cnt -= (int32_t) fpp;
-	else { st->peak *= fall; st->peak += 1e-10f; }
+	double z1 = g.a * (double) zi1 + e1;
+	double z2 = g.c * (double) zi1 + g.b * (double) zi2 + e2;
+	if (n_groups == 0) { z1 = (double) zi1; z2 = (double) zi2; }
+	const KmClose r = km_close (z1, z2, t);                            // :100-109 (z1, z2: f32 values from here)
+	st->z1 = (float) z1;
+	st->z2 = (float) z2;
+	if (st->flag) { st->rms = r.rms; st->flag = 0; }                   // :112-118
+	else if (r.rms > st->rms) st->rms = r.rms;
+	km_peak_hold (r.t, st->peak, st->cnt, a.hold, fpp, fall);          // :121-138
 }
 
 // ---- the reading series (P > 0) ----------------------------------------------------------------------------------------------------
 
 constexpr uint32_t KMB_CHUNK = 32768;    // frames per piece at most: a multiple of four
 
-using mtr_sc::Piece;
 using mtr_sc::piece_of;
-using mtr_sc::ipow;
-
-// the call frame at which the block of piece `pc` starts (negative: it started in an earlier call)
-__device__ __forceinline__ int64_t kmb_block_start (const mtr_kmb_args& a, const Piece& pc)
-{
-	if ((uint64_t) pc.b0 < a.e0) return (int64_t) a.e0 - (int64_t) a.period;
-	return (int64_t) (a.e0 + ((uint64_t) pc.b0 - a.e0) / a.period * a.period);
-}
 
 // LEN: the stream ends at call frame a.ends[s] (0: closed, untouched; n_frames: the dense call's stream).  A piece that starts at or
 // behind the end returns before it loads anything; the block an end inside the call cuts has L = the frames the stream has of it.
@@ -282,20 +249,15 @@ __global__ __launch_bounds__ (NT) void k_kmeter_blocks (const mtr_kmb_args a)
 	const uint32_t s = blockIdx.y;
 	const Piece pc = piece_of (a, blockIdx.x);
 	const int64_t b0 = pc.b0;
-	int64_t b1 = pc.b1;
-	const int64_t blk0 = kmb_block_start (a, pc);
-	int64_t L = (int64_t) a.period;
+	const int64_t blk0 = km_block_start (a.e0, a.period, a.period, b0);
+	int64_t end = 0;
 	if constexpr (LEN) {
-		const int64_t end = (int64_t) a.ends[s];
+		end = (int64_t) a.ends[s];
 		if (b0 >= end) return;                                     // (uniform in the workgroup; end 0: every piece of the stream)
-		if (end < (int64_t) a.n_frames && end < blk0 + L) L = end - blk0;   // one last process (p, L)
-		if (end < b1) b1 = end;
 	}
+	const KmGeom g = km_geom<LEN> (pc, blk0, a.period, end, a.n_frames);
+	const int64_t b1 = g.b1, Lg = g.Lg, E1 = g.E1, pe = g.pe;
 	const float* const src = a.audio + (size_t) s * a.stride * C;
-	const int64_t Lg = L & ~(int64_t) 3;                           // frames of the block that count (kmeterdsp.cc:79)
-	// block offset at which the piece's z1 stands: its end, but never inside the block's dropped trailing frames
-	const int64_t E1 = b1 - blk0 < Lg ? b1 - blk0 : Lg;
-	const int64_t pe = E1 & ~(int64_t) 3;                           // ... and its last group end
 	const double up = ipow (a.k.kri, (uint64_t) (E1 - pe));         // from a weight at E1 to the weight at pe
 	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
 	// how wide the piece's loads may be: the address of its first frame (every lane's first frame lies 4 frames x a multiple behind it)
@@ -304,15 +266,11 @@ __global__ __launch_bounds__ (NT) void k_kmeter_blocks (const mtr_kmb_args a)
 	const bool w16 = (a0 & 15) == 0;
 	const bool w8 = (a0 & 7) == 0;
 
-	// the powers of the lane's first frame — its distance to E1 for z1, inside its group and in group ends behind it for z2 — from exp ();
-	// from one of its groups of four frames to the next (4 NT frames = NT groups) they move by constants
+	// the powers of the lane's first frame from exp (); from one of its groups of four frames to the next (4 NT frames = NT groups) they
+	// move by constants
 	int64_t f0 = b0 + 4 * (int64_t) tid;
-	const int64_t jt0 = f0 - blk0;
-	const int64_t gt0 = (jt0 | 3) + 1;                             // its group's end
-	int64_t kt = (pe - gt0) >> 2;                                  // group ends behind that one inside the piece; < 0: none
-	double pt1 = (double) a.omega * exp ((double) (E1 - 1 - jt0) * a.k.lkr);
-	double pta = a.k.ca * exp ((double) (4 * kt) * a.k.lkr), ptb = a.k.cb * exp ((double) kt * a.k.lkb);
-	const double pg0 = ipow (1.0 - (double) a.omega, (uint64_t) (gt0 - 1 - jt0));
+	KmLane lt;
+	lt.init (a.k, E1, pe, f0 - blk0);
 	double e1[C], e2[C], eb[C];
 	float tm[C], tb[C];
 #pragma unroll
@@ -340,31 +298,28 @@ __global__ __launch_bounds__ (NT) void k_kmeter_blocks (const mtr_kmb_args a)
 				for (int c = 0; c < C; ++c) v[k * C + c] = f0 + k < b1 ? p[k * C + c] : 0.f;
 		}
 		const int64_t j0 = f0 - blk0;
-		int64_t kk = kt;
-		double p1 = pt1, pa = pta, pb = ptb, pg = pg0;               // omega kr^(E1 - 1 - j), ca ka^k, cb kb^k, kr^(ge - 1 - j)
+		KmLane ln = lt;
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
 			const int64_t jk = j0 + k;
 			if (f0 + k < b1 && jk < Lg) {                           // (jk < E1 with it: E1 = min (Lg, b1 - blk0))
-				const bool grp = kk >= 0, front = jk < pe;          // its group ends inside the piece; it lies in front of the last group end
-				const double wz1 = p1, wz2 = pg * (pa + pb), wzb = p1 * up;
+				const bool grp = ln.kt >= 0, front = jk < pe;       // its group ends inside the piece; it lies in front of the last group end
+				const double wz1 = ln.z1_weight (), wz2 = ln.z2_weight (), wzb = ln.front_weight (up);
 #pragma unroll
 				for (int c = 0; c < C; ++c) {
 					const float x = v[k * C + c];
-					float sq = x * x;
-					tm[c] = tm[c] < sq ? sq : tm[c];                 // kmeterdsp.cc:84: if (t < s) t = s (a NaN never enters)
-					if (front) tb[c] = tb[c] < sq ? sq : tb[c];
-					if (!isfinite (sq) && !(jk == Lg - 1 && sq == INFINITY)) sq = NAN;   // (see the head of the file)
+					const float s2 = x * x;
+					tm[c] = tm[c] < s2 ? s2 : tm[c];                 // kmeterdsp.cc:84: if (t < s) t = s (a NaN never enters)
+					if (front) tb[c] = tb[c] < s2 ? s2 : tb[c];
+					const float sq = km_square (s2, jk, Lg);
 					e1[c] = fma (wz1, (double) sq, e1[c]);
 					if (grp) e2[c] = fma (wz2, (double) sq, e2[c]);   // (no 0 x NaN: a later ragged close may drop the open group whole)
 					if (front) eb[c] = fma (wzb, (double) sq, eb[c]);
 				}
 			}
-			p1 *= a.k.kri;
-			if (((jk + 1) & 3) == 0) { kk -= 1; pa *= a.k.kai; pb *= a.k.kbi; pg = a.k.kr3; }
-			else pg *= a.k.kri;
+			ln.next_frame (a.k, jk);
 		}
-		pt1 *= a.k.st1; pta *= a.k.sta; ptb *= a.k.stb; kt -= NT;
+		lt.next_step (a.k, NT);
 	}
 
 	__shared__ double shd[NT / 64][C][3];
@@ -408,29 +363,21 @@ __global__ void k_kmeter_walk (const mtr_kmb_args a)
 	}
 	mtr_kmeter_state* const st = a.state + (size_t) s * 2 + c;
 	mtr_kmeter_carry* const cy = &a.open[s].ch[c];
-	const double kr = 1.0 - (double) a.omega;
+	const double kr = 1.0 - (double) a.k.omega;
 	double z1 = cy->z1, z2 = cy->z2, bz1 = cy->bz1;
 	float tmax = cy->tmax, btmax = cy->btmax;
 	float rms = st->rms, peak = st->peak;
 	int32_t cnt = st->cnt;
 	uint64_t point = a.point0;
 	for (uint32_t pi = 0; pi < a.n_pieces; ++pi) {
-		Piece pc = piece_of (a, pi);
-		const int64_t blk0 = kmb_block_start (a, pc);
-		int64_t L = (int64_t) a.period;
+		const Piece pc = piece_of (a, pi);
 		if constexpr (LEN) {
 			if (pc.b0 >= end) break;
-			if (end < (int64_t) a.n_frames && end < blk0 + L) L = end - blk0;
-			if (end <= pc.b1) {
-				pc.b1 = end;
-				if (L != (int64_t) a.period) pc.closes = true;         // one last process (), of what the stream has of the block
-			}
 		}
-		const int64_t Lg = L & ~(int64_t) 3;
-		const int64_t p0 = pc.b0 - blk0, E1 = pc.b1 - blk0 < Lg ? pc.b1 - blk0 : Lg, pe = E1 & ~(int64_t) 3;   // (as the pieces kernel's)
-		if (p0 == 0) {                                             // :74-75 (a NaN state falls through, as there; it is an f32 here)
-			z1 = z1 > 50 ? 50 : (z1 < 0 ? 0 : z1);
-			z2 = z2 > 50 ? 50 : (z2 < 0 ? 0 : z2);
+		const KmGeom g = km_geom<LEN> (pc, km_block_start (a.e0, a.period, a.period, pc.b0), a.period, end, a.n_frames);
+		const int64_t p0 = g.p0, E1 = g.E1, pe = g.pe;
+		if (p0 == 0) {
+			km_open (z1, z2);
 			tmax = 0.f;
 			bz1 = z1; btmax = 0.f;
 		}
@@ -441,31 +388,18 @@ __global__ void k_kmeter_walk (const mtr_kmb_args a)
 				const float pb = (float) pv[4];
 				btmax = tmax < pb ? pb : tmax;
 			}
-			const int64_t m = (E1 >> 2) - (p0 >> 2);                   // group ends in (p0, E1]
-			if (m > 0) {
-				const Mat g = mat_pow (a.pw[0], a.pw[1], a.pw[2], (double) m);
-				z2 = g.b * z2 + g.c * ipow (a.k.kri, (uint64_t) (p0 & 3)) * z1 + pv[1];
-			}
-			z1 = pow (kr, (double) (E1 - p0)) * z1 + pv[0];
+			km_carry (a.k, p0, E1, pv[0], pv[1], z1, z2);
 			const float pm = (float) pv[2];
 			tmax = tmax < pm ? pm : tmax;
-		} else if (LEN && pc.closes && pc.b0 == 0 && Lg < p0) {
+		} else if (LEN && g.closes && pc.b0 == 0 && g.Lg < p0) {
 			// the stream ends before the group that the call before left open completes: that group's frames drop out, all of them
 			z1 = bz1; tmax = btmax;
 		}
-		if (!pc.closes) continue;
-		float f1 = (float) z1, f2 = (float) z2, t = tmax;
-		if (isnan (f1)) f1 = 0;                                    // :101-103
-		if (isnan (f2)) f2 = 0;
-		if (!isfinite (t)) t = 0;
-		z1 = (double) (f1 + 1e-20f);                               // :106-107
-		z2 = (double) (f2 + 1e-20f);
+		if (!g.closes) continue;
+		const KmClose r = km_close (z1, z2, tmax);
 		bz1 = z1; btmax = 0.f; tmax = 0.f;
-		rms = sqrtf (2.0f * f2);                                   // :109, 112-121 (a read follows every block: the flag is always set)
-		t = sqrtf (t);
-		if (t >= peak) { peak = t; cnt = a.hold; }                 // :124-139
-		else if (cnt > 0) cnt -= (int32_t) L;
-		else { peak *= L == (int64_t) a.period ? a.fall : a.falls[s]; peak += 1e-10f; }
+		rms = r.rms;                                               // :112-121 (a read follows every block: the flag is always set)
+		km_peak_hold (r.t, peak, cnt, a.k.hold, (uint32_t) g.L, g.L == (int64_t) a.period ? a.fall : a.falls[s]);
 		if (point < a.capacity) {
 			const size_t o = ((size_t) s * a.capacity + point) * C + c;
 			a.s_rms[o] = rms; a.s_peak[o] = peak;
@@ -477,13 +411,6 @@ __global__ void k_kmeter_walk (const mtr_kmb_args a)
 }
 
 }  // namespace
-
-static void mtr_kmeter_powers (float omega, double* pw1 /* [3] */)
-{
-	const double w = (double) omega;
-	const double a1 = pow (1.0 - w, 4.0), b1 = 1.0 - 4.0 * w, c1 = 4.0 * w * a1;
-	pw1[0] = a1; pw1[1] = c1; pw1[2] = b1;
-}
 
 static uint32_t mtr_kmeter_pieces (uint64_t n_groups) { return (uint32_t) ((n_groups + CH - 1) / CH); }
 
@@ -507,15 +434,6 @@ static int mtr_launch_kmeter (const mtr_kmeter_args& a, void* stream)
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-static void mtr_kmb_constants (float omega, const double* pw /* [3] */, mtr_kmb_consts* k)
-{
-	const double w = (double) omega, kr = 1.0 - w, ka = pw[0], kb = pw[2], cab = pw[1] / (ka - kb);
-	k->lkr = log (kr); k->lkb = log (kb);
-	k->kri = 1.0 / kr; k->kai = 1.0 / ka; k->kbi = 1.0 / kb; k->kr3 = kr * kr * kr;
-	k->ca = w * cab; k->cb = w * (4.0 * w - cab);
-	k->st1 = pow (kr, (double) (-4 * NT)); k->sta = pow (ka, (double) -NT); k->stb = pow (kb, (double) -NT);
-}
-
 static int mtr_launch_kmb (const mtr_kmb_args& a, void* stream)
 {
 	hipStream_t st = (hipStream_t) stream;
@@ -530,12 +448,6 @@ static int mtr_launch_kmb (const mtr_kmb_args& a, void* stream)
 
 // ---- KMETER in the engine: the call's step, the blob's section, reset, the reading ------------------------------------------------------
 
-// kmeterdsp.cc:60-65: the fall-back factor of a process () of n frames (15 dB/s)
-static float kmeter_fall (const mtr_engine* e, uint64_t n)
-{
-	return powf (10.0f, -0.05f * 15.0f * ((float) n / e->cfg.sample_rate));
-}
-
 // A K-meter's word of a ragged call: the fall-back factor of each stream of the view that ends inside the call.  Its process () is one of
 // f frames (kmeterdsp.cc:60-65 with fpp = f; every other stream takes the cursor's) — with a period P: one of the frames it has of the
 // block it ends in, if it ends inside one; `fill`: the frames into the open block where the call started
@@ -544,7 +456,7 @@ void kmeter_falls (const mtr_engine* e, const Call& c, uint64_t fill, uint64_t P
 	float* const fall = reinterpret_cast<float*> (own);
 	for (uint32_t i = 0; i < c.cnt; ++i) {
 		const uint64_t f = call_frames (e, c, i), kf = P ? (fill + f) % P : f;
-		fall[i] = f && f < c.n_frames && kf ? kmeter_fall (e, kf) : 0.f;
+		fall[i] = f && f < c.n_frames && kf ? km_fall (e->cfg.sample_rate, kf) : 0.f;
 	}
 }
 static uint64_t kmeter_ends_fill (const mtr_engine* e, const Call& c, uint32_t* own) { kmeter_falls (e, c, e->pos.km.fill, e->km.ser.period, own); return 0; }
@@ -564,15 +476,11 @@ static int kmeter_blocks_step (mtr_engine* e, const Call& c, Cursors& nx, const 
 	ka.n_streams = c.cnt; ka.n_channels = C; ka.chunk = KMB_CHUNK;
 	ka.n_pieces = mtr_sc::n_pieces (c.n_frames, ka.e0, P, ka.chunk);
 	if (nx.km_fpp != (uint32_t) P) {                                   // kmeterdsp.cc:65-70
-		nx.km_fall = kmeter_fall (e, P);
+		nx.km_fall = km_fall (e->cfg.sample_rate, P);
 		nx.km_fpp = (uint32_t) P;
 	}
 	ka.fall = nx.km_fall;
-	ka.hold = (int32_t) (0.5f * e->cfg.sample_rate + 0.5f);             // :52
-	ka.omega = 9.72f / e->cfg.sample_rate;
-	memcpy (ka.pw, e->km.pw1, sizeof (ka.pw));
-	static_assert (sizeof (mtr_kmb_consts) == sizeof (e->km.k), "mtr_kmb_consts");
-	memcpy (&ka.k, e->km.k, sizeof (ka.k));
+	ka.k = e->km.k;
 	ka.capacity = cap; ka.point0 = e->pos.km.points;
 	if (e->km.bpiece.reserve ((size_t) e->cfg.n_streams * ka.n_pieces * C * MTR_KMB_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc KMETER pieces");
 	ka.state = e->km.state.p + vo * 2;
@@ -594,13 +502,12 @@ static int kmeter_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamE
 	ka.n_streams = c.cnt; ka.n_channels = e->cfg.n_channels; ka.ends = se.ends; ka.falls = reinterpret_cast<const float*> (se.own);
 	ka.n_pieces = mtr_kmeter_pieces (ka.n_groups);
 	if (nx.km_fpp != (uint32_t) c.n_frames) {                          // kmeterdsp.cc:60-65
-		nx.km_fall = kmeter_fall (e, c.n_frames);
+		nx.km_fall = km_fall (e->cfg.sample_rate, c.n_frames);
 		nx.km_fpp = (uint32_t) c.n_frames;
 	}
 	ka.fpp = nx.km_fpp; ka.fall = nx.km_fall;
-	ka.hold = (int32_t) (0.5f * e->cfg.sample_rate + 0.5f);             // :51
-	ka.omega = 9.72f / e->cfg.sample_rate;
-	memcpy (ka.pw1, e->km.pw1, sizeof (ka.pw1));
+	ka.hold = e->km.k.hold; ka.omega = e->km.k.omega;
+	memcpy (ka.pw1, e->km.k.pw, sizeof (ka.pw1));
 	ka.state = e->km.state.p + vo * 2;
 	if (e->km.piece.reserve ((size_t) e->cfg.n_streams * std::max<uint32_t> (ka.n_pieces, 1) * 4) || e->km.max.reserve ((size_t) e->cfg.n_streams * std::max<uint32_t> (ka.n_pieces, 1) * 2))
 		return fail (MTR_ERR_NOMEM, "hipMalloc KMETER pieces");
@@ -667,12 +574,7 @@ int mtr_engine_kmeter_reset (mtr_engine* e)
 	HIPCHK (hipSetDevice (e->cfg.device));
 	const size_t n = (size_t) e->cfg.n_streams * 2;
 	if (e->km.state.reserve (n)) return fail (MTR_ERR_NOMEM, "hipMalloc KMETER state");
-	mtr_kmeter_powers (9.72f / e->cfg.sample_rate, e->km.pw1);           // kmeterdsp.cc:52
-	{
-		mtr_kmb_consts k;
-		mtr_kmb_constants (9.72f / e->cfg.sample_rate, e->km.pw1, &k);
-		memcpy (e->km.k, &k, sizeof (k));
-	}
+	km_setup (e->cfg.sample_rate, 4 * NT, &e->km.k);                     // (a lane of k_kmeter_blocks: four frames, every 4 NT)
 	HIPCHK (hipStreamSynchronize (e->last_stream));
 	HIPCHK (hipMemset (e->km.state.p, 0, n * sizeof (mtr_kmeter_state)));   // :142-146
 	e->pos.km_fpp = 0;                                                   // (the next process () works its fall-back factor out again)

@@ -12,7 +12,8 @@
 // so a call is cut into PIECES that never span a period boundary (and are at most `chunk` frames, so that one long period
 // still fills the chip); one workgroup reduces one (stream, piece) to the three sums carried to the piece's end, and one
 // thread per stream walks the pieces in order — z = q^len z + sum — and does the flush, the + 1e-10f, the reading and the
-// series append at every period end.  Plain and deterministic: no atomics.
+// series append at every period end (stcorr_walk in mtr_stcorr_scan.h, which SURROUND's pairs take too).  Plain and
+// deterministic: no atomics.
 //
 // The products are not pointwise in the input: zl is a one-pole over the samples.  A workgroup takes its piece tile by tile
 // (4096 frames, staged in LDS by coalesced 16-byte loads); lane t walks the 16 contiguous frames t of the tile twice: once
@@ -52,9 +53,6 @@ typedef struct mtr_stcorr_state {
 	uint32_t period, fill;
 } mtr_stcorr_state;
 
-#define MTR_STCORR_PIECE 9         /* doubles per (stream, piece): the sums of zlr zll zrr carried to the piece's end, zl and zr there; of a piece
-                                    * that starts where a period ended inside the call also sum c rho zl, sum c rho zr (rho = (1 - w1)^(frames
-                                    * since the period end): what the sums owe to the start state) and the zl, zr it started from */
 typedef struct mtr_stcorr_args {
 	const float*    audio;        /* [S][stride][2] */
 	uint64_t        stride, n_frames;
@@ -67,7 +65,7 @@ typedef struct mtr_stcorr_args {
 	uint32_t        capacity;     /* points per stream the series holds */
 	uint64_t        point0;       /* periods completed before this call: the series index of the first one that ends in it */
 	mtr_stcorr_state* state;      /* [S] */
-	double*         piece;        /* [S][n_pieces][MTR_STCORR_PIECE] */
+	double*         piece;        /* [S][n_pieces][MTR_STCORR_PIECE] (mtr_stcorr_scan.h) */
 	float*          series;       /* [S][capacity], NULL if capacity == 0 */
 	const uint32_t* ends;         /* [S] per-stream ends of a ragged call (the LEN instantiations), NULL on a dense one */
 } mtr_stcorr_args;
@@ -249,10 +247,7 @@ __global__ __launch_bounds__ (NT) void k_stcorr_pieces (const mtr_stcorr_args a)
 	}
 }
 
-// one thread per stream: the pieces in order, and stcorrdsp.cc:65-75 + read () at every end of a process ()
-// LEN: the pieces up to the stream's end; the one that holds it is the stream's last, with its own length, and — if the stream ends inside
-// the call — it ends a process () whether a period ends there or not: the truncated block, appended at the stream's own point index.
-// end == 0: the stream is not touched.
+// one thread per stream: stcorr_walk (mtr_stcorr_scan.h) over the stream's pieces.  LEN, end == 0: the stream is not touched.
 template <bool LEN>
 __global__ void k_stcorr_final (const mtr_stcorr_args a)
 {
@@ -264,65 +259,9 @@ __global__ void k_stcorr_final (const mtr_stcorr_args a)
 		if (end == 0) return;
 	}
 	mtr_stcorr_state* const st = a.state + s;
-	const double q1 = 1.0 - (double) a.w2;
-	double z[3] = { (double) st->z[2], (double) st->z[3], (double) st->z[4] };
-	float zl = st->z[0], zr = st->z[1], corr = st->corr;
-	uint64_t point = a.point0;
-	int64_t len_of = -1;
-	double qp = 1.0;
-	bool flushed[2] = { false, false };
-	for (uint32_t i = 0; i < a.n_pieces; ++i) {
-		Piece pc = piece_of (a, i);
-		bool ends_here = false;                                        // (LEN: the stream's last piece)
-		if constexpr (LEN) {
-			if (pc.b0 >= end) break;
-			if (end <= pc.b1) {
-				ends_here = true;
-				if ((uint64_t) end < a.n_frames) pc.closes = true;         // one last process (), of what the stream has of the block
-				pc.b1 = end;
-			}
-		}
-		const int64_t len = pc.b1 - pc.b0;
-		if (len != len_of) { qp = pow (q1, (double) len); len_of = len; }
-		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_STCORR_PIECE;
-		double sum[3] = { pv[0], pv[1], pv[2] }, el = pv[3], er = pv[4];
-		if (pc.after_period && (flushed[0] || flushed[1])) {
-			// the period before left zl (zr) = 0 where the piece started from pv[7] (pv[8]): with rho = r^(frames since), zl' = zl + rho dl
-			const double dl = flushed[0] ? -pv[7] : 0.0, dr = flushed[1] ? -pv[8] : 0.0;
-			const double r = 1.0 - (double) a.w1, r2 = r * r;
-			double cq = 0.0, rr = 1.0;                                 // sum c rho^2 = w2 sum_m q^(len - m) r^(2m), m = 1 .. len
-			for (int64_t m = 1; m <= len && rr > 1e-300; ++m) { rr *= r2; cq += ipow (q1, (uint64_t) (len - m)) * rr; }
-			cq *= (double) a.w2;
-			sum[0] += dr * pv[5] + dl * pv[6] + dl * dr * cq;
-			sum[1] += 2.0 * dl * pv[5] + dl * dl * cq;
-			sum[2] += 2.0 * dr * pv[6] + dr * dr * cq;
-			const double re = ipow (r, (uint64_t) len);
-			el += re * dl; er += re * dr;
-		}
-		if (pc.after_period) flushed[0] = flushed[1] = false;
-		for (int j = 0; j < 3; ++j) z[j] = fma (qp, z[j], sum[j]);
-		const bool last = i + 1 == a.n_pieces || ends_here;
-		if (last) { zl = (float) el; zr = (float) er; }
-		if (!pc.closes) continue;
-		float f[3] = { (float) z[0], (float) z[1], (float) z[2] };
-		flushed[0] = !isfinite (f[1]); flushed[1] = !isfinite (f[2]);  // this period leaves zl (zr) = 0 to the next
-		// (the channel's first stage: not finite anywhere in the process () means not finite at its end, stcorrdsp.cc:65-66)
-		if (last && (!isfinite (zl) || !isfinite (f[1]))) zl = 0.f;
-		if (last && (!isfinite (zr) || !isfinite (f[2]))) zr = 0.f;
-		for (int j = 0; j < 3; ++j) {
-			if (!isfinite (f[j])) f[j] = 0.f;                      // :67-69
-			f[j] = __fadd_rn (f[j], 1e-10f);                       // :73-75
-			z[j] = (double) f[j];
-		}
-		corr = f[0] / sqrtf (__fadd_rn (__fmul_rn (f[1], f[2]), 1e-10f));   // :81
-		if (a.period) {
-			if (point < a.capacity) a.series[(size_t) s * a.capacity + point] = corr;
-			++point;
-		}
-	}
-	st->z[0] = zl; st->z[1] = zr;
-	for (int j = 0; j < 3; ++j) st->z[2 + j] = (float) z[j];
-	st->corr = corr;
+	const StcorrWalk v = { st->z, &st->corr, a.piece + (size_t) s * a.n_pieces * MTR_STCORR_PIECE, MTR_STCORR_PIECE,
+	                       a.capacity ? a.series + (size_t) s * a.capacity : nullptr, 1 };
+	stcorr_walk<LEN> (a, v, end);
 }
 
 }  // namespace

@@ -15,22 +15,20 @@
 // channel-planar in LDS: [C][1792] floats, 57 344 bytes at C = 8.  Everything else reads LDS: lane t owns frames 7 t .. 7 t + 6 of the
 // tile (stride 7 dwords: no bank conflicts).
 //
-//  * K-meters.  Kmeterdsp's end state is linear in the squares s = x^2 (mtr_kmeter.hip): z1 is a one-pole per frame (decay r = 1 - w),
-//    z2 takes 4 w (z1 - z2) at the end of every group of four.  A frame at offset j of its block (group j / 4, slot j mod 4) gives
-//    w r^(E - 1 - j) s to z1 at the piece's end E and w r^(ge - 1 - j) (c_k + 4 w b^k) s to z2 there — ge its group's end, k the group ends
-//    behind it inside the piece, A^k = [[a^k, 0], [c_k, b^k]] as in mtr_kmeter.hip.  Frames at j >= L - L mod 4 (L = P, or the call's
+//  * K-meters.  Kmeterdsp's end state is linear in the squares s = x^2, so every frame of a piece weighs into z1 and z2 at the piece's end
+//    by powers that depend on its place in its block alone: mtr_kmeter_dsp.h derives these pointwise weights and holds the piece's
+//    geometry, the lane's powers, the rule for a square that is not finite and the walk's arithmetic for KMETER's reading series and
+//    for the walk here; k_sur_pieces writes the geometry and the powers out itself.  Frames at j >= L - L mod 4 (L = P, or the call's
 //    length) weigh nothing and do not enter the maximum (kmeterdsp.cc:71), nor do the warm-up frames in front of the piece.  A lane
-//    takes the three powers of its first frame in the first tile from exp () of logarithms the host computed, steps them through its
-//    seven frames and from tile to tile by constants (no pow () in the loop); the sums are double.  The walk
-//    carries (z1, z2) from piece to piece in closed form — also through a call that ends inside a group — and rounds to f32 where the
-//    reference ends a process ().  A square that is not finite makes the block's z1 NaN in the reference (Inf - Inf at the next frame)
-//    unless it is the block's very last frame: the kernel adds a NaN for it, so the sums become what the reference's would be.
+//    takes the powers of its first frame in the first tile from exp (), steps them through its seven frames and from tile to tile by
+//    constants (no pow () in the loop); the sums are double.  The walk (final_channel) carries (z1, z2) from piece to piece in closed
+//    form and rounds to f32 where the reference ends a process ().
 //  * Correlations.  Per pair exactly k_stcorr_pieces' two passes (the head of mtr_stcorr.hip explains them: the carried zl / zr at
 //    "frame -1", the first stage rebuilt over `warm` frames, what the sums "owe" behind a period end that flushed), on 7-frame runs;
 //    the four pairs walk the staged tile one after the other, and the second pass computes its inputs from the staged samples again
 //    instead of holding them: with the constants every lane would compute alike passed from the host (scalar registers), every pair's
 //    carried first-stage state in LDS and the rare "owes" sums reduced where they arise, the kernel holds 223 .. 248 VGPRs, no
-//    scratch, and two workgroups fit a CU.
+//    scratch, and two workgroups fit a CU.  The walk over a pair's pieces is stcorr_walk (mtr_stcorr_scan.h).
 //
 // Track lengths (mtr_any.h): k_sur_pieces<C, true> and k_sur_final<true>, launched only by a call that carries
 // per-stream ends.  A workgroup is one (stream, piece), so the stream's end is one scalar: it cuts the piece, and the block it cuts has
@@ -44,6 +42,7 @@
 #include <vector>
 
 #include "mtr_engine_impl.h"
+#include "mtr_kmeter_dsp.h"
 #include "mtr_stcorr_scan.h"
 
 #define MTR_SUR_MAXCH 8
@@ -76,17 +75,21 @@ typedef struct mtr_sur_state {
 	mtr_sur_pair pr[MTR_SUR_PAIRS];
 } mtr_sur_state;
 
-#define MTR_SUR_PIECE_PAIR 9       /* doubles per (stream, piece, pair): as MTR_STCORR_PIECE */
-#define MTR_SUR_PIECE (MTR_SUR_PAIRS * MTR_SUR_PIECE_PAIR + 3 * MTR_SUR_MAXCH)   /* ... and per channel: what the piece's frames give to z1 and z2 at its end, max x^2 */
+/* doubles per (stream, piece): MTR_SUR_PIECE_PAIR per pair (mtr_stcorr_scan.h), and per channel what the piece's frames give to z1 and z2
+ * at its end, max x^2 */
+#define MTR_SUR_PIECE (MTR_SUR_PAIRS * MTR_SUR_PIECE_PAIR + 3 * MTR_SUR_MAXCH)
 
-/* the constants of k_sur_pieces, computed once on the host in double (kr = 1 - omega, ka = kr^4, kb = 1 - 4 omega; r = 1 - w1, q = 1 - w2) */
-typedef struct mtr_sur_consts {
+/* mtr_sur_consts (mtr_km_consts.h) as k_sur_pieces takes it: flat, in the order its scalar loads are grouped by.  The pieces kernel
+ * steps its lanes' powers itself (the statements of KmLane, on 7-frame runs out of LDS): through KmLane and the nested struct it
+ * measured 0.2 - 0.6 % slower without a period, dense and with track lengths, outside the spread of this one's own runs
+ * (profiles/r38_dsp_once.md) */
+typedef struct mtr_sur_pieces_consts {
 	double lkr, lkb, lq;          /* log kr, log kb, log q */
 	double kri, kai, kbi, kr3;    /* 1 / kr, 1 / ka, 1 / kb, kr^3 */
-	double ca, cb;                /* omega c / (ka - kb), omega (4 omega - c / (ka - kb)): the z2 weight of a frame is kr^(..) (ca ka^k + cb kb^k) */
+	double ca, cb;                /* the z2 weight of a frame is kr^(..) (ca ka^k + cb kb^k) */
 	double st1, sta, stb, sq;     /* kr^-TILE, ka^-(TILE / 4), kb^-(TILE / 4), q^-TILE: from tile to tile */
 	double d1, d2, d4, d8, d64;   /* r^K to the powers of the wave scan */
-} mtr_sur_consts;
+} mtr_sur_pieces_consts;
 
 typedef struct mtr_sur_args {
 	const float*    audio;        /* [S][stride][C] */
@@ -97,11 +100,11 @@ typedef struct mtr_sur_args {
 	uint32_t        n_streams, n_channels, n_pairs, n_pieces;
 	uint32_t        chunk, warm;
 	float           w1, w2;       /* Stcorrdsp::init */
-	float           omega, fall;  /* Kmeterdsp: 9.72f / fs, the fall-back factor of fpp */
+	float           omega, fall;  /* Kmeterdsp: omega, the fall-back factor of fpp */
 	uint32_t        fpp;
 	int32_t         hold;
-	double          pw[3];        /* A = [[a, 0], [c, b]] per group of four frames (mtr_kmeter.hip) */
-	mtr_sur_consts  k;            /* what every lane would compute alike: in scalar registers */
+	double          pw[3];        /* A = [[a, 0], [c, b]] per group of four frames (mtr_kmeter_dsp.h) */
+	mtr_sur_pieces_consts k;      /* what every lane would compute alike: in scalar registers */
 	uint8_t         pa[MTR_SUR_PAIRS], pb[MTR_SUR_PAIRS];
 	uint32_t        capacity;     /* points per stream the series hold */
 	uint64_t        point0;       /* blocks completed before this call */
@@ -122,17 +125,19 @@ typedef struct mtr_sur_len_args : mtr_sur_args {
 namespace {
 
 using namespace mtr_sc;
+using namespace mtr_km;                  // the K-meters' geometry, weights and walk (mtr_kmeter_dsp.h)
 
 constexpr int NT = 256;                  // threads per workgroup
 constexpr int K = 7;                     // frames per lane run: an odd dword stride in LDS
 constexpr int TILE = NT * K;             // frames per tile: 1792
 constexpr int MAX_TILES = 8;             // tiles per piece (chunk + warm)
 
-// the call frame at which the block of piece `pc` starts (negative: it started in an earlier call)
-__device__ __forceinline__ int64_t block_start (const mtr_sur_args& a, const Piece& pc)
+__device__ __forceinline__ int64_t block_start (const mtr_sur_args& a, const Piece& pc) { return km_block_start (a.e0, a.block, a.period, pc.b0); }
+
+// Kmeterdsp's constants for the walk (one thread per channel), out of the flat arguments
+__device__ __forceinline__ mtr_km_consts km_of (const mtr_sur_args& a)
 {
-	if ((uint64_t) pc.b0 < a.e0) return (int64_t) a.e0 - (int64_t) a.block;
-	return (int64_t) (a.e0 + ((uint64_t) pc.b0 - a.e0) / a.period * a.period);
+	return mtr_km_consts{a.omega, a.hold, {a.pw[0], a.pw[1], a.pw[2]}, a.k.lkr, a.k.lkb, a.k.kri, a.k.kai, a.k.kbi, a.k.kr3, a.k.ca, a.k.cb, a.k.st1, a.k.sta, a.k.stb};
 }
 
 template <bool LEN> using sur_args_of = std::conditional_t<LEN, mtr_sur_len_args, mtr_sur_args>;
@@ -400,60 +405,35 @@ __device__ void final_channel (const sur_args_of<LEN>& a, uint32_t s, uint32_t c
 {
 #pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
 	mtr_sur_chan* const st = &a.state[s].ch[c];
-	const double kw = (double) a.omega, kr = 1.0 - kw, ka = a.pw[0], kb = a.pw[2];
+	const mtr_km_consts km = km_of (a);
 	double z1 = st->z1, z2 = st->z2;
 	float level = st->level, peak = st->peak, tmax = st->tmax;
 	int32_t cnt = st->cnt, flag = st->flag;
 	uint64_t point = a.point0;
 	for (uint32_t i = 0; i < a.n_pieces; ++i) {
-		Piece pc = piece_of (a, i);
-		const int64_t blk0 = block_start (a, pc);
-		int64_t L = (int64_t) a.block;
+		const Piece pc = piece_of (a, i);
 		if constexpr (LEN) {
 			if (pc.b0 >= end) break;
-			if (end < (int64_t) a.n_frames && end < blk0 + L) L = end - blk0;
-			if (end <= pc.b1) {
-				pc.b1 = end;
-				if (L != (int64_t) a.block) pc.closes = true;          // one last process (), of what the stream has of the block
-			}
 		}
-		const int64_t Lg = L & ~(int64_t) 3;
-		const int64_t p0 = pc.b0 - blk0, E1 = pc.b1 - blk0 < Lg ? pc.b1 - blk0 : Lg;   // (as the pieces kernel's: z1 stops at Lg)
-		if (p0 == 0) {                                             // :74-75 (a NaN state falls through, as there; it is an f32 here)
-			z1 = z1 > 50 ? 50 : (z1 < 0 ? 0 : z1);
-			z2 = z2 > 50 ? 50 : (z2 < 0 ? 0 : z2);
+		const KmGeom g = km_geom<LEN> (pc, block_start (a, pc), a.block, end, a.n_frames);
+		if (g.p0 == 0) {
+			km_open (z1, z2);
 			tmax = 0.f;
 		}
 		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_SUR_PIECE + MTR_SUR_PAIRS * MTR_SUR_PIECE_PAIR + 3 * c;
-		if (E1 > p0) {
-			const int64_t m = (E1 >> 2) - (p0 >> 2);               // group ends in (p0, E1]
-			if (m > 0) {
-				const double am = pow (ka, (double) m), bm = pow (kb, (double) m);
-				z2 = bm * z2 + 4.0 * kw * ipow (kr, (uint64_t) (4 - (p0 & 3))) * ((am - bm) / (ka - kb)) * z1 + pv[1];
-			}
-			z1 = pow (kr, (double) (E1 - p0)) * z1 + pv[0];
-		}
+		if (g.E1 > g.p0) km_carry (km, g.p0, g.E1, pv[0], pv[1], z1, z2);
 		const float pm = (float) pv[2];
 		tmax = tmax < pm ? pm : tmax;
-		if (!pc.closes) continue;
-		float f1 = (float) z1, f2 = (float) z2, t = tmax;
-		if (isnan (f1)) f1 = 0;                                    // :101-103
-		if (isnan (f2)) f2 = 0;
-		if (!isfinite (t)) t = 0;
-		z1 = (double) (f1 + 1e-20f);                      // :106-107
-		z2 = (double) (f2 + 1e-20f);
-		const float rms = sqrtf (2.0f * f2);
-		t = sqrtf (t);
-		if (a.period || flag) { level = rms; flag = 0; }           // :112-121 (a host that reads after every block always finds the flag set)
-		else if (rms > level) level = rms;
+		if (!g.closes) continue;
+		const KmClose r = km_close (z1, z2, tmax);
+		if (a.period || flag) { level = r.rms; flag = 0; }         // :112-121 (a host that reads after every block always finds the flag set)
+		else if (r.rms > level) level = r.rms;
 		uint32_t fpp = a.fpp;
 		float fall = a.fall;
 		if constexpr (LEN) {
-			if (L != (int64_t) a.block) { fpp = (uint32_t) L; fall = a.falls[s]; }
+			if (g.L != (int64_t) a.block) { fpp = (uint32_t) g.L; fall = a.falls[s]; }
 		}
-		if (t >= peak) { peak = t; cnt = a.hold; }                 // :124-139
-		else if (cnt > 0) cnt -= (int32_t) fpp;
-		else { peak *= fall; peak += 1e-10f; }
+		km_peak_hold (r.t, peak, cnt, a.hold, fpp, fall);
 		if (a.period) {
 			if (point < a.capacity) {
 				const size_t o = ((size_t) s * a.capacity + point) * a.n_channels + c;
@@ -465,71 +445,14 @@ __device__ void final_channel (const sur_args_of<LEN>& a, uint32_t s, uint32_t c
 	st->z1 = z1; st->z2 = z2; st->level = level; st->peak = peak; st->tmax = tmax; st->cnt = cnt; st->flag = flag;
 }
 
-// one thread per (stream, pair): k_stcorr_final, LEN as there — the piece that holds the stream's end is its last, with its own length, and
-// an end inside the call ends a process () there
+// one thread per (stream, pair): stcorr_walk (mtr_stcorr_scan.h) over the pair's slots, as k_stcorr_final
 template <bool LEN>
 __device__ void final_pair (const sur_args_of<LEN>& a, uint32_t s, uint32_t p, int64_t end)
 {
-#pragma clang fp contract(off)     // (the f32 steps at a block's end are the reference's, one rounding each: no fused multiply-add)
 	mtr_sur_pair* const st = &a.state[s].pr[p];
-	const double q1 = 1.0 - (double) a.w2;
-	double z[3] = { (double) st->z[2], (double) st->z[3], (double) st->z[4] };
-	float zl = st->z[0], zr = st->z[1], corr = st->corr;
-	uint64_t point = a.point0;
-	int64_t len_of = -1;
-	double qp = 1.0;
-	bool flushed[2] = { false, false };
-	for (uint32_t i = 0; i < a.n_pieces; ++i) {
-		Piece pc = piece_of (a, i);
-		bool ends_here = false;                                        // (LEN: the stream's last piece)
-		if constexpr (LEN) {
-			if (pc.b0 >= end) break;
-			if (end <= pc.b1) {
-				ends_here = true;
-				if ((uint64_t) end < a.n_frames) pc.closes = true;
-				pc.b1 = end;
-			}
-		}
-		const int64_t len = pc.b1 - pc.b0;
-		if (len != len_of) { qp = pow (q1, (double) len); len_of = len; }
-		const double* const pv = a.piece + ((size_t) s * a.n_pieces + i) * MTR_SUR_PIECE + p * MTR_SUR_PIECE_PAIR;
-		double sum[3] = { pv[0], pv[1], pv[2] }, el = pv[3], er = pv[4];
-		if (pc.after_period && (flushed[0] || flushed[1])) {
-			// the period before left zl (zr) = 0 where the piece started from pv[7] (pv[8]): with rho = r^(frames since), zl' = zl + rho dl
-			const double dl = flushed[0] ? -pv[7] : 0.0, dr = flushed[1] ? -pv[8] : 0.0;
-			const double r = 1.0 - (double) a.w1, r2 = r * r;
-			double cq = 0.0, rr = 1.0;                             // sum c rho^2 = w2 sum_m q^(len - m) r^(2m), m = 1 .. len
-			for (int64_t m = 1; m <= len && rr > 1e-300; ++m) { rr *= r2; cq += ipow (q1, (uint64_t) (len - m)) * rr; }
-			cq *= (double) a.w2;
-			sum[0] += dr * pv[5] + dl * pv[6] + dl * dr * cq;
-			sum[1] += 2.0 * dl * pv[5] + dl * dl * cq;
-			sum[2] += 2.0 * dr * pv[6] + dr * dr * cq;
-			const double re = ipow (r, (uint64_t) len);
-			el += re * dl; er += re * dr;
-		}
-		if (pc.after_period) flushed[0] = flushed[1] = false;
-		for (int j = 0; j < 3; ++j) z[j] = fma (qp, z[j], sum[j]);
-		const bool last = i + 1 == a.n_pieces || ends_here;
-		if (last) { zl = (float) el; zr = (float) er; }
-		if (!pc.closes) continue;
-		float f[3] = { (float) z[0], (float) z[1], (float) z[2] };
-		flushed[0] = !isfinite (f[1]); flushed[1] = !isfinite (f[2]);  // this period leaves zl (zr) = 0 to the next
-		if (last && (!isfinite (zl) || !isfinite (f[1]))) zl = 0.f;    // stcorrdsp.cc:65-66
-		if (last && (!isfinite (zr) || !isfinite (f[2]))) zr = 0.f;
-		for (int j = 0; j < 3; ++j) {
-			if (!isfinite (f[j])) f[j] = 0.f;                      // :67-69
-			f[j] = f[j] + 1e-10f;                       // :73-75
-			z[j] = (double) f[j];
-		}
-		corr = f[0] / sqrtf (f[1] * f[2] + 1e-10f);   // :81
-		if (a.period) {
-			if (point < a.capacity) a.s_corr[((size_t) s * a.capacity + point) * MTR_SUR_PAIRS + p] = corr;
-			++point;
-		}
-	}
-	st->z[0] = zl; st->z[1] = zr;
-	for (int j = 0; j < 3; ++j) st->z[2 + j] = (float) z[j];
-	st->corr = corr;
+	const StcorrWalk v = { st->z, &st->corr, a.piece + (size_t) s * a.n_pieces * MTR_SUR_PIECE + p * MTR_SUR_PIECE_PAIR, MTR_SUR_PIECE,
+	                       a.capacity ? a.s_corr + (size_t) s * a.capacity * MTR_SUR_PAIRS + p : nullptr, MTR_SUR_PAIRS };
+	stcorr_walk<LEN> (a, v, end);
 }
 
 template <bool LEN>
@@ -592,21 +515,11 @@ static int surround_create (mtr_engine* e)
 	const uint32_t C = e->cfg.n_channels;
 	mtr_setup_stcorr (e->cfg.sample_rate, e->su.w);
 	mtr_sur_geometry (e->su.w[0], &e->su.warm, &e->su.chunk);
-	const double w = (double) (9.72f / e->cfg.sample_rate);        // kmeterdsp.cc:53; A as mtr_kmeter.hip
-	const double a1 = pow (1.0 - w, 4.0);
-	e->su.pw[0] = a1; e->su.pw[1] = 4.0 * w * a1; e->su.pw[2] = 1.0 - 4.0 * w;
-	{
-		static_assert (sizeof (mtr_sur_consts) == sizeof (e->su.k), "mtr_sur_consts");
-		mtr_sur_consts k;
-		const double kr = 1.0 - w, ka = a1, kb = e->su.pw[2], cab = e->su.pw[1] / (ka - kb);
-		const double r = 1.0 - (double) e->su.w[0], q = 1.0 - (double) e->su.w[1];
-		k.lkr = log (kr); k.lkb = log (kb); k.lq = log (q);
-		k.kri = 1.0 / kr; k.kai = 1.0 / ka; k.kbi = 1.0 / kb; k.kr3 = kr * kr * kr;
-		k.ca = w * cab; k.cb = w * (4.0 * w - cab);
-		k.st1 = pow (kr, (double) -TILE); k.sta = pow (ka, (double) (-TILE / 4)); k.stb = pow (kb, (double) (-TILE / 4)); k.sq = pow (q, (double) -TILE);
-		k.d1 = ipow (r, K); k.d2 = k.d1 * k.d1; k.d4 = k.d2 * k.d2; k.d8 = k.d4 * k.d4; k.d64 = ipow (k.d8, 8);
-		memcpy (e->su.k, &k, sizeof (k));
-	}
+	mtr_sur_consts& k = e->su.k;
+	km_setup (e->cfg.sample_rate, TILE, &k.km);                    // (a lane of k_sur_pieces: seven frames, every tile)
+	const double r = 1.0 - (double) e->su.w[0], q = 1.0 - (double) e->su.w[1];
+	k.lq = log (q); k.sq = pow (q, (double) -TILE);
+	k.d1 = ipow (r, K); k.d2 = k.d1 * k.d1; k.d4 = k.d2 * k.d2; k.d8 = k.d4 * k.d4; k.d64 = ipow (k.d8, 8);
 	for (uint32_t p = 0; p < MTR_SUR_PAIRS; ++p) {                 // the surround8 port defaults (lv2ttl/surmeter.h), clamped
 		e->su.pa[p] = (uint8_t) std::min (2 * p, C - 1); e->su.pb[p] = (uint8_t) std::min (2 * p + 1, C - 1);
 	}
@@ -632,14 +545,14 @@ static int surround_step (mtr_engine* e, const Call& c, Cursors& nx, const Strea
 	sa.w1 = e->su.w[0]; sa.w2 = e->su.w[1];
 	const uint32_t fpp = P ? (uint32_t) P : (uint32_t) c.n_frames;
 	if (nx.su_fpp != fpp) {                                        // kmeterdsp.cc:65-70
-		nx.su_fall = powf (10.0f, -0.05f * 15.0f * ((float) fpp / e->cfg.sample_rate));
+		nx.su_fall = km_fall (e->cfg.sample_rate, fpp);
 		nx.su_fpp = fpp;
 	}
 	sa.fpp = nx.su_fpp; sa.fall = nx.su_fall;
-	sa.hold = (int32_t) (0.5f * e->cfg.sample_rate + 0.5f);        // :52
-	sa.omega = 9.72f / e->cfg.sample_rate;
-	memcpy (sa.pw, e->su.pw, sizeof (sa.pw));
-	memcpy (&sa.k, e->su.k, sizeof (sa.k));
+	const mtr_sur_consts& k = e->su.k;
+	sa.omega = k.km.omega; sa.hold = k.km.hold;
+	memcpy (sa.pw, k.km.pw, sizeof (sa.pw));
+	sa.k = { k.km.lkr, k.km.lkb, k.lq, k.km.kri, k.km.kai, k.km.kbi, k.km.kr3, k.km.ca, k.km.cb, k.km.st1, k.km.sta, k.km.stb, k.sq, k.d1, k.d2, k.d4, k.d8, k.d64 };
 	memcpy (sa.pa, e->su.pa, sizeof (sa.pa)); memcpy (sa.pb, e->su.pb, sizeof (sa.pb));
 	sa.capacity = cap; sa.point0 = e->pos.su.points;
 	if (e->su.piece.reserve ((size_t) e->cfg.n_streams * sa.n_pieces * MTR_SUR_PIECE)) return fail (MTR_ERR_NOMEM, "hipMalloc SURROUND pieces");
