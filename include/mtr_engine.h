@@ -35,7 +35,8 @@ extern "C" {
  *    _kmeter_series; mtr_engine_spectr_set_period, _spectr_period, _spectr_series; mtr_engine_process_device_ends, _process_host_ends,
  *    _spectr_points; mtr_engine_scope_set_series, _scope_series_config, _scope_series, mtr_scope_series_cut; mtr_engine_process_device_any,
  *    _process_host_any, _scope_points; MTR_METER_GONIO, mtr_gonio_derive, mtr_engine_gonio_configure, _gonio_config, _gonio_set_gain,
- *    _gonio_image, _gonio_read, _gonio_blocks, _gonio_series, _gonio_image_clear, _gonio_reset):
+ *    _gonio_image, _gonio_read, _gonio_blocks, _gonio_series, _gonio_image_clear, _gonio_reset; mtr_gonio_os_table, mtr_gonio_os_hpw,
+ *    mtr_engine_gonio_set_oversample, _gonio_oversample, _gonio_os_timing):
  *    + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
@@ -413,6 +414,9 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* Track lengths for the goniometer, beside the stereo meters of _any: mtr_engine_process_device_gonio_ends / _host_gonio_ends, mtr_gonio_cut
  * and mtr_engine_gonio_points, declared in mtr_gonio_ends.h */
 #include "mtr_gonio_ends.h"
+/* The goniometer's oversampling, the 2 - 32x interpolator in front of draw_rb: mtr_gonio_os_table, mtr_gonio_os_hpw,
+ * mtr_engine_gonio_set_oversample / _gonio_oversample / _gonio_os_timing, declared in mtr_gonio_os.h */
+#include "mtr_gonio_os.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

@@ -16,7 +16,8 @@ extern "C" {
 /* The goniometer for a batch (MTR_METER_GONIO; stereo engines only — a pair of a wider frame goes through mtr_engine_set_frame_layout).
  * Combines with every other stereo meter.  Track lengths: mtr_engine_process_device_gonio_ends / _host_gonio_ends (mtr_gonio_ends.h); the six
  * older pairs of calls with per-stream ends (mtr_engine_process_*_lengths .. _any) refuse the meter.
- * What is reproduced is draw_rb in points mode (s_line false), without oversampling (src_fact 1), with infinite persistence
+ * What is reproduced is draw_rb in points mode (s_line false), with or without oversampling (src_fact 1, the default, or 2 .. 32 through
+ * mtr_engine_gonio_set_oversample: mtr_gonio_os.h, which says what a frame below becomes then), with infinite persistence
  * (persist >= 1.0, gui/goniometer.c:327) and without inflate, in the reference's f32 / double operations and their order: per frame
  * (:401-449) the one-pole per channel, lp += hpw (d - lp), lp += 1e-12f; ax = lp0 - lp1, ay = lp0 + lp1; x = 186.5f - gain ax 100.f, y
  * alike; a frame whose point moved less than sqrt (2) from the last painted one is skipped, any other is painted at
@@ -43,7 +44,8 @@ typedef struct mtr_gonio_config {
 typedef struct mtr_gonio_derived {
 	uint32_t period_frames;      /* P, resolved */
 	uint32_t G;                  /* cells per image row and column */
-	float    hpw;                /* expf (-2.0 * M_PI * 20 / rate)  (:165) */
+	float    hpw;                /* expf (-2.0 * M_PI * 20 / rate)  (:165): the factor-1 value, whatever mtr_engine_gonio_set_oversample set
+	                              * (what the chain runs on then: mtr_engine_gonio_oversample) */
 	float    attack[2];          /* `attack` of :524 for elapsed = P / rate: [0] where the target is below the gain, [1] otherwise */
 	float    g_target, g_rms;    /* :906-912 */
 } mtr_gonio_derived;
@@ -78,7 +80,7 @@ int  mtr_engine_gonio_image_clear (mtr_engine* e);
 int  mtr_engine_gonio_reset (mtr_engine* e);
 /* For measurements (tools/gonio_rate.py): enable != 0 starts timing the two kernels of every piece with events, 0 stops it; *points_ms /
  * *image_ms: k_gonio_points' and k_gonio_image's time summed over the *pieces timed since the last query, which are then forgotten.  No
- * reference counterpart.  Synchronises. */
+ * reference counterpart.  Synchronises.  (k_gonio_os of an oversampling engine: mtr_engine_gonio_os_timing, mtr_gonio_os.h.) */
 int  mtr_engine_gonio_timing (mtr_engine* e, int enable, float* points_ms, float* image_ms, uint32_t* pieces);
 /* Getters synchronise; any output pointer may be NULL; a NULL engine or one without the meter: MTR_ERR_ARG. */
 

@@ -55,7 +55,9 @@ int  mtr_engine_process_host_gonio_ends (mtr_engine* e, const float* h_audio, ui
  * `period` frames it completes; *closing_frames: r where a closing update runs, else 0; *drawn_frames: the call frame at which its
  * drawing ends (frames, or frames - r for 0 < r < 64, never below 0); attack [2]: the closing update's `attack` of :524 from cfg's dials
  * ([0] where the target is below the gain, [1] otherwise; negative where the formula gives it so: r = 64 at 192 kHz), 0 without one.
- * MTR_ERR_ARG: a NULL, fill >= period, frames > n_frames, or what mtr_gonio_derive refuses. */
+ * MTR_ERR_ARG: a NULL, fill >= period, frames > n_frames, or what mtr_gonio_derive refuses.
+ * Everything here counts INPUT frames, with or without oversampling (mtr_gonio_os.h): draw_rb's floor of 64 and `elapsed` do; a closing
+ * update of r frames then walks r f points with rms_c = r f. */
 int  mtr_gonio_cut (uint64_t fill, uint32_t period, double rate, uint64_t n_frames, uint64_t frames, const mtr_gonio_config* cfg,
                     uint64_t* whole, uint32_t* closing_frames, uint64_t* drawn_frames, float attack[2]);
 /* updates [count], points [count]: each stream's own display updates since reset, closing ones included, and the points its series has

@@ -120,6 +120,8 @@ static int check_limits (const mtr_engine* e, uint64_t n_frames)
 		return fail (MTR_ERR_ARG, "SPECTR30 with a closed stream: n_frames per call must be < 2^32 - 1");
 	if ((e->cfg.meters & MTR_METER_GONIO) && e->n_closed && n_frames > 0xFFFFFFFEull)   // (likewise: mtr_gonio_ends.h)
 		return fail (MTR_ERR_ARG, "GONIO with a closed stream: n_frames per call must be < 2^32 - 1");
+	if ((e->cfg.meters & MTR_METER_GONIO) && e->go.os > 1 && n_frames > 0xFFFFFFFEull / e->go.os)   // (its kernels count points: mtr_gonio_os.h)
+		return fail (MTR_ERR_ARG, "GONIO oversampled: n_frames * factor per call must be < 2^32 - 1");
 	if ((e->cfg.meters & MTR_METER_TPBALLIST) && n_frames >= 0x7ffff000ull) return fail (MTR_ERR_ARG, "TPBALLIST: n_frames per call must be < 2^31 - 4096");
 	if ((e->cfg.meters & (MTR_METER_EBU | MTR_METER_TRUEPEAK)) && n_frames >= 0xFFFFFFFFull) return fail (MTR_ERR_ARG, "n_frames per call must be < 2^32 - 1");
 	return MTR_OK;

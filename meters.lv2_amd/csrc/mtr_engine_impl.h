@@ -118,6 +118,7 @@ struct Cursors {
 	uint64_t ll_frags = 0;        // loudness log: fragments the open streams have ended since it was set / reset
 	SeriesPos tb;                 // TPBALLIST with a period: where its reading series stands (mtr_series.h)
 	SeriesPos go;                 // GONIO: frames into the open display update, updates completed since reset (mtr_series.h)
+	int      go_hist_cur = 0;     // GONIO oversampled: which of go.os_hist [2] holds the 23 input frames before the next call
 };
 
 // per-stream state of the side meters: defined where their kernels are
@@ -347,6 +348,15 @@ struct mtr_engine {
 		std::vector<Event>         ev;          // while mtr_engine_gonio_timing is on: three per piece, around its two kernels
 		bool                       timed = false;
 		std::vector<uint64_t>      updates;     // [S] each stream's own display updates since reset, closing ones included (mtr_gonio_ends.h)
+		// oversampling (mtr_gonio_os.h): a control (it survives a reset).  Everything below is allocated only with a factor above 1
+		uint32_t                   os = 1;      // the factor: 1 (off) or 2 .. 32
+		float                      os_hpw = 0.f;   // the hpw the chain runs on with the factor (:175)
+		DevBuf<float>              os_tab;      // [os + 1][12] Resampler_table's _ctab
+		DevBuf<float>              os_pts;      // [S][os_pitch][2] the points of one piece of a call: k_gonio_os writes, k_gonio_points reads
+		DevBuf<float>              os_hist[2];  // [S] rows of 48 floats, ping-pong (pos.go_hist_cur): the last 23 input frames, then the blob's header
+		DevBuf<uint32_t>           os_cut;      // [S] a ragged call's cuts as k_gonio_os rebases them to the piece's first point
+		uint32_t                   os_pitch = 0;   // points per stream of os_pts: even, so that a row starts on 16 bytes
+		std::vector<Event>         os_ev;       // while mtr_engine_gonio_timing is on: two per piece, around k_gonio_os
 	} go;
 };
 
@@ -462,13 +472,15 @@ struct SideMeter {
 // (Constant-initialised and never written, but not declared const: the device pass of a .hip file would emit a const object of namespace
 // scope too, and there the host functions it names do not exist.  Everything reads the rows through SIDE_METERS' pointers to const.)
 extern SideMeter bank_meter, intstat_meter, dr14_meter, kmeter_meter, stcorr_meter, needle_meter, surround_meter, scope_meter, kmeter_series_meter,
-                 bank_series_meter, scope_series_meter, tpb_meter, gonio_meter;
+                 bank_series_meter, scope_series_meter, tpb_meter, gonio_meter, gonio_os_meter;
 inline constexpr const SideMeter* SIDE_METERS[] = { &bank_meter, &intstat_meter, &dr14_meter, &kmeter_meter, &stcorr_meter, &needle_meter, &surround_meter, &scope_meter,
                                                     &kmeter_series_meter,     // (KMETER's second row: nothing but the blob section of its open block, behind every older one)
                                                     &bank_series_meter,       // (SPECTR30's second row, likewise)
                                                     &scope_series_meter,      // (SCOPE's second row, likewise)
                                                     &tpb_meter,               // (TPBALLIST: its states are the stream state's; the section is its series' open block)
-                                                    &gonio_meter };
+                                                    &gonio_meter,
+                                                    &gonio_os_meter };        // (GONIO's second row: the input history of its oversampling — its kernel, the call's last of
+                                                                              // the meter, and its blob section with the factor; nothing at factor 1)
 // the points of each of streams [first, first + count) in the series of the meter with `bit`, which the engine holds and which keeps such counts
 void series_points_of (mtr_engine* e, uint32_t bit, uint32_t first, uint32_t count, uint64_t* points);
 // Stream g's own counts, every meter's of the engine: the points of the reading series (the blocks the stream completed and, closed inside one,

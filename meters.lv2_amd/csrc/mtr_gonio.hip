@@ -1,5 +1,6 @@
-// mtr_gonio.hip — the goniometer (draw_rb, gui/goniometer.c:299-538: points mode, no oversampling, infinite persistence, no inflate) for
-// a batch: the M/S point image as counts per cell, the auto gain, a point per display update (gfx950).
+// mtr_gonio.hip — the goniometer (draw_rb, gui/goniometer.c:299-538: points mode, infinite persistence, no inflate; oversampling by 2 .. 32
+// as an option: k_gonio_os and k_gonio_hist, further down) for a batch: the M/S point image as counts per cell, the auto gain, a point per
+// display update (gfx950).
 //
 // Per frame (:401-449), all in f32 and in the reference's order — this file is compiled without FMA contraction and without fast-math,
 // f32 subnormals are kept:
@@ -395,6 +396,105 @@ __global__ __launch_bounds__ (NT) void k_gonio_image (const std::conditional_t<E
 
 constexpr uint32_t cells_of (uint32_t shift) { return (MTR_GONIO_BOUNDS + (1u << shift) - 1) >> shift; }
 
+// ---- oversampling (mtr_gonio_os.h): the Resampler in front of draw_rb (gui/goniometer.c:359-377; zita-resampler/resampler.cc:215-228) ----
+// With a factor f above 1 a piece is walked by three kernels: k_gonio_os writes the piece's n f points [S][n f][2] into the engine's
+// scratch, then k_gonio_points and k_gonio_image run on that scratch as on a call's buffer — audio = the scratch, stride = its pitch,
+// f0 = 0, with P f, fill f, n f and the oversampled hpw — and behind the call's last piece k_gonio_hist leaves every stream's last 23
+// input frames for the next call.
+//   k_gonio_os    throughput work: every point is independent of every other.  A workgroup of 256 lanes takes a tile of OS_TILE input
+//                 frames of one stream: the table (pitch 13 dwords: the lanes of a wave read f different rows at the same tap, 13 is odd, so
+//                 up to 32 rows fall into different banks) and the tile with its 23-frame halo (from the call's buffer, or — in front of the
+//                 call's first frame — from the stream's history row) go into LDS; a lane takes one point and both its channels, two serial
+//                 sums of 12 steps in exactly the reference's operations (two products, their sum, the sum onto s: this file is built without
+//                 contraction), the frames read as ds_read_b64 (lanes of one frame: a broadcast; of neighbouring frames: neighbouring banks),
+//                 and stores its 8 bytes next to its neighbour's.
+//                 ENDS: nothing at or behind a stream's cut is loaded or written (the interpolator is causal), and the first tile's first lane
+//                 leaves the cut REBASED to the piece's first point in os_cut[s] — which is what lets the ENDS instantiations of the two older
+//                 kernels run with f0 = 0 on the scratch, unchanged: they only ever compare the cut with f0 and f0 + n.
+//   k_gonio_hist  one lane per (stream, history frame), the cut rules of mtr_history.hip in one formula: the row's frame i takes call frame
+//                 end - 23 + i, end = the call's frames (a dense call) or the stream's own end (a call with ends; 0 — closed or untouched — keeps
+//                 the old row), a negative frame coming from the old row: calls shorter than 23 frames mix the two.  The rows ping-pong.
+constexpr int OS_TAPS = MTR_GONIO_OS_TAPS, OS_HALO = 2 * OS_TAPS - 1, OS_TILE = 128, OS_TPITCH = OS_TAPS + 1;
+constexpr int OS_HROW = 48;                      // floats of a history row: [23][2], then the blob's header (mtr_gonio_os_hdr), on 16 bytes
+
+typedef struct mtr_gonio_os_args {
+	const float*    audio;       /* [S][stride][2] */
+	uint64_t        stride;
+	uint64_t        f0;          /* the piece's first frame in the call */
+	uint32_t        n;           /* ... and its input frames */
+	uint32_t        n_streams;
+	uint32_t        f;           /* the factor, 2 .. 32 */
+	uint32_t        tiles;       /* tiles of OS_TILE frames per stream: the grid is n_streams * tiles */
+	const float*    hist;        /* [S][OS_HROW] the 23 frames in front of the call */
+	const float*    tab;         /* [f + 1][12] */
+	float*          pts;         /* [S][pitch][2] */
+	uint64_t        pitch;       /* points per stream of the scratch */
+	const uint32_t* cut;         /* ENDS: [S] the call POINT at which the stream's drawing ends (mtr_gonio_ends_args::cut) */
+	uint32_t*       piece_cut;   /* ENDS: [S] out: the same, counted from the piece's first point */
+} mtr_gonio_os_args;
+
+template <bool ENDS>
+__global__ __launch_bounds__ (256) void k_gonio_os (const mtr_gonio_os_args a)
+{
+	__shared__ float tab[(MTR_GONIO_OS_MAX + 1) * OS_TPITCH];
+	__shared__ float2 x[OS_TILE + OS_HALO];
+	const int tid = threadIdx.x;
+	const uint32_t s = blockIdx.x / a.tiles, tile = blockIdx.x - s * a.tiles;
+	const int f = (int) a.f;
+	const int t0 = (int) tile * OS_TILE;                                 // the tile's first frame in the piece
+	int lim = (int) a.n;                                                 // the frames of the piece the stream takes
+	if constexpr (ENDS) {
+		const uint32_t cut = a.cut[s];
+		const uint64_t p0 = a.f0 * (uint64_t) f;
+		if (tile == 0 && tid == 0) a.piece_cut[s] = cut == MTR_GONIO_OPEN ? cut : (uint64_t) cut <= p0 ? 0u : (uint32_t) ((uint64_t) cut - p0);
+		lim = gonio_limit (cut == MTR_GONIO_OPEN ? cut : cut / (uint32_t) f, a.f0, lim);   // (a cut is a whole number of frames)
+	}
+	const int nf = min (OS_TILE, lim - t0);
+	if (nf <= 0) return;
+	for (int i = tid; i < (f + 1) * OS_TAPS; i += 256) tab[(i / OS_TAPS) * OS_TPITCH + i % OS_TAPS] = a.tab[i];
+	for (int k = tid; k < nf + OS_HALO; k += 256) {                      // x [k]: piece frame t0 - 23 + k, < t0 + nf <= lim
+		const int64_t g = (int64_t) a.f0 + t0 - OS_HALO + k;                 // ... and call frame g
+		const float* const p = g >= 0 ? a.audio + ((uint64_t) s * a.stride + (uint64_t) g) * 2 : a.hist + (size_t) s * OS_HROW + (size_t) (OS_HALO + g) * 2;
+		x[k] = float2{p[0], p[1]};
+	}
+	__syncthreads ();
+	float2* const out = reinterpret_cast<float2*> (a.pts) + (size_t) s * a.pitch + (size_t) t0 * f;
+	for (int p = tid; p < nf * f; p += 256) {
+		const int m = p / f, ph = p - m * f;
+		const float* const c1 = &tab[ph * OS_TPITCH];
+		const float* const c2 = &tab[(f - ph) * OS_TPITCH];
+		float s0 = 1e-20f, s1 = 1e-20f;                                  // resampler.cc:221-228, both channels
+#pragma unroll
+		for (int i = 0; i < OS_TAPS; ++i) {
+			const float2 q1 = x[m + i], q2 = x[m + OS_HALO - i];             // frames m - 23 + i and m - i
+			s0 += q1.x * c1[i] + q2.x * c2[i];
+			s1 += q1.y * c1[i] + q2.y * c2[i];
+		}
+		out[p] = float2{s0 - 1e-20f, s1 - 1e-20f};
+	}
+}
+
+typedef struct mtr_gonio_hist_args {
+	const float*    audio;       /* [S][stride][2] */
+	uint64_t        stride, n_frames;
+	uint32_t        n_streams;
+	const uint32_t* ends;        /* [S] the call frame at which the stream ends (0: closed, untouched), or null: a dense call */
+	const float*    hist_in;     /* [S][OS_HROW] */
+	float*          hist_out;
+} mtr_gonio_hist_args;
+
+__global__ void k_gonio_hist (const mtr_gonio_hist_args a)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= a.n_streams * (uint32_t) OS_HALO) return;
+	const uint32_t s = g / OS_HALO, i = g % OS_HALO;
+	const int64_t end = a.ends ? (int64_t) a.ends[s] : (int64_t) a.n_frames;
+	const int64_t f = (int64_t) i - OS_HALO + end;                       // < end <= n_frames <= stride
+	const float* const p = f >= 0 ? a.audio + ((uint64_t) s * a.stride + (uint64_t) f) * 2 : a.hist_in + (size_t) s * OS_HROW + (size_t) (OS_HALO + f) * 2;
+	float* const o = a.hist_out + (size_t) s * OS_HROW + 2 * (size_t) i;
+	o[0] = p[0]; o[1] = p[1];
+}
+
 }  // namespace
 
 static int mtr_launch_gonio (const mtr_gonio_args& a, bool autogain, hipStream_t st, hipEvent_t* ev)
@@ -431,6 +531,18 @@ static int mtr_launch_gonio_ends (const mtr_gonio_ends_args& a, bool autogain, h
 	else if (a.shift == 2) hipLaunchKernelGGL ((k_gonio_image<cells_of (2), 256, true>), grid, dim3 (256), 0, st, a);
 	else hipLaunchKernelGGL ((k_gonio_image<cells_of (3), 256, true>), grid, dim3 (256), 0, st, a);
 	if (ev && hipEventRecord (ev[2], st) != hipSuccess) return -1;
+	return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// the interpolator of a piece (factor above 1), in front of the two launchers above: `ends` selects the ENDS instantiation
+static int mtr_launch_gonio_os (mtr_gonio_os_args& a, bool ends, hipStream_t st, hipEvent_t* ev)
+{
+	a.tiles = (a.n + OS_TILE - 1) / OS_TILE;
+	const dim3 grid (a.n_streams * a.tiles);
+	if (ev && hipEventRecord (ev[0], st) != hipSuccess) return -1;
+	if (ends) hipLaunchKernelGGL (k_gonio_os<true>, grid, dim3 (256), 0, st, a);
+	else hipLaunchKernelGGL (k_gonio_os<false>, grid, dim3 (256), 0, st, a);
+	if (ev && hipEventRecord (ev[1], st) != hipSuccess) return -1;
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
@@ -508,6 +620,44 @@ static int gonio_apply (mtr_engine* e, const mtr_gonio_config& c, const mtr_goni
 	return MTR_OK;
 }
 
+// ---- oversampling: the table, hpw, the engine's buffers ----
+// Resampler_table for fr = 1.0, hl = 12, np = F in double, as zita-resampler/resampler-table.cc:52-75 builds it (t grows by additions of 1)
+static double os_sinc (double x) { x = fabs (x); if (x < 1e-6) return 1.0; x *= M_PI; return sin (x) / x; }
+static double os_wind (double x) { x = fabs (x); if (x >= 1.0) return 0.0; x *= M_PI; return 0.384 + 0.500 * cos (x) + 0.116 * cos (2 * x); }
+static void gonio_os_table (uint32_t F, float* out)
+{
+	const double fr = 1.0;
+	for (uint32_t j = 0; j <= F; ++j) {
+		double t = (double) j / (double) F;
+		for (uint32_t i = 0; i < (uint32_t) OS_TAPS; ++i, t += 1) out[j * OS_TAPS + OS_TAPS - 1 - i] = (float) (fr * os_sinc (t * fr) * os_wind (t / OS_TAPS));
+	}
+}
+
+static float gonio_os_hpw (double rate, uint32_t F) { return expf ((float) (-2.0 * M_PI * 20 / (rate * (double) (float) F))); }   // :175 (F = 1: :165)
+
+constexpr const char* GONIO_OS_PERIOD = "GONIO oversampled: a display update is at most floor (rate) frames (the reference's scratch, gui/goniometer.c:173-181)";
+
+// the engine's buffers for factor F and the configuration it holds (F = 1: none are kept)
+static int gonio_os_apply (mtr_engine* e, uint32_t F)
+{
+	const size_t S = e->cfg.n_streams;
+	e->go.os = F;
+	e->go.os_hpw = gonio_os_hpw ((double) e->cfg.sample_rate, F);
+	if (F <= 1) {
+		e->go.os_pts.drop (); e->go.os_tab.drop (); e->go.os_cut.drop ();
+		for (auto& h : e->go.os_hist) h.drop ();
+		return MTR_OK;
+	}
+	e->go.os_pitch = (e->go.cfg.tune_piece + 1u) & ~1u;
+	if (e->go.os_pts.reserve (S * e->go.os_pitch * 2) || e->go.os_tab.reserve ((size_t) (MTR_GONIO_OS_MAX + 1) * OS_TAPS) || e->go.os_cut.reserve (S)
+	    || e->go.os_hist[0].reserve (S * OS_HROW) || e->go.os_hist[1].reserve (S * OS_HROW))
+		return fail (MTR_ERR_NOMEM, "hipMalloc GONIO oversampling");
+	float tab[(MTR_GONIO_OS_MAX + 1) * OS_TAPS];
+	gonio_os_table (F, tab);
+	HIPCHK (hipMemcpy (e->go.os_tab.p, tab, (size_t) (F + 1) * OS_TAPS * sizeof (float), hipMemcpyHostToDevice));
+	return MTR_OK;
+}
+
 static int gonio_create (mtr_engine* e)
 {
 	mtr_gonio_config z, c;
@@ -563,17 +713,19 @@ static void gonio_count (mtr_engine* e, size_t g, const Call* c, uint64_t frames
 }
 
 // The meter's words of a ragged call (SideMeter::ends_fill): [cut S | closing S | attack S x 2], per stream of the view the call frame at
-// which its drawing ends (MTR_GONIO_OPEN: not in this call), the frames of its closing display update or 0, that update's attack pair.
-// The note: the last call frame any stream of the view draws
+// which its drawing ends (MTR_GONIO_OPEN: not in this call), the frames of its closing display update or 0, that update's attack pair —
+// cut and closing in POINTS, F per frame, where the engine oversamples.  The note: the last call frame (an input frame) any stream of the view draws
 static uint64_t gonio_ends_fill (const mtr_engine* e, const Call& c, uint32_t* own)
 {
 	const size_t S = c.cnt;
+	const uint32_t F = e->go.os;
 	uint64_t last = 0;
 	for (uint32_t i = 0; i < S; ++i) {
 		const uint64_t f = call_frames (e, c, i);
 		const GonioCut k = gonio_cut (e, c, f);
-		own[i] = f == c.n_frames ? 0xFFFFFFFFu : (uint32_t) k.drawn;     // (MTR_GONIO_OPEN: the stream does not end in this call)
-		own[S + i] = k.closing;
+		// (oversampled: the kernels walk POINTS, F per frame — check_limits keeps n_frames F below 2^32 - 1; the cut itself counts input frames)
+		own[i] = f == c.n_frames ? 0xFFFFFFFFu : (uint32_t) (k.drawn * F);   // (MTR_GONIO_OPEN: the stream does not end in this call)
+		own[S + i] = k.closing * F;
 		memcpy (own + 2 * S + 2 * (size_t) i, k.attack, sizeof (k.attack));
 		last = std::max (last, k.drawn);
 	}
@@ -585,13 +737,15 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 	const mtr_gonio_config& g = e->go.cfg;
 	const mtr_gonio_derived& d = e->go.der;
 	const uint32_t P = g.period_frames, cap = g.capacity;
+	const uint32_t F = e->go.os;                                       // oversampling: F points per input frame (1: none — today's launches, argument for argument)
+	const uint32_t piece = g.tune_piece / F;                           // input frames per piece: never more than tune_piece points (>= 2: tune_piece >= 64, F <= 32)
 	const size_t S = e->cfg.n_streams;
 	mtr_gonio_ends_args a;                                             // (a dense call launches on its base)
 	memset (static_cast<void*> (&a), 0, sizeof (a));
 	if (se.own) { a.cut = se.own; a.closing = se.own + c.cnt; a.c_attack = reinterpret_cast<const float*> (se.own + 2 * (size_t) c.cnt); }   // (gonio_ends_fill)
 	a.audio = c.audio; a.stride = c.stride; a.n_streams = c.cnt;
-	a.P = P; a.capacity = cap; a.shift = g.shift; a.G = d.G; a.code_pitch = e->go.code_pitch;
-	a.hpw = d.hpw; a.attack[0] = d.attack[0]; a.attack[1] = d.attack[1]; a.g_target = d.g_target; a.g_rms = d.g_rms;
+	a.P = P * F; a.capacity = cap; a.shift = g.shift; a.G = d.G; a.code_pitch = e->go.code_pitch;
+	a.hpw = F > 1 ? e->go.os_hpw : d.hpw; a.attack[0] = d.attack[0]; a.attack[1] = d.attack[1]; a.g_target = d.g_target; a.g_rms = d.g_rms;
 	a.hw = (float) (g.point_width * .5);
 	a.pitch = e->go.pitch;
 	a.state = e->go.state.p + (size_t) c.off * a.pitch;
@@ -599,15 +753,28 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 	a.s_drawn = reinterpret_cast<uint32_t*> (e->go.series.p + S * cap) + (size_t) c.off * cap;
 	a.s_clipped = reinterpret_cast<uint32_t*> (e->go.series.p + 2 * S * cap) + (size_t) c.off * cap;
 	a.codes = e->go.codes.p;                                           // (a scratch: every view of a host call takes it from the start)
+	mtr_gonio_os_args o;
+	memset (&o, 0, sizeof (o));
+	if (F > 1) {
+		// k_gonio_os reads the call, the two older kernels read its points: the scratch [cnt][os_pitch][2] as their `audio`, every piece at f0 = 0,
+		// and — a ragged call — the cuts as k_gonio_os rebases them to the piece (both scratches are taken from the start, like the codes)
+		o.audio = c.audio; o.stride = c.stride; o.n_streams = c.cnt; o.f = F;
+		o.hist = e->go.os_hist[e->pos.go_hist_cur].p + (size_t) c.off * OS_HROW;
+		o.tab = e->go.os_tab.p; o.pts = e->go.os_pts.p; o.pitch = e->go.os_pitch;
+		o.cut = a.cut; o.piece_cut = e->go.os_cut.p;
+		a.audio = e->go.os_pts.p; a.stride = e->go.os_pitch;
+		if (se.own) a.cut = e->go.os_cut.p;
+	}
 	// the periods are cut from where the CALL started (e->pos): every chunk of a host call sees the same cuts
 	SeriesPos pos = e->pos.go;
-	for (uint64_t f0 = 0; f0 < c.n_frames; f0 += g.tune_piece) {
-		a.f0 = f0;
-		a.n = (uint32_t) std::min<uint64_t> (g.tune_piece, c.n_frames - f0);
-		a.fill = (uint32_t) pos.fill; a.point0 = pos.points;
+	for (uint64_t f0 = 0; f0 < c.n_frames; f0 += piece) {
+		const uint32_t nf = (uint32_t) std::min<uint64_t> (piece, c.n_frames - f0);   // the piece's input frames
+		a.f0 = F > 1 ? 0 : f0;
+		a.n = nf * F;
+		a.fill = (uint32_t) pos.fill * F; a.point0 = pos.points;
 		// (per-stream ends: only the pieces in which some stream of the view still draws are launched; the cursor moves on regardless)
-		if (se.ends && f0 >= se.note) { pos = series_advance (pos, P, a.n); continue; }
-		hipEvent_t ev[3];
+		if (se.ends && f0 >= se.note) { pos = series_advance (pos, P, nf); continue; }
+		hipEvent_t ev[3], oev[2];
 		const bool tm = e->go.timed && c.commit;
 		if (tm) {
 			for (int i = 0; i < 3; ++i) {
@@ -615,10 +782,19 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 				HIPCHK (e->go.ev.back ().ensure (hipEventDefault));
 				ev[i] = e->go.ev.back ().v;
 			}
+			for (int i = 0; F > 1 && i < 2; ++i) {
+				e->go.os_ev.emplace_back ();
+				HIPCHK (e->go.os_ev.back ().ensure (hipEventDefault));
+				oev[i] = e->go.os_ev.back ().v;
+			}
+		}
+		if (F > 1) {
+			o.f0 = f0; o.n = nf;
+			if (mtr_launch_gonio_os (o, se.ends != nullptr, c.st, tm ? oev : nullptr)) return fail (MTR_ERR_HIP, "k_gonio_os launch");
 		}
 		if (se.ends ? mtr_launch_gonio_ends (a, g.autogain != 0, c.st, tm ? ev : nullptr) : mtr_launch_gonio (a, g.autogain != 0, c.st, tm ? ev : nullptr))
 			return fail (MTR_ERR_HIP, "k_gonio launch");
-		pos = series_advance (pos, P, a.n);
+		pos = series_advance (pos, P, nf);
 	}
 	nx.go = pos;
 	return MTR_OK;
@@ -651,6 +827,49 @@ static void gonio_hdr_take (mtr_engine* e, const void* in) { e->pos.go.fill = st
 
 static constinit BlobHeader gonio_hdr = { 0, sizeof (mtr_gonio_hdr), GONIO_CORRUPT, gonio_hdr_write, gonio_hdr_check, gonio_hdr_take };
 
+// ---- oversampling: the second row of the meter (SIDE_METERS): its step is the call's last kernel of the meter, its section the history ----
+static int gonio_os_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
+{
+	if (e->go.os <= 1) return MTR_OK;
+	mtr_gonio_hist_args h;
+	memset (&h, 0, sizeof (h));
+	h.audio = c.audio; h.stride = c.stride; h.n_frames = c.n_frames; h.n_streams = c.cnt; h.ends = se.ends;
+	h.hist_in = e->go.os_hist[e->pos.go_hist_cur].p + (size_t) c.off * OS_HROW;
+	h.hist_out = e->go.os_hist[e->pos.go_hist_cur ^ 1].p + (size_t) c.off * OS_HROW;
+	hipLaunchKernelGGL (k_gonio_hist, dim3 ((c.cnt * (uint32_t) OS_HALO + 255) / 256), dim3 (256), 0, c.st, h);
+	if (hipGetLastError () != hipSuccess) return fail (MTR_ERR_HIP, "k_gonio_hist launch");
+	nx.go_hist_cur = e->pos.go_hist_cur ^ 1;
+	return MTR_OK;
+}
+
+// With a factor above 1 the blob carries one more section, behind every older one: a stream's history row, and in the two words behind its
+// 23 frames the factor.  An engine takes a blob of its own factor only.  (At factor 1 there is no section and the blob is what it was.)
+typedef struct mtr_gonio_os_hdr { uint32_t factor, zero; } mtr_gonio_os_hdr;
+static_assert (OS_HALO * 2 * sizeof (float) + sizeof (mtr_gonio_os_hdr) == OS_HROW * sizeof (float), "mtr_gonio_os_hdr");
+
+static void gonio_os_sections (const mtr_engine* e, std::vector<StateSection>& v)
+{
+	if (e->go.os > 1) v.push_back ({ e->go.os_hist[e->pos.go_hist_cur].p, OS_HROW * sizeof (float) });
+}
+
+constexpr const char* GONIO_OS_CORRUPT = "mtr_engine_state_import: corrupt blob (oversampling of the goniometer)";
+
+static void gonio_os_hdr_write (const mtr_engine* e, void* out) { *static_cast<mtr_gonio_os_hdr*> (out) = { e->go.os, 0 }; }
+
+static int gonio_os_hdr_check (const mtr_engine* e, const void* in, bool)
+{
+	const mtr_gonio_os_hdr& h = *static_cast<const mtr_gonio_os_hdr*> (in);
+	if (h.factor < 2 || h.factor > MTR_GONIO_OS_MAX || h.zero) return fail (MTR_ERR_STATE, GONIO_OS_CORRUPT);
+	if (h.factor != e->go.os) return fail (MTR_ERR_STATE, "mtr_engine_state_import: the blob's goniometer oversamples by another factor");
+	return MTR_OK;
+}
+
+static void gonio_os_hdr_take (mtr_engine*, const void*) {}
+
+static constinit BlobHeader gonio_os_hdr = { OS_HALO * 2 * sizeof (float), sizeof (mtr_gonio_os_hdr), GONIO_OS_CORRUPT, gonio_os_hdr_write, gonio_os_hdr_check, gonio_os_hdr_take };
+// (no create and no reset: the meter's first row does both)
+constinit SideMeter gonio_os_meter = { MTR_METER_GONIO, 0, nullptr, nullptr, nullptr, gonio_os_step, gonio_os_sections, &gonio_os_hdr };
+
 constinit SideMeter gonio_meter = { MTR_METER_GONIO, 0, nullptr, gonio_create, mtr_engine_gonio_reset, gonio_step, gonio_sections, &gonio_hdr, nullptr, gonio_count, 4, gonio_ends_fill };
 
 extern "C" {
@@ -677,9 +896,13 @@ int mtr_engine_gonio_reset (mtr_engine* e)
 	HIPCHK (hipMemset (e->go.state.p, 0, (size_t) S * e->go.pitch));
 	HIPCHK (gonio_states (e, 0, S, h.data (), true));
 	if (e->go.series.n) HIPCHK (hipMemset (e->go.series.p, 0, e->go.series.n * sizeof (float)));
+	if (e->go.os > 1)                                                  // (the input history: zeros in front of the stream, as setup_src primes the resampler)
+		for (auto& h : e->go.os_hist) HIPCHK (hipMemset (h.p, 0, (size_t) S * OS_HROW * sizeof (float)));
 	e->pos.go = {};
+	e->pos.go_hist_cur = 0;
 	e->go.updates.assign (S, 0);
 	e->go.ev.clear ();
+	e->go.os_ev.clear ();
 	return MTR_OK;
 }
 
@@ -690,8 +913,9 @@ int mtr_engine_gonio_configure (mtr_engine* e, const mtr_gonio_config* cfg)
 	mtr_gonio_derived d;
 	int rc = gonio_resolve (cfg, (double) e->cfg.sample_rate, &c, &d);
 	if (rc) return rc;
+	if (e->go.os > 1 && (double) c.period_frames > floor ((double) e->cfg.sample_rate)) return fail (MTR_ERR_ARG, GONIO_OS_PERIOD);
 	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_gonio_configure: only on an engine that has processed nothing since create / reset");
-	if ((rc = wait_stream (e)) || (rc = gonio_apply (e, c, d))) return rc;
+	if ((rc = wait_stream (e)) || (rc = gonio_apply (e, c, d)) || (rc = gonio_os_apply (e, e->go.os))) return rc;   // (the factor stays)
 	return mtr_engine_gonio_reset (e);
 }
 
@@ -815,6 +1039,57 @@ int mtr_engine_gonio_image_clear (mtr_engine* e)
 	for (auto& v : h) v.drawn = v.clipped = v.skipped = 0;
 	HIPCHK (gonio_states (e, 0, S, h.data (), true));
 	HIPCHK (hipMemset2D (e->go.state.p + sizeof (mtr_gonio_state), e->go.pitch, 0, e->go.pitch - sizeof (mtr_gonio_state), S));
+	return MTR_OK;
+}
+
+int mtr_gonio_os_table (uint32_t factor, float* out)
+{
+	if (!out || factor < 2 || factor > MTR_GONIO_OS_MAX) return fail (MTR_ERR_ARG, "mtr_gonio_os_table: a factor of 2 .. 32 and a table");
+	gonio_os_table (factor, out);
+	return MTR_OK;
+}
+
+int mtr_gonio_os_hpw (double rate, uint32_t factor, float* hpw)
+{
+	if (!hpw || factor < 1 || factor > MTR_GONIO_OS_MAX || !(rate >= 8000.0)) return fail (MTR_ERR_ARG, "mtr_gonio_os_hpw: a factor of 1 .. 32, rate >= 8000");
+	*hpw = gonio_os_hpw (rate, factor);
+	return MTR_OK;
+}
+
+int mtr_engine_gonio_set_oversample (mtr_engine* e, uint32_t factor)
+{
+	if (no_gonio (e)) return fail (MTR_ERR_ARG, NO_GONIO);
+	if (factor < 1 || factor > MTR_GONIO_OS_MAX) return fail (MTR_ERR_ARG, "mtr_engine_gonio_set_oversample: the factor is 1 (off) or 2 .. 32");
+	if (factor > 1 && (double) e->go.cfg.period_frames > floor ((double) e->cfg.sample_rate)) return fail (MTR_ERR_ARG, GONIO_OS_PERIOD);
+	if (e->advanced) return fail (MTR_ERR_STATE, "mtr_engine_gonio_set_oversample: only on an engine that has processed nothing since create / reset");
+	int rc = wait_stream (e);
+	if (rc || (rc = gonio_os_apply (e, factor))) return rc;
+	return mtr_engine_gonio_reset (e);
+}
+
+int mtr_engine_gonio_oversample (mtr_engine* e, uint32_t* factor, float* hpw)
+{
+	if (no_gonio (e)) return fail (MTR_ERR_ARG, NO_GONIO);
+	if (factor) *factor = e->go.os;
+	if (hpw) *hpw = e->go.os > 1 ? e->go.os_hpw : e->go.der.hpw;
+	return MTR_OK;
+}
+
+int mtr_engine_gonio_os_timing (mtr_engine* e, float* os_ms, uint32_t* pieces)
+{
+	if (no_gonio (e)) return fail (MTR_ERR_ARG, NO_GONIO);
+	int rc = wait_stream (e);
+	if (rc) return rc;
+	float t = 0.f;
+	const size_t n = e->go.os_ev.size () / 2;
+	for (size_t i = 0; i < n; ++i) {
+		float x = 0.f;
+		HIPCHK (hipEventElapsedTime (&x, e->go.os_ev[2 * i].v, e->go.os_ev[2 * i + 1].v));
+		t += x;
+	}
+	e->go.os_ev.clear ();
+	if (os_ms) *os_ms = t;
+	if (pieces) *pieces = (uint32_t) n;
 	return MTR_OK;
 }
 

@@ -249,6 +249,12 @@ def _load():
         L.mtr_gonio_cut.argtypes = [u64, u32, C.c_double, u64, u64, C.POINTER(GonioConfig), C.POINTER(u64), C.POINTER(u32), C.POINTER(u64),
                                     C.POINTER(f32)]
         L.mtr_engine_gonio_points.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "mtr_engine_gonio_set_oversample"):          # (an addition inside ABI version 2: the goniometer's oversampling)
+        L.mtr_gonio_os_table.argtypes = [u32, vp]
+        L.mtr_gonio_os_hpw.argtypes = [C.c_double, u32, C.POINTER(f32)]
+        L.mtr_engine_gonio_set_oversample.argtypes = [vp, u32]
+        L.mtr_engine_gonio_oversample.argtypes = [vp, C.POINTER(u32), C.POINTER(f32)]
+        L.mtr_engine_gonio_os_timing.argtypes = [vp, C.POINTER(f32), C.POINTER(u32)]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -391,6 +397,28 @@ def gonio_derive(rate, config=None, **kw):
     d = GonioDerived()
     _check(lib.mtr_gonio_derive(C.byref(c), float(rate), C.byref(d)), "mtr_gonio_derive")
     return d
+
+
+def _need_gonio_os():
+    if not hasattr(lib, "mtr_engine_gonio_set_oversample"):
+        raise EngineError(f"{lib_path} has no oversampling for the goniometer: rebuild it")
+
+
+def gonio_os_table(factor):
+    """float32 [factor + 1, 12]: the interpolator's table for a factor of 2 .. 32, Resampler_table's _ctab (mtr_gonio_os_table; no engine,
+    no device)."""
+    _need_gonio_os()
+    tab = np.zeros((max(int(factor), 0) + 1, 12), np.float32)
+    _check(lib.mtr_gonio_os_table(int(factor), tab.ctypes.data), "mtr_gonio_os_table")
+    return tab
+
+
+def gonio_os_hpw(rate, factor):
+    """the hpw the chain runs on at `rate` with `factor` (1 .. 32), a float32 (mtr_gonio_os_hpw; no engine, no device)."""
+    _need_gonio_os()
+    h = C.c_float()
+    _check(lib.mtr_gonio_os_hpw(float(rate), int(factor), C.byref(h)), "mtr_gonio_os_hpw")
+    return np.float32(h.value)
 
 
 def _need_gonio_ends():
@@ -1299,6 +1327,25 @@ class Engine:
         up, pt = np.zeros(count, np.uint64), np.zeros(count, np.uint64)
         _check(lib.mtr_engine_gonio_points(self._h, first, count, up.ctypes.data, pt.ctypes.data), "gonio_points")
         return up, pt
+
+    def gonio_set_oversample(self, factor):
+        """factor 1 (off) or 2 .. 32: the reference's "Oversampling" preference.  Only before the first process call; resets the meter."""
+        _need_gonio_os()
+        _check(lib.mtr_engine_gonio_set_oversample(self._h, int(factor)), "gonio_set_oversample")
+
+    def gonio_oversample(self):
+        """(factor, hpw float32): what is set, and the hpw the chain runs on"""
+        _need_gonio_os()
+        f, h = C.c_uint32(), C.c_float()
+        _check(lib.mtr_engine_gonio_oversample(self._h, C.byref(f), C.byref(h)), "gonio_oversample")
+        return f.value, np.float32(h.value)
+
+    def gonio_os_timing(self):
+        """(k_gonio_os ms, pieces) summed since the last query of this getter, while gonio_timing is on"""
+        _need_gonio_os()
+        t, n = C.c_float(), C.c_uint32()
+        _check(lib.mtr_engine_gonio_os_timing(self._h, C.byref(t), C.byref(n)), "gonio_os_timing")
+        return t.value, n.value
 
     def gonio_image_clear(self):
         _need_gonio()

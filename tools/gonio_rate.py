@@ -15,6 +15,12 @@ five forms on the same buffer in rotating order, each from a reset engine, devic
 call with every stream open; (c) every end at a quarter of the call, next to (d) the dense call of that quarter; (e) lengths uniform in
 [0, 10 s] — with the chunks of 128 frames each form must walk (16 lanes share a wave's loop: a workgroup walks up to its last cut).
 
+    python tools/gonio_rate.py --oversample [F] [reps] [tune_piece]
+what the oversampling (mtr_engine_gonio_set_oversample: k_gonio_os in front of the two kernels, which then walk F points per frame) costs,
+auto gain on, shift 2: the call at factor 1, 2 and F (4) on the same buffer in rotating order, each from a reset engine — device events
+around the call, and around every launch for the three kernels apart (mtr_engine_gonio_timing, mtr_engine_gonio_os_timing) — with the
+bytes each kernel moves and the rate that implies.
+
     python tools/gonio_rate.py --pairs [N] [reps] [tune_piece]
 the dense call of this build against the parent's library (tools/build_ab.sh -> meters.lv2_amd/lib_ab): N pairs of child processes
 alternating on the same box (--dense, with MTR_LIB naming the library), a table row per child.
@@ -187,6 +193,57 @@ def ends(reps, piece):
         print("%s: k_gonio_points %.3f ms, k_gonio_image %.3f ms (medians of 3, summed over the call's pieces)" % (NAMES[k], v[0], v[1]), flush=True)
 
 
+def oversample(top, reps, piece):
+    """the auto-gain 94 x 94 call at factor 1, 2 and `top`, taking turns on one buffer in rotating order, each from a reset engine"""
+    buf = buffer()
+    st = torch.cuda.current_stream().cuda_stream
+    piece = piece or 4096
+    factors = sorted({1, 2, top})
+    engines = {}
+    for f in factors:
+        e = M.Engine(S, FS, M.METER_GONIO)
+        e.gonio_configure(tune_piece=piece, **ENDS_CFG)
+        e.gonio_set_oversample(f)
+        e.gonio_timing(True)
+        e.timing_enable(True)
+        engines[f] = e
+    whole, parts = {f: [] for f in factors}, {f: [] for f in factors}
+    for it in range(WARM + reps):
+        r = it % len(factors)
+        for f in factors[r:] + factors[:r]:
+            e = engines[f]
+            e.reset()
+            e.process_device(buf.data_ptr(), T, T, st)
+            e.sync()
+            ms = e.timing_calls()
+            p, i, n = e.gonio_timing(True)
+            o = e.gonio_os_timing()[0]
+            if it >= WARM:
+                whole[f].append(float(ms[-1, 3]))
+                parts[f].append((o, p, i))
+    print("GONIO auto gain, shift 2, tune_piece %d: %d streams x %d s, %d turns after %d warm ones, rotating order; ms: median (min - max)"
+          % (piece, S, T // int(FS), reps, WARM))
+    print("| factor | input frames per piece | whole call | k_gonio_os | k_gonio_points | k_gonio_image | k_gonio_os / k_gonio_points |\n|---|---|---|---|---|---|---|")
+    med = {}
+    for f in factors:
+        v = np.asarray(parts[f])
+        m = np.median(v, axis=0)
+        med[f] = (float(np.median(whole[f])), *[float(t) for t in m])
+        cell = lambda a: "%.2f (%.2f - %.2f)" % (np.median(a), np.min(a), np.max(a))   # noqa: E731
+        print("| %d | %d | %s | %s | %s | %s | %.3f |" % (f, piece // f, cell(whole[f]), cell(v[:, 0]), cell(v[:, 1]), cell(v[:, 2]), m[0] / m[1]), flush=True)
+    audio = S * T * 8
+    for f in factors:
+        w, o, p, i = med[f]
+        pts = audio * f
+        print("factor %d: k_gonio_points %.2f x its factor-1 time (%.1f ns per point and stream-lane)" % (f, p / med[1][2], p * 1e6 / (T * f)), flush=True)
+        if f > 1:
+            print("  k_gonio_os reads %.2f GB of audio (+ %.0f %% halo) and writes %.2f GB of points: %.2f TB/s; k_gonio_points reads them back (%.2f TB/s) and"
+                  " writes %.2f GB of cell codes; k_gonio_image reads those" % (audio / 1e9, 100.0 * 23 / 128, pts / 1e9, (audio * (1 + 23 / 128) + pts) / o / 1e9,
+                                                                               pts / p / 1e9, S * T * f * 2 / 1e9), flush=True)
+    for e in engines.values():
+        e.close()
+
+
 def dense(reps, piece):
     """the dense call alone, of whichever library MTR_LIB names: one table row"""
     buf = buffer()
@@ -225,12 +282,14 @@ def pairs(n, reps, piece):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    mode = args.pop(0) if args and args[0] in ("--ends", "--pairs", "--dense") else None
+    mode = args.pop(0) if args and args[0] in ("--ends", "--pairs", "--dense", "--oversample") else None
     num = [int(v) for v in args]
     if mode == "--ends":
         ends(num[0] if num else 7, num[1] if len(num) > 1 else 0)
     elif mode == "--pairs":
         pairs(num[0] if num else 3, num[1] if len(num) > 1 else 7, num[2] if len(num) > 2 else 0)
+    elif mode == "--oversample":
+        oversample(num[0] if num else 4, num[1] if len(num) > 1 else 7, num[2] if len(num) > 2 else 0)
     elif mode == "--dense":
         dense(num[0] if num else 7, num[1] if len(num) > 1 else 0)
     else:
