@@ -5,7 +5,11 @@ gui/stereoscope.c:705-741 and gui/phasewheel.c:1307-1339.
 The reference's FFT is fftw3f, which the test machines do not have: the transform here is numpy's float64 DFT of the f32 windowed
 frames.  Everything around it is written in the reference's types: the window as ft_gen_window makes it (double arithmetic, stored
 f32), the windowed frame an f32 product, power and phase f32 from the f32-rounded spectrum, thresholds and smoothers with the
-double intermediates C's promotions give them."""
+double intermediates C's promotions give them.
+
+Behind it: the mirror of k_scope's own transform (mirror_fft, mirror_powers) — the kernel's passes on the kernel's slots in numpy.  In
+complex128 it shows that the pass structure as written is the DFT; in complex64 it is the yardstick for eps (W): what f32 arithmetic in
+this order costs, measured without the kernel (tests/test_scope_cpu.py)."""
 import math
 
 import numpy as np
@@ -131,3 +135,82 @@ def ratios(x, W, H, win=None):
         nmax[0] = max(nmax[0], sc.N)
     run(x, W, H, win=win, each=each)
     return rho, nmax[0]
+
+
+# ---- the mirror of k_scope's transform (mtr_scope.hip): the same passes on the same slots, in numpy ------------------------------------
+
+def bitrev(W):
+    """bitrev (k) over log2 W bits for k = 0 .. W - 1"""
+    L = W.bit_length() - 1
+    k, r = np.arange(W), np.zeros(W, np.int64)
+    for b in range(L):
+        r |= ((k >> b) & 1) << (L - 1 - b)
+    return r
+
+
+def twiddles(W, ctype=np.complex128):
+    """exp (-2 pi i m / W), m = 0 .. W - 1, as mtr_engine_scope_configure makes them: cos and -sin in double; complex64: each rounded once"""
+    ph = 2.0 * math.pi * np.arange(W).astype(np.float64) / float(W)
+    tw = np.empty(W, ctype)
+    tw.real, tw.imag = np.cos(ph), -np.sin(ph)                                     # (the assignment rounds to the part's type)
+    return tw
+
+
+def _cmul(a, w):
+    """cmul of mtr_scope.hip: four products, one difference, one sum, each rounded in the part's type (no fused multiply-add)"""
+    y = np.empty_like(a)
+    y.real = a.real * w.real - a.imag * w.imag
+    y.imag = a.real * w.imag + a.imag * w.real
+    return y
+
+
+def mirror_fft(z, ctype=np.complex128):
+    """The forward DFT of z [..., W] by the kernel's own pass structure, every operation in ctype: in place, decimation in frequency,
+    radix-4 passes for ln = LOGW, LOGW - 2, .. >= 2 — butterfly bf of a pass has jj = bf & (q - 1), base = ((bf >> (ln - 2)) << ln) + jj,
+    works on base + {0, q, 2q, 3q} (q = 2^ln / 4) and multiplies y1, y2, y3 by tw [2m], tw [m], tw [3m] at m = jj << (LOGW - ln) — then one
+    radix-2 pass where LOGW is odd; X [k] ends at slot bitrev (k).  The lane remap of ln = 3 .. 5 is kept: it must visit every butterfly
+    of the pass once."""
+    W = z.shape[-1]
+    L = W.bit_length() - 1
+    assert 1 << L == W and L >= 2
+    z = np.array(z, ctype)
+    tw = twiddles(W, ctype)
+    b0 = np.arange(W // 4)
+    for ln in range(L, 1, -2):
+        q = 1 << (ln - 2)
+        bf = ((b0 & ((1 << (L - ln)) - 1)) << (ln - 2)) + (b0 >> (L - ln)) if 3 <= ln <= 5 else b0
+        assert np.array_equal(np.sort(bf), b0)
+        jj = bf & (q - 1)
+        base = ((bf >> (ln - 2)) << ln) + jj
+        a0, a1, a2, a3 = z[..., base], z[..., base + q], z[..., base + 2 * q], z[..., base + 3 * q]
+        t0, t1, u, d = a0 + a2, a1 + a3, a0 - a2, a1 - a3
+        v = np.empty_like(d)
+        v.real, v.imag = d.imag, -d.real                                           # -i (a1 - a3)
+        y0, y1, y2, y3 = t0 + t1, t0 - t1, u + v, u - v
+        if ln > 2:
+            m = jj << (L - ln)
+            y1, y2, y3 = _cmul(y1, tw[2 * m]), _cmul(y2, tw[m]), _cmul(y3, tw[3 * m])
+        z[..., base], z[..., base + q], z[..., base + 2 * q], z[..., base + 3 * q] = y0, y1, y2, y3
+    if L & 1:
+        e = 2 * np.arange(W // 2)
+        a0, a1 = z[..., e], z[..., e + 1]
+        z[..., e], z[..., e + 1] = a0 + a1, a0 - a1
+    return z[..., bitrev(W)]
+
+
+def mirror_powers(fw, ctype=np.complex64):
+    """the windowed frames fw [W, 2] f32 -> the two powers [2, B] as the kernel makes them: ONE transform of L + iR, the even / odd
+    split and ft_analyze's power in the part's type (bin_of); bins 0 and B - 1 zero, as they are never written"""
+    W = fw.shape[0]
+    B = W // 2
+    z = np.empty(W, ctype)
+    z.real, z.imag = fw[:, 0], fw[:, 1]
+    Z = mirror_fft(z, ctype)
+    i = np.arange(1, B - 1)
+    zi, zc = Z[i], Z[W - i]
+    h = zi.real.dtype.type(.5)
+    lre, lim = h * (zi.real + zc.real), h * (zi.imag - zc.imag)
+    rre, rim = h * (zi.imag + zc.imag), h * (zc.real - zi.real)
+    p = np.zeros((2, B), zi.real.dtype)
+    p[0, 1:B - 1], p[1, 1:B - 1] = lre * lre + lim * lim, rre * rre + rim * rim
+    return p

@@ -4,7 +4,9 @@ of k_scope, mtr_scope.hip).
 The yardstick is exact.  Every analysis is a function of its W frames and the carried state alone, so stream s of a batch whose streams
 end at their own frames must be — bit for bit, in all seven arrays of scope_read and in every point of the series — what an engine of ONE
 stream gives that was fed exactly that stream's own frames through plain process_device in the same cuts: the dense kernel, which
-tests/test_gpu_scope.py holds against the restatement of tests/_scope.py.
+tests/test_gpu_scope.py holds against the restatement of tests/_scope.py — the float64 DFT — at every one of the seven windows, so an
+ENDS kernel (SHAPES: every window) and a series + ends kernel (test_series_rows_are_the_streams_own_points_then_zeros: every window) that
+equal it bit for bit are held to the DFT with it.
 
 S = 6 streams, three calls: 3 H + 5 frames whole; n2 = 4 H + 1 frames through _any with the ends below; H + 9 frames through plain
 process_device.  With first = H - 5 — the call-2 frame at which its first analysis ends — the ends are
@@ -21,7 +23,8 @@ import _scope
 
 pytestmark = pytest.mark.gpu
 FS, S = 48000, 6
-SHAPES = [(256, 777), (1024, 1920), (8192, 4096)]                      # H > W, H > W by less than 2 (H ~ W), H < W with the LDS attribute path
+# H > W, H > W by less than 2 (H ~ W), H < W with the LDS attribute path; then the other four windows: every ENDS kernel is launched
+SHAPES = [(256, 777), (1024, 1920), (8192, 4096), (512, 777), (2048, 1920), (4096, 777), (16384, 4096)]
 NAMES = ("level", "lr", "phase", "plevel", "peak", "power_l", "power_r")
 ERR_ARG, ERR_UNSUPPORTED = -1, -2
 
@@ -228,10 +231,11 @@ def test_whole_streams_are_the_dense_call(M):
 
 # ---- the series ----------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("K,cap", [(1, 16), (2, 2)])
-def test_series_rows_are_the_streams_own_points_then_zeros(M, K, cap):
-    W, H = 1024, 1920
-    ref = alone(W, H, K, cap)
+# (1, 16) at every window — the series + ends kernel of each; the two cases at W = 1024 keep the names they had
+@pytest.mark.parametrize("W,H,K,cap", [pytest.param(1024, 1920, 1, 16, id="1-16"), pytest.param(1024, 1920, 2, 2, id="2-2")]
+                         + [(W, H, 1, 16) for W, H in SHAPES if W != 1024])
+def test_series_rows_are_the_streams_own_points_then_zeros(M, W, H, K, cap):
+    ref, dense = alone(W, H, K, cap), alone(W, H)                      # (one-stream engines: the series kernel, the dense kernel)
     e, mid, (an2, pt2), _ = run_batch(M, W, H, K, cap, reset_first=True)
     got, n, d = e.scope_series()
     total = 8 // K                                                      # the open stream's: lock-step
@@ -245,6 +249,7 @@ def test_series_rows_are_the_streams_own_points_then_zeros(M, K, cap):
             assert same(got[name][s, :own], ref[s]["series"][name][0, :own]), (s, name)
             assert (bits(got[name][s, own:]) == 0).all(), (s, name)     # 0.0f behind a closed stream's own points
             assert same(mid[name][s], ref[s]["after2"][name][0]), (s, name)
+            assert same(mid[name][s], dense[s]["after2"][name][0]), (s, name)
     assert an.tolist() == [8, 3, 3, 4, 6, 7] and pt.tolist() == [v // K for v in (8, 3, 3, 4, 6, 7)]
     if K == 2:
         assert d == 2 and (pt > cap).any() and (pt < cap).any()

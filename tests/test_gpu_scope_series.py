@@ -3,8 +3,8 @@ instantiation of k_scope, mtr_scope.hip).
 
 The yardstick is the engine WITHOUT a series, whose kernel is the one tests/test_gpu_scope.py holds against the restatement of
 tests/_scope.py: point n of a series of one point per K analyses is, bit for bit and in all seven fields — bins 0 and B - 1 included —
-what scope_read of a series-off engine answers after exactly (n + 1) K H frames, however the calls cut the audio.  One case holds the
-points against the restatement itself, to the tolerances tests/test_gpu_scope.py states.  S = 5 streams, its signals and seeds
+what scope_read of a series-off engine answers after exactly (n + 1) K H frames, however the calls cut the audio.  Two cases (an even and an odd log2 W) hold
+the points against the restatement itself, to the tolerances tests/test_gpu_scope.py states.  S = 5 streams, its signals and seeds
 (13 analyses and 5 frames), buffer rows longer than T with NaN in the gap."""
 import ctypes as C
 import functools
@@ -117,9 +117,11 @@ def raw(M, e, capacity, names, first=0, count=S):
 
 # ---- against the engine without a series, bit for bit -----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("K", [1, 3, 5])
-@pytest.mark.parametrize("hk", ["777", "default"])
-@pytest.mark.parametrize("W", [256, 1024, 16384])
+# every window: 256, 1024 and 16384 at both hops and K = 1, 3, 5; the others — an odd log2 W, or the r loops at 1 and 4 trips — at H 777, K 3
+POINT_CASES = [(W, hk, K) for W in (256, 1024, 16384) for hk in ("777", "default") for K in (1, 3, 5)] + [(W, "777", 3) for W in (512, 2048, 4096, 8192)]
+
+
+@pytest.mark.parametrize("W,hk,K", POINT_CASES)
 def test_points_are_what_scope_read_would_answer(M, W, hk, K):
     H, B = tg.hop_of(W, hk), W // 2
     snaps, final = snapshots(W, H)
@@ -140,13 +142,13 @@ def test_points_are_what_scope_read_would_answer(M, W, hk, K):
 
 # ---- against the restatement ---------------------------------------------------------------------------------------------------------
 
-def test_points_against_the_restatement(M):
-    """W 1024 at the default hop, K = 3: every point to the tolerances of tests/test_gpu_scope.py — sqrt power to eps N; level, plevel and
-    peak to 4 eps max N^2; lr to 4 eps rho on the bins with rho <= 1 / LR_FLOOR (at most 1 % of a stream's bins outside); phase to
+@pytest.mark.parametrize("W,H,K", [(1024, DEFAULT, 3), (2048, DEFAULT, 3)])
+def test_points_against_the_restatement(M, W, H, K):
+    """W 1024 and W 2048 — a series kernel with an odd log2 W — at the default hop, K = 3: every point to the tolerances of
+    tests/test_gpu_scope.py — sqrt power to eps N; level, plevel and peak to 4 eps max N^2; lr to 4 eps rho on the bins with rho <= 1 / LR_FLOOR (at most 1 % of a stream's bins outside); phase to
     |wrap (delta)| min |X| <= 4 eps N above the threshold, 0 / -100 exactly below it, bins within 1e-4 of it left out (at most 0.1 %) —
     with N, max N and rho taken over the analyses up to the point's own."""
-    W, H, K = 1024, DEFAULT, 3
-    B, x = W // 2, tg.signal_of(1024, DEFAULT)
+    B, x = W // 2, tg.signal_of(W, H)
     got, n, d, _ = run_series(M, W, H, K)
     assert (n, d) == (NA // K, 0)
     eps, win = _scope.eps(W), _scope.window(W)

@@ -1,7 +1,8 @@
 """MTR_METER_SCOPE (the stereoscope's and the phase wheel's FFT analysis for a batch) without a GPU: the header and the symbols, what
 mtr_engine_create accepts, the NULL-engine answers, the window bit for bit, and the restatement of tests/_scope.py — the GPU tests'
 yardstick — checked against what it must give on a sine and on silence, and for how many bins of the GPU tests' signals its bound on
-the balance is stated at all."""
+the balance is stated at all; the numpy mirror of the kernel's passes against the DFT and against eps (W); and the census of the windows
+the GPU modules run."""
 import ctypes as C
 import os
 import re
@@ -89,7 +90,7 @@ def test_window_bit_for_bit(M):
     assert (out == 7).all()
 
 
-@pytest.mark.parametrize("W", [256, 1024, 16384])
+@pytest.mark.parametrize("W", _scope.WINDOWS)
 def test_a_sine_at_a_bin_centre_reads_its_amplitude(W):
     """the meaning of the 2 / sum normalisation: power = A^2 at the sine's bin, to 1e-5"""
     A, k = 0.3, W // 8 + 3
@@ -135,3 +136,47 @@ def test_how_many_bins_the_bounds_cover():
             out = float(np.mean(rho * tg.LR_FLOOR > 1))
             print(f"W {W} H {H} stream {s}: {100 * out:.3f} % of the bins below {tg.LR_FLOOR} N (below 1e-3 N: {100 * float(np.mean(rho > 1e3)):.2f} %)")
             assert out <= 0.01, (W, H, s, out)
+    assert len(tg.CASES) == 21
+
+
+@pytest.mark.parametrize("W", _scope.WINDOWS)
+def test_the_mirror_of_the_kernels_passes(W):
+    """_scope.mirror_fft restates k_scope's pass structure (radix-4 passes, the lane remap, the radix-2 pass of an odd log2 W, X [k] at
+    slot bitrev (k)).  In complex128 it is the DFT: to 1e-13 of the norm.  In complex64, with the twiddles rounded once from double as the
+    host makes them, it is what the kernel computes up to the device's contraction of cmul — and the yardstick for eps (W): on the
+    signals of the GPU tests' CASES its |sqrt p - sqrt p64| / N must stay under the bound the kernel is held to."""
+    import test_gpu_scope as tg
+    rng = np.random.default_rng(300 + W)
+    z = rng.normal(0, 1, (3, W)) + 1j * rng.normal(0, 1, (3, W))
+    ref = np.fft.fft(z, axis=-1)
+    d128 = float(np.linalg.norm(_scope.mirror_fft(z) - ref) / np.linalg.norm(ref))
+    assert d128 <= 1e-13, (W, d128)
+    win, worst = _scope.window(W), 0.0
+    for hk in ("default", "quarter", "777"):
+        H = tg.hop_of(W, hk)
+        x = tg.signal_of(W, H)
+        for s in range(x.shape[0]):
+            fw = _scope.windowed(x[s], W, H, tg.NA - 1, win)
+            sc = _scope.Scope(W).analyse(fw)
+            p = _scope.mirror_powers(fw)
+            assert p.dtype == np.float32
+            worst = max(worst, float(np.max(np.abs(np.sqrt(p.astype(np.float64)) - np.sqrt(sc.p64)))) / sc.N)
+    print(f"W {W}: the mirror in complex128: {d128:.2e} of the norm; in complex64: largest |sqrt p - sqrt p64| = {worst:.3e} N = "
+          f"{worst / _scope.eps(W):.4f} of eps (W)")
+    assert worst <= _scope.eps(W), (W, worst)
+
+
+def test_every_window_is_run_by_every_scope_module(M):
+    """the census: the windows of test_gpu_scope.CASES, of the series module's POINT_CASES and of test_gpu_scope_any.SHAPES are each
+    exactly _scope.WINDOWS, and those are exactly the windows mtr_scope_window takes — an eighth window cannot arrive untested"""
+    import test_gpu_scope as tg
+    import test_gpu_scope_any as ta
+    import test_gpu_scope_series as ts
+    want = set(_scope.WINDOWS)
+    assert len(_scope.WINDOWS) == len(want) == 7
+    assert {W for W, _ in tg.CASES} == want
+    assert {W for W, _, _ in ts.POINT_CASES} == want
+    assert {W for W, _ in ta.SHAPES} == want
+    out = np.zeros(1 << 17, np.float32)
+    took = {W for W in range((1 << 17) + 1) if M.lib.mtr_scope_window(W, out.ctypes.data) == 0}
+    assert took == want
