@@ -511,7 +511,7 @@ static void bank_sections (const mtr_engine* e, std::vector<StateSection>& v)
 
 static SeriesView bank_series (mtr_engine* e) { return { &e->bank.ser, &Cursors::bk, &e->bank.points }; }
 
-constinit SideMeter bank_meter = { MTR_METER_SPECTR30, 0, nullptr, bank_create, bank_reset, bank_step, bank_sections, nullptr, bank_series };
+constinit SideMeter bank_meter = { .bits = MTR_METER_SPECTR30, .create = bank_create, .reset = bank_reset, .step = bank_step, .sections = bank_sections, .series = bank_series };
 
 // With a period the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): where the open block
 // stands.  All of an entry is its host-owned header — period, peak mode, the frames into the open block; the block's levels and filter states are
@@ -548,9 +548,9 @@ static void bank_hdr_take (mtr_engine* e, const void* in)
 	e->pos.bk.fill = h.fill;
 }
 
-static constinit BlobHeader bank_hdr = { 0, sizeof (mtr_bank_open), BANK_CORRUPT, bank_hdr_write, bank_hdr_check, bank_hdr_take };
+static constinit BlobHeader bank_hdr = { .offset = 0, .bytes = sizeof (mtr_bank_open), .corrupt = BANK_CORRUPT, .write = bank_hdr_write, .check = bank_hdr_check, .take = bank_hdr_take };
 // (no reset and no step: the meter's first row resets and queues all of it)
-constinit SideMeter bank_series_meter = { MTR_METER_SPECTR30, 0, nullptr, nullptr, nullptr, nullptr, bank_open_sections, &bank_hdr };
+constinit SideMeter bank_series_meter = { .bits = MTR_METER_SPECTR30, .sections = bank_open_sections, .hdr = &bank_hdr };
 
 // spectrumlv2.c:240-247 for n levels: the raw val_f / max_f and the dB values of ports 0-29 / 30-59 (any output may be null).  The stored val
 // carries the +1e-20f of :237; above the -100 dB floor (val > 5e-11) that addition does not change the float, so the port value is unaffected.

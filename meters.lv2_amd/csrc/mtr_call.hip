@@ -438,7 +438,7 @@ struct CallRun {
 		// (beside the true-peak bar a stream that ends inside the call leaves the frames in front of its OWN end; everywhere else a call with
 		// lengths leaves those in front of the call's end: the two rules of mtr_history.hip)
 		const HistCut cut = !d_ends ? HIST_CALL_END : e->layout != 8 && (e->cfg.meters & MTR_METER_TPBALLIST) ? HIST_OWN_END : HIST_CALL_END_IF_TOUCHED;
-		if ((e->layout != 8 || tp) && mtr_launch_history (cut, ha, c.st)) return fail (MTR_ERR_HIP, "k_history launch");
+		if ((e->layout != 8 || tp) && mtr_launch_history (cut, HIST_ROW_FIR, ha, c.st)) return fail (MTR_ERR_HIP, "k_history launch");
 		nx.hist_cur = e->pos.hist_cur ^ 1;
 		return MTR_OK;
 	}

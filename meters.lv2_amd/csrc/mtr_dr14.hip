@@ -254,7 +254,7 @@ static void dr14_sections (const mtr_engine* e, std::vector<StateSection>& v)
 	v.push_back ({ e->dr.hist.p, (size_t) e->cfg.n_channels * MTR_DR_HISTBINS * sizeof (uint32_t) });
 }
 
-constinit SideMeter dr14_meter = { MTR_METER_DR14, 0, nullptr, nullptr, mtr_engine_dr14_reset, dr14_step, dr14_sections, nullptr };
+constinit SideMeter dr14_meter = { .bits = MTR_METER_DR14, .reset = mtr_engine_dr14_reset, .step = dr14_step, .sections = dr14_sections };
 
 extern "C" {
 

@@ -1,5 +1,5 @@
 // mtr_gonio.hip — the goniometer (draw_rb, gui/goniometer.c:299-538: points mode, infinite persistence, no inflate; oversampling by 2 .. 32
-// as an option: k_gonio_os and k_gonio_hist, further down) for a batch: the M/S point image as counts per cell, the auto gain, a point per
+// as an option: k_gonio_os, further down, and k_history's 23-frame rows) for a batch: the M/S point image as counts per cell, the auto gain, a point per
 // display update (gfx950).
 //
 // Per frame (:401-449), all in f32 and in the reference's order — this file is compiled without FMA contraction and without fast-math,
@@ -399,8 +399,8 @@ constexpr uint32_t cells_of (uint32_t shift) { return (MTR_GONIO_BOUNDS + (1u <<
 // ---- oversampling (mtr_gonio_os.h): the Resampler in front of draw_rb (gui/goniometer.c:359-377; zita-resampler/resampler.cc:215-228) ----
 // With a factor f above 1 a piece is walked by three kernels: k_gonio_os writes the piece's n f points [S][n f][2] into the engine's
 // scratch, then k_gonio_points and k_gonio_image run on that scratch as on a call's buffer — audio = the scratch, stride = its pitch,
-// f0 = 0, with P f, fill f, n f and the oversampled hpw — and behind the call's last piece k_gonio_hist leaves every stream's last 23
-// input frames for the next call.
+// f0 = 0, with P f, fill f, n f and the oversampled hpw — and behind the call's last piece k_history (mtr_history.hip, HIST_ROW_GONIO:
+// gonio_os_step) leaves every stream's last 23 input frames for the next call.
 //   k_gonio_os    throughput work: every point is independent of every other.  A workgroup of 256 lanes takes a tile of OS_TILE input
 //                 frames of one stream: the table (pitch 13 dwords: the lanes of a wave read f different rows at the same tap, 13 is odd, so
 //                 up to 32 rows fall into different banks) and the tile with its 23-frame halo (from the call's buffer, or — in front of the
@@ -411,11 +411,8 @@ constexpr uint32_t cells_of (uint32_t shift) { return (MTR_GONIO_BOUNDS + (1u <<
 //                 ENDS: nothing at or behind a stream's cut is loaded or written (the interpolator is causal), and the first tile's first lane
 //                 leaves the cut REBASED to the piece's first point in os_cut[s] — which is what lets the ENDS instantiations of the two older
 //                 kernels run with f0 = 0 on the scratch, unchanged: they only ever compare the cut with f0 and f0 + n.
-//   k_gonio_hist  one lane per (stream, history frame), the cut rules of mtr_history.hip in one formula: the row's frame i takes call frame
-//                 end - 23 + i, end = the call's frames (a dense call) or the stream's own end (a call with ends; 0 — closed or untouched — keeps
-//                 the old row), a negative frame coming from the old row: calls shorter than 23 frames mix the two.  The rows ping-pong.
-constexpr int OS_TAPS = MTR_GONIO_OS_TAPS, OS_HALO = 2 * OS_TAPS - 1, OS_TILE = 128, OS_TPITCH = OS_TAPS + 1;
-constexpr int OS_HROW = 48;                      // floats of a history row: [23][2], then the blob's header (mtr_gonio_os_hdr), on 16 bytes
+// (OS_HALO, the 23 frames, and OS_HROW, the floats of a history row: mtr_internal.h — k_history's instantiations are made of them)
+constexpr int OS_TAPS = MTR_GONIO_OS_TAPS, OS_TILE = 128, OS_TPITCH = OS_TAPS + 1;
 
 typedef struct mtr_gonio_os_args {
 	const float*    audio;       /* [S][stride][2] */
@@ -474,62 +471,25 @@ __global__ __launch_bounds__ (256) void k_gonio_os (const mtr_gonio_os_args a)
 	}
 }
 
-typedef struct mtr_gonio_hist_args {
-	const float*    audio;       /* [S][stride][2] */
-	uint64_t        stride, n_frames;
-	uint32_t        n_streams;
-	const uint32_t* ends;        /* [S] the call frame at which the stream ends (0: closed, untouched), or null: a dense call */
-	const float*    hist_in;     /* [S][OS_HROW] */
-	float*          hist_out;
-} mtr_gonio_hist_args;
-
-__global__ void k_gonio_hist (const mtr_gonio_hist_args a)
-{
-	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-	if (g >= a.n_streams * (uint32_t) OS_HALO) return;
-	const uint32_t s = g / OS_HALO, i = g % OS_HALO;
-	const int64_t end = a.ends ? (int64_t) a.ends[s] : (int64_t) a.n_frames;
-	const int64_t f = (int64_t) i - OS_HALO + end;                       // < end <= n_frames <= stride
-	const float* const p = f >= 0 ? a.audio + ((uint64_t) s * a.stride + (uint64_t) f) * 2 : a.hist_in + (size_t) s * OS_HROW + (size_t) (OS_HALO + f) * 2;
-	float* const o = a.hist_out + (size_t) s * OS_HROW + 2 * (size_t) i;
-	o[0] = p[0]; o[1] = p[1];
-}
-
 }  // namespace
 
-static int mtr_launch_gonio (const mtr_gonio_args& a, bool autogain, hipStream_t st, hipEvent_t* ev)
+// a piece's two kernels.  A = mtr_gonio_ends_args: a call with per-stream ends, the ENDS instantiations on the same grids
+template <typename A>
+static int mtr_launch_gonio (const A& a, bool autogain, hipStream_t st, hipEvent_t* ev)
 {
+	constexpr bool ENDS = std::is_same_v<A, mtr_gonio_ends_args>;
 	const auto points = [&] (auto NS) {
 		const dim3 grid ((a.n_streams + NS.value - 1) / NS.value);
-		if (autogain) hipLaunchKernelGGL ((k_gonio_points<NS.value, true>), grid, dim3 (64), 0, st, a);
-		else hipLaunchKernelGGL ((k_gonio_points<NS.value, false>), grid, dim3 (64), 0, st, a);
+		if (autogain) hipLaunchKernelGGL ((k_gonio_points<NS.value, true, ENDS>), grid, dim3 (64), 0, st, a);
+		else hipLaunchKernelGGL ((k_gonio_points<NS.value, false, ENDS>), grid, dim3 (64), 0, st, a);
 	};
 	if (ev && hipEventRecord (ev[0], st) != hipSuccess) return -1;
 	if (a.n_streams >= 16384) points (std::integral_constant<int, 64> {}); else points (std::integral_constant<int, 16> {});
 	if (ev && hipEventRecord (ev[1], st) != hipSuccess) return -1;
 	const dim3 grid (a.n_streams);
-	if (a.shift == 1) hipLaunchKernelGGL ((k_gonio_image<cells_of (1), 1024>), grid, dim3 (1024), 0, st, a);
-	else if (a.shift == 2) hipLaunchKernelGGL ((k_gonio_image<cells_of (2), 256>), grid, dim3 (256), 0, st, a);
-	else hipLaunchKernelGGL ((k_gonio_image<cells_of (3), 256>), grid, dim3 (256), 0, st, a);
-	if (ev && hipEventRecord (ev[2], st) != hipSuccess) return -1;
-	return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-// a piece of a call with per-stream ends: the ENDS instantiations, the same grids
-static int mtr_launch_gonio_ends (const mtr_gonio_ends_args& a, bool autogain, hipStream_t st, hipEvent_t* ev)
-{
-	const auto points = [&] (auto NS) {
-		const dim3 grid ((a.n_streams + NS.value - 1) / NS.value);
-		if (autogain) hipLaunchKernelGGL ((k_gonio_points<NS.value, true, true>), grid, dim3 (64), 0, st, a);
-		else hipLaunchKernelGGL ((k_gonio_points<NS.value, false, true>), grid, dim3 (64), 0, st, a);
-	};
-	if (ev && hipEventRecord (ev[0], st) != hipSuccess) return -1;
-	if (a.n_streams >= 16384) points (std::integral_constant<int, 64> {}); else points (std::integral_constant<int, 16> {});
-	if (ev && hipEventRecord (ev[1], st) != hipSuccess) return -1;
-	const dim3 grid (a.n_streams);
-	if (a.shift == 1) hipLaunchKernelGGL ((k_gonio_image<cells_of (1), 1024, true>), grid, dim3 (1024), 0, st, a);
-	else if (a.shift == 2) hipLaunchKernelGGL ((k_gonio_image<cells_of (2), 256, true>), grid, dim3 (256), 0, st, a);
-	else hipLaunchKernelGGL ((k_gonio_image<cells_of (3), 256, true>), grid, dim3 (256), 0, st, a);
+	if (a.shift == 1) hipLaunchKernelGGL ((k_gonio_image<cells_of (1), 1024, ENDS>), grid, dim3 (1024), 0, st, a);
+	else if (a.shift == 2) hipLaunchKernelGGL ((k_gonio_image<cells_of (2), 256, ENDS>), grid, dim3 (256), 0, st, a);
+	else hipLaunchKernelGGL ((k_gonio_image<cells_of (3), 256, ENDS>), grid, dim3 (256), 0, st, a);
 	if (ev && hipEventRecord (ev[2], st) != hipSuccess) return -1;
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
@@ -792,7 +752,7 @@ static int gonio_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEn
 			o.f0 = f0; o.n = nf;
 			if (mtr_launch_gonio_os (o, se.ends != nullptr, c.st, tm ? oev : nullptr)) return fail (MTR_ERR_HIP, "k_gonio_os launch");
 		}
-		if (se.ends ? mtr_launch_gonio_ends (a, g.autogain != 0, c.st, tm ? ev : nullptr) : mtr_launch_gonio (a, g.autogain != 0, c.st, tm ? ev : nullptr))
+		if (se.ends ? mtr_launch_gonio (a, g.autogain != 0, c.st, tm ? ev : nullptr) : mtr_launch_gonio<mtr_gonio_args> (a, g.autogain != 0, c.st, tm ? ev : nullptr))
 			return fail (MTR_ERR_HIP, "k_gonio launch");
 		pos = series_advance (pos, P, nf);
 	}
@@ -825,19 +785,20 @@ static int gonio_hdr_check (const mtr_engine* e, const void* in, bool fresh)
 
 static void gonio_hdr_take (mtr_engine* e, const void* in) { e->pos.go.fill = static_cast<const mtr_gonio_hdr*> (in)->fill; }
 
-static constinit BlobHeader gonio_hdr = { 0, sizeof (mtr_gonio_hdr), GONIO_CORRUPT, gonio_hdr_write, gonio_hdr_check, gonio_hdr_take };
+static constinit BlobHeader gonio_hdr = { .offset = 0, .bytes = sizeof (mtr_gonio_hdr), .corrupt = GONIO_CORRUPT, .write = gonio_hdr_write, .check = gonio_hdr_check, .take = gonio_hdr_take };
 
 // ---- oversampling: the second row of the meter (SIDE_METERS): its step is the call's last kernel of the meter, its section the history ----
 static int gonio_os_step (mtr_engine* e, const Call& c, Cursors& nx, const StreamEnds& se)
 {
 	if (e->go.os <= 1) return MTR_OK;
-	mtr_gonio_hist_args h;
-	memset (&h, 0, sizeof (h));
+	mtr_history_args h = {};                                           // (no fold pointers: the row and nothing else)
 	h.audio = c.audio; h.stride = c.stride; h.n_frames = c.n_frames; h.n_streams = c.cnt; h.ends = se.ends;
+	h.C = h.FC = h.HC = 2;
 	h.hist_in = e->go.os_hist[e->pos.go_hist_cur].p + (size_t) c.off * OS_HROW;
 	h.hist_out = e->go.os_hist[e->pos.go_hist_cur ^ 1].p + (size_t) c.off * OS_HROW;
-	hipLaunchKernelGGL (k_gonio_hist, dim3 ((c.cnt * (uint32_t) OS_HALO + 255) / 256), dim3 (256), 0, c.st, h);
-	if (hipGetLastError () != hipSuccess) return fail (MTR_ERR_HIP, "k_gonio_hist launch");
+	// (a stream that ends inside the call leaves the frames in front of its OWN end — an open one's end is the call's length, end 0, closed
+	// or untouched, keeps the old row — so that its part of the state blob does not depend on what lies behind it)
+	if (mtr_launch_history (se.ends ? HIST_OWN_END : HIST_CALL_END, HIST_ROW_GONIO, h, c.st)) return fail (MTR_ERR_HIP, "k_history launch (GONIO)");
 	nx.go_hist_cur = e->pos.go_hist_cur ^ 1;
 	return MTR_OK;
 }
@@ -866,11 +827,13 @@ static int gonio_os_hdr_check (const mtr_engine* e, const void* in, bool)
 
 static void gonio_os_hdr_take (mtr_engine*, const void*) {}
 
-static constinit BlobHeader gonio_os_hdr = { OS_HALO * 2 * sizeof (float), sizeof (mtr_gonio_os_hdr), GONIO_OS_CORRUPT, gonio_os_hdr_write, gonio_os_hdr_check, gonio_os_hdr_take };
+static constinit BlobHeader gonio_os_hdr = { .offset = OS_HALO * 2 * sizeof (float), .bytes = sizeof (mtr_gonio_os_hdr), .corrupt = GONIO_OS_CORRUPT,
+                                             .write = gonio_os_hdr_write, .check = gonio_os_hdr_check, .take = gonio_os_hdr_take };
 // (no create and no reset: the meter's first row does both)
-constinit SideMeter gonio_os_meter = { MTR_METER_GONIO, 0, nullptr, nullptr, nullptr, gonio_os_step, gonio_os_sections, &gonio_os_hdr };
+constinit SideMeter gonio_os_meter = { .bits = MTR_METER_GONIO, .step = gonio_os_step, .sections = gonio_os_sections, .hdr = &gonio_os_hdr };
 
-constinit SideMeter gonio_meter = { MTR_METER_GONIO, 0, nullptr, gonio_create, mtr_engine_gonio_reset, gonio_step, gonio_sections, &gonio_hdr, nullptr, gonio_count, 4, gonio_ends_fill };
+constinit SideMeter gonio_meter = { .bits = MTR_METER_GONIO, .create = gonio_create, .reset = mtr_engine_gonio_reset, .step = gonio_step, .sections = gonio_sections,
+                                    .hdr = &gonio_hdr, .count = gonio_count, .ends_words = 4, .ends_fill = gonio_ends_fill };
 
 extern "C" {
 

@@ -216,16 +216,25 @@ int  mtr_launch_kwmc (int C, bool ebu, bool tp, const mtr_kwmc_args& a, const ui
 /* ... and for a 5-channel engine whose call's buffer holds WAVE 5.1 frames (a.audio: [S][stride][6], L R C LFE Ls Rs;
  * mtr_engine_set_frame_layout with 6, {0, 1, 2, 4, 5} on device f32): the kernel reads the wide frames itself */
 int  mtr_launch_kwmc51 (bool ebu, bool tp, const mtr_kwmc_args& a, const uint32_t* ends, uint32_t n_units, void* stream);
-/* The 47-frame interpolator history for the next call, the last step of a call (mtr_history.hip).  Which 47 frames a stream leaves: */
+/* The interpolator history for the next call, the last step of a call (mtr_history.hip).  Which frames a stream leaves: */
 enum HistCut {
 	HIST_CALL_END,             /* the frames in front of the call's end, every stream touched: the dense call */
 	HIST_CALL_END_IF_TOUCHED,  /* ... of a stream with ends [s] != 0, one that closes included (it keeps what follows its end); ends [s] == 0: its row stays */
 	HIST_OWN_END               /* the frames in front of the stream's OWN end, ends [s]; ends [s] == 0: its row stays */
 };
+/* ... and what a stream's row is: */
+enum HistRow {
+	HIST_ROW_FIR,              /* [47][HC]: the true-peak interpolator's (MTR_FIR_HALO) */
+	HIST_ROW_GONIO             /* OS_HROW floats: [OS_HALO][2], then two words k_history never writes (HC == 2; HIST_CALL_END and HIST_OWN_END only) */
+};
+/* the goniometer's oversampling (mtr_gonio.hip): frames of input history its 12-tap rows need, and the floats of a stream's history row —
+ * [23][2], then the two words of the state blob's header (mtr_gonio_os_hdr), on 16 bytes */
+constexpr int OS_HALO = 2 * MTR_GONIO_OS_TAPS - 1, OS_HROW = 48;
+static_assert (OS_HROW == 2 * OS_HALO + 2 && OS_HROW % 4 == 0, "OS_HROW: 2 * MTR_GONIO_OS_TAPS - 1 stereo frames and two header words");
 struct mtr_history_args {
 	const float*    audio;        /* [S][stride][FC] */
 	uint64_t        stride, n_frames;
-	const float*    hist_in;      /* [S][47][HC]: what the call read */
+	const float*    hist_in;      /* [S][47][HC] (HIST_ROW_GONIO: [S][OS_HROW]): what the call read */
 	float*          hist_out;     /* ... and what the next one reads (the buffers ping-pong: a row that stays is copied across) */
 	uint32_t        n_streams;
 	const uint32_t* ends;         /* [S] frames of stream s in this call (<= n_frames; 0: untouched, not folded either), NULL: HIST_CALL_END */
@@ -237,8 +246,8 @@ struct mtr_history_args {
 	float*          tp_hold;
 	mtr_stream_state* state;      /* [S] */
 };
-/* -1: an ends rule without ends, C outside 1 .. 5, FC neither C nor 6 with C == 5 */
-int  mtr_launch_history (HistCut cut, const mtr_history_args& a, void* stream);
+/* -1: an ends rule without ends, C outside 1 .. 5, FC neither C nor 6 with C == 5; HIST_ROW_GONIO with HC != 2 or HIST_CALL_END_IF_TOUCHED */
+int  mtr_launch_history (HistCut cut, HistRow row, const mtr_history_args& a, void* stream);
 /* log != NULL: the instantiations that append the call's points to the loudness log; NULL: the kernels as they are without it */
 int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);

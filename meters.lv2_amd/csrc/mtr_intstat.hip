@@ -198,8 +198,8 @@ static void intstat_sections (const mtr_engine* e, std::vector<StateSection>& v)
 	if (m & MTR_METER_SIGDIST) v.push_back ({ e->is.sdh.p, sizeof (mtr_sigdist_state) });
 }
 
-constinit SideMeter intstat_meter = { MTR_METER_BITSTATS | MTR_METER_SIGDIST, 0x7fffffffull, "BITSTATS / SIGDIST: n_frames per call must be < 2^31 - 1",
-                                            nullptr, mtr_engine_intstat_reset, intstat_step, intstat_sections, nullptr };
+constinit SideMeter intstat_meter = { .bits = MTR_METER_BITSTATS | MTR_METER_SIGDIST, .max_frames = 0x7fffffffull, .max_text = "BITSTATS / SIGDIST: n_frames per call must be < 2^31 - 1",
+                                      .reset = mtr_engine_intstat_reset, .step = intstat_step, .sections = intstat_sections };
 
 extern "C" {
 

@@ -556,14 +556,14 @@ static void kmeter_hdr_take (mtr_engine* e, const void* in)
 	e->pos.km.fill = h.fill; e->pos.km_fpp = h.fpp; e->pos.km_fall = h.fall;
 }
 
-static constinit BlobHeader kmeter_hdr = { 0, KM_HDR_BYTES, KM_CORRUPT, kmeter_hdr_write, kmeter_hdr_check, kmeter_hdr_take };
+static constinit BlobHeader kmeter_hdr = { .offset = 0, .bytes = KM_HDR_BYTES, .corrupt = KM_CORRUPT, .write = kmeter_hdr_write, .check = kmeter_hdr_check, .take = kmeter_hdr_take };
 // (no reset and no step: the meter's first row resets and queues all of it)
-constinit SideMeter kmeter_series_meter = { MTR_METER_KMETER, 0, nullptr, nullptr, nullptr, nullptr, kmeter_open_sections, &kmeter_hdr };
+constinit SideMeter kmeter_series_meter = { .bits = MTR_METER_KMETER, .sections = kmeter_open_sections, .hdr = &kmeter_hdr };
 
 static SeriesView kmeter_series (mtr_engine* e) { return { &e->km.ser, &Cursors::km, &e->km.points }; }
 
-constinit SideMeter kmeter_meter = { MTR_METER_KMETER, 0x7fffffffull, "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           nullptr, mtr_engine_kmeter_reset, kmeter_step, kmeter_sections, nullptr, kmeter_series, nullptr, 1, kmeter_ends_fill };
+constinit SideMeter kmeter_meter = { .bits = MTR_METER_KMETER, .max_frames = 0x7fffffffull, .max_text = "KMETER: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                     .reset = mtr_engine_kmeter_reset, .step = kmeter_step, .sections = kmeter_sections, .series = kmeter_series, .ends_words = 1, .ends_fill = kmeter_ends_fill };
 
 extern "C" {
 

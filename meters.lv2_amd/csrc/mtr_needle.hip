@@ -576,11 +576,11 @@ static void needle_hdr_take (mtr_engine* e, const void* in)
 	memcpy (e->nd.db, h.db, sizeof (h.db)); memcpy (e->nd.mv, h.mv, sizeof (h.mv));
 }
 
-static constinit BlobHeader needle_hdr = { 0, sizeof (mtr_needle_hdr), NEEDLE_CORRUPT, needle_hdr_write, needle_hdr_check, needle_hdr_take };
+static constinit BlobHeader needle_hdr = { .offset = 0, .bytes = sizeof (mtr_needle_hdr), .corrupt = NEEDLE_CORRUPT, .write = needle_hdr_write, .check = needle_hdr_check, .take = needle_hdr_take };
 static SeriesView needle_series (mtr_engine* e) { return { &e->nd.ser, &Cursors::nd, &e->nd.points }; }
 
-constinit SideMeter needle_meter = { MTR_METER_NEEDLE, 0x7fffffffull, "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           needle_create, mtr_engine_needle_reset, needle_step, needle_sections, &needle_hdr, needle_series };
+constinit SideMeter needle_meter = { .bits = MTR_METER_NEEDLE, .max_frames = 0x7fffffffull, .max_text = "NEEDLE: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                     .create = needle_create, .reset = mtr_engine_needle_reset, .step = needle_step, .sections = needle_sections, .hdr = &needle_hdr, .series = needle_series };
 
 extern "C" {
 

@@ -525,9 +525,9 @@ static void scope_hdr_take (mtr_engine* e, const void* in)
 	e->pos.sp_fill = h.fill; e->pos.sp_analyses = h.analyses;
 }
 
-static constinit BlobHeader scope_hdr = { 0, sizeof (mtr_scope_hdr), SCOPE_CORRUPT, scope_hdr_write, scope_hdr_check, scope_hdr_take };
-constinit SideMeter scope_meter = { MTR_METER_SCOPE, 0x7fffffffull, "SCOPE: n_frames per call must be < 2^31 - 1",
-                                          scope_create, mtr_engine_scope_reset, scope_step, scope_sections, &scope_hdr, nullptr, scope_count };
+static constinit BlobHeader scope_hdr = { .offset = 0, .bytes = sizeof (mtr_scope_hdr), .corrupt = SCOPE_CORRUPT, .write = scope_hdr_write, .check = scope_hdr_check, .take = scope_hdr_take };
+constinit SideMeter scope_meter = { .bits = MTR_METER_SCOPE, .max_frames = 0x7fffffffull, .max_text = "SCOPE: n_frames per call must be < 2^31 - 1",
+                                    .create = scope_create, .reset = mtr_engine_scope_reset, .step = scope_step, .sections = scope_sections, .hdr = &scope_hdr, .count = scope_count };
 
 // With a series the blob carries one more section, behind every older one (the second row of the meter in SIDE_METERS): where the open group
 // of K analyses stands.  All of an entry is its host-owned header — K and the analyses since the last point.  An engine takes a blob of its
@@ -562,9 +562,9 @@ static void scope_open_take (mtr_engine* e, const void* in)
 	e->pos.sp_since = h.since;
 }
 
-static constinit BlobHeader scope_open_hdr = { 0, sizeof (mtr_scope_open), SCOPE_SERIES_CORRUPT, scope_open_write, scope_open_check, scope_open_take };
+static constinit BlobHeader scope_open_hdr = { .offset = 0, .bytes = sizeof (mtr_scope_open), .corrupt = SCOPE_SERIES_CORRUPT, .write = scope_open_write, .check = scope_open_check, .take = scope_open_take };
 // (no reset and no step: the meter's first row resets and queues all of it)
-constinit SideMeter scope_series_meter = { MTR_METER_SCOPE, 0, nullptr, nullptr, nullptr, nullptr, scope_open_sections, &scope_open_hdr };
+constinit SideMeter scope_series_meter = { .bits = MTR_METER_SCOPE, .sections = scope_open_sections, .hdr = &scope_open_hdr };
 
 extern "C" {
 

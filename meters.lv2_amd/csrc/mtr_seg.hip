@@ -35,6 +35,7 @@
 // not know which kernel ran.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "mtr_internal.h"
@@ -1304,38 +1305,18 @@ int mtr_launch_seg (bool ebu, const mtr_seg_args& a, uint32_t n_waves, void* str
 		a2.screen = 2u;
 		return mtr_launch_seg (ebu, a2, n_waves, stream);
 	}
-	if (a.screen == 4u) {
-		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else              hipLaunchKernelGGL ((k_seg<true, false, true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-	} else if (a.screen == 3u) {
-		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else              hipLaunchKernelGGL ((k_seg<true, false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-	} else if (a.ends) {
-		if (a.screen) {
-			if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-			else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-			else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-			else              hipLaunchKernelGGL ((k_seg<true, false, true, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		} else {
-			if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-			else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-			else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-			else              hipLaunchKernelGGL ((k_seg<true, false, false, true>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		}
-	} else if (a.screen) {
-		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // (no tiles without Σ y²; the
-		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);   // same code but for the launch's last step)
-		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else              hipLaunchKernelGGL ((k_seg<true, false, true, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-	} else {
-		if (!ebu && aligned) hipLaunchKernelGGL ((k_seg<false, true, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (!ebu)    hipLaunchKernelGGL ((k_seg<false, false, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else if (aligned) hipLaunchKernelGGL ((k_seg<true, true, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-		else              hipLaunchKernelGGL ((k_seg<true, false, false, false>), dim3 (n_waves), dim3 (64), LDS_BYTES, st, a);
-	}
+	// the six forms <SCREEN, LEN, LAZY, CORE>, each for the four (EBU, ALIGNED): 24 instantiations (an unaligned one: the same code but for the
+	// launch's last step; EBU false: no tiles without Σ y²)
+	const auto launch = [&] (auto EBU, auto ALIGNED) {
+		const auto form = [&] (auto kernel) { hipLaunchKernelGGL (kernel, dim3 (n_waves), dim3 (64), LDS_BYTES, st, a); };
+		if (a.screen == 4u)          form (k_seg<EBU.value, ALIGNED.value, true, false, true, true>);
+		else if (a.screen == 3u)     form (k_seg<EBU.value, ALIGNED.value, true, false, true>);
+		else if (a.ends && a.screen) form (k_seg<EBU.value, ALIGNED.value, true, true>);
+		else if (a.ends)             form (k_seg<EBU.value, ALIGNED.value, false, true>);
+		else if (a.screen)           form (k_seg<EBU.value, ALIGNED.value, true, false>);
+		else                         form (k_seg<EBU.value, ALIGNED.value, false, false>);
+	};
+	if (ebu) { if (aligned) launch (std::true_type {}, std::true_type {}); else launch (std::true_type {}, std::false_type {}); }
+	else     { if (aligned) launch (std::false_type {}, std::true_type {}); else launch (std::false_type {}, std::false_type {}); }
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }

@@ -352,9 +352,10 @@ static void stcorr_hdr_take (mtr_engine* e, const void* in)
 
 static SeriesView stcorr_series (mtr_engine* e) { return { &e->sc.ser, &Cursors::sc, &e->sc.points }; }
 
-static constinit BlobHeader stcorr_hdr = { offsetof (mtr_stcorr_state, period), sizeof (StcorrHdr), STCORR_CORRUPT, stcorr_hdr_write, stcorr_hdr_check, stcorr_hdr_take };
-constinit SideMeter stcorr_meter = { MTR_METER_STCORR, 0x7fffffffull, "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                           stcorr_create, mtr_engine_stcorr_reset, stcorr_step, stcorr_sections, &stcorr_hdr, stcorr_series };
+static constinit BlobHeader stcorr_hdr = { .offset = offsetof (mtr_stcorr_state, period), .bytes = sizeof (StcorrHdr), .corrupt = STCORR_CORRUPT,
+                                           .write = stcorr_hdr_write, .check = stcorr_hdr_check, .take = stcorr_hdr_take };
+constinit SideMeter stcorr_meter = { .bits = MTR_METER_STCORR, .max_frames = 0x7fffffffull, .max_text = "STCORR: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                     .create = stcorr_create, .reset = mtr_engine_stcorr_reset, .step = stcorr_step, .sections = stcorr_sections, .hdr = &stcorr_hdr, .series = stcorr_series };
 
 extern "C" {
 

@@ -615,10 +615,11 @@ static void surround_hdr_take (mtr_engine* e, const void* in)
 	memcpy (e->su.pa, h.pa, sizeof (h.pa)); memcpy (e->su.pb, h.pb, sizeof (h.pb));
 }
 
-static constinit BlobHeader surround_hdr = { 0, SUR_HDR_BYTES, SUR_CORRUPT, surround_hdr_write, surround_hdr_check, surround_hdr_take };
+static constinit BlobHeader surround_hdr = { .offset = 0, .bytes = SUR_HDR_BYTES, .corrupt = SUR_CORRUPT, .write = surround_hdr_write, .check = surround_hdr_check, .take = surround_hdr_take };
 static SeriesView surround_series (mtr_engine* e) { return { &e->su.ser, &Cursors::su, &e->su.points }; }
-constinit SideMeter surround_meter = { MTR_METER_SURROUND, 0x7fffffffull, "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)",
-                                             surround_create, mtr_engine_surround_reset, surround_step, surround_sections, &surround_hdr, surround_series, nullptr, 1, surround_ends_fill };
+constinit SideMeter surround_meter = { .bits = MTR_METER_SURROUND, .max_frames = 0x7fffffffull, .max_text = "SURROUND: n_frames per call must be < 2^31 - 1 (the reference's int n)",
+                                       .create = surround_create, .reset = mtr_engine_surround_reset, .step = surround_step, .sections = surround_sections, .hdr = &surround_hdr,
+                                       .series = surround_series, .ends_words = 1, .ends_fill = surround_ends_fill };
 
 extern "C" {
 

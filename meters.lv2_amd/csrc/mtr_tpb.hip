@@ -1162,10 +1162,10 @@ static int tpb_series_reset (mtr_engine* e)
 	return MTR_OK;
 }
 
-static constinit BlobHeader tpb_hdr = { 0, TPB_HDR_BYTES, TPB_CORRUPT, tpb_hdr_write, tpb_hdr_check, tpb_hdr_take };
+static constinit BlobHeader tpb_hdr = { .offset = 0, .bytes = TPB_HDR_BYTES, .corrupt = TPB_CORRUPT, .write = tpb_hdr_write, .check = tpb_hdr_check, .take = tpb_hdr_take };
 static int tpb_series_create (mtr_engine* e) { e->tb.points.assign (e->cfg.n_streams, 0); return MTR_OK; }
 static SeriesView tpb_series (mtr_engine* e) { return { &e->tb.ser, &Cursors::tb, &e->tb.points }; }
-constinit SideMeter tpb_meter = { MTR_METER_TPBALLIST, 0, nullptr, tpb_series_create, tpb_series_reset, tpb_step, tpb_open_sections, &tpb_hdr, tpb_series };
+constinit SideMeter tpb_meter = { .bits = MTR_METER_TPBALLIST, .create = tpb_series_create, .reset = tpb_series_reset, .step = tpb_step, .sections = tpb_open_sections, .hdr = &tpb_hdr, .series = tpb_series };
 
 static int no_tpb (const mtr_engine* e) { return !e || !(e->cfg.meters & MTR_METER_TPBALLIST); }
 static const char* const NO_TPB = "no TPBALLIST in this engine";

@@ -412,6 +412,28 @@ def test_the_64_stream_form(M):
     assert np.array_equal(got["img"], got["drawn"])
 
 
+@pytest.mark.parametrize("cfg", [dict(autogain=1), dict(gain=4.0)], ids=["autogain", "fixed_gain"])
+def test_the_64_stream_form_dense(M, cfg):
+    """... and its dense arm (n_streams >= 16384 without ends), at the same shape: a dense call against a call whose every end is the
+    call's length — the ENDS instantiations on the same frames, which the test above holds to the restatement.  Equal by bytes."""
+    S_, T_, P_ = 16384 + 3, 600, 128
+    dev = device(signal(S_, T_, 8))
+    got = []
+    for ends in (None, np.full(S_, T_, np.uint64)):
+        with engine(M, S_, period_frames=P_, capacity=8, tune_piece=256, shift=3, **cfg) as e:
+            if ends is None:
+                e.process_device(dev.data_ptr(), T_)
+            else:
+                e.process_device_gonio_ends(dev.data_ptr(), T_, ends)
+            e.sync()
+            got.append(snap(e))
+    dense, open_ = got
+    assert dense["blocks"].tolist() == [T_ // P_, T_ // P_] and dense["drawn"].any() and (dense["s_drawn"] > 0).any()
+    if "autogain" in cfg:
+        assert (dense["s_gain"] != dense["s_gain"][:, :1]).any()           # (the gain moved)
+    same(dense, open_)
+
+
 # ---- 8: the image kernel's other instantiations ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shift", [1, 3])
 def test_the_other_shifts(M, shift):

@@ -1,4 +1,4 @@
-"""The goniometer's oversampling on the GPU (include/mtr_gonio_os.h: mtr_engine_gonio_set_oversample; k_gonio_os and k_gonio_hist in front of
+"""The goniometer's oversampling on the GPU (include/mtr_gonio_os.h: mtr_engine_gonio_set_oversample; k_gonio_os and k_history's 23-frame rows in front of
 and behind k_gonio_points / k_gonio_image) against the restatement of tests/_gonio_os.py, which tests/test_gonio_os_cpu.py holds to the
 reference's Resampler.
 
