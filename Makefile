@@ -9,6 +9,8 @@
 #                     and the CPU suite runs against them (MTR_LIB / MTR_PLUGIN_SO / MTR_ORACLE_SO point the tests at
 #                     the instrumented libraries; the sanitizer runtimes are preloaded because the host process is
 #                     python; leak checking is off: the interpreter's own allocations drown it).
+#   make check-san-plane   mtr_setup_plane_decode alone under the same sanitizers, in a stand-alone program (tools/plane_decode_san.c):
+#                     needs no python, no preload and no GPU
 CC      ?= gcc
 ROOT    := $(abspath .)
 CSRC    := meters.lv2_amd/csrc
@@ -18,7 +20,7 @@ INC     := -I$(ROOT)/include -I$(CSRC)
 LV2SRC  := $(addprefix $(CSRC)/,lv2_plugin.c lv2_ebur128.c lv2_intstat.c lv2_needle.c lv2_dr14.c)
 SANFLAGS := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-.PHONY: build test check-asan
+.PHONY: build test check-asan check-san-plane
 build:
 	python3 -c "import __graft_entry__ as g; g.build()"
 
@@ -39,3 +41,8 @@ check-asan: build
 	    MTR_LIB=$(ROOT)/$(ASAN)/libmtr_engine.so MTR_PLUGIN_SO=$(ROOT)/$(ASAN)/meters_amd.so \
 	    MTR_ORACLE_SO=$(ROOT)/$(ASAN)/libmtr_oracle.so \
 	    python3 -m pytest tests -x -q -m "not gpu and not ref" -p no:cacheprovider
+
+check-san-plane:
+	@mkdir -p $(ASAN)
+	$(CC) $(SANFLAGS) -std=gnu11 -ffp-contract=off -msse2 -mfpmath=sse $(INC) -Wall -o $(ASAN)/plane_decode_san tools/plane_decode_san.c $(CSRC)/mtr_setup.c -lm
+	$(ASAN)/plane_decode_san

@@ -36,7 +36,8 @@ extern "C" {
  *    _spectr_points; mtr_engine_scope_set_series, _scope_series_config, _scope_series, mtr_scope_series_cut; mtr_engine_process_device_any,
  *    _process_host_any, _scope_points; MTR_METER_GONIO, mtr_gonio_derive, mtr_engine_gonio_configure, _gonio_config, _gonio_set_gain,
  *    _gonio_image, _gonio_read, _gonio_blocks, _gonio_series, _gonio_image_clear, _gonio_reset; mtr_gonio_os_table, mtr_gonio_os_hpw,
- *    mtr_engine_gonio_set_oversample, _gonio_oversample, _gonio_os_timing):
+ *    mtr_engine_gonio_set_oversample, _gonio_oversample, _gonio_os_timing; mtr_engine_set_plane_layout, _plane_layout, _plane_stats,
+ *    mtr_plane_decode_host):
  *    + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
@@ -282,6 +283,7 @@ int  mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, flo
  * frame_channels == 0 (map ignored): back to the default — frames of n_channels, in order.  It describes buffers, not streams:
  * callable between any two process calls, not part of the state blob, kept across mtr_engine_reset.
  * frame_channels > MTR_MAX_FRAME_CHANNELS, map == NULL, an entry >= frame_channels: MTR_ERR_ARG, layout unchanged.
+ * A successful call takes a plane layout (mtr_planes.h) away: the two exclude each other.
  * mtr_engine_process_planar_host / _prepare_host take planar channels and are not affected.
  * A 5.1 file (WAVE order L R C LFE Ls Rs) on a 5-channel engine: frame_channels 6, map {0, 1, 2, 4, 5}; the stereo mix in channels
  * 6 and 7 of an 8-channel frame on a stereo engine: 8, {6, 7}; a mono file on a stereo engine (the reference's mono loudness is the
@@ -417,6 +419,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The goniometer's oversampling, the 2 - 32x interpolator in front of draw_rb: mtr_gonio_os_table, mtr_gonio_os_hpw,
  * mtr_engine_gonio_set_oversample / _gonio_oversample / _gonio_os_timing, declared in mtr_gonio_os.h */
 #include "mtr_gonio_os.h"
+
+/* Plane layouts — the process calls on planar (stream, channel, time) buffers, k_plane in front of the meters:
+ * mtr_engine_set_plane_layout / _plane_layout / _plane_stats and mtr_plane_decode_host, declared in mtr_planes.h */
+#include "mtr_planes.h"
 
 /* ---- multi-GPU aggregate ---------------------------------------------------- */
 

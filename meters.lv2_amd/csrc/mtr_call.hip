@@ -191,7 +191,12 @@ struct CallRun {
 			t1 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2 + 1);
 		}
 		if (t0 && t1) HIPCHK (hipEventRecord (t0, c.st));
-		if (c.pick_fc) {
+		if (c.plane_p) {
+			if (mtr_launch_plane (c.pcm_format, c.pcm, c.pcm_pitch, c.plane_p, e->plane_map, e->cfg.n_channels, const_cast<float*> (c.audio),
+			                      c.stride * e->cfg.n_channels, c.cnt, c.n_frames, c.st))
+				return fail (MTR_ERR_HIP, "k_plane launch");
+			e->plane_staged++;
+		} else if (c.pick_fc) {
 			if (mtr_launch_pick (c.pcm_format, c.pcm, c.pcm_pitch, c.pick_fc, e->frame_map, e->cfg.n_channels, const_cast<float*> (c.audio),
 			                     c.stride * e->cfg.n_channels, c.cnt, c.n_frames, c.st))
 				return fail (MTR_ERR_HIP, "k_pick launch");
@@ -200,9 +205,9 @@ struct CallRun {
 			return fail (MTR_ERR_HIP, "k_pcm launch");
 		if (t0 && t1) { HIPCHK (hipEventRecord (t1, c.st)); e->pcm_timed++; }
 		if (c.pcm_read) HIPCHK (hipEventRecord (c.pcm_read, c.st));
-		if (!pcm) { e->lay_staged++; return MTR_OK; }
+		if (!pcm) { if (c.pick_fc) e->lay_staged++; return MTR_OK; }
 		e->pcm_chunks++;
-		e->pcm_bytes += (uint64_t) c.cnt * c.n_frames * (c.pick_fc ? c.pick_fc : e->cfg.n_channels) * mtr_setup_pcm_sample_bytes (c.pcm_format);
+		e->pcm_bytes += (uint64_t) c.cnt * c.n_frames * (c.plane_p ? c.plane_p : c.pick_fc ? c.pick_fc : e->cfg.n_channels) * mtr_setup_pcm_sample_bytes (c.pcm_format);
 		return MTR_OK;
 	}
 
@@ -530,6 +535,8 @@ struct Source {
 // float path stages it (same dstride, same chunks: host_chunk_bytes counts decoded bytes), so the meters see the very same call.  The
 // raw buffer is free again once the decode has read it, the float buffer once the meters have: stream order, both on the engine's stream.
 // PCM in device memory: the same chunks without the copy, decoded straight from the caller's rows on the caller's stream.
+// A plane layout (mtr_planes.h) is one more source geometry of the same loop: the chunk's cnt * P planes cross the link as the rows of
+// ONE 2-D copy into the raw buffer (or are read where they lie in device memory), and k_plane is the chunk's first step.
 static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames, uint64_t stride, const uint64_t* frames)
 {
 	if (n_frames == 0) return MTR_OK;
@@ -551,9 +558,13 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 	// frame layout: the source rows hold frames of FC samples (the default: C), picked by the chunk's first step as PCM is decoded by it
 	const bool pick = e->picks;
 	const size_t FC = pick ? e->frame_channels : C;
-	const size_t raw_pitch = (n_frames * FC * sb + 15) & ~(size_t) 15;         // PCM / wide frames from the host: bytes per landed row ...
-	const size_t raw_bytes = ((size_t) cs * raw_pitch + 255) & ~(size_t) 255;  // ... and per raw buffer
-	const bool landing = src.host && (src.format || pick);
+	// plane layout (it excludes the frame layout): per stream P planes of n_frames samples, `stride` samples from plane to plane; a row
+	// of the link copy and of the landing buffer is ONE PLANE, a chunk cnt * P of them, interleaved by the chunk's first step (k_plane)
+	const size_t P = e->planes ? e->plane_count : 0;
+	const size_t row_samples = P ? n_frames : n_frames * FC, rows_per_stream = P ? P : 1;
+	const size_t raw_pitch = (row_samples * sb + 15) & ~(size_t) 15;           // PCM / wide frames / planes from the host: bytes per landed row ...
+	const size_t raw_bytes = ((size_t) cs * rows_per_stream * raw_pitch + 255) & ~(size_t) 255;  // ... and per raw buffer
+	const bool landing = src.host && (src.format || pick || P);
 	hipStream_t st = (hipStream_t) src.hip_stream;
 	if (src.host) {
 		HIPCHK (e->own_stream.ensure ());
@@ -583,23 +594,24 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 		float* const dst = e->stage.p + (size_t) b * buf_floats;
 		// (the lengths of the chunk's streams are indexed from its first; the cursors move with the last chunk)
 		Call c { dst, n_frames, dstride, st, off, cnt, frames ? frames + off : nullptr, true, k + 1 == n_chunks };
-		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * stride * FC * sb;
-		size_t pitch = stride * FC * sb;
+		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * stride * (P ? P : FC) * sb;
+		size_t pitch = P ? stride * sb : stride * FC * sb;
 		if (src.host) {
 			void* const land = landing ? (void*) (e->pcm_raw.p + (size_t) b * raw_bytes) : (void*) dst;
 			const size_t land_pitch = landing ? raw_pitch : row * sizeof (float);
 			if (k >= 2) HOSTCHK (hipStreamWaitEvent (e->copy_stream.v, e->ev_computed[b].v, 0));   // the kernels of chunk k - 2 have read this buffer
-			HOSTCHK (hipMemcpy2DAsync (land, land_pitch, from, pitch, n_frames * FC * sb, cnt, hipMemcpyHostToDevice, e->copy_stream.v));
+			HOSTCHK (hipMemcpy2DAsync (land, land_pitch, from, pitch, row_samples * sb, cnt * rows_per_stream, hipMemcpyHostToDevice, e->copy_stream.v));
 			HOSTCHK (hipEventRecord (e->ev_copied[b].v, e->copy_stream.v));
 			HOSTCHK (hipStreamWaitEvent (st, e->ev_copied[b].v, 0));
 			from = (const uint8_t*) land;
 			pitch = land_pitch;
 		}
-		if (src.format || pick) {
+		if (src.format || pick || P) {
 			c.pcm = from;
 			c.pcm_pitch = pitch;
 			c.pcm_format = src.format;
 			c.pick_fc = pick ? (uint32_t) FC : 0;
+			c.plane_p = (uint32_t) P;
 			if (landing) c.pcm_read = e->ev_computed[b].v;
 		}
 		rc = process_call (e, c);
@@ -625,7 +637,8 @@ static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frame
 	// by chunk into the staging buffers, as device PCM is decoded.
 	// (not beside the surround meter, whose kernel takes frames of the engine's five channels: that engine stages the call like any other map)
 	const bool direct = e->picks && e->wave51 && !(e->cfg.meters & MTR_METER_SURROUND);
-	if (e->picks && !direct) return process_chunked (e, { d_audio, 0, false, hip_stream }, n_frames, stride, frames);
+	// A plane layout: always staged, chunk by chunk through k_plane (no kernel of the meters reads planes)
+	if (e->planes || (e->picks && !direct)) return process_chunked (e, { d_audio, 0, false, hip_stream }, n_frames, stride, frames);
 	if (n_frames == 0) return MTR_OK;
 	if (stride < n_frames) return fail (MTR_ERR_ARG, "stream_stride_frames < n_frames");
 	HIPCHK (hipSetDevice (e->cfg.device));
@@ -911,6 +924,13 @@ int mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, floa
 	return MTR_OK;
 }
 
+static void plane_default (mtr_engine* e)
+{
+	e->planes = false;
+	e->plane_count = 0;
+	for (uint32_t c = 0; c < MTR_MAX_ENGINE_CHANNELS; ++c) e->plane_map[c] = (uint8_t) c;
+}
+
 int mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const uint8_t* map)
 {
 	if (!e) return fail (MTR_ERR_ARG, "null engine");
@@ -919,6 +939,7 @@ int mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const u
 		e->frame_channels = 0;
 		for (uint32_t c = 0; c < MTR_MAX_ENGINE_CHANNELS; ++c) e->frame_map[c] = (uint8_t) c;
 		e->picks = e->wave51 = false;
+		plane_default (e);
 		return MTR_OK;
 	}
 	if (frame_channels > MTR_MAX_FRAME_CHANNELS) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: frame_channels > MTR_MAX_FRAME_CHANNELS");
@@ -932,6 +953,50 @@ int mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const u
 	for (uint32_t c = 0; c < C; ++c) e->frame_map[c] = map[c];
 	e->picks = !identity;                                          // (the explicit identity is the default and takes its paths)
 	e->wave51 = e->layout == 8 && C == 5 && frame_channels == 6 && map[0] == 0 && map[1] == 1 && map[2] == 2 && map[3] == 4 && map[4] == 5;
+	plane_default (e);                                              // (frames or planes: the two exclude each other)
+	return MTR_OK;
+}
+
+int mtr_engine_set_plane_layout (mtr_engine* e, uint32_t n_planes, const uint8_t* map)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	const uint32_t C = e->cfg.n_channels;
+	if (n_planes > MTR_MAX_FRAME_CHANNELS) return fail (MTR_ERR_ARG, "mtr_engine_set_plane_layout: n_planes > MTR_MAX_FRAME_CHANNELS");
+	if (n_planes && !map) return fail (MTR_ERR_ARG, "mtr_engine_set_plane_layout: null map");
+	for (uint32_t c = 0; n_planes && c < C; ++c)
+		if (map[c] >= n_planes) return fail (MTR_ERR_ARG, "mtr_engine_set_plane_layout: a map entry >= n_planes");
+	const int rc = mtr_engine_set_frame_layout (e, 0, nullptr);      // (which also puts the plane layout back to its default)
+	if (rc || !n_planes) return rc;
+	e->plane_count = n_planes;
+	for (uint32_t c = 0; c < C; ++c) e->plane_map[c] = map[c];
+	e->planes = true;
+	return MTR_OK;
+}
+
+int mtr_engine_plane_layout (const mtr_engine* e, uint32_t* n_planes, uint8_t* map)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if (n_planes) *n_planes = e->plane_count;
+	if (map) for (uint32_t c = 0; c < e->cfg.n_channels; ++c) map[c] = e->plane_map[c];
+	return MTR_OK;
+}
+
+int mtr_plane_decode_host (int format, const void* src, size_t n_frames, uint64_t stride_frames, uint32_t n_planes, const uint8_t* map, uint32_t n_channels,
+                           float* dst)
+{
+	if (format && !mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown format (0 = f32, MTR_PCM_S16, _S24, _S32)");
+	if (!map || !n_planes || n_planes > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_ENGINE_CHANNELS)
+		return fail (MTR_ERR_ARG, "mtr_plane_decode_host: map / n_planes / n_channels");
+	if (stride_frames < n_frames) return fail (MTR_ERR_ARG, "mtr_plane_decode_host: stride_frames < n_frames");
+	if (n_frames && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_plane_decode_host: null argument");
+	return mtr_setup_plane_decode (format, src, n_frames, stride_frames, n_planes, map, n_channels, dst)
+	       ? fail (MTR_ERR_ARG, "mtr_plane_decode_host: a map entry >= n_planes") : MTR_OK;
+}
+
+int mtr_engine_plane_stats (mtr_engine* e, uint64_t* staged_chunks)
+{
+	if (!e) return fail (MTR_ERR_ARG, "null engine");
+	if (staged_chunks) *staged_chunks = e->plane_staged;
 	return MTR_OK;
 }
 

@@ -234,6 +234,12 @@ struct mtr_engine {
 	bool             picks = false;
 	bool             wave51 = false;      // ... and it is 6, {0, 1, 2, 4, 5} on a 5-channel engine: device f32 calls go to k_kwmc51 instead
 	uint64_t         lay_staged = 0, lay_direct = 0;
+	// plane layout (mtr_engine_set_plane_layout, mtr_planes.h): the buffers hold plane_count planes of one channel per stream, engine
+	// channel c is plane plane_map[c].  `planes`: one is set (it excludes `picks`), every chunk goes through k_plane (mtr_plane.hip)
+	bool             planes = false;
+	uint32_t         plane_count = 0;
+	uint8_t          plane_map[MTR_MAX_ENGINE_CHANNELS] = { 0, 1, 2, 3, 4, 5, 6, 7 };
+	uint64_t         plane_staged = 0;
 
 	bool timing = false;
 	std::vector<Event> ev;          // groups of EV_PER_CALL: start, fused end, gate begin, gate end (those two on the stream the gate ran on), rest begin, end; a PCM chunk's start in front of its decode
@@ -380,6 +386,8 @@ struct Call {
 	hipEvent_t      pcm_read = nullptr;
 	// frame layout: the rows at `pcm` (format 0: f32) hold frames of pick_fc samples, k_pick decodes and picks them (0: k_pcm on frames of C)
 	uint32_t        pick_fc = 0;
+	// plane layout: `pcm` holds plane_p planes per stream, pcm_pitch bytes from plane to plane; k_plane decodes and interleaves them
+	uint32_t        plane_p = 0;
 	// ... or `audio` itself holds WAVE 5.1 frames, [cnt][stride][6], which the 5-channel kernels read themselves (k_kwmc51, k_history with FC = 6)
 	bool            wave51 = false;
 };

@@ -196,6 +196,8 @@ size_t mtr_setup_pcm_sample_bytes (int format);
 int  mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst);   /* -1: unknown format */
 /* frames of fc samples (format 0 = f32, else MTR_PCM_*) to frames of C floats, channel c = source channel map[c]; -1: bad argument */
 int  mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_t fc, const uint8_t* map, uint32_t C, float* dst);
+/* one stream's P planes (plane p at src + p * stride samples) to frames of C floats, channel c = plane map[c]; -1: bad argument */
+int  mtr_setup_plane_decode (int format, const void* src, size_t n_frames, uint64_t stride, uint32_t P, const uint8_t* map, uint32_t C, float* dst);
 void mtr_setup_stcorr (float fsamp, float* out2);   /* w1, w2 of Stcorrdsp::init ((int) fsamp, 2e3f, 0.3f) */
 int  mtr_setup_needle (uint32_t kind, float fsamp, float* out4);   /* w1 w2 w3 g of the needle meters' init (VU: w, 4 w, 0, g); -1: unknown kind */
 void mtr_setup_scope_window (uint32_t n, float* out);   /* the Hann window of ft_gen_window (gui/fft.c): n floats */
@@ -293,6 +295,10 @@ int  mtr_launch_pcm (int format, const void* src, uint64_t src_pitch, float* dst
  * f32 (pitch in floats), channel c = source channel map[c]: mtr_pick.hip */
 int  mtr_launch_pick (int format, const void* src, uint64_t src_pitch, uint32_t frame_channels, const uint8_t* map, uint32_t n_channels,
                       float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_frames, void* stream);
+/* per row n_planes planes of n_frames samples (format 0 = f32, else MTR_PCM_*; plane p of row r at src + (r * n_planes + p) * plane_pitch
+ * BYTES) to rows of n_frames x n_channels f32 (pitch in floats), channel c = plane map[c]: mtr_plane.hip */
+int  mtr_launch_plane (int format, const void* src, uint64_t plane_pitch, uint32_t n_planes, const uint8_t* map, uint32_t n_channels,
+                       float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_frames, void* stream);
 int  mtr_launch_synth (float* d_audio, uint32_t n_streams, uint64_t n_frames, uint64_t stride,
                        uint32_t seed, float fs, int kind, void* stream);
 #endif

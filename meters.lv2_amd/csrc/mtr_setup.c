@@ -283,6 +283,24 @@ int mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_
 	return 0;
 }
 
+/* One stream's P planes of one channel each (plane p at src + p * stride samples) to n_frames frames of C floats, channel c = plane map[c]
+ * (mtr_engine_set_plane_layout): samples move as in mtr_setup_pick_decode.  What k_plane (mtr_plane.hip) is held against. */
+int mtr_setup_plane_decode (int format, const void* src, size_t n_frames, uint64_t stride, uint32_t P, const uint8_t* map, uint32_t C, float* dst)
+{
+	const size_t sb = format ? mtr_setup_pcm_sample_bytes (format) : sizeof (float);
+	if (!sb || !map || !P || !C || stride < n_frames) return -1;
+	for (uint32_t c = 0; c < C; ++c) if (map[c] >= P) return -1;
+	const unsigned char* p = (const unsigned char*) src;
+	for (uint32_t c = 0; c < C; ++c) {
+		const unsigned char* pl = p + (size_t) map[c] * stride * sb;
+		for (size_t i = 0; i < n_frames; ++i) {
+			if (format) mtr_setup_pcm_decode (format, pl + i * sb, 1, dst + i * C + c);
+			else memcpy (dst + i * C + c, pl + i * sb, sizeof (float));
+		}
+	}
+	return 0;
+}
+
 /* Stcorrdsp::init ((int) fsamp, 2e3f, 0.3f) as the plugins call it (jmeters/stcorrdsp.cc:85-93; src/meters.cc:202-207) */
 void mtr_setup_stcorr (float fsamp, float* out2)
 {

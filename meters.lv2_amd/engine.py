@@ -3,8 +3,10 @@
 Names follow the reference's classes: Engine.integr_start/.integr_pause/.integr_reset mirror
 Ebu_r128_proc (ebumeter/ebu_r128_proc.h:77-79), Engine.results() returns the getters of
 ebu_r128_proc.h:81-94 per stream, Engine.process() is the batched process()/process_max()/
-spectrum_run inner loop.  Device buffers are passed as raw pointers (torch tensors' data_ptr()).
+spectrum_run inner loop.  Device buffers are passed as raw pointers (torch tensors' data_ptr());
+Engine.process_tensor() takes a torch tensor or a numpy array as it lies, channels first or last.
 """
+import collections
 import ctypes as C
 import os
 import re
@@ -255,6 +257,11 @@ def _load():
         L.mtr_engine_gonio_set_oversample.argtypes = [vp, u32]
         L.mtr_engine_gonio_oversample.argtypes = [vp, C.POINTER(u32), C.POINTER(f32)]
         L.mtr_engine_gonio_os_timing.argtypes = [vp, C.POINTER(f32), C.POINTER(u32)]
+    if hasattr(L, "mtr_engine_set_plane_layout"):              # (an addition inside ABI version 2: plane layouts)
+        L.mtr_engine_set_plane_layout.argtypes = [vp, u32, vp]
+        L.mtr_engine_plane_layout.argtypes = [vp, C.POINTER(u32), vp]
+        L.mtr_plane_decode_host.argtypes = [C.c_int, vp, C.c_size_t, u64, u32, vp, u32, vp]
+        L.mtr_engine_plane_stats.argtypes = [vp, C.POINTER(u64)]
     if hasattr(L, "mtr_engine_loudlog_series"):                # (an addition inside ABI version 2: the loudness log)
         L.mtr_engine_loudlog_set_period.argtypes = [vp, u32, u32, C.c_int]
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
@@ -533,6 +540,129 @@ def pick_decode(format, array, map, n_channels=None):
     return out
 
 
+def _need_planes():
+    if not hasattr(lib, "mtr_engine_set_plane_layout"):
+        raise EngineError(f"{lib_path} has no plane layouts: rebuild it")
+
+
+def _plane_map(map, n_planes, n_channels):
+    """the map of a plane (or frame) layout as uint8 [n_channels]; None: the identity, which needs n_planes == n_channels"""
+    if map is None:
+        if n_planes != n_channels:
+            raise ValueError(f"map=None is the identity and needs {n_channels} planes, not {n_planes}")
+        return np.arange(n_channels, dtype=np.uint8)
+    m = np.ascontiguousarray(map, np.uint8)
+    if m.shape != (n_channels,):
+        raise ValueError(f"map: one entry per engine channel, shape ({n_channels},), not {m.shape}")
+    return m
+
+
+def plane_decode(format, array, map, n_channels=None, stride=None):
+    """mtr_plane_decode_host on every stream of `array`: [..., P, n_frames] planes of one channel each — float32 for format 0, int16 /
+    int32 for PCM_S16 / PCM_S32, packed uint8 [..., P, n_frames * 3] for PCM_S24 — to [..., n_frames, n_channels] float32, channel c =
+    plane map[c] (map=None: the identity).  `array` is read where it lies: a view whose last axis is contiguous and whose planes lie
+    `stride` samples apart (by default: what the view's strides say) is not copied, so the planes may be windows of longer ones, with
+    anything behind their ends, and start on any byte.  The definition the GPU's k_plane is held against."""
+    _need_planes()
+    x = np.asarray(array)
+    if x.ndim < 2:
+        raise ValueError(f"planes: [..., P, n_frames], not {x.shape}")
+    if format == 0:
+        if x.dtype != np.float32:
+            raise ValueError(f"format 0 takes float32, not {x.dtype}")
+        sb = 4
+    else:
+        _pcm_format(x, format)
+        sb = {PCM_S16: 2, PCM_S24: 3, PCM_S32: 4}[format]
+    P, row = x.shape[-2], x.shape[-1] * x.itemsize
+    if row % sb:
+        raise ValueError(f"PCM_S24: the last axis holds n_frames * 3 bytes, not {x.shape}")
+    n_frames = row // sb
+    if n_frames > 1 and x.strides[-1] != x.itemsize:
+        raise ValueError(f"planes: the last axis must be contiguous, strides {x.strides}")
+    if stride is None:
+        stride = n_frames if P == 1 or n_frames == 0 else x.strides[-2] // sb
+    if P > 1 and n_frames and x.strides[-2] != stride * sb:
+        raise ValueError(f"planes {x.strides[-2]} bytes apart are not {stride} samples of {sb} bytes apart")
+    n_channels = (P if map is None else len(map)) if n_channels is None else n_channels
+    m = _plane_map(map, P, n_channels)
+    out = np.empty(x.shape[:-2] + (n_frames, n_channels), np.float32)
+    for idx in np.ndindex(*x.shape[:-2]):
+        _check(lib.mtr_plane_decode_host(int(format), x[idx].ctypes.data, n_frames, int(stride), P, m.ctypes.data, n_channels,
+                                         out[idx].ctypes.data), "mtr_plane_decode_host")
+    return out
+
+
+TensorSource = collections.namedtuple("TensorSource", "format kind width map n_frames stride")
+_TENSOR_FORMATS = {"float32": 0, "int16": PCM_S16, "int32": PCM_S32}
+
+
+def tensor_source(shape, strides, dtype, n_channels, channels_first=None, map=None):
+    """How a process call takes a 3-D tensor as it lies, never a copy: a TensorSource (format: 0 / PCM_S16 / PCM_S32; kind: "frames" — a
+    frame layout of `width` interleaved channels — or "planes" — a plane layout of `width` planes —; map: a tuple of n_channels entries;
+    n_frames; stride: the call's stream_stride_frames), or ValueError.  shape and strides (in ELEMENTS) are the tensor's: (batch, time,
+    channel) — channels last — with strides (st * W, W, 1), or (batch, channel, time) — channels first — with strides (P * st, st, 1), st >=
+    n_frames either way (a window of a longer tensor has st = its length); an axis of one element may have any stride.  The width must be
+    n_channels (map=None: the identity) or go with `map`.  channels_first=None decides from shape and strides, and refuses a tensor that
+    fits both ways with different meanings.  No device and no torch are needed."""
+    name = str(dtype).split(".")[-1]
+    if name not in _TENSOR_FORMATS:
+        raise ValueError(f"tensor dtype {dtype}: float32, int16 or int32 (24-bit PCM has no tensor dtype: process_pcm)")
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 3 or len(strides) != 3:
+        raise ValueError(f"a tensor of three axes, (batch, channel, time) or (batch, time, channel), not shape {shape} strides {strides}")
+    if min(shape) < 1:
+        raise ValueError(f"an empty tensor: shape {shape}")
+    if min(strides) < 0:
+        raise ValueError(f"negative strides {strides}: a flipped view is not taken (and never copied)")
+    B, a, b = shape
+    s0, s1, s2 = strides
+    if b > 1 and s2 != 1:
+        raise ValueError(f"the innermost stride must be 1: strides {strides} of shape {shape} (a transposed view is not taken, and never copied)")
+
+    def width_ok(w):
+        if map is None:
+            return None if w == n_channels else f"width {w} is not n_channels = {n_channels} and there is no map"
+        m = tuple(int(v) for v in map)
+        if len(m) != n_channels or not 1 <= w <= 8 or max(m) >= w or min(m) < 0:
+            return f"map {m} does not go with width {w} and n_channels = {n_channels}"
+        return None
+
+    def first():                                              # (B, P, T) with strides (P * st, st, 1)
+        P, T = a, b
+        st = s1 if P > 1 else s0 if B > 1 else T
+        if st < T:
+            return f"channels first: planes {st} apart are shorter than n_frames = {T} (strides {strides})"
+        if B > 1 and s0 != P * st:
+            return f"channels first: strides {strides} are not ({P} * st, st, 1)"
+        return width_ok(P) or TensorSource(_TENSOR_FORMATS[name], "planes", P, tuple(range(P)) if map is None else tuple(int(v) for v in map), T, st)
+
+    def last():                                               # (B, T, W) with strides (st * W, W, 1)
+        T, W = a, b
+        if T > 1 and s1 != W:
+            return f"channels last: strides {strides} are not (st * {W}, {W}, 1)"
+        if B > 1 and s0 % W:
+            return f"channels last: strides {strides} are not (st * {W}, {W}, 1)"
+        st = s0 // W if B > 1 else T
+        if st < T:
+            return f"channels last: streams {st} frames apart are shorter than n_frames = {T} (strides {strides})"
+        return width_ok(W) or TensorSource(_TENSOR_FORMATS[name], "frames", W, tuple(range(W)) if map is None else tuple(int(v) for v in map), T, st)
+
+    if channels_first is not None:
+        r = first() if channels_first else last()
+        if isinstance(r, str):
+            raise ValueError(r)
+        return r
+    f, l = first(), last()
+    if isinstance(f, str) and isinstance(l, str):
+        raise ValueError(f"shape {shape} with strides {strides} is neither: {f}; {l}")
+    if isinstance(f, str) or isinstance(l, str):
+        return l if isinstance(f, str) else f
+    if a == 1 and b == 1:
+        return l                                              # (one sample per stream: the same either way)
+    raise ValueError(f"shape {shape} with strides {strides} is {a} planes of {b} samples as well as {a} frames of {b} channels: say channels_first")
+
+
 def synth_fill_device(ptr, n_streams, n_frames, stride, seed, fs=48000.0, kind=1, stream=0):
     _check(lib.mtr_synth_fill_device(ptr, n_streams, n_frames, stride, seed, fs, kind, stream),
            "mtr_synth_fill_device")
@@ -613,6 +743,7 @@ class Engine:
                       tune_layout=tune_layout, tune_fir=tune_fir, tune_prune=tune_prune)
         self._h = C.c_void_p()
         self.n_streams, self.meters, self.sample_rate, self.n_channels = n_streams, meters, sample_rate, n_channels
+        self._device = device
         _check(lib.mtr_engine_create(C.byref(cfg), C.byref(self._h)), "mtr_engine_create")
 
     def close(self):
@@ -847,6 +978,99 @@ class Engine:
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib.mtr_engine_layout_stats(self._h, C.byref(a), C.byref(b)), "layout_stats")
         return a.value, b.value
+
+    def set_plane_layout(self, n_planes, map=None):
+        """The buffers of every later process call hold, per stream, `n_planes` planes of one channel each, the call's stride counting
+        from plane to plane; engine channel c = plane map[c] (mtr_engine_set_plane_layout, include/mtr_planes.h).  map=None: the identity,
+        which needs n_planes == n_channels; n_planes 0: back to the default.  It takes a frame layout away, as set_frame_layout takes this
+        one.  The host wrappers that check an array's shape (process, process_pcm, ...) go on expecting frames: planar buffers go through
+        process_tensor or process_raw."""
+        _need_planes()
+        m = None if not n_planes else _plane_map(map, int(n_planes), self.n_channels)
+        _check(lib.mtr_engine_set_plane_layout(self._h, int(n_planes), None if m is None else m.ctypes.data), "set_plane_layout")
+
+    def plane_layout(self):
+        """(n_planes, map) as mtr_engine_plane_layout reads them back: n_planes 0 without a plane layout."""
+        _need_planes()
+        p, m = C.c_uint32(), np.zeros(self.n_channels, np.uint8)
+        _check(lib.mtr_engine_plane_layout(self._h, C.byref(p), m.ctypes.data), "plane_layout")
+        return p.value, tuple(int(v) for v in m)
+
+    def plane_stats(self):
+        """chunks that went through the plane kernel since create"""
+        _need_planes()
+        a = C.c_uint64()
+        _check(lib.mtr_engine_plane_stats(self._h, C.byref(a)), "plane_stats")
+        return a.value
+
+    def process_raw(self, ptr, n_frames, stride=None, format=0, frames=None, family=None, host=False, stream=0):
+        """One process call on the buffer at address `ptr` as the layout in force describes it — host memory (host=True) or device memory
+        on `stream` —, nothing about it checked here: format 0 = float32, else PCM_*; frames: per-stream lengths; family: the pair of
+        entry points, by the names _device_frames / _host_frames use ("lengths", "tracks", "ragged", "ends", "tpb", "any", "gonio_ends"),
+        None: the plain call, the _lengths call with frames, the _pcm call for integer samples."""
+        stride = stride or n_frames
+        if format and family not in (None, "lengths"):
+            raise ValueError(f"integer PCM goes through the _pcm entry points, with per-stream lengths or without: no family {family!r}")
+        if frames is None and family is not None:
+            raise ValueError(f"family {family!r} takes per-stream lengths: frames")
+        if not host:                                             # the device forms: the wrappers above, which check nothing about a buffer
+            if format:
+                self.process_device_pcm(ptr, format, n_frames, stride, frames, stream)
+            elif frames is None:
+                self.process_device(ptr, n_frames, stride, stream)
+            else:
+                self._device_frames(family or "lengths", ptr, n_frames, frames, stride, stream)
+            return
+        # the host forms: the wrappers above take arrays and check their shape against a frame layout, so the entry points themselves
+        if format:
+            _need_pcm()
+            f = None if frames is None else self._frames(frames, "lengths")
+            _check(lib.mtr_engine_process_host_pcm(self._h, ptr, int(format), n_frames, stride, None if f is None else f.ctypes.data), "process_host_pcm")
+        elif frames is None:
+            _check(lib.mtr_engine_process_host(self._h, ptr, n_frames, stride), "process_host")
+        else:
+            family = family or "lengths"
+            f = self._frames(frames, family)
+            _check(getattr(lib, "mtr_engine_process_host_" + family)(self._h, ptr, n_frames, stride, f.ctypes.data), "process_host_" + family)
+
+    def process_tensor(self, t, channels_first=None, map=None, frames=None, family=None):
+        """One process call on a tensor as it lies: a torch tensor — on the engine's device: the device entry point on
+        torch.cuda.current_stream (); on the CPU: the host entry point — or a numpy array (host), float32 / int16 / int32, (batch, channel,
+        time) or (batch, time, channel), contiguous or a window in time of a longer one: what tensor_source () accepts, which also says how
+        channels_first and map are read.  Nothing is copied or transposed on the way: the call runs under the frame or plane layout the
+        tensor needs, and the layout that stood before stands again afterwards, also after an error.  frames / family as process_raw."""
+        _need_planes()
+        if hasattr(t, "data_ptr") and hasattr(t, "stride"):                  # a torch tensor
+            shape, strides, dev = tuple(t.shape), tuple(t.stride()), t.device
+            host = dev.type == "cpu"
+            if not host and (dev.type != "cuda" or dev.index != self._device):
+                raise ValueError(f"a tensor on {dev}: the engine is on device {self._device}")
+            ptr = t.data_ptr()
+        elif isinstance(t, np.ndarray):
+            if any(v % t.itemsize for v in t.strides):
+                raise ValueError(f"strides {t.strides} of {t.dtype} are no whole elements")
+            shape, strides, host, ptr = t.shape, tuple(v // t.itemsize for v in t.strides), True, t.ctypes.data
+        else:
+            raise ValueError(f"a torch tensor or a numpy array, not {type(t).__name__}")
+        src = tensor_source(shape, strides, t.dtype, self.n_channels, channels_first, map)
+        if shape[0] != self.n_streams:
+            raise ValueError(f"{shape[0]} streams in a tensor of shape {tuple(shape)}: the engine has {self.n_streams}")
+        stream = 0
+        if not host:
+            import torch
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        before_p, before_f = self.plane_layout(), self.frame_layout()
+        try:
+            if src.kind == "planes":
+                self.set_plane_layout(src.width, src.map)
+            else:
+                self.set_frame_layout(src.width, src.map)
+            self.process_raw(ptr, src.n_frames, src.stride, src.format, frames, family, host, stream)
+        finally:
+            if before_p[0]:
+                self.set_plane_layout(*before_p)
+            else:
+                self.set_frame_layout(*before_f)
 
     def _width(self):
         """samples per frame of the buffers a process call takes"""
