@@ -247,7 +247,7 @@ int  mtr_engine_prepare_host (mtr_engine* e, uint32_t max_block_frames);
                             two's complement                            x * 2^-23 */
 #define MTR_PCM_S32  3   /* int32_t, little endian          (float) x * 2^-31     */
 /* Host PCM: mtr_engine_process_host with one more step per chunk of streams — chunk k + 1's INTEGER rows cross the link on the
- * copy stream, k_pcm (mtr_pcm.hip) turns chunk k into floats on the engine's stream, the meters run on that float chunk, laid
+ * copy stream, k_pcm (mtr_source.hip) turns chunk k into floats on the engine's stream, the meters run on that float chunk, laid
  * out exactly as mtr_engine_process_host stages it (mtr_engine_set_host_chunk_bytes counts DECODED float bytes here, so the
  * chunks are those of the float path).  stream s at h_pcm + s * stream_stride_frames * n_channels * sample bytes.
  * frames == NULL: every stream advances by n_frames (as mtr_engine_process_host); else per-stream lengths with every rule of
@@ -287,7 +287,7 @@ int  mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, flo
  * mtr_engine_process_planar_host / _prepare_host take planar channels and are not affected.
  * A 5.1 file (WAVE order L R C LFE Ls Rs) on a 5-channel engine: frame_channels 6, map {0, 1, 2, 4, 5}; the stereo mix in channels
  * 6 and 7 of an 8-channel frame on a stereo engine: 8, {6, 7}; a mono file on a stereo engine (the reference's mono loudness is the
- * stereo loudness of L = R): 1, {0, 0}.  A call with a non-default layout runs k_pick (mtr_pick.hip) in front of the meters: the
+ * stereo loudness of L = R): 1, {0, 0}.  A call with a non-default layout runs k_pick (mtr_source.hip) in front of the meters: the
  * wide rows (for host memory: as they crossed the link) are decoded and picked into the float chunk the default layout would have
  * staged — for device memory in chunks of mtr_engine_set_host_chunk_bytes, as mtr_engine_process_device_pcm (set it to the picked
  * batch where HBM allows) —, so every result is bit for bit that of the default layout on mtr_pick_decode_host () of the same buffer.

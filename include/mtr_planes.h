@@ -11,7 +11,7 @@
  * whatever they hold, and nothing at or behind n_frames samples of a plane is read.
  * It applies to every entry point that honours a frame layout: mtr_engine_process_device / _host, _pcm, _lengths, _tracks, _ragged, _ends,
  * _tpb, _any, _gonio_ends.  mtr_engine_process_planar_host / _prepare_host (the LV2 block path, n_streams == 1) are not affected.
- * A call with a plane layout runs k_plane (mtr_plane.hip) in front of the meters: the planes (for host memory: as they crossed the link,
+ * A call with a plane layout runs k_plane (mtr_source.hip) in front of the meters: the planes (for host memory: as they crossed the link,
  * one 2-D copy of the chunk's P planes per stream) are decoded and interleaved into the float chunk the default layout would have staged —
  * for device memory in chunks of mtr_engine_set_host_chunk_bytes, as mtr_engine_process_device_pcm (set it to the decoded batch where HBM
  * allows) —, so every result is bit for bit that of the same entry point with the default layout on mtr_plane_decode_host () of each

@@ -180,34 +180,29 @@ struct CallRun {
 		return MTR_OK;
 	}
 
-	// A PCM chunk's first step: its integer rows to floats, where the meters will read them
+	// A chunk's first step (mtr_source.hip): its source — integer rows, wide frames, planes — to f32 frames, where the meters will read them
 	int decode ()
 	{
-		const uint64_t n = c.n_frames * e->cfg.n_channels;
-		const bool pcm = c.pcm_format != 0;                        // (wide f32 frames are picked, and nothing of it counts as PCM)
+		const Call::Decode& d = c.dec;
+		const uint32_t C = e->cfg.n_channels;
+		const bool pcm = d.format != 0;                            // (wide f32 frames and f32 planes are staged, and nothing of it counts as PCM)
 		hipEvent_t t0 = nullptr, t1 = nullptr;
 		if (pcm && e->timing && e->pcm_timed < 4096) {
 			t0 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2);
 			t1 = next_event (e->pcm_ev, (size_t) e->pcm_timed * 2 + 1);
 		}
 		if (t0 && t1) HIPCHK (hipEventRecord (t0, c.st));
-		if (c.plane_p) {
-			if (mtr_launch_plane (c.pcm_format, c.pcm, c.pcm_pitch, c.plane_p, e->plane_map, e->cfg.n_channels, const_cast<float*> (c.audio),
-			                      c.stride * e->cfg.n_channels, c.cnt, c.n_frames, c.st))
-				return fail (MTR_ERR_HIP, "k_plane launch");
-			e->plane_staged++;
-		} else if (c.pick_fc) {
-			if (mtr_launch_pick (c.pcm_format, c.pcm, c.pcm_pitch, c.pick_fc, e->frame_map, e->cfg.n_channels, const_cast<float*> (c.audio),
-			                     c.stride * e->cfg.n_channels, c.cnt, c.n_frames, c.st))
-				return fail (MTR_ERR_HIP, "k_pick launch");
-			if (pcm) e->lay_staged++;
-		} else if (mtr_launch_pcm (c.pcm_format, c.pcm, c.pcm_pitch, const_cast<float*> (c.audio), c.stride * e->cfg.n_channels, c.cnt, n, c.st))
-			return fail (MTR_ERR_HIP, "k_pcm launch");
+		if (mtr_launch_decode ({ d.kind, d.format, d.src, d.pitch, d.width, e->src.map, C, const_cast<float*> (c.audio), c.stride * C, c.cnt, c.n_frames, c.st }))
+			return fail (MTR_ERR_HIP, d.kind == MTR_DECODE_PLANES ? "k_plane launch" : d.kind == MTR_DECODE_FRAMES ? "k_pick launch" : "k_pcm launch");
 		if (t0 && t1) { HIPCHK (hipEventRecord (t1, c.st)); e->pcm_timed++; }
-		if (c.pcm_read) HIPCHK (hipEventRecord (c.pcm_read, c.st));
-		if (!pcm) { if (c.pick_fc) e->lay_staged++; return MTR_OK; }
-		e->pcm_chunks++;
-		e->pcm_bytes += (uint64_t) c.cnt * c.n_frames * (c.plane_p ? c.plane_p : c.pick_fc ? c.pick_fc : e->cfg.n_channels) * mtr_setup_pcm_sample_bytes (c.pcm_format);
+		if (d.read) HIPCHK (hipEventRecord (d.read, c.st));
+		// the counters: chunks per staging kernel; chunks and source bytes of the integer formats, whichever kernel decoded them
+		e->plane_staged += d.kind == MTR_DECODE_PLANES;
+		e->lay_staged += d.kind == MTR_DECODE_FRAMES;
+		if (pcm) {
+			e->pcm_chunks++;
+			e->pcm_bytes += (uint64_t) c.cnt * c.n_frames * d.width * mtr_setup_pcm_sample_bytes (d.format);
+		}
 		return MTR_OK;
 	}
 
@@ -458,11 +453,11 @@ struct CallRun {
 		if ((rc = enter_stream (e, c.st))) return rc;
 		const bool fused = ebu || tp;
 		const uint32_t meters = e->cfg.meters;
-		if (c.pcm && ((rc = mark (6, c.st)) || (rc = decode ()))) return rc;
+		if (c.dec.kind && ((rc = mark (6, c.st)) || (rc = decode ()))) return rc;
 		if ((rc = mark (0, c.st))) return rc;
 		if (tm) {
 			if (e->ev_decode.size () <= e->timed_calls) e->ev_decode.resize ((size_t) e->timed_calls + 1);
-			e->ev_decode[e->timed_calls] = c.pcm != nullptr;
+			e->ev_decode[e->timed_calls] = c.dec.kind != MTR_DECODE_NONE;
 		}
 
 		r = route ();
@@ -546,7 +541,6 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 	HIPCHK (hipSetDevice (e->cfg.device));
 	const size_t C = e->cfg.n_channels;
 	const uint32_t S = e->cfg.n_streams;
-	const size_t sb = src.format ? mtr_setup_pcm_sample_bytes (src.format) : sizeof (float);   // bytes per sample at the source
 	// (streams start on 16 bytes in the staging buffers — an even stride of stereo frames, a multiple of four mono ones — so that
 	// every layout can take the call and k_tpb's LDS-DMA its source)
 	const uint64_t dstride = C == 2 ? (n_frames + 1) & ~(uint64_t) 1 : (n_frames + 3) & ~(uint64_t) 3;   // (and 1, 3, 4, 5 channels: a multiple of four frames)
@@ -555,16 +549,24 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 	const uint32_t n_chunks = (S + cs - 1) / cs;
 	cs = (S + n_chunks - 1) / n_chunks;                                         // even chunks
 	const size_t buf_floats = ((size_t) cs * row + 63) & ~(size_t) 63;         // the second buffer starts on 256 bytes
-	// frame layout: the source rows hold frames of FC samples (the default: C), picked by the chunk's first step as PCM is decoded by it
-	const bool pick = e->picks;
-	const size_t FC = pick ? e->frame_channels : C;
-	// plane layout (it excludes the frame layout): per stream P planes of n_frames samples, `stride` samples from plane to plane; a row
-	// of the link copy and of the landing buffer is ONE PLANE, a chunk cnt * P of them, interleaved by the chunk's first step (k_plane)
-	const size_t P = e->planes ? e->plane_count : 0;
-	const size_t row_samples = P ? n_frames : n_frames * FC, rows_per_stream = P ? P : 1;
-	const size_t raw_pitch = (row_samples * sb + 15) & ~(size_t) 15;           // PCM / wide frames / planes from the host: bytes per landed row ...
-	const size_t raw_bytes = ((size_t) cs * rows_per_stream * raw_pitch + 255) & ~(size_t) 255;  // ... and per raw buffer
-	const bool landing = src.host && (src.format || pick || P);
+	// The source's geometry, once.  A ROW is what one row of the link copy and of the landing buffer is: a stream's frames — of the layout's
+	// width under a frame layout, which the chunk's first step picks as PCM is decoded by it —, or under a plane layout ONE PLANE of n_frames
+	// samples, `stride` samples from plane to plane, a chunk cnt * width of them, interleaved by the chunk's first step
+	const mtr_decode_kind kind = e->src.kind ? e->src.kind : src.format ? MTR_DECODE_ROWS : MTR_DECODE_NONE;
+	const bool planes = kind == MTR_DECODE_PLANES;
+	struct {
+		size_t sb, width;             // bytes per sample at the source; samples of a source frame, or planes of a stream
+		size_t rows, row_samples;     // rows per stream, samples per row
+		size_t pitch, land_pitch;     // bytes from row to row at the source, and where a host source's rows land
+	} g;
+	g.sb = src.format ? mtr_setup_pcm_sample_bytes (src.format) : sizeof (float);
+	g.width = e->src.kind ? e->src.width : C;
+	g.rows = planes ? g.width : 1;
+	g.row_samples = planes ? n_frames : n_frames * g.width;
+	g.pitch = (planes ? stride : stride * g.width) * g.sb;
+	const bool landing = src.host && kind;                                     // PCM / wide frames / planes from the host land raw, rows on 16 bytes
+	g.land_pitch = landing ? (g.row_samples * g.sb + 15) & ~(size_t) 15 : row * sizeof (float);
+	const size_t raw_bytes = ((size_t) cs * g.rows * g.land_pitch + 255) & ~(size_t) 255;   // bytes per raw buffer
 	hipStream_t st = (hipStream_t) src.hip_stream;
 	if (src.host) {
 		HIPCHK (e->own_stream.ensure ());
@@ -594,26 +596,18 @@ static int process_chunked (mtr_engine* e, const Source& src, uint64_t n_frames,
 		float* const dst = e->stage.p + (size_t) b * buf_floats;
 		// (the lengths of the chunk's streams are indexed from its first; the cursors move with the last chunk)
 		Call c { dst, n_frames, dstride, st, off, cnt, frames ? frames + off : nullptr, true, k + 1 == n_chunks };
-		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * stride * (P ? P : FC) * sb;
-		size_t pitch = P ? stride * sb : stride * FC * sb;
+		const uint8_t* from = (const uint8_t*) src.p + (size_t) off * g.rows * g.pitch;
+		size_t pitch = g.pitch;
 		if (src.host) {
 			void* const land = landing ? (void*) (e->pcm_raw.p + (size_t) b * raw_bytes) : (void*) dst;
-			const size_t land_pitch = landing ? raw_pitch : row * sizeof (float);
 			if (k >= 2) HOSTCHK (hipStreamWaitEvent (e->copy_stream.v, e->ev_computed[b].v, 0));   // the kernels of chunk k - 2 have read this buffer
-			HOSTCHK (hipMemcpy2DAsync (land, land_pitch, from, pitch, row_samples * sb, cnt * rows_per_stream, hipMemcpyHostToDevice, e->copy_stream.v));
+			HOSTCHK (hipMemcpy2DAsync (land, g.land_pitch, from, g.pitch, g.row_samples * g.sb, cnt * g.rows, hipMemcpyHostToDevice, e->copy_stream.v));
 			HOSTCHK (hipEventRecord (e->ev_copied[b].v, e->copy_stream.v));
 			HOSTCHK (hipStreamWaitEvent (st, e->ev_copied[b].v, 0));
 			from = (const uint8_t*) land;
-			pitch = land_pitch;
+			pitch = g.land_pitch;
 		}
-		if (src.format || pick || P) {
-			c.pcm = from;
-			c.pcm_pitch = pitch;
-			c.pcm_format = src.format;
-			c.pick_fc = pick ? (uint32_t) FC : 0;
-			c.plane_p = (uint32_t) P;
-			if (landing) c.pcm_read = e->ev_computed[b].v;
-		}
+		if (kind) c.dec = { kind, from, pitch, src.format, (uint32_t) g.width, landing ? e->ev_computed[b].v : nullptr };
 		rc = process_call (e, c);
 		if (rc) goto done;
 		if (src.host && !landing) HOSTCHK (hipEventRecord (e->ev_computed[b].v, st));
@@ -636,9 +630,9 @@ static int process_device (mtr_engine* e, const float* d_audio, uint64_t n_frame
 	// in front of an HBM-bound kernel would read 6/5 and write 5/5 of the batch on top).  Every other map: the wide rows are picked chunk
 	// by chunk into the staging buffers, as device PCM is decoded.
 	// (not beside the surround meter, whose kernel takes frames of the engine's five channels: that engine stages the call like any other map)
-	const bool direct = e->picks && e->wave51 && !(e->cfg.meters & MTR_METER_SURROUND);
+	const bool direct = e->src.wave51 && !(e->cfg.meters & MTR_METER_SURROUND);
 	// A plane layout: always staged, chunk by chunk through k_plane (no kernel of the meters reads planes)
-	if (e->planes || (e->picks && !direct)) return process_chunked (e, { d_audio, 0, false, hip_stream }, n_frames, stride, frames);
+	if (e->src.kind && !direct) return process_chunked (e, { d_audio, 0, false, hip_stream }, n_frames, stride, frames);
 	if (n_frames == 0) return MTR_OK;
 	if (stride < n_frames) return fail (MTR_ERR_ARG, "stream_stride_frames < n_frames");
 	HIPCHK (hipSetDevice (e->cfg.device));
@@ -895,135 +889,6 @@ int mtr_engine_process_device_pcm (mtr_engine* e, const void* d_pcm, int format,
 	const int crc = pcm_check (e, d_pcm, format, n_frames, frames, "mtr_engine_process_device_pcm: null argument");
 	if (crc) return crc;
 	return process_chunked (e, { d_pcm, format, false, hip_stream }, n_frames, stride, frames);
-}
-
-size_t mtr_pcm_sample_bytes (int format) { return mtr_setup_pcm_sample_bytes (format); }
-
-int mtr_pcm_decode_host (int format, const void* src, size_t n_samples, float* dst)
-{
-	if (!mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown PCM format (MTR_PCM_S16, _S24, _S32)");
-	if (n_samples && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_pcm_decode_host: null argument");
-	return mtr_setup_pcm_decode (format, src, n_samples, dst) ? fail (MTR_ERR_ARG, "mtr_pcm_decode_host") : MTR_OK;
-}
-
-int mtr_engine_pcm_stats (mtr_engine* e, uint64_t* chunks, uint64_t* bytes, float* decode_ms)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	if (e->pcm_timed) {
-		const int rc = mtr_engine_sync (e);
-		if (rc) return rc;
-		for (uint32_t i = 0; i < e->pcm_timed && (size_t) 2 * i + 1 < e->pcm_ev.size (); ++i) {
-			float ms;
-			if (hipEventElapsedTime (&ms, e->pcm_ev[2 * i].v, e->pcm_ev[2 * i + 1].v) == hipSuccess) e->pcm_ms += ms;
-		}
-		e->pcm_timed = 0;
-	}
-	if (chunks) *chunks = e->pcm_chunks;
-	if (bytes) *bytes = e->pcm_bytes;
-	if (decode_ms) *decode_ms = e->pcm_ms;
-	return MTR_OK;
-}
-
-static void plane_default (mtr_engine* e)
-{
-	e->planes = false;
-	e->plane_count = 0;
-	for (uint32_t c = 0; c < MTR_MAX_ENGINE_CHANNELS; ++c) e->plane_map[c] = (uint8_t) c;
-}
-
-int mtr_engine_set_frame_layout (mtr_engine* e, uint32_t frame_channels, const uint8_t* map)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	const uint32_t C = e->cfg.n_channels;
-	if (frame_channels == 0) {
-		e->frame_channels = 0;
-		for (uint32_t c = 0; c < MTR_MAX_ENGINE_CHANNELS; ++c) e->frame_map[c] = (uint8_t) c;
-		e->picks = e->wave51 = false;
-		plane_default (e);
-		return MTR_OK;
-	}
-	if (frame_channels > MTR_MAX_FRAME_CHANNELS) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: frame_channels > MTR_MAX_FRAME_CHANNELS");
-	if (!map) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: null map");
-	bool identity = frame_channels == C;
-	for (uint32_t c = 0; c < C; ++c) {
-		if (map[c] >= frame_channels) return fail (MTR_ERR_ARG, "mtr_engine_set_frame_layout: a map entry >= frame_channels");
-		identity = identity && map[c] == c;
-	}
-	e->frame_channels = frame_channels;
-	for (uint32_t c = 0; c < C; ++c) e->frame_map[c] = map[c];
-	e->picks = !identity;                                          // (the explicit identity is the default and takes its paths)
-	e->wave51 = e->layout == 8 && C == 5 && frame_channels == 6 && map[0] == 0 && map[1] == 1 && map[2] == 2 && map[3] == 4 && map[4] == 5;
-	plane_default (e);                                              // (frames or planes: the two exclude each other)
-	return MTR_OK;
-}
-
-int mtr_engine_set_plane_layout (mtr_engine* e, uint32_t n_planes, const uint8_t* map)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	const uint32_t C = e->cfg.n_channels;
-	if (n_planes > MTR_MAX_FRAME_CHANNELS) return fail (MTR_ERR_ARG, "mtr_engine_set_plane_layout: n_planes > MTR_MAX_FRAME_CHANNELS");
-	if (n_planes && !map) return fail (MTR_ERR_ARG, "mtr_engine_set_plane_layout: null map");
-	for (uint32_t c = 0; n_planes && c < C; ++c)
-		if (map[c] >= n_planes) return fail (MTR_ERR_ARG, "mtr_engine_set_plane_layout: a map entry >= n_planes");
-	const int rc = mtr_engine_set_frame_layout (e, 0, nullptr);      // (which also puts the plane layout back to its default)
-	if (rc || !n_planes) return rc;
-	e->plane_count = n_planes;
-	for (uint32_t c = 0; c < C; ++c) e->plane_map[c] = map[c];
-	e->planes = true;
-	return MTR_OK;
-}
-
-int mtr_engine_plane_layout (const mtr_engine* e, uint32_t* n_planes, uint8_t* map)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	if (n_planes) *n_planes = e->plane_count;
-	if (map) for (uint32_t c = 0; c < e->cfg.n_channels; ++c) map[c] = e->plane_map[c];
-	return MTR_OK;
-}
-
-int mtr_plane_decode_host (int format, const void* src, size_t n_frames, uint64_t stride_frames, uint32_t n_planes, const uint8_t* map, uint32_t n_channels,
-                           float* dst)
-{
-	if (format && !mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown format (0 = f32, MTR_PCM_S16, _S24, _S32)");
-	if (!map || !n_planes || n_planes > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_ENGINE_CHANNELS)
-		return fail (MTR_ERR_ARG, "mtr_plane_decode_host: map / n_planes / n_channels");
-	if (stride_frames < n_frames) return fail (MTR_ERR_ARG, "mtr_plane_decode_host: stride_frames < n_frames");
-	if (n_frames && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_plane_decode_host: null argument");
-	return mtr_setup_plane_decode (format, src, n_frames, stride_frames, n_planes, map, n_channels, dst)
-	       ? fail (MTR_ERR_ARG, "mtr_plane_decode_host: a map entry >= n_planes") : MTR_OK;
-}
-
-int mtr_engine_plane_stats (mtr_engine* e, uint64_t* staged_chunks)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	if (staged_chunks) *staged_chunks = e->plane_staged;
-	return MTR_OK;
-}
-
-int mtr_engine_frame_layout (const mtr_engine* e, uint32_t* frame_channels, uint8_t* map)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	if (frame_channels) *frame_channels = e->frame_channels ? e->frame_channels : e->cfg.n_channels;
-	if (map) for (uint32_t c = 0; c < e->cfg.n_channels; ++c) map[c] = e->frame_map[c];
-	return MTR_OK;
-}
-
-int mtr_pick_decode_host (int format, const void* src, size_t n_frames, uint32_t frame_channels, const uint8_t* map, uint32_t n_channels, float* dst)
-{
-	if (format && !mtr_setup_pcm_sample_bytes (format)) return fail (MTR_ERR_ARG, "unknown format (0 = f32, MTR_PCM_S16, _S24, _S32)");
-	if (!map || !frame_channels || frame_channels > MTR_MAX_FRAME_CHANNELS || !n_channels || n_channels > MTR_MAX_ENGINE_CHANNELS)
-		return fail (MTR_ERR_ARG, "mtr_pick_decode_host: map / frame_channels / n_channels");
-	if (n_frames && (!src || !dst)) return fail (MTR_ERR_ARG, "mtr_pick_decode_host: null argument");
-	return mtr_setup_pick_decode (format, src, n_frames, frame_channels, map, n_channels, dst)
-	       ? fail (MTR_ERR_ARG, "mtr_pick_decode_host: a map entry >= frame_channels") : MTR_OK;
-}
-
-int mtr_engine_layout_stats (mtr_engine* e, uint64_t* staged_chunks, uint64_t* direct_calls)
-{
-	if (!e) return fail (MTR_ERR_ARG, "null engine");
-	if (staged_chunks) *staged_chunks = e->lay_staged;
-	if (direct_calls) *direct_calls = e->lay_direct;
-	return MTR_OK;
 }
 
 // One LV2 block: interleave into page-locked memory, one H2D copy, the kernels, one D2H copy of the stream's state

@@ -1,5 +1,5 @@
 // mtr_engine_impl.h — what the host side of libmtr_engine.so shares between its TUs: mtr_engine.hip (create / reset, the tail, the
-// EBU / true-peak getters), mtr_call.hip (one process call), mtr_state.hip (the state blob) and the host half of every side meter, which
+// EBU / true-peak getters), mtr_call.hip (one process call), mtr_source.hip (the source step and the engine's source layout), mtr_state.hip (the state blob) and the host half of every side meter, which
 // lives next to its kernels (mtr_bank.hip, mtr_intstat.hip, mtr_dr14.hip, mtr_kmeter.hip, mtr_stcorr.hip, mtr_needle.hip, mtr_surround.hip, mtr_scope.hip, mtr_tpb.hip, mtr_gonio.hip), and mtr_loudlog.hip (the host
 // side of the loudness log, whose points the gate writes).  Not installed; needs the HIP
 // runtime header, so the planner (mtr_plan.cpp) never sees it.
@@ -121,6 +121,17 @@ struct Cursors {
 	int      go_hist_cur = 0;     // GONIO oversampled: which of go.os_hist [2] holds the 23 input frames before the next call
 };
 
+// What the buffers of a process call hold (mtr_engine_set_frame_layout, mtr_engine_set_plane_layout: one at a time).  MTR_DECODE_NONE: frames
+// of the engine's channels, the default — an explicit identity frame layout is that too; _FRAMES: frames of `width` samples, engine
+// channel c = source channel map[c], every chunk through k_pick; _PLANES: `width` planes of one channel per stream, channel c = plane
+// map[c], every chunk through k_plane
+struct SourceLayout {
+	mtr_decode_kind kind = MTR_DECODE_NONE;
+	uint32_t        width = 0;
+	uint8_t         map[MTR_MAX_ENGINE_CHANNELS] = { 0, 1, 2, 3, 4, 5, 6, 7 };
+	bool            wave51 = false;   // frames of 6, {0, 1, 2, 4, 5} on a 5-channel engine: device f32 calls go to k_kwmc51 instead of k_pick
+};
+
 // per-stream state of the side meters: defined where their kernels are
 struct mtr_sigdist_state;
 struct mtr_dr14_state;
@@ -219,27 +230,17 @@ struct mtr_engine {
 	size_t           host_chunk_bytes = (size_t) 256 << 20;
 	Stream           copy_stream;
 	Event            ev_copied[2], ev_computed[2];   // per staging buffer: the chunk has landed / its landing buffer has been read
-	// integer PCM in (mtr_engine_process_*_pcm): the host form's integer rows land in two raw buffers of one chunk each, k_pcm
-	// (mtr_pcm.hip) decodes a chunk from there — or from the caller's device rows — into `stage`
+	// The source step (mtr_source.hip): whatever is not resident f32 frames of n_channels — integer PCM, a frame layout, a plane layout —
+	// is decoded chunk by chunk into `stage`, from two raw landing buffers of one chunk each (host memory) or from the caller's rows
+	// (device memory)
 	DevBuf<uint8_t>  pcm_raw;
-	uint64_t         pcm_chunks = 0, pcm_bytes = 0;
+	SourceLayout     src;
+	uint64_t         pcm_chunks = 0, pcm_bytes = 0;   // integer formats only, whichever kernel decoded them
+	uint64_t         lay_staged = 0, lay_direct = 0;  // chunks through k_pick; device calls whose kernels read WAVE 5.1 frames themselves
+	uint64_t         plane_staged = 0;                // chunks through k_plane
 	std::vector<Event> pcm_ev;      // while timing is on: pairs around the decode kernels not yet summed into pcm_ms
 	uint32_t         pcm_timed = 0;
 	float            pcm_ms = 0.f;
-	// frame layout (mtr_engine_set_frame_layout): the buffers of a process call hold frames of frame_channels samples, engine channel c
-	// is source channel frame_map[c]; 0 = the default.  `picks`: the layout is not the identity, every chunk goes through k_pick
-	// (mtr_pick.hip) — from the raw landing buffers (host memory) or the caller's rows (device memory) into `stage`
-	uint32_t         frame_channels = 0;
-	uint8_t          frame_map[MTR_MAX_ENGINE_CHANNELS] = { 0, 1, 2, 3, 4, 5, 6, 7 };
-	bool             picks = false;
-	bool             wave51 = false;      // ... and it is 6, {0, 1, 2, 4, 5} on a 5-channel engine: device f32 calls go to k_kwmc51 instead
-	uint64_t         lay_staged = 0, lay_direct = 0;
-	// plane layout (mtr_engine_set_plane_layout, mtr_planes.h): the buffers hold plane_count planes of one channel per stream, engine
-	// channel c is plane plane_map[c].  `planes`: one is set (it excludes `picks`), every chunk goes through k_plane (mtr_plane.hip)
-	bool             planes = false;
-	uint32_t         plane_count = 0;
-	uint8_t          plane_map[MTR_MAX_ENGINE_CHANNELS] = { 0, 1, 2, 3, 4, 5, 6, 7 };
-	uint64_t         plane_staged = 0;
 
 	bool timing = false;
 	std::vector<Event> ev;          // groups of EV_PER_CALL: start, fused end, gate begin, gate end (those two on the stream the gate ran on), rest begin, end; a PCM chunk's start in front of its decode
@@ -378,16 +379,17 @@ struct Call {
 	const uint64_t* frames;       // per-stream lengths, indexed from the view's first stream, or nullptr
 	bool            chunk;        // a chunk of a host call (mtr_engine_process_host walks the batch view by view), not a batch of its own
 	bool            commit;       // the lock-step cursors move with this call: the last view of a host call, every other call
-	// integer PCM: the call first decodes the view's rows from `pcm` (device memory, row pitch in bytes) into `audio` — a staging buffer
-	// of the engine's — with k_pcm, and records `pcm_read` (if any) behind that: the integer rows have been read
-	const void*     pcm = nullptr;
-	uint64_t        pcm_pitch = 0;
-	int             pcm_format = 0;
-	hipEvent_t      pcm_read = nullptr;
-	// frame layout: the rows at `pcm` (format 0: f32) hold frames of pick_fc samples, k_pick decodes and picks them (0: k_pcm on frames of C)
-	uint32_t        pick_fc = 0;
-	// plane layout: `pcm` holds plane_p planes per stream, pcm_pitch bytes from plane to plane; k_plane decodes and interleaves them
-	uint32_t        plane_p = 0;
+	// The source step: the call first decodes the view's rows from dec.src (device memory) into `audio` — a staging buffer of the
+	// engine's — and records dec.read (if any) behind that: the source has been read.  The fields are mtr_decode_args' (width: the
+	// samples of a source frame — n_channels for _ROWS —, or the planes); the default: no decode
+	struct Decode {
+		mtr_decode_kind kind = MTR_DECODE_NONE;
+		const void*     src = nullptr;
+		uint64_t        pitch = 0;
+		int             format = 0;
+		uint32_t        width = 0;
+		hipEvent_t      read = nullptr;
+	} dec;
 	// ... or `audio` itself holds WAVE 5.1 frames, [cnt][stride][6], which the 5-channel kernels read themselves (k_kwmc51, k_history with FC = 6)
 	bool            wave51 = false;
 };

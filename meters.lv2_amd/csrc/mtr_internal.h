@@ -289,16 +289,30 @@ int  mtr_launch_tpb_series_ends (const mtr_tpb_series_ends_args& a, void* stream
 int  mtr_launch_bitstats (const float* audio, uint64_t stride, uint64_t n_frames, mtr_bitstats_state* out,
                           uint32_t n_streams, const uint32_t* ends, void* stream);
 int  mtr_launch_aggregate (const mtr_stream_state* st, const int32_t* hist, uint32_t n_streams, int32_t* d_hist, float* d_max, void* stream);
-/* rows of packed integer PCM (format MTR_PCM_*, n_samples per row, pitch in bytes) to rows of f32 (pitch in floats): mtr_pcm.hip */
-int  mtr_launch_pcm (int format, const void* src, uint64_t src_pitch, float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_samples, void* stream);
-/* rows of n_frames wide frames (frame_channels samples: format 0 = f32, else MTR_PCM_*; pitch in bytes) to rows of n_frames x n_channels
- * f32 (pitch in floats), channel c = source channel map[c]: mtr_pick.hip */
-int  mtr_launch_pick (int format, const void* src, uint64_t src_pitch, uint32_t frame_channels, const uint8_t* map, uint32_t n_channels,
-                      float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_frames, void* stream);
-/* per row n_planes planes of n_frames samples (format 0 = f32, else MTR_PCM_*; plane p of row r at src + (r * n_planes + p) * plane_pitch
- * BYTES) to rows of n_frames x n_channels f32 (pitch in floats), channel c = plane map[c]: mtr_plane.hip */
-int  mtr_launch_plane (int format, const void* src, uint64_t plane_pitch, uint32_t n_planes, const uint8_t* map, uint32_t n_channels,
-                       float* dst, uint64_t dst_pitch, uint32_t n_rows, uint64_t n_frames, void* stream);
+/* The source step (mtr_source.hip): the caller's bytes to rows of n_frames x n_channels f32.  What the source is: */
+enum mtr_decode_kind {
+	MTR_DECODE_NONE,           /* f32 frames of n_channels: the meters read them where they lie */
+	MTR_DECODE_ROWS,           /* k_pcm: rows of n_frames x n_channels packed integer samples (format MTR_PCM_*), `pitch` bytes from row to row */
+	MTR_DECODE_FRAMES,         /* k_pick: rows of n_frames frames of `width` samples, channel c = source channel map[c] */
+	MTR_DECODE_PLANES          /* k_plane: per row `width` planes of n_frames samples, `pitch` bytes from PLANE to plane (plane p of row r
+	                            * at src + (r * width + p) * pitch), channel c = plane map[c] */
+};
+struct mtr_decode_args {
+	mtr_decode_kind kind;
+	int             format;       /* 0 = f32 (FRAMES and PLANES only), else MTR_PCM_* */
+	const void*     src;
+	uint64_t        pitch;        /* bytes */
+	uint32_t        width;        /* frame_channels or n_planes; ROWS: not read */
+	const uint8_t*  map;          /* [n_channels] entries below width; ROWS: not read */
+	uint32_t        n_channels;
+	float*          dst;
+	uint64_t        dst_pitch;    /* floats */
+	uint32_t        n_rows;
+	uint64_t        n_frames;
+	void*           stream;
+};
+/* -1: a kind, format, width, channel count or map entry out of range, planes that overlap (pitch < n_frames samples), a launch error */
+int  mtr_launch_decode (const mtr_decode_args& a);
 int  mtr_launch_synth (float* d_audio, uint32_t n_streams, uint64_t n_frames, uint64_t stride,
                        uint32_t seed, float fs, int kind, void* stream);
 #endif

@@ -228,7 +228,7 @@ void mtr_setup_hist_loudness (const int32_t* hm, const int32_t* hs, float* integ
 
 /* Integer PCM to float, the contract of include/mtr_engine.h (MTR_PCM_*): little-endian samples read byte-wise through
  * memcpy (any alignment), S16 / S24 exact, S32 the int-to-float conversion (round to nearest even) and an exact scale.
- * What k_pcm (mtr_pcm.hip) is held against. */
+ * What k_pcm (mtr_source.hip) is held against. */
 size_t mtr_setup_pcm_sample_bytes (int format)
 {
 	return format == MTR_PCM_S16 ? 2 : format == MTR_PCM_S24 ? 3 : format == MTR_PCM_S32 ? 4 : 0;
@@ -266,38 +266,39 @@ int mtr_setup_pcm_decode (int format, const void* src, size_t n, float* dst)
 	return -1;
 }
 
-/* Frames of fc samples to frames of C floats, channel c = source channel map[c] (mtr_engine_set_frame_layout): f32 samples move as
- * bit patterns (memcpy: a NaN keeps its payload), integers convert as above.  What k_pick (mtr_pick.hip) is held against. */
+/* n_frames frames of C floats from the samples of ONE stream: channel c of frame i is the sample (i * frame_step + map[c] * chan_step) of
+ * `src`, the steps in samples.  f32 samples move as bit patterns (memcpy: a NaN keeps its payload), integers convert as above. */
+static void gather_decode (int format, size_t sb, const void* src, size_t n_frames, size_t frame_step, size_t chan_step, const uint8_t* map, uint32_t C,
+                           float* dst)
+{
+	const unsigned char* p = (const unsigned char*) src;
+	for (size_t i = 0; i < n_frames; ++i)
+		for (uint32_t c = 0; c < C; ++c) {
+			const unsigned char* s = p + (i * frame_step + map[c] * chan_step) * sb;
+			if (format) mtr_setup_pcm_decode (format, s, 1, dst + i * C + c);
+			else memcpy (dst + i * C + c, s, sizeof (float));
+		}
+}
+
+/* Frames of fc samples to frames of C floats, channel c = source channel map[c] (mtr_engine_set_frame_layout).  What k_pick
+ * (mtr_source.hip) is held against. */
 int mtr_setup_pick_decode (int format, const void* src, size_t n_frames, uint32_t fc, const uint8_t* map, uint32_t C, float* dst)
 {
 	const size_t sb = format ? mtr_setup_pcm_sample_bytes (format) : sizeof (float);
 	if (!sb || !map || !fc || !C) return -1;
 	for (uint32_t c = 0; c < C; ++c) if (map[c] >= fc) return -1;
-	const unsigned char* p = (const unsigned char*) src;
-	for (size_t i = 0; i < n_frames; ++i)
-		for (uint32_t c = 0; c < C; ++c) {
-			const unsigned char* s = p + (i * fc + map[c]) * sb;
-			if (format) mtr_setup_pcm_decode (format, s, 1, dst + i * C + c);
-			else memcpy (dst + i * C + c, s, sizeof (float));
-		}
+	gather_decode (format, sb, src, n_frames, fc, 1, map, C, dst);
 	return 0;
 }
 
 /* One stream's P planes of one channel each (plane p at src + p * stride samples) to n_frames frames of C floats, channel c = plane map[c]
- * (mtr_engine_set_plane_layout): samples move as in mtr_setup_pick_decode.  What k_plane (mtr_plane.hip) is held against. */
+ * (mtr_engine_set_plane_layout).  What k_plane (mtr_source.hip) is held against. */
 int mtr_setup_plane_decode (int format, const void* src, size_t n_frames, uint64_t stride, uint32_t P, const uint8_t* map, uint32_t C, float* dst)
 {
 	const size_t sb = format ? mtr_setup_pcm_sample_bytes (format) : sizeof (float);
 	if (!sb || !map || !P || !C || stride < n_frames) return -1;
 	for (uint32_t c = 0; c < C; ++c) if (map[c] >= P) return -1;
-	const unsigned char* p = (const unsigned char*) src;
-	for (uint32_t c = 0; c < C; ++c) {
-		const unsigned char* pl = p + (size_t) map[c] * stride * sb;
-		for (size_t i = 0; i < n_frames; ++i) {
-			if (format) mtr_setup_pcm_decode (format, pl + i * sb, 1, dst + i * C + c);
-			else memcpy (dst + i * C + c, pl + i * sb, sizeof (float));
-		}
-	}
+	gather_decode (format, sb, src, n_frames, 1, (size_t) stride, map, C, dst);
 	return 0;
 }
 

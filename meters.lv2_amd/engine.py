@@ -489,19 +489,28 @@ def _pcm_format(x, format):
     return want
 
 
+def _samples(x, format, what, f32=True):
+    """Array `x` as a source of samples: (format, bytes per sample, samples on the last axis).  Format 0 takes float32 (f32=False: the
+    caller takes integers only); an integer format is checked against the dtype — None: inferred from it — by _pcm_format, and the last
+    axis of PCM_S24's packed bytes holds whole samples: `what`."""
+    if format == 0 and f32:
+        if x.dtype != np.float32:
+            raise ValueError(f"format 0 takes float32, not {x.dtype}")
+        return 0, 4, x.shape[-1]
+    fmt = _pcm_format(x, format)
+    sb = {PCM_S16: 2, PCM_S24: 3, PCM_S32: 4}[fmt]
+    if x.shape[-1] * x.itemsize % sb:
+        raise ValueError(f"PCM_S24: the last axis holds {what}, not {x.shape}")
+    return fmt, sb, x.shape[-1] * x.itemsize // sb
+
+
 def pcm_decode(format, array):
     """mtr_pcm_decode_host: the integer samples of `array` (int16 for PCM_S16, int32 for PCM_S32, packed little-endian uint8 bytes
     for PCM_S24) as float32 — the same shape, PCM_S24 a third of the last axis.  The definition the GPU decode is held against."""
     _need_pcm()
     x = np.ascontiguousarray(array)
-    _pcm_format(x, format)
-    if format == PCM_S24:
-        if x.ndim == 0 or x.shape[-1] % 3:
-            raise ValueError(f"PCM_S24: the last axis holds 3 bytes per sample, not {x.shape}")
-        shape = x.shape[:-1] + (x.shape[-1] // 3,)
-    else:
-        shape = x.shape
-    out = np.empty(shape, np.float32)
+    format, _, n = _samples(x, format, "3 bytes per sample", f32=False)
+    out = np.empty(x.shape[:-1] + (n,), np.float32)
     _check(lib.mtr_pcm_decode_host(format, x.ctypes.data, out.size, out.ctypes.data), "mtr_pcm_decode_host")
     return out
 
@@ -522,18 +531,7 @@ def pick_decode(format, array, map, n_channels=None):
     if m.ndim != 1 or m.size != n_channels:
         raise ValueError(f"map: {n_channels} entries, not {m.shape}")
     x = np.ascontiguousarray(array)
-    if format == 0:
-        if x.dtype != np.float32:
-            raise ValueError(f"format 0 takes float32, not {x.dtype}")
-        fc = x.shape[-1]
-    else:
-        _pcm_format(x, format)
-        if format == PCM_S24:
-            if x.shape[-1] % 3:
-                raise ValueError(f"PCM_S24: the last axis holds frame_channels * 3 bytes, not {x.shape}")
-            fc = x.shape[-1] // 3
-        else:
-            fc = x.shape[-1]
+    format, _, fc = _samples(x, format, "frame_channels * 3 bytes")
     out = np.empty(x.shape[:-1] + (n_channels,), np.float32)
     n_frames = out.size // n_channels
     _check(lib.mtr_pick_decode_host(int(format), x.ctypes.data, n_frames, fc, m.ctypes.data, n_channels, out.ctypes.data), "mtr_pick_decode_host")
@@ -567,17 +565,8 @@ def plane_decode(format, array, map, n_channels=None, stride=None):
     x = np.asarray(array)
     if x.ndim < 2:
         raise ValueError(f"planes: [..., P, n_frames], not {x.shape}")
-    if format == 0:
-        if x.dtype != np.float32:
-            raise ValueError(f"format 0 takes float32, not {x.dtype}")
-        sb = 4
-    else:
-        _pcm_format(x, format)
-        sb = {PCM_S16: 2, PCM_S24: 3, PCM_S32: 4}[format]
-    P, row = x.shape[-2], x.shape[-1] * x.itemsize
-    if row % sb:
-        raise ValueError(f"PCM_S24: the last axis holds n_frames * 3 bytes, not {x.shape}")
-    n_frames = row // sb
+    format, sb, n_frames = _samples(x, format, "n_frames * 3 bytes")
+    P = x.shape[-2]
     if n_frames > 1 and x.strides[-1] != x.itemsize:
         raise ValueError(f"planes: the last axis must be contiguous, strides {x.strides}")
     if stride is None:
@@ -927,8 +916,8 @@ class Engine:
         or packed 24-bit samples as uint8 [S, T * C * 3] with format=PCM_S24.  frames: per-stream lengths as process_lengths()."""
         _need_pcm()
         x = np.ascontiguousarray(x)
-        fmt = _pcm_format(x, format)
         C_ = self._width()                                       # (frames of frame_channels samples once a layout is set)
+        fmt = _samples(x, format, f"T * {C_} * 3 bytes", f32=False)[0]
         if fmt == PCM_S24:
             if x.ndim != 2 or x.shape[0] != self.n_streams or x.shape[1] % (3 * C_):
                 raise ValueError(f"PCM_S24: uint8 [{self.n_streams}, T * {C_} * 3], not {x.shape}")
@@ -937,8 +926,7 @@ class Engine:
             if x.shape[:1] != (self.n_streams,) or not (x.shape[2:] == (C_,) and x.ndim == 3 or (C_ == 1 and x.ndim == 2)):
                 raise ValueError(f"integer PCM: [{self.n_streams}, T, {C_}]" + (" or [S, T]" if C_ == 1 else "") + f", not {x.shape}")
             n = x.shape[1]
-        f = None if frames is None else self._frames(frames, "lengths")
-        _check(lib.mtr_engine_process_host_pcm(self._h, x.ctypes.data, fmt, n, n, None if f is None else f.ctypes.data), "process_host_pcm")
+        self.process_raw(x.ctypes.data, n, n, fmt, frames, host=True)
 
     def process_device_pcm(self, ptr, format, n_frames, stride=None, frames=None, stream=0):
         """process_device() for integer PCM in device memory at `ptr` (stream s at ptr + s * stride * n_channels * sample bytes): one

@@ -1,6 +1,6 @@
 """Frame layouts (mtr_engine_set_frame_layout): the surface and the pick / decode contract, without a GPU.
 
-mtr_pick_decode_host is what k_pick (mtr_pick.hip) is held against (tests/test_gpu_frames.py), so it is pinned here to numpy
+mtr_pick_decode_host is what k_pick (mtr_source.hip) is held against (tests/test_gpu_frames.py), so it is pinned here to numpy
 BIT FOR BIT: `decode (x)[:, map]`, compared as uint32 views — a NaN keeps its payload, -0.0 stays -0.0.
 """
 import ctypes as C

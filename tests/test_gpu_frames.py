@@ -1,4 +1,4 @@
-"""Frame layouts on the GPU: mtr_engine_set_frame_layout (include/mtr_engine.h), k_pick (mtr_pick.hip) in front of the meters.
+"""Frame layouts on the GPU: mtr_engine_set_frame_layout (include/mtr_engine.h), k_pick (mtr_source.hip) in front of the meters.
 
 The rule of tests/test_gpu_pcm.py, no tolerance anywhere: a call with a layout on the WIDE buffer against the same entry point with
 the default layout on pick_decode of that buffer (for PCM: on the compacted integers), same set_host_chunk_bytes — every record of

@@ -1,4 +1,4 @@
-"""Integer PCM in, decoded on the GPU: mtr_engine_process_host_pcm / _device_pcm (include/mtr_engine.h, k_pcm in mtr_pcm.hip).
+"""Integer PCM in, decoded on the GPU: mtr_engine_process_host_pcm / _device_pcm (include/mtr_engine.h, k_pcm in mtr_source.hip).
 
 The conversion is exact integer-to-float (tests/test_pcm_cpu.py pins mtr_pcm_decode_host to numpy bit for bit), and the float
 chunk a PCM call hands the meters is laid out exactly as mtr_engine_process_host stages it.  So the comparison is always

@@ -1,4 +1,4 @@
-"""Plane layouts on the GPU: mtr_engine_set_plane_layout (include/mtr_planes.h), k_plane (mtr_plane.hip) in front of the meters.
+"""Plane layouts on the GPU: mtr_engine_set_plane_layout (include/mtr_planes.h), k_plane (mtr_source.hip) in front of the meters.
 
 The rule of tests/test_gpu_frames.py, no tolerance anywhere: a call with a plane layout on the PLANAR buffer against the same entry point
 with the default layout on plane_decode of that buffer (for PCM: on the interleaved integers, whose pcm_decode is checked to be that
