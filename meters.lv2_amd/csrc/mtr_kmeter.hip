@@ -16,8 +16,14 @@
 // [4 w a (a^k - b^k) / (a - b), b^k]]), sums in double, and a one-thread-per-channel kernel adds the chunks and
 // A^G times the carried state and does the per-call bookkeeping.  (First version: pieces run serially from a
 // zero state, four groups per lane, and combined in a tree: each lane read its own 128 contiguous bytes — 8.1 ms
-// per 31.5 GB.)  The sums are re-associated and carried in double: tests/test_gpu_kmeter.py states 1e-5
-// relative against the restatement.
+// per 31.5 GB.)  The sums are re-associated and carried in double: tests/test_gpu_kmeter.py holds the RMS to
+// 4 * 2^-24 relative against the same recurrence in double (oracle mo_kmeter_process_f64).
+// A square that is not finite (a sample that is, or |x| > 1.84e19) is not linear: the reference's z1 becomes Inf, the
+// next frame makes it NaN (Inf - Inf), :101-102 zero the states — the reading is 0 and the next call starts from 0 —
+// unless it is the last frame the stream takes (k == 0, slot 3; with LEN too), where the states end as Inf, the reading
+// is Inf and the next call starts from the clamp at 50.  A weighted sum would read Inf wherever the weight is not 0
+// and NaN -> 0 where a^k has underflowed: the sums take km_square (s) (mtr_kmeter_dsp.h, the series' and SURROUND's
+// rule), a NaN for such a square anywhere but there; the maximum takes s itself (:103 zeroes an infinite one).
 //
 // LEN (both kernels): the call carries per-stream ends (a.ends, call-relative: mtr_engine_process_*_tracks, or any call once a stream of
 // its view is closed).  Stream s ends at frame E = ends [s], workgroup-uniform (one scalar load): a stream that ends inside the call sees
@@ -155,6 +161,7 @@ __global__ __launch_bounds__ (NT) void k_kmeter_pieces (const mtr_kmeter_args a)
 			for (int i = 0; i < 4 * C; ++i) v[i] = p[i];
 		}
 		const double U1 = m.a, U2 = m.c + w4 * m.b;
+		const int64_t j0 = (int64_t) (n_groups - 1 - k) * 4, Lg = (int64_t) n_groups * 4;   // the group's first frame; the frames the stream takes
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			const float s0 = v[c] * v[c], s1 = v[C + c] * v[C + c], s2 = v[2 * C + c] * v[2 * C + c], s3 = v[3 * C + c] * v[3 * C + c];
@@ -162,7 +169,13 @@ __global__ __launch_bounds__ (NT) void k_kmeter_pieces (const mtr_kmeter_args a)
 			t[c] = t[c] < s1 ? s1 : t[c];
 			t[c] = t[c] < s2 ? s2 : t[c];
 			t[c] = t[c] < s3 ? s3 : t[c];
-			const double g = (double) (u0 * s0) + (double) (u1 * s1) + (double) (u2 * s2) + (double) (u3 * s3);
+			// a square that is not finite: NaN into the sums, unless it is the last frame the stream takes (km_square; the maximum took s
+			// itself).  One test per group: the sum of four squares is finite only if each is, and km_square keeps a finite one as it is
+			float q0 = s0, q1 = s1, q2 = s2, q3 = s3;
+			if (!isfinite ((s0 + s1) + (s2 + s3))) {
+				q0 = km_square (s0, j0, Lg); q1 = km_square (s1, j0 + 1, Lg); q2 = km_square (s2, j0 + 2, Lg); q3 = km_square (s3, j0 + 3, Lg);
+			}
+			const double g = (double) (u0 * q0) + (double) (u1 * q1) + (double) (u2 * q2) + (double) (u3 * q3);
 			z1[c] += U1 * g;
 			z2[c] += U2 * g;
 		}

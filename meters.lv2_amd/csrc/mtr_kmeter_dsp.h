@@ -1,6 +1,7 @@
 // mtr_kmeter_dsp.h — Kmeterdsp (jmeters/kmeterdsp.cc) as the three "pieces + walk" meters compute it: KMETER's reading series
 // (mtr_kmeter.hip: k_kmeter_blocks / k_kmeter_walk), SURROUND's C K-meters (mtr_surround.hip: the walk, final_channel) and, for the
-// bookkeeping at the end of a process (), KMETER without a period (k_kmeter_final).  One copy of the constants, of a piece's geometry, of
+// rule for a square that is not finite (k_kmeter_pieces) and the bookkeeping at the end of a process () (k_kmeter_final), KMETER without
+// a period.  One copy of the constants, of a piece's geometry, of
 // a lane's weights and of what a walker does between two pieces and at a block's end.  Host + device, header only; the loops — how a
 // lane gets its frames, how a workgroup reduces, what a meter carries between two calls — stay with the kernels.  k_sur_pieces computes
 // the same weights by statements of its own (mtr_surround.hip says why): whoever changes KmLane or km_square changes them there too.

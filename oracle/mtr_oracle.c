@@ -764,6 +764,56 @@ void mo_kmeter_process (mo_kmeter* k, const float* p, int n)
 	}
 }
 
+/* The float64 yardstick of mo_kmeter_process: the same statements with z1, z2 and the filter's arithmetic in double (omega: the f32
+ * value widened; the square is still formed in f32, as the reference forms it).  From :101 on it is the f32 restatement: the states
+ * are rounded to f32 where they are stored.  What a kernel that re-associates the sums in double is held to */
+void mo_kmeter_process_f64 (mo_kmeter* k, const float* p, int n)
+{
+	if (k->fpp != n) {
+		const float fall = 15.0f;
+		const float tme = (float) n / k->fsamp;
+		k->fall = powf (10.0f, -0.05f * fall * tme);
+		k->fpp = n;
+	}
+	float s, t = 0;
+	double z1 = k->z1 > 50 ? 50 : (k->z1 < 0 ? 0 : k->z1);
+	double z2 = k->z2 > 50 ? 50 : (k->z2 < 0 ? 0 : k->z2);
+	const double omega = (double) k->omega;
+	n /= 4;
+	while (n--) {
+		for (int q = 0; q < 4; ++q) {
+			s = *p++;
+			s *= s;
+			if (t < s) t = s;
+			z1 += omega * ((double) s - z1);
+		}
+		z2 += 4 * omega * (z1 - z2);
+	}
+	float f1 = (float) z1, f2 = (float) z2;
+	if (isnan (f1)) f1 = 0;
+	if (isnan (f2)) f2 = 0;
+	if (!isfinite (t)) t = 0;
+	k->z1 = f1 + 1e-20f;
+	k->z2 = f2 + 1e-20f;
+	s = sqrtf (2.0f * f2);
+	t = sqrtf (t);
+	if (k->flag) {
+		k->rms = s;
+		k->flag = 0;
+	} else if (s > k->rms) {
+		k->rms = s;
+	}
+	if (t >= k->peak) {
+		k->peak = t;
+		k->cnt = k->hold;
+	} else if (k->cnt > 0) {
+		k->cnt -= k->fpp;
+	} else {
+		k->peak *= k->fall;
+		k->peak += 1e-10f;
+	}
+}
+
 void mo_kmeter_read (mo_kmeter* k, float* rms, float* peak)
 {
 	*rms = k->rms;

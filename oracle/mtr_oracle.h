@@ -169,6 +169,7 @@ float mo_stcorr_read (const mo_stcorr* c);                 /* stcorrdsp.cc:79-82
 typedef struct { float z1, z2, rms, peak; int cnt, fpp; float fall; int flag; int hold; float fsamp, omega; } mo_kmeter;
 void  mo_kmeter_init (mo_kmeter* k, float fsamp);          /* kmeterdsp.cc:47-54 */
 void  mo_kmeter_process (mo_kmeter* k, const float* p, int n);   /* kmeterdsp.cc:56-138 */
+void  mo_kmeter_process_f64 (mo_kmeter* k, const float* p, int n);   /* ... its filter in double: the yardstick of the dense K-meter kernels */
 void  mo_kmeter_read (mo_kmeter* k, float* rms, float* peak);    /* kmeterdsp.cc:148-153 */
 void  mo_kmeter_reset (mo_kmeter* k);                      /* kmeterdsp.cc:155-160 */
 

@@ -14,6 +14,10 @@ profiles/r22_kmeter_series.md — the table and the ratios; the sections that fo
     python tools/kmeter_rate.py --ebu [reps]
 times the bench step instead (EBU R128 + true peak on the same buffer, integration on): run it once per library (MTR_LIB names
 another build of libmtr_engine.so) to hold a build against its parent, in same-box pairs.
+
+    python tools/kmeter_rate.py --dense [reps]
+times the dense call alone, (a), by device events and prints median / min / max as one JSON line: run it in child processes that
+take turns, one with MTR_LIB on the parent's library (tools/build_ab.sh) and one without, to hold k_kmeter_pieces against its parent.
 """
 import ctypes as C
 import json
@@ -167,7 +171,32 @@ def bench_step(reps):
     print("EBU | TRUEPEAK step, %s: median %.3f ms  min %.3f  max %.3f" % (os.environ.get("MTR_LIB") or "this build", np.median(v), v.min(), v.max()), flush=True)
 
 
+def dense(reps):
+    buf = buffer()
+    st = torch.cuda.current_stream().cuda_stream
+    t = []
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with M.Engine(S, FS, M.METER_KMETER) as e:
+        for it in range(WARM + reps):
+            ev0.record()
+            e.process_device(buf.data_ptr(), T, T, st)
+            ev1.record()
+            e.sync()
+            torch.cuda.synchronize()
+            if it >= WARM:
+                t.append(ev0.elapsed_time(ev1))
+        rms, peak = e.kmeter_read()
+    assert np.isfinite(rms).all() and (rms > 0).all()
+    v = np.asarray(t)
+    print(json.dumps({"dense_kmeter_ms": {"lib": os.environ.get("MTR_LIB") or "this build", "median": float(np.median(v)), "min": float(v.min()),
+                                          "max": float(v.max()), "reps": reps}}), flush=True)
+
+
 if __name__ == "__main__":
+    if "--dense" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--dense"]
+        dense(int(rest[0]) if rest else 9)
+        sys.exit(0)
     args = [a for a in sys.argv[1:] if a != "--ebu"]
     out = os.path.join(ROOT, "profiles")
     if "--out" in args:
