@@ -37,7 +37,7 @@ extern "C" {
  *    _process_host_any, _scope_points; MTR_METER_GONIO, mtr_gonio_derive, mtr_engine_gonio_configure, _gonio_config, _gonio_set_gain,
  *    _gonio_image, _gonio_read, _gonio_blocks, _gonio_series, _gonio_image_clear, _gonio_reset; mtr_gonio_os_table, mtr_gonio_os_hpw,
  *    mtr_engine_gonio_set_oversample, _gonio_oversample, _gonio_os_timing; mtr_engine_set_plane_layout, _plane_layout, _plane_stats,
- *    mtr_plane_decode_host):
+ *    mtr_plane_decode_host; mtr_engine_integlog_set_every, _integlog_every, _integlog_series, _integlog_reset, mtr_integlog_cut):
  *    + mtr_engine_set_deferred_tail / _join / _deferred_stats, mtr_comm_nranks / _device (round 6); the entry points of
  *    round 5 (mtr_comm_init_timeout, mtr_comm_probe, mtr_comm_set_timeout, mtr_rccl_version, mtr_engine_state_*,
  *    mtr_state_blob_count, MTR_ERR_TIMEOUT / MTR_ERR_STATE) are what a version-1 library may lack.  A client checks
@@ -395,6 +395,10 @@ int  mtr_engine_kmeter_reset (mtr_engine* e);
 /* The loudness log of an MTR_METER_EBU engine — momentary / short-term loudness over time, a (M, S) point per period of P fragments
  * and stream: mtr_engine_loudlog_set_period / _period / _series / _reset */
 #include "mtr_loudlog.h"
+
+/* The integration log of an MTR_METER_EBU engine — integrated loudness and loudness range over time, a point of five values per K
+ * evaluations and stream: mtr_engine_integlog_set_every / _every / _series / _reset and mtr_integlog_cut */
+#include "mtr_integlog.h"
 
 /* The needle meters for a batch (MTR_METER_NEEDLE) — VU, IEC I / II PPM and M/S PPM, with a reading series: mtr_needle_coef and
  * mtr_engine_needle_configure / _set_gain / _read / _series / _reset */

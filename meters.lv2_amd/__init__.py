@@ -14,5 +14,5 @@ from .engine import (  # noqa: F401
     PCM_S16, PCM_S24, PCM_S32, pcm_decode, pick_decode, LOUDLOG_SAMPLE, LOUDLOG_MAX, SPECTR_PEAK_HOLD, SPECTR_PEAK_BLOCK,
     scope_series_cut, SCOPE_F_LEVEL, SCOPE_F_LR, SCOPE_F_PHASE, SCOPE_F_PLEVEL, SCOPE_F_PEAK, SCOPE_F_POWER_L, SCOPE_F_POWER_R, SCOPE_F_ALL,
     METER_GONIO, GonioConfig, GonioDerived, gonio_config, gonio_derive, gonio_cut, gonio_os_table, gonio_os_hpw,
-    plane_decode, tensor_source, TensorSource,
+    plane_decode, tensor_source, TensorSource, integlog_cut, INTEGLOG_FIELDS,
 )

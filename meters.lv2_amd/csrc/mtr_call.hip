@@ -402,7 +402,10 @@ struct CallRun {
 		// (the loudness log: where the streams stand in it is an argument, computed here — the gate may run a call late)
 		mtr_loudlog_args la;
 		const bool log = ebu && loudlog_args (e, e->pos, c.off, &la);
-		if (mtr_launch_gate (ga, d_lim, log ? &la : nullptr, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
+		// (the integration log: where a stream stands in it is device state, the gate's own)
+		mtr_integlog_args ia;
+		const bool evl = ebu && integlog_args (e, c.off, &ia);
+		if (mtr_launch_gate (ga, d_lim, log ? &la : nullptr, evl ? &ia : nullptr, gst)) { plan_abort (e, gst); return fail (MTR_ERR_HIP, "k_gate launch"); }
 		if (ls) { HIPCHK (hipEventRecord (ls->done[1].v, gst)); ls->pending[1] = true; }
 		{ const int rc = mark (3, gst); if (rc) return rc; }
 		{

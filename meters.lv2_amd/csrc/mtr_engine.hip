@@ -393,7 +393,8 @@ int mtr_engine_reset (mtr_engine* e)
 	e->last_deferred = false;
 	for (const SideMeter* m : SIDE_METERS)
 		if ((e->cfg.meters & m->bits) && m->reset && (rc = m->reset (e))) return rc;
-	if (e->ll.period) return loudlog_reset (e, st);
+	if (e->ll.period && (rc = loudlog_reset (e, st))) return rc;
+	if (e->il.every) return integlog_reset (e, st);
 	return MTR_OK;
 }
 

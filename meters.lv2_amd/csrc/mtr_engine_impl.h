@@ -337,6 +337,11 @@ struct mtr_engine {
 		int                        mode = 0;
 		std::vector<uint64_t>      points;      // [S] periods each stream has completed (streams end at their own lengths)
 	} ll;
+	struct IntegLog {                           // the integration log of an EBU engine (mtr_integlog.hip; the gate appends: the EVAL instantiations of mtr_gate.hip)
+		DevBuf<float>              v;           // [5][S][cap] integrated, integ_thr, range_min, range_max, range_thr
+		DevBuf<uint32_t>           count;       // [S] evaluations of each stream since the log was set / reset: the gate advances it
+		uint32_t                   every = 0, cap = 0;   // evaluations per point (0: off), points per stream the series holds
+	} il;
 	struct Tpb {                                // the reading series of TPBALLIST (mtr_tpb.hip; the meter's states are the stream state's)
 		SeriesCfg                  ser;         // frames per process () of the series (0: the call), points per stream it holds
 		DevBuf<mtr_tpb_open>       open;        // [S] the blob's header and the open block's maxima per channel
@@ -505,6 +510,8 @@ void kmeter_falls (const mtr_engine* e, const Call& c, uint64_t fill, uint64_t P
 // [off, off + cnt) (false: the log is off); its part of mtr_engine_reset
 bool loudlog_args (const mtr_engine* e, const Cursors& pos, uint32_t off, mtr_loudlog_args* out);
 int  loudlog_reset (mtr_engine* e, hipStream_t st);
+bool integlog_args (const mtr_engine* e, uint32_t off, mtr_integlog_args* out);
+int  integlog_reset (mtr_engine* e, hipStream_t st);
 
 #pragma GCC visibility pop
 

@@ -16,7 +16,10 @@
 //   * histogram inserts are integer atomics (order-independent, exact),
 //   * calc_integ / calc_range run once, at the last fragment whose `_div2` counter wraps inside
 //     this call — only that evaluation survives in the reference — one wave each, walking the
-//     occupied bins in the reference's order so that the float accumulation of integrate() is the reference's.
+//     occupied bins in the reference's order so that the float accumulation of integrate() is the reference's;
+//   * with the integration log on (EVAL, mtr_integlog.hip) they run at every recorded wrap as well, in order, and
+//     each such evaluation's five values go to the stream's series (ebu_r128_proc.cc:236-242: the reference
+//     evaluates at every wrap, and a host that polls the getters sees them move).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -29,7 +32,10 @@
 // mtr_loudlog.hip) puts the log's arguments behind them — without it an instantiation is the kernel it was before there was a log
 template <bool LEN> using gate_base_t = std::conditional_t<LEN, mtr_gate_len_args, mtr_gate_args>;
 template <bool LEN> struct gate_log_args : gate_base_t<LEN> { mtr_loudlog_args log; };
-template <bool LEN, bool LOG = false> using gate_args_t = std::conditional_t<LOG, gate_log_args<LEN>, gate_base_t<LEN>>;
+// ... and EVAL (the integration log is on, mtr_integlog.hip) that log's behind those: again a kernel without it takes what it took
+template <bool LEN, bool LOG> struct gate_eval_args : std::conditional_t<LOG, gate_log_args<LEN>, gate_base_t<LEN>> { mtr_integlog_args ev; };
+template <bool LEN, bool LOG = false, bool EVAL = false>
+using gate_args_t = std::conditional_t<EVAL, gate_eval_args<LEN, LOG>, std::conditional_t<LOG, gate_log_args<LEN>, gate_base_t<LEN>>>;
 template <bool LEN> __device__ __forceinline__ uint32_t gate_lim (const gate_base_t<LEN>& a, uint32_t s)
 {
 	if constexpr (LEN) return a.frag_lim[s];
@@ -156,14 +162,29 @@ __device__ __forceinline__ void hist_add (int32_t* h, int32_t* count, int32_t* e
 // LOG (the loudness log): the lane that holds the last fragment of a period appends the period's point — its own (lm, ls)
 // (MTR_LOUDLOG_SAMPLE) or the maxima over the period's fragments (MTR_LOUDLOG_MAX): those of this chunk from LDS, those before it —
 // earlier chunks, earlier calls — from the running maxima the workgroup carries from chunk to chunk and the stream from call to call.
-template <bool LEN, bool LOG>
-__global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN, LOG> a)
+//
+// EVAL (the integration log): the workgroup walks the wraps of _div2 inside the chunk in order.  At a wrap that is recorded (the
+// stream's evaluation count reaches a multiple of `every`) or the call's last, the lanes whose fragment lies behind the previous such
+// wrap and at or before this one insert — at the wrap's own fragment the M point, the S point, then calc_*, as :231-242 —, waves 0 and 1
+// evaluate into the stream's five values, and their lane 0 copies them to the series slot; the call's last wrap leaves them in the
+// stream state as without the log.  A wrap that is neither needs no evaluation: its inserts go in with the next one's.  The count is
+// device state, advanced here.
+// (amdgpu_waves_per_eu: six waves per SIMD is a budget of 80 VGPRs, so that two EVAL workgroups per CU still leave the batch kernel its
+// 344 of 512 — see launch_gate; the compiler meets it without scratch, 74 - 80 VGPRs.  A minimum of 1 is no constraint: the other
+// instantiations are the instruction streams they were.)
+template <bool LEN, bool LOG, bool EVAL>
+__global__ __launch_bounds__ (256) __attribute__ ((amdgpu_waves_per_eu (EVAL ? 6 : 1))) void k_gate (const gate_args_t<LEN, LOG, EVAL> a)
 {
 #pragma clang fp contract(off)
 	__shared__ float   pw[64 + CHUNK];          // chronological fragment powers: 64 history + chunk
 	__shared__ int32_t sh_hist[2][MTR_HIST_LEN];
 	__shared__ float   sh_red[2][256];
 	__shared__ int32_t sh_cnt[4];               // cnt_M cnt_S err_M err_S
+	float* cur = nullptr;                       // EVAL: integ integ_thr rmin rmax rthr as the last evaluation left them
+	if constexpr (EVAL) {
+		__shared__ float sh_cur[MTR_INTEGLOG_FIELDS];
+		cur = sh_cur;
+	}
 	float* ll = nullptr;                        // LOG, MAX: [2][CHUNK] lm / ls of the chunk, then the two running maxima
 	if constexpr (LOG) {
 		__shared__ float sh_ll[2 * CHUNK + 2];
@@ -197,6 +218,11 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN, LOG> a)
 	float last_M = st->loud_M, last_S = st->loud_S;
 	float run_M = -INFINITY, run_S = -INFINITY;    // LOG, MAX: maxima of the open period in front of the chunk (workgroup-uniform)
 	if constexpr (LOG) if (a.log.mode == MTR_LOUDLOG_MAX) { run_M = a.log.run[2 * s]; run_S = a.log.run[2 * s + 1]; }
+	uint32_t ev0 = 0;                              // EVAL: the stream's evaluations in front of the call (workgroup-uniform)
+	if constexpr (EVAL) {
+		ev0 = a.ev.count[s];
+		if (tid < MTR_INTEGLOG_FIELDS) cur[tid] = (&st->integ)[tid];
+	}
 	__syncthreads ();
 
 	// Index (within this call) of the last fragment at which _div2 wraps: calc_* run there.
@@ -259,21 +285,61 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN, LOG> a)
 		const int f_abs = (int) base + tid;
 		const bool addM = a.integr && tid < nf && ((div1_0 + f_abs + 1) % 2 == 0);
 		const bool addS = a.integr && tid < nf && ((div2_0 + f_abs + 1) % 10 == 0);
-		if (addM && f_abs <= f_calc) hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
-		if (addS && f_abs <= f_calc) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
-		__syncthreads ();
-
-		if (f_calc >= (int) base && f_calc < (int) base + nf) {
-			// wave 0 integrates, wave 1 finds the range
-			if (tid < 64) {
-				hist_calc_integ (sh_hist[0], sh_cnt[0], a.bin_power, &st->integ, &st->integ_thr, tid);
-			} else if (tid < 128) {
-				hist_calc_range (sh_hist[1], sh_cnt[1], a.bin_power, &st->rmin, &st->rmax, &st->rthr, tid - 64);
+		if constexpr (EVAL) {
+			// the chunk's wraps in order: fragment 9 - div2_0 of the call is the first, evaluation ev0 + 1 of the stream
+			const mtr_integlog_args& g = a.ev;
+			int done = (int) base - 1;                                // fragments up to here have been inserted
+			const int w0 = 9 - div2_0, lastw = min (f_calc, (int) base + nf - 1);
+			for (int fw = w0 + 10 * (((int) base - w0 + 9) / 10); fw <= lastw; fw += 10) {      // (fw >= base: base >= 0 and w0 <= 9)
+				const uint32_t n = ev0 + (uint32_t) (fw - w0) / 10u + 1u;
+				const bool rec = n % g.every == 0;
+				if (!rec && fw != f_calc) continue;
+				if (addM && f_abs > done && f_abs <= fw) hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
+				if (addS && f_abs > done && f_abs <= fw) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
+				done = fw;
+				__syncthreads ();
+				const uint32_t j = n / g.every - 1;
+				if (tid < 64) {
+					hist_calc_integ (sh_hist[0], sh_cnt[0], a.bin_power, &cur[0], &cur[1], tid);
+					if (tid == 0) {
+						if (rec && j < g.cap) {
+							float* const p = g.v + (size_t) s * g.cap + j;
+							p[0] = cur[0]; p[g.field_pitch] = cur[1];
+						}
+						if (fw == f_calc) { st->integ = cur[0]; st->integ_thr = cur[1]; }
+					}
+				} else if (tid < 128) {
+					hist_calc_range (sh_hist[1], sh_cnt[1], a.bin_power, &cur[2], &cur[3], &cur[4], tid - 64);
+					if (tid == 64) {
+						if (rec && j < g.cap) {
+							float* const p = g.v + (size_t) s * g.cap + j;
+							p[2 * g.field_pitch] = cur[2]; p[3 * g.field_pitch] = cur[3]; p[4 * g.field_pitch] = cur[4];
+						}
+						if (fw == f_calc) { st->rmin = cur[2]; st->rmax = cur[3]; st->rthr = cur[4]; }
+					}
+				}
+				__syncthreads ();
 			}
+			// the rest of the chunk: behind the call's last wrap, or in front of a wrap of a later chunk
+			if (addM && f_abs > done) hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
+			if (addS && f_abs > done) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
+		} else {
+			if (addM && f_abs <= f_calc) hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
+			if (addS && f_abs <= f_calc) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
+			__syncthreads ();
+
+			if (f_calc >= (int) base && f_calc < (int) base + nf) {
+				// wave 0 integrates, wave 1 finds the range
+				if (tid < 64) {
+					hist_calc_integ (sh_hist[0], sh_cnt[0], a.bin_power, &st->integ, &st->integ_thr, tid);
+				} else if (tid < 128) {
+					hist_calc_range (sh_hist[1], sh_cnt[1], a.bin_power, &st->rmin, &st->rmax, &st->rthr, tid - 64);
+				}
+			}
+			__syncthreads ();
+			if (addM && f_abs > f_calc) hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
+			if (addS && f_abs > f_calc) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
 		}
-		__syncthreads ();
-		if (addM && f_abs > f_calc) hist_add (sh_hist[0], &sh_cnt[0], &sh_cnt[2], lm);
-		if (addS && f_abs > f_calc) hist_add (sh_hist[1], &sh_cnt[1], &sh_cnt[3], ls);
 
 		if (tid < nf) {                              // max-hold is order-free: per-lane, folded once at the end
 			max_M = lm > max_M ? lm : max_M;
@@ -316,6 +382,7 @@ __global__ __launch_bounds__ (256) void k_gate (const gate_args_t<LEN, LOG> a)
 		// then k_history, mtr_history.hip, has folded it on the caller's stream — mtr_fold_truepeak, mtr_internal.h; layout 8: always)
 		if (a.fold_tp) mtr_fold_truepeak (st);
 		if constexpr (LOG) if (a.log.mode == MTR_LOUDLOG_MAX) { a.log.run[2 * s] = run_M; a.log.run[2 * s + 1] = run_S; }
+		if constexpr (EVAL) if (f_calc >= 0) a.ev.count[s] = ev0 + (uint32_t) (f_calc - (9 - div2_0)) / 10u + 1u;
 	}
 	for (int i = tid; i < 64; i += 256) st->ring[i] = pw[i];
 	for (int i = tid; i < 2 * MTR_HIST_LEN; i += 256) ghist[i] = (&sh_hist[0][0])[i];
@@ -586,15 +653,18 @@ int mtr_launch_delay (uint32_t us, void* stream)
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-template <bool LEN, bool LOG>
-static int launch_gate (const mtr_gate_args& ga, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream)
+template <bool LEN, bool LOG, bool EVAL>
+static int launch_gate (const mtr_gate_args& ga, const uint32_t* frag_lim, const mtr_loudlog_args* log, const mtr_integlog_args* ev, void* stream)
 {
-	gate_args_t<LEN, LOG> a;
+	gate_args_t<LEN, LOG, EVAL> a;
 	static_cast<mtr_gate_args&> (a) = ga;
 	if constexpr (LEN) a.frag_lim = frag_lim;
 	if constexpr (LOG) a.log = *log;
-	// many fragments per call and few streams: spread a stream over several workgroups
-	if (a.n_frag >= 4 * GATE_FPB && a.max_scratch) {
+	if constexpr (EVAL) a.ev = *ev;
+	// many fragments per call and few streams: spread a stream over several workgroups.  (Not with the integration log: those
+	// kernels merge their histograms out of order, so the state at a wrap inside the call exists nowhere — k_gate, one workgroup per
+	// stream walking its chunks, is the general kernel and takes a call of any length.)
+	if constexpr (!EVAL) if (a.n_frag >= 4 * GATE_FPB && a.max_scratch) {
 		const uint32_t nb = (a.n_frag + GATE_FPB - 1) / GATE_FPB;
 		hipLaunchKernelGGL ((k_gate_frag<LEN, LOG>), dim3 (nb, a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
 		hipLaunchKernelGGL ((k_gate_final<LEN, LOG>), dim3 (a.n_streams), dim3 (256), 0, (hipStream_t) stream, a);
@@ -603,16 +673,23 @@ static int launch_gate (const mtr_gate_args& ga, const uint32_t* frag_lim, const
 	// A deferred gate (a.polite_grid) runs beside the next call's fused kernel, whose one-wave workgroups own a SIMD each for
 	// the whole call: two gate workgroups per CU — two 72-VGPR waves per SIMD, 19 KB of LDS — always leave room for one of
 	// those (344 VGPRs of 512, 35 KB of 160), so the gate is launched as that many workgroups, each walking its share of the
-	// streams, and cannot stand in the way of k_seg's placement whenever the two are dispatched together.
+	// streams, and cannot stand in the way of k_seg's placement whenever the two are dispatched together.  (The EVAL
+	// instantiations stay inside that: DESIGN.md 3.13.1 has their registers and LDS.)
 	const uint32_t grid = a.polite_grid ? (a.n_streams < a.polite_grid ? a.n_streams : a.polite_grid) : a.n_streams;
-	hipLaunchKernelGGL ((k_gate<LEN, LOG>), dim3 (grid), dim3 (256), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL ((k_gate<LEN, LOG, EVAL>), dim3 (grid), dim3 (256), 0, (hipStream_t) stream, a);
 	return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-int mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream)
+template <bool LEN, bool LOG>
+static int launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, const mtr_integlog_args* ev, void* stream)
 {
-	if (log) return frag_lim ? launch_gate<true, true> (a, frag_lim, log, stream) : launch_gate<false, true> (a, nullptr, log, stream);
-	return frag_lim ? launch_gate<true, false> (a, frag_lim, nullptr, stream) : launch_gate<false, false> (a, nullptr, nullptr, stream);
+	return ev ? launch_gate<LEN, LOG, true> (a, frag_lim, log, ev, stream) : launch_gate<LEN, LOG, false> (a, frag_lim, log, nullptr, stream);
+}
+
+int mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, const mtr_integlog_args* ev, void* stream)
+{
+	if (log) return frag_lim ? launch_gate<true, true> (a, frag_lim, log, ev, stream) : launch_gate<false, true> (a, nullptr, log, ev, stream);
+	return frag_lim ? launch_gate<true, false> (a, frag_lim, nullptr, ev, stream) : launch_gate<false, false> (a, nullptr, nullptr, ev, stream);
 }
 
 // ---- state initialisation --------------------------------------------------------------------

@@ -163,6 +163,19 @@ typedef struct mtr_loudlog_args {
 } mtr_loudlog_args;
 #define MTR_LOUDLOG_EMPTY 0x807fffff   /* -inf as a sortable int (mtr_gate.hip): what the series and run_new are cleared to */
 
+/* The integration log (mtr_engine_integlog_set_every; host side: mtr_integlog.hip) as a gate sees it — behind the gate's arguments (and
+ * the loudness log's) in the EVAL instantiations only.  Where a stream stands in it is device state: count [s] = evaluations (fragments
+ * at which _div2 wrapped while the integration ran) since the log was set or reset, read and advanced by the stream's workgroup, so a
+ * deferred gate, a call with lengths or a chunk of a host call needs no host-side cursor.  Evaluation n (1-based) with n % every == 0
+ * is point n / every - 1 and lands in v [k][s][n / every - 1] if that is < cap. */
+#define MTR_INTEGLOG_FIELDS 5          /* integrated, integ_thr, range_min, range_max, range_thr */
+typedef struct mtr_integlog_args {
+	float*          v;            /* [5][S_engine][cap] the series, field-major; the view's first stream's row of field 0 */
+	uint64_t        field_pitch;  /* floats between two fields: S_engine * cap */
+	uint32_t*       count;        /* [S] evaluations of the view's streams */
+	uint32_t        every, cap;
+} mtr_integlog_args;
+
 /* per-stream state of BITSTATS: shared by mtr_bitstats.hip (the kernel) and mtr_intstat.hip (the meter's host side) */
 typedef struct mtr_bitstats_state {
 	int32_t hist[MTR_BIM_LAST];      /* src/uris.h:53-60 layout */
@@ -250,8 +263,10 @@ struct mtr_history_args {
 };
 /* -1: an ends rule without ends, C outside 1 .. 5, FC neither C nor 6 with C == 5; HIST_ROW_GONIO with HC != 2 or HIST_CALL_END_IF_TOUCHED */
 int  mtr_launch_history (HistCut cut, HistRow row, const mtr_history_args& a, void* stream);
-/* log != NULL: the instantiations that append the call's points to the loudness log; NULL: the kernels as they are without it */
-int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, void* stream);
+/* log != NULL: the instantiations that append the call's points to the loudness log; NULL: the kernels as they are without it.
+ * ev != NULL: the EVAL instantiations of k_gate, which evaluate at every recorded wrap of _div2 and append to the integration log —
+ * a call of any length then goes through k_gate, one workgroup per stream */
+int  mtr_launch_gate (const mtr_gate_args& a, const uint32_t* frag_lim, const mtr_loudlog_args* log, const mtr_integlog_args* ev, void* stream);
 int  mtr_launch_delay (uint32_t us, void* stream);
 int  mtr_launch_state_init (mtr_stream_state* st, int32_t* hist, uint32_t n_streams, int what, void* stream);
 int  mtr_launch_tpb (const mtr_tpb_args& a, void* stream);

@@ -29,6 +29,7 @@ SCOPE_F_LEVEL, SCOPE_F_LR, SCOPE_F_PHASE, SCOPE_F_PLEVEL, SCOPE_F_PEAK, SCOPE_F_
 SCOPE_FIELDS = ("level", "lr", "phase", "plevel", "peak", "power_l", "power_r")
 SPECTR_PEAK_HOLD, SPECTR_PEAK_BLOCK = 0, 1   # MTR_SPECTR_PEAK_*: max as held since reset / reset_peak, or zeroed behind every point
 LOUDLOG_SAMPLE, LOUDLOG_MAX = 0, 1         # MTR_LOUDLOG_*: a point is the period's last (M, S) / the maxima over the period
+INTEGLOG_FIELDS = ("I", "I_thr", "Rmin", "Rmax", "R_thr")   # a point of the integration log (mtr_integlog.h), in the getters' order
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MTR_LIB: an alternative build of the same library (instrumented kernels, tools/f4_prof.py); never a different backend
@@ -267,6 +268,12 @@ def _load():
         L.mtr_engine_loudlog_period.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
         L.mtr_engine_loudlog_series.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp]
         L.mtr_engine_loudlog_reset.argtypes = [vp]
+    if hasattr(L, "mtr_engine_integlog_series"):               # (an addition inside ABI version 2: the integration log)
+        L.mtr_engine_integlog_set_every.argtypes = [vp, u32, u32]
+        L.mtr_engine_integlog_every.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.mtr_engine_integlog_series.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.mtr_engine_integlog_reset.argtypes = [vp]
+        L.mtr_integlog_cut.argtypes = [u32, u64, u32, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_prune_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_refine_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mtr_engine_layout.argtypes = [vp]
@@ -368,6 +375,17 @@ def scope_series_cut(fill, hop, since, every, n_frames):
     an, pt = C.c_uint64(), C.c_uint64()
     _check(lib.mtr_scope_series_cut(int(fill), int(hop), int(since), int(every), int(n_frames), C.byref(an), C.byref(pt)), "mtr_scope_series_cut")
     return an.value, pt.value
+
+
+def integlog_cut(div2, evaluations, every, n_fragments):
+    """(evaluations, points) a stream gains from `n_fragments` integrating fragments when its _div2 stands at `div2` (0 .. 9) and it has
+    made `evaluations` evaluations so far, a point per `every` evaluations (every 0: the log is off, 0 points) (mtr_integlog_cut; no
+    device)."""
+    if not hasattr(lib, "mtr_integlog_cut"):
+        raise EngineError(f"{lib_path} has no integration log: rebuild it")
+    ev, pt = C.c_uint64(), C.c_uint64()
+    _check(lib.mtr_integlog_cut(int(div2), int(evaluations), int(every), int(n_fragments), C.byref(ev), C.byref(pt)), "mtr_integlog_cut")
+    return ev.value, pt.value
 
 
 def series_cut(fill, period, n_frames, frames):
@@ -1449,6 +1467,41 @@ class Engine:
     def loudlog_reset(self):
         self._need_loudlog()
         _check(lib.mtr_engine_loudlog_reset(self._h), "loudlog_reset")
+
+    def _need_integlog(self):
+        if not hasattr(lib, "mtr_engine_integlog_series"):
+            raise EngineError(f"{lib_path} has no integration log: rebuild it")
+
+    def integlog_set_every(self, every_evaluations, capacity_points):
+        """The integration log of an EBU engine: the five values (integrated, integ_thr, range_min, range_max, range_thr) per stream after
+        every `every_evaluations`-th evaluation — an evaluation falls every ten integrating fragments, 0.5 s —, `capacity_points` of them
+        kept per stream; 0 turns it off.  Only before the first process call since create / reset."""
+        self._need_integlog()
+        _check(lib.mtr_engine_integlog_set_every(self._h, int(every_evaluations), int(capacity_points)), "integlog_set_every")
+
+    def integlog_every(self):
+        """(every_evaluations, capacity_points) as set; every 0: the log is off."""
+        self._need_integlog()
+        k, c = C.c_uint32(), C.c_uint32()
+        _check(lib.mtr_engine_integlog_every(self._h, C.byref(k), C.byref(c)), "integlog_every")
+        return k.value, c.value
+
+    def integlog_series(self, first=0, count=None):
+        """dict(I, I_thr, Rmin, Rmax, R_thr: [count, cap] float32, rows filled with NaN past the stream's own min(n_points, cap);
+        n_points, dropped: [count] uint32)."""
+        self._need_integlog()
+        count = self.n_streams - first if count is None else count
+        cap = self.integlog_every()[1]
+        out = {k: np.full((count, cap), np.nan, np.float32) for k in INTEGLOG_FIELDS}
+        n, d = np.zeros(count, np.uint32), np.zeros(count, np.uint32)
+        _check(lib.mtr_engine_integlog_series(self._h, first, count, *[out[k].ctypes.data for k in INTEGLOG_FIELDS], cap, n.ctypes.data, d.ctypes.data),
+               "integlog_series")
+        out["n_points"], out["dropped"] = n, d
+        return out
+
+    def integlog_reset(self):
+        self._need_integlog()
+        _check(lib.mtr_engine_integlog_reset(self._h), "integlog_reset")
 
     def dr14_reset(self):
         _check(lib.mtr_engine_dr14_reset(self._h), "dr14_reset")
